@@ -6,7 +6,7 @@ One "step" = one pass of the hot path (la3d_fit_instances: unproject + fit, fuse
 a u8 mask plane holding one axis-aligned rectangle (h~U{8..300}, w~U{8..330}) — resident in HBM before
 the timed region.  Full-mask mode, ground=None, K=[[500,0,320],[0,500,240],[0,0,1]].
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -228,6 +228,27 @@ def rect_rle(rects):
         counts += c
         offs.append(len(counts))
     return np.asarray(counts, np.int32), np.asarray(offs, np.int64)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, seed=0):
+    """--dump-outputs DIR: what the timed path handed its caller in its last step, one DIR/<name>.npy per array, all float64
+    (integer outputs - status, object ids - convert exactly).  The arrays share their leading axis (one row per instance); above
+    DUMP_LIMIT_BYTES in all, a fixed sample of rows (RandomState(seed), sorted) is written instead and DIR/rows.npy names them."""
+    arrays = {k: np.asarray(v.cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64) for k, v in arrays.items()}
+    n = {a.shape[0] for a in arrays.values()}
+    assert len(n) == 1, {k: a.shape for k, a in arrays.items()}
+    n = n.pop()
+    row_bytes = sum(a[:1].nbytes for a in arrays.values())
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.RandomState(seed).choice(n, DUMP_LIMIT_BYTES // (row_bytes + 8), replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def cpu_baseline_all_cores(d, m, per_worker=12, timeout_s=90.0):
@@ -614,6 +635,7 @@ def run_config4(args, dist, rank, world, device, red_dev):
         if it >= args.warmup_jobs and (best is None or tm["job_s"] < best["job_s"]):
             best = tm
             best_out = out
+        last_out = out
     vals = torch.tensor([best["fit_s"], best["gather_s"], best["job_s"]], dtype=torch.float64, device=red_dev)
     allv = [torch.zeros_like(vals) for _ in range(world)]
     if dist_ is None:
@@ -626,6 +648,8 @@ def run_config4(args, dist, rank, world, device, red_dev):
         mask_input = "u8 planes" if not ann_mode else ("COCO run lengths" if args.rle else "polygon parts (24-vertex outlines)")
         if args.dump:   # tests: the gathered records in global instance order
             np.save(args.dump, boxes.cpu().numpy())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"boxes": last_out[0], "status": last_out[1]})
         fit = [float(v[0]) for v in allv]
         gat = [float(v[1]) for v in allv]
         job = max(float(v[2]) for v in allv)
@@ -680,15 +704,28 @@ def run_end_to_end(args, device):
     for _ in range(3):
         tm = {}
         pipe = ScenePipeline(device=device, batch_images=args.batch_images, write=False, timings=tm)
+        last = [] if args.dump_outputs else None    # --dump-outputs: the records of this pass, per scene
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        nb = sum(len(recs) for _, recs in pipe.run(scenes))
+        nb = 0
+        for _, recs in pipe.run(scenes):
+            nb += len(recs)
+            if last is not None:
+                last.append(recs)
         torch.cuda.synchronize()
         tm["total_s"] = time.perf_counter() - t0
         tm["boxes"] = nb
         if best is None or tm["total_s"] < best["total_s"]:
             best = tm
     t = best
+    if last is not None:    # the records as the caller reads them back (category names are looked up, not computed: left out)
+        rows = [(s, r) for s, recs in enumerate(last) for r in recs]
+        dump_outputs(args.dump_outputs, {
+            "scene": [s for s, _ in rows], "obj_id": [int(r["obj_id"]) for _, r in rows],
+            "center_cam": np.reshape([r["center_cam"] for _, r in rows], (-1, 3)),
+            "dimensions": np.reshape([r["dimensions"] for _, r in rows], (-1, 3)),
+            "R_cam": np.reshape([r["R_cam"] for _, r in rows], (-1, 3, 3)),
+            "bbox3D_cam": np.reshape([r["bbox3D_cam"] for _, r in rows], (-1, 8, 3))})
     bytes_per_image = t["h2d_bytes"] / t["images"]
     ceiling_images = link * 1e9 / bytes_per_image
     print(json.dumps({
@@ -803,6 +840,11 @@ def main():
                          "B = 1024; 1 = every step reads the same batch, the protocol of rounds 1-5; falls back to 1 when memory is short)")
     ap.add_argument("--streams", type=int, default=1,
                     help="HIP streams the independent steps are issued on round-robin (1 = strictly serial steps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the run, write what the timed path computed in its last step as DIR/<name>.npy (float64): boxes, status "
+                         "and aux of the last timed step (N > 1 ranks: the gathered boxes and status of every rank's last step); --config4: "
+                         "the last job's gathered boxes and status; --end-to-end: the records of the last timed pass.  At most 64 MB (a "
+                         "fixed sample of rows above that, listed in DIR/rows.npy)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -919,6 +961,16 @@ def main():
         gather_s = time.perf_counter() - tg
     barrier()
     t1 = time.perf_counter()
+    # --dump-outputs: the last timed step's output slot, copied before the secondary loops below write into the slots again
+    last_out = None
+    if args.dump_outputs and dist is None:
+        s_last = fitter.boxes.shape[0] - 1      # step k writes slot k (config 3: every step writes slot 0)
+        last_out = {"boxes": fitter.boxes[s_last].clone(), "status": fitter.status[s_last].clone(), "aux": fitter.aux[s_last].clone()}
+    elif args.dump_outputs and rank == 0:
+        # the gathered rows are rank-major, each rank's in slot order: keep every rank's last slot
+        n_rank, slots = fitter.boxes.shape[0] * B, fitter.boxes.shape[0]
+        keep = torch.cat([torch.arange(r * n_rank + (slots - 1) * B, (r + 1) * n_rank) for r in range(world)])
+        last_out = {"boxes": gathered[0][keep.to(gathered[0].device)], "status": gathered[1][keep.to(gathered[1].device)]}
 
     # secondary figure, AFTER the timed region (round 5; round 4 ran it before the warm-up, which conditioned the chip's clocks for
     # the timed steps - 2-4 us per step of the round-4 headline): the SAME serial step in back-to-back loops of 100 (>= 40 ms of
@@ -984,6 +1036,8 @@ def main():
 
     ok = int((fitter.status == 0).sum())
     if rank == 0:
+        if last_out is not None:
+            dump_outputs(args.dump_outputs, last_out)
         assert ok == fitter.status.numel(), f"{fitter.status.numel() - ok} boxes failed"
         if gathered is not None:
             assert gathered[0].shape[1] == 39, gathered[0].shape

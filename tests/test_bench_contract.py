@@ -102,6 +102,69 @@ def test_required_bytes_model():
     assert len(bench.kernel_source_sha256()) == 64
 
 
+def test_dump_outputs_float64_and_a_fixed_sample_above_the_limit(tmp_path, monkeypatch):
+    """bench.dump_outputs: every array as float64 (integer status exact); above the byte limit the same seeded, sorted rows of
+    every array, named in rows.npy, within the limit."""
+    import torch
+
+    import bench
+
+    boxes = torch.arange(40 * 39, dtype=torch.float64).reshape(40, 39) / 7
+    status = torch.zeros(40, dtype=torch.int32)
+    status[3] = 5
+    bench.dump_outputs(str(tmp_path / "all"), {"boxes": boxes, "status": status})
+    assert sorted(os.listdir(tmp_path / "all")) == ["boxes.npy", "status.npy"]
+    b, s = np.load(tmp_path / "all" / "boxes.npy"), np.load(tmp_path / "all" / "status.npy")
+    assert b.dtype == s.dtype == np.float64 and np.array_equal(b, boxes.numpy()) and s.shape == (40,) and s[3] == 5
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 10 * (39 * 8 + 8 + 8))   # room for 10 rows and their row numbers
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"boxes": boxes, "status": status})
+    names = sorted(os.listdir(tmp_path / "s1"))
+    assert names == ["boxes.npy", "rows.npy", "status.npy"]
+    rows = np.load(tmp_path / "s1" / "rows.npy")
+    assert rows.shape == (10,) and (np.diff(rows) > 0).all()
+    np.testing.assert_array_equal(np.load(tmp_path / "s1" / "boxes.npy"), boxes.numpy()[rows.astype(np.int64)])
+    assert sum(np.load(tmp_path / "s1" / n).nbytes for n in names) <= bench.DUMP_LIMIT_BYTES
+    for n in names:
+        np.testing.assert_array_equal(np.load(tmp_path / "s1" / n), np.load(tmp_path / "s2" / n))
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: two runs with the same arguments write identical arrays, and they are the fit of the batch the last
+    timed step read (step 4 of 5 reads resident batch 4 % 3 = 1), against the CPU oracle."""
+    import torch
+
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import bench
+    from oracle import la3d_oracle as O
+    from tests.test_gpu_parity import assert_records
+
+    B = 64
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--batch", str(B), "--no-cpu-baseline",
+           "--no-steady", "--no-pipelined", "--no-same-batch"]
+    for d in ("a", "b"):
+        out = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+        assert line["steps"] == 5 and line["ms_per_step"] > 0 and line["rotation"]["batches"] == 3
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["aux.npy", "boxes.npy", "status.npy"]
+    for n in names:
+        a = np.load(tmp_path / "a" / n)
+        assert a.dtype == np.float64 and a.shape[0] == B and np.array_equal(a, np.load(tmp_path / "b" / n)), n
+    boxes, status, aux = (np.load(tmp_path / "a" / n) for n in ("boxes.npy", "status.npy", "aux.npy"))
+
+    depth, masks, K, _, _ = bench.make_inputs(B, torch.device("cuda", 0), 1234 + 7919)
+    depth, masks, K = depth.cpu().numpy(), masks.cpu().numpy().astype(bool), K.cpu().numpy()
+    ref = [O.fit_instance(depth[i], masks[i], K) for i in range(B)]
+    assert (status == 0).all() and (status == [r[1] for r in ref]).all()
+    assert_records(boxes, np.array([r[0] for r in ref]), "dump", gap=aux[:, 3])
+    np.testing.assert_array_equal(aux[:, 2], masks.reshape(B, -1).sum(1))
+
+
 def test_bench_refuses_to_measure_fewer_gpus_than_asked():
     """`python bench.py --gpus N` on a node with fewer than N GPUs (this container: none; the one-GPU box: one) must fail
     loudly instead of recording a one-GPU number under n_gpus = N - both as its own launcher and under a torchrun line whose
