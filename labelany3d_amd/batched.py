@@ -205,29 +205,53 @@ class InstanceFitter:
             area_hint=None):
         """All arguments already on the device with the ABI's dtypes (f32 / u8 / f64 / f64 / i32 / i32).
         ``engine`` / ``launch_order`` / ``build``: scheduling of THIS call (labelany3d_amd.options; speed only)."""
-        B, H, W = self.B, self.H, self.W
-        planes = depth.shape[0] if depth.dim() == 3 else 1
-        dstride = H * W if planes > 1 else 0
-        kstride = 9 if (K.dim() == 3 and K.shape[0] > 1) else 0
-        oe, oo, ob = options.codes(engine, launch_order, build)
-        if oe or oo or ob or area_hint is not None:   # per-call options travel in the argument block
-            a = FitArgs()
-            a.struct_size = C.sizeof(FitArgs)
-            a.B, a.H, a.W = B, H, W
-            a.depth, a.depth_plane_stride, a.image_index = _ptr(depth), dstride, _ptr(image_index)
-            a.mask, a.K, a.k_stride = _ptr(masks), _ptr(K), kstride
-            a.ground, a.sample_idx, a.area_hint = _ptr(ground), _ptr(sample_idx), _ptr(area_hint)
-            a.out, a.status, a.aux = _ptr(self.boxes[slot]), _ptr(self.status[slot]), _ptr(self.aux[slot])
-            a.workspace, a.stream = _ptr(self.workspace[ws_slot]), _stream(stream, raw=True)
-            a.opt_engine, a.opt_launch_order, a.opt_build = oe, oo, ob
-            check(lib.la3d_fit_instances_ex(C.byref(a)), "la3d_fit_instances_ex")
-            return self.boxes[slot], self.status[slot], self.aux[slot]
-        rc = lib.la3d_fit_instances(_ptr(depth), dstride, _ptr(image_index), _ptr(masks), _ptr(K), kstride,
-                                    _ptr(ground), _ptr(sample_idx), B, H, W, _ptr(self.boxes[slot]),
-                                    _ptr(self.status[slot]), _ptr(self.aux[slot]), _ptr(self.workspace[ws_slot]),
-                                    _stream(stream, raw=True))
-        check(rc, "la3d_fit_instances")
+        a = _fit_args(self.B, self.H, self.W, _ptr(depth), depth.shape[0] if depth.dim() == 3 else 1, _ptr(K),
+                      K.shape[0] if K.dim() == 3 else 1, _ptr(self.boxes[slot]), _ptr(self.status[slot]), _ptr(self.aux[slot]),
+                      _ptr(self.workspace[ws_slot]), _stream(stream, raw=True), mask=_ptr(masks), image_index=_ptr(image_index),
+                      ground=_ptr(ground), sample_idx=_ptr(sample_idx), area_hint=_ptr(area_hint),
+                      opts=options.codes(engine, launch_order, build))
+        check(lib.la3d_fit_instances_ex(C.byref(a)), "la3d_fit_instances_ex")
         return self.boxes[slot], self.status[slot], self.aux[slot]
+
+
+def _filter_args(filter):
+    """``filter`` of fit_instances_rle / fit_instances_poly: True or a dict with the reference's three thresholds
+    (src/util.py:291-326, :375): boundary strip width (10), minimum area (100), boundary pixels that make a mask "truncated" (10)."""
+    f = {} if filter is True else dict(filter)
+    unknown = set(f) - {"boundary_threshold", "scale_threshold", "truncation_pixels"}
+    if unknown:
+        raise ValueError(f"unknown filter keys: {sorted(unknown)}")
+    b, a, e = int(f.get("boundary_threshold", 10)), int(f.get("scale_threshold", 100)), int(f.get("truncation_pixels", 10))
+    if b < 0 or e <= 0:
+        # the C-ABI reads filter_boundary < 0 or filter_max_edge <= 0 as "no filter" (a zero-initialised la3d_fit_args means none);
+        # truncation_pixels <= 0 would mean "reject every instance" in the reference's rule (edge < 0 never holds): refuse it here
+        # instead of silently fitting everything
+        raise ValueError("filter: boundary_threshold must be >= 0 and truncation_pixels >= 1")
+    return b, a, e
+
+
+def _fit_args(B, H, W, depth, planes, K, nk, out, status, aux, workspace, stream, mask=None, rle=None, poly=None, image_index=None,
+              ground=None, sample_idx=None, filter=None, stats=None, proj=None, image_size=None, area_hint=None, opts=(0, 0, 0),
+              frame_width=0) -> FitArgs:
+    """The argument block of every fit call (C-ABI ``la3d_fit_instances_ex``) from pointers (None = NULL; device pointers, or host
+    pointers for ``la3d_fit_annotations_host``) and sizes: ``planes`` depth planes of H*W floats, ``nk`` intrinsics matrices (one
+    of either is shared by every instance).  rle = (counts, offsets), poly = (xy, ring_offsets, inst_rings); ``filter`` as in
+    ``fit_instances_rle`` (None: no filter); ``proj`` with ``image_size`` = (width, height); ``opts`` = options.codes().
+    Built fresh for every call: one InstanceFitter may be driven from several threads and streams."""
+    a = FitArgs(struct_size=C.sizeof(FitArgs), B=B, H=H, W=W, depth=depth, depth_plane_stride=H * W if planes > 1 else 0,
+                image_index=image_index, mask=mask, K=K, k_stride=9 if nk > 1 else 0, ground=ground, sample_idx=sample_idx,
+                out=out, status=status, aux=aux, workspace=workspace, stream=stream, area_hint=area_hint, frame_width=frame_width)
+    if rle is not None:
+        a.rle_counts, a.rle_offsets = rle
+    if poly is not None:
+        a.poly_xy, a.ring_offsets, a.inst_rings = poly
+    if filter:
+        a.filter_boundary, a.filter_min_area, a.filter_max_edge = _filter_args(filter)
+        a.stats = stats
+    if image_size is not None:
+        a.proj, a.image_width, a.image_height = proj, float(image_size[0]), float(image_size[1])
+    a.opt_engine, a.opt_launch_order, a.opt_build = opts
+    return a
 
 
 def _check_image_index(given, ii, B, P):
@@ -246,6 +270,48 @@ def _check_image_index(given, ii, B, P):
     lo, hi = torch.aminmax(ii)
     if int(lo) < 0 or int(hi) >= P:
         raise ValueError("image_index out of range")
+
+
+def _fit_inputs(depth, K, image_index, ground, sample_idx, B, H, W, dev, frame, check_device_index=False, given_index=None):
+    """The inputs every fit entry shares, checked against the call's B masks of H x W and on the device: depth (P,H,W) | (H,W)
+    float32, K (P,3,3) | (3,3) float64 (a shared matrix is expanded to P), image_index (B,) int32, ground (B,4) float64,
+    sample_idx (B,500) int32; None stays None.  ``frame`` names the masks in the error text.  The range of a host image_index is
+    checked on the host (``given_index``: the array as the caller gave it, when it has been uploaded already); a device tensor's
+    only with ``check_device_index`` (a ~40 us read-back).  Returns (depth, K, image_index, ground, sample_idx, P)."""
+    d = _as_dev(depth, torch.float32, dev)
+    if d.dim() == 2:
+        d = d[None]
+    if d.shape[1:] != (H, W):
+        raise ValueError(f"depth planes {tuple(d.shape[1:])} do not match {frame} {(H, W)}")
+    k = _as_dev(K, torch.float64, dev, cache=True)
+    if k.dim() == 2:
+        k = k[None]
+    P = d.shape[0]
+    if k.shape[0] not in (1, P) or k.shape[1:] != (3, 3):
+        raise ValueError("K must be (3,3) or (P,3,3)")
+    if k.shape[0] == 1 and P > 1:
+        k = k.expand(P, 3, 3).contiguous()
+    ii = None
+    if image_index is not None:
+        ii = _as_dev(image_index, torch.int32, dev)
+        if ii.shape != (B,):
+            raise ValueError("image_index must be (B,)")
+        given = image_index if given_index is None else given_index
+        if check_device_index or not (isinstance(given, torch.Tensor) and given.is_cuda):
+            _check_image_index(given, ii, B, P)
+    elif P not in (1, B):
+        raise ValueError("without image_index, depth must have 1 or B planes")
+    g = None
+    if ground is not None:
+        g = _as_dev(ground, torch.float64, dev)
+        if g.shape != (B, 4):
+            raise ValueError("ground must be (B,4)")
+    si = None
+    if sample_idx is not None:
+        si = _as_dev(sample_idx, torch.int32, dev)
+        if si.shape != (B, NSAMPLE):
+            raise ValueError("sample_idx must be (B,500)")
+    return d, k, ii, g, si, P
 
 
 def pad_rows_f32(d: torch.Tensor, Wp: int) -> torch.Tensor:
@@ -276,35 +342,7 @@ def fit_instances(depth, masks, K, ground=None, sample_idx=None, image_index=Non
     if m.dim() != 3:
         raise ValueError("masks must be (B,H,W)")
     B, H, W = m.shape
-    d = _as_dev(depth, torch.float32, dev)
-    if d.dim() == 2:
-        d = d[None]
-    if d.shape[1:] != (H, W):
-        raise ValueError(f"depth planes {tuple(d.shape[1:])} do not match masks {(H, W)}")
-    k = _as_dev(K, torch.float64, dev, cache=True)
-    if k.dim() == 2:
-        k = k[None]
-    P = d.shape[0]
-    if k.shape[0] not in (1, P) or k.shape[1:] != (3, 3):
-        raise ValueError("K must be (3,3) or (P,3,3)")
-    ii = None
-    if image_index is not None:
-        ii = _as_dev(image_index, torch.int32, dev)
-        if ii.shape != (B,):
-            raise ValueError("image_index must be (B,)")
-        _check_image_index(image_index, ii, B, P)
-    elif P not in (1, B):
-        raise ValueError("without image_index, depth must have 1 or B planes")
-    g = None
-    if ground is not None:
-        g = _as_dev(ground, torch.float64, dev)
-        if g.shape != (B, 4):
-            raise ValueError("ground must be (B,4)")
-    si = None
-    if sample_idx is not None:
-        si = _as_dev(sample_idx, torch.int32, dev)
-        if si.shape != (B, NSAMPLE):
-            raise ValueError("sample_idx must be (B,500)")
+    d, k, ii, g, si, P = _fit_inputs(depth, K, image_index, ground, sample_idx, B, H, W, dev, "masks", check_device_index=True)
     with torch.cuda.device(dev):
         if W % 32 != 0 and 2 <= B <= 256 and si is None:
             # a small batch on a frame of odd width (COCO: 427, 500, 375, 333 ...): the tiled forms - and the row engine small batches
@@ -326,8 +364,6 @@ def fit_instances(depth, masks, K, ground=None, sample_idx=None, image_index=Non
         f = InstanceFitter(B, H, W, dev)
         if B == 0:
             return f.boxes[0], f.status[0], f.aux[0]
-        if k.shape[0] == 1 and P > 1:
-            k = k.expand(P, 3, 3).contiguous()
         _order(stream)   # the arguments were uploaded / converted on the current stream
         out = f.run(d if P > 1 else d[0], m, k, g, si, ii, stream=stream)
         _record(stream, d, m, k, g, si, ii, f.workspace, f.boxes, f.status, f.aux)

@@ -104,88 +104,76 @@ double la3d_f16_round_host(double x) { return f16_round(x); }
 
 // Workspace layout (one per concurrently running call; contents need not be initialised or preserved):
 //   instance engine: [B] u32 sort keys of the size-balanced launch order (4*B bytes)
-//   band engine:     [B] u32 sort keys | [B][4] i32 arrival counters | [B][88] f64 exchange records (band_workspace_bytes)
+//   band engine:     [B] u32 sort keys | [B][4] u64 tagged arrival words | [B][BAND_NB_MAX = 8][22] f64 exchange records
+//                    (band_workspace_bytes)
 //   split engine:    [B][GEO_D] f64 geometry, then bit images, tile lists and partial-sum slots (split_workspace_bytes)
-//   row engine:      [B][nb][10] f64 partial records | [B][nb][2 W] u32 per-column depth ranges (rows_workspace_bytes)
+//   row engine:      [B][nb][ROWS_PART_D = 20] f64 partial records | [B][nb][2 W] u32 per-column depth ranges | [B] u64 tagged
+//                    arrival words of the one-launch form; nb <= 16 bands per instance (rows_plan, rows_workspace_bytes)
 size_t la3d_workspace_bytes(int B, int H, int W) {
   if (B <= 0) return 0;
   const size_t inst = (size_t)B * GEO_D * sizeof(double);  // kept as the minimum (older callers size by it)
   const size_t split = split_workspace_bytes(B, H, W);     // split engine: + bit image, tile lists, partial slots
-  const size_t band = band_frame_ok(H, W, 2) ? band_workspace_bytes(B) : 0;   // band engine: keys, arrival counters, exchange records
+  const size_t band = band_frame_ok(H, W, 2) ? band_workspace_bytes(B) : 0;   // band engine: keys, arrival words, exchange records
   const size_t rows = rows_workspace_bytes(B, H, W);         // row engine: partial records and per-column ranges of every band
   size_t m = split > inst ? split : inst;
   if (band > m) m = band;
   return rows > m ? rows : m;
 }
 
-struct PolyArgs { const int32_t* xy; const int64_t* ring_off; const int64_t* inst_rings; };
-struct FilterArgs { int boundary, min_area, max_edge; int32_t* stats; };
-struct ProjArgs { double* out; double width, height; };
-struct CallOpts { int engine, order, build, frame_w; };
-
-static int fit_dispatch(const float* depth, int64_t depth_plane_stride, const int32_t* image_index, const uint8_t* mask,
-                        const int32_t* rle_counts, const int64_t* rle_offsets, const double* K, int32_t k_stride,
-                        const double* ground, const int32_t* sample_idx, int B, int H, int W, double* out,
-                        int32_t* status, double* aux, void* workspace, void* stream, const char* who,
-                        const PolyArgs* poly = nullptr, const FilterArgs* filter = nullptr, const ProjArgs* proj = nullptr,
-                        const int32_t* area_hint = nullptr, const CallOpts* opts = nullptr) {
-  const bool rle = rle_counts != nullptr || poly != nullptr;   // "no u8 plane": the mask is decoded into the LDS bit image
-  if (!depth || (!mask && !rle) || (rle_counts && !rle_offsets) || (poly && (!poly->ring_off || !poly->inst_rings)) || !K ||
-      !out || !status || B < 0 || H <= 0 || W <= 0 ||
-      depth_plane_stride < 0 || (k_stride != 0 && k_stride < 9) || (long long)H * W > (1LL << 28)) {
+// Every fit entry ends here with its arguments in one block.  filter_on: the fused instance filter runs (the *_filtered entries
+// always; la3d_fit_instances_ex when filter_boundary >= 0 and filter_max_edge > 0).  who: the entry named in la3d_last_error().
+static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who) {
+  const int B = a.B, H = a.H, W = a.W;
+  const bool rle = a.rle_counts != nullptr || a.poly_xy != nullptr;   // "no u8 plane": the mask is decoded into the LDS bit image
+  if (!a.depth || (!a.mask && !rle) || (a.rle_counts && !a.rle_offsets) || (a.poly_xy && (!a.ring_offsets || !a.inst_rings)) ||
+      !a.K || !a.out || !a.status || B < 0 || H <= 0 || W <= 0 ||
+      a.depth_plane_stride < 0 || (a.k_stride != 0 && a.k_stride < 9) || (long long)H * W > (1LL << 28)) {
     snprintf(g_err, sizeof(g_err), "%s: bad argument", who);
     return LA3D_ERR_ARG;
   }
   if (B == 0) return LA3D_SUCCESS;
-  if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 7)) {
+  if (!a.workspace || (reinterpret_cast<uintptr_t>(a.workspace) & 7)) {
     snprintf(g_err, sizeof(g_err), "%s: workspace of la3d_workspace_bytes() bytes (8-aligned) required", who);
     return LA3D_ERR_ARG;
   }
-  FitParams p;
-  p.geo = static_cast<double*>(workspace);
-  p.depth = depth; p.depth_plane_stride = depth_plane_stride; p.image_index = image_index;
-  p.mask = mask; p.K = K; p.k_stride = k_stride; p.ground = ground; p.sample_idx = sample_idx;
-  p.rle_counts = rle_counts; p.rle_offsets = reinterpret_cast<const long long*>(rle_offsets);
-  p.poly_xy = poly ? poly->xy : nullptr;
-  p.poly_ring_off = poly ? reinterpret_cast<const long long*>(poly->ring_off) : nullptr;
-  p.poly_inst_rings = poly ? reinterpret_cast<const long long*>(poly->inst_rings) : nullptr;
+  FitParams p;   // (every other field keeps its default: see FitParams)
+  p.geo = static_cast<double*>(a.workspace);
+  p.depth = a.depth; p.depth_plane_stride = a.depth_plane_stride; p.image_index = a.image_index;
+  p.mask = a.mask; p.K = a.K; p.k_stride = a.k_stride; p.ground = a.ground; p.sample_idx = a.sample_idx;
+  p.rle_counts = a.rle_counts; p.rle_offsets = reinterpret_cast<const long long*>(a.rle_offsets);
+  p.poly_xy = a.poly_xy;
+  p.poly_ring_off = reinterpret_cast<const long long*>(a.ring_offsets);
+  p.poly_inst_rings = reinterpret_cast<const long long*>(a.inst_rings);
   p.B = B; p.H = H; p.W = W; p.HW = H * W;
   p.nwords = (p.HW + 31) / 32;
   p.rows_aligned = (W % 4 == 0);
   p.rcpW = 1.0f / (float)W;
-  p.out = out; p.status = status; p.aux = aux;
-  p.ntx = p.nty = p.tiles_per_wave = p.list_cap = 0;
-  p.rcp_ntx = 1.0f;
-  p.order_nch = 0; p.order_keys = nullptr; p.order_resident = 0; p.order_shift = 0;
-  p.order_self = 0; p.order_flags = nullptr; p.order_nonce = 0; p.est_step = 1;
-  p.stagger_ticks = 0;
+  p.out = a.out; p.status = a.status; p.aux = a.aux;
   p.band_test = config().band_test;
   // build of the call: the default (separable single pass where it applies), PLAIN = the two-pass form for every camera, NOCULL = the
   // two-pass form that also walks EVERY active tile in pass B (no culling plan): the reference build the culling tests compare with
-  const int build = (opts && opts->build != LA3D_BUILD_DEFAULT) ? opts->build : config().build;
+  const int build = a.opt_build != LA3D_BUILD_DEFAULT ? a.opt_build : config().build;
   p.sep_off = (config().sep == 0 || build != LA3D_BUILD_DEFAULT) ? 1 : 0;
-  p.band_trows = 0; p.band_arrive = nullptr; p.band_tag = 0; p.band_xch = nullptr;
-  p.cull_min = build == LA3D_BUILD_NOCULL ? 0x7fffffff : config().cull_min > 0 ? config().cull_min : (mask != nullptr ? config().cull_min_u8 : CULL_MIN);
-  p.filter_boundary = -1; p.filter_min_area = 0; p.filter_max_edge = 0; p.filter_stats = nullptr;
-  p.proj = proj ? proj->out : nullptr; p.proj_w = proj ? proj->width : 0; p.proj_h = proj ? proj->height : 0;
-  p.area_hint = area_hint;
-  p.opt_engine = opts ? opts->engine : 0; p.opt_order = opts ? opts->order : 0; p.opt_build = opts ? opts->build : 0;
+  p.cull_min = build == LA3D_BUILD_NOCULL ? 0x7fffffff : config().cull_min > 0 ? config().cull_min : (a.mask != nullptr ? config().cull_min_u8 : CULL_MIN);
+  p.proj = a.proj; p.proj_w = a.image_width; p.proj_h = a.image_height;
+  p.area_hint = a.area_hint;
+  p.opt_engine = a.opt_engine; p.opt_order = a.opt_launch_order; p.opt_build = a.opt_build;
   p.frame_w = W;
-  if (opts && opts->frame_w != 0 && opts->frame_w != W) {
+  if (a.frame_width != 0 && a.frame_width != W) {
     // rows padded on the right (la3d_fit_args::frame_width): run-length / polygon masks, word-aligned rows
-    if (opts->frame_w < 0 || opts->frame_w > W || mask != nullptr || W % 32 != 0) {
+    if (a.frame_width < 0 || a.frame_width > W || a.mask != nullptr || W % 32 != 0) {
       snprintf(g_err, sizeof(g_err), "%s: frame_width must be 0 or in (0, W], with run-length / polygon masks and W %% 32 == 0", who);
       return LA3D_ERR_ARG;
     }
-    p.frame_w = opts->frame_w;
+    p.frame_w = a.frame_width;
   }
-  if (filter) {
-    if (!rle || filter->boundary < 0) {
+  if (filter_on) {
+    if (!rle || a.filter_boundary < 0) {
       snprintf(g_err, sizeof(g_err), "%s: the fused filter needs run-length or polygon masks and boundary >= 0", who);
       return LA3D_ERR_ARG;
     }
-    p.filter_boundary = filter->boundary; p.filter_min_area = filter->min_area; p.filter_max_edge = filter->max_edge;
-    p.filter_stats = filter->stats;
+    p.filter_boundary = a.filter_boundary; p.filter_min_area = a.filter_min_area; p.filter_max_edge = a.filter_max_edge;
+    p.filter_stats = a.stats;
   }
   const int bit_bytes = ((((p.HW + 15) / 16 + 1) / 2) * 4 + 15) & ~15;  // u16 per 16 px, padded to u32, 16-aligned
   const bool ldsmask = bit_bytes <= MAX_MASK_LDS;
@@ -195,45 +183,71 @@ static int fit_dispatch(const float* depth, int64_t depth_plane_stride, const in
     return LA3D_ERR_UNSUPPORTED;
   }
   // 16-byte vector path: every plane base 16-aligned (the u8 mask only when it is read at all)
-  const bool vec = (p.HW % 16 == 0) && (rle || (reinterpret_cast<uintptr_t>(mask) & 15) == 0) &&
-                   ((reinterpret_cast<uintptr_t>(depth) & 15) == 0) && (depth_plane_stride % 4 == 0);
-  const bool sample = sample_idx != nullptr;
+  const bool vec = (p.HW % 16 == 0) && (rle || (reinterpret_cast<uintptr_t>(a.mask) & 15) == 0) &&
+                   ((reinterpret_cast<uintptr_t>(a.depth) & 15) == 0) && (a.depth_plane_stride % 4 == 0);
+  const bool sample = a.sample_idx != nullptr;
   size_t lds = (size_t)p.mask_lds_bytes + sizeof(Shared);
   // polygons: the side stage sits behind Shared, where the tile list / rank prefix go later (disjoint in time)
-  const size_t poly_stage = poly ? (size_t)POLY_STAGE_BYTES : 0;
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t poly_stage = a.poly_xy ? (size_t)POLY_STAGE_BYTES : 0;
+  hipStream_t s = static_cast<hipStream_t>(a.stream);
   // Round 5: a call WITHOUT a ground array on a frame the one-pass tile list covers takes the instance engine at EVERY batch size - its
   // separable single pass (no pass B, no cull plan: a chain of three short phases per workgroup) is faster than the chain of six
   // launches of the split engine and than the band engine's exchange from B = 1 on, for all three mask formats
   // (profiles/r05/r05_small_batches.txt: B = 1 / 16 / 64 / 256, u8 planes: 27.7 / 32.1 / 36.8 / 45.1 us vs 31.7 / 34.8 / 37.9 / 59.8;
   // run lengths 31.2 / 35.6 / 36.4 / 40.0 vs 34.3 / 37.9 / 43.3 / 57.4).  A skewed K (not separable) still takes this route - the
   // kernel then runs its two passes -; a call WITH a ground array keeps the old choice below (two passes either way).
-  // Small batches of u8 planes (up to 192 instances by default) go one step further: the same single pass split over up to sixteen
-  // workgroups per instance, one per band of rows, and a short merge launch (row engine: B = 1 / 16 / 64 / 128 18.2 / 19.3 / 24.0 /
-  // 30.0 us per call, profiles/r05/r05_rows_engine.txt).
+  // Small batches of u8 planes (up to config().rows_maxb = 160 instances by default) go one step further: the same single pass split
+  // over up to sixteen workgroups per instance, one per band of rows, and a short merge launch (row engine: B = 1 / 16 / 64 / 128
+  // 18.2 / 19.3 / 24.0 / 30.0 us per call, profiles/r05/r05_rows_engine.txt).
   const int eng = p.opt_engine != LA3D_ENGINE_DEFAULT ? p.opt_engine : config().engine;
-  const bool single_pass_call = ground == nullptr && !sample && !p.sep_off && ldsmask && vec && W % 32 == 0 && W / 32 <= 255 &&
+  const bool single_pass_call = a.ground == nullptr && !sample && !p.sep_off && ldsmask && vec && W % 32 == 0 && W / 32 <= 255 &&
                                 (H + 7) / 8 <= 255 && ((W / 32) * ((H + 7) / 8) + NWAVE - 1) / NWAVE <= 256 &&
                                 (eng == LA3D_ENGINE_DEFAULT || eng == LA3D_ENGINE_ROWS || eng == LA3D_ENGINE_ROWS2);   // (rows pinned but not applicable: as by default)
   {
     int rc = LA3D_SUCCESS;
-    if (rows_fit_if_eligible(p, vec, sample, s, workspace, &rc)) return rc;
+    if (rows_fit_if_eligible(p, vec, sample, s, a.workspace, &rc)) return rc;
   }
-  if (!single_pass_call && band_eligible(p, vec, sample)) return band_fit(p, s, workspace);   // grounded u8 planes, 1 <= B <= 160 (or pinned): two / four / eight workgroups per instance, ONE launch
+  if (!single_pass_call && band_eligible(p, vec, sample)) return band_fit(p, s, a.workspace);   // grounded u8 planes, 1 <= B <= 160 (or pinned): two / four / eight workgroups per instance, ONE launch
   if (!single_pass_call && !sample && p.frame_w == W && split_eligible(p, vec, ldsmask)) {   // (the split engine's decoders know no padded rows)
-    const int rc = split_fit(p, workspace, s);   // (the split engine's final kernel does not project: one small follow-up launch)
+    const int rc = split_fit(p, a.workspace, s);   // (the split engine's final kernel does not project: one small follow-up launch)
     if (rc != LA3D_SUCCESS || !p.proj) return rc;
-    return la3d_project_boxes(out, K, k_stride, image_index, B, p.proj_w, p.proj_h, p.proj, stream);   // (la3d_consumers.hip)
+    return la3d_project_boxes(a.out, a.K, a.k_stride, a.image_index, B, p.proj_w, p.proj_h, p.proj, a.stream);   // (la3d_consumers.hip)
   }
-  return instance_fit(p, vec, ldsmask, sample, lds, poly_stage, s, workspace, who);
+  return instance_fit(p, vec, ldsmask, sample, lds, poly_stage, s, a.workspace, who);
+}
+
+// The entries of ABI 1 fill a zeroed block (no filter, no options) and keep their own checks and error texts.
+static la3d_fit_args legacy_args(const float* depth, int64_t depth_plane_stride, const int32_t* image_index, const double* K,
+                                 int32_t k_stride, const double* ground, const int32_t* sample_idx, int B, int H, int W,
+                                 double* out, int32_t* status, double* aux, void* workspace, void* stream) {
+  la3d_fit_args a{};
+  a.struct_size = (int32_t)sizeof(a);
+  a.B = B; a.H = H; a.W = W;
+  a.depth = depth; a.depth_plane_stride = depth_plane_stride; a.image_index = image_index;
+  a.K = K; a.k_stride = k_stride; a.ground = ground; a.sample_idx = sample_idx;
+  a.out = out; a.status = status; a.aux = aux; a.workspace = workspace; a.stream = stream;
+  return a;
+}
+
+// polygon parts of the legacy entries: a batch of zero instances may come without vertices (an empty array has no data pointer) and
+// is still a polygon call - poly_xy then borrows ring_offsets' non-null value, which nothing reads
+static void legacy_poly(la3d_fit_args& a, const int32_t* poly_xy, const int64_t* ring_offsets, const int64_t* inst_rings) {
+  a.poly_xy = poly_xy ? poly_xy : reinterpret_cast<const int32_t*>(ring_offsets);
+  a.ring_offsets = ring_offsets; a.inst_rings = inst_rings;
+}
+
+static void legacy_filter(la3d_fit_args& a, int boundary, int min_area, int max_edge, int32_t* stats) {
+  a.filter_boundary = boundary; a.filter_min_area = min_area; a.filter_max_edge = max_edge; a.stats = stats;
 }
 
 int la3d_fit_instances(const float* depth, int64_t depth_plane_stride, const int32_t* image_index,
                        const uint8_t* mask, const double* K, int32_t k_stride, const double* ground,
                        const int32_t* sample_idx, int B, int H, int W, double* out, int32_t* status, double* aux,
                        void* workspace, void* stream) {
-  return fit_dispatch(depth, depth_plane_stride, image_index, mask, nullptr, nullptr, K, k_stride, ground, sample_idx, B, H,
-                      W, out, status, aux, workspace, stream, "la3d_fit_instances");
+  la3d_fit_args a = legacy_args(depth, depth_plane_stride, image_index, K, k_stride, ground, sample_idx, B, H, W, out, status, aux,
+                                workspace, stream);
+  a.mask = mask;
+  return fit_dispatch(a, false, "la3d_fit_instances");
 }
 
 int la3d_fit_instances_rle(const float* depth, int64_t depth_plane_stride, const int32_t* image_index,
@@ -244,8 +258,10 @@ int la3d_fit_instances_rle(const float* depth, int64_t depth_plane_stride, const
     set_err("la3d_fit_instances_rle: bad argument");
     return LA3D_ERR_ARG;
   }
-  return fit_dispatch(depth, depth_plane_stride, image_index, nullptr, rle_counts, rle_offsets, K, k_stride, ground,
-                      sample_idx, B, H, W, out, status, aux, workspace, stream, "la3d_fit_instances_rle");
+  la3d_fit_args a = legacy_args(depth, depth_plane_stride, image_index, K, k_stride, ground, sample_idx, B, H, W, out, status, aux,
+                                workspace, stream);
+  a.rle_counts = rle_counts; a.rle_offsets = rle_offsets;
+  return fit_dispatch(a, false, "la3d_fit_instances_rle");
 }
 
 int la3d_fit_instances_poly(const float* depth, int64_t depth_plane_stride, const int32_t* image_index,
@@ -256,11 +272,13 @@ int la3d_fit_instances_poly(const float* depth, int64_t depth_plane_stride, cons
     set_err("la3d_fit_instances_poly: bad argument");
     return LA3D_ERR_ARG;
   }
-  const PolyArgs pa{poly_xy, ring_offsets, inst_rings};
-  return fit_dispatch(depth, depth_plane_stride, image_index, nullptr, nullptr, nullptr, K, k_stride, ground, sample_idx, B, H, W,
-                      out, status, aux, workspace, stream, "la3d_fit_instances_poly", &pa);
+  la3d_fit_args a = legacy_args(depth, depth_plane_stride, image_index, K, k_stride, ground, sample_idx, B, H, W, out, status, aux,
+                                workspace, stream);
+  legacy_poly(a, poly_xy, ring_offsets, inst_rings);
+  return fit_dispatch(a, false, "la3d_fit_instances_poly");
 }
 
+// The *_filtered entries always run the filter: boundary < 0 is an error, max_edge <= 0 drops every instance.
 int la3d_fit_instances_rle_filtered(const float* depth, int64_t depth_plane_stride, const int32_t* image_index,
                                     const int32_t* rle_counts, const int64_t* rle_offsets, const double* K, int32_t k_stride,
                                     const double* ground, const int32_t* sample_idx, int B, int H, int W, int boundary,
@@ -270,9 +288,11 @@ int la3d_fit_instances_rle_filtered(const float* depth, int64_t depth_plane_stri
     set_err("la3d_fit_instances_rle_filtered: bad argument");
     return LA3D_ERR_ARG;
   }
-  const FilterArgs fa{boundary, min_area, max_edge, stats};
-  return fit_dispatch(depth, depth_plane_stride, image_index, nullptr, rle_counts, rle_offsets, K, k_stride, ground, sample_idx, B,
-                      H, W, out, status, aux, workspace, stream, "la3d_fit_instances_rle_filtered", nullptr, &fa);
+  la3d_fit_args a = legacy_args(depth, depth_plane_stride, image_index, K, k_stride, ground, sample_idx, B, H, W, out, status, aux,
+                                workspace, stream);
+  a.rle_counts = rle_counts; a.rle_offsets = rle_offsets;
+  legacy_filter(a, boundary, min_area, max_edge, stats);
+  return fit_dispatch(a, true, "la3d_fit_instances_rle_filtered");
 }
 
 int la3d_fit_instances_poly_filtered(const float* depth, int64_t depth_plane_stride, const int32_t* image_index,
@@ -284,10 +304,11 @@ int la3d_fit_instances_poly_filtered(const float* depth, int64_t depth_plane_str
     set_err("la3d_fit_instances_poly_filtered: bad argument");
     return LA3D_ERR_ARG;
   }
-  const PolyArgs pa{poly_xy, ring_offsets, inst_rings};
-  const FilterArgs fa{boundary, min_area, max_edge, stats};
-  return fit_dispatch(depth, depth_plane_stride, image_index, nullptr, nullptr, nullptr, K, k_stride, ground, sample_idx, B, H, W,
-                      out, status, aux, workspace, stream, "la3d_fit_instances_poly_filtered", &pa, &fa);
+  la3d_fit_args a = legacy_args(depth, depth_plane_stride, image_index, K, k_stride, ground, sample_idx, B, H, W, out, status, aux,
+                                workspace, stream);
+  legacy_poly(a, poly_xy, ring_offsets, inst_rings);
+  legacy_filter(a, boundary, min_area, max_edge, stats);
+  return fit_dispatch(a, true, "la3d_fit_instances_poly_filtered");
 }
 
 int la3d_fit_instances_ex(const la3d_fit_args* args) {
@@ -312,21 +333,14 @@ int la3d_fit_instances_ex(const la3d_fit_args* args) {
     set_err("la3d_fit_instances_ex: proj needs image_width / image_height > 0");
     return LA3D_ERR_ARG;
   }
-  const PolyArgs pa{a.poly_xy, a.ring_offsets, a.inst_rings};
-  // the fused filter is on when filter_boundary >= 0 AND filter_max_edge > 0: a zero-initialised block (the natural C idiom, and
-  // what "missing fields are zero" gives) means NO filter - max_edge == 0 would reject every instance (edge < 0 never holds)
-  const bool filter_on = a.filter_boundary >= 0 && a.filter_max_edge > 0;
-  const FilterArgs fa{a.filter_boundary, a.filter_min_area, a.filter_max_edge, a.stats};
-  const ProjArgs pr{a.proj, a.image_width, a.image_height};
   if (a.opt_engine < 0 || a.opt_engine > LA3D_ENGINE_ROWS2 || a.opt_launch_order < 0 || a.opt_launch_order > LA3D_ORDER_ON ||
       a.opt_build < 0 || a.opt_build > LA3D_BUILD_NOCULL) {
     set_err("la3d_fit_instances_ex: bad opt_engine / opt_launch_order / opt_build");
     return LA3D_ERR_ARG;
   }
-  const CallOpts co{a.opt_engine, a.opt_launch_order, a.opt_build, a.frame_width};
-  return fit_dispatch(a.depth, a.depth_plane_stride, a.image_index, a.mask, a.rle_counts, a.rle_offsets, a.K, a.k_stride, a.ground,
-                      a.sample_idx, a.B, a.H, a.W, a.out, a.status, a.aux, a.workspace, a.stream, "la3d_fit_instances_ex",
-                      a.poly_xy ? &pa : nullptr, filter_on ? &fa : nullptr, a.proj ? &pr : nullptr, a.area_hint, &co);
+  // the fused filter is on when filter_boundary >= 0 AND filter_max_edge > 0: a zero-initialised block (the natural C idiom, and
+  // what "missing fields are zero" gives) means NO filter - max_edge == 0 would reject every instance (edge < 0 never holds)
+  return fit_dispatch(a, a.filter_boundary >= 0 && a.filter_max_edge > 0, "la3d_fit_instances_ex");
 }
 
 }  // extern "C"

@@ -478,63 +478,65 @@ __device__ inline double dmax(double a, double b) {
   return r;
 }
 
+// The kernel parameters of one fit call: its layout is the kernel argument layout.  fit_dispatch (la3d.hip) sets what a call
+// decides; every other field keeps its default.
 struct FitParams {
-  const float* depth;
-  long long depth_plane_stride;
-  const int* image_index;
-  const unsigned char* mask;
-  const double* K;
-  int k_stride;
-  const double* ground;
-  const int* sample_idx;
-  int B, H, W, HW;
-  int nwords;          // ceil(HW / 32) bit-image words
-  int mask_lds_bytes;  // bit-image bytes in LDS (16-aligned), 0 when the image does not fit
-  int rows_aligned;    // W % 4 == 0: a 4-pixel quad never straddles a row
-  float rcpW;
-  double* geo;         // workspace: [B][GEO_D]
-  const int* rle_counts;        // masks given as COCO run lengths (column-major, zeros first) instead of u8 planes
-  const long long* rle_offsets; // [B+1] into rle_counts
-  const int* poly_xy;           // masks given as polygon parts: int32 (x, y) pairs ...
-  const long long* poly_ring_off;   // ... [R+1] point offsets of the parts ...
-  const long long* poly_inst_rings; // ... [B+1] part offsets of the instances
-  int ntx, nty;        // TILED: tiles of 32 px x 8 rows (ntx = W/32, nty = ceil(H/8))
-  int tiles_per_wave;  // TILED: ceil(ntx*nty / NWAVE)
-  int list_cap;        // TILED: entries of the active-tile list that fit the LDS budget
-  float rcp_ntx;       // TILED: 1 / ntx
+  const float* depth = nullptr;
+  long long depth_plane_stride = 0;
+  const int* image_index = nullptr;
+  const unsigned char* mask = nullptr;
+  const double* K = nullptr;
+  int k_stride = 0;
+  const double* ground = nullptr;
+  const int* sample_idx = nullptr;
+  int B = 0, H = 0, W = 0, HW = 0;
+  int nwords = 0;      // ceil(HW / 32) bit-image words
+  int mask_lds_bytes = 0;  // bit-image bytes in LDS (16-aligned), 0 when the image does not fit
+  int rows_aligned = 0;  // W % 4 == 0: a 4-pixel quad never straddles a row
+  float rcpW = 0;
+  double* geo = nullptr;  // workspace: [B][GEO_D]
+  const int* rle_counts = nullptr;  // masks given as COCO run lengths (column-major, zeros first) instead of u8 planes
+  const long long* rle_offsets = nullptr;  // [B+1] into rle_counts
+  const int* poly_xy = nullptr;  // masks given as polygon parts: int32 (x, y) pairs ...
+  const long long* poly_ring_off = nullptr;  // ... [R+1] point offsets of the parts ...
+  const long long* poly_inst_rings = nullptr;  // ... [B+1] part offsets of the instances
+  int ntx = 0, nty = 0;  // TILED: tiles of 32 px x 8 rows (ntx = W/32, nty = ceil(H/8))
+  int tiles_per_wave = 0;  // TILED: ceil(ntx*nty / NWAVE)
+  int list_cap = 0;    // TILED: entries of the active-tile list that fit the LDS budget
+  float rcp_ntx = 1.0f;  // TILED: 1 / ntx
   // size-balanced launch order (order_nch > 0; otherwise workgroup b fits instance xcd_remap(b)): sort keys per instance from
   // the estimate kernel, or built on the fly from area_hint; every workgroup ranks the <= ORDER_CHUNK keys of its chunk itself
-  const unsigned* order_keys;
+  const unsigned* order_keys = nullptr;
   // self-estimating launch (round 4; order_self != 0): no helper kernel - workgroup b estimates the key of instance b in its prologue
   // and publishes it with a per-call nonce; order_select waits for the nonces of its chunk (la3d.hip: estimate_publish)
-  unsigned long long* order_flags;
-  unsigned long long order_nonce;
-  int order_self, est_step;
-  int order_nch;       // chunks of consecutive instances (ceil(B / ORDER_CHUNK)), 0 = launch order off
-  int order_resident;  // workgroups of the grid that are resident at once
-  int order_shift;     // area_hint >> order_shift fits 18 bits
-  int cull_min;        // pass-B culling: instances with at least this many active tiles plan (cull_plan)
-  int stagger_ticks;   // u8 planes: resident groups of 256 workgroups start this many 100 MHz ticks apart (0: off; see fit_instances_kernel)
+  unsigned long long* order_flags = nullptr;
+  unsigned long long order_nonce = 0;
+  int order_self = 0, est_step = 1;
+  int order_nch = 0;   // chunks of consecutive instances (ceil(B / ORDER_CHUNK)), 0 = launch order off
+  int order_resident = 0;  // workgroups of the grid that are resident at once
+  int order_shift = 0;  // area_hint >> order_shift fits 18 bits
+  int cull_min = 0;    // pass-B culling: instances with at least this many active tiles plan (cull_plan)
+  int stagger_ticks = 0;  // u8 planes: resident groups of 256 workgroups start this many 100 MHz ticks apart (0: off; see fit_instances_kernel)
   // instance filter fused into the fit (run-length / polygon input): boundary < 0 = off
-  int filter_boundary, filter_min_area, filter_max_edge;
-  int* filter_stats;   // [B][4] area, rows, span, edge (may be null)
+  int filter_boundary = -1, filter_min_area = 0, filter_max_edge = 0;
+  int* filter_stats = nullptr;  // [B][4] area, rows, span, edge (may be null)
   // optional epilogue: bbox2D_proj | bbox2D_trunc of every record ([B][8], la3d_project_boxes' layout), frame size proj_w x proj_h
-  double* proj;
-  double proj_w, proj_h;
-  const int* area_hint;   // [B] mask areas known to the caller (launch order without the estimate pass), or null
-  int opt_engine, opt_order, opt_build;   // per-call overrides (la3d_fit_args::opt_*; host side only), 0 = the library's choice
-  // band engine (fit_bands_kernel): tile rows per band (the last band takes the remainder), arrival counters [B][4] (zeroed before
-  // the launch) and the exchange area [B][NB * 22] doubles, both in the workspace
-  int band_trows;
-  unsigned long long* band_arrive;   // [B][4] arrival words: 48-bit per-call tag | 16-bit count (tagged_arrive in la3d.hip): never cleared
-  unsigned long long band_tag;
-  double* band_xch;
-  int band_test;       // Config::band_test
-  int sep_off;         // 1: never take the separable single pass (LA3D_SEP=0, opt_build = LA3D_BUILD_PLAIN)
-  double* out;
-  int* status;
-  double* aux;
-  int frame_w;         // la3d_fit_args::frame_width (run-length / polygon input): image columns of the W-wide planes; == W when not given
+  double* proj = nullptr;
+  double proj_w = 0, proj_h = 0;
+  const int* area_hint = nullptr;  // [B] mask areas known to the caller (launch order without the estimate pass), or null
+  int opt_engine = 0, opt_order = 0, opt_build = 0;  // per-call overrides (la3d_fit_args::opt_*; host side only), 0 = the library's choice
+  // band engine (fit_bands_kernel): tile rows per band (the last band takes the remainder), arrival words [B][4] and the exchange
+  // area [B][NB * 22] doubles, both in the workspace
+  int band_trows = 0;
+  unsigned long long* band_arrive = nullptr;  // [B][4] arrival words: 48-bit per-call tag | 16-bit count (tagged_arrive in la3d.hip): never cleared
+  unsigned long long band_tag = 0;
+  double* band_xch = nullptr;
+  int band_test = 0;   // Config::band_test
+  int sep_off = 0;     // 1: never take the separable single pass (LA3D_SEP=0, opt_build = LA3D_BUILD_PLAIN)
+  double* out = nullptr;
+  int* status = nullptr;
+  double* aux = nullptr;
+  int frame_w = 0;     // la3d_fit_args::frame_width (run-length / polygon input): image columns of the W-wide planes; == W when not given
 };
 
 // per-instance geometry in the workspace (20 doubles = 160 B), written by the split engine's plan_kernel (geo_one)

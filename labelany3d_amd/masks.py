@@ -30,7 +30,8 @@ import torch
 
 from . import options
 from ._lib import AUX, BOX_FILTERED, REC, check, lib
-from .batched import InstanceFitter, _as_dev, _bulk, _dev, _ptr, _record, _stream, _upload_many, pad_rows_f32
+from .batched import (InstanceFitter, _as_dev, _bulk, _dev, _filter_args, _fit_args, _fit_inputs, _ptr, _record, _stream,  # noqa: F401
+                      _upload_many, pad_rows_f32)
 
 
 def rle_from_string(s) -> np.ndarray:
@@ -257,20 +258,14 @@ def fit_instances_ex(depth, K, masks=None, rles=None, polys=None, ground=None, s
     masks; a hint only orders the work.  ``frame_width`` (run-length / polygon masks): None - a frame whose width is not a multiple
     of 32 has its depth rows padded here (``pad_depth_rows``); an int - ``depth`` already IS padded (its last dimension is the padded
     width) and the masks' frame is ``frame_width`` columns wide.  Returns a dict: boxes, status, aux, and stats / boxes2d when asked."""
-    import ctypes as C
-
-    from ._lib import FitArgs
-
     dev = _dev(device)
     if (masks is not None) + (rles is not None) + (polys is not None) != 1:
         raise ValueError("give exactly one of masks / rles / polys")
-    a = FitArgs()
-    keep = []
+    given_index = image_index   # (a host image_index is range-checked on the host, before the upload below)
     if masks is not None:
         m = _as_dev(masks, torch.uint8, dev)
         B, H, W = m.shape
-        a.mask = _ptr(m); keep.append(m)
-        what = "mask"
+        kind, keep, what = dict(mask=_ptr(m)), [m], "mask"
     elif rles is not None:
         counts, offsets, H, W = pack_rle(rles)
         counts, offsets, ground, image_index, sample_idx, area_hint = _bulk(
@@ -278,8 +273,7 @@ def fit_instances_ex(depth, K, masks=None, rles=None, polys=None, ground=None, s
             (area_hint, torch.int32))
         c, o = _as_dev(counts, torch.int32, dev), _as_dev(offsets, torch.int64, dev)
         B = o.numel() - 1
-        a.rle_counts, a.rle_offsets = _ptr(c), _ptr(o); keep += [c, o]
-        what = "RLE"
+        kind, keep, what = dict(rle=(_ptr(c), _ptr(o))), [c, o], "RLE"
     else:
         pxy, pro, pir, H, W = polys
         pxy, pro, pir, ground, image_index, sample_idx, area_hint = _bulk(
@@ -287,8 +281,7 @@ def fit_instances_ex(depth, K, masks=None, rles=None, polys=None, ground=None, s
             (sample_idx, torch.int32), (area_hint, torch.int32))
         xy, ro, ir, H, W = _poly_dev((pxy, pro, pir, H, W), dev)
         B = ir.numel() - 1
-        a.poly_xy, a.ring_offsets, a.inst_rings = _ptr(xy), _ptr(ro), _ptr(ir); keep += [xy, ro, ir]
-        what = "polygon"
+        kind, keep, what = dict(poly=(_ptr(xy), _ptr(ro), _ptr(ir))), [xy, ro, ir], "polygon"
     if filter and masks is not None:
         raise ValueError("the fused filter needs run-length or polygon masks")
     fw = 0
@@ -306,7 +299,8 @@ def fit_instances_ex(depth, K, masks=None, rles=None, polys=None, ground=None, s
                 if Wd < W or Wd % 32 != 0:
                     raise ValueError("padded depth rows must be a multiple of 32 wide and at least frame_width")
                 fw, W = W, Wd
-    d, k, P, ii, g, si = _fit_common(depth, K, H, W, B, ground, sample_idx, image_index, dev, what)
+    d, k, ii, g, si, P = _fit_inputs(depth, K, image_index, ground, sample_idx, B, H, W, dev, f"the {what} frame",
+                                     given_index=given_index)
     out = {}
     with torch.cuda.device(dev):
         # (_fitter / _stats: buffers a per-image caller keeps between calls - fit_annotations - instead of allocating them per call)
@@ -320,25 +314,16 @@ def fit_instances_ex(depth, K, masks=None, rles=None, polys=None, ground=None, s
             out["boxes2d"] = torch.full((B, 8), float("nan"), dtype=torch.float64, device=dev)
         if B == 0:
             return out
-        a.struct_size = C.sizeof(FitArgs)
-        a.B, a.H, a.W = B, H, W
-        a.depth, a.depth_plane_stride, a.image_index = _ptr(d), (H * W if P > 1 else 0), _ptr(ii)
-        a.K, a.k_stride = _ptr(k), (9 if k.shape[0] > 1 else 0)
-        a.ground, a.sample_idx = _ptr(g), _ptr(si)
-        if filter:
-            a.filter_boundary, a.filter_min_area, a.filter_max_edge = _filter_args(filter)
-            a.stats = _ptr(out["stats"])
-        if image_size is not None:
-            a.proj, a.image_width, a.image_height = _ptr(out["boxes2d"]), float(image_size[0]), float(image_size[1])
+        ah = None
         if area_hint is not None:
             ah = _as_dev(area_hint, torch.int32, dev).reshape(-1)
             if ah.numel() != B:
                 raise ValueError("area_hint must have one entry per instance")
-            a.area_hint = _ptr(ah); keep.append(ah)
-        a.out, a.status, a.aux = _ptr(f.boxes[0]), _ptr(f.status[0]), _ptr(f.aux[0])
-        a.workspace, a.stream = _ptr(f.workspace[0]), _stream(stream)
-        a.opt_engine, a.opt_launch_order, a.opt_build = options.codes()
-        a.frame_width = fw
+            keep.append(ah)
+        a = _fit_args(B, H, W, _ptr(d), P, _ptr(k), k.shape[0], _ptr(f.boxes[0]), _ptr(f.status[0]), _ptr(f.aux[0]),
+                      _ptr(f.workspace[0]), _stream(stream), image_index=_ptr(ii), ground=_ptr(g), sample_idx=_ptr(si), filter=filter,
+                      stats=_ptr(out.get("stats")), proj=_ptr(out.get("boxes2d")), image_size=image_size, area_hint=_ptr(ah),
+                      opts=options.codes(), frame_width=fw, **kind)
         check(lib.la3d_fit_instances_ex(C.byref(a)), "la3d_fit_instances_ex")
     _record(stream, d, k, ii, g, si, *keep, f.workspace, *out.values())
     return out
@@ -518,8 +503,6 @@ def _fit_annotations_host(annotations, groups, W_img, H_img, depth, K, ground, i
     """``fit_annotations(to_host=True)`` with the depth plane(s) resident and everything else on the host: ONE foreign call per
     segmentation kind (``la3d_fit_annotations_host``: the small arrays go up through the library's pinned block, the records come back
     through it, the call polls a completion flag) - no torch tensor, no wrapper layers in between."""
-    from ._lib import FitArgs
-
     P = depth.shape[0] if depth.dim() == 3 else 1
     dev_index = depth.device.index if depth.device.index is not None else torch.cuda.current_device()
     Wp = padded_width(W_img)
@@ -528,54 +511,43 @@ def _fit_annotations_host(annotations, groups, W_img, H_img, depth, K, ground, i
     Kh = np.ascontiguousarray(np.asarray(K, dtype=np.float64).reshape(-1, 9))
     if Kh.shape[0] not in (1, P):
         raise ValueError("K must be (3,3) or (P,3,3)")
+    host = lambda v: None if v is None else v.ctypes.data   # noqa: E731
     sels, recs, sts = [], [], []
     for kind, (idx, segs) in groups.items():
         if not idx:
             continue
         sel = np.asarray(idx, np.int64)
         B = len(idx)
-        a = FitArgs()
-        a.struct_size = C.sizeof(FitArgs)
-        keep = []
         if kind == "rle":
             counts, offsets, Hh, Ww = pack_rle(segs)
-            a.rle_counts, a.rle_offsets = counts.ctypes.data, offsets.ctypes.data
-            keep += [counts, offsets]
+            masks_kw = dict(rle=(counts.ctypes.data, offsets.ctypes.data))
         else:
             xy, ro, ir, Hh, Ww = pack_polygons(segs, H_img, W_img)
-            a.poly_xy, a.ring_offsets, a.inst_rings = xy.ctypes.data, ro.ctypes.data, ir.ctypes.data
-            keep += [xy, ro, ir]
+            masks_kw = dict(poly=(xy.ctypes.data, ro.ctypes.data, ir.ctypes.data))
         if (Hh, Ww) != (H_img, W_img) or depth.shape[-2:] != (Hh, Wp):
             raise ValueError(f"depth {tuple(depth.shape[-2:])} / image size {(H_img, W_img)} do not match the mask size {(Hh, Ww)}")
-        a.B, a.H, a.W = B, Hh, Wp
-        a.frame_width = Ww if Wp != Ww else 0
-        a.depth, a.depth_plane_stride = depth.data_ptr(), (Hh * Wp if P > 1 else 0)
+        ii = g = hint = None
         if image_index is not None:
             ii = np.ascontiguousarray(np.asarray(image_index)[sel], np.int32)
             if ii.size and (ii.min() < 0 or ii.max() >= P):
                 raise ValueError("image_index out of range")
-            a.image_index = ii.ctypes.data; keep.append(ii)
         elif P > 1:
             # one plane per ANNOTATION (crowd / unsegmented ones included): this kind's instances pick theirs by annotation index
             if P != len(annotations):
                 raise ValueError("several depth planes need image_index (or one plane per annotation)")
             ii = sel.astype(np.int32)
-            a.image_index = ii.ctypes.data; keep.append(ii)
-        a.K, a.k_stride = Kh.ctypes.data, (9 if Kh.shape[0] > 1 else 0)
         if ground is not None:
             g = np.ascontiguousarray(np.asarray(ground, dtype=np.float64).reshape(-1, 4)[sel])
-            a.ground = g.ctypes.data; keep.append(g)
         ar = [annotations[i].get("area") for i in idx]
         if not any(v is None for v in ar):
             hint = np.clip(np.asarray(ar, dtype=np.float64), 0, 2**31 - 1).astype(np.int32)
-            a.area_hint = hint.ctypes.data; keep.append(hint)
-        a.filter_boundary, a.filter_min_area, a.filter_max_edge = _filter_args(flt)
         out = np.empty((B, REC), np.float64)
         st = np.empty(B, np.int32)
-        a.out, a.status = out.ctypes.data, st.ctypes.data
         # the C entry enqueues on the stream it is handed, on the thread's CURRENT device: the depth's device, and the stream the
         # depth (and the padding above) was produced on - torch's current stream of that device
-        a.stream = _raw_stream(dev_index)
+        a = _fit_args(B, Hh, Wp, depth.data_ptr(), P, Kh.ctypes.data, Kh.shape[0], out.ctypes.data, st.ctypes.data, None, None,
+                      _raw_stream(dev_index), image_index=host(ii), ground=host(g), area_hint=host(hint), filter=flt,
+                      frame_width=Ww if Wp != Ww else 0, **masks_kw)
         if dev_index == torch.cuda.current_device():
             check(lib.la3d_fit_annotations_host(C.byref(a)), "la3d_fit_annotations_host")
         else:
@@ -607,49 +579,6 @@ def segmentations_to_masks(segmentations, H: int, W: int, device=None) -> torch.
     return out
 
 
-def _fit_block(f, d, P, ii, k, g, si, B, H, W, stream, filt, stats, opts, rle=None, poly=None):
-    """The argument block of la3d_fit_instances_ex for the run-length / polygon wrappers: used when a scheduling option
-    (labelany3d_amd.options) is active for the call - the plain entry points carry none."""
-    import ctypes as C
-
-    from ._lib import FitArgs
-
-    a = FitArgs()
-    a.struct_size = C.sizeof(FitArgs)
-    a.B, a.H, a.W = B, H, W
-    a.depth, a.depth_plane_stride, a.image_index = _ptr(d), (H * W if P > 1 else 0), _ptr(ii)
-    if rle is not None:
-        a.rle_counts, a.rle_offsets = _ptr(rle[0]), _ptr(rle[1])
-    else:
-        a.poly_xy, a.ring_offsets, a.inst_rings = _ptr(poly[0]), _ptr(poly[1]), _ptr(poly[2])
-    a.K, a.k_stride = _ptr(k), (9 if k.shape[0] > 1 else 0)
-    a.ground, a.sample_idx = _ptr(g), _ptr(si)
-    a.filter_boundary = -1
-    if filt is not None:
-        a.filter_boundary, a.filter_min_area, a.filter_max_edge = filt
-        a.stats = _ptr(stats)
-    a.out, a.status, a.aux = _ptr(f.boxes[0]), _ptr(f.status[0]), _ptr(f.aux[0])
-    a.workspace, a.stream = _ptr(f.workspace[0]), _stream(stream)
-    a.opt_engine, a.opt_launch_order, a.opt_build = opts
-    return lib.la3d_fit_instances_ex(C.byref(a))
-
-
-def _filter_args(filter):
-    """``filter`` of fit_instances_rle / fit_instances_poly: True or a dict with the reference's three thresholds
-    (src/util.py:291-326, :375): boundary strip width (10), minimum area (100), boundary pixels that make a mask "truncated" (10)."""
-    f = {} if filter is True else dict(filter)
-    unknown = set(f) - {"boundary_threshold", "scale_threshold", "truncation_pixels"}
-    if unknown:
-        raise ValueError(f"unknown filter keys: {sorted(unknown)}")
-    b, a, e = int(f.get("boundary_threshold", 10)), int(f.get("scale_threshold", 100)), int(f.get("truncation_pixels", 10))
-    if b < 0 or e <= 0:
-        # the C-ABI reads filter_boundary < 0 or filter_max_edge <= 0 as "no filter" (a zero-initialised la3d_fit_args means none);
-        # truncation_pixels <= 0 would mean "reject every instance" in the reference's rule (edge < 0 never holds): refuse it here
-        # instead of silently fitting everything
-        raise ValueError("filter: boundary_threshold must be >= 0 and truncation_pixels >= 1")
-    return b, a, e
-
-
 def fit_instances_poly(depth, polys, K, ground=None, sample_idx=None, image_index=None, stream=None, device=None, filter=None):
     """fit_instances with polygon masks: the parts are rasterised inside the fit kernel, straight into its LDS bit image
     (cv2.fillPoly semantics, reference src/util.py:386-400).  Arguments and returns as ``labelany3d_amd.fit_instances``;
@@ -662,60 +591,9 @@ def fit_instances_poly(depth, polys, K, ground=None, sample_idx=None, image_inde
     ``filter=True`` (or a dict of thresholds, see ``_filter_args``) fuses the reference's instance filter (src/util.py:375, polygon
     branch: height = last row - first row + 1) into the same launch: dropped instances get status 6 and a NaN record and cost no
     passes; a fourth return value holds the (B,4) statistics (area, rows, span, edge pixels) as ``mask_stats_poly`` gives them."""
-    dev = _dev(device)
-    pxy, pro, pir, H, W = polys
-    if W % 32 != 0:   # a frame of odd width: depth rows padded to the next multiple of 32 (fit_instances_ex: la3d_fit_args::frame_width)
-        r = fit_instances_ex(depth, K, polys=polys, ground=ground, sample_idx=sample_idx, image_index=image_index, filter=filter,
-                             stream=stream, device=dev)
-        return (r["boxes"], r["status"], r["aux"]) + ((r["stats"],) if filter else ())
-    pxy, pro, pir, ground, image_index, sample_idx = _bulk(dev, (pxy, torch.int32), (pro, torch.int64), (pir, torch.int64), (ground, torch.float64),
-                                                           (image_index, torch.int32), (sample_idx, torch.int32))
-    xy, ro, ir, H, W = _poly_dev((pxy, pro, pir, H, W), dev)
-    B = ir.numel() - 1
-    d, k, P, ii, g, si = _fit_common(depth, K, H, W, B, ground, sample_idx, image_index, dev, "polygon")
-    stats = None
-    with torch.cuda.device(dev):
-        f = InstanceFitter(B, H, W, dev)
-        if filter:
-            stats = torch.zeros((B, 4), dtype=torch.int32, device=dev)
-        if B == 0:
-            return (f.boxes[0], f.status[0], f.aux[0]) + ((stats,) if filter else ())
-        opts = options.codes()
-        if any(opts):
-            rc = _fit_block(f, d, P, ii, k, g, si, B, H, W, stream, _filter_args(filter) if filter else None, stats, opts, poly=(xy, ro, ir))
-        elif filter:
-            b, a, e = _filter_args(filter)
-            rc = lib.la3d_fit_instances_poly_filtered(_ptr(d), H * W if P > 1 else 0, _ptr(ii), _ptr(xy), _ptr(ro), _ptr(ir), _ptr(k),
-                                                      9 if k.shape[0] > 1 else 0, _ptr(g), _ptr(si), B, H, W, b, a, e,
-                                                      _ptr(f.boxes[0]), _ptr(f.status[0]), _ptr(f.aux[0]), _ptr(stats),
-                                                      _ptr(f.workspace[0]), _stream(stream))
-        else:
-            rc = lib.la3d_fit_instances_poly(_ptr(d), H * W if P > 1 else 0, _ptr(ii), _ptr(xy), _ptr(ro), _ptr(ir), _ptr(k),
-                                             9 if k.shape[0] > 1 else 0, _ptr(g), _ptr(si), B, H, W, _ptr(f.boxes[0]),
-                                             _ptr(f.status[0]), _ptr(f.aux[0]), _ptr(f.workspace[0]), _stream(stream))
-        check(rc, "la3d_fit_instances_poly")
-    _record(stream, d, k, ii, g, si, xy, ro, ir, stats, f.workspace, f.boxes, f.status, f.aux)
-    return (f.boxes[0], f.status[0], f.aux[0]) + ((stats,) if filter else ())
-
-
-def _fit_common(depth, K, H, W, B, ground, sample_idx, image_index, dev, what):
-    d = _as_dev(depth, torch.float32, dev)
-    if d.dim() == 2:
-        d = d[None]
-    if d.shape[1:] != (H, W):
-        raise ValueError(f"depth planes {tuple(d.shape[1:])} do not match the {what} frame {(H, W)}")
-    k = _as_dev(K, torch.float64, dev, cache=True)
-    if k.dim() == 2:
-        k = k[None]
-    P = d.shape[0]
-    if k.shape[0] == 1 and P > 1:
-        k = k.expand(P, 3, 3).contiguous()
-    ii = None if image_index is None else _as_dev(image_index, torch.int32, dev)
-    if ii is None and P not in (1, B):
-        raise ValueError("without image_index, depth must have 1 or B planes")
-    g = None if ground is None else _as_dev(ground, torch.float64, dev)
-    si = None if sample_idx is None else _as_dev(sample_idx, torch.int32, dev)
-    return d, k, P, ii, g, si
+    r = fit_instances_ex(depth, K, polys=polys, ground=ground, sample_idx=sample_idx, image_index=image_index, filter=filter,
+                         stream=stream, device=device)
+    return (r["boxes"], r["status"], r["aux"]) + ((r["stats"],) if filter else ())
 
 
 def fit_instances_rle(depth, rles, K, ground=None, sample_idx=None, image_index=None, stream=None, device=None, filter=None):
@@ -723,39 +601,9 @@ def fit_instances_rle(depth, rles, K, ground=None, sample_idx=None, image_index=
     bit image.  Arguments and returns as ``labelany3d_amd.fit_instances``; ``rles`` is a list of COCO RLE
     objects or the tuple from ``pack_rle``.  ``filter``: as in ``fit_instances_poly`` (RLE branch of the rule: height = rows
     holding a pixel, src/util.py:368-369)."""
-    counts, offsets, H, W = pack_rle(rles)
-    dev = _dev(device)
-    if W % 32 != 0:   # (as in fit_instances_poly)
-        r = fit_instances_ex(depth, K, rles=(counts, offsets, H, W), ground=ground, sample_idx=sample_idx, image_index=image_index,
-                             filter=filter, stream=stream, device=dev)
-        return (r["boxes"], r["status"], r["aux"]) + ((r["stats"],) if filter else ())
-    counts, offsets, ground, image_index, sample_idx = _bulk(dev, (counts, torch.int32), (offsets, torch.int64), (ground, torch.float64),
-                                                             (image_index, torch.int32), (sample_idx, torch.int32))
-    c, o = _as_dev(counts, torch.int32, dev), _as_dev(offsets, torch.int64, dev)
-    B = o.numel() - 1
-    d, k, P, ii, g, si = _fit_common(depth, K, H, W, B, ground, sample_idx, image_index, dev, "RLE")
-    stats = None
-    with torch.cuda.device(dev):
-        f = InstanceFitter(B, H, W, dev)
-        if filter:
-            stats = torch.zeros((B, 4), dtype=torch.int32, device=dev)
-        if B == 0:
-            return (f.boxes[0], f.status[0], f.aux[0]) + ((stats,) if filter else ())
-        opts = options.codes()
-        if any(opts):
-            rc = _fit_block(f, d, P, ii, k, g, si, B, H, W, stream, _filter_args(filter) if filter else None, stats, opts, rle=(c, o))
-        elif filter:
-            b, a, e = _filter_args(filter)
-            rc = lib.la3d_fit_instances_rle_filtered(_ptr(d), H * W if P > 1 else 0, _ptr(ii), _ptr(c), _ptr(o), _ptr(k),
-                                                     9 if k.shape[0] > 1 else 0, _ptr(g), _ptr(si), B, H, W, b, a, e, _ptr(f.boxes[0]),
-                                                     _ptr(f.status[0]), _ptr(f.aux[0]), _ptr(stats), _ptr(f.workspace[0]), _stream(stream))
-        else:
-            rc = lib.la3d_fit_instances_rle(_ptr(d), H * W if P > 1 else 0, _ptr(ii), _ptr(c), _ptr(o), _ptr(k),
-                                            9 if k.shape[0] > 1 else 0, _ptr(g), _ptr(si), B, H, W, _ptr(f.boxes[0]),
-                                            _ptr(f.status[0]), _ptr(f.aux[0]), _ptr(f.workspace[0]), _stream(stream))
-        check(rc, "la3d_fit_instances_rle")
-    _record(stream, d, k, ii, g, si, c, o, stats, f.workspace, f.boxes, f.status, f.aux)
-    return (f.boxes[0], f.status[0], f.aux[0]) + ((stats,) if filter else ())
+    r = fit_instances_ex(depth, K, rles=rles, ground=ground, sample_idx=sample_idx, image_index=image_index, filter=filter,
+                         stream=stream, device=device)
+    return (r["boxes"], r["status"], r["aux"]) + ((r["stats"],) if filter else ())
 
 
 def masked_ratio_median(depth_map, depth_render, mask, render_mask=None, image_index=None, stream=None):
