@@ -1,0 +1,112 @@
+"""GPU slices of the differential campaigns (oracle/campaigns/, driven at scale by profiles/r06/fuzz_*.py): fixed seed lists
+(tests/campaign_slices.py) through the campaigns' own GPU runners and checkers, against the CPU oracle computed here, serially.
+
+  engines       every entry of RUNS (default dispatch, every pinned engine, both two-pass builds, launch order off) and ANN_RUNS (run
+                lengths, polygons, la3d_fit_instances_ex with the 2-D box epilogue, an area hint and the fused filter) for 45 regular
+                and 40 tiny-frame cases
+  points        both yaw methods, every launch form of RUNS and the scalar drop-in, 40 cases
+  annotations   fit_annotations (GPU-resident and through the host entry) and fit_annotations_all with three filters, 40 images
+  aux           unproject, decoders, mask statistics, filters, consumers, depth statistics, matcher, 40 cases
+A case fails with the campaign's own message, which names its seed."""
+import numpy as np
+import pytest
+
+from oracle.campaigns import annotations as A
+from oracle.campaigns import aux as X
+from oracle.campaigns import engines as E
+from oracle.campaigns import points as PT
+from tests import campaign_slices as S
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    import torch
+
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import labelany3d_amd  # noqa: F401
+
+
+def _groups(seeds, n):
+    return [seeds[i:i + n] for i in range(0, len(seeds), n)]
+
+
+def _report(fails):
+    return f"{len(fails)} failures:\n" + "\n".join(fails[:20])
+
+
+@pytest.mark.parametrize("tiny,seeds", [(False, g) for g in _groups(S.ENGINE_SEEDS, 5)] + [(True, g) for g in _groups(S.ENGINE_TINY_SEEDS, 10)],
+                         ids=lambda v: str(v[0]) if isinstance(v, list) else ("tiny" if v else "regular"))
+def test_engine_campaign_slice(gpu, tiny, seeds):
+    fails = []
+    for s in seeds:
+        c = E.make_case(s, tiny)
+        ref = E.oracle_case(s, tiny)[1:]
+        cache = {}
+        for r in E.RUNS + E.ANN_RUNS:
+            if not E.applies(c, r):
+                continue
+            try:
+                got = E.run_gpu(c, r, cache)
+            except Exception as e:   # noqa: BLE001 - every failure of the slice is reported, not only the first
+                if not E.documented_refusal(c, r, e):
+                    fails.append(f"seed {s} {r}: call failed: {e!r}")
+                continue
+            fails += [f"seed {s} {r}: {m}" for m in E.check_run(c, ref, r, got)]
+    assert not fails, _report(fails)
+
+
+@pytest.mark.parametrize("seeds", _groups(S.POINT_SEEDS, 10), ids=lambda v: str(v[0]))
+def test_point_campaign_slice(gpu, seeds):
+    fails = []
+    for s in seeds:
+        c = PT.make_case(s)
+        ref = PT.oracle_case(s)[1]
+        for method in PT.METHODS:
+            for r in PT.runs_for(method):
+                try:
+                    got = PT.run_gpu(c, method, r)
+                except Exception as e:   # noqa: BLE001
+                    fails.append(f"seed {s} {method} {r}: call failed: {e!r}"); continue
+                fails += [f"seed {s} {method} {r}: {m}" for m in PT.check_run(c, ref[method], method, r, got)]
+            for n in PT.scalar_clouds(c):
+                got = PT.run_scalar(c, method, n, ref[method][1][n])
+                fails += [f"seed {s} cloud {n} scalar drop-in {method}: {m}" for m in PT.check_scalar(c, ref[method], method, n, got)]
+    assert not fails, _report(fails)
+
+
+@pytest.mark.parametrize("seeds", _groups(S.ANNOTATION_SEEDS, 10), ids=lambda v: str(v[0]))
+def test_annotation_campaign_slice(gpu, seeds):
+    fails = []
+    for s in seeds:
+        c = A.make_case(s)
+        ref = A.oracle_case(s)[1]
+        for call in A.CALLS:
+            try:
+                got = A.run_gpu(c, call)
+            except Exception as e:   # noqa: BLE001
+                fails.append(f"{A.call_tag(c, call)}: raised {e!r}"); continue
+            fails += [f"{A.call_tag(c, call)}: {m}" for m in A.check_call(c, ref, call, got)]
+    assert not fails, _report(fails)
+
+
+@pytest.mark.parametrize("seeds", _groups(S.AUX_SEEDS, 10), ids=lambda v: str(v[0]))
+def test_aux_campaign_slice(gpu, seeds):
+    fails = []
+    for s in seeds:
+        c = X.make_case(s)
+        fails += [f"seed {s} {c['H']}x{c['W']}: {m}" for m in X.check(c, X.expected(c), X.run_gpu(c))]
+    assert not fails, _report(fails)
+
+
+def test_engine_slice_reaches_the_documented_refusal(gpu):
+    """The slice's frame above 1 Mpx is refused loudly in annotation mode (include/la3d.h) - and fitted in full through the u8 entry."""
+    s = next(s for s in S.ENGINE_SEEDS if np.prod(E.make_case(s)["masks"].shape[1:]) > 1 << 20)
+    c = E.make_case(s)
+    with pytest.raises(Exception, match="bit image in LDS") as e:
+        E.run_gpu(c, dict(entry="rle"))
+    assert E.documented_refusal(c, dict(entry="rle"), e.value)
+    if c["sidx"] is None:
+        assert not E.check_run(c, E.oracle_case(s)[1:], {}, E.run_gpu(c, {}))
