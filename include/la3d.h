@@ -101,14 +101,23 @@ int la3d_pad_rows(const float* src, int64_t rows, int W, int Wp, float* dst, voi
  * LA3D_* environment variables the measurement scripts use (LA3D_ENGINE, LA3D_BALANCE, LA3D_BUILD, ...) are read ONCE, at
  * the first call, into an immutable table of process defaults; they never change records, only speed.
  * (ABI 2: la3d_set_launch_order / la3d_get_launch_order of ABI 1 - a process-wide switch - are gone; use opt_launch_order.) */
+/* Which engine fits a call: the engines are tried in the order rows -> band -> split -> instance, each where it applies and - by
+ * default - up to its batch limit (160 instances each; LA3D_ROWS_MAXB moves the row engine's).  A pinned engine starts the walk at
+ * itself and has no batch limit; where it does not apply the walk goes on to the engines after it, under their own limits - a
+ * pinned rows engine may give way to the band engine, a pinned band engine to the split engine -, and the instance engine takes
+ * what is left.  A call
+ * without a ground array on a frame the single pass covers that the row engine does not take goes to the instance engine unless
+ * band or split is pinned. */
 #define LA3D_ENGINE_DEFAULT 0
-#define LA3D_ENGINE_INSTANCE 1        /* one workgroup per instance */
-#define LA3D_ENGINE_SPLIT 2           /* band scan + tile-range-balanced passes (falls back to the instance engine where it does not apply) */
-#define LA3D_ENGINE_BAND 3            /* two, four or eight workgroups per instance, one per band of tile rows (u8 planes, tiled frames; falls back likewise) */
-#define LA3D_ENGINE_ROWS 4            /* up to sixteen workgroups per instance, one per band of rows (u8 planes, no ground array; falls
-                                         back likewise).  Taken by default for batches of up to 160 instances (LA3D_ROWS_MAXB), and up to
-                                         512 when pinned.  Round 6: ONE launch - the band that finishes last merges its instance's partial
-                                         sums and writes the record */
+#define LA3D_ENGINE_INSTANCE 1        /* one workgroup per instance: takes every call */
+#define LA3D_ENGINE_SPLIT 2           /* band scan + tile-range-balanced passes (16-byte aligned, word-aligned rows, no subsample mode, no
+                                         padded rows; run-length / polygon masks without the fused filter) */
+#define LA3D_ENGINE_BAND 3            /* two, four or eight workgroups per instance, one per band of tile rows (u8 planes, tiled frames, no
+                                         subsample mode) */
+#define LA3D_ENGINE_ROWS 4            /* up to sixteen workgroups per instance, one per band of rows (u8 planes, no ground array, the
+                                         default build, no subsample mode).  Taken by default for batches of up to 160 instances
+                                         (LA3D_ROWS_MAXB), and up to 512 when pinned.  Round 6: ONE launch - the band that finishes last
+                                         merges its instance's partial sums and writes the record */
 #define LA3D_ENGINE_ROWS2 5           /* the row engine in its round-5 form: the partial sums merged by a second short launch (what a call
                                          captured into a HIP graph takes anyway) */
 #define LA3D_ORDER_DEFAULT 0          /* size-balanced launch order for 256 < B <= 3 resident sets; the sort keys are estimated inside the

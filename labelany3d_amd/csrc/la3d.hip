@@ -17,8 +17,8 @@
 //   la3d_points.hip     explicit point clouds (la3d_fit_points) and the host-pointer single calls
 //   la3d_masks.hip      whole-frame depth_to_points, mask decode / statistics;  la3d_consumers.hip  box consumers, depth statistics, matcher geometry
 //   la3d_json.cpp       the host-side writer of 3dbbox.json + the build identity
-// This file: the process defaults read once from the environment (config), workspace sizing, argument checks, and which engine
-// fits a call (fit_dispatch; profiles/r06/r06_engines_by_batch.txt has the row in which each engine is the fastest).
+// This file: the process defaults read once from the environment (config), workspace sizing, argument checks (fit_dispatch), and
+// which engine fits a call (choose_engine; profiles/r06/r06_engines_by_batch.txt has the row in which each engine is the fastest).
 #include <atomic>
 #include <chrono>
 #include <cstdint>
@@ -34,6 +34,57 @@
 
 namespace la3d {
 thread_local char g_err[256] = "";
+
+// ==========================================================================================
+// Which engine fits a call.  Each engine says which calls its kernels can take (*_applies, la3d_engines.hpp); the batch
+// limits below and the pins are applied here only.
+// ==========================================================================================
+// Row engine: by default batches of up to LA3D_ROWS_MAXB = ROWS_MAXB instances (0: never).  Small batches of u8 planes without a
+// ground array: the single pass split over up to sixteen workgroups per instance, one per band of rows (B = 1 / 16 / 64 / 128:
+// 18.2 / 19.3 / 24.0 / 30.0 us per call, profiles/r05/r05_rows_engine.txt); above, one workgroup per instance is as fast (round 6,
+// us per call, instance | rows: B = 128: 37.1 | 30.3; 192: 39.8 | 41.1 - profiles/r06/r06_rows_engine.txt).
+constexpr int ROWS_MAXB = 160;
+// Band engine: by default the calls of 1 <= B <= BAND_MAXB instances (B >= 1 always holds here: a call of B = 0 returns before).
+// Round 6: eight bands per instance put it ahead of the split engine from one instance on - B = 1 / 16 / 64: 23 / 28 / 34 us vs
+// 32 / 36 / 43 (rounds 4-5 it took batches from 16 instances on) -, and above ~160 one workgroup per instance is as fast or
+// faster: B = 192: 57 vs 54 us.  History - round 4, us per call, split | four bands once the band launch lost its memset: B = 1:
+// 32.2 | 32.3; 16: 34.9 | 33.9; 64: 42.1 | 36.6; instance | two | four bands: B = 256: 59.7 | 58.6 | 60.0; 384: 63.4 | 66.2 | 78.1.
+constexpr int BAND_MAXB = 160;
+// Split engine: by default batches of up to SPLIT_MAXB instances, for every mask format.  Measured on MI355X, round 3 (BASELINE
+// config-2 inputs, us per call, split vs one workgroup per instance; profiles/r03/r03_small_batches.txt): u8 planes B = 1 / 16 / 64 /
+// 128 / 192 / 272 / 288 / 304 / 336: 34 / 37 / 45 / 50 / 58 / 70 / 74 / 76 / 81 vs 40 / 52 / 57 / 58 / 62 / 75 / 72 / 71 / 76; run
+// lengths B = 1 / 16 / 64 / 160 / 256 / 288 / 304: 36 / 40 / 46 / 53 / 59 / 65 / 66 vs 47 / 57 / 59 / 66 / 64 / 66 / 65 (polygons
+// ~1 us below both).  A lone 60-90 k-px instance keeps ONE CU's fp64 VALU busy for ~40 us in the instance engine; the split engine
+// spreads its tiles over the chip at the price of six dependent launches.  Round 6: the crossover with the instance engine for
+// grounded run lengths, split | instance: B = 128: 48 | 53, 192: 52.6 | 51.2, 256: 58 | 51; u8 planes up to 160 instances only
+// (where the band engine does not apply: it is the faster one there) - grounded u8, split | instance: B = 192: 56.8 | 54.2, 256:
+// 66.7 | 56.9 (profiles/r06/r06_engines_by_batch.txt).
+constexpr int SPLIT_MAXB = 160;
+
+// The engines are tried in the order rows -> band -> split -> instance.  pin (opt_engine, else LA3D_ENGINE) starts the walk at the
+// pinned engine (rows2 counts as rows) and lifts that engine's batch limit; the instance engine takes every call.
+//
+// Round 5: a call WITHOUT a ground array on a frame the one-pass tile list covers, that the row engine does not take, takes the
+// instance engine at EVERY batch size - its separable single pass (no pass B, no cull plan: a chain of three short phases per
+// workgroup) is faster than the chain of six launches of the split engine and than the band engine's exchange from B = 1 on, for
+// all three mask formats (profiles/r05/r05_small_batches.txt: B = 1 / 16 / 64 / 256, u8 planes: 27.7 / 32.1 / 36.8 / 45.1 us vs
+// 31.7 / 34.8 / 37.9 / 59.8; run lengths 31.2 / 35.6 / 36.4 / 40.0 vs 34.3 / 37.9 / 43.3 / 57.4).  A skewed K (not separable) still
+// takes this route - the kernel then runs its two passes -; a call WITH a ground array goes on to the band and split engines (two
+// passes either way).  This shortcut belongs to the walk from rows: a pinned band or split engine skips it.
+static int choose_engine(const FitParams& p, const CallFacts& f, int pin) {
+  const int B = p.B, H = p.H, W = p.W;
+  if (pin == LA3D_ENGINE_DEFAULT || pin == LA3D_ENGINE_ROWS || pin == LA3D_ENGINE_ROWS2) {
+    if (rows_applies(p, f) && (pin != LA3D_ENGINE_DEFAULT || B <= config().rows_maxb)) return LA3D_ENGINE_ROWS;
+    const bool single_pass_call = p.ground == nullptr && !f.sample && !p.sep_off && f.ldsmask && f.vec && W % 32 == 0 && W / 32 <= 255 &&
+                                  (H + 7) / 8 <= 255 && ((W / 32) * ((H + 7) / 8) + NWAVE - 1) / NWAVE <= 256;
+    if (single_pass_call) return LA3D_ENGINE_INSTANCE;
+  }
+  if (pin == LA3D_ENGINE_INSTANCE) return LA3D_ENGINE_INSTANCE;
+  if (pin != LA3D_ENGINE_SPLIT && band_applies(p, f) && (pin == LA3D_ENGINE_BAND || B <= BAND_MAXB)) return LA3D_ENGINE_BAND;
+  if (split_applies(p, f) && (pin == LA3D_ENGINE_SPLIT || B <= SPLIT_MAXB)) return LA3D_ENGINE_SPLIT;
+  return LA3D_ENGINE_INSTANCE;
+}
+
 // the ONE place that reads the environment: a function-local static, initialised once (thread-safe since C++11)
 const Config& config() {
   static const Config c = [] {
@@ -44,25 +95,14 @@ const Config& config() {
              : (e && !strcmp(e, "rows2")) ? LA3D_ENGINE_ROWS2 : LA3D_ENGINE_DEFAULT;
     e = getenv("LA3D_BANDS");
     k.bands = (e && (atoi(e) == 8 || atoi(e) == 4 || atoi(e) == 2)) ? atoi(e) : 0;
-    e = getenv("LA3D_BAND_DEFAULT");      // 0: the band engine only when asked for (LA3D_ENGINE=band / opt_engine)
-    k.band_default = !(e && e[0] == '0');
-    e = getenv("LA3D_BAND_MAXB");
-    k.band_maxb = (e && atoi(e) > 0) ? atoi(e) : 160;
     e = getenv("LA3D_ROWS_MAXB");
-    k.rows_maxb = e ? atoi(e) : 160;   // largest batch the row engine takes by default (0: never); above, one workgroup per instance is as fast
-                                       // (round 6, us per call, instance | rows: B = 128: 37.1 | 30.3; 192: 39.8 | 41.1 - profiles/r06/r06_rows_engine.txt)
-    e = getenv("LA3D_ROWS_FUSED");        // 0: the two-launch form of the row engine (fit_rows_kernel + merge_rows_kernel)
-    k.rows_fused = !(e && e[0] == '0');
+    k.rows_maxb = e ? atoi(e) : ROWS_MAXB;
     e = getenv("LA3D_ROWS_WGS");          // workgroups the row engine spreads a batch over, at most
     k.rows_wgs = (e && atoi(e) > 0) ? atoi(e) : 640;
     e = getenv("LA3D_BALANCE");
     k.balance = !(e && e[0] == '0');
-    e = getenv("LA3D_BALANCE_ROUNDS");
-    k.balance_rounds = (e && atoi(e) > 0) ? atoi(e) : 3;
-    e = getenv("LA3D_BUILD");             // plain | nocull -> LA3D_BUILD_PLAIN / LA3D_BUILD_NOCULL for every call (LA3D_RETAIN=0 / 1: the old spelling)
+    e = getenv("LA3D_BUILD");             // plain | nocull -> LA3D_BUILD_PLAIN / LA3D_BUILD_NOCULL for every call
     k.build = (e && !strcmp(e, "plain")) ? LA3D_BUILD_PLAIN : (e && !strcmp(e, "nocull")) ? LA3D_BUILD_NOCULL : LA3D_BUILD_DEFAULT;
-    e = getenv("LA3D_RETAIN");
-    if (e && k.build == LA3D_BUILD_DEFAULT) k.build = atoi(e) > 0 ? LA3D_BUILD_NOCULL : LA3D_BUILD_PLAIN;
     e = getenv("LA3D_CULL_MIN");          // pass-B culling threshold (active tiles) for every input; unset: 224, u8 planes LA3D_CULL_MIN_U8
     k.cull_min = e ? atoi(e) : 0;
     e = getenv("LA3D_CULL_MIN_U8");
@@ -71,12 +111,6 @@ const Config& config() {
     k.order_self = e ? atoi(e) : 1;
     e = getenv("LA3D_STAGGER_US");
     k.stagger_us = e ? atof(e) : -1.0;
-    e = getenv("LA3D_STAGGER_NOMASK_US");   // run-length / polygon input: stagger period of the resident groups (0 / unset: none)
-    k.stagger_nomask_us = e ? atof(e) : 0.0;
-    e = getenv("LA3D_SPLIT_GRID");
-    k.split_grid = (e && atoi(e) > 0) ? atoi(e) : 0;
-    e = getenv("LA3D_SPLIT_SUB");
-    k.split_sub = (e && atoi(e) > 0) ? atoi(e) : 0;
     e = getenv("LA3D_BAND_TEST");
     k.band_test = e ? atoi(e) : 0;
     e = getenv("LA3D_SEP");               // 0: no separable single pass (the two-pass plain build everywhere)
@@ -176,44 +210,35 @@ static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who)
     p.filter_stats = a.stats;
   }
   const int bit_bytes = ((((p.HW + 15) / 16 + 1) / 2) * 4 + 15) & ~15;  // u16 per 16 px, padded to u32, 16-aligned
-  const bool ldsmask = bit_bytes <= MAX_MASK_LDS;
-  p.mask_lds_bytes = ldsmask ? bit_bytes : 0;
-  if (rle && !ldsmask) {
+  CallFacts f;
+  f.ldsmask = bit_bytes <= MAX_MASK_LDS;
+  p.mask_lds_bytes = f.ldsmask ? bit_bytes : 0;
+  if (rle && !f.ldsmask) {
     snprintf(g_err, sizeof(g_err), "%s: run-length / polygon masks need the bit image in LDS (H*W <= 1048576)", who);
     return LA3D_ERR_UNSUPPORTED;
   }
   // 16-byte vector path: every plane base 16-aligned (the u8 mask only when it is read at all)
-  const bool vec = (p.HW % 16 == 0) && (rle || (reinterpret_cast<uintptr_t>(a.mask) & 15) == 0) &&
-                   ((reinterpret_cast<uintptr_t>(a.depth) & 15) == 0) && (a.depth_plane_stride % 4 == 0);
-  const bool sample = a.sample_idx != nullptr;
-  size_t lds = (size_t)p.mask_lds_bytes + sizeof(Shared);
+  f.vec = (p.HW % 16 == 0) && (rle || (reinterpret_cast<uintptr_t>(a.mask) & 15) == 0) &&
+          ((reinterpret_cast<uintptr_t>(a.depth) & 15) == 0) && (a.depth_plane_stride % 4 == 0);
+  f.sample = a.sample_idx != nullptr;
+  f.lds = (size_t)p.mask_lds_bytes + sizeof(Shared);
   // polygons: the side stage sits behind Shared, where the tile list / rank prefix go later (disjoint in time)
-  const size_t poly_stage = a.poly_xy ? (size_t)POLY_STAGE_BYTES : 0;
+  f.poly_stage = a.poly_xy ? (size_t)POLY_STAGE_BYTES : 0;
+  const int pin = a.opt_engine != LA3D_ENGINE_DEFAULT ? a.opt_engine : config().engine;   // per-call pin, else the process default
   hipStream_t s = static_cast<hipStream_t>(a.stream);
-  // Round 5: a call WITHOUT a ground array on a frame the one-pass tile list covers takes the instance engine at EVERY batch size - its
-  // separable single pass (no pass B, no cull plan: a chain of three short phases per workgroup) is faster than the chain of six
-  // launches of the split engine and than the band engine's exchange from B = 1 on, for all three mask formats
-  // (profiles/r05/r05_small_batches.txt: B = 1 / 16 / 64 / 256, u8 planes: 27.7 / 32.1 / 36.8 / 45.1 us vs 31.7 / 34.8 / 37.9 / 59.8;
-  // run lengths 31.2 / 35.6 / 36.4 / 40.0 vs 34.3 / 37.9 / 43.3 / 57.4).  A skewed K (not separable) still takes this route - the
-  // kernel then runs its two passes -; a call WITH a ground array keeps the old choice below (two passes either way).
-  // Small batches of u8 planes (up to config().rows_maxb = 160 instances by default) go one step further: the same single pass split
-  // over up to sixteen workgroups per instance, one per band of rows, and a short merge launch (row engine: B = 1 / 16 / 64 / 128
-  // 18.2 / 19.3 / 24.0 / 30.0 us per call, profiles/r05/r05_rows_engine.txt).
-  const int eng = p.opt_engine != LA3D_ENGINE_DEFAULT ? p.opt_engine : config().engine;
-  const bool single_pass_call = a.ground == nullptr && !sample && !p.sep_off && ldsmask && vec && W % 32 == 0 && W / 32 <= 255 &&
-                                (H + 7) / 8 <= 255 && ((W / 32) * ((H + 7) / 8) + NWAVE - 1) / NWAVE <= 256 &&
-                                (eng == LA3D_ENGINE_DEFAULT || eng == LA3D_ENGINE_ROWS || eng == LA3D_ENGINE_ROWS2);   // (rows pinned but not applicable: as by default)
-  {
-    int rc = LA3D_SUCCESS;
-    if (rows_fit_if_eligible(p, vec, sample, s, a.workspace, &rc)) return rc;
-  }
-  if (!single_pass_call && band_eligible(p, vec, sample)) return band_fit(p, s, a.workspace);   // grounded u8 planes, 1 <= B <= 160 (or pinned): two / four / eight workgroups per instance, ONE launch
-  if (!single_pass_call && !sample && p.frame_w == W && split_eligible(p, vec, ldsmask)) {   // (the split engine's decoders know no padded rows)
+  switch (choose_engine(p, f, pin)) {
+  case LA3D_ENGINE_ROWS:   // (two launches when pinned so, and for a call captured into a HIP graph: it would replay with the same tag)
+    return rows_fit(p, pin == LA3D_ENGINE_ROWS2 || stream_capturing(s), s, a.workspace);
+  case LA3D_ENGINE_BAND:
+    return band_fit(p, s, a.workspace);
+  case LA3D_ENGINE_SPLIT: {
     const int rc = split_fit(p, a.workspace, s);   // (the split engine's final kernel does not project: one small follow-up launch)
     if (rc != LA3D_SUCCESS || !p.proj) return rc;
     return la3d_project_boxes(a.out, a.K, a.k_stride, a.image_index, B, p.proj_w, p.proj_h, p.proj, a.stream);   // (la3d_consumers.hip)
   }
-  return instance_fit(p, vec, ldsmask, sample, lds, poly_stage, s, a.workspace, who);
+  default:
+    return instance_fit(p, f, s, a.workspace, who);
+  }
 }
 
 // The entries of ABI 1 fill a zeroed block (no filter, no options) and keep their own checks and error texts.

@@ -465,8 +465,6 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_bands_kernel(const FitParams 
 
 // ---- band engine (fit_bands_kernel) ----
 constexpr int BAND_NB_MAX = 8;
-constexpr int BAND_MINB = 1;    // smallest batch the band engine takes by default (round 6: with eight bands per instance it leads from one
-                                // instance on - 23 vs 32 us through the split engine; rounds 4-5: 16)
 constexpr size_t band_xch_doubles(int nb) { return (size_t)nb * (2 * BAND_XD + 6); }
 
 // workspace of the band engine: [B] u32 sort keys | [B][4] u64 tagged arrival words | [B][NB_MAX * 22] f64 exchange records
@@ -494,19 +492,6 @@ inline int band_count(const FitParams& p) {
   return nb;
 }
 
-// u8 planes, 16-byte aligned, full-mask mode.  By default the band engine takes the GROUNDED calls of 1 <= B <= 160 instances (round
-// 6: eight bands per instance put it ahead of the split engine from one instance on - B = 1 / 16 / 64: 23 / 28 / 34 us vs 32 / 36 / 43 -,
-// and above ~160 one workgroup per instance is as fast or faster: B = 192: 57 vs 54 us).  History - round 4, us per call, split | four
-// bands once the band launch lost its memset: B = 1: 32.2 | 32.3; 16: 34.9 | 33.9; 64: 42.1 | 36.6; instance | two | four bands:
-// B = 256: 59.7 | 58.6 | 60.0; 384: 63.4 | 66.2 | 78.1.  LA3D_ENGINE=band / opt_engine pins it for any batch, LA3D_BAND_MAXB moves the limit.
-inline bool band_eligible_impl(const FitParams& p, bool vec, bool sample) {
-  const int e = p.opt_engine != LA3D_ENGINE_DEFAULT ? p.opt_engine : config().engine;
-  if (e == LA3D_ENGINE_INSTANCE || e == LA3D_ENGINE_SPLIT) return false;
-  if (!vec || sample || p.mask == nullptr || !band_frame_ok_impl(p.H, p.W, band_count(p))) return false;
-  if (e == LA3D_ENGINE_BAND) return true;
-  return config().band_default && p.B >= BAND_MINB && p.B <= config().band_maxb;
-}
-
 template <int NB>
 int launch_fit_bands(const FitParams& p_in, hipStream_t s, void* workspace) {
   FitParams p = p_in;
@@ -530,37 +515,21 @@ int launch_fit_bands(const FitParams& p_in, hipStream_t s, void* workspace) {
   unsigned* keys = reinterpret_cast<unsigned*>(w);
   p.band_arrive = reinterpret_cast<unsigned long long*>(w + band_keys_bytes(p.B));
   p.band_xch = reinterpret_cast<double*>(w + band_keys_bytes(p.B) + (size_t)p.B * 32);
-  {
-    const unsigned long long t = (unsigned long long)std::chrono::steady_clock::now().time_since_epoch().count();
-    p.band_tag = (((t * 0x9E3779B97F4A7C15ull) >> 13) ^ (unsigned long long)reinterpret_cast<uintptr_t>(workspace)) & 0xffffffffffffull;
-    if (p.band_tag == 0) p.band_tag = 1;   // (zeroed words - a captured call's memset - never look like this call's)
-  }
-  p.order_nch = 0; p.order_keys = nullptr; p.order_resident = 0; p.order_shift = 0;
-  p.order_self = 0; p.order_flags = nullptr; p.order_nonce = 0; p.est_step = 1;
-  if (p.B > 256 && p.B <= ORDER_MAX_B && balance_enabled(p) && p.B <= balance_max_rounds() * 4 * 256) {
+  p.band_tag = call_tag(workspace);
+  if (p.B > 256 && p.B <= ORDER_MAX_B && balance_enabled(p) && p.B <= BALANCE_MAX_ROUNDS * 4 * 256) {
     // largest instances first (chunk-local ranking as in the instance engine; no per-CU pairing: an instance's bands sit on NB CUs)
     p.order_nch = (p.B + ORDER_CHUNK - 1) / ORDER_CHUNK;
+    const OrderKeyScale k = order_key_scale(p);
     if (p.area_hint) {
-      while (((long long)p.HW >> p.order_shift) > 0x3ffff) ++p.order_shift;
+      p.order_shift = k.shift;
     } else {
-      int step = 1;
-      for (int cand : {EST_STEP, 31, 17, 7, 3})
-        if ((p.HW >> 7) / cand >= 64) { step = cand; break; }
-      const long long amax = (long long)p.HW / step + 128;
-      int shift = 0;
-      while ((amax >> shift) > 0x3ffff) ++shift;
       hipLaunchKernelGGL(size_estimate_kernel, dim3((p.B + 3) / 4), dim3(256), 0, s, p.mask, nullptr, nullptr, nullptr, nullptr, nullptr,
-                         p.B, p.HW, step, shift, keys, nullptr);
+                         p.B, p.HW, k.step, k.shift, keys, nullptr);
       p.order_keys = keys;
     }
   }
-  {
-    // a call captured into a HIP graph replays with the same tag: its arrival words are cleared by a memset node of the graph
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
-    (void)hipGetLastError();
-    if (capturing && hipMemsetAsync(p.band_arrive, 0, (size_t)p.B * 32, s) != hipSuccess) return check_launch("band engine memset");
-  }
+  // a call captured into a HIP graph replays with the same tag: its arrival words are cleared by a memset node of the graph
+  if (stream_capturing(s) && hipMemsetAsync(p.band_arrive, 0, (size_t)p.B * 32, s) != hipSuccess) return check_launch("band engine memset");
   const int grid = ((p.B + 7) / 8) * 8 * NB;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), region + fixed, s, p);
   return check_launch("fit_bands_kernel");
@@ -569,7 +538,10 @@ int launch_fit_bands(const FitParams& p_in, hipStream_t s, void* workspace) {
 }  // namespace
 
 namespace la3d {
-bool band_eligible(const FitParams& p, bool vec, bool sample) { return ::band_eligible_impl(p, vec, sample); }
+// u8 planes, 16-byte aligned, full-mask mode, a frame the bands' one-pass tile lists cover
+bool band_applies(const FitParams& p, const CallFacts& f) {
+  return f.vec && !f.sample && p.mask != nullptr && ::band_frame_ok_impl(p.H, p.W, band_count(p));
+}
 bool band_frame_ok(int H, int W, int nb) { return ::band_frame_ok_impl(H, W, nb); }
 size_t band_workspace_bytes(int B) { return ::band_workspace_bytes_impl(B); }
 int band_fit(const FitParams& p, hipStream_t s, void* workspace) {

@@ -33,22 +33,15 @@ inline void set_err(const char* msg) { snprintf(g_err, sizeof(g_err), "%s", msg)
 // the hot path of the C-ABI never calls getenv.  Measurement scripts set the variables before the first call; a caller that
 // wants a different decision for one call uses la3d_fit_args::opt_*.  Speed only - records never depend on any of it.
 struct Config {
-  int engine;          // LA3D_ENGINE=instance|split|band -> LA3D_ENGINE_*
-  int bands;           // LA3D_BANDS=2|4 pins the workgroups per instance of the band engine (0: by batch size)
-  int band_default;    // LA3D_BAND_DEFAULT=0: the band engine only when pinned
-  int band_maxb;       // LA3D_BAND_MAXB: largest batch the band engine takes by default
-  int rows_maxb;       // LA3D_ROWS_MAXB: largest batch the row engine takes by default (u8 planes, no ground array)
-  int rows_fused;      // LA3D_ROWS_FUSED=0: the row engine in its two-launch form (a merge launch behind the band launch)
+  int engine;          // LA3D_ENGINE=instance|split|band|rows|rows2 -> LA3D_ENGINE_* (the pin of fit_dispatch, la3d.hip)
+  int bands;           // LA3D_BANDS=2|4|8 pins the workgroups per instance of the band engine (0: by batch size)
+  int rows_maxb;       // LA3D_ROWS_MAXB: largest batch the row engine takes by default (u8 planes, no ground array; default 160)
   int rows_wgs;        // LA3D_ROWS_WGS: workgroups the row engine spreads a batch over, at most (default 640)
   int balance;         // LA3D_BALANCE=0 -> launch order off by default
-  int balance_rounds;  // LA3D_BALANCE_ROUNDS: batches up to this many resident sets are ordered (default 3)
-  int build;           // LA3D_BUILD=plain|nocull (LA3D_RETAIN=0|1: the old spelling) -> LA3D_BUILD_PLAIN / LA3D_BUILD_NOCULL for every call
+  int build;           // LA3D_BUILD=plain|nocull -> LA3D_BUILD_PLAIN / LA3D_BUILD_NOCULL for every call
   int cull_min, cull_min_u8;   // LA3D_CULL_MIN (all inputs; 0: defaults), LA3D_CULL_MIN_U8 (u8 planes, default 128)
   int order_self;      // LA3D_ORDER_SELF=0: keep the estimate kernel in front of ordered launches of up to one resident set
   double stagger_us;   // LA3D_STAGGER_US (< 0: the computed default)
-  double stagger_nomask_us;   // LA3D_STAGGER_NOMASK_US: the same for run-length / polygon input (default 0: off)
-  int split_grid;      // LA3D_SPLIT_GRID (0: by batch size)
-  int split_sub;       // LA3D_SPLIT_SUB (0: by batch size)
   int sep;             // LA3D_SEP=0: the separable single pass off (two passes for every camera)
   int band_test;       // LA3D_BAND_TEST (tests only): 1 = band 1 of every third instance never arrives and the watchdog is short (the
                        // takeover path runs); 2 = blocks permuted so that the bands of an instance sit on different XCDs

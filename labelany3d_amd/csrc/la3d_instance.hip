@@ -609,53 +609,38 @@ int launch_fit_inst(const FitParams& p_in, size_t lds, hipStream_t s, void* work
   auto kern = fit_instances_kernel<VEC, LDSMASK, SAMPLE, TILED, SRC>;
   allow_big_lds(reinterpret_cast<const void*>(kern));
   FitParams p = p_in;
-  p.order_nch = 0; p.order_keys = nullptr; p.order_resident = 0; p.order_shift = 0;
-  p.order_self = 0; p.order_flags = nullptr; p.order_nonce = 0; p.est_step = 1;
   // size-balanced launch order: needs the 16-byte mask groups (VEC), more than one workgroup per CU, and a batch
   // the O(B^2) ranking is cheap for
   if (workspace && VEC && !SAMPLE && p.B > 256 && p.B <= ORDER_MAX_B && balance_enabled(p)) {
-    const int max_rounds = balance_max_rounds();
     int wg_per_cu = 2048 / NT;  // wave slots: 32 per CU at 64 VGPRs
     const int by_lds = (int)((160 * 1024) / (lds ? lds : 1));
     if (by_lds < wg_per_cu) wg_per_cu = by_lds;
-    if (wg_per_cu >= 1 && p.B <= max_rounds * wg_per_cu * 256) {
+    if (wg_per_cu >= 1 && p.B <= BALANCE_MAX_ROUNDS * wg_per_cu * 256) {
       p.order_nch = (p.B + ORDER_CHUNK - 1) / ORDER_CHUNK;
       p.order_resident = wg_per_cu * 256;
-      p.order_shift = 0;
-      p.order_keys = nullptr;
+      const OrderKeyScale k = order_key_scale(p);
       if (p.area_hint) {   // the caller knows the mask areas (annotation metadata, a preceding filter): no helper launch at all
-        while (((long long)p.HW >> p.order_shift) > 0x3ffff) ++p.order_shift;
+        p.order_shift = k.shift;
       } else {
         unsigned* est = static_cast<unsigned*>(workspace);  // [B] sort keys
-        // quantise the area to 18 bits: run lengths give the exact area (<= HW), the byte lattice about HW / 67
-        int step = 1;
-        for (int cand : {EST_STEP, 31, 17, 7, 3})
-          if ((p.HW >> 7) / cand >= 64) { step = cand; break; }
-        long long amax = (p.rle_counts || p.poly_xy) ? (long long)p.HW : (long long)p.HW / step + 128;
-        int shift = 0;
-        while ((amax >> shift) > 0x3ffff) ++shift;
         p.order_keys = est;
         bool self = config().order_self != 0 && wg_per_cu * 256 >= 256;
 #ifdef LA3D_TIMELINE
         self = false;   // (the stamp rows of the measurement build live where the nonces would)
 #endif
-        if (self) {
-          // a call captured into a HIP graph would replay with the SAME nonce: the records of the previous replay would read as
-          // complete while this replay's keys are still on their way - with new masks in the same buffers, two workgroups could rank
-          // with different keys.  Captured calls keep the helper kernel.
-          hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-          if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) self = false;
-          (void)hipGetLastError();
-        }
+        // a call captured into a HIP graph would replay with the SAME nonce: the records of the previous replay would read as
+        // complete while this replay's keys are still on their way - with new masks in the same buffers, two workgroups could rank
+        // with different keys.  Captured calls keep the helper kernel.
+        if (self && stream_capturing(s)) self = false;
         if (self) {
           // no helper launch: the fit kernel estimates in its prologue (estimate_publish); nonces behind the keys, 256-byte aligned
-          p.order_self = config().order_self; p.est_step = step; p.order_shift = shift;
+          p.order_self = config().order_self; p.est_step = k.step; p.order_shift = k.shift;
           p.order_flags = reinterpret_cast<unsigned long long*>(static_cast<unsigned char*>(workspace) + (((size_t)p.B * 4 + 255) & ~(size_t)255));
           const unsigned long long t = (unsigned long long)std::chrono::steady_clock::now().time_since_epoch().count();
           p.order_nonce = (t * 0x9E3779B97F4A7C15ull) ^ (unsigned long long)reinterpret_cast<uintptr_t>(workspace) ^ 0xA5A5A5A55A5A5A5Aull;
         } else {
           hipLaunchKernelGGL(size_estimate_kernel, dim3((p.B + 3) / 4), dim3(256), 0, s, p.mask, p.rle_counts, p.rle_offsets, p.poly_xy,
-                             p.poly_ring_off, p.poly_inst_rings, p.B, p.HW, step, shift, est, nullptr);
+                             p.poly_ring_off, p.poly_inst_rings, p.B, p.HW, k.step, k.shift, est, nullptr);
         }
       }
     }
@@ -676,11 +661,13 @@ int launch_fit(const FitParams& p, size_t lds, hipStream_t s, void* workspace = 
 }  // namespace
 
 namespace la3d {
-int instance_fit(FitParams p, bool vec, bool ldsmask, bool sample, size_t lds, size_t poly_stage, hipStream_t s, void* workspace,
-                 const char* who) {
+int instance_fit(FitParams p, const CallFacts& f, hipStream_t s, void* workspace, const char* who) {
   const int H = p.H, W = p.W, B = p.B;
+  const bool vec = f.vec, ldsmask = f.ldsmask;
+  const size_t poly_stage = f.poly_stage;
+  size_t lds = f.lds;
   const unsigned char* mask = p.mask;
-  if (sample) {
+  if (f.sample) {
     if (!ldsmask) {
       snprintf(g_err, sizeof(g_err), "%s: reference-subsample mode needs the bit image in LDS (H*W <= 1048576)", who);
       return LA3D_ERR_UNSUPPORTED;
@@ -739,7 +726,6 @@ int instance_fit(FitParams p, bool vec, bool ldsmask, bool sample, size_t lds, s
         if (config().stagger_us >= 0) us = config().stagger_us;
         p.stagger_ticks = (int)(us * 100.0);
       }
-      if (mask == nullptr && B > 256 && config().stagger_nomask_us > 0) p.stagger_ticks = (int)(config().stagger_nomask_us * 100.0);   // (experiment switch)
       return launch_fit<true, true, false, true>(p, fixed + ((size_t)cap * 2 > poly_stage ? (size_t)cap * 2 : poly_stage), s, workspace);
     }
   }

@@ -407,17 +407,7 @@ __global__ __launch_bounds__(NT, NT / 64) void merge_rows_kernel(const FitParams
   rows_merge<false>(sh, p, ra, inst, img, mcol, tid, wave, lane);
 }
 
-// u8 planes, 16-byte aligned, full-mask mode, no ground array, B <= ROWS_MAX_B: LA3D_ENGINE=rows / opt_engine pins it, by default
-// it takes the batches up to config().rows_maxb
-inline bool rows_eligible(const FitParams& p, bool vec, bool sample, RowsArgs* ra) {
-  const int e = p.opt_engine != LA3D_ENGINE_DEFAULT ? p.opt_engine : config().engine;
-  if (e != LA3D_ENGINE_DEFAULT && e != LA3D_ENGINE_ROWS && e != LA3D_ENGINE_ROWS2) return false;
-  if (!vec || sample || p.mask == nullptr || p.ground != nullptr || p.sep_off || p.filter_boundary >= 0) return false;
-  if (!rows_plan(p.B, p.H, p.W, ra)) return false;
-  return e == LA3D_ENGINE_ROWS || e == LA3D_ENGINE_ROWS2 || p.B <= config().rows_maxb;
-}
-
-int launch_fit_rows(const FitParams& p_in, RowsArgs ra, hipStream_t s, void* workspace) {
+int launch_fit_rows(const FitParams& p_in, RowsArgs ra, bool two_launch, hipStream_t s, void* workspace) {
   FitParams p = p_in;
   p.ntx = p.W / 32; p.nty = p.H / 8;
   p.rcp_ntx = 1.0f / (float)p.ntx;
@@ -427,26 +417,17 @@ int launch_fit_rows(const FitParams& p_in, RowsArgs ra, hipStream_t s, void* wor
   ra.part = reinterpret_cast<double*>(w);
   ra.col = reinterpret_cast<unsigned*>(w + part_bytes);
   // One launch (round 6): the last band to arrive merges its instance.  Two launches - fit_rows_kernel, then merge_rows_kernel -
-  // when pinned (LA3D_ENGINE_ROWS2 / LA3D_ROWS_FUSED=0) and for a call captured into a HIP graph (it would replay with the same tag).
-  const int e = p.opt_engine != LA3D_ENGINE_DEFAULT ? p.opt_engine : config().engine;
-  bool fused = e != LA3D_ENGINE_ROWS2 && config().rows_fused != 0;
-  if (fused) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) fused = false;
-    (void)hipGetLastError();
-  }
+  // when pinned (LA3D_ENGINE_ROWS2) and for a call captured into a HIP graph (it would replay with the same tag).
   ra.arrive = nullptr; ra.tag = 0;
-  if (fused) {
+  if (!two_launch) {
     ra.arrive = reinterpret_cast<unsigned long long*>(w + part_bytes + col_bytes);
-    const unsigned long long t = (unsigned long long)std::chrono::steady_clock::now().time_since_epoch().count();
-    ra.tag = (((t * 0x9E3779B97F4A7C15ull) >> 13) ^ (unsigned long long)reinterpret_cast<uintptr_t>(workspace)) & 0xffffffffffffull;
-    if (ra.tag == 0) ra.tag = 1;
+    ra.tag = call_tag(workspace);
   }
   const size_t lds = (size_t)ra.bits_bytes + sizeof(Shared) + (size_t)p.ntx * ra.trows * 2 + 16;
   allow_big_lds(reinterpret_cast<const void*>(fit_rows_kernel));
   hipLaunchKernelGGL(fit_rows_kernel, dim3(p.B * ra.nb), dim3(NT), lds, s, p, ra);
   const int rc = check_launch("fit_rows_kernel");
-  if (rc != LA3D_SUCCESS || fused) return rc;
+  if (rc != LA3D_SUCCESS || !two_launch) return rc;
   hipLaunchKernelGGL(merge_rows_kernel, dim3(p.B), dim3(NT), sizeof(Shared) + (size_t)2 * p.W * 4, s, p, ra);
   return check_launch("merge_rows_kernel");
 }
@@ -454,11 +435,16 @@ int launch_fit_rows(const FitParams& p_in, RowsArgs ra, hipStream_t s, void* wor
 }  // namespace
 
 namespace la3d {
-bool rows_fit_if_eligible(const FitParams& p, bool vec, bool sample, hipStream_t s, void* workspace, int* rc) {
+// u8 planes, 16-byte aligned, full-mask mode, no ground array, the default build (the separable single pass), a batch and frame
+// rows_plan can split
+bool rows_applies(const FitParams& p, const CallFacts& f) {
   RowsArgs ra;
-  if (!rows_eligible(p, vec, sample, &ra)) return false;
-  *rc = launch_fit_rows(p, ra, s, workspace);
-  return true;
+  return f.vec && !f.sample && p.mask != nullptr && p.ground == nullptr && !p.sep_off && p.filter_boundary < 0 && rows_plan(p.B, p.H, p.W, &ra);
+}
+int rows_fit(const FitParams& p, bool two_launch, hipStream_t s, void* workspace) {
+  RowsArgs ra;
+  if (!rows_plan(p.B, p.H, p.W, &ra)) return LA3D_ERR_UNSUPPORTED;   // (choose_engine takes the row engine only where rows_applies)
+  return launch_fit_rows(p, ra, two_launch, s, workspace);
 }
 size_t rows_workspace_bytes(int B, int H, int W) { return ::rows_workspace_bytes_impl(B, H, W); }
 }  // namespace la3d

@@ -29,6 +29,7 @@
 
 #include "la3d_device.hpp"
 #include "la3d_poly.hpp"
+#include "la3d_engines.hpp"
 
 namespace la3d {
 
@@ -189,9 +190,6 @@ __global__ __launch_bounds__(SNT) void scan_kernel(const SplitParams sp) {
 // dynamic LDS: bit image (mask_lds_bytes) | 16 flag words | decode scratch (column-scan block totals / polygon side stage)
 // ------------------------------------------------------------------------------------------
 constexpr int DNT = 512;
-#ifndef LA3D_SPLIT_MAXB_NOMASK
-#define LA3D_SPLIT_MAXB_NOMASK 160   // measured crossover with the instance engine (see split_eligible; round 6: grounded run lengths, split | instance: B = 128: 48 | 53, 192: 52.6 | 51.2, 256: 58 | 51)
-#endif
 constexpr int DEC_SCRATCH_BYTES = POLY_STAGE_BYTES > 8192 ? POLY_STAGE_BYTES : 8192;
 template <int SRC>
 __global__ __launch_bounds__(DNT) void scan_bits_kernel(const SplitParams sp) {
@@ -591,7 +589,6 @@ int walk_waves(int nb) {
   int g = nb * 4;
   if (g < 256) g = 256;
   if (g > 1024) g = 1024;
-  if (config().split_grid > 0) g = config().split_grid;
   return g * SNW;
 }
 
@@ -653,29 +650,17 @@ size_t split_workspace_bytes(int B, int H, int W) {
   return make_layout(B, H, W).total;
 }
 
-bool split_eligible(const FitParams& p, bool vec, bool ldsmask) {
-  (void)ldsmask;
-  if (!vec || p.sample_idx != nullptr || p.W % 32 != 0) return false;
+// 16-byte aligned, word-aligned rows without padding (the decoders know no frame_width), a frame whose bands the scan keeps in LDS;
+// run lengths / polygon parts: the bit image and the decode scratch fit the decode workgroup's LDS, no fused filter
+bool split_applies(const FitParams& p, const CallFacts& f) {
+  if (!f.vec || f.sample || p.frame_w != p.W || p.W % 32 != 0) return false;
   const int ntx = p.W / 32, nty = (p.H + 7) / 8;
   if (ntx > 64 || nty > 255) return false;  // scan keeps a band's bits in LDS: 8 tile rows x ntx x 32 B <= 16 KB
   const int nband = (nty + BAND_TROWS - 1) / BAND_TROWS;
   if (nband > 64) return false;
-  // Measured on MI355X, round 3 (BASELINE config-2 inputs, us per call, split vs one workgroup per instance;
-  // profiles/r03/r03_small_batches.txt): u8 planes B = 1 / 16 / 64 / 128 / 192 / 272 / 288 / 304 / 336: 34 / 37 / 45 / 50 / 58 / 70 / 74 / 76 /
-  // 81 vs 40 / 52 / 57 / 58 / 62 / 75 / 72 / 71 / 76; run lengths B = 1 / 16 / 64 / 160 / 256 / 288 / 304: 36 / 40 / 46 / 53 / 59 / 65 / 66 vs
-  // 47 / 57 / 59 / 66 / 64 / 66 / 65 (polygons ~1 us below both).  A lone 60-90 k-px instance keeps ONE CU's fp64 VALU busy for ~40 us
-  // in the instance engine; the split engine spreads its tiles over the chip at the price of six dependent launches.
-  const int e = p.opt_engine != LA3D_ENGINE_DEFAULT ? p.opt_engine : config().engine;   // per-call pin, else the process default
-  if (e == LA3D_ENGINE_INSTANCE) return false;
-  if (p.mask == nullptr) {   // run lengths / polygon parts (scan_bits_kernel): the bit image must fit the decode workgroup's LDS
-    if (p.mask_lds_bytes <= 0 || (size_t)p.mask_lds_bytes + 64 + DEC_SCRATCH_BYTES > 160 * 1024 - 256 || p.filter_boundary >= 0) return false;
-    if (e == LA3D_ENGINE_SPLIT) return true;
-    return p.B <= LA3D_SPLIT_MAXB_NOMASK;
-  }
-  if (e == LA3D_ENGINE_SPLIT) return true;
-  // round 6: u8 planes up to 160 instances only (where the band engine does not apply: it is the faster one there); above, one
-  // workgroup per instance leads - grounded u8, split | instance: B = 192: 56.8 | 54.2, 256: 66.7 | 56.9 (profiles/r06/r06_engines_by_batch.txt)
-  return p.B <= 160;
+  if (p.mask == nullptr)   // run lengths / polygon parts (scan_bits_kernel): the bit image must fit the decode workgroup's LDS
+    return p.mask_lds_bytes > 0 && (size_t)p.mask_lds_bytes + 64 + DEC_SCRATCH_BYTES <= 160 * 1024 - 256 && p.filter_boundary < 0;
+  return true;
 }
 
 // One call = one batch.  Sub-batch j: scan on the scan stream (scans are bandwidth-bound, so they run
@@ -704,7 +689,6 @@ int split_fit(const FitParams& pin, void* workspace, hipStream_t s) {
   int nsub = B / 256;
   if (nsub < 1) nsub = 1;
   if (nsub > 4) nsub = 4;
-  if (config().split_sub > 0) nsub = config().split_sub;
   while ((B + nsub - 1) / nsub * L.nband > MAX_SEG && nsub < MAX_SUB) ++nsub;
   if (nsub > MAX_SUB) nsub = MAX_SUB;
   if ((B + nsub - 1) / nsub * L.nband > MAX_SEG) {

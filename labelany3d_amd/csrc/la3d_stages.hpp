@@ -397,8 +397,22 @@ inline bool balance_enabled(const FitParams& p) {
   return config().balance != 0;
 }
 
-inline int balance_max_rounds() {
-  return config().balance_rounds;  // measured: +21 % at one resident set, +9 % at two, +3 % at three, none at four, negative beyond
+// batches of up to this many resident sets are ordered - measured: +21 % at one resident set, +9 % at two, +3 % at three, none at
+// four, negative beyond
+constexpr int BALANCE_MAX_ROUNDS = 3;
+
+// The 18-bit area of the launch-order keys: step = every step-th 128-byte line of a u8 plane is counted (EST_STEP, or a smaller
+// prime on small frames), shift = the smallest that brings the largest estimate into 18 bits.  Run lengths and polygons count
+// exactly (at most H*W), the byte lattice about H*W / step.  With area_hint the caller's areas are exact: shift for H*W.
+struct OrderKeyScale { int step, shift; };
+inline OrderKeyScale order_key_scale(const FitParams& p) {
+  OrderKeyScale k{1, 0};
+  if (!p.area_hint)
+    for (int cand : {EST_STEP, 31, 17, 7, 3})
+      if ((p.HW >> 7) / cand >= 64) { k.step = cand; break; }
+  const long long amax = (p.area_hint || p.mask == nullptr) ? (long long)p.HW : (long long)p.HW / k.step + 128;
+  while ((amax >> k.shift) > 0x3ffff) ++k.shift;
+  return k;
 }
 
 // ------------------------------------------------------------------------------------------
