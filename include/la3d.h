@@ -51,7 +51,8 @@ extern "C" {
 #define LA3D_BOX_BAD_GROUND 2 /* ground parallel/antiparallel to [0,-1,0] or zero: NaN rotation (:37-55)   */
 #define LA3D_BOX_TOO_FEW 3    /* one valid point: scikit-learn PCA(2) ValueError (:183-184)              */
 #define LA3D_BOX_NONFINITE 4  /* +-inf coordinate reaches PCA: scikit-learn ValueError (:183-184)        */
-#define LA3D_BOX_UNSUPPORTED 5 /* convex_hull on more than 2048 valid points (the reference feeds it <= 500) */
+#define LA3D_BOX_UNSUPPORTED 5 /* convex_hull on more than 2048 valid points (the reference feeds it <= 500); la3d_fit_args::method =
+                                  LA3D_METHOD_CONVEX_HULL in full-mask mode on an instance it does not cover (see "convex-hull yaw") */
 #define LA3D_BOX_FILTERED 6   /* dropped by the instance filter of the *_filtered entry points (src/util.py:375)        */
 
 /* yaw method (reference src/util_3dbox.py:146-151) */
@@ -144,6 +145,7 @@ size_t la3d_workspace_bytes(int B, int H, int W);
  *         img  = image_index[n] if image_index else n
  *         pts  = depth_to_points(depth[img][None], K[img])[mask[n]]     # src/util.py:52-75, :480-481
  *         out[n] = estimate_bbox(pts, None, ground[n], 'pca')          # src/util_3dbox.py:106-178
+ *     ('convex_hull' instead of 'pca': la3d_fit_args::method of la3d_fit_instances_ex, see "convex-hull yaw" below)
  * depth        dev f32, planes of H*W floats, plane p at depth + p*depth_plane_stride
  *              (stride in floats; 0 = one shared plane)
  * image_index  dev i32 [B] or NULL (instance n uses plane n)
@@ -265,8 +267,35 @@ typedef struct la3d_fit_args {
                                  clipped to frame_width (cv2.fillPoly on the unpadded frame), run lengths are column-major and need
                                  nothing, the fused filter takes its right border from frame_width; K and the pixel coordinates are
                                  those of the unpadded frame.  With u8 planes the caller pads the planes with zeros and leaves 0. */
+  int32_t method;             /* LA3D_METHOD_PCA (0: what a block without this field means) or LA3D_METHOD_CONVEX_HULL; anything else:
+                                 LA3D_ERR_ARG.  See "convex-hull yaw" below. */
 } la3d_fit_args;
 int la3d_fit_instances_ex(const la3d_fit_args* args);
+
+/* Convex-hull yaw for the depth + mask fit (la3d_fit_args::method = LA3D_METHOD_CONVEX_HULL; la3d_fit_instances_ex and
+ * la3d_fit_annotations_host - the positional entries stay PCA):
+ *     out[n] = estimate_bbox(pts, None, ground[n], 'convex_hull')        # src/util_3dbox.py:189-224
+ * the minimum-area enclosing rectangle over the hull edges of the x/z footprint, the remedy for the L-shaped footprints a depth
+ * map gives (only the camera-facing surfaces are seen, and their principal axis is the diagonal of the L).
+ *  - reference-subsample mode (sample_idx given): every camera, every ground vector; the at most 500 points of an instance
+ *    go through the hull.  Exactly the reference's call.
+ *  - full-mask mode (sample_idx NULL): for an instance WITHOUT ground rotation (ground NULL or a NaN row) and a K without skew,
+ *    on a frame the tiled single pass covers (W % 32 == 0, 16-byte aligned planes, H*W % 16 == 0, the column arrays fit behind
+ *    the instance's tile list).  All points of pixel column u lie on one ray through the origin of the x/z plane, so only the
+ *    nearest and the farthest valid depth of a column can be hull vertices: the hull of the whole mask is the hull of at most
+ *    2 x (occupied columns) points.  NaN and infinite depths under the mask are dropped (as the reference and the PCA call
+ *    drop them), negative depths are fitted.  Every other instance - a finite ground row, a skewed K, a mask with too many
+ *    active tiles, more than 1024 occupied columns - gets LA3D_BOX_UNSUPPORTED and a NaN record, never a PCA box; a call on a
+ *    frame outside the tiled path gets it for every instance.  Use reference-subsample mode there.
+ *  - the hull call runs on the instance engine, two launches on the caller's stream (fit -> hand-off through the workspace ->
+ *    hull finish), capturable into a HIP graph.  opt_engine pins give way; opt_build values / process defaults that switch the
+ *    single pass off (LA3D_BUILD_PLAIN, LA3D_BUILD_NOCULL) are speed options and are IGNORED by hull calls: they never turn a
+ *    fitted box into a refusal.
+ *  - aux = [yaw, n_valid, n_in, -(hull vertices)]; aux[3] >= 0 (the PCA gap) where the hull had fewer than 3 vertices and the
+ *    reference's PCA fallback decided the yaw (:222-224).
+ *  - workspace: la3d_fit_workspace_bytes(args) bytes - larger than la3d_workspace_bytes(B,H,W) for a hull call (the hand-off
+ *    area), equal to it for a PCA call, 0 for B <= 0.  Only struct_size, B, H, W and method of the block are read. */
+size_t la3d_fit_workspace_bytes(const la3d_fit_args* args);
 
 /* create_boolean_mask_from_polygon for a batch: polygon parts -> u8 planes mask_out dev [B][H*W] (0/1). */
 int la3d_poly_decode(const int32_t* poly_xy, const int64_t* ring_offsets, const int64_t* inst_rings, int B, int H, int W,

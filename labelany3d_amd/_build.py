@@ -10,7 +10,7 @@ CSRC = os.path.join(HERE, "csrc")
 # it carries the build identity)
 SOURCES = [os.path.join(CSRC, f) for f in ("la3d_instance.hip", "la3d_band.hip", "la3d_rows.hip", "la3d_split.hip", "la3d_points.hip", "la3d_masks.hip", "la3d_consumers.hip", "la3d.hip",
                                            "la3d_json.cpp")]
-HEADERS = [os.path.join(CSRC, f) for f in ("la3d_device.hpp", "la3d_walks.hpp", "la3d_stages.hpp", "la3d_engines.hpp", "la3d_poly.hpp")] + \
+HEADERS = [os.path.join(CSRC, f) for f in ("la3d_device.hpp", "la3d_walks.hpp", "la3d_stages.hpp", "la3d_engines.hpp", "la3d_poly.hpp", "la3d_hull.hpp")] + \
           [os.path.join(ROOT, "include", "la3d.h")]
 LIB = os.environ.get("LA3D_LIB") or os.path.join(HERE, "lib", "libla3d.so")  # LA3D_LIB: experiment builds only
 INCLUDE = os.path.join(ROOT, "include")

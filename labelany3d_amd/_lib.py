@@ -29,11 +29,13 @@ class FitArgs(C.Structure):
                 ("out", C.c_void_p), ("status", C.c_void_p), ("aux", C.c_void_p),
                 ("workspace", C.c_void_p), ("stream", C.c_void_p),
                 ("area_hint", C.c_void_p),
-                ("opt_engine", C.c_int32), ("opt_launch_order", C.c_int32), ("opt_build", C.c_int32), ("frame_width", C.c_int32)]
+                ("opt_engine", C.c_int32), ("opt_launch_order", C.c_int32), ("opt_build", C.c_int32), ("frame_width", C.c_int32),
+                ("method", C.c_int32)]
 
 
 _SIGS = {
     "la3d_fit_instances_ex": (C.c_int, [C.POINTER(FitArgs)]),
+    "la3d_fit_workspace_bytes": (C.c_size_t, [C.POINTER(FitArgs)]),
     "la3d_version": (C.c_int, []),
     "la3d_last_error": (C.c_char_p, []),
     "la3d_unproject": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int,
@@ -150,6 +152,21 @@ lib = load()
 
 class La3dError(RuntimeError):
     pass
+
+
+def method_code(method) -> int:
+    """``method`` of the fit entries ("pca" | "convex_hull", the reference's estimate_bbox argument) -> LA3D_METHOD_*; anything else
+    raises the reference's error (src/util_3dbox.py:151) - before any device work."""
+    code = {"pca": METHOD_PCA, "convex_hull": METHOD_CONVEX_HULL}.get(method) if isinstance(method, str) else None
+    if code is None:
+        raise ValueError(f"Unknown method: {method}. Use 'pca' or 'convex_hull'")
+    return code
+
+
+def fit_workspace_bytes(B: int, H: int, W: int, method: int = METHOD_PCA) -> int:
+    """C-ABI ``la3d_fit_workspace_bytes`` for a call of B instances of H x W with the given LA3D_METHOD_* code."""
+    a = FitArgs(struct_size=C.sizeof(FitArgs), B=B, H=H, W=W, method=method)
+    return int(lib.la3d_fit_workspace_bytes(C.byref(a)))
 
 
 def check(rc: int, what: str) -> None:

@@ -183,11 +183,14 @@ class InstanceFitter:
     """Reusable launch state for fit_instances on fixed (B,H,W): owns the output / status / aux /
     workspace buffers so the steady-state call allocates nothing and is a pure enqueue."""
 
-    def __init__(self, B: int, H: int, W: int, device=None, slots: int = 1, ws_slots: int = 1):
+    def __init__(self, B: int, H: int, W: int, device=None, slots: int = 1, ws_slots: int = 1, method: str = "pca"):
+        """``method``: the yaw estimator the workspace is sized for ("convex_hull" needs the hand-off area of the hull finish,
+        ``la3d_fit_workspace_bytes``) and the default of ``run``; a fitter sized for "convex_hull" also serves "pca" calls."""
+        self.method = _lib.method_code(method)
         self.B, self.H, self.W = int(B), int(H), int(W)
         self.device = _dev(device)
         self.slots = slots
-        nbytes = int(lib.la3d_workspace_bytes(self.B, self.H, self.W))
+        nbytes = _lib.fit_workspace_bytes(self.B, self.H, self.W, self.method)
         wsz = max((nbytes + 255) // 256 * 256, 256)
         # ONE device allocation carved into the four buffers (a call through the convenience wrappers allocates once)
         up = lambda v: (v + 255) // 256 * 256  # noqa: E731  (every region starts 256-byte aligned, like a fresh allocation)
@@ -202,16 +205,25 @@ class InstanceFitter:
 
     def run(self, depth: torch.Tensor, masks: torch.Tensor, K: torch.Tensor, ground=None, sample_idx=None,
             image_index=None, slot: int = 0, stream=None, ws_slot: int = 0, engine=None, launch_order=None, build=None,
-            area_hint=None):
+            area_hint=None, method=None):
         """All arguments already on the device with the ABI's dtypes (f32 / u8 / f64 / f64 / i32 / i32).
-        ``engine`` / ``launch_order`` / ``build``: scheduling of THIS call (labelany3d_amd.options; speed only)."""
+        ``engine`` / ``launch_order`` / ``build``: scheduling of THIS call (labelany3d_amd.options; speed only).
+        ``method``: "pca" | "convex_hull" (None: what the fitter was built for)."""
+        meth = self._method(method)
         a = _fit_args(self.B, self.H, self.W, _ptr(depth), depth.shape[0] if depth.dim() == 3 else 1, _ptr(K),
                       K.shape[0] if K.dim() == 3 else 1, _ptr(self.boxes[slot]), _ptr(self.status[slot]), _ptr(self.aux[slot]),
                       _ptr(self.workspace[ws_slot]), _stream(stream, raw=True), mask=_ptr(masks), image_index=_ptr(image_index),
                       ground=_ptr(ground), sample_idx=_ptr(sample_idx), area_hint=_ptr(area_hint),
-                      opts=options.codes(engine, launch_order, build))
+                      opts=options.codes(engine, launch_order, build), method=meth)
         check(lib.la3d_fit_instances_ex(C.byref(a)), "la3d_fit_instances_ex")
         return self.boxes[slot], self.status[slot], self.aux[slot]
+
+    def _method(self, method) -> int:
+        """The LA3D_METHOD_* code of a call on this fitter; a hull call needs a fitter whose workspace was sized for it."""
+        meth = self.method if method is None else _lib.method_code(method)
+        if meth == _lib.METHOD_CONVEX_HULL and self.method != _lib.METHOD_CONVEX_HULL:
+            raise ValueError("this InstanceFitter was sized for method='pca': build it with method='convex_hull'")
+        return meth
 
 
 def _filter_args(filter):
@@ -232,7 +244,7 @@ def _filter_args(filter):
 
 def _fit_args(B, H, W, depth, planes, K, nk, out, status, aux, workspace, stream, mask=None, rle=None, poly=None, image_index=None,
               ground=None, sample_idx=None, filter=None, stats=None, proj=None, image_size=None, area_hint=None, opts=(0, 0, 0),
-              frame_width=0) -> FitArgs:
+              frame_width=0, method=0) -> FitArgs:
     """The argument block of every fit call (C-ABI ``la3d_fit_instances_ex``) from pointers (None = NULL; device pointers, or host
     pointers for ``la3d_fit_annotations_host``) and sizes: ``planes`` depth planes of H*W floats, ``nk`` intrinsics matrices (one
     of either is shared by every instance).  rle = (counts, offsets), poly = (xy, ring_offsets, inst_rings); ``filter`` as in
@@ -240,7 +252,8 @@ def _fit_args(B, H, W, depth, planes, K, nk, out, status, aux, workspace, stream
     Built fresh for every call: one InstanceFitter may be driven from several threads and streams."""
     a = FitArgs(struct_size=C.sizeof(FitArgs), B=B, H=H, W=W, depth=depth, depth_plane_stride=H * W if planes > 1 else 0,
                 image_index=image_index, mask=mask, K=K, k_stride=9 if nk > 1 else 0, ground=ground, sample_idx=sample_idx,
-                out=out, status=status, aux=aux, workspace=workspace, stream=stream, area_hint=area_hint, frame_width=frame_width)
+                out=out, status=status, aux=aux, workspace=workspace, stream=stream, area_hint=area_hint, frame_width=frame_width,
+                method=method)
     if rle is not None:
         a.rle_counts, a.rle_offsets = rle
     if poly is not None:
@@ -324,7 +337,7 @@ def pad_rows_f32(d: torch.Tensor, Wp: int) -> torch.Tensor:
     return out
 
 
-def fit_instances(depth, masks, K, ground=None, sample_idx=None, image_index=None, stream=None, device=None):
+def fit_instances(depth, masks, K, ground=None, sample_idx=None, image_index=None, stream=None, device=None, method: str = "pca"):
     """Batched composed hot path on the GPU.
 
     depth        (P,H,W) or (H,W) float32 — P planes; one plane = shared by all instances
@@ -333,8 +346,14 @@ def fit_instances(depth, masks, K, ground=None, sample_idx=None, image_index=Non
     ground       (B,4) float64 or None; rows whose first entry is NaN mean "no ground"
     sample_idx   None = full-mask mode; (B,500) int = reference-subsample mode (see draw_sample_idx)
     image_index  (B,) int — depth plane / K of each instance (default: instance n -> plane n, or 0)
+    method       "pca" | "convex_hull": the reference's estimate_bbox argument (src/util_3dbox.py:146-151).  "convex_hull" = the
+                 minimum-area rectangle over the hull edges of the footprint.  In full-mask mode it needs an instance without
+                 ground rotation and a K without skew on a frame whose (padded) width is a multiple of 32; every other instance
+                 comes back with status 5 (LA3D_BOX_UNSUPPORTED) and a NaN record - pass sample_idx there (every camera, every
+                 ground).  aux[3] = -(hull vertices), or the eigen-gap (>= 0) where the reference's PCA fallback was taken.
     Returns (boxes (B,39) f64, status (B,) i32, aux (B,4) f64 = yaw, n_valid, n_masked, eigen-gap), on the GPU.
     """
+    _lib.method_code(method)   # (the reference's error for an unknown method, before any device work)
     if device is None and isinstance(masks, torch.Tensor) and masks.is_cuda:
         device = masks.device
     dev = _dev(device)
@@ -344,7 +363,8 @@ def fit_instances(depth, masks, K, ground=None, sample_idx=None, image_index=Non
     B, H, W = m.shape
     d, k, ii, g, si, P = _fit_inputs(depth, K, image_index, ground, sample_idx, B, H, W, dev, "masks", check_device_index=True)
     with torch.cuda.device(dev):
-        if W % 32 != 0 and 2 <= B <= 256 and si is None:
+        hull = method == "convex_hull"   # (full-mask hull exists on the tiled path only: an odd width is padded at every batch size)
+        if W % 32 != 0 and si is None and (2 <= B <= 256 or (hull and B >= 1)):
             # a small batch on a frame of odd width (COCO: 427, 500, 375, 333 ...): the tiled forms - and the row engine small batches
             # take - need word-aligned rows; padding the B mask planes and the depth rows with zeros costs less than the row-linear
             # form they would otherwise run (profiles/r05/r05_odd_width_u8.txt: 8 / 64 / 256 masks of 640x427: 172 / 198 / 202 us ->
@@ -361,7 +381,7 @@ def fit_instances(depth, masks, K, ground=None, sample_idx=None, image_index=Non
                 ii, P = None, B
             d = pad_rows_f32(d, Wp)
             W = Wp
-        f = InstanceFitter(B, H, W, dev)
+        f = InstanceFitter(B, H, W, dev, method=method)
         if B == 0:
             return f.boxes[0], f.status[0], f.aux[0]
         _order(stream)   # the arguments were uploaded / converted on the current stream
@@ -408,9 +428,7 @@ def fit_points(clouds, ground=None, sample_idx=None, method: str = "pca", stream
             else:
                 pts = torch.zeros((1, 3), dtype=torch.float64, device=dev)
     B = off.numel() - 1
-    meth = {"pca": _lib.METHOD_PCA, "convex_hull": _lib.METHOD_CONVEX_HULL}.get(method)
-    if meth is None:
-        raise ValueError(f"Unknown method: {method}. Use 'pca' or 'convex_hull'")  # reference :151
+    meth = _lib.method_code(method)  # (reference :151)
     g = None if ground is None else _as_dev(ground, torch.float64, dev)
     si = None if sample_idx is None else _as_dev(sample_idx, torch.int32, dev)
     # one output buffer (records | aux | status): a caller that wants everything on the host reads it back in one copy

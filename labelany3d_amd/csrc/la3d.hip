@@ -31,6 +31,7 @@
 #include "la3d_device.hpp"
 #include "la3d_poly.hpp"
 #include "la3d_engines.hpp"
+#include "la3d_hull.hpp"
 
 namespace la3d {
 thread_local char g_err[256] = "";
@@ -73,6 +74,8 @@ constexpr int SPLIT_MAXB = 160;
 // passes either way).  This shortcut belongs to the walk from rows: a pinned band or split engine skips it.
 static int choose_engine(const FitParams& p, const CallFacts& f, int pin) {
   const int B = p.B, H = p.H, W = p.W;
+  // a convex-hull call (la3d_fit_args::method) runs on the instance engine, whatever is pinned: pins change speed, never records
+  if (f.method == LA3D_METHOD_CONVEX_HULL) return LA3D_ENGINE_INSTANCE;
   if (pin == LA3D_ENGINE_DEFAULT || pin == LA3D_ENGINE_ROWS || pin == LA3D_ENGINE_ROWS2) {
     if (rows_applies(p, f) && (pin != LA3D_ENGINE_DEFAULT || B <= config().rows_maxb)) return LA3D_ENGINE_ROWS;
     const bool single_pass_call = p.ground == nullptr && !f.sample && !p.sep_off && f.ldsmask && f.vec && W % 32 == 0 && W / 32 <= 255 &&
@@ -154,6 +157,20 @@ size_t la3d_workspace_bytes(int B, int H, int W) {
   return rows > m ? rows : m;
 }
 
+static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// The workspace of ONE call: la3d_workspace_bytes(B,H,W) for a PCA call; a convex-hull call adds its hand-off area behind that,
+// 256-aligned - per instance the larger of the two modes' slots (hull_stride_bytes), so the size does not depend on sample_idx
+size_t la3d_fit_workspace_bytes(const la3d_fit_args* args) {
+  constexpr int32_t V1_SIZE = (int32_t)offsetof(la3d_fit_args, area_hint);
+  if (!args || args->struct_size < V1_SIZE || args->B <= 0) return 0;
+  const size_t base = la3d_workspace_bytes(args->B, args->H, args->W);
+  const bool has_method = (size_t)args->struct_size >= offsetof(la3d_fit_args, method) + sizeof(int32_t);
+  if (!has_method || args->method != LA3D_METHOD_CONVEX_HULL) return base;
+  const size_t full = hull_stride_bytes(false, args->W > 0 ? args->W : 0), samp = hull_stride_bytes(true, 0);
+  return up256(base) + (size_t)args->B * (full > samp ? full : samp);
+}
+
 // Every fit entry ends here with its arguments in one block.  filter_on: the fused instance filter runs (the *_filtered entries
 // always; la3d_fit_instances_ex when filter_boundary >= 0 and filter_max_edge > 0).  who: the entry named in la3d_last_error().
 static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who) {
@@ -165,9 +182,14 @@ static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who)
     snprintf(g_err, sizeof(g_err), "%s: bad argument", who);
     return LA3D_ERR_ARG;
   }
+  if (a.method != LA3D_METHOD_PCA && a.method != LA3D_METHOD_CONVEX_HULL) {
+    snprintf(g_err, sizeof(g_err), "%s: unknown method (LA3D_METHOD_PCA or LA3D_METHOD_CONVEX_HULL)", who);
+    return LA3D_ERR_ARG;
+  }
   if (B == 0) return LA3D_SUCCESS;
   if (!a.workspace || (reinterpret_cast<uintptr_t>(a.workspace) & 7)) {
-    snprintf(g_err, sizeof(g_err), "%s: workspace of la3d_workspace_bytes() bytes (8-aligned) required", who);
+    if (a.method == LA3D_METHOD_CONVEX_HULL) snprintf(g_err, sizeof(g_err), "%s: a convex-hull call needs a workspace of la3d_fit_workspace_bytes() bytes (8-aligned)", who);
+    else snprintf(g_err, sizeof(g_err), "%s: workspace of la3d_workspace_bytes() bytes (8-aligned) required", who);
     return LA3D_ERR_ARG;
   }
   FitParams p;   // (every other field keeps its default: see FitParams)
@@ -221,6 +243,9 @@ static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who)
   f.vec = (p.HW % 16 == 0) && (rle || (reinterpret_cast<uintptr_t>(a.mask) & 15) == 0) &&
           ((reinterpret_cast<uintptr_t>(a.depth) & 15) == 0) && (a.depth_plane_stride % 4 == 0);
   f.sample = a.sample_idx != nullptr;
+  f.method = a.method;
+  if (a.method == LA3D_METHOD_CONVEX_HULL)
+    f.hull_area = static_cast<unsigned char*>(a.workspace) + up256(la3d_workspace_bytes(B, H, W));
   f.lds = (size_t)p.mask_lds_bytes + sizeof(Shared);
   // polygons: the side stage sits behind Shared, where the tile list / rank prefix go later (disjoint in time)
   f.poly_stage = a.poly_xy ? (size_t)POLY_STAGE_BYTES : 0;

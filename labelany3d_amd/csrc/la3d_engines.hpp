@@ -14,6 +14,8 @@ struct CallFacts {
   bool sample;         // reference-subsample mode (sample_idx given)
   size_t lds;          // bit image + Shared
   size_t poly_stage;   // polygon input: the side stage behind Shared, else 0
+  int method = 0;      // LA3D_METHOD_*: a convex-hull call (la3d_fit_args::method) runs on the instance engine only
+  void* hull_area = nullptr;   // hull call: the hand-off area behind the first la3d_workspace_bytes(B,H,W) bytes of the workspace
 };
 
 // instance engine (la3d_instance.hip): one workgroup per instance - takes every call; picks the instantiation of

@@ -15,6 +15,7 @@
 #include "la3d_engines.hpp"
 #include "la3d_walks.hpp"
 #include "la3d_stages.hpp"
+#include "la3d_hull.hpp"
 
 
 namespace {
@@ -22,7 +23,51 @@ namespace {
 // instance engine: one workgroup per instance
 // ------------------------------------------------------------------------------------------
 // SRC: where the mask comes from - 0 = u8 plane, 1 = COCO run lengths, 2 = polygon parts (both decoded into the LDS bit image)
-template <bool VEC, bool LDSMASK, bool SAMPLE, bool TILED, int SRC>
+// The checked separable walk of the hull instantiations (full-mask mode): what sweep_sep does - moments, y extent, per-column depth
+// range in ONE walk over the compacted tile list - with a finite test per pixel (NaN / infinite depths under the mask are holes of a
+// real depth map: dropped, as the reference drops them, src/util_3dbox.py:139) and range keys that order negative depths too
+// (hull_key).  Moments about (px0, pz0).  col = colmin[W] | colmax[W], initialised to 0xffffffff / 0.  One tile per wave and step;
+// lane = (column c of the tile, four rows from h4).
+__device__ inline void sweep_sep_hull(const FitParams& p, const float* __restrict__ dpl, const unsigned* bits, const unsigned short* list,
+                                      int nactive, const double* Mg, unsigned* col, int wave, int lane, double px0, double pz0,
+                                      double* acc, double* yext, int* cnt) {
+  const int c = lane & 31, h4 = (lane >> 5) * 4;
+  const double a00 = Mg[0], a02 = Mg[2], a11 = Mg[4], a12 = Mg[5];
+  double s0 = acc[0], s1 = acc[1], s2 = acc[2], s3 = acc[3], s4 = acc[4], ylo = yext[0], yhi = yext[1];
+  int n = *cnt;
+  for (int e = wave; e < nactive; e += NWAVE) {   // wave-uniform
+    const unsigned t = __builtin_amdgcn_readfirstlane((unsigned)list[e]);
+    const int u = (int)(t & 0xffu) * 32 + c, v0 = (int)(t >> 8) * 8 + h4;   // u < W: the tiles cover exactly W = 32 ntx columns
+    const uint4 w = *reinterpret_cast<const uint4*>(bits + e * 8 + h4);
+    const unsigned nib = ((w.x >> c) & 1u) | (((w.y >> c) & 1u) << 1) | (((w.z >> c) & 1u) << 2) | (((w.w >> c) & 1u) << 3);
+    const double r0 = fma(a00, (double)u, a02);
+    unsigned kmin = 0xffffffffu, kmax = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int v = v0 + k;
+      if (((nib >> k) & 1u) && v < p.H) {   // (rows past the frame carry no mask bit; the test keeps the load inside the plane regardless)
+        const float df = dpl[(long long)v * p.W + u];
+        if (finite_f32(df)) {
+          const unsigned key = hull_key(__float_as_uint(df));
+          kmin = min(kmin, key); kmax = max(kmax, key);
+          const double d = (double)df;
+          const double x = d * r0 - px0, z = d - pz0, y = d * fma(a11, (double)v, a12);
+          s0 += x; s1 += z; s2 = fma(x, x, s2); s3 = fma(x, z, s3); s4 = fma(z, z, s4);
+          ylo = fmin(ylo, y); yhi = fmax(yhi, y);
+          n += 1;
+        }
+      }
+    }
+    if (kmin <= kmax) { atomicMin(col + u, kmin); atomicMax(col + p.W + u, kmax); }
+  }
+  acc[0] = s0; acc[1] = s1; acc[2] = s2; acc[3] = s3; acc[4] = s4; yext[0] = ylo; yext[1] = yhi;
+  *cnt = n;
+}
+
+// HULL: the instantiations of a convex-hull call (la3d_fit_args::method) - everything a PCA call does up to
+// and including the axis, then, instead of extents and record, the hand-off of hull_finish_kernel through the workspace (p.geo
+// points at the call's hand-off area).  Every difference sits behind the constant HULL: the PCA instantiations (HULL = false) compile to the code they were.
+template <bool VEC, bool LDSMASK, bool SAMPLE, bool TILED, int SRC, bool HULL = false>
 __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitParams p) {
   constexpr bool RLE = SRC == 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -57,6 +102,7 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
   }
   const int inst = p.order_nch > 0 ? order_select(p, (int)blockIdx.x, sh, wave, lane) : xcd_remap(blockIdx.x, p.B);
   if (tid == 0) { sh->order_inst = inst; sh->sep_bad = 0; }   // (the instance is re-read after the mask stage, see below)
+  if constexpr (HULL) { if (tid == 0) hull_slot(p.geo, inst, hull_stride_bytes(SAMPLE, p.W))[HH_STATE] = -1.0; }   // nothing to finish, until the hand-off says so
   const int img = p.image_index ? p.image_index[inst] : inst;
   const int HW = p.HW;
   const float* dpl = p.depth + (long long)img * p.depth_plane_stride;
@@ -215,7 +261,9 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
     if (lane == 0) sh->nmask[wave] = wsum;
     __syncthreads();
     for (int w = 0; w < NWAVE; ++w) ntot += sh->nmask[w];
-    sampled = ntot > LA3D_NSAMPLE;
+    // (hull call: every instance goes the sampled way - a mask of <= 500 pixels draws its own ranks 0 .. ntot-1 -, so that its
+    // points exist one per thread for the hand-off)
+    sampled = HULL || ntot > LA3D_NSAMPLE;
   }
 
   // ---- active-tile list (deterministic two-pass compaction: count, prefix, write) ----------------
@@ -226,7 +274,7 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
   int compact = 0;
   // separable single pass (sweep_sep): no ground rotation, no skew - x ray by column, y ray by row, z = depth
   bool sep = false;
-  const bool sep_cam = LK && !p.sep_off && Mg[1] == 0.0 && Mg[3] == 0.0 && Mg[6] == 0.0 && Mg[7] == 0.0 && Mg[8] == 1.0;   // uniform
+  const bool sep_cam = LK && (HULL || !p.sep_off) && Mg[1] == 0.0 && Mg[3] == 0.0 && Mg[6] == 0.0 && Mg[7] == 0.0 && Mg[8] == 1.0;   // uniform
   if (TILED && !sampled) {
     const int ntiles = p.ntx * p.nty, per = p.tiles_per_wave;
     const int tbeg = wave * per, tend = min(tbeg + per, ntiles);
@@ -367,6 +415,54 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
     __syncthreads();
   }
 
+  if constexpr (HULL && LK) {
+    // ---- hull call, full-mask mode: the checked separable walk, the axis (the PCA yaw is the fallback), then the hand-off ----
+    if (!sep) {   // uniform: no per-column structure (ground rotation, skewed K, too many active tiles) - refused, never fitted as PCA
+      if (tid == 0) {
+        if (p.aux) {
+          double* a = p.aux + (long long)inst_p * LA3D_AUX;
+          a[0] = NAN; a[1] = 0.0; a[2] = NAN; a[3] = NAN;
+        }
+        p.status[inst_p] = LA3D_BOX_UNSUPPORTED;
+        write_nan_box(p.out + (long long)inst_p * LA3D_REC);
+        if (p.proj) { for (int j = 0; j < 8; ++j) p.proj[(long long)inst_p * 8 + j] = NAN; }
+      }
+      return;
+    }
+    unsigned* col = bits + nactive * 8;
+    double hacc[5] = {0, 0, 0, 0, 0}, yx[2] = {INFINITY, -INFINITY};
+    int hcnt = 0;
+    sweep_sep_hull(p, dpl, bits, list, nactive, Mg, col, wave, lane, 0.0, 0.0, hacc, yx, &hcnt);
+    stage_moments_to_axis(sh, p, inst_p, hacc, hcnt, nmask, tid, wave, lane, true);
+    if (sh->redo) {   // uniform: ill-conditioned raw sums - the moments once more about the pivot the stage left (the ranges stand)
+      __syncthreads();
+      double piv[2];
+      get_pivot(sh, piv);
+#pragma unroll
+      for (int i = 0; i < 5; ++i) hacc[i] = 0;
+      hcnt = 0;
+      sweep_sep_hull(p, dpl, bits, list, nactive, Mg, col, wave, lane, piv[0], piv[1], hacc, yx, &hcnt);
+      stage_moments_to_axis(sh, p, inst_p, hacc, hcnt, nmask, tid, wave, lane, false);
+    }
+    if (sh->st != LA3D_BOX_OK) return;   // (the stage wrote status and the NaN record; nothing to finish)
+    const double ylo_w = wave_min(yx[0]), yhi_w = wave_max(yx[1]);
+    if (lane == 0) { sh->part[wave][5] = ylo_w; sh->part[wave][6] = yhi_w; }
+    __syncthreads();
+    double* hh = hull_slot(p.geo, inst_p, hull_stride_bytes(false, p.W));
+    unsigned* hcol = reinterpret_cast<unsigned*>(hh + HH_D);
+    for (int i = tid; i < 2 * p.W; i += NT) hcol[i] = col[i];
+    if (tid == 0) {
+      double ylo = INFINITY, yhi = -INFINITY;
+      for (int w = 0; w < NWAVE; ++w) { ylo = fmin(ylo, sh->part[w][5]); yhi = fmax(yhi, sh->part[w][6]); }
+      hh[HH_NVALID] = (double)sh->n_valid; hh[HH_NM] = (double)sh->nm; hh[HH_CYAW] = sh->cyaw; hh[HH_SYAW] = sh->syaw;
+      hh[HH_GAP] = sh->gap; hh[HH_YLO] = ylo; hh[HH_YHI] = yhi;
+      for (int i = 0; i < 9; ++i) hh[HH_RG + i] = sh->Rg[i];
+      hh[HH_A00] = Mg[0]; hh[HH_A02] = Mg[2]; hh[HH_NPTS] = 0.0;
+      hh[HH_STATE] = 0.0;
+    }
+    return;
+  }
+
   // ---- separable single pass: moments, y extent and per-column depth ranges in ONE walk; x / z extents from the ranges -------
   if constexpr (LK) {
     if (sep) {   // uniform
@@ -456,8 +552,8 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
         run0 += tot;
         __syncthreads();
       }
-      if (tid < LA3D_NSAMPLE) {
-        int r = my_draw;
+      if (tid < (HULL ? min(ntot, LA3D_NSAMPLE) : LA3D_NSAMPLE)) {
+        int r = (HULL && ntot <= LA3D_NSAMPLE) ? tid_plain : my_draw;
         r = r < 0 ? 0 : (r >= ntot ? ntot - 1 : r);
         int lo = 0, hi = nblk - 1;
         while (lo < hi) {  // last block whose exclusive prefix is <= r
@@ -564,6 +660,23 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
   LA3D_STAMP(4);
   if (sh->st != LA3D_BOX_OK) return;
 
+  if constexpr (HULL && SAMPLE) {
+    // ---- hull call, reference-subsample mode: the at most 500 points in the ground-aligned frame, one per thread, handed over ----
+    double* hh = hull_slot(p.geo, inst_p, hull_stride_bytes(true, p.W));
+    if (tid_plain < HULL_SMALL) {
+      double* q = hh + HH_D + 3 * tid_plain;
+      q[0] = pok ? px : NAN; q[1] = pok ? py : NAN; q[2] = pok ? pz : NAN;
+    }
+    if (tid_plain == 0) {
+      hh[HH_NVALID] = (double)sh->n_valid; hh[HH_NM] = (double)sh->nm; hh[HH_CYAW] = sh->cyaw; hh[HH_SYAW] = sh->syaw;
+      hh[HH_GAP] = sh->gap; hh[HH_YLO] = 0.0; hh[HH_YHI] = 0.0;
+      for (int i = 0; i < 9; ++i) hh[HH_RG + i] = sh->Rg[i];
+      hh[HH_A00] = 0.0; hh[HH_A02] = 0.0; hh[HH_NPTS] = (double)min(ntot, LA3D_NSAMPLE);
+      hh[HH_STATE] = 0.0;
+    }
+    return;
+  }
+
   // ---- pass B: extents along the principal axes -----------------------------------------
   double ext[6] = {INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY};  // x, y, z : lo, hi
   if (sampled) {
@@ -603,6 +716,150 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
 }
 #undef tid
 
+
+
+// ------------------------------------------------------------------------------------------
+// hull finish: one workgroup of NTP threads per instance - candidates -> hull_yaw -> extents over the candidates under the hull yaw
+// (the extents of a point set along ANY direction are taken at hull vertices, and every hull vertex is a candidate) -> record.
+// ------------------------------------------------------------------------------------------
+struct alignas(16) SharedF {
+  double part[NWAVEP][8];
+  double cyaw, syaw;
+  int nvalid;       // candidates held in hs.x / hs.z (hull_yaw's point count)
+  int hull_n;
+  int fill;
+};
+
+template <bool SAMPLE, int HCAP>
+__global__ __launch_bounds__(NTP) void hull_finish_kernel(const FitParams p, unsigned long long stride) {
+  __shared__ SharedF sh;
+  __shared__ SharedHullT<HCAP> hs;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int inst = blockIdx.x;
+  const double* hh = hull_slot(p.geo, inst, (size_t)stride);
+  if (hh[HH_STATE] != 0.0) return;   // uniform: the fit kernel has finished this instance itself
+  if (tid == 0) { sh.fill = 0; sh.hull_n = 0; }
+  __syncthreads();
+  double ylo = INFINITY, yhi = -INFINITY;
+  if (SAMPLE) {
+    const int npts = min((int)hh[HH_NPTS], HULL_SMALL);
+    const double* pts = hh + HH_D;
+    for (int i = tid; i < npts; i += NTP) {
+      const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
+      if (x == x) {   // (a point the fit kernel dropped is three NaNs)
+        const int slot = atomicAdd(&sh.fill, 1);
+        if (slot < HCAP) { hs.x[slot] = x; hs.z[slot] = z; }
+        ylo = fmin(ylo, y); yhi = fmax(yhi, y);
+      }
+    }
+  } else {
+    const unsigned* col = reinterpret_cast<const unsigned*>(hh + HH_D);
+    const double a00 = hh[HH_A00], a02 = hh[HH_A02];
+    if (tid == 0) { ylo = hh[HH_YLO]; yhi = hh[HH_YHI]; }
+    for (int u = tid; u < p.W; u += NTP) {
+      const unsigned lo = col[u], hi = col[p.W + u];
+      if (lo <= hi) {   // the column holds a valid pixel: the two ends of its ray (one point when they coincide)
+        const int k = lo == hi ? 1 : 2;
+        const int slot = atomicAdd(&sh.fill, k);
+        if (slot + k <= HCAP) {
+          const double r0 = fma(a00, (double)u, a02), dlo = (double)hull_unkey(lo), dhi = (double)hull_unkey(hi);
+          hs.x[slot] = dlo * r0; hs.z[slot] = dlo;
+          if (k == 2) { hs.x[slot + 1] = dhi * r0; hs.z[slot + 1] = dhi; }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const int n = sh.fill;
+  double* out = p.out + (long long)inst * LA3D_REC;
+  double* aux = p.aux ? p.aux + (long long)inst * LA3D_AUX : nullptr;
+  if (n > HCAP) {   // uniform: more than HCAP / 2 occupied columns - refused, never fitted as PCA
+    if (tid == 0) {
+      if (aux) { aux[0] = NAN; aux[1] = hh[HH_NVALID]; aux[2] = hh[HH_NM]; aux[3] = NAN; }
+      p.status[inst] = LA3D_BOX_UNSUPPORTED;
+      write_nan_box(out);
+      if (p.proj) { for (int j = 0; j < 8; ++j) p.proj[(long long)inst * 8 + j] = NAN; }
+    }
+    return;
+  }
+  if (tid == 0) { sh.nvalid = n; sh.cyaw = hh[HH_CYAW]; sh.syaw = hh[HH_SYAW]; }
+  __syncthreads();
+  double yaw = 0.0;
+  const bool by_hull = hull_yaw(&hs, &sh, tid, &yaw);   // false: fewer than 3 hull vertices - the PCA axis stands (reference :222-224)
+  if (by_hull && tid == 0) {
+    double s_, c_;
+    sincos(yaw, &s_, &c_);
+    sh.cyaw = c_; sh.syaw = s_;
+  }
+  __syncthreads();
+  const double cy = sh.cyaw, sy = sh.syaw;
+  double xlo = INFINITY, xhi = -INFINITY, zlo = INFINITY, zhi = -INFINITY;
+  for (int i = tid; i < n; i += NTP) {
+    const double x = hs.x[i], z = hs.z[i];
+    const double x2 = cy * x + sy * z, z2 = -sy * x + cy * z;   // rotate_y(yaw) @ rotated^T  (:154)
+    xlo = fmin(xlo, x2); xhi = fmax(xhi, x2); zlo = fmin(zlo, z2); zhi = fmax(zhi, z2);
+  }
+  {
+    const double r0 = wave_min(xlo), r1 = wave_max(xhi), r2 = wave_min(zlo), r3 = wave_max(zhi), r4 = wave_min(ylo), r5 = wave_max(yhi);
+    if (lane == 0) { double* pp = sh.part[wave]; pp[0] = r0; pp[1] = r1; pp[2] = r2; pp[3] = r3; pp[4] = r4; pp[5] = r5; }
+  }
+  __syncthreads();
+  if (wave == 0) {
+    double xmin = INFINITY, xmax = -INFINITY, zmin = INFINITY, zmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
+    for (int w = 0; w < NWAVEP; ++w) {
+      xmin = fmin(xmin, sh.part[w][0]); xmax = fmax(xmax, sh.part[w][1]); zmin = fmin(zmin, sh.part[w][2]); zmax = fmax(zmax, sh.part[w][3]);
+      ymin = fmin(ymin, sh.part[w][4]); ymax = fmax(ymax, sh.part[w][5]);
+    }
+    double Rg[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) Rg[i] = hh[HH_RG + i];
+    if (p.proj) {   // uniform
+      const int img = p.image_index ? p.image_index[inst] : inst;
+      write_box_wave(out, Rg, cy, sy, xmin, xmax, ymin, ymax, zmin, zmax, lane, p.proj + (long long)inst * 8, p.K + (long long)img * p.k_stride,
+                     p.proj_w, p.proj_h);
+    } else {
+      write_box_wave(out, Rg, cy, sy, xmin, xmax, ymin, ymax, zmin, zmax, lane);
+    }
+  } else if (tid == 64) {
+    if (aux) {
+      aux[0] = by_hull ? yaw : atan2(sy, cy); aux[1] = hh[HH_NVALID]; aux[2] = hh[HH_NM];
+      aux[3] = by_hull ? -(double)sh.hull_n : hh[HH_GAP];   // negative: the hull decided the yaw (value = number of hull vertices)
+    }
+    p.status[inst] = LA3D_BOX_OK;
+  }
+}
+
+// a hull call in full-mask mode on a frame outside the tiled vector path: every instance is refused (status 5, NaN record)
+__global__ __launch_bounds__(256) void hull_refuse_kernel(const FitParams p) {
+  const int inst = blockIdx.x * 256 + threadIdx.x;
+  if (inst >= p.B) return;
+  if (p.aux) { double* a = p.aux + (long long)inst * LA3D_AUX; a[0] = NAN; a[1] = 0.0; a[2] = NAN; a[3] = NAN; }
+  p.status[inst] = LA3D_BOX_UNSUPPORTED;
+  write_nan_box(p.out + (long long)inst * LA3D_REC);
+  if (p.proj) { for (int j = 0; j < 8; ++j) p.proj[(long long)inst * 8 + j] = NAN; }
+}
+
+// the two launches of a hull call, one linear chain on the caller's stream (no launch order: workgroup b fits instance xcd_remap(b))
+template <bool VEC, bool SAMPLE, int SRC>
+int launch_hull_inst(const FitParams& p, size_t lds, hipStream_t s) {
+  // (full-mask mode = the tiled vector build, subsample mode = the build without tile list)
+  auto kern = fit_instances_kernel<VEC, true, SAMPLE, !SAMPLE, SRC, true>;
+  allow_big_lds(reinterpret_cast<const void*>(kern));
+  hipLaunchKernelGGL(kern, dim3(p.B), dim3(NT), lds, s, p);
+  const int rc = check_launch("fit_instances_kernel (hull)");
+  if (rc != LA3D_SUCCESS) return rc;
+  const unsigned long long stride = hull_stride_bytes(SAMPLE, p.W);
+  if (SAMPLE) hipLaunchKernelGGL((hull_finish_kernel<true, HULL_SMALL>), dim3(p.B), dim3(NTP), 0, s, p, stride);
+  else hipLaunchKernelGGL((hull_finish_kernel<false, HULL_MAX>), dim3(p.B), dim3(NTP), 0, s, p, stride);
+  return check_launch("hull_finish_kernel");
+}
+template <bool VEC, bool SAMPLE>
+int launch_hull(const FitParams& p, size_t lds, hipStream_t s) {
+  if (p.rle_counts != nullptr) return launch_hull_inst<true, SAMPLE, 1>(p, lds, s);
+  if (p.poly_xy != nullptr) return launch_hull_inst<true, SAMPLE, 2>(p, lds, s);
+  return launch_hull_inst<VEC, SAMPLE, 0>(p, lds, s);
+}
 
 template <bool VEC, bool LDSMASK, bool SAMPLE, bool TILED, int SRC>
 int launch_fit_inst(const FitParams& p_in, size_t lds, hipStream_t s, void* workspace) {
@@ -678,6 +935,10 @@ int instance_fit(FitParams p, const CallFacts& f, hipStream_t s, void* workspace
       snprintf(g_err, sizeof(g_err), "%s: reference-subsample mode: frame too large for LDS", who);
       return LA3D_ERR_UNSUPPORTED;
     }
+    if (f.method == LA3D_METHOD_CONVEX_HULL) {   // every instance goes the sampled way: no tile list
+      p.geo = static_cast<double*>(f.hull_area);
+      return vec ? launch_hull<true, true>(p, lds, s) : launch_hull<false, true>(p, lds, s);
+    }
     if (vec && W % 32 == 0 && W / 32 <= 255 && (H + 7) / 8 <= 255) {
       // masks of <= 500 px (not sampled) walk their active tiles; the list shares the LDS of the block prefix
       p.ntx = W / 32; p.nty = (H + 7) / 8;
@@ -716,6 +977,10 @@ int instance_fit(FitParams p, const CallFacts& f, hipStream_t s, void* workspace
     if (cap > ntiles) cap = ntiles;
     if (cap >= 64) {
       p.list_cap = (int)cap;
+      if (f.method == LA3D_METHOD_CONVEX_HULL) {
+        p.geo = static_cast<double*>(f.hull_area);
+        return launch_hull<true, false>(p, fixed + ((size_t)cap * 2 > poly_stage ? (size_t)cap * 2 : poly_stage), s);
+      }
       if (mask != nullptr && B > 256) {
         // u8 planes: the resident groups start one group's stream time apart - 256 x H*W bytes at the ~6.4 TB/s a pure reader gets:
         // 12.3 us for 640x480 (the kernel applies it only under the size-ordered launch; LA3D_STAGGER_US overrides, 0 switches it
@@ -728,6 +993,12 @@ int instance_fit(FitParams p, const CallFacts& f, hipStream_t s, void* workspace
       }
       return launch_fit<true, true, false, true>(p, fixed + ((size_t)cap * 2 > poly_stage ? (size_t)cap * 2 : poly_stage), s, workspace);
     }
+  }
+  if (f.method == LA3D_METHOD_CONVEX_HULL) {
+    // full-mask hull on a frame outside the tiled vector path: no per-column structure to take the hull from - every instance is
+    // refused (LA3D_BOX_UNSUPPORTED); reference-subsample mode (sample_idx) covers such frames
+    hipLaunchKernelGGL(hull_refuse_kernel, dim3((B + 255) / 256), dim3(256), 0, s, p);
+    return check_launch("hull_refuse_kernel");
   }
   lds += poly_stage;
   if (ldsmask) return vec ? launch_fit<true, true, false>(p, lds, s, workspace) : launch_fit<false, true, false>(p, lds, s);

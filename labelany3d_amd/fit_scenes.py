@@ -39,7 +39,7 @@ from typing import Dict, Iterable, Iterator, List, Optional
 import numpy as np
 import torch
 
-from ._lib import lib
+from ._lib import lib, method_code
 from .batched import _dev, _upload_many, draw_sample_idx
 from .jsonout import SceneRecords, format_scenes
 from .masks import fit_instances_ex, mask_stats_poly, mask_stats_rle, pack_polygons, pack_rle, pad_depth_rows, padded_width
@@ -177,7 +177,11 @@ class ScenePipeline:
 
     def __init__(self, device=None, batch_images: int = 256, subsample: bool = False, boundary_threshold: int = 10,
                  scale_threshold: int = 100, loader_threads: int = 16, write: bool = True, out_name: str = OUT_NAME, rng=None,
-                 timings: Optional[dict] = None):
+                 timings: Optional[dict] = None, method: str = "pca"):
+        """``method``: "pca" | "convex_hull" - the reference's ``bbox_method`` (save_3d_with_ground_alignment_bbox); see
+        ``fit_instances`` for what the hull method covers in full-mask mode."""
+        method_code(method)   # (the reference's error for an unknown method, before any device work)
+        self.method = method
         self.dev = _dev(device)
         self.batch_images = int(batch_images)
         self.subsample = bool(subsample)
@@ -287,13 +291,13 @@ class ScenePipeline:
         """output buffers + workspace of a fit call, kept per (kind, ring slot, frame size) and sized by capacity (the number of
         annotations changes with every batch; a fresh InstanceFitter per call cost ~1 ms of allocations)"""
         from .batched import InstanceFitter
-        key = (kind, parity, H, W)
+        key = (kind, parity, H, W, self.method)
         f = self._fitters.pop(key, None)
         if f is None or f.B < B:
             cap = 256
             while cap < B:
                 cap *= 2
-            f = InstanceFitter(cap, H, W, self.dev)
+            f = InstanceFitter(cap, H, W, self.dev, method=self.method)
         self._fitters[key] = f                      # (most recently used last)
         while len(self._fitters) > 24:              # a run over many frame sizes: the least recently used sizes give their memory back
             self._fitters.pop(next(iter(self._fitters)))
@@ -319,7 +323,8 @@ class ScenePipeline:
             ii, hint = up[-2], up[-1]
             if not two_phase:
                 res = fit_instances_ex(pr.depth, K, image_index=ii, filter=self.flt, area_hint=hint, device=self.dev, frame_width=W,
-                                       _fitter=self._fitter(kind, pr.parity, len(g["seg"]), H, padded_width(W)), **masks_kw)
+                                       _fitter=self._fitter(kind, pr.parity, len(g["seg"]), H, padded_width(W)), method=self.method,
+                                       **masks_kw)
                 results[kind] = (res["boxes"], res["status"], g)
             else:
                 # the keep rule first (its statistics also give N for the subsample draw), then the fit of the whole group with
@@ -376,7 +381,7 @@ class ScenePipeline:
                         si[r] = draws[n]
             gr = ground[kind] if np.isfinite(ground[kind][:, 0]).any() else None
             res = fit_instances_ex(pr.depth, K, image_index=ii, filter=self.flt, area_hint=hint, ground=gr, sample_idx=si, device=self.dev,
-                                   frame_width=pr.W, **masks_kw)
+                                   frame_width=pr.W, method=self.method, **masks_kw)
             out[kind] = (res["boxes"], res["status"], g)
         return out
 
@@ -560,7 +565,7 @@ def synthetic_scenes(n_scenes: int, seed: int = 0, H: int = 480, W: int = 640, m
     return scenes, data
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--scenes", required=True, help="directory holding one folder per image (depth_map.npy, cam_params.json)")
     ap.add_argument("--annotations", help="COCO / COCONut annotation JSON (default: <scenes>/annotations.json)")
@@ -574,7 +579,13 @@ def main(argv=None) -> int:
     ap.add_argument("--file-categories", action="store_true", help="category names from the annotation file's own `categories` block "
                                                                    "(default: the reference's built-in COCO / COCONut table, src/util.py:419-462)")
     ap.add_argument("--make-synthetic", type=int, default=0, metavar="N", help="first write a synthetic tree of N scenes into --scenes")
-    args = ap.parse_args(argv)
+    ap.add_argument("--bbox-method", choices=("pca", "convex_hull"), default="pca",
+                    help="yaw estimator (the reference's bbox_method): principal axis, or the minimum-area rectangle over the hull edges")
+    return ap
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
     if args.make_synthetic:
         synthetic_scenes(args.make_synthetic, seed=0, root=args.scenes)
     ann = args.annotations or os.path.join(args.scenes, "annotations.json")
@@ -582,7 +593,8 @@ def main(argv=None) -> int:
         np.random.seed(args.seed)
     torch.cuda.set_device(args.gpu_idx)
     timings: dict = {}
-    pipe = ScenePipeline(device=torch.device("cuda", args.gpu_idx), batch_images=args.batch_images, subsample=args.subsample, timings=timings)
+    pipe = ScenePipeline(device=torch.device("cuda", args.gpu_idx), batch_images=args.batch_images, subsample=args.subsample, timings=timings,
+                         method=args.bbox_method)
     t0 = time.perf_counter()
     n_scenes = n_boxes = 0
     for sc, recs in pipe.run(scenes_from_disk(args.scenes, ann, args.start_index, args.end_index, args.skip_done,

@@ -28,7 +28,7 @@ import threading
 import numpy as np
 import torch
 
-from . import options
+from . import _lib, options
 from ._lib import AUX, BOX_FILTERED, REC, check, lib
 from .batched import (InstanceFitter, _as_dev, _bulk, _dev, _filter_args, _fit_args, _fit_inputs, _ptr, _record, _stream,  # noqa: F401
                       _upload_many, pad_rows_f32)
@@ -248,7 +248,8 @@ def pad_depth_rows(depth, device=None):
 
 
 def fit_instances_ex(depth, K, masks=None, rles=None, polys=None, ground=None, sample_idx=None, image_index=None, filter=None,
-                     image_size=None, area_hint=None, stream=None, device=None, frame_width=None, _fitter=None, _stats=None):
+                     image_size=None, area_hint=None, stream=None, device=None, frame_width=None, _fitter=None, _stats=None,
+                     method: str = "pca"):
     """Every option of the fit in one call (C-ABI ``la3d_fit_instances_ex``): exactly one of ``masks`` (B,H,W) u8 / bool,
     ``rles`` (COCO RLE list or ``pack_rle`` tuple), ``polys`` (``pack_polygons`` tuple) gives the masks; ``filter`` as in
     ``fit_instances_poly`` (run-length / polygon masks only); ``image_size=(width, height)`` adds the 2-D boxes the reference's
@@ -257,7 +258,9 @@ def fit_instances_ex(depth, K, masks=None, rles=None, polys=None, ground=None, s
     annotation's ``area``, a preceding filter's statistics) - the size-balanced launch order then skips its estimate pass over the
     masks; a hint only orders the work.  ``frame_width`` (run-length / polygon masks): None - a frame whose width is not a multiple
     of 32 has its depth rows padded here (``pad_depth_rows``); an int - ``depth`` already IS padded (its last dimension is the padded
-    width) and the masks' frame is ``frame_width`` columns wide.  Returns a dict: boxes, status, aux, and stats / boxes2d when asked."""
+    width) and the masks' frame is ``frame_width`` columns wide.  ``method``: "pca" | "convex_hull" (see ``fit_instances``).
+    Returns a dict: boxes, status, aux, and stats / boxes2d when asked."""
+    meth = _lib.method_code(method)   # (the reference's error for an unknown method, before any device work)
     dev = _dev(device)
     if (masks is not None) + (rles is not None) + (polys is not None) != 1:
         raise ValueError("give exactly one of masks / rles / polys")
@@ -304,8 +307,8 @@ def fit_instances_ex(depth, K, masks=None, rles=None, polys=None, ground=None, s
     out = {}
     with torch.cuda.device(dev):
         # (_fitter / _stats: buffers a per-image caller keeps between calls - fit_annotations - instead of allocating them per call)
-        f = _fitter if _fitter is not None else InstanceFitter(B, H, W, dev)
-        if f.B < B or (f.H, f.W) != (H, W):
+        f = _fitter if _fitter is not None else InstanceFitter(B, H, W, dev, method=method)
+        if f.B < B or (f.H, f.W) != (H, W) or (meth != f.method and meth != _lib.METHOD_PCA):
             raise ValueError("_fitter too small for this call")
         out.update(boxes=f.boxes[0][:B], status=f.status[0][:B], aux=f.aux[0][:B])   # (a kept fitter may have more rows than this call)
         if filter:
@@ -323,7 +326,7 @@ def fit_instances_ex(depth, K, masks=None, rles=None, polys=None, ground=None, s
         a = _fit_args(B, H, W, _ptr(d), P, _ptr(k), k.shape[0], _ptr(f.boxes[0]), _ptr(f.status[0]), _ptr(f.aux[0]),
                       _ptr(f.workspace[0]), _stream(stream), image_index=_ptr(ii), ground=_ptr(g), sample_idx=_ptr(si), filter=filter,
                       stats=_ptr(out.get("stats")), proj=_ptr(out.get("boxes2d")), image_size=image_size, area_hint=_ptr(ah),
-                      opts=options.codes(), frame_width=fw, **kind)
+                      opts=options.codes(), frame_width=fw, method=meth, **kind)
         check(lib.la3d_fit_instances_ex(C.byref(a)), "la3d_fit_instances_ex")
     _record(stream, d, k, ii, g, si, *keep, f.workspace, *out.values())
     return out
@@ -335,16 +338,16 @@ _ANN_CACHE: dict = {}   # (B, H, W, device) -> (InstanceFitter, stats, pinned re
 _ANN_LOCK = threading.Lock()
 
 
-def _ann_buffers(B, H, W, dev, kind):
+def _ann_buffers(B, H, W, dev, kind, method="pca"):
     # per THREAD: two threads calling fit_annotations with equal shapes must not share a fitter, its statistics
     # buffer and its pinned read-back buffer; the dict itself is guarded by a lock
-    key = (B, H, W, kind, dev.index if dev.index is not None else torch.cuda.current_device(), threading.get_ident())
+    key = (B, H, W, kind, dev.index if dev.index is not None else torch.cuda.current_device(), threading.get_ident(), method)
     with _ANN_LOCK:
         ent = _ANN_CACHE.get(key)
         if ent is None and len(_ANN_CACHE) >= 64:
             _ANN_CACHE.pop(next(iter(_ANN_CACHE)))
     if ent is None:
-        f = InstanceFitter(B, H, W, dev)
+        f = InstanceFitter(B, H, W, dev, method=method)
         # the pinned buffer mirrors the head of the fitter's arena: boxes | aux | status (256-aligned pieces), without the workspace
         ent = (f, torch.empty((B, 4), dtype=torch.int32, device=dev), torch.empty(f._arena.numel() - f.workspace.numel(), dtype=torch.uint8, pin_memory=True))
         with _ANN_LOCK:
@@ -353,7 +356,7 @@ def _ann_buffers(B, H, W, dev, kind):
 
 
 def fit_annotations(annotations, image_size, depth, K, ground=None, boundary_threshold: int = 10, scale_threshold: int = 100,
-                    image_index=None, device=None, to_host: bool = False):
+                    image_index=None, device=None, to_host: bool = False, method: str = "pca"):
     """``read_bounding_boxes_segmentations`` (reference src/util.py:336-383) and the box fit in ONE pass over the annotations:
     crowd annotations are skipped (:355-357); every other annotation's segmentation is decoded / rasterised once, inside the
     fit launch, which also evaluates the keep rule (:375) on the bit image and fits only the kept instances (``filter=`` of
@@ -364,14 +367,16 @@ def fit_annotations(annotations, image_size, depth, K, ground=None, boundary_thr
     annotations in annotation order, the last two on the GPU - or, with ``to_host=True``, as NumPy arrays taken from the ONE
     packed read-back (records | aux | status in a single copy into pinned memory) that the keep decision needs anyway: no
     further device work, which is what a caller writing JSON wants.  Output buffers, workspace and the pinned buffer are kept per
-    (B, H, W) between calls (the per-image pattern repeats a handful of shapes)."""
+    (B, H, W) between calls (the per-image pattern repeats a handful of shapes).  ``method``: "pca" | "convex_hull" (see
+    ``fit_instances``)."""
+    _lib.method_code(method)   # (the reference's error for an unknown method, before any device work)
     W_img, H_img = int(image_size[0]), int(image_size[1])
     dev = _dev(device)
     groups = split_annotations(annotations)
     flt = {"boundary_threshold": boundary_threshold, "scale_threshold": scale_threshold}
     if (to_host and isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous()
             and not isinstance(K, torch.Tensor) and not isinstance(ground, torch.Tensor) and not isinstance(image_index, torch.Tensor)):
-        return _fit_annotations_host(annotations, groups, W_img, H_img, depth, K, ground, image_index, flt)
+        return _fit_annotations_host(annotations, groups, W_img, H_img, depth, K, ground, image_index, flt, method)
     Wp = padded_width(W_img)
     if Wp != W_img and any(idx for idx, _ in groups.values()):   # a frame of odd width: rows padded once for both segmentation kinds
         with torch.cuda.device(dev):
@@ -404,9 +409,9 @@ def fit_annotations(annotations, image_size, depth, K, ground=None, boundary_thr
         g_d = up[-4] if up[-4] is not None else g
         ii_d = up[-3] if up[-3] is not None else ii
         K_d = up[-1] if up[-1] is not None else K
-        fitter, stats_buf, pin = _ann_buffers(len(idx), Hh, padded_width(Ww), dev, kind)
+        fitter, stats_buf, pin = _ann_buffers(len(idx), Hh, padded_width(Ww), dev, kind, method)
         res = fit_instances_ex(depth, K_d, ground=g_d, image_index=ii_d, device=dev, filter=flt, area_hint=up[-2], _fitter=fitter,
-                               _stats=stats_buf, frame_width=Ww, **kw)
+                               _stats=stats_buf, frame_width=Ww, method=method, **kw)
         head = fitter._arena[:pin.numel()]
         pin.copy_(head, non_blocking=True)      # records | aux | status of this group: one copy, read after the one synchronisation
         sels.append(sel); box_all.append(res["boxes"]); st_all.append(res["status"]); pins.append((pin, len(idx)))
@@ -456,12 +461,14 @@ def annotation_areas(annotations, default: float = 0.0) -> np.ndarray:
     return np.asarray([float(a.get("area", default) or default) for a in annotations], dtype=np.float64)
 
 
-def fit_annotations_all(annotations, image_size, depth, K, ground=None, image_index=None, filter=None, device=None):
+def fit_annotations_all(annotations, image_size, depth, K, ground=None, image_index=None, filter=None, device=None,
+                        method: str = "pca"):
     """The fit of ``fit_annotations`` with one record per ANNOTATION, in annotation order, on the GPU: ``(boxes (n,39) f64,
     status (n,) i32)``.  Skipped annotations (crowd, no segmentation) and - with ``filter`` (a dict of ``boundary_threshold`` /
     ``scale_threshold``, or True for the reference's 10 / 100) - the ones the keep rule drops carry status 6 and a NaN record.
     One launch per segmentation kind present; the segmentations are decoded / rasterised inside the fit kernel (no u8 plane
-    exists anywhere).  This is the rank-local step of ``shard.fit_annotations_sharded``."""
+    exists anywhere).  This is the rank-local step of ``shard.fit_annotations_sharded``.  ``method``: "pca" | "convex_hull"."""
+    _lib.method_code(method)   # (the reference's error for an unknown method, before any device work)
     W_img, H_img = int(image_size[0]), int(image_size[1])
     dev = _dev(device)
     n = len(annotations)
@@ -484,7 +491,7 @@ def fit_annotations_all(annotations, image_size, depth, K, ground=None, image_in
         hint = None if any(v is None for v in ar) else np.clip(np.asarray(ar, dtype=np.float64), 0, 2**31 - 1).astype(np.int32)
         kw = dict(rles=segs) if kind == "rle" else dict(polys=pack_polygons(segs, H_img, W_img))
         res = fit_instances_ex(depth, K, ground=take(ground), image_index=take(image_index), device=dev, filter=flt, area_hint=hint,
-                               frame_width=W_img, **kw)
+                               frame_width=W_img, method=method, **kw)
         boxes.index_copy_(0, sel_t, res["boxes"])
         status.index_copy_(0, sel_t, res["status"])
     return boxes, status
@@ -499,7 +506,7 @@ def _raw_stream(dev_index: int) -> int:
         return torch.cuda.current_stream(dev_index).cuda_stream
 
 
-def _fit_annotations_host(annotations, groups, W_img, H_img, depth, K, ground, image_index, flt):
+def _fit_annotations_host(annotations, groups, W_img, H_img, depth, K, ground, image_index, flt, method="pca"):
     """``fit_annotations(to_host=True)`` with the depth plane(s) resident and everything else on the host: ONE foreign call per
     segmentation kind (``la3d_fit_annotations_host``: the small arrays go up through the library's pinned block, the records come back
     through it, the call polls a completion flag) - no torch tensor, no wrapper layers in between."""
@@ -547,7 +554,7 @@ def _fit_annotations_host(annotations, groups, W_img, H_img, depth, K, ground, i
         # depth (and the padding above) was produced on - torch's current stream of that device
         a = _fit_args(B, Hh, Wp, depth.data_ptr(), P, Kh.ctypes.data, Kh.shape[0], out.ctypes.data, st.ctypes.data, None, None,
                       _raw_stream(dev_index), image_index=host(ii), ground=host(g), area_hint=host(hint), filter=flt,
-                      frame_width=Ww if Wp != Ww else 0, **masks_kw)
+                      frame_width=Ww if Wp != Ww else 0, method=_lib.method_code(method), **masks_kw)
         if dev_index == torch.cuda.current_device():
             check(lib.la3d_fit_annotations_host(C.byref(a)), "la3d_fit_annotations_host")
         else:
@@ -579,7 +586,8 @@ def segmentations_to_masks(segmentations, H: int, W: int, device=None) -> torch.
     return out
 
 
-def fit_instances_poly(depth, polys, K, ground=None, sample_idx=None, image_index=None, stream=None, device=None, filter=None):
+def fit_instances_poly(depth, polys, K, ground=None, sample_idx=None, image_index=None, stream=None, device=None, filter=None,
+                       method: str = "pca"):
     """fit_instances with polygon masks: the parts are rasterised inside the fit kernel, straight into its LDS bit image
     (cv2.fillPoly semantics, reference src/util.py:386-400).  Arguments and returns as ``labelany3d_amd.fit_instances``;
     ``polys`` is the tuple from ``pack_polygons``.
@@ -592,17 +600,18 @@ def fit_instances_poly(depth, polys, K, ground=None, sample_idx=None, image_inde
     branch: height = last row - first row + 1) into the same launch: dropped instances get status 6 and a NaN record and cost no
     passes; a fourth return value holds the (B,4) statistics (area, rows, span, edge pixels) as ``mask_stats_poly`` gives them."""
     r = fit_instances_ex(depth, K, polys=polys, ground=ground, sample_idx=sample_idx, image_index=image_index, filter=filter,
-                         stream=stream, device=device)
+                         stream=stream, device=device, method=method)
     return (r["boxes"], r["status"], r["aux"]) + ((r["stats"],) if filter else ())
 
 
-def fit_instances_rle(depth, rles, K, ground=None, sample_idx=None, image_index=None, stream=None, device=None, filter=None):
+def fit_instances_rle(depth, rles, K, ground=None, sample_idx=None, image_index=None, stream=None, device=None, filter=None,
+                      method: str = "pca"):
     """fit_instances with run-length masks: the runs are decoded inside the fit kernel, straight into its LDS
     bit image.  Arguments and returns as ``labelany3d_amd.fit_instances``; ``rles`` is a list of COCO RLE
     objects or the tuple from ``pack_rle``.  ``filter``: as in ``fit_instances_poly`` (RLE branch of the rule: height = rows
     holding a pixel, src/util.py:368-369)."""
     r = fit_instances_ex(depth, K, rles=rles, ground=ground, sample_idx=sample_idx, image_index=image_index, filter=filter,
-                         stream=stream, device=device)
+                         stream=stream, device=device, method=method)
     return (r["boxes"], r["status"], r["aux"]) + ((r["stats"],) if filter else ())
 
 

@@ -17,7 +17,7 @@ import torch
 from .batched import InstanceFitter
 
 
-def fit_batches(batches: Iterable, streams: int = 2, copy: bool = True) -> Iterator[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
+def fit_batches(batches: Iterable, streams: int = 2, copy: bool = True, method: str = "pca") -> Iterator[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
     """``batches`` yields ``(depth, masks, K)`` tuples or dicts with the keyword arguments of ``InstanceFitter.run``
     (``depth, masks, K, ground, sample_idx, image_index``); all tensors on the GPU with the ABI's dtypes (f32 / u8|bool / f64 /
     f64 / i32 / i32).  Yields ``(boxes (B,39), status (B,), aux (B,4))`` per batch, in order; every result is complete (its
@@ -29,7 +29,10 @@ def fit_batches(batches: Iterable, streams: int = 2, copy: bool = True) -> Itera
     ``copy=True`` (default) hands out clones: results stay valid for as long as the caller keeps them (``list(fit_batches(..))``
     is safe).  ``copy=False`` hands out views of internal buffers (``streams + 1`` rotating sets per batch shape): a result is
     overwritten once the generator has been advanced TWICE more - use it before asking for the result after next.
-    The size-balanced launch order is switched off PER CALL (``la3d_fit_args::opt_launch_order``): no process state is touched."""
+    The size-balanced launch order is switched off PER CALL (``la3d_fit_args::opt_launch_order``): no process state is touched.
+    ``method``: "pca" | "convex_hull" for every batch (see ``fit_instances``)."""
+    from ._lib import method_code
+    method_code(method)   # (the reference's error for an unknown method, before any device work)
     dev = None
     pool, fitters = [], {}
     pending = []          # (event, result) in issue order
@@ -50,7 +53,7 @@ def fit_batches(batches: Iterable, streams: int = 2, copy: bool = True) -> Itera
         B, H, W = kw["masks"].shape
         key = (B, H, W, k % nbuf)
         if key not in fitters:
-            fitters[key] = InstanceFitter(B, H, W, dev)
+            fitters[key] = InstanceFitter(B, H, W, dev, method=method)
         while len(pending) >= len(pool):    # keep at most `streams` batches in flight: hand out the oldest result
             ev, res = pending.pop(0)
             ev.synchronize()

@@ -132,8 +132,20 @@ def gather_boxes(boxes: torch.Tensor, status: torch.Tensor, dst: int = 0, group=
     return allp[:, :boxes.shape[1]].contiguous(), allp[:, boxes.shape[1]].to(status.dtype), counts
 
 
+def _check_method(method) -> None:
+    """The reference's error for an unknown yaw method (src/util_3dbox.py:151), raised before any collective or device work.
+    (Spelled out here: this module must import on ranks that have no GPU library loaded.)"""
+    if method not in ("pca", "convex_hull"):
+        raise ValueError(f"Unknown method: {method}. Use 'pca' or 'convex_hull'")
+
+
+def _method_kw(method) -> dict:
+    return {} if method == "pca" else {"method": method}   # (an injected fit_fn without the keyword keeps working for "pca")
+
+
 def fit_instances_sharded(depth, masks, K, image_index, ground=None, sample_idx=None, areas=None, dst: int = 0, group=None,
-                          fit_fn: Optional[Callable] = None, load_fn: Optional[Callable] = None, timings: Optional[dict] = None):
+                          fit_fn: Optional[Callable] = None, load_fn: Optional[Callable] = None, timings: Optional[dict] = None,
+                          method: str = "pca"):
     """Every rank passes the same METADATA (``image_index``, optionally ``areas``); images are split into contiguous,
     cost-balanced ranges (``plan_shards``), each rank fits the instances of its images on its own GPU and the records are
     gathered on ``dst`` in global instance order.
@@ -146,7 +158,9 @@ def fit_instances_sharded(depth, masks, K, image_index, ground=None, sample_idx=
     ``areas`` (B,) are per-instance mask areas for the balance (None: count-based).  ``fit_fn`` defaults to
     labelany3d_amd.fit_instances (injectable so the sharding logic is testable on CPU with gloo).  ``timings`` (a dict, optional):
     filled with this rank's ``load_s`` / ``fit_s`` / ``gather_s`` wall-clock seconds (the device is synchronised around each
-    stage then, which a production call has no reason to do) and its shard."""
+    stage then, which a production call has no reason to do) and its shard.  ``method``: "pca" | "convex_hull", handed to
+    ``fit_fn`` as a keyword when it is not "pca"."""
+    _check_method(method)
     if fit_fn is None:
         from .batched import fit_instances as fit_fn
     world = dist.get_world_size(group)
@@ -178,7 +192,7 @@ def fit_instances_sharded(depth, masks, K, image_index, ground=None, sample_idx=
         si = None if sample_idx is None else sample_idx[sh.inst_lo:sh.inst_hi]
     t1 = _sync()
     if sh.inst_hi > sh.inst_lo:
-        boxes, status, _ = fit_fn(d, m, k, ground=g, sample_idx=si, image_index=local_img)
+        boxes, status, _ = fit_fn(d, m, k, ground=g, sample_idx=si, image_index=local_img, **_method_kw(method))
     else:  # a rank without instances still takes part in the gather
         dev = m.device if isinstance(m, torch.Tensor) else torch.device("cpu")
         boxes = torch.zeros((0, 39), dtype=torch.float64, device=dev)
@@ -193,7 +207,8 @@ def fit_instances_sharded(depth, masks, K, image_index, ground=None, sample_idx=
 
 
 def fit_annotations_sharded(annotations, image_size, image_index, num_images: int, depth_loader: Callable, ground=None, areas=None,
-                            filter=None, dst: int = 0, group=None, fit_fn: Optional[Callable] = None, timings: Optional[dict] = None):
+                            filter=None, dst: int = 0, group=None, fit_fn: Optional[Callable] = None, timings: Optional[dict] = None,
+                            method: str = "pca"):
     """BASELINE config 4 on the reference's own annotation formats (round 5): COCO / COCONut annotations - polygon parts or run
     lengths, ``src/util.py:336-383``, ``src/download_coconut.py:167-199`` - sharded per image across the ranks, never expanded to
     u8 planes (860 k instances are 264 GB of planes and < 1 GB of polygons / run lengths; the fit kernel decodes them into its LDS
@@ -204,7 +219,9 @@ def fit_annotations_sharded(annotations, image_size, image_index, num_images: in
     ``area`` fields: count-based).  Each rank fits its annotation range in one launch per segmentation kind
     (``masks.fit_annotations_all``; ``filter`` = the reference's keep rule fused into the fit) and the records travel to ``dst`` in ONE
     gather, one record per annotation in global order (status 6 = skipped / dropped by the keep rule).
-    ``fit_fn(annotations, image_size, depth, K, ground=, image_index=, filter=) -> (boxes, status)`` is injectable (CPU tests)."""
+    ``fit_fn(annotations, image_size, depth, K, ground=, image_index=, filter=) -> (boxes, status)`` is injectable (CPU tests).
+    ``method``: "pca" | "convex_hull", handed to ``fit_fn`` as a keyword when it is not "pca"."""
+    _check_method(method)
     if fit_fn is None:
         from .masks import fit_annotations_all as fit_fn
     from .masks import annotation_areas
@@ -232,7 +249,7 @@ def fit_annotations_sharded(annotations, image_size, image_index, num_images: in
     if n > 0:
         g = None if ground is None else ground[sh.inst_lo:sh.inst_hi]
         boxes, status = fit_fn(annotations[sh.inst_lo:sh.inst_hi], (W, H), depth, K, ground=g,
-                               image_index=(img[sh.inst_lo:sh.inst_hi] - sh.img_lo).astype(np.int32), filter=filter)
+                               image_index=(img[sh.inst_lo:sh.inst_hi] - sh.img_lo).astype(np.int32), filter=filter, **_method_kw(method))
     else:  # a rank without annotations still takes part in the gather
         dev = depth.device if isinstance(depth, torch.Tensor) else torch.device("cpu")
         boxes = torch.zeros((0, 39), dtype=torch.float64, device=dev)
