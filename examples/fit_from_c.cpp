@@ -4,8 +4,9 @@
 // Builds B synthetic instances (private depth planes, one rectangle each, a ground plane per instance) with a small
 // LCG, runs la3d_fit_instances on HIP buffers and prints status + the 39 doubles of every record in hex-exact form
 // ("%a"), then repeats the fit through la3d_fit_instances_ex (C struct argument block) with the 2-D boxes of the records ("P"
-// lines).  tests/test_gpu_cabi.py regenerates the same inputs in NumPy and checks the printed records against the oracle.
+// lines) and, with the masks packed to bit planes, through la3d_fit_instances_bits.  tests/test_gpu_cabi.py regenerates the same inputs in NumPy and checks the printed records against the oracle.
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -89,6 +90,31 @@ int main(int argc, char** argv) {
       printf("P");
       for (int k = 0; k < 8; ++k) printf(" %a", pr[(size_t)i * 8 + k]);
       printf("\n");
+    }
+    // the same masks once more as bit planes (1 bit per pixel, la3d.h "masks as bit planes"): packed on the device, then fitted
+    // through the same block without its u8 pointer - same status, same records to rounding (another engine may have fitted the u8 call)
+    {
+      const size_t nw = la3d_mask_bits_words(H, W);
+      uint32_t* d_bits;
+      int32_t* d_status3;
+      HIPCHK(hipMalloc(&d_bits, (size_t)B * nw * 4)); HIPCHK(hipMalloc(&d_status3, (size_t)B * 4));
+      if (la3d_pack_mask_bits(d_mask, (int64_t)HW, B, H, W, W, d_bits, (int64_t)nw, stream) != LA3D_SUCCESS) { fprintf(stderr, "la3d_pack_mask_bits: %s\n", la3d_last_error()); return 11; }
+      la3d_fit_args b = a;
+      b.mask = nullptr; b.proj = nullptr; b.status = d_status3;
+      if (la3d_fit_instances_bits(&b, d_bits, (int64_t)nw, LA3D_BITS_HEIGHT_ROWS) != LA3D_SUCCESS) { fprintf(stderr, "la3d_fit_instances_bits: %s\n", la3d_last_error()); return 12; }
+      HIPCHK(hipStreamSynchronize(stream));
+      std::vector<double> out3(out.size());
+      std::vector<int32_t> status3(B);
+      HIPCHK(hipMemcpy(out3.data(), d_out2, out3.size() * 8, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(status3.data(), d_status3, (size_t)B * 4, hipMemcpyDeviceToHost));
+      for (int i = 0; i < B; ++i) {
+        bool same = status3[i] == status[i];
+        for (int k = 0; same && status[i] == LA3D_BOX_OK && k < 15; ++k) {
+          const double x = out[(size_t)i * LA3D_REC + k], y = out3[(size_t)i * LA3D_REC + k];
+          same = fabs(x - y) <= 1e-9 * (fabs(x) > 1.0 ? fabs(x) : 1.0);
+        }
+        if (!same) { fprintf(stderr, "la3d_fit_instances_bits: instance %d differs from the u8 call\n", i); return 13; }
+      }
     }
     a.struct_size = 8;   // a truncated argument block is an error, not a crash
     if (la3d_fit_instances_ex(&a) != LA3D_ERR_ARG) { fprintf(stderr, "expected LA3D_ERR_ARG for a short struct\n"); return 10; }

@@ -297,6 +297,53 @@ int la3d_fit_instances_ex(const la3d_fit_args* args);
  *    area), equal to it for a PCA call, 0 for B <= 0.  Only struct_size, B, H, W and method of the block are read. */
 size_t la3d_fit_workspace_bytes(const la3d_fit_args* args);
 
+/* ---- masks as bit planes ---------------------------------------------------------------------------------------------
+ * The fit kernel turns every mask into a row-major, LSB-first bit image in LDS; a bit plane IS that image, 1 bit per pixel
+ * (38 400 B instead of 307 200 B for 640x480), copied in without any decode.
+ *
+ * FORMAT.  Per instance one plane of nwords = la3d_mask_bits_words(H, W) = ceil(H*W / 32) uint32 words: pixel (v, u) of a frame
+ * stored W pixels wide is bit (v*W + u) & 31 of word (v*W + u) >> 5 - np.packbits(mask.reshape(B, -1), axis=1,
+ * bitorder="little") viewed as little-endian uint32.  Planes lie bits_plane_stride words apart (>= nwords; what lies between
+ * two planes is never read as mask and never written by the packers).  Bits of the last word past H*W are ignored by every
+ * kernel (cleared in LDS, not trusted).  Rows padded on the right (la3d_fit_args::frame_width, W % 32 == 0): the bits of
+ * columns >= frame_width MUST be zero - the packers below guarantee it; a caller who packs by hand owns that.
+ * The base must be 4-byte aligned; a 16-byte aligned base with bits_plane_stride % 4 == 0 streams in 16-byte groups.
+ *
+ * la3d_fit_instances_bits: la3d_fit_instances_ex with the masks given as bit planes.  args->mask, rle_counts and poly_xy must all
+ * be NULL; every other field of the block means what it means there: ground, sample_idx, image_index, k_stride, filter_*, stats,
+ * proj, area_hint, opt_*, frame_width, method (LA3D_METHOD_CONVEX_HULL included, with its workspace size), stream.  The call
+ * runs on the instance engine at every batch size (opt_engine pins give way, as for hull calls).  Without area_hint the
+ * size-balanced launch order takes its keys from an exact popcount of the planes.  H*W <= 1048576, else LA3D_ERR_UNSUPPORTED.
+ * flags: the height rule of the fused filter (filter_boundary >= 0 and filter_max_edge > 0).  The reference has one per annotation
+ * kind and a bit plane does not say where it came from: LA3D_BITS_HEIGHT_ROWS (0) = rows holding a pixel (run lengths,
+ * src/util.py:368-369), LA3D_BITS_HEIGHT_SPAN = last row - first row + 1 (polygons, :328-335).  Other bits: LA3D_ERR_ARG. */
+#define LA3D_BITS_HEIGHT_ROWS 0
+#define LA3D_BITS_HEIGHT_SPAN 1
+size_t la3d_mask_bits_words(int H, int W);   /* host, no device; 0 for H <= 0 or W <= 0 */
+int la3d_fit_instances_bits(const la3d_fit_args* args, const uint32_t* mask_bits, int64_t bits_plane_stride, int32_t flags);
+
+/* Packers (streaming kernels; any plane stride, any base alignment of the input: a general form stands behind the 16-byte form).
+ * Output: B planes of la3d_mask_bits_words(H, W_out) words, bits_plane_stride words apart, rows padded from W to W_out >= W
+ * columns with zero bits (W_out = W: none; the next multiple of 32 is what the tiled forms of the fit want).  Only the
+ * words of a plane are written.
+ * la3d_pack_mask_bits:   mask dev u8, plane b at mask + b*mask_plane_stride (bytes, >= H*W); non-zero byte -> 1.
+ * la3d_pack_logits_bits: logits dev f32 / f16 / bf16 (LA3D_DTYPE_*), plane b at logits + b*plane_stride ELEMENTS; bit = x > threshold
+ *                        (compared in float32; NaN -> 0, +inf -> 1 unless threshold is +inf, -inf -> 0).
+ * la3d_unpack_mask_bits: planes stored W_in pixels wide -> mask dev u8 [B][H][W] (0 / 1), the first W <= W_in columns.
+ * la3d_mask_stats_bits:  the four quantities of la3d_mask_stats per plane stored W pixels wide; frame_width (0 = W) = the image
+ *                        columns, from which the right border strip is taken.  H*W <= 1048576. */
+#define LA3D_DTYPE_F32 0
+#define LA3D_DTYPE_F16 1
+#define LA3D_DTYPE_BF16 2
+int la3d_pack_mask_bits(const uint8_t* mask, int64_t mask_plane_stride, int B, int H, int W, int W_out, uint32_t* bits,
+                        int64_t bits_plane_stride, void* stream);
+int la3d_pack_logits_bits(const void* logits, int dtype, int64_t plane_stride, float threshold, int B, int H, int W, int W_out,
+                          uint32_t* bits, int64_t bits_plane_stride, void* stream);
+int la3d_unpack_mask_bits(const uint32_t* bits, int64_t bits_plane_stride, int B, int H, int W_in, int W, uint8_t* mask,
+                          void* stream);
+int la3d_mask_stats_bits(const uint32_t* bits, int64_t bits_plane_stride, int B, int H, int W, int frame_width, int boundary,
+                         int32_t* stats, void* stream);
+
 /* create_boolean_mask_from_polygon for a batch: polygon parts -> u8 planes mask_out dev [B][H*W] (0/1). */
 int la3d_poly_decode(const int32_t* poly_xy, const int64_t* ring_offsets, const int64_t* inst_rings, int B, int H, int W,
                      uint8_t* mask_out, void* stream);

@@ -13,6 +13,8 @@ METHOD_PCA, METHOD_CONVEX_HULL = 0, 1
 HINT_SMALL_CLOUDS = 0x100
 HINT_HULL_512 = 0x200
 ERR_UNSUPPORTED = -2
+BITS_HEIGHT_ROWS, BITS_HEIGHT_SPAN = 0, 1          # flags of la3d_fit_instances_bits: the height rule of the fused filter
+DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2        # la3d_pack_logits_bits
 
 class FitArgs(C.Structure):
     """``la3d_fit_args`` of include/la3d.h (argument block of la3d_fit_instances_ex); field order is the header's."""
@@ -36,6 +38,13 @@ class FitArgs(C.Structure):
 _SIGS = {
     "la3d_fit_instances_ex": (C.c_int, [C.POINTER(FitArgs)]),
     "la3d_fit_workspace_bytes": (C.c_size_t, [C.POINTER(FitArgs)]),
+    "la3d_fit_instances_bits": (C.c_int, [C.POINTER(FitArgs), C.c_void_p, C.c_int64, C.c_int32]),
+    "la3d_mask_bits_words": (C.c_size_t, [C.c_int, C.c_int]),
+    "la3d_pack_mask_bits": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "la3d_pack_logits_bits": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_int64, C.c_void_p]),
+    "la3d_unpack_mask_bits": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "la3d_mask_stats_bits": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "la3d_version": (C.c_int, []),
     "la3d_last_error": (C.c_char_p, []),
     "la3d_unproject": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int,

@@ -218,12 +218,51 @@ class InstanceFitter:
         check(lib.la3d_fit_instances_ex(C.byref(a)), "la3d_fit_instances_ex")
         return self.boxes[slot], self.status[slot], self.aux[slot]
 
+    def run_bits(self, depth: torch.Tensor, bits, K: torch.Tensor, ground=None, sample_idx=None, image_index=None, slot: int = 0,
+                 stream=None, ws_slot: int = 0, engine=None, launch_order=None, build=None, area_hint=None, method=None,
+                 frame_width: int = 0, height_rule: str = "rows"):
+        """``run`` with the masks given as bit planes (C-ABI ``la3d_fit_instances_bits``; format: include/la3d.h "masks as bit
+        planes"): ``bits`` is the tuple ``masks.pack_mask_bits`` returns, or an int32 device tensor (B, stride) whose rows hold the
+        ``ceil(H*W/32)`` words of a plane stored ``self.W`` pixels wide (``frame_width``: the image columns when the rows are
+        padded, 0 = all).  One launch (two for a hull call) on the caller's stream, capturable into a graph like ``run``."""
+        meth = self._method(method)
+        t, fw = (bits[0], bits[3]) if isinstance(bits, tuple) else (bits, int(frame_width))
+        if isinstance(bits, tuple) and (bits[1], bits[2]) != (self.H, self.W):
+            raise ValueError(f"bit planes of a {bits[1]} x {bits[2]} frame do not match the fitter's {self.H} x {self.W}")
+        stride = _bits_stride(t, self.B, self.H, self.W)
+        a = _fit_args(self.B, self.H, self.W, _ptr(depth), depth.shape[0] if depth.dim() == 3 else 1, _ptr(K),
+                      K.shape[0] if K.dim() == 3 else 1, _ptr(self.boxes[slot]), _ptr(self.status[slot]), _ptr(self.aux[slot]),
+                      _ptr(self.workspace[ws_slot]), _stream(stream, raw=True), image_index=_ptr(image_index),
+                      ground=_ptr(ground), sample_idx=_ptr(sample_idx), area_hint=_ptr(area_hint),
+                      opts=options.codes(engine, launch_order, build), frame_width=0 if fw == self.W else fw, method=meth)
+        check(lib.la3d_fit_instances_bits(C.byref(a), _ptr(t), stride, height_rule_code(height_rule)), "la3d_fit_instances_bits")
+        return self.boxes[slot], self.status[slot], self.aux[slot]
+
     def _method(self, method) -> int:
         """The LA3D_METHOD_* code of a call on this fitter; a hull call needs a fitter whose workspace was sized for it."""
         meth = self.method if method is None else _lib.method_code(method)
         if meth == _lib.METHOD_CONVEX_HULL and self.method != _lib.METHOD_CONVEX_HULL:
             raise ValueError("this InstanceFitter was sized for method='pca': build it with method='convex_hull'")
         return meth
+
+
+def height_rule_code(height_rule) -> int:
+    """``height_rule`` of the bit-plane entries -> LA3D_BITS_HEIGHT_*: "rows" = rows holding a pixel (the reference's rule for run-length
+    annotations, src/util.py:368-369), "span" = last row - first row + 1 (polygons, :328-335)."""
+    code = {"rows": _lib.BITS_HEIGHT_ROWS, "span": _lib.BITS_HEIGHT_SPAN}.get(height_rule) if isinstance(height_rule, str) else None
+    if code is None:
+        raise ValueError(f"unknown height_rule: {height_rule!r}. Use 'rows' or 'span'")
+    return code
+
+
+def _bits_stride(t, B: int, H: int, W: int) -> int:
+    """The plane stride (words) of a bit-plane tensor, checked: int32 on the GPU, (B, >= ceil(H*W/32)), rows dense."""
+    nwords = (H * W + 31) // 32
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 2):
+        raise ValueError("bit planes must be an int32 tensor (B, words) on the GPU")
+    if t.shape[0] != B or t.shape[1] < nwords or (t.shape[1] > 1 and t.stride(1) != 1) or (B > 1 and t.stride(0) < nwords):
+        raise ValueError(f"bit planes {tuple(t.shape)} (strides {t.stride()}) do not hold {B} planes of {nwords} words")
+    return int(t.stride(0)) if B > 1 else max(int(t.shape[1]), nwords)
 
 
 def _filter_args(filter):

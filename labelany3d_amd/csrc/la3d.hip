@@ -76,6 +76,9 @@ static int choose_engine(const FitParams& p, const CallFacts& f, int pin) {
   const int B = p.B, H = p.H, W = p.W;
   // a convex-hull call (la3d_fit_args::method) runs on the instance engine, whatever is pinned: pins change speed, never records
   if (f.method == LA3D_METHOD_CONVEX_HULL) return LA3D_ENGINE_INSTANCE;
+  // masks given as bit planes: the instance engine at every batch size (the engines of several workgroups per instance have no
+  // bit-plane form); pins give way, as for hull calls
+  if (p.mask_bits != nullptr) return LA3D_ENGINE_INSTANCE;
   if (pin == LA3D_ENGINE_DEFAULT || pin == LA3D_ENGINE_ROWS || pin == LA3D_ENGINE_ROWS2) {
     if (rows_applies(p, f) && (pin != LA3D_ENGINE_DEFAULT || B <= config().rows_maxb)) return LA3D_ENGINE_ROWS;
     const bool single_pass_call = p.ground == nullptr && !f.sample && !p.sep_off && f.ldsmask && f.vec && W % 32 == 0 && W / 32 <= 255 &&
@@ -171,11 +174,14 @@ size_t la3d_fit_workspace_bytes(const la3d_fit_args* args) {
   return up256(base) + (size_t)args->B * (full > samp ? full : samp);
 }
 
+struct BitsSource { const uint32_t* planes; int64_t plane_stride; int32_t flags; };   // la3d_fit_instances_bits' own arguments
+
 // Every fit entry ends here with its arguments in one block.  filter_on: the fused instance filter runs (the *_filtered entries
 // always; la3d_fit_instances_ex when filter_boundary >= 0 and filter_max_edge > 0).  who: the entry named in la3d_last_error().
-static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who) {
+// bs: the bit planes of la3d_fit_instances_bits (an internal parameter: the public block is frozen), null for every other entry.
+static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who, const BitsSource* bs = nullptr) {
   const int B = a.B, H = a.H, W = a.W;
-  const bool rle = a.rle_counts != nullptr || a.poly_xy != nullptr;   // "no u8 plane": the mask is decoded into the LDS bit image
+  const bool rle = a.rle_counts != nullptr || a.poly_xy != nullptr || bs != nullptr;   // "no u8 plane": the mask is decoded into the LDS bit image
   if (!a.depth || (!a.mask && !rle) || (a.rle_counts && !a.rle_offsets) || (a.poly_xy && (!a.ring_offsets || !a.inst_rings)) ||
       !a.K || !a.out || !a.status || B < 0 || H <= 0 || W <= 0 ||
       a.depth_plane_stride < 0 || (a.k_stride != 0 && a.k_stride < 9) || (long long)H * W > (1LL << 28)) {
@@ -200,6 +206,11 @@ static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who)
   p.poly_xy = a.poly_xy;
   p.poly_ring_off = reinterpret_cast<const long long*>(a.ring_offsets);
   p.poly_inst_rings = reinterpret_cast<const long long*>(a.inst_rings);
+  if (bs) {
+    p.mask_bits = bs->planes; p.bits_plane_stride = bs->plane_stride;
+    p.bits_vec = ((reinterpret_cast<uintptr_t>(bs->planes) & 15) == 0 && bs->plane_stride % 4 == 0) ? 1 : 0;
+    p.bits_span = (bs->flags & LA3D_BITS_HEIGHT_SPAN) ? 1 : 0;
+  }
   p.B = B; p.H = H; p.W = W; p.HW = H * W;
   p.nwords = (p.HW + 31) / 32;
   p.rows_aligned = (W % 4 == 0);
@@ -218,7 +229,8 @@ static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who)
   if (a.frame_width != 0 && a.frame_width != W) {
     // rows padded on the right (la3d_fit_args::frame_width): run-length / polygon masks, word-aligned rows
     if (a.frame_width < 0 || a.frame_width > W || a.mask != nullptr || W % 32 != 0) {
-      snprintf(g_err, sizeof(g_err), "%s: frame_width must be 0 or in (0, W], with run-length / polygon masks and W %% 32 == 0", who);
+      snprintf(g_err, sizeof(g_err), bs ? "%s: frame_width must be 0 or in (0, W], with W %% 32 == 0"
+                                        : "%s: frame_width must be 0 or in (0, W], with run-length / polygon masks and W %% 32 == 0", who);
       return LA3D_ERR_ARG;
     }
     p.frame_w = a.frame_width;
@@ -236,7 +248,8 @@ static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who)
   f.ldsmask = bit_bytes <= MAX_MASK_LDS;
   p.mask_lds_bytes = f.ldsmask ? bit_bytes : 0;
   if (rle && !f.ldsmask) {
-    snprintf(g_err, sizeof(g_err), "%s: run-length / polygon masks need the bit image in LDS (H*W <= 1048576)", who);
+    snprintf(g_err, sizeof(g_err), bs ? "%s: bit-plane masks need the bit image in LDS (H*W <= 1048576)"
+                                      : "%s: run-length / polygon masks need the bit image in LDS (H*W <= 1048576)", who);
     return LA3D_ERR_UNSUPPORTED;
   }
   // 16-byte vector path: every plane base 16-aligned (the u8 mask only when it is read at all)
@@ -361,6 +374,20 @@ int la3d_fit_instances_poly_filtered(const float* depth, int64_t depth_plane_str
   return fit_dispatch(a, true, "la3d_fit_instances_poly_filtered");
 }
 
+// what la3d_fit_instances_ex and la3d_fit_instances_bits check alike
+static int check_block_options(const la3d_fit_args& a, const char* who) {
+  if (a.proj && !(a.image_width > 0 && a.image_height > 0)) {
+    snprintf(g_err, sizeof(g_err), "%s: proj needs image_width / image_height > 0", who);
+    return LA3D_ERR_ARG;
+  }
+  if (a.opt_engine < 0 || a.opt_engine > LA3D_ENGINE_ROWS2 || a.opt_launch_order < 0 || a.opt_launch_order > LA3D_ORDER_ON ||
+      a.opt_build < 0 || a.opt_build > LA3D_BUILD_NOCULL) {
+    snprintf(g_err, sizeof(g_err), "%s: bad opt_engine / opt_launch_order / opt_build", who);
+    return LA3D_ERR_ARG;
+  }
+  return LA3D_SUCCESS;
+}
+
 int la3d_fit_instances_ex(const la3d_fit_args* args) {
   constexpr int32_t V1_SIZE = (int32_t)offsetof(la3d_fit_args, area_hint);   // the block as first published: every field up to `stream`
   if (!args || args->struct_size < V1_SIZE) {   // (a longer block from a newer caller is fine, fields it lacks are taken as zero)
@@ -379,18 +406,47 @@ int la3d_fit_instances_ex(const la3d_fit_args* args) {
     set_err("la3d_fit_instances_ex: polygon masks need ring_offsets and inst_rings");
     return LA3D_ERR_ARG;
   }
-  if (a.proj && !(a.image_width > 0 && a.image_height > 0)) {
-    set_err("la3d_fit_instances_ex: proj needs image_width / image_height > 0");
-    return LA3D_ERR_ARG;
-  }
-  if (a.opt_engine < 0 || a.opt_engine > LA3D_ENGINE_ROWS2 || a.opt_launch_order < 0 || a.opt_launch_order > LA3D_ORDER_ON ||
-      a.opt_build < 0 || a.opt_build > LA3D_BUILD_NOCULL) {
-    set_err("la3d_fit_instances_ex: bad opt_engine / opt_launch_order / opt_build");
-    return LA3D_ERR_ARG;
-  }
+  const int rc = check_block_options(a, "la3d_fit_instances_ex");
+  if (rc != LA3D_SUCCESS) return rc;
   // the fused filter is on when filter_boundary >= 0 AND filter_max_edge > 0: a zero-initialised block (the natural C idiom, and
   // what "missing fields are zero" gives) means NO filter - max_edge == 0 would reject every instance (edge < 0 never holds)
   return fit_dispatch(a, a.filter_boundary >= 0 && a.filter_max_edge > 0, "la3d_fit_instances_ex");
+}
+
+size_t la3d_mask_bits_words(int H, int W) {
+  if (H <= 0 || W <= 0) return 0;
+  return (size_t)(((long long)H * W + 31) / 32);
+}
+
+int la3d_fit_instances_bits(const la3d_fit_args* args, const uint32_t* mask_bits, int64_t bits_plane_stride, int32_t flags) {
+  constexpr int32_t V1_SIZE = (int32_t)offsetof(la3d_fit_args, area_hint);
+  if (!args || args->struct_size < V1_SIZE) {
+    set_err("la3d_fit_instances_bits: bad struct_size");
+    return LA3D_ERR_ARG;
+  }
+  la3d_fit_args a;
+  memset(&a, 0, sizeof(a));
+  memcpy(&a, args, (size_t)args->struct_size < sizeof(a) ? (size_t)args->struct_size : sizeof(a));
+  if (a.mask || a.rle_counts || a.poly_xy) {
+    set_err("la3d_fit_instances_bits: the masks are the bit planes - mask, rle_counts and poly_xy must be NULL");
+    return LA3D_ERR_ARG;
+  }
+  if (flags & ~(int32_t)LA3D_BITS_HEIGHT_SPAN) {
+    set_err("la3d_fit_instances_bits: unknown flags (LA3D_BITS_HEIGHT_ROWS or LA3D_BITS_HEIGHT_SPAN)");
+    return LA3D_ERR_ARG;
+  }
+  if (a.B > 0 && (!mask_bits || (reinterpret_cast<uintptr_t>(mask_bits) & 3))) {
+    set_err("la3d_fit_instances_bits: mask_bits must be a 4-byte aligned device pointer");
+    return LA3D_ERR_ARG;
+  }
+  if (a.B > 0 && a.H > 0 && a.W > 0 && bits_plane_stride < (int64_t)la3d_mask_bits_words(a.H, a.W)) {
+    set_err("la3d_fit_instances_bits: bits_plane_stride is smaller than la3d_mask_bits_words(H, W)");
+    return LA3D_ERR_ARG;
+  }
+  const int rc = check_block_options(a, "la3d_fit_instances_bits");
+  if (rc != LA3D_SUCCESS) return rc;
+  const BitsSource bs{mask_bits, bits_plane_stride, flags};
+  return fit_dispatch(a, a.filter_boundary >= 0 && a.filter_max_edge > 0, "la3d_fit_instances_bits", &bs);
 }
 
 }  // extern "C"

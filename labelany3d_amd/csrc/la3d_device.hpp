@@ -530,7 +530,53 @@ struct FitParams {
   int* status = nullptr;
   double* aux = nullptr;
   int frame_w = 0;     // la3d_fit_args::frame_width (run-length / polygon input): image columns of the W-wide planes; == W when not given
+  // masks given as bit planes (la3d_fit_instances_bits; the fields sit behind every older one, whose offsets stay what they were):
+  // nwords uint32 words per instance, pixel i = bit i & 31 of word i >> 5 - the layout of the LDS bit image -, planes
+  // bits_plane_stride words apart
+  const unsigned* mask_bits = nullptr;
+  long long bits_plane_stride = 0;
+  int bits_vec = 0;    // base 16-byte aligned and bits_plane_stride % 4 == 0: the plane streams in 16-byte groups
+  int bits_span = 0;   // fused filter: height = last row - first row + 1 (LA3D_BITS_HEIGHT_SPAN) instead of the rows holding a pixel
 };
+
+// Bit plane (global) -> LDS bit image, by all NTH threads of the workgroup: a straight copy - 16-byte non-temporal loads and 16-byte
+// LDS stores where base and stride allow, single words otherwise - plus the popcount; bits of the last word past H*W are cleared in
+// LDS (they are not trusted).  Returns this thread's share of the mask pixels.  No barrier: the caller's follows.
+template <int NTH>
+__device__ inline int bits_plane_to_lds(const unsigned* __restrict__ src, unsigned* bits, int nwords, int HW, int vec, int tid) {
+  int n = 0;
+  int owner = (nwords - 1) % NTH;   // the thread that writes the last word
+  if (vec) {   // uniform
+    const int ng = nwords >> 2;
+    const u32x4* s4 = reinterpret_cast<const u32x4*>(src);
+    u32x4* d4 = reinterpret_cast<u32x4*>(bits);
+#pragma unroll 4
+    for (int g = tid; g < ng; g += NTH) {
+      const u32x4 w = __builtin_nontemporal_load(s4 + g);
+      d4[g] = w;
+      n += (__popc(w.x) + __popc(w.y)) + (__popc(w.z) + __popc(w.w));
+    }
+    const int r = ng * 4 + tid;   // the up to three words behind the last whole group
+    if (tid < 4 && r < nwords) {
+      const unsigned w = src[r];
+      bits[r] = w;
+      n += __popc(w);
+    }
+    owner = (nwords & 3) ? (nwords - 1) - ng * 4 : (ng - 1) % NTH;
+  } else {
+    for (int i = tid; i < nwords; i += NTH) {
+      const unsigned w = src[i];
+      bits[i] = w;
+      n += __popc(w);
+    }
+  }
+  if ((HW & 31) && tid == owner) {   // (the same thread wrote the word: program order)
+    const unsigned w = bits[nwords - 1], keep = w & ((1u << (HW & 31)) - 1u);
+    bits[nwords - 1] = keep;
+    n -= __popc(w ^ keep);
+  }
+  return n;
+}
 
 // per-instance geometry in the workspace (20 doubles = 160 B), written by the split engine's plan_kernel (geo_one)
 // (the instance engine keeps it in LDS)

@@ -22,7 +22,8 @@ namespace {
 // ------------------------------------------------------------------------------------------
 // instance engine: one workgroup per instance
 // ------------------------------------------------------------------------------------------
-// SRC: where the mask comes from - 0 = u8 plane, 1 = COCO run lengths, 2 = polygon parts (both decoded into the LDS bit image)
+// SRC: where the mask comes from - 0 = u8 plane, 1 = COCO run lengths, 2 = polygon parts (both decoded into the LDS bit image),
+// 3 = bit plane (la3d_fit_instances_bits: the LDS bit image itself, copied in)
 // The checked separable walk of the hull instantiations (full-mask mode): what sweep_sep does - moments, y extent, per-column depth
 // range in ONE walk over the compacted tile list - with a finite test per pixel (NaN / infinite depths under the mask are holes of a
 // real depth map: dropped, as the reference drops them, src/util_3dbox.py:139) and range keys that order negative depths too
@@ -97,10 +98,10 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
   if (!SAMPLE && p.order_self && (int)blockIdx.x < p.order_resident && !(p.order_self == 2 && blockIdx.x % 7 == 3)) {
     for (int ie = (int)blockIdx.x; ie < p.B; ie += p.order_resident) {   // uniform
       if (ie != (int)blockIdx.x) __syncthreads();   // (the block totals of the previous estimate have been read)
-      estimate_publish_wg(p, ie, sh, tid, wave, lane);
+      estimate_publish_wg<SRC == 3>(p, ie, sh, tid, wave, lane);
     }
   }
-  const int inst = p.order_nch > 0 ? order_select(p, (int)blockIdx.x, sh, wave, lane) : xcd_remap(blockIdx.x, p.B);
+  const int inst = p.order_nch > 0 ? order_select<SRC == 3>(p, (int)blockIdx.x, sh, wave, lane) : xcd_remap(blockIdx.x, p.B);
   if (tid == 0) { sh->order_inst = inst; sh->sep_bad = 0; }   // (the instance is re-read after the mask stage, see below)
   if constexpr (HULL) { if (tid == 0) hull_slot(p.geo, inst, hull_stride_bytes(SAMPLE, p.W))[HH_STATE] = -1.0; }   // nothing to finish, until the hand-off says so
   const int img = p.image_index ? p.image_index[inst] : inst;
@@ -167,6 +168,10 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
     nmask = poly_to_bits<NT>(p.poly_xy, p.poly_ring_off, p.poly_inst_rings[inst], p.poly_inst_rings[inst + 1],
                              reinterpret_cast<PolySide*>(smem + p.mask_lds_bytes + sizeof(Shared)), sh->scan, bits, p.nwords, p.H,
                              p.W, tid, p.frame_w);
+  } else if (LDSMASK && SRC == 3) {
+    // masks arrive as bit planes: the plane IS the bit image - a straight stream into LDS, no decode (38 400 B for 640x480 against
+    // the 307 200 B of a u8 plane)
+    nmask = bits_plane_to_lds<NT>(p.mask_bits + (long long)inst * p.bits_plane_stride, bits, p.nwords, HW, p.bits_vec, tid);
   } else if (LDSMASK) {
     unsigned short* b16 = reinterpret_cast<unsigned short*>(bits);
     const int ngroups = (HW + 15) >> 4;
@@ -232,7 +237,8 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
     int st4[4];
     bits_filter_stats<NT>(bits, p.H, p.frame_w, p.filter_boundary, reinterpret_cast<int*>(sh->part), tid, st4, p.W);   // (frame_w == W unless the rows are padded)
     if (p.filter_stats && tid < 4) (p.filter_stats + (long long)inst_p * 4)[tid] = st4[tid];   // (uniform base: scalar address arithmetic)
-    const int height = SRC == 1 ? st4[1] : st4[2];   // run lengths: rows holding a pixel (:368-369); polygons: last - first + 1 (:328-335)
+    // run lengths: rows holding a pixel (:368-369); polygons: last - first + 1 (:328-335); a bit plane does not say where it came from: the caller's flag
+    const int height = SRC == 1 ? st4[1] : (SRC == 3 && !p.bits_span) ? st4[1] : st4[2];
     const bool keep = 16 * height > p.H && st4[3] < p.filter_max_edge && st4[0] >= p.filter_min_area;   // height / H > 0.0625
     if (!keep) {
       if (tid == 0) {
@@ -856,6 +862,7 @@ int launch_hull_inst(const FitParams& p, size_t lds, hipStream_t s) {
 }
 template <bool VEC, bool SAMPLE>
 int launch_hull(const FitParams& p, size_t lds, hipStream_t s) {
+  if (p.mask_bits != nullptr) return launch_hull_inst<true, SAMPLE, 3>(p, lds, s);
   if (p.rle_counts != nullptr) return launch_hull_inst<true, SAMPLE, 1>(p, lds, s);
   if (p.poly_xy != nullptr) return launch_hull_inst<true, SAMPLE, 2>(p, lds, s);
   return launch_hull_inst<VEC, SAMPLE, 0>(p, lds, s);
@@ -895,6 +902,8 @@ int launch_fit_inst(const FitParams& p_in, size_t lds, hipStream_t s, void* work
           p.order_flags = reinterpret_cast<unsigned long long*>(static_cast<unsigned char*>(workspace) + (((size_t)p.B * 4 + 255) & ~(size_t)255));
           const unsigned long long t = (unsigned long long)std::chrono::steady_clock::now().time_since_epoch().count();
           p.order_nonce = (t * 0x9E3779B97F4A7C15ull) ^ (unsigned long long)reinterpret_cast<uintptr_t>(workspace) ^ 0xA5A5A5A55A5A5A5Aull;
+        } else if (SRC == 3) {
+          hipLaunchKernelGGL(size_estimate_bits_kernel, dim3((p.B + 3) / 4), dim3(256), 0, s, p, k.shift, est);
         } else {
           hipLaunchKernelGGL(size_estimate_kernel, dim3((p.B + 3) / 4), dim3(256), 0, s, p.mask, p.rle_counts, p.rle_offsets, p.poly_xy,
                              p.poly_ring_off, p.poly_inst_rings, p.B, p.HW, k.step, k.shift, est, nullptr);
@@ -910,6 +919,7 @@ int launch_fit_inst(const FitParams& p_in, size_t lds, hipStream_t s, void* work
 // run-length input is its own instantiation (it needs the LDS bit image), so the u8 kernels carry no decode code
 template <bool VEC, bool LDSMASK, bool SAMPLE, bool TILED = false>
 int launch_fit(const FitParams& p, size_t lds, hipStream_t s, void* workspace = nullptr) {
+  if (LDSMASK && p.mask_bits != nullptr) return launch_fit_inst<VEC, LDSMASK, SAMPLE, TILED, LDSMASK ? 3 : 0>(p, lds, s, workspace);
   if (LDSMASK && p.rle_counts != nullptr) return launch_fit_inst<VEC, LDSMASK, SAMPLE, TILED, LDSMASK ? 1 : 0>(p, lds, s, workspace);
   if (LDSMASK && p.poly_xy != nullptr) return launch_fit_inst<VEC, LDSMASK, SAMPLE, TILED, LDSMASK ? 2 : 0>(p, lds, s, workspace);
   return launch_fit_inst<VEC, LDSMASK, SAMPLE, TILED, 0>(p, lds, s, workspace);

@@ -418,6 +418,136 @@ __global__ __launch_bounds__(256) void mask_stats_rle_kernel(const int* __restri
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// masks as bit planes (include/la3d.h "masks as bit planes"): packers, unpacker, filter statistics
+// ------------------------------------------------------------------------------------------
+// element kinds of the packers: a u8 mask (bit = byte != 0) or logits (bit = x > threshold in float32; NaN compares false)
+enum { PK_U8 = 0, PK_F32 = 1, PK_F16 = 2, PK_BF16 = 3 };
+template <int KIND> struct PackElem;
+template <> struct PackElem<PK_U8>   { typedef unsigned char T; };
+template <> struct PackElem<PK_F32>  { typedef float T; };
+template <> struct PackElem<PK_F16>  { typedef unsigned short T; };
+template <> struct PackElem<PK_BF16> { typedef unsigned short T; };
+
+__device__ inline float pk_f16(unsigned h) { return (float)__builtin_bit_cast(_Float16, (unsigned short)h); }
+__device__ inline float pk_bf16(unsigned h) { return __uint_as_float(h << 16); }
+template <int KIND>
+__device__ inline bool pack_pred(typename PackElem<KIND>::T x, float thr) {
+  if constexpr (KIND == PK_U8) return x != 0;
+  else if constexpr (KIND == PK_F32) return x > thr;
+  else if constexpr (KIND == PK_F16) return pk_f16(x) > thr;
+  else return pk_bf16(x) > thr;
+}
+// the bits of the 16 bytes one lane loads: 16 (u8), 8 (f16 / bf16) or 4 (f32) elements, element 0 -> bit 0
+template <int KIND>
+__device__ inline unsigned pack_group(const u32x4 w, float thr) {
+  if constexpr (KIND == PK_U8) {
+    return nz16(w.x, w.y, w.z, w.w);
+  } else if constexpr (KIND == PK_F32) {
+    return (__uint_as_float(w.x) > thr ? 1u : 0u) | (__uint_as_float(w.y) > thr ? 2u : 0u) | (__uint_as_float(w.z) > thr ? 4u : 0u) |
+           (__uint_as_float(w.w) > thr ? 8u : 0u);
+  } else {
+    const unsigned q[4] = {w.x, w.y, w.z, w.w};
+    unsigned r = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float lo = KIND == PK_F16 ? pk_f16(q[k] & 0xffffu) : pk_bf16(q[k] & 0xffffu);
+      const float hi = KIND == PK_F16 ? pk_f16(q[k] >> 16) : pk_bf16(q[k] >> 16);
+      r |= (lo > thr ? 1u : 0u) << (2 * k) | (hi > thr ? 1u : 0u) << (2 * k + 1);
+    }
+    return r;
+  }
+}
+
+// Vector form (chosen on the host: W_out == W, H*W % 32 == 0, every plane base 16-byte aligned): the plane is one linear run of
+// elements, every lane loads 16 bytes (fully coalesced) and the 2 / 4 / 8 neighbouring lanes that share an output word OR their
+// pieces together with DPP moves; one lane of each group stores the whole word.  blockIdx.x = plane * chunks + chunk.
+template <int KIND>
+__global__ __launch_bounds__(256) void pack_bits_vec_kernel(const void* __restrict__ src, long long plane_stride_bytes, float thr, int HW,
+                                                            int chunks, unsigned* __restrict__ out, long long out_stride) {
+  constexpr int EPL = 16 / (int)sizeof(typename PackElem<KIND>::T);   // elements per lane
+  constexpr int LPW = 32 / EPL;                                      // lanes per output word: 2, 4, 8
+  const int b = blockIdx.x / chunks, chunk = blockIdx.x - b * chunks;
+  const u32x4* s4 = reinterpret_cast<const u32x4*>(static_cast<const unsigned char*>(src) + (long long)b * plane_stride_bytes);
+  unsigned* o = out + (long long)b * out_stride;
+  const int ngroups = HW / EPL;   // a multiple of LPW
+  for (int g0 = chunk * 256; g0 < ngroups; g0 += chunks * 256) {   // uniform trip count: every lane takes part in the DPP steps
+    const int g = g0 + (int)threadIdx.x;
+    unsigned pat = 0;
+    if (g < ngroups) pat = pack_group<KIND>(__builtin_nontemporal_load(s4 + g), thr) << (EPL * (g & (LPW - 1)));
+    pat |= (unsigned)dpp_i32<DPP_XOR1>((int)pat);
+    if constexpr (LPW >= 4) pat |= (unsigned)dpp_i32<DPP_XOR2>((int)pat);
+    if constexpr (LPW >= 8) pat |= (unsigned)dpp_i32<DPP_HALF_MIRROR>((int)pat);
+    if (g < ngroups && (g & (LPW - 1)) == 0) o[g / LPW] = pat;
+  }
+}
+
+// General form: one thread per output word, any stride / alignment / row padding; element (v, u) is read when v < H and u < W.
+template <int KIND>
+__global__ __launch_bounds__(256) void pack_bits_kernel(const void* __restrict__ src, long long plane_stride_elems, float thr, int H, int W,
+                                                        int W_out, int nwords, int chunks, unsigned* __restrict__ out,
+                                                        long long out_stride) {
+  typedef typename PackElem<KIND>::T T;
+  const int b = blockIdx.x / chunks, chunk = blockIdx.x - b * chunks;
+  const T* sp = static_cast<const T*>(src) + (long long)b * plane_stride_elems;
+  unsigned* o = out + (long long)b * out_stride;
+  const long long total = (long long)H * W_out;
+  for (int w = chunk * 256 + (int)threadIdx.x; w < nwords; w += chunks * 256) {
+    const long long i0 = (long long)w * 32;
+    int v = (int)(i0 / W_out), u = (int)(i0 - (long long)v * W_out);
+    unsigned pat = 0;
+    for (int k = 0; k < 32 && i0 + k < total; ++k) {
+      if (u < W && pack_pred<KIND>(sp[(long long)v * W + u], thr)) pat |= 1u << k;
+      if (++u == W_out) { u = 0; ++v; }
+    }
+    o[w] = pat;
+  }
+}
+
+// bit planes stored W_in pixels wide -> u8 planes [B][H][W] (0 / 1): one thread per four output bytes where W % 4 == 0 (one 32-bit
+// store), per byte otherwise
+__global__ __launch_bounds__(256) void unpack_mask_bits_kernel(const unsigned* __restrict__ bits, long long stride, int H, int W_in, int W,
+                                                               int quads, int chunks, unsigned char* __restrict__ mask) {
+  const int b = blockIdx.x / chunks, chunk = blockIdx.x - b * chunks;
+  const unsigned* bp = bits + (long long)b * stride;
+  unsigned char* mp = mask + (long long)b * H * W;
+  const long long HW = (long long)H * W;
+  if (quads) {   // uniform
+    const int wq = W >> 2;
+    const long long nq = HW >> 2;
+    for (long long q = (long long)chunk * 256 + threadIdx.x; q < nq; q += (long long)chunks * 256) {
+      const int v = (int)(q / wq), u = (int)(q - (long long)v * wq) * 4;
+      const long long i = (long long)v * W_in + u;
+      const unsigned sh = (unsigned)(i & 31);
+      unsigned n = bp[i >> 5] >> sh;
+      if (sh > 28) n |= bp[(i >> 5) + 1] << (32 - sh);
+      n &= 15u;
+      reinterpret_cast<unsigned*>(mp)[q] = (n & 1u) | ((n & 2u) << 7) | ((n & 4u) << 14) | ((n & 8u) << 21);
+    }
+  } else {
+    for (long long q = (long long)chunk * 256 + threadIdx.x; q < HW; q += (long long)chunks * 256) {
+      const int v = (int)(q / W), u = (int)(q - (long long)v * W);
+      const long long i = (long long)v * W_in + u;
+      mp[q] = (unsigned char)((bp[i >> 5] >> (i & 31)) & 1u);
+    }
+  }
+}
+
+// the four filter quantities of one bit plane per workgroup: the plane into LDS (as the fit kernel's phase 0 takes it), then the
+// statistics the fused filter computes (bits_filter_stats).  Dynamic LDS: the bit image.
+__global__ __launch_bounds__(256) void mask_stats_bits_kernel(const unsigned* __restrict__ planes, long long stride, int vec, int H, int W,
+                                                              int frame_w, int nwords, int boundary, int* __restrict__ stats) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  unsigned* bits = reinterpret_cast<unsigned*>(smem);
+  __shared__ int red[5 * 4];
+  const int tid = threadIdx.x;
+  bits_plane_to_lds<256>(planes + (long long)blockIdx.x * stride, bits, nwords, H * W, vec, tid);
+  __syncthreads();
+  int st4[4];
+  bits_filter_stats<256>(bits, H, frame_w, boundary, red, tid, st4, W);
+  if (tid < 4) (stats + (long long)blockIdx.x * 4)[tid] = st4[tid];
+}
+
 // host-side 3x3 inverse (same elimination as the device-side inv3)
 void inv3_host(const double* A, double* X) {
   double a[3][6];
@@ -634,6 +764,117 @@ int la3d_mask_stats_rle(const int32_t* counts, const int64_t* offsets, int B, in
   hipLaunchKernelGGL(mask_stats_rle_kernel, dim3(B), dim3(256), (size_t)(H + 1) * 4, static_cast<hipStream_t>(stream), counts,
                      reinterpret_cast<const long long*>(offsets), H, W, boundary, stats);
   return check_launch("mask_stats_rle_kernel");
+}
+
+}  // extern "C"
+
+// ---- masks as bit planes ------------------------------------------------------------------
+namespace {
+// workgroups per plane: enough to cover `items` once, at most 64 (grid-stride inside the plane beyond that)
+inline int plane_chunks(long long items) {
+  const long long c = (items + 255) / 256;
+  return (int)(c < 1 ? 1 : (c > 64 ? 64 : c));
+}
+
+template <int KIND>
+int pack_bits_launch(const void* src, long long plane_stride, float thr, int B, int H, int W, int W_out, uint32_t* bits,
+                     long long bits_plane_stride, hipStream_t s, const char* what) {
+  constexpr long long ES = (long long)sizeof(typename PackElem<KIND>::T);
+  const long long HW = (long long)H * W;
+  const int nwords = (int)la3d_mask_bits_words(H, W_out);
+  // (CallFacts::vec of the packers: one linear run of whole words per plane, every plane base 16-byte aligned)
+  const bool vec = W_out == W && HW % 32 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && (plane_stride * ES) % 16 == 0;
+  if (vec) {
+    const int chunks = plane_chunks(HW / (16 / ES));
+    hipLaunchKernelGGL(pack_bits_vec_kernel<KIND>, dim3((unsigned)((long long)B * chunks)), dim3(256), 0, s, src, plane_stride * ES, thr, (int)HW,
+                       chunks, bits, bits_plane_stride);
+  } else {
+    const int chunks = plane_chunks(nwords);
+    hipLaunchKernelGGL(pack_bits_kernel<KIND>, dim3((unsigned)((long long)B * chunks)), dim3(256), 0, s, src, plane_stride, thr, H, W, W_out,
+                       nwords, chunks, bits, bits_plane_stride);
+  }
+  return check_launch(what);
+}
+
+// the argument checks the two packers share; 1 = nothing to do (B == 0)
+int pack_bits_check(const void* src, long long plane_stride, int B, int H, int W, int W_out, const uint32_t* bits,
+                    long long bits_plane_stride, const char* who) {
+  char msg[200];
+  const char* bad = nullptr;
+  if (B < 0 || H <= 0 || W <= 0 || W_out < W) bad = "bad argument (B >= 0, H, W > 0, W_out >= W)";
+  else if ((long long)H * W_out > (1LL << 28) || (long long)B * 64 > 0x7fffffffLL) bad = "frame or batch too large (H*W_out <= 2^28, B <= 2^25)";
+  else if (B > 0 && (!src || !bits || (reinterpret_cast<uintptr_t>(bits) & 3))) bad = "NULL input or bits not a 4-byte aligned pointer";
+  else if (B > 0 && plane_stride < (long long)H * W) bad = "input plane stride smaller than H*W";
+  else if (B > 0 && bits_plane_stride < (long long)la3d_mask_bits_words(H, W_out)) bad = "bits_plane_stride is smaller than la3d_mask_bits_words(H, W_out)";
+  if (bad) {
+    snprintf(msg, sizeof(msg), "%s: %s", who, bad);
+    set_err(msg);
+    return LA3D_ERR_ARG;
+  }
+  return B == 0 ? 1 : LA3D_SUCCESS;
+}
+}  // namespace
+
+extern "C" {
+
+int la3d_pack_mask_bits(const uint8_t* mask, int64_t mask_plane_stride, int B, int H, int W, int W_out, uint32_t* bits,
+                        int64_t bits_plane_stride, void* stream) {
+  const int rc = pack_bits_check(mask, mask_plane_stride, B, H, W, W_out, bits, bits_plane_stride, "la3d_pack_mask_bits");
+  if (rc != LA3D_SUCCESS) return rc < 0 ? rc : LA3D_SUCCESS;
+  return pack_bits_launch<PK_U8>(mask, mask_plane_stride, 0.0f, B, H, W, W_out, bits, bits_plane_stride, static_cast<hipStream_t>(stream),
+                                 "pack_mask_bits_kernel");
+}
+
+int la3d_pack_logits_bits(const void* logits, int dtype, int64_t plane_stride, float threshold, int B, int H, int W, int W_out,
+                          uint32_t* bits, int64_t bits_plane_stride, void* stream) {
+  if (dtype != LA3D_DTYPE_F32 && dtype != LA3D_DTYPE_F16 && dtype != LA3D_DTYPE_BF16) {
+    set_err("la3d_pack_logits_bits: unknown dtype (LA3D_DTYPE_F32, LA3D_DTYPE_F16 or LA3D_DTYPE_BF16)");
+    return LA3D_ERR_ARG;
+  }
+  if (B > 0 && logits && (reinterpret_cast<uintptr_t>(logits) & (dtype == LA3D_DTYPE_F32 ? 3 : 1))) {
+    set_err("la3d_pack_logits_bits: logits not aligned to their element size");
+    return LA3D_ERR_ARG;
+  }
+  const int rc = pack_bits_check(logits, plane_stride, B, H, W, W_out, bits, bits_plane_stride, "la3d_pack_logits_bits");
+  if (rc != LA3D_SUCCESS) return rc < 0 ? rc : LA3D_SUCCESS;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dtype == LA3D_DTYPE_F32) return pack_bits_launch<PK_F32>(logits, plane_stride, threshold, B, H, W, W_out, bits, bits_plane_stride, s, "pack_logits_bits_kernel");
+  if (dtype == LA3D_DTYPE_F16) return pack_bits_launch<PK_F16>(logits, plane_stride, threshold, B, H, W, W_out, bits, bits_plane_stride, s, "pack_logits_bits_kernel");
+  return pack_bits_launch<PK_BF16>(logits, plane_stride, threshold, B, H, W, W_out, bits, bits_plane_stride, s, "pack_logits_bits_kernel");
+}
+
+int la3d_unpack_mask_bits(const uint32_t* bits, int64_t bits_plane_stride, int B, int H, int W_in, int W, uint8_t* mask, void* stream) {
+  if (B < 0 || H <= 0 || W <= 0 || W_in < W || (long long)H * W_in > (1LL << 28) || (long long)B * 64 > 0x7fffffffLL ||
+      (B > 0 && (!bits || !mask || (reinterpret_cast<uintptr_t>(bits) & 3) || bits_plane_stride < (int64_t)la3d_mask_bits_words(H, W_in)))) {
+    set_err("la3d_unpack_mask_bits: bad argument (W <= W_in, bits 4-byte aligned, bits_plane_stride >= la3d_mask_bits_words(H, W_in))");
+    return LA3D_ERR_ARG;
+  }
+  if (B == 0) return LA3D_SUCCESS;
+  const int quads = (W % 4 == 0 && (reinterpret_cast<uintptr_t>(mask) & 3) == 0) ? 1 : 0;
+  const int chunks = plane_chunks(quads ? (long long)H * W / 4 : (long long)H * W);
+  hipLaunchKernelGGL(unpack_mask_bits_kernel, dim3((unsigned)((long long)B * chunks)), dim3(256), 0, static_cast<hipStream_t>(stream), bits,
+                     (long long)bits_plane_stride, H, W_in, W, quads, chunks, mask);
+  return check_launch("unpack_mask_bits_kernel");
+}
+
+int la3d_mask_stats_bits(const uint32_t* bits, int64_t bits_plane_stride, int B, int H, int W, int frame_width, int boundary,
+                         int32_t* stats, void* stream) {
+  if (B < 0 || H <= 0 || W <= 0 || boundary < 0 || frame_width < 0 || frame_width > W ||
+      (B > 0 && (!bits || !stats || (reinterpret_cast<uintptr_t>(bits) & 3) || bits_plane_stride < (int64_t)la3d_mask_bits_words(H, W)))) {
+    set_err("la3d_mask_stats_bits: bad argument (0 <= frame_width <= W, bits 4-byte aligned, bits_plane_stride >= la3d_mask_bits_words(H, W))");
+    return LA3D_ERR_ARG;
+  }
+  if ((long long)H * W > (1LL << 20)) {
+    set_err("la3d_mask_stats_bits: the bit image must fit LDS (H*W <= 1048576)");
+    return LA3D_ERR_UNSUPPORTED;
+  }
+  if (B == 0) return LA3D_SUCCESS;
+  const int nwords = (int)la3d_mask_bits_words(H, W);
+  const int vec = ((reinterpret_cast<uintptr_t>(bits) & 15) == 0 && bits_plane_stride % 4 == 0) ? 1 : 0;
+  allow_big_lds(reinterpret_cast<const void*>(mask_stats_bits_kernel));
+  hipLaunchKernelGGL(mask_stats_bits_kernel, dim3(B), dim3(256), (((size_t)nwords * 4 + 15) & ~(size_t)15) + 16, static_cast<hipStream_t>(stream),
+                     bits, (long long)bits_plane_stride, vec, H, W, frame_width > 0 ? frame_width : W, nwords, boundary, stats);
+  return check_launch("mask_stats_bits_kernel");
 }
 
 }  // extern "C"

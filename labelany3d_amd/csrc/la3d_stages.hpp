@@ -240,10 +240,26 @@ __device__ inline unsigned long long ld_agent_u64(const unsigned long long* q) {
 // this thread's share of the estimate of instance inst when NTH threads work on it (NTH = 64: one wave, NT: the workgroup): the
 // SAME integer whoever computes it - every step-th 128-byte line of the plane, all eight 16-byte groups of a line (u8 planes);
 // the ones-runs (run lengths).  One load in flight per thread: few registers (this code sits in the prologue of the fit kernel).
-template <int NTH>
+// BITS (the bit-plane instantiations only): the exact popcount of the plane - it is an eighth of a u8 plane, so every word is looked
+// at (16-byte groups where the plane allows, words otherwise; bits of the last word past H*W are counted as they come: a key only
+// orders the work).
+template <int NTH, bool BITS = false>
 __device__ inline int estimate_share(const FitParams& p, int inst, int t) {
   int c = 0;
-  if (p.rle_counts) {
+  if constexpr (BITS) {
+    const unsigned* src = p.mask_bits + (long long)inst * p.bits_plane_stride;
+    if (p.bits_vec) {   // uniform
+      const u32x4* s4 = reinterpret_cast<const u32x4*>(src);
+      const int ng = p.nwords >> 2;
+      for (int g = t; g < ng; g += NTH) {
+        const u32x4 v = s4[g];
+        c += (__popc(v.x) + __popc(v.y)) + (__popc(v.z) + __popc(v.w));
+      }
+      if (t < (p.nwords & 3)) c += __popc(src[ng * 4 + t]);
+    } else {
+      for (int i = t; i < p.nwords; i += NTH) c += __popc(src[i]);
+    }
+  } else if (p.rle_counts) {
     const long long lo = p.rle_offsets[inst], hi = p.rle_offsets[inst + 1];
 #pragma unroll 1
     for (long long k = lo + 1 + 2 * t; k < hi; k += 2 * NTH) {
@@ -279,23 +295,28 @@ __device__ inline unsigned published_key(const FitParams& p, int inst) {
 }
 // one wave estimates (polygon input in the prologue - its shoelace sums are per ring -, and the fallback of order_select); every lane
 // returns the key
+template <bool BITS = false>
 __device__ inline unsigned estimate_key_wave(const FitParams& p, int inst, int lane) {
   int c;
-  if (p.poly_xy) c = estimate_wave(nullptr, nullptr, nullptr, p.poly_xy, p.poly_ring_off, p.poly_inst_rings, inst, p.HW, p.est_step, lane);
+  if constexpr (BITS) c = wave_sum_i(estimate_share<64, true>(p, inst, lane));
+  else if (p.poly_xy) c = estimate_wave(nullptr, nullptr, nullptr, p.poly_xy, p.poly_ring_off, p.poly_inst_rings, inst, p.HW, p.est_step, lane);
   else c = wave_sum_i(estimate_share<64>(p, inst, lane));
   return make_order_key(c, p.order_shift, inst);
 }
 __device__ inline void estimate_publish_wave(const FitParams& p, int inst, int lane) {
-  const unsigned key = estimate_key_wave(p, inst, lane);
+  const unsigned key = estimate_key_wave<false>(p, inst, lane);
   if (lane == 0) publish_key_word(p, inst, key);
 }
 // the prologue: workgroup b estimates instance b with all its threads (every thread of the workgroup calls it; one barrier)
+template <bool BITS = false>
 __device__ inline void estimate_publish_wg(const FitParams& p, int inst, Shared* sh, int tid, int wave, int lane) {
-  if (p.poly_xy) {   // uniform
-    if (wave == 0) estimate_publish_wave(p, inst, lane);
-    return;
+  if constexpr (!BITS) {
+    if (p.poly_xy) {   // uniform
+      if (wave == 0) estimate_publish_wave(p, inst, lane);
+      return;
+    }
   }
-  const int c = wave_sum_i(estimate_share<NT>(p, inst, tid));
+  const int c = wave_sum_i(estimate_share<NT, BITS>(p, inst, tid));
   if (lane == 0) sh->scan[wave] = (unsigned)c;
   __syncthreads();
   if (tid == 0) {
@@ -307,6 +328,7 @@ __device__ inline void estimate_publish_wg(const FitParams& p, int inst, Shared*
 }
 
 // every thread of the workgroup calls it (one barrier); returns the instance of block b, wave-uniform
+template <bool BITS = false>
 __device__ inline int order_select(const FitParams& p, int b, Shared* sh, int wave, int lane) {
   const int R = p.B < p.order_resident ? p.B : p.order_resident;
   int grank = b;
@@ -336,7 +358,7 @@ __device__ inline int order_select(const FitParams& p, int b, Shared* sh, int wa
       while (missing) {   // (fallback, normally never: see above)
         const int m = __ffsll((long long)missing) - 1;
         missing &= missing - 1ull;
-        const unsigned km = estimate_key_wave(p, start + m, lane);   // (every lane gets the key; not published: the owner will)
+        const unsigned km = estimate_key_wave<BITS>(p, start + m, lane);   // (every lane gets the key; not published: the owner will)
         if (lane == m) self_key = km;
       }
     }
@@ -388,6 +410,16 @@ __global__ __launch_bounds__(256) void size_estimate_kernel(const unsigned char*
   if (lane == 0) {
     keys[inst] = make_order_key(c, shift, inst);
   }
+}
+
+// the helper kernel of a bit-plane call (a call captured into a HIP graph, LA3D_ORDER_SELF=0): one wave per instance, the exact
+// popcount - the same integer estimate_share<.., true> gives
+__global__ __launch_bounds__(256) void size_estimate_bits_kernel(const FitParams p, int shift, unsigned* __restrict__ keys) {
+  const int lane = threadIdx.x & 63;
+  const int inst = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (inst >= p.B) return;
+  const int c = wave_sum_i(estimate_share<64, true>(p, inst, lane));
+  if (lane == 0) keys[inst] = make_order_key(c, shift, inst);
 }
 
 // size-balanced launch order on for this call?  (per-call opt_order, else the process default)

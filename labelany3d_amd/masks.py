@@ -24,14 +24,15 @@ from __future__ import annotations
 import ctypes as C
 import itertools
 import threading
+from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from . import _lib, options
 from ._lib import AUX, BOX_FILTERED, REC, check, lib
-from .batched import (InstanceFitter, _as_dev, _bulk, _dev, _filter_args, _fit_args, _fit_inputs, _ptr, _record, _stream,  # noqa: F401
-                      _upload_many, pad_rows_f32)
+from .batched import (InstanceFitter, _as_dev, _bits_stride, _bulk, _dev, _filter_args, _fit_args, _fit_inputs, _ptr, _record, _stream,  # noqa: F401
+                      _upload_many, height_rule_code, pad_rows_f32)
 
 
 def rle_from_string(s) -> np.ndarray:
@@ -613,6 +614,163 @@ def fit_instances_rle(depth, rles, K, ground=None, sample_idx=None, image_index=
     r = fit_instances_ex(depth, K, rles=rles, ground=ground, sample_idx=sample_idx, image_index=image_index, filter=filter,
                          stream=stream, device=device, method=method)
     return (r["boxes"], r["status"], r["aux"]) + ((r["stats"],) if filter else ())
+
+
+class MaskBits(NamedTuple):
+    """Masks as bit planes (include/la3d.h "masks as bit planes"): ``bits`` int32 (B, words) on the GPU - row b holds the
+    ``ceil(H*W/32)`` little-endian words of plane b, pixel (v, u) = bit ``(v*W + u) & 31`` of word ``(v*W + u) >> 5``, i.e.
+    ``np.packbits(mask.reshape(B, -1), axis=1, bitorder="little")`` viewed as uint32 -; ``H``, ``W``: the frame as STORED (rows
+    padded to ``W``); ``frame_width``: the image columns (== W when the rows are not padded)."""
+    bits: torch.Tensor
+    H: int
+    W: int
+    frame_width: int
+
+
+def _mask_bits(bits) -> MaskBits:
+    if not (isinstance(bits, tuple) and len(bits) == 4):
+        raise ValueError("bits must be the (bits, H, W, frame_width) tuple of pack_mask_bits / pack_logits_bits")
+    mb = MaskBits(bits[0], int(bits[1]), int(bits[2]), int(bits[3]))
+    if not 0 < mb.frame_width <= mb.W:
+        raise ValueError("frame_width must lie in (0, W]")
+    _bits_stride(mb.bits, mb.bits.shape[0] if isinstance(mb.bits, torch.Tensor) and mb.bits.dim() == 2 else 0, mb.H, mb.W)
+    return mb
+
+
+def _plane_source(x, dev, dtypes):
+    """(B,H,W) input of a packer -> (tensor, plane stride in elements): a device tensor whose planes are dense (rows W apart, pixels
+    adjacent) is read where it lies, whatever its plane stride and base alignment; everything else is made contiguous first."""
+    if isinstance(x, torch.Tensor) and x.is_cuda and x.device == dev and x.dim() == 3 and x.dtype in dtypes:
+        B, H, W = x.shape
+        if (W == 1 or x.stride(2) == 1) and (H == 1 or x.stride(1) == W) and (B <= 1 or x.stride(0) >= H * W):
+            t = x.view(torch.uint8) if x.dtype == torch.bool else x
+            return t, (int(x.stride(0)) if B > 1 else H * W)
+    t = _as_dev(x, dtypes[0] if not (isinstance(x, torch.Tensor) and x.dtype in dtypes) else x.dtype, dev)
+    if t.dim() != 3:
+        raise ValueError("expected (B,H,W)")
+    return t, int(t.shape[1] * t.shape[2])
+
+
+def _bits_out(out, B, H, W_out, dev):
+    nwords = (H * W_out + 31) // 32
+    if out is None:
+        return torch.empty((B, nwords), dtype=torch.int32, device=dev)
+    _bits_stride(out, B, H, W_out)
+    return out
+
+
+def pack_mask_bits(masks, frame_pad: bool = True, device=None, stream=None, out=None) -> MaskBits:
+    """(B,H,W) bool / uint8 masks (non-zero = True) -> ``MaskBits`` on the GPU (C-ABI ``la3d_pack_mask_bits``).  ``frame_pad``: rows
+    of a width that is not a multiple of 32 are padded with zero bits to ``padded_width(W)`` - exactly as ``pad_depth_rows`` pads
+    the depth -, which is what the tiled forms of the fit want (``frame_width`` of the result keeps W).  A device tensor with
+    dense planes is read in place (any plane stride, any base alignment).  ``out``: an int32 (B, >= words) device tensor to fill
+    (only the words of each plane are written).  Worth it when the masks are fitted more than once or stay resident: a single
+    fit of a u8 plane that already exists reads fewer bytes through ``fit_instances``."""
+    if device is None and isinstance(masks, torch.Tensor) and masks.is_cuda:
+        device = masks.device
+    dev = _dev(device)
+    m, ps = _plane_source(masks, dev, (torch.uint8, torch.bool))
+    B, H, W = m.shape
+    W_out = padded_width(W) if frame_pad else W
+    o = _bits_out(out, B, H, W_out, dev)
+    with torch.cuda.device(dev):
+        check(lib.la3d_pack_mask_bits(_ptr(m), ps, B, H, W, W_out, _ptr(o), _bits_stride(o, B, H, W_out), _stream(stream)),
+              "la3d_pack_mask_bits")
+    _record(stream, m, o)
+    return MaskBits(o, H, W_out, W)
+
+
+_LOGIT_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
+
+
+def pack_logits_bits(logits, threshold: float = 0.0, frame_pad: bool = True, device=None, stream=None, out=None) -> MaskBits:
+    """(B,H,W) float32 / float16 / bfloat16 logits of a segmentation network -> ``MaskBits`` of ``logits > threshold`` (compared in
+    float32; NaN -> 0), without a boolean plane in between (C-ABI ``la3d_pack_logits_bits``).  Other arguments as
+    ``pack_mask_bits``."""
+    if device is None and isinstance(logits, torch.Tensor) and logits.is_cuda:
+        device = logits.device
+    dev = _dev(device)
+    x, ps = _plane_source(logits, dev, (torch.float32, torch.float16, torch.bfloat16))
+    B, H, W = x.shape
+    W_out = padded_width(W) if frame_pad else W
+    o = _bits_out(out, B, H, W_out, dev)
+    with torch.cuda.device(dev):
+        check(lib.la3d_pack_logits_bits(_ptr(x), _LOGIT_DTYPES[x.dtype], ps, float(threshold), B, H, W, W_out, _ptr(o),
+                                        _bits_stride(o, B, H, W_out), _stream(stream)), "la3d_pack_logits_bits")
+    _record(stream, x, o)
+    return MaskBits(o, H, W_out, W)
+
+
+def unpack_mask_bits(bits, stream=None) -> torch.Tensor:
+    """``MaskBits`` -> (B,H,frame_width) bool masks on the GPU (C-ABI ``la3d_unpack_mask_bits``)."""
+    mb = _mask_bits(bits)
+    B = mb.bits.shape[0]
+    out = torch.empty((B, mb.H, mb.frame_width), dtype=torch.uint8, device=mb.bits.device)
+    with torch.cuda.device(mb.bits.device):
+        check(lib.la3d_unpack_mask_bits(_ptr(mb.bits), _bits_stride(mb.bits, B, mb.H, mb.W), B, mb.H, mb.W, mb.frame_width, _ptr(out),
+                                        _stream(stream)), "la3d_unpack_mask_bits")
+    _record(stream, mb.bits, out)
+    return out.view(torch.bool)
+
+
+def mask_stats_bits(bits, boundary_threshold: int = 10, stream=None) -> torch.Tensor:
+    """``mask_stats`` of ``MaskBits``: (B,4) int32 - area, rows holding a pixel, last - first + 1 rows, boundary-strip pixels (the
+    right strip ends at ``frame_width``)."""
+    mb = _mask_bits(bits)
+    B = mb.bits.shape[0]
+    out = torch.empty((B, 4), dtype=torch.int32, device=mb.bits.device)
+    with torch.cuda.device(mb.bits.device):
+        check(lib.la3d_mask_stats_bits(_ptr(mb.bits), _bits_stride(mb.bits, B, mb.H, mb.W), B, mb.H, mb.W, mb.frame_width,
+                                       int(boundary_threshold), _ptr(out), _stream(stream)), "la3d_mask_stats_bits")
+    _record(stream, mb.bits, out)
+    return out
+
+
+def fit_instances_bits(depth, bits, K, ground=None, sample_idx=None, image_index=None, stream=None, device=None, filter=None,
+                       image_size=None, area_hint=None, frame_width=None, method: str = "pca", height_rule: str = "rows"):
+    """fit_instances with the masks given as bit planes (``pack_mask_bits`` / ``pack_logits_bits``; C-ABI
+    ``la3d_fit_instances_bits``): the planes are copied straight into the fit kernel's LDS bit image - an eighth of the bytes of a u8
+    plane, no decode.  Arguments and returns as ``fit_instances_rle`` (``filter`` adds the (B,4) statistics), plus ``image_size`` /
+    ``area_hint`` as in ``fit_instances_ex`` (``image_size`` appends ``boxes2d`` (B,8) to the returned tuple).  ``depth``: planes as
+    wide as the bit planes are stored (``bits.W``), or ``bits.frame_width`` wide - then the rows are padded here
+    (``pad_depth_rows``).  ``frame_width``: None, or the image width, checked against the planes'.  ``height_rule``: the height the
+    fused filter uses - "rows" (rows holding a pixel, the reference's rule for run-length annotations) or "span" (last - first + 1,
+    its rule for polygons); a bit plane does not say where it came from."""
+    meth = _lib.method_code(method)   # (the reference's error for an unknown method, before any device work)
+    flags = height_rule_code(height_rule)
+    mb = _mask_bits(bits)
+    dev = mb.bits.device if device is None else _dev(device)
+    if mb.bits.device != dev:
+        raise ValueError("the bit planes live on another device")
+    B, H, W, fw = mb.bits.shape[0], mb.H, mb.W, mb.frame_width
+    if frame_width is not None and int(frame_width) != fw:
+        raise ValueError(f"frame_width {frame_width} does not match the bit planes' frame width {fw}")
+    Wd = int(depth.shape[-1])
+    if Wd != W:
+        if Wd != fw or padded_width(fw) != W:
+            raise ValueError(f"depth rows of {Wd} pixels match neither the stored width {W} nor the frame width {fw} of the bit planes")
+        with torch.cuda.device(dev):
+            depth, _ = pad_depth_rows(depth, dev)
+    d, k, ii, g, si, P = _fit_inputs(depth, K, image_index, ground, sample_idx, B, H, W, dev, "the bit-plane frame")
+    with torch.cuda.device(dev):
+        f = InstanceFitter(B, H, W, dev, method=method)
+        stats = torch.zeros((B, 4), dtype=torch.int32, device=dev) if filter else None
+        boxes2d = torch.full((B, 8), float("nan"), dtype=torch.float64, device=dev) if image_size is not None else None
+        res = (f.boxes[0], f.status[0], f.aux[0]) + ((stats,) if filter else ()) + ((boxes2d,) if image_size is not None else ())
+        if B == 0:
+            return res
+        ah = None
+        if area_hint is not None:
+            ah = _as_dev(area_hint, torch.int32, dev).reshape(-1)
+            if ah.numel() != B:
+                raise ValueError("area_hint must have one entry per instance")
+        a = _fit_args(B, H, W, _ptr(d), P, _ptr(k), k.shape[0], _ptr(f.boxes[0]), _ptr(f.status[0]), _ptr(f.aux[0]),
+                      _ptr(f.workspace[0]), _stream(stream), image_index=_ptr(ii), ground=_ptr(g), sample_idx=_ptr(si), filter=filter,
+                      stats=_ptr(stats), proj=_ptr(boxes2d), image_size=image_size, area_hint=_ptr(ah), opts=options.codes(),
+                      frame_width=0 if fw == W else fw, method=meth)
+        check(lib.la3d_fit_instances_bits(C.byref(a), _ptr(mb.bits), _bits_stride(mb.bits, B, H, W), flags), "la3d_fit_instances_bits")
+    _record(stream, d, k, ii, g, si, ah, mb.bits, f.workspace, *res)
+    return res
 
 
 def masked_ratio_median(depth_map, depth_render, mask, render_mask=None, image_index=None, stream=None):
