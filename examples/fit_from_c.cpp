@@ -4,7 +4,8 @@
 // Builds B synthetic instances (private depth planes, one rectangle each, a ground plane per instance) with a small
 // LCG, runs la3d_fit_instances on HIP buffers and prints status + the 39 doubles of every record in hex-exact form
 // ("%a"), then repeats the fit through la3d_fit_instances_ex (C struct argument block) with the 2-D boxes of the records ("P"
-// lines) and, with the masks packed to bit planes, through la3d_fit_instances_bits.  tests/test_gpu_cabi.py regenerates the same inputs in NumPy and checks the printed records against the oracle.
+// lines), with the masks packed to bit planes, through la3d_fit_instances_bits and, with two frame sizes in one call, through
+// la3d_fit_instances_frames.  tests/test_gpu_cabi.py regenerates the same inputs in NumPy and checks the printed records against the oracle.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -114,6 +115,93 @@ int main(int argc, char** argv) {
           same = fabs(x - y) <= 1e-9 * (fabs(x) > 1.0 ? fabs(x) : 1.0);
         }
         if (!same) { fprintf(stderr, "la3d_fit_instances_bits: instance %d differs from the u8 call\n", i); return 13; }
+      }
+    }
+    // images of two DIFFERENT sizes in ONE call (la3d.h "images of different sizes in one call"): frame 0 is plane 0 at H x W, frame 1
+    // the upper left quarter of the last plane, both in one depth buffer at their own pitch (the next multiple of 32); instance i
+    // belongs to frame i % 2, its rectangle - cut to the frame - goes in as column-major run lengths over the frame's own size.
+    // Checked against one uniform call per frame size (la3d_fit_instances_ex with frame_width): same status, records to rounding.
+    {
+      const int fh[2] = {H, H > 1 ? H / 2 : 1}, fw[2] = {W, W > 1 ? W / 2 : 1}, src[2] = {0, B - 1};
+      int pitch[2]; int64_t off[2]; size_t total = 0;
+      for (int f = 0; f < 2; ++f) { pitch[f] = (fw[f] + 31) / 32 * 32; off[f] = (int64_t)total; total += (size_t)fh[f] * pitch[f]; }
+      std::vector<float> fdepth(total, 0.0f);
+      for (int f = 0; f < 2; ++f)
+        for (int r = 0; r < fh[f]; ++r)
+          for (int c = 0; c < fw[f]; ++c) fdepth[(size_t)off[f] + (size_t)r * pitch[f] + c] = depth[src[f] * HW + (size_t)r * W + c];
+      std::vector<la3d_frame> table(2);
+      for (int f = 0; f < 2; ++f) { table[f].depth_offset = off[f]; table[f].H = fh[f]; table[f].W = pitch[f]; table[f].frame_width = fw[f]; table[f].reserved = 0; }
+      std::vector<int32_t> counts, index(B);
+      std::vector<int64_t> offsets(B + 1, 0);
+      for (int i = 0; i < B; ++i) {   // column-major runs of instance i's mask inside its frame, zeros first
+        const int f = i % 2;
+        index[i] = f;
+        int run = 0, val = 0;
+        for (int c = 0; c < fw[f]; ++c)
+          for (int r = 0; r < fh[f]; ++r) {
+            const int v = mask[i * HW + (size_t)r * W + c] != 0;
+            if (v != val) { counts.push_back(run); run = 0; val = v; }
+            ++run;
+          }
+        counts.push_back(run);
+        offsets[i + 1] = (int64_t)counts.size();
+      }
+      float* d_fdepth; la3d_frame* d_table; int32_t *d_counts, *d_index, *d_status4; int64_t* d_offsets; double* d_out4;
+      HIPCHK(hipMalloc(&d_fdepth, total * 4)); HIPCHK(hipMalloc(&d_table, sizeof(la3d_frame) * 2)); HIPCHK(hipMalloc(&d_counts, counts.size() * 4));
+      HIPCHK(hipMalloc(&d_index, (size_t)B * 4)); HIPCHK(hipMalloc(&d_offsets, (size_t)(B + 1) * 8)); HIPCHK(hipMalloc(&d_status4, (size_t)B * 4));
+      HIPCHK(hipMalloc(&d_out4, (size_t)B * LA3D_REC * 8));
+      HIPCHK(hipMemcpy(d_fdepth, fdepth.data(), total * 4, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(d_table, table.data(), sizeof(la3d_frame) * 2, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(d_counts, counts.data(), counts.size() * 4, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(d_index, index.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(d_offsets, offsets.data(), (size_t)(B + 1) * 8, hipMemcpyHostToDevice));
+      la3d_fit_args m = {};
+      m.struct_size = (int32_t)sizeof(m);
+      m.B = B; m.H = fh[0]; m.W = pitch[0];                 // the bounds: the largest rows, the largest pitch
+      m.depth = d_fdepth; m.image_index = d_index; m.rle_counts = d_counts; m.rle_offsets = d_offsets; m.K = d_K; m.ground = d_ground;
+      m.out = d_out4; m.status = d_status4; m.stream = stream;
+      void* d_ws4;
+      const size_t ws4 = la3d_fit_workspace_bytes(&m);
+      HIPCHK(hipMalloc(&d_ws4, ws4 ? ws4 : 8));
+      m.workspace = d_ws4;
+      if (la3d_fit_instances_frames(&m, d_table, 2) != LA3D_SUCCESS) { fprintf(stderr, "la3d_fit_instances_frames: %s\n", la3d_last_error()); return 14; }
+      HIPCHK(hipStreamSynchronize(stream));
+      std::vector<double> out4((size_t)B * LA3D_REC), out5((size_t)B * LA3D_REC);
+      std::vector<int32_t> status4(B), status5(B);
+      HIPCHK(hipMemcpy(out4.data(), d_out4, out4.size() * 8, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(status4.data(), d_status4, (size_t)B * 4, hipMemcpyDeviceToHost));
+      for (int f = 0; f < 2; ++f) {   // the uniform entry, one call per frame size, on the instances of that frame
+        std::vector<int32_t> cf;
+        std::vector<int64_t> of(1, 0);
+        std::vector<double> gf;
+        std::vector<int> ids;
+        for (int i = f; i < B; i += 2) {
+          cf.insert(cf.end(), counts.begin() + offsets[i], counts.begin() + offsets[i + 1]);
+          of.push_back((int64_t)cf.size());
+          gf.insert(gf.end(), ground.begin() + i * 4, ground.begin() + i * 4 + 4);
+          ids.push_back(i);
+        }
+        const int Bf = (int)ids.size();
+        if (Bf == 0) continue;
+        HIPCHK(hipMemcpy(d_counts, cf.data(), cf.size() * 4, hipMemcpyHostToDevice));      // (the buffers of the mixed call are large enough)
+        HIPCHK(hipMemcpy(d_offsets, of.data(), of.size() * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_out2, gf.data(), gf.size() * 8, hipMemcpyHostToDevice));        // (d_out2 is free by now: the sub-batch's ground rows)
+        la3d_fit_args u = m;
+        u.B = Bf; u.H = fh[f]; u.W = pitch[f]; u.frame_width = fw[f] == pitch[f] ? 0 : fw[f];
+        u.depth = d_fdepth + off[f]; u.image_index = nullptr; u.depth_plane_stride = 0; u.ground = d_out2;
+        if (la3d_fit_instances_ex(&u) != LA3D_SUCCESS) { fprintf(stderr, "la3d_fit_instances_ex (frame %d): %s\n", f, la3d_last_error()); return 15; }
+        HIPCHK(hipStreamSynchronize(stream));
+        HIPCHK(hipMemcpy(out5.data(), d_out4, (size_t)Bf * LA3D_REC * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(status5.data(), d_status4, (size_t)Bf * 4, hipMemcpyDeviceToHost));
+        for (int n = 0; n < Bf; ++n) {
+          const int i = ids[n];
+          bool same = status5[n] == status4[i];
+          for (int k = 0; same && status4[i] == LA3D_BOX_OK && k < 15; ++k) {
+            const double x = out4[(size_t)i * LA3D_REC + k], y = out5[(size_t)n * LA3D_REC + k];
+            same = fabs(x - y) <= 1e-9 * (fabs(x) > 1.0 ? fabs(x) : 1.0);
+          }
+          if (!same) { fprintf(stderr, "la3d_fit_instances_frames: instance %d differs from the uniform call of its frame size\n", i); return 16; }
+        }
       }
     }
     a.struct_size = 8;   // a truncated argument block is an error, not a crash

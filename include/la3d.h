@@ -344,6 +344,47 @@ int la3d_unpack_mask_bits(const uint32_t* bits, int64_t bits_plane_stride, int B
 int la3d_mask_stats_bits(const uint32_t* bits, int64_t bits_plane_stride, int B, int H, int W, int frame_width, int boundary,
                          int32_t* stats, void* stream);
 
+/* ---- images of different sizes in one call ---------------------------------------------------------------------------
+ * Every entry above takes ONE (H, W) per call; a COCO shard comes in hundreds of frame sizes.  la3d_fit_instances_frames fits
+ * instances of images of DIFFERENT sizes in one launch: the depth planes lie in one buffer, each at its own offset and pitch, and a
+ * device-resident table says where - one la3d_frame row per IMAGE:
+ *   depth_offset  floats from args->depth to the image's plane (>= 0, a multiple of 4: 16-byte aligned planes)
+ *   H, W          rows, and pixels per row IN MEMORY (the pitch), W % 32 == 0
+ *   frame_width   image columns, 0 < frame_width <= W; the columns beyond are padding (what la3d_fit_args::frame_width says for a
+ *                 uniform call, here per image)
+ *   reserved      0
+ * args: the block of la3d_fit_instances_ex, where
+ *   - H, W are BOUNDS: every frame has H <= args->H and W <= args->W.  They size the kernel's LDS and the workspace
+ *     (la3d_fit_workspace_bytes(args) stays the sizing call); they need not be multiples of anything, H * roundup32(W) <= 1048576;
+ *   - image_index is REQUIRED: instance n belongs to frame row image_index[n] (and, as ever, to K + image_index[n] * k_stride);
+ *   - depth must be 16-byte aligned; depth_plane_stride and frame_width of the block must be 0;
+ *   - image_width / image_height are ignored: proj clamps to the instance's own frame_width x H;
+ *   - run lengths are column-major over the instance's own (H, frame_width); polygon sides are clipped to the instance's own
+ *     frame_width x H; the fused filter takes H and the right and bottom borders from the instance's frame;
+ *   - masks: rle_counts (+ rle_offsets) or poly_xy (+ ring_offsets, inst_rings) - the annotation formats.  mask (u8 planes) and
+ *     bit planes: LA3D_ERR_UNSUPPORTED.  method = LA3D_METHOD_CONVEX_HULL: LA3D_ERR_UNSUPPORTED in this first form;
+ *   - ground, sample_idx (reference-subsample mode), filter_* + stats, proj, aux, area_hint, opt_launch_order, stream mean what they
+ *     mean in la3d_fit_instances_ex.  The call runs on the instance engine (opt_engine pins give way, as for bit planes), in its
+ *     tiled form.  The size-balanced launch order runs when area_hint is given (same batch range as elsewhere); without a hint
+ *     workgroup b fits instance xcd_remap(b) - no estimate pass.  Records never depend on either.
+ * frames: DEVICE pointer to P rows.  The library never synchronises, so a row that breaks the contract cannot fail the call: every
+ * instance whose image_index lies outside [0, P), or whose frame row has a pitch that is not a multiple of 32, a negative or
+ * misaligned depth_offset, H or W outside (0, bound], or frame_width outside (0, W], gets LA3D_BOX_UNSUPPORTED and a NaN record
+ * (aux = NaN, 0, NaN, NaN; stats row untouched), decided in the kernel before any address is formed from the row; every other
+ * instance of the call is fitted as if the broken row were not there.  What a conforming row addresses - H * W floats from
+ * depth_offset on - must lie inside the caller's buffer: that the library cannot check.
+ * Covered frames: EVERY frame inside the contract is fitted, small ones included (a frame of fewer than 64 tiles of 32 x 8 pixels,
+ * the floor of the uniform entry's tiled form, is fitted too: the call's LDS is sized for at least 64 tiles whatever the bounds).
+ * A call whose bounds exceed what the tiled form holds (H > 2040, W > 8160, or - subsample mode - a bit image + rank prefix beyond
+ * one workgroup's LDS) returns LA3D_ERR_UNSUPPORTED as a whole. */
+typedef struct la3d_frame {      /* one row per IMAGE, device-resident */
+  int64_t depth_offset;          /* floats from args->depth to this image's plane; % 4 == 0 */
+  int32_t H, W;                  /* rows; pixels per row IN MEMORY (the pitch), W % 32 == 0 */
+  int32_t frame_width;           /* image columns, 0 < frame_width <= W; columns beyond are padding */
+  int32_t reserved;              /* 0 */
+} la3d_frame;
+int la3d_fit_instances_frames(const la3d_fit_args* args, const la3d_frame* frames, int32_t P);
+
 /* create_boolean_mask_from_polygon for a batch: polygon parts -> u8 planes mask_out dev [B][H*W] (0/1). */
 int la3d_poly_decode(const int32_t* poly_xy, const int64_t* ring_offsets, const int64_t* inst_rings, int B, int H, int W,
                      uint8_t* mask_out, void* stream);

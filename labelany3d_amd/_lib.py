@@ -35,8 +35,14 @@ class FitArgs(C.Structure):
                 ("method", C.c_int32)]
 
 
+class Frame(C.Structure):
+    """``la3d_frame`` of include/la3d.h: one row per image of a frames call (la3d_fit_instances_frames)."""
+    _fields_ = [("depth_offset", C.c_int64), ("H", C.c_int32), ("W", C.c_int32), ("frame_width", C.c_int32), ("reserved", C.c_int32)]
+
+
 _SIGS = {
     "la3d_fit_instances_ex": (C.c_int, [C.POINTER(FitArgs)]),
+    "la3d_fit_instances_frames": (C.c_int, [C.POINTER(FitArgs), C.c_void_p, C.c_int32]),
     "la3d_fit_workspace_bytes": (C.c_size_t, [C.POINTER(FitArgs)]),
     "la3d_fit_instances_bits": (C.c_int, [C.POINTER(FitArgs), C.c_void_p, C.c_int64, C.c_int32]),
     "la3d_mask_bits_words": (C.c_size_t, [C.c_int, C.c_int]),

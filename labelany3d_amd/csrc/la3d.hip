@@ -175,12 +175,23 @@ size_t la3d_fit_workspace_bytes(const la3d_fit_args* args) {
 }
 
 struct BitsSource { const uint32_t* planes; int64_t plane_stride; int32_t flags; };   // la3d_fit_instances_bits' own arguments
+struct FramesSource { const la3d_frame* rows; int32_t P; };                           // la3d_fit_instances_frames' own arguments
 
 // Every fit entry ends here with its arguments in one block.  filter_on: the fused instance filter runs (the *_filtered entries
 // always; la3d_fit_instances_ex when filter_boundary >= 0 and filter_max_edge > 0).  who: the entry named in la3d_last_error().
 // bs: the bit planes of la3d_fit_instances_bits (an internal parameter: the public block is frozen), null for every other entry.
-static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who, const BitsSource* bs = nullptr) {
-  const int B = a.B, H = a.H, W = a.W;
+// fr: the frame table of la3d_fit_instances_frames (H, W of the block are then bounds), null for every other entry.
+static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who, const BitsSource* bs = nullptr,
+                        const FramesSource* fr = nullptr) {
+  const int B = a.B;
+  int H = a.H, W = a.W;
+  if (fr && H > 0 && W > 0 && W <= (1 << 20)) {
+    // frames of different sizes: what the call reserves (LDS bit image, tile list) is sized for the bounds with the pitch rounded up
+    // to whole words and, so that every frame inside the contract has a tiled form, for at least 64 tiles of 32 x 8 pixels
+    W = (W + 31) / 32 * 32;
+    const int ntx = W / 32, need = (64 + ntx - 1) / ntx;
+    if ((H + 7) / 8 < need) H = need * 8;
+  }
   const bool rle = a.rle_counts != nullptr || a.poly_xy != nullptr || bs != nullptr;   // "no u8 plane": the mask is decoded into the LDS bit image
   if (!a.depth || (!a.mask && !rle) || (a.rle_counts && !a.rle_offsets) || (a.poly_xy && (!a.ring_offsets || !a.inst_rings)) ||
       !a.K || !a.out || !a.status || B < 0 || H <= 0 || W <= 0 ||
@@ -226,6 +237,7 @@ static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who,
   p.area_hint = a.area_hint;
   p.opt_engine = a.opt_engine; p.opt_order = a.opt_launch_order; p.opt_build = a.opt_build;
   p.frame_w = W;
+  if (fr) { p.frames = fr->rows; p.frames_P = fr->P; p.frames_max_h = a.H; p.frames_max_w = a.W; }
   if (a.frame_width != 0 && a.frame_width != W) {
     // rows padded on the right (la3d_fit_args::frame_width): run-length / polygon masks, word-aligned rows
     if (a.frame_width < 0 || a.frame_width > W || a.mask != nullptr || W % 32 != 0) {
@@ -243,7 +255,7 @@ static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who,
     p.filter_boundary = a.filter_boundary; p.filter_min_area = a.filter_min_area; p.filter_max_edge = a.filter_max_edge;
     p.filter_stats = a.stats;
   }
-  const int bit_bytes = ((((p.HW + 15) / 16 + 1) / 2) * 4 + 15) & ~15;  // u16 per 16 px, padded to u32, 16-aligned
+  const int bit_bytes = mask_bit_bytes(p.HW);
   CallFacts f;
   f.ldsmask = bit_bytes <= MAX_MASK_LDS;
   p.mask_lds_bytes = f.ldsmask ? bit_bytes : 0;
@@ -257,6 +269,7 @@ static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who,
           ((reinterpret_cast<uintptr_t>(a.depth) & 15) == 0) && (a.depth_plane_stride % 4 == 0);
   f.sample = a.sample_idx != nullptr;
   f.method = a.method;
+  f.frames = fr != nullptr;
   if (a.method == LA3D_METHOD_CONVEX_HULL)
     f.hull_area = static_cast<unsigned char*>(a.workspace) + up256(la3d_workspace_bytes(B, H, W));
   f.lds = (size_t)p.mask_lds_bytes + sizeof(Shared);
@@ -264,6 +277,8 @@ static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who,
   f.poly_stage = a.poly_xy ? (size_t)POLY_STAGE_BYTES : 0;
   const int pin = a.opt_engine != LA3D_ENGINE_DEFAULT ? a.opt_engine : config().engine;   // per-call pin, else the process default
   hipStream_t s = static_cast<hipStream_t>(a.stream);
+  // frames of different sizes: the instance engine at every batch size (no other engine reads a frame table); pins give way
+  if (fr) return instance_fit(p, f, s, a.workspace, who);
   switch (choose_engine(p, f, pin)) {
   case LA3D_ENGINE_ROWS:   // (two launches when pinned so, and for a call captured into a HIP graph: it would replay with the same tag)
     return rows_fit(p, pin == LA3D_ENGINE_ROWS2 || stream_capturing(s), s, a.workspace);
@@ -447,6 +462,56 @@ int la3d_fit_instances_bits(const la3d_fit_args* args, const uint32_t* mask_bits
   if (rc != LA3D_SUCCESS) return rc;
   const BitsSource bs{mask_bits, bits_plane_stride, flags};
   return fit_dispatch(a, a.filter_boundary >= 0 && a.filter_max_edge > 0, "la3d_fit_instances_bits", &bs);
+}
+
+int la3d_fit_instances_frames(const la3d_fit_args* args, const la3d_frame* frames, int32_t P) {
+  constexpr int32_t V1_SIZE = (int32_t)offsetof(la3d_fit_args, area_hint);
+  static_assert(sizeof(la3d_frame) == 24, "la3d_frame is part of the ABI");
+  if (!args || args->struct_size < V1_SIZE) {
+    set_err("la3d_fit_instances_frames: bad struct_size");
+    return LA3D_ERR_ARG;
+  }
+  la3d_fit_args a;
+  memset(&a, 0, sizeof(a));
+  memcpy(&a, args, (size_t)args->struct_size < sizeof(a) ? (size_t)args->struct_size : sizeof(a));
+  if (a.mask) {
+    set_err("la3d_fit_instances_frames: u8 mask planes are not supported - run lengths or polygon parts");
+    return LA3D_ERR_UNSUPPORTED;
+  }
+  if (a.method == LA3D_METHOD_CONVEX_HULL) {
+    set_err("la3d_fit_instances_frames: method = LA3D_METHOD_CONVEX_HULL is not supported in this form");
+    return LA3D_ERR_UNSUPPORTED;
+  }
+  const int kinds = (a.rle_counts ? 1 : 0) + (a.poly_xy ? 1 : 0);
+  if (kinds != 1 && a.B > 0) {
+    set_err("la3d_fit_instances_frames: give exactly one of rle_counts / poly_xy");
+    return LA3D_ERR_ARG;
+  }
+  if (a.poly_xy && (!a.ring_offsets || !a.inst_rings)) {
+    set_err("la3d_fit_instances_frames: polygon masks need ring_offsets and inst_rings");
+    return LA3D_ERR_ARG;
+  }
+  if (P < 0 || (a.B > 0 && (!frames || P == 0 || (reinterpret_cast<uintptr_t>(frames) & 7)))) {
+    set_err("la3d_fit_instances_frames: frames must be an 8-byte aligned device pointer to P >= 1 rows");
+    return LA3D_ERR_ARG;
+  }
+  if (a.B > 0 && !a.image_index) {
+    set_err("la3d_fit_instances_frames: image_index is required (instance n belongs to frame row image_index[n])");
+    return LA3D_ERR_ARG;
+  }
+  if (a.depth_plane_stride != 0 || a.frame_width != 0) {
+    set_err("la3d_fit_instances_frames: depth_plane_stride and frame_width must be 0 (the frame table holds them per image)");
+    return LA3D_ERR_ARG;
+  }
+  if (reinterpret_cast<uintptr_t>(a.depth) & 15) {
+    set_err("la3d_fit_instances_frames: depth must be 16-byte aligned");
+    return LA3D_ERR_ARG;
+  }
+  a.image_width = a.image_height = 1.0;   // (ignored: proj clamps to the instance's own frame)
+  const int rc = check_block_options(a, "la3d_fit_instances_frames");
+  if (rc != LA3D_SUCCESS) return rc;
+  const FramesSource fs{frames, P};
+  return fit_dispatch(a, a.filter_boundary >= 0 && a.filter_max_edge > 0, "la3d_fit_instances_frames", nullptr, &fs);
 }
 
 }  // extern "C"

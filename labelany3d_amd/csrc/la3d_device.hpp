@@ -537,6 +537,11 @@ struct FitParams {
   long long bits_plane_stride = 0;
   int bits_vec = 0;    // base 16-byte aligned and bits_plane_stride % 4 == 0: the plane streams in 16-byte groups
   int bits_span = 0;   // fused filter: height = last row - first row + 1 (LA3D_BITS_HEIGHT_SPAN) instead of the rows holding a pixel
+  // frames of different sizes in one call (la3d_fit_instances_frames): one la3d_frame row per IMAGE; H / W above (and everything
+  // sized by them: mask_lds_bytes, list_cap) are then the call's sizing bounds, frames_max_h / frames_max_w the bounds of the contract
+  const la3d_frame* frames = nullptr;
+  int frames_P = 0;
+  int frames_max_h = 0, frames_max_w = 0;
 };
 
 // Bit plane (global) -> LDS bit image, by all NTH threads of the workgroup: a straight copy - 16-byte non-temporal loads and 16-byte
@@ -609,6 +614,82 @@ struct alignas(16) Shared {
 #else
 #define LA3D_SUBSTAMP(sh, k) do { } while (0)
 #endif
+
+// Frames call: the geometry of the instance's own frame replaces the call constants in the workgroup's copy of the parameters.  img =
+// image_index[inst], wave-uniform, so the row is read with scalar loads and everything derived from it stays in SGPRs.  A row that
+// breaks the contract of la3d_frame (or an image index outside the table) returns false BEFORE any address is formed from it: the
+// caller then writes LA3D_BOX_UNSUPPORTED and touches neither depth nor K.  The LDS layout (mask_lds_bytes, list_cap) stays the
+// call's: H <= frames_max_h and W <= frames_max_w keep every per-frame size below what the launch reserved.
+// The call constants of the other instantiations are kernel arguments, which the compiler re-loads wherever registers are short; a
+// frame's values would stay live from here to the record.  So the kernel calls frame_geometry again behind its mask stage (checked
+// = false: the row has passed), and takes the values only a single stage needs where that stage begins (frame_rcp_ntx, frame_proj,
+// rcpW): without that the instantiations spill.
+// What a call on a frame of H x W reserves in LDS - the bytes of the bit image and the entries of the active-tile list - in ONE place,
+// for the host (fit_dispatch sizes the image, instance_fit the list of the tiled forms) and for the kernel: the kernel decides by
+// these two how an instance is walked (tile list or dense walk, compacted image, single pass).  A frames call decides by the values of
+// the instance's OWN frame, not by its larger reservation, wherever they fit into it: the instance then takes the path, and so the
+// grouping of the fp64 partial sums, it takes in a uniform call of its frame size - the same record bit for bit (a frame whose
+// uniform list would be longer than the call's takes the call's: equal to rounding).
+// mask_bit_bytes: u16 per 16 px, padded to u32, 16-aligned.
+__host__ __device__ inline int mask_bit_bytes(int HW) { return ((((HW + 15) / 16 + 1) / 2) * 4 + 15) & ~15; }
+// rank_prefix_bytes (subsample mode): one prefix word per 32-word block of the bit image
+__host__ __device__ inline int rank_prefix_bytes(int nwords) { return ((nwords + 31) / 32) * 4 + 16; }
+// tiled_list_cap: entries of the list behind bit image + Shared.  Full-mask mode: the largest number of workgroups per CU (160 KiB of
+// LDS) that still leaves a useful list - up to 256 entries are worth giving up a workgroup for; subsample mode: a quarter of the CU's
+// LDS, grown in 8 KiB steps until the rank prefix fits (budget_out: what the workgroup then takes).  Never more than the frame's tiles.
+template <bool SAMPLE>
+__host__ __device__ inline int tiled_list_cap(int bit_bytes, int nwords, int ntiles, int* budget_out = nullptr) {
+  const int fixed = bit_bytes + (int)sizeof(Shared);
+  int cap = 0, budget = (160 * 1024 / 4) & ~15;
+  if (SAMPLE) {
+    const int blocks = rank_prefix_bytes(nwords);
+    while (budget < fixed + (blocks > 128 ? blocks : 128)) budget += 8 * 1024;
+    cap = (budget - fixed) / 2;
+  } else {
+    const int want = ntiles < 256 ? ntiles : 256;
+    for (int wg = 4; wg >= 1 && cap < want; --wg) {
+      budget = (160 * 1024 / wg) & ~15;
+      cap = (budget - fixed) / 2;
+    }
+  }
+  if (budget_out) *budget_out = budget;
+  return cap > ntiles ? ntiles : cap;
+}
+template <bool CHECKED, bool SAMPLE>
+__device__ inline bool frame_geometry(FitParams& p, const FitParams& call, int img) {
+  if (CHECKED && (unsigned)img >= (unsigned)call.frames_P) return false;
+  const la3d_frame* fr = call.frames + img;
+  const long long off_v = fr->depth_offset;
+  const long long off = ((long long)__builtin_amdgcn_readfirstlane((int)(off_v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)off_v);
+  const int H = __builtin_amdgcn_readfirstlane(fr->H), W = __builtin_amdgcn_readfirstlane(fr->W);
+  const int fw = __builtin_amdgcn_readfirstlane(fr->frame_width);
+  if (CHECKED && (H <= 0 || W <= 0 || (W & 31) != 0 || H > call.frames_max_h || W > call.frames_max_w || fw <= 0 || fw > W || off < 0 ||
+                  (off & 3) != 0))
+    return false;
+  p.depth = call.depth + off; p.depth_plane_stride = 0;
+  p.H = H; p.W = W; p.HW = H * W; p.nwords = p.HW >> 5;   // (W % 32 == 0: whole words)
+  p.rows_aligned = 1;
+  p.ntx = W >> 5; p.nty = (H + 7) >> 3;
+  p.tiles_per_wave = (p.ntx * p.nty + NWAVE - 1) / NWAVE;
+  p.frame_w = fw;
+  p.mask_lds_bytes = min(call.mask_lds_bytes, mask_bit_bytes(p.HW));
+  p.list_cap = min(call.list_cap, max(tiled_list_cap<SAMPLE>(p.mask_lds_bytes, p.nwords, p.ntx * p.nty), 64));
+  // (rcpW, rcp_ntx and proj_w / proj_h are NOT set here: until the stage that needs one sets it - the subsample pick, the tile list,
+  // the record - the copy holds the value of the call's bounds, which is wrong for the frame; a new reader of p.rcpW in these
+  // instantiations must compute it first, as the subsample pick does - pix_uv corrects a reciprocal by one step only)
+  return true;
+}
+// 1 / ntx of the tile index arithmetic: IEEE division, as on the host (the arithmetic relies on it, see instance_fit); computed by
+// the vector unit - the scalar unit has no such arithmetic - and moved to an SGPR
+__device__ inline void frame_rcp_ntx(FitParams& p) {
+  p.rcp_ntx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(1.0f / (float)p.ntx)));
+}
+// the clamp limits of proj: the instance's own frame_width x H, read where the record is written
+__device__ inline void frame_proj(FitParams& p, const FitParams& call, int inst) {
+  if (!call.proj) return;
+  const la3d_frame* fr = call.frames + call.image_index[inst];
+  p.proj_w = (double)__builtin_amdgcn_readfirstlane(fr->frame_width); p.proj_h = (double)__builtin_amdgcn_readfirstlane(fr->H);
+}
 
 __device__ inline void pix_uv(unsigned i, int W, float rcpW, unsigned* u, unsigned* v) {
   unsigned vv = (unsigned)((float)i * rcpW);

@@ -15,6 +15,7 @@ struct CallFacts {
   size_t lds;          // bit image + Shared
   size_t poly_stage;   // polygon input: the side stage behind Shared, else 0
   int method = 0;      // LA3D_METHOD_*: a convex-hull call (la3d_fit_args::method) runs on the instance engine only
+  bool frames = false; // la3d_fit_instances_frames: frames of different sizes (FitParams::frames), the instance engine's tiled form only
   void* hull_area = nullptr;   // hull call: the hand-off area behind the first la3d_workspace_bytes(B,H,W) bytes of the workspace
 };
 

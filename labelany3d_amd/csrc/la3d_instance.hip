@@ -68,15 +68,23 @@ __device__ inline void sweep_sep_hull(const FitParams& p, const float* __restric
 // HULL: the instantiations of a convex-hull call (la3d_fit_args::method) - everything a PCA call does up to
 // and including the axis, then, instead of extents and record, the hand-off of hull_finish_kernel through the workspace (p.geo
 // points at the call's hand-off area).  Every difference sits behind the constant HULL: the PCA instantiations (HULL = false) compile to the code they were.
-template <bool VEC, bool LDSMASK, bool SAMPLE, bool TILED, int SRC, bool HULL = false>
-__global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitParams p) {
+// FRAMES: the instantiations of la3d_fit_instances_frames - images of different sizes in one call.  The kernel argument then holds
+// the call's sizing bounds; once the workgroup knows its instance and image it reads the image's la3d_frame row and replaces the
+// frame geometry in ITS copy of the parameters (frame_geometry, la3d_device.hpp), which everything below reads.  Every difference sits behind the
+// constant FRAMES: the other instantiations read the kernel argument itself, as they did.
+template <bool VEC, bool LDSMASK, bool SAMPLE, bool TILED, int SRC, bool HULL = false, bool FRAMES = false>
+__global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitParams p_call) {
+  static_assert(!FRAMES || (VEC && LDSMASK && TILED && !HULL && (SRC == 1 || SRC == 2)), "frames calls: run lengths / polygons, tiled form");
+  FitParams p_frame;   // FRAMES only: this workgroup's parameters (dead otherwise)
+  if constexpr (FRAMES) p_frame = p_call;
+  const FitParams& p = FRAMES ? p_frame : p_call;   // (the LDS LAYOUT below is always the call's: p_call.mask_lds_bytes)
   constexpr bool RLE = SRC == 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned* bits = reinterpret_cast<unsigned*>(smem);
-  Shared* sh = reinterpret_cast<Shared*>(smem + p.mask_lds_bytes);
-  unsigned* prefix = reinterpret_cast<unsigned*>(smem + p.mask_lds_bytes + sizeof(Shared));  // SAMPLE only
+  Shared* sh = reinterpret_cast<Shared*>(smem + p_call.mask_lds_bytes);
+  unsigned* prefix = reinterpret_cast<unsigned*>(smem + p_call.mask_lds_bytes + sizeof(Shared));  // SAMPLE only
   // TILED only: compacted list of active tile ids
-  unsigned short* list = reinterpret_cast<unsigned short*>(smem + p.mask_lds_bytes + sizeof(Shared));
+  unsigned short* list = reinterpret_cast<unsigned short*>(smem + p_call.mask_lds_bytes + sizeof(Shared));
 
   // (builds that carry the separable pass take the lane from the execution mask, not from threadIdx.x - the workgroup's waves are
   // full -, and rebuild the thread index where it is used: neither then keeps the kernel's input register alive across the passes)
@@ -95,7 +103,7 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
   // (self-estimating launch; order_self == 2 is the test mode of the fallback: every seventh workgroup keeps its key to itself)
   // (batches above one resident set: the workgroups of the FIRST set - the only ones certain to run without waiting for anybody -
   // estimate instances b, b + R, b + 2R, ...)
-  if (!SAMPLE && p.order_self && (int)blockIdx.x < p.order_resident && !(p.order_self == 2 && blockIdx.x % 7 == 3)) {
+  if (!FRAMES && !SAMPLE && p.order_self && (int)blockIdx.x < p.order_resident && !(p.order_self == 2 && blockIdx.x % 7 == 3)) {
     for (int ie = (int)blockIdx.x; ie < p.B; ie += p.order_resident) {   // uniform
       if (ie != (int)blockIdx.x) __syncthreads();   // (the block totals of the previous estimate have been read)
       estimate_publish_wg<SRC == 3>(p, ie, sh, tid, wave, lane);
@@ -105,6 +113,20 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
   if (tid == 0) { sh->order_inst = inst; sh->sep_bad = 0; }   // (the instance is re-read after the mask stage, see below)
   if constexpr (HULL) { if (tid == 0) hull_slot(p.geo, inst, hull_stride_bytes(SAMPLE, p.W))[HH_STATE] = -1.0; }   // nothing to finish, until the hand-off says so
   const int img = p.image_index ? p.image_index[inst] : inst;
+  if constexpr (FRAMES) {
+    if (!frame_geometry<true, SAMPLE>(p_frame, p_call, img)) {   // uniform: an image index outside the table or a frame row outside the contract - refused
+      if (tid == 0) {                    // before anything is read through it (no barrier has been passed: the whole workgroup leaves)
+        if (p.aux) {
+          double* a = p.aux + (long long)inst * LA3D_AUX;
+          a[0] = NAN; a[1] = 0.0; a[2] = NAN; a[3] = NAN;
+        }
+        p.status[inst] = LA3D_BOX_UNSUPPORTED;
+        write_nan_box(p.out + (long long)inst * LA3D_REC);
+        if (p.proj) { for (int j = 0; j < 8; ++j) p.proj[(long long)inst * 8 + j] = NAN; }
+      }
+      return;
+    }
+  }
   const int HW = p.HW;
   const float* dpl = p.depth + (long long)img * p.depth_plane_stride;
   const unsigned char* mpl = p.mask ? p.mask + (long long)inst * HW : nullptr;
@@ -161,12 +183,12 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
     const long long o0 = p.rle_offsets[inst];
     // (the block totals of the column scan borrow the LDS of the tile list, which is built afterwards)
     nmask = rle_to_bits<NT>(p.rle_counts + o0, (int)(p.rle_offsets[inst + 1] - o0), bits, p.nwords, p.H, p.W, sh->scan, tid,
-                            reinterpret_cast<unsigned*>(smem + p.mask_lds_bytes + sizeof(Shared)), TILED ? p.list_cap / 2 : 0, p.frame_w);
+                            reinterpret_cast<unsigned*>(smem + p_call.mask_lds_bytes + sizeof(Shared)), TILED ? p.list_cap / 2 : 0, p.frame_w);
   } else if (LDSMASK && SRC == 2) {
     // masks arrive as polygon parts (the reference's create_boolean_mask_from_polygon, src/util.py:386-400): rasterised with
     // cv2.fillPoly's rule straight into the LDS bit image; the side stage borrows the space of the tile list
     nmask = poly_to_bits<NT>(p.poly_xy, p.poly_ring_off, p.poly_inst_rings[inst], p.poly_inst_rings[inst + 1],
-                             reinterpret_cast<PolySide*>(smem + p.mask_lds_bytes + sizeof(Shared)), sh->scan, bits, p.nwords, p.H,
+                             reinterpret_cast<PolySide*>(smem + p_call.mask_lds_bytes + sizeof(Shared)), sh->scan, bits, p.nwords, p.H,
                              p.W, tid, p.frame_w);
   } else if (LDSMASK && SRC == 3) {
     // masks arrive as bit planes: the plane IS the bit image - a straight stream into LDS, no decode (38 400 B for 640x480 against
@@ -227,6 +249,7 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
   // (from here on the instance index is re-read from LDS: live across the decode stage it costs the polygon build a spilled
   // register pair)
   const int inst_p = __builtin_amdgcn_readfirstlane(sh->order_inst);
+  if constexpr (FRAMES) frame_geometry<false, SAMPLE>(p_frame, p_call, p.image_index[inst_p]);   // (re-read for the same reason: see frame_geometry)
   // (and from here on the thread index is rebuilt where it is used - one v_lshl_or from the wave's scalar index and the lane -
   // instead of staying live from kernel entry: with the separable pass in the kernel the allocator otherwise spills it to scratch,
   // and a kernel with scratch launches its waves visibly slower: round 5, B = 8192 590 -> 670 us)
@@ -282,6 +305,7 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
   bool sep = false;
   const bool sep_cam = LK && (HULL || !p.sep_off) && Mg[1] == 0.0 && Mg[3] == 0.0 && Mg[6] == 0.0 && Mg[7] == 0.0 && Mg[8] == 1.0;   // uniform
   if (TILED && !sampled) {
+    if constexpr (FRAMES) frame_rcp_ntx(p_frame);
     const int ntiles = p.ntx * p.nty, per = p.tiles_per_wave;
     const int tbeg = wave * per, tend = min(tbeg + per, ntiles);
     int base = 0;
@@ -491,6 +515,7 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
         sep_col_extents(col, p.W, N0, N2, tid, ext);
         ext[2] = ylo_w; ext[3] = yhi_w;
         LA3D_STAMP(5);
+        if constexpr (FRAMES) frame_proj(p_frame, p_call, inst_p);
         stage_extents_to_box(sh, p, inst_p, ext, tid, wave, lane);
         stage_status_aux(sh, p, inst_p, tid);
         LA3D_STAMP(6);
@@ -599,6 +624,7 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
         const unsigned i = (unsigned)lo * 32u + (unsigned)(__ffs((int)w) - 1);
         const float df = dpl[i];
         unsigned u, v;
+        if constexpr (FRAMES) p_frame.rcpW = 1.0f / (float)p.W;
         pix_uv(i, p.W, p.rcpW, &u, &v);
         const double ud = (double)u, vd = (double)v;
         pok = finite_f32(df);
@@ -716,6 +742,7 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
     else sweep<VEC, LDSMASK, 1>(p, dpl, mpl, bits, N0, Mg + 3, N2, wave, lane, ext, &d0, &d1);
   }
   LA3D_STAMP(5);
+  if constexpr (FRAMES) frame_proj(p_frame, p_call, inst_p);
   stage_extents_to_box(sh, p, inst_p, ext, tid, wave, lane);
   stage_status_aux(sh, p, inst_p, tid);
   LA3D_STAMP(6);
@@ -868,14 +895,15 @@ int launch_hull(const FitParams& p, size_t lds, hipStream_t s) {
   return launch_hull_inst<VEC, SAMPLE, 0>(p, lds, s);
 }
 
-template <bool VEC, bool LDSMASK, bool SAMPLE, bool TILED, int SRC>
+template <bool VEC, bool LDSMASK, bool SAMPLE, bool TILED, int SRC, bool FRAMES = false>
 int launch_fit_inst(const FitParams& p_in, size_t lds, hipStream_t s, void* workspace) {
-  auto kern = fit_instances_kernel<VEC, LDSMASK, SAMPLE, TILED, SRC>;
+  auto kern = fit_instances_kernel<VEC, LDSMASK, SAMPLE, TILED, SRC, false, FRAMES>;
   allow_big_lds(reinterpret_cast<const void*>(kern));
   FitParams p = p_in;
   // size-balanced launch order: needs the 16-byte mask groups (VEC), more than one workgroup per CU, and a batch
   // the O(B^2) ranking is cheap for
-  if (workspace && VEC && !SAMPLE && p.B > 256 && p.B <= ORDER_MAX_B && balance_enabled(p)) {
+  // (a frames call orders by the caller's area_hint only: the estimates know one frame size per call)
+  if (workspace && VEC && !SAMPLE && p.B > 256 && p.B <= ORDER_MAX_B && balance_enabled(p) && (!FRAMES || p.area_hint)) {
     int wg_per_cu = 2048 / NT;  // wave slots: 32 per CU at 64 VGPRs
     const int by_lds = (int)((160 * 1024) / (lds ? lds : 1));
     if (by_lds < wg_per_cu) wg_per_cu = by_lds;
@@ -925,6 +953,14 @@ int launch_fit(const FitParams& p, size_t lds, hipStream_t s, void* workspace = 
   return launch_fit_inst<VEC, LDSMASK, SAMPLE, TILED, 0>(p, lds, s, workspace);
 }
 
+
+// la3d_fit_instances_frames: run lengths or polygon parts, the tiled form (full-mask or subsample)
+template <bool SAMPLE>
+int launch_fit_frames(const FitParams& p, size_t lds, hipStream_t s, void* workspace) {
+  if (p.rle_counts != nullptr) return launch_fit_inst<true, true, SAMPLE, true, 1, true>(p, lds, s, workspace);
+  return launch_fit_inst<true, true, SAMPLE, true, 2, true>(p, lds, s, workspace);
+}
+
 }  // namespace
 
 namespace la3d {
@@ -939,7 +975,7 @@ int instance_fit(FitParams p, const CallFacts& f, hipStream_t s, void* workspace
       snprintf(g_err, sizeof(g_err), "%s: reference-subsample mode needs the bit image in LDS (H*W <= 1048576)", who);
       return LA3D_ERR_UNSUPPORTED;
     }
-    const size_t blocks = (size_t)((p.nwords + 31) / 32) * 4 + 16;   // one prefix word per 32-word block of the bit image
+    const size_t blocks = (size_t)rank_prefix_bytes(p.nwords);   // one prefix word per 32-word block of the bit image
     lds += blocks > poly_stage ? blocks : poly_stage;
     if (lds > 160 * 1024 - 256) {
       snprintf(g_err, sizeof(g_err), "%s: reference-subsample mode: frame too large for LDS", who);
@@ -955,15 +991,19 @@ int instance_fit(FitParams p, const CallFacts& f, hipStream_t s, void* workspace
       p.rcp_ntx = 1.0f / (float)p.ntx;
       p.tiles_per_wave = (p.ntx * p.nty + NWAVE - 1) / NWAVE;
       const size_t fixed = lds - (blocks > poly_stage ? blocks : poly_stage);
-      size_t budget = (160 * 1024 / 4) & ~(size_t)15;          // four workgroups per CU if the frame allows
-      while (budget < fixed + (blocks > 128 ? blocks : 128)) budget += 8 * 1024;
-      long cap = (long)(budget - fixed) / 2;
-      if (cap > (long)p.ntx * p.nty) cap = (long)p.ntx * p.nty;
+      int budget = 0;                                          // four workgroups per CU if the frame allows (tiled_list_cap)
+      const long cap = tiled_list_cap<true>(p.mask_lds_bytes, p.nwords, p.ntx * p.nty, &budget);
       if (cap >= 64 && budget <= 160 * 1024 - 256) {
         p.list_cap = (int)cap;
         const size_t tail = (size_t)cap * 2 > blocks ? (size_t)cap * 2 : blocks;
+        if (f.frames) return launch_fit_frames<true>(p, fixed + (tail > poly_stage ? tail : poly_stage), s, nullptr);
         return launch_fit<true, true, true, true>(p, fixed + (tail > poly_stage ? tail : poly_stage), s);
       }
+    }
+    if (f.frames) {
+      snprintf(g_err, sizeof(g_err), "%s: reference-subsample mode: bounds outside the tiled form: H <= 2040, W <= 8160, and bit image + rank "
+               "prefix + 64 tile-list entries within one workgroup's LDS (160 KiB)", who);
+      return LA3D_ERR_UNSUPPORTED;
     }
     return vec ? launch_fit<true, true, true>(p, lds, s) : launch_fit<false, true, true>(p, lds, s);
   }
@@ -975,22 +1015,16 @@ int instance_fit(FitParams p, const CallFacts& f, hipStream_t s, void* workspace
   p.tiles_per_wave = (p.ntx * p.nty + NWAVE - 1) / NWAVE;
   if (ldsmask && vec && W % 32 == 0 && p.ntx <= 255 && p.nty <= 255) {
     // LDS per workgroup: the largest number of workgroups per CU (160 KiB LDS) that still leaves room
-    // for a useful list; masks with more active tiles than the cap take the dense walk
+    // for a useful list (tiled_list_cap); masks with more active tiles than the cap take the dense walk
     const size_t fixed = lds;
-    const long ntiles = (long)p.ntx * p.nty;
-    const long want = ntiles < 256 ? ntiles : 256;
-    long cap = 0;
-    for (int wg_per_cu = 4; wg_per_cu >= 1 && cap < want; --wg_per_cu) {
-      const long budget = (160 * 1024 / wg_per_cu) & ~15L;
-      cap = (budget - (long)fixed) / 2;
-    }
-    if (cap > ntiles) cap = ntiles;
+    const long cap = tiled_list_cap<false>(p.mask_lds_bytes, p.nwords, p.ntx * p.nty);
     if (cap >= 64) {
       p.list_cap = (int)cap;
       if (f.method == LA3D_METHOD_CONVEX_HULL) {
         p.geo = static_cast<double*>(f.hull_area);
         return launch_hull<true, false>(p, fixed + ((size_t)cap * 2 > poly_stage ? (size_t)cap * 2 : poly_stage), s);
       }
+      if (f.frames) return launch_fit_frames<false>(p, fixed + ((size_t)cap * 2 > poly_stage ? (size_t)cap * 2 : poly_stage), s, workspace);
       if (mask != nullptr && B > 256) {
         // u8 planes: the resident groups start one group's stream time apart - 256 x H*W bytes at the ~6.4 TB/s a pure reader gets:
         // 12.3 us for 640x480 (the kernel applies it only under the size-ordered launch; LA3D_STAGGER_US overrides, 0 switches it
@@ -1003,6 +1037,11 @@ int instance_fit(FitParams p, const CallFacts& f, hipStream_t s, void* workspace
       }
       return launch_fit<true, true, false, true>(p, fixed + ((size_t)cap * 2 > poly_stage ? (size_t)cap * 2 : poly_stage), s, workspace);
     }
+  }
+  if (f.frames) {
+    snprintf(g_err, sizeof(g_err), "%s: bounds outside the tiled form: H <= 2040, W <= 8160, and bit image + 64 tile-list entries within one "
+             "workgroup's LDS (160 KiB)", who);
+    return LA3D_ERR_UNSUPPORTED;
   }
   if (f.method == LA3D_METHOD_CONVEX_HULL) {
     // full-mask hull on a frame outside the tiled vector path: no per-column structure to take the hull from - every instance is

@@ -42,7 +42,8 @@ import torch
 from ._lib import lib, method_code
 from .batched import _dev, _upload_many, draw_sample_idx
 from .jsonout import SceneRecords, format_scenes
-from .masks import fit_instances_ex, mask_stats_poly, mask_stats_rle, pack_polygons, pack_rle, pad_depth_rows, padded_width
+from .masks import (PackedFrames, fit_instances_ex, fit_instances_frames, frame_table, mask_stats_poly, mask_stats_rle, pack_polygons, pack_rle,
+                    pack_rle_frames, pad_depth_rows, padded_width)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 OUT_NAME = "3dbbox.json"
@@ -177,11 +178,16 @@ class ScenePipeline:
 
     def __init__(self, device=None, batch_images: int = 256, subsample: bool = False, boundary_threshold: int = 10,
                  scale_threshold: int = 100, loader_threads: int = 16, write: bool = True, out_name: str = OUT_NAME, rng=None,
-                 timings: Optional[dict] = None, method: str = "pca"):
+                 timings: Optional[dict] = None, method: str = "pca", mixed_frames: bool = False):
         """``method``: "pca" | "convex_hull" - the reference's ``bbox_method`` (save_3d_with_ground_alignment_bbox); see
-        ``fit_instances`` for what the hull method covers in full-mask mode."""
+        ``fit_instances`` for what the hull method covers in full-mask mode.  ``mixed_frames``: batches hold images of DIFFERENT
+        sizes in arrival order, ``batch_images`` each, and every batch is one frames call per annotation kind
+        (``fit_instances_frames``) instead of one call per frame size ("pca" only).  Off: batches are keyed by frame size."""
         method_code(method)   # (the reference's error for an unknown method, before any device work)
+        if mixed_frames and method != "pca":
+            raise ValueError("mixed_frames fits with method='pca' only (the frames call has no convex-hull form)")
         self.method = method
+        self.mixed_frames = bool(mixed_frames)
         self.dev = _dev(device)
         self.batch_images = int(batch_images)
         self.subsample = bool(subsample)
@@ -203,7 +209,90 @@ class ScenePipeline:
         flat = _pinned_bytes(("depth", parity), P * H * W * 4)
         return flat[:P * H * W * 4].view(torch.float32).view(P, H, W), _pinned_rows(("K", parity), P, (9,), torch.float64)
 
+    def _prepare_mixed(self, scenes: List[dict], parity: int) -> _Prepared:
+        """``_prepare`` for a batch of images of different sizes: the depth planes go into ONE ragged pinned buffer (each at its own
+        pitch, ``pack_frames``), the annotations of all sizes into one group per kind."""
+        P = len(scenes)
+        pr = _Prepared()
+        pr.scenes, pr.H, pr.W = scenes, max(sc["height"] for sc in scenes), max(padded_width(sc["width"]) for sc in scenes)
+        t0 = time.perf_counter()
+        sizes = [(sc["height"], sc["width"]) for sc in scenes]
+        table = frame_table(sizes)
+        total = int(table["depth_offset"][-1]) + int(table["H"][-1]) * int(table["W"][-1])
+        ev = self._busy.get(parity)
+        if ev is not None:
+            ev.synchronize()
+        dpin = _pinned_bytes(("depth", parity), total * 4)[:total * 4].view(torch.float32)
+        kpin = _pinned_rows(("K", parity), P, (9,), torch.float64)
+        dnp, knp = dpin.numpy(), kpin.numpy()
+        nthr = max(1, min(self.pool._max_workers, P))
+        cuts = [P * t // nthr for t in range(nthr + 1)]
+
+        def load_range(t):
+            for i in range(cuts[t], cuts[t + 1]):
+                o, h, wp, w = int(table["depth_offset"][i]), int(table["H"][i]), int(table["W"][i]), int(table["frame_width"][i])
+                plane = dnp[o:o + h * wp].reshape(h, wp)
+                _load_scene(scenes[i], plane[:, :w], knp[i])
+                plane[:, w:] = 0.0
+        loads = [self.pool.submit(load_range, t) for t in range(nthr)]
+        tp0 = time.perf_counter()
+        groups = {"rle": {"seg": [], "img": [], "ann": [], "area": [], "cat": []}, "poly": {"seg": [], "img": [], "ann": [], "area": [], "cat": []}}
+        for p, sc in enumerate(scenes):
+            for j, a in enumerate(sc["annotations"]):
+                if a.get("iscrowd") or "segmentation" not in a:
+                    continue
+                seg = a["segmentation"]
+                kind = "rle" if isinstance(seg, dict) and "counts" in seg else "poly"
+                g = groups[kind]
+                g["seg"].append({"size": seg["size"], "counts": seg["counts"]} if kind == "rle" else seg)
+                g["img"].append(p); g["ann"].append(j); g["area"].append(a.get("area")); g["cat"].append(int(a["category_id"]))
+        pr.grounds = [(_ground_files(sc["dir"]) if "dir" in sc else {}) if "ground" not in sc else sc["ground"] for sc in scenes]
+        packed = {}
+        for kind, g in groups.items():
+            if not g["seg"]:
+                continue
+            hint = None if any(v is None for v in g["area"]) else np.clip(np.asarray(g["area"], dtype=np.float64), 0, 2**31 - 1).astype(np.int32)
+            if kind == "rle":
+                counts, offsets, rsz = pack_rle_frames(g["seg"])
+                want = np.asarray(sizes, np.int64)[np.asarray(g["img"], np.int64)]
+                if (rsz != want).any():
+                    n = int(np.flatnonzero((rsz != want).any(1))[0])
+                    raise ValueError(f"RLE size {tuple(rsz[n])} does not match the image size {tuple(want[n])}")
+                arrays = [(counts, torch.int32), (offsets, torch.int64)]
+            else:
+                xy, ro, ir, _, _ = pack_polygons(g["seg"], pr.H, pr.W)
+                arrays = [(xy, torch.int32), (ro, torch.int64), (ir, torch.int64)]
+            arrays += [(np.asarray(g["img"], np.int32), torch.int32), (hint, torch.int32)]
+            packed[kind] = (arrays, g)
+        pr.t_pack = time.perf_counter() - tp0
+        for f in loads:
+            f.result()
+        pr.t_load = time.perf_counter() - t0
+        pr.nbytes = total * 4
+        with torch.cuda.stream(self.copy_stream):
+            pr.h2d0 = torch.cuda.Event(enable_timing=True)
+            pr.h2d0.record(self.copy_stream)
+            depth = torch.empty((total,), dtype=torch.float32, device=self.dev)
+            depth.copy_(dpin, non_blocking=True)
+            words = torch.as_tensor(np.ascontiguousarray(table).view(np.int32).reshape(P, 6).copy(), device=self.dev)
+            pr.depth = PackedFrames(depth, words, table, pr.H, pr.W, sizes)
+            pr.K = torch.empty((P, 9), dtype=torch.float64, device=self.dev)
+            pr.K.copy_(kpin, non_blocking=True)
+            pr.groups = {}
+            for kind, (arrays, g) in packed.items():
+                up = _upload_many(arrays, self.dev, pinned=_pinned_rows(("small", kind, parity), sum((np.asarray(a).nbytes + 15) & ~15 for a, _ in arrays if a is not None) or 16,
+                                                                     (), torch.uint8))
+                pr.nbytes += sum(int(np.asarray(a).nbytes) for a, _ in arrays if a is not None)
+                pr.groups[kind] = (up, g)
+            pr.ready = torch.cuda.Event(enable_timing=True)
+            pr.ready.record(self.copy_stream)
+        self._busy[parity] = pr.ready
+        pr.parity = parity
+        return pr
+
     def _prepare(self, scenes: List[dict], parity: int) -> _Prepared:
+        if self.mixed_frames:
+            return self._prepare_mixed(scenes, parity)
         H, W = scenes[0]["height"], scenes[0]["width"]
         P = len(scenes)
         pr = _Prepared()
@@ -308,7 +397,7 @@ class ScenePipeline:
         H, W, P = pr.H, pr.W, len(pr.scenes)
         cur = torch.cuda.current_stream(self.dev)
         cur.wait_event(pr.ready)
-        for t in (pr.depth, pr.K):
+        for t in ((pr.depth.depth, pr.depth.table, pr.K) if self.mixed_frames else (pr.depth, pr.K)):
             t.record_stream(cur)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(cur)
@@ -321,7 +410,13 @@ class ScenePipeline:
                     t.record_stream(cur)
             masks_kw = dict(rles=(up[0], up[1], H, W)) if kind == "rle" else dict(polys=(up[0], up[1], up[2], H, W))
             ii, hint = up[-2], up[-1]
-            if not two_phase:
+            if self.mixed_frames:
+                # one frames call per annotation kind for the whole batch, whatever its sizes; two-phase: the first call is the
+                # keep rule's statistics pass (the fused filter writes them), the second fits with ground rows / drawn indices
+                res = fit_instances_frames(pr.depth, K, image_index=ii, filter=self.flt, area_hint=hint,
+                                           _fitter=self._fitter(kind, pr.parity, len(g["seg"]), H, W), **masks_kw)
+                results[kind] = (res["boxes"], res["status"], g) if not two_phase else (res["stats"], None, g, masks_kw, ii, hint)
+            elif not two_phase:
                 res = fit_instances_ex(pr.depth, K, image_index=ii, filter=self.flt, area_hint=hint, device=self.dev, frame_width=W,
                                        _fitter=self._fitter(kind, pr.parity, len(g["seg"]), H, padded_width(W)), method=self.method,
                                        **masks_kw)
@@ -345,12 +440,16 @@ class ScenePipeline:
 
     def _second_phase(self, pr, results, K):
         H = pr.H
+        if self.mixed_frames:   # the keep rule takes the height of the instance's own image
+            heights = np.asarray([sc["height"] for sc in pr.scenes], np.int64)
         kept_rows = []   # (image, annotation index, kind, row in its group)
         host_stats = {}
         for kind, (stats, _, g, masks_kw, ii, hint) in results.items():
             st = stats.cpu().numpy()
             host_stats[kind] = st
             height = st[:, 1] if kind == "rle" else st[:, 2]
+            if self.mixed_frames:
+                H = heights[np.asarray(g["img"], np.int64)]
             keep = (16 * height > H) & (st[:, 3] < 10) & (st[:, 0] >= self.flt["scale_threshold"])   # src/util.py:375; analyze_mask :326
             for r in np.nonzero(keep)[0]:
                 kept_rows.append((g["img"][r], g["ann"][r], kind, int(r)))
@@ -380,6 +479,10 @@ class ScenePipeline:
                     if kd == kind:
                         si[r] = draws[n]
             gr = ground[kind] if np.isfinite(ground[kind][:, 0]).any() else None
+            if self.mixed_frames:
+                res = fit_instances_frames(pr.depth, K, image_index=ii, filter=self.flt, area_hint=hint, ground=gr, sample_idx=si, **masks_kw)
+                out[kind] = (res["boxes"], res["status"], g)
+                continue
             res = fit_instances_ex(pr.depth, K, image_index=ii, filter=self.flt, area_hint=hint, ground=gr, sample_idx=si, device=self.dev,
                                    frame_width=pr.W, method=self.method, **masks_kw)
             out[kind] = (res["boxes"], res["status"], g)
@@ -432,6 +535,16 @@ class ScenePipeline:
                 f.write(recs.text)
 
     def _batches(self, scenes: Iterable[dict]) -> Iterator[List[dict]]:
+        if self.mixed_frames:   # arrival order, whatever the sizes
+            batch: list = []
+            for sc in scenes:
+                batch.append(sc)
+                if len(batch) >= self.batch_images:
+                    yield batch
+                    batch = []
+            if batch:
+                yield batch
+            return
         pending: Dict[tuple, list] = {}
         for sc in scenes:
             key = (sc["height"], sc["width"])
@@ -579,6 +692,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--file-categories", action="store_true", help="category names from the annotation file's own `categories` block "
                                                                    "(default: the reference's built-in COCO / COCONut table, src/util.py:419-462)")
     ap.add_argument("--make-synthetic", type=int, default=0, metavar="N", help="first write a synthetic tree of N scenes into --scenes")
+    ap.add_argument("--mixed-frames", action="store_true", help="batch images of different sizes together, in arrival order: one frames "
+                    "call per annotation kind and batch instead of one call per frame size (pca only)")
     ap.add_argument("--bbox-method", choices=("pca", "convex_hull"), default="pca",
                     help="yaw estimator (the reference's bbox_method): principal axis, or the minimum-area rectangle over the hull edges")
     return ap
@@ -594,7 +709,7 @@ def main(argv=None) -> int:
     torch.cuda.set_device(args.gpu_idx)
     timings: dict = {}
     pipe = ScenePipeline(device=torch.device("cuda", args.gpu_idx), batch_images=args.batch_images, subsample=args.subsample, timings=timings,
-                         method=args.bbox_method)
+                         method=args.bbox_method, mixed_frames=args.mixed_frames)
     t0 = time.perf_counter()
     n_scenes = n_boxes = 0
     for sc, recs in pipe.run(scenes_from_disk(args.scenes, ann, args.start_index, args.end_index, args.skip_done,

@@ -773,6 +773,182 @@ def fit_instances_bits(depth, bits, K, ground=None, sample_idx=None, image_index
     return res
 
 
+FRAME_DTYPE = np.dtype([("depth_offset", "<i8"), ("H", "<i4"), ("W", "<i4"), ("frame_width", "<i4"), ("reserved", "<i4")])
+"""One row of the frame table of a frames call: ``la3d_frame`` of include/la3d.h (24 bytes)."""
+
+
+class PackedFrames(NamedTuple):
+    """Depth maps of different sizes in one buffer (``pack_frames``; C-ABI ``la3d_fit_instances_frames``): ``depth`` flat float32 -
+    plane p starts ``table_host["depth_offset"][p]`` floats in (a multiple of 4: 16-byte aligned), its rows ``padded_width(W_p)``
+    floats apart, the columns past ``W_p`` zero -; ``table`` int32 (P, 6) on the same device: the ``la3d_frame`` rows as the kernel
+    reads them; ``table_host``: the same rows as a NumPy array of ``FRAME_DTYPE``; ``H``, ``W``: the bounds of the call (largest
+    rows, largest pitch); ``sizes``: the (H, W) of every image, unpadded."""
+    depth: torch.Tensor
+    table: torch.Tensor
+    table_host: np.ndarray
+    H: int
+    W: int
+    sizes: list
+
+
+def frame_table(sizes) -> np.ndarray:
+    """The frame table (``FRAME_DTYPE``) of images of the given unpadded (H, W) sizes packed back to back: pitch =
+    ``padded_width(W)``, planes 16-byte aligned (every pitch is a multiple of 32 floats, so they follow each other directly)."""
+    t = np.zeros(len(sizes), FRAME_DTYPE)
+    off = 0
+    for p, (h, w) in enumerate(sizes):
+        h, w = int(h), int(w)
+        if h <= 0 or w <= 0:
+            raise ValueError(f"depth map {p} has an empty frame {(h, w)}")
+        t[p] = (off, h, padded_width(w), w, 0)
+        off += h * padded_width(w)
+    return t
+
+
+def pack_frames(depth_maps, device=None, pinned=None) -> PackedFrames:
+    """Depth maps of DIFFERENT sizes -> ``PackedFrames``: one flat float32 buffer on the device, each plane at its own pitch
+    (``padded_width``) and 16-byte aligned offset, the padding zero, plus the device frame table ``fit_instances_frames`` takes.
+    ``depth_maps``: a sequence of (H_p, W_p) arrays / tensors.  ``pinned``: a pinned float32 staging tensor of at least the packed size
+    (host maps only) - the upload is then asynchronous on the current stream and the caller keeps the buffer untouched until that
+    stream has passed it.  ``device="cpu"`` gives the layout on the host (no GPU needed)."""
+    dev = torch.device(device) if device is not None and torch.device(device).type == "cpu" else _dev(device)
+    maps = list(depth_maps)
+    for p, m in enumerate(maps):
+        if len(m.shape) != 2:
+            raise ValueError(f"depth map {p} must be (H, W), got {tuple(m.shape)}")
+    sizes = [(int(m.shape[0]), int(m.shape[1])) for m in maps]
+    table = frame_table(sizes)
+    total = int(sum(int(r["H"]) * int(r["W"]) for r in table))
+    if any(isinstance(m, torch.Tensor) and m.is_cuda for m in maps):
+        flat = torch.zeros(max(total, 4), dtype=torch.float32, device=dev)
+        for m, r in zip(maps, table):
+            o, h, wp, w = int(r["depth_offset"]), int(r["H"]), int(r["W"]), int(r["frame_width"])
+            flat[o:o + h * wp].view(h, wp)[:, :w].copy_(torch.as_tensor(m).to(device=dev, dtype=torch.float32))
+    else:
+        if pinned is not None and pinned.dtype == torch.float32 and pinned.numel() >= max(total, 4):
+            host_t = pinned[:max(total, 4)]
+        else:
+            pinned, host_t = None, torch.empty(max(total, 4), dtype=torch.float32)
+        host = host_t.numpy()
+        for m, r in zip(maps, table):
+            o, h, wp, w = int(r["depth_offset"]), int(r["H"]), int(r["W"]), int(r["frame_width"])
+            dst = host[o:o + h * wp].reshape(h, wp)
+            dst[:, :w] = m.numpy() if isinstance(m, torch.Tensor) else np.asarray(m)
+            dst[:, w:] = 0.0
+        host[total:] = 0.0
+        flat = host_t if dev.type == "cpu" else host_t.to(dev, non_blocking=pinned is not None)
+    words = np.ascontiguousarray(table).view(np.int32).reshape(len(maps), 6) if len(maps) else np.zeros((0, 6), np.int32)
+    tab = torch.as_tensor(words.copy(), device=dev)
+    return PackedFrames(flat, tab, table, max((h for h, _ in sizes), default=0), max((int(r["W"]) for r in table), default=0), sizes)
+
+
+def pack_rle_frames(rles):
+    """Run-length masks of images of different sizes -> ``(counts int32 (T,), offsets int64 (B+1,), sizes int64 (B, 2))``: ``pack_rle``
+    without its one-size rule; ``sizes[n]`` = the (h, w) the annotation states, or -1 where the input does not say."""
+    if isinstance(rles, tuple):
+        counts, offsets = rles[0], rles[1]
+        return counts, offsets, None
+    parts = [rle_from_string(r["counts"]) if isinstance(r["counts"], (str, bytes)) else np.asarray(r["counts"], dtype=np.int32) for r in rles]
+    offsets = np.zeros(len(parts) + 1, np.int64)
+    np.cumsum([len(p) for p in parts], out=offsets[1:])
+    counts = np.concatenate(parts).astype(np.int32) if parts and offsets[-1] else np.zeros(1, np.int32)
+    sizes = np.asarray([tuple(r["size"]) for r in rles], np.int64).reshape(-1, 2)
+    return counts, offsets, sizes
+
+
+def fit_instances_frames(frames, K, rles=None, polys=None, image_index=None, ground=None, sample_idx=None, filter=None, proj: bool = False,
+                         area_hint=None, stream=None, method: str = "pca", _fitter=None):
+    """The fit for instances of images of DIFFERENT sizes in one call (C-ABI ``la3d_fit_instances_frames``): ``frames`` is what
+    ``pack_frames`` returns; instance n belongs to image ``image_index[n]`` (required), whose K is ``K[image_index[n]]`` (K: (P,3,3),
+    or (3,3) shared).  Exactly one of ``rles`` - a list of COCO RLE objects, each of its own image's size, or a ``(counts, offsets)``
+    tuple - and ``polys`` - the tuple of ``pack_polygons`` (its H, W are ignored: every instance is clipped to its own frame) - gives
+    the masks.  ``ground`` / ``sample_idx`` / ``filter`` / ``area_hint`` as in ``fit_instances_ex``; ``proj=True`` adds ``boxes2d``,
+    clamped to each instance's own frame.  An instance whose image index or frame row breaks the contract of ``la3d_frame`` comes
+    back with status 5 and a NaN record - decided on the device, never an exception.  ``method="convex_hull"`` is not offered in
+    this form (ValueError).  Returns the dict of ``fit_instances_ex``.  The size-balanced launch order of large batches runs when
+    ``area_hint`` is given."""
+    if _lib.method_code(method) != _lib.METHOD_PCA:   # (the reference's error for an unknown method; before any device work)
+        raise ValueError("fit_instances_frames: method='convex_hull' is not supported for frames of different sizes; group by size and use fit_instances_ex")
+    if not isinstance(frames, PackedFrames):
+        raise ValueError("frames must be the PackedFrames of pack_frames")
+    if (rles is not None) + (polys is not None) != 1:
+        raise ValueError("give exactly one of rles / polys")
+    if image_index is None:
+        raise ValueError("image_index is required: instance n belongs to frame image_index[n]")
+    if not frames.depth.is_cuda:
+        raise ValueError("frames must live on the GPU (pack_frames with a GPU device)")
+    dev = frames.depth.device
+    P = int(frames.table.shape[0])
+    if rles is not None:
+        counts, offsets, sizes = pack_rle_frames(rles)
+        if sizes is not None and not (isinstance(image_index, torch.Tensor) and image_index.is_cuda):
+            ii_h = np.asarray(image_index.numpy() if isinstance(image_index, torch.Tensor) else image_index).reshape(-1)
+            ok = (ii_h >= 0) & (ii_h < P)
+            if len(ii_h) == len(sizes) and ok.any():
+                want = np.asarray(frames.sizes, np.int64).reshape(-1, 2)[ii_h[ok]]
+                if (sizes[ok] != want).any():
+                    raise ValueError("an RLE annotation's size differs from the size of its image")
+        counts, offsets, ground, image_index, sample_idx, area_hint = _bulk(
+            dev, (counts, torch.int32), (offsets, torch.int64), (ground, torch.float64), (image_index, torch.int32), (sample_idx, torch.int32),
+            (area_hint, torch.int32))
+        c, o = _as_dev(counts, torch.int32, dev), _as_dev(offsets, torch.int64, dev)
+        B = o.numel() - 1
+        kind, keep = dict(rle=(_ptr(c), _ptr(o))), [c, o]
+    else:
+        pxy, pro, pir = polys[0], polys[1], polys[2]
+        pxy, pro, pir, ground, image_index, sample_idx, area_hint = _bulk(
+            dev, (pxy, torch.int32), (pro, torch.int64), (pir, torch.int64), (ground, torch.float64), (image_index, torch.int32),
+            (sample_idx, torch.int32), (area_hint, torch.int32))
+        xy, ro, ir = _as_dev(pxy, torch.int32, dev), _as_dev(pro, torch.int64, dev), _as_dev(pir, torch.int64, dev)
+        B = ir.numel() - 1
+        kind, keep = dict(poly=(_ptr(xy), _ptr(ro), _ptr(ir))), [xy, ro, ir]
+    k = _as_dev(K, torch.float64, dev, cache=True)
+    if k.dim() == 2:
+        k = k[None]
+    if k.shape[0] not in (1, P) or k.shape[1:] != (3, 3):
+        raise ValueError("K must be (3,3) or (P,3,3)")
+    ii = _as_dev(image_index, torch.int32, dev)
+    if ii.shape != (B,):
+        raise ValueError("image_index must be (B,)")
+    g = None
+    if ground is not None:
+        g = _as_dev(ground, torch.float64, dev)
+        if g.shape != (B, 4):
+            raise ValueError("ground must be (B,4)")
+    si = None
+    if sample_idx is not None:
+        si = _as_dev(sample_idx, torch.int32, dev)
+        if si.shape != (B, _lib.NSAMPLE):
+            raise ValueError("sample_idx must be (B,500)")
+    H, W = max(int(frames.H), 1), max(int(frames.W), 1)
+    out = {}
+    with torch.cuda.device(dev):
+        # (_fitter: buffers a caller keeps between calls - fit_scenes -, sized for at least this call's B and bounds)
+        f = _fitter if _fitter is not None else InstanceFitter(B, H, W, dev)
+        if f.B < B or f.H < H or f.W < W:
+            raise ValueError("_fitter too small for this call")
+        out.update(boxes=f.boxes[0][:B], status=f.status[0][:B], aux=f.aux[0][:B])
+        if filter:
+            out["stats"] = torch.zeros((B, 4), dtype=torch.int32, device=dev)
+        if proj:
+            out["boxes2d"] = torch.full((B, 8), float("nan"), dtype=torch.float64, device=dev)
+        if B == 0:
+            return out
+        ah = None
+        if area_hint is not None:
+            ah = _as_dev(area_hint, torch.int32, dev).reshape(-1)
+            if ah.numel() != B:
+                raise ValueError("area_hint must have one entry per instance")
+            keep.append(ah)
+        a = _fit_args(B, H, W, _ptr(frames.depth), 1, _ptr(k), k.shape[0], _ptr(f.boxes[0]), _ptr(f.status[0]), _ptr(f.aux[0]),
+                      _ptr(f.workspace[0]), _stream(stream), image_index=_ptr(ii), ground=_ptr(g), sample_idx=_ptr(si), filter=filter,
+                      stats=_ptr(out.get("stats")), proj=_ptr(out.get("boxes2d")), image_size=(1, 1) if proj else None,
+                      area_hint=_ptr(ah), opts=options.codes(), **kind)
+        check(lib.la3d_fit_instances_frames(C.byref(a), _ptr(frames.table), P), "la3d_fit_instances_frames")
+    _record(stream, frames.depth, frames.table, k, ii, g, si, *keep, f.workspace, *out.values())
+    return out
+
+
 def masked_ratio_median(depth_map, depth_render, mask, render_mask=None, image_index=None, stream=None):
     """Per instance ``np.median(depth_map[overlap] / depth_render[overlap])`` with ``overlap = mask & render_mask``
     — the scale estimate of the reference's align_to_depth_match (src/util.py:476-486), exact (radix select on
