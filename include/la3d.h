@@ -284,9 +284,26 @@ int la3d_fit_instances_ex(const la3d_fit_args* args);
  *    the instance's tile list).  All points of pixel column u lie on one ray through the origin of the x/z plane, so only the
  *    nearest and the farthest valid depth of a column can be hull vertices: the hull of the whole mask is the hull of at most
  *    2 x (occupied columns) points.  NaN and infinite depths under the mask are dropped (as the reference and the PCA call
- *    drop them), negative depths are fitted.  Every other instance - a finite ground row, a skewed K, a mask with too many
- *    active tiles, more than 1024 occupied columns - gets LA3D_BOX_UNSUPPORTED and a NaN record, never a PCA box; a call on a
- *    frame outside the tiled path gets it for every instance.  Use reference-subsample mode there.
+ *    drop them), negative depths are fitted.  Every other instance gets LA3D_BOX_UNSUPPORTED and a NaN record (NaN proj), never a
+ *    PCA box.  The rule, in the order it is applied:
+ *      1. the frame (the whole call): outside the tiled path - W % 32 != 0, H*W % 16 != 0, planes not 16-byte aligned, fewer than
+ *         64 tiles of 32 x 8 pixels (W/32 * ceil(H/8)) - every instance is refused;
+ *      2. the instance: a finite ground row (degenerate or not), a skewed K (K[0][1] != 0), or more ACTIVE TILES (tiles of 32 x 8
+ *         pixels holding a mask pixel) than the frame has room for.  Room = the largest n with n x 32 B + 8 W bytes within the
+ *         bit image's H W / 8 bytes (the column arrays behind the compacted tiles), n x 40 B + 384 B within them (the tiles with
+ *         their range words), and n within the tile list the launch reserves.  The list has 2-byte entries and lies behind the bit
+ *         image and 752 B of fixed state in a workgroup's share of the 160 KiB of LDS of a CU: (160 KiB / g rounded down to 16 B
+ *         - bit image - 752 B) / 2 entries for the first g of 4, 3, 2, 1 workgroups per CU that gives min(256, tiles of the
+ *         frame) of them, never more than the frame has tiles.  So: 28 of the 84 tiles of a 224 x 96 frame, 220 of the 300 of
+ *         320 x 240, 904 of the 1200 of 640 x 480 (the list of four workgroups per CU; the column arrays alone would allow
+ *         1040), none on 256 x 64.  These come BEFORE the reference's own rejections: an empty mask, a mask without a valid depth or
+ *         a degenerate ground row gets status 5 here, not 1 / 2, when it is refused for one of them;
+ *      3. the candidates: a column whose nearest and farthest valid depth are the same float gives ONE candidate, every other
+ *         occupied column two (-0 and +0 are two floats); more than 2048 candidates are refused.  Frames up to 1024 columns
+ *         never get there; on a wider frame a one-row mask over 1056 columns is fitted (1056 candidates), a two-row mask over
+ *         1025 columns of differing depths is refused (2050).
+ *    aux of a refused instance: yaw and aux[3] NaN; n_valid 0 and n_in NaN where rule 1 / 2 refused (before the mask was counted),
+ *    both exact where rule 3 did.  Use reference-subsample mode for what full-mask mode refuses.
  *  - the hull call runs on the instance engine, two launches on the caller's stream (fit -> hand-off through the workspace ->
  *    hull finish), capturable into a HIP graph.  opt_engine pins give way; opt_build values / process defaults that switch the
  *    single pass off (LA3D_BUILD_PLAIN, LA3D_BUILD_NOCULL) are speed options and are IGNORED by hull calls: they never turn a

@@ -609,6 +609,10 @@ struct alignas(16) Shared {
   double* tl;      // measurement build: this workgroup's stamp row (profiles/timeline.py)
 #endif
 };
+#ifndef LA3D_TIMELINE
+// include/la3d.h states the tile list of a hull call in bytes (752 behind the bit image); oracle/campaigns/hull.py restates it
+static_assert(sizeof(Shared) == 752, "include/la3d.h (convex-hull yaw, rule 2) and oracle/campaigns/hull.py state this size");
+#endif
 #ifdef LA3D_TIMELINE
 #define LA3D_SUBSTAMP(sh, k) do { if (threadIdx.x == 0 && (sh)->tl) (sh)->tl[k] = (double)wall_clock64(); } while (0)
 #else

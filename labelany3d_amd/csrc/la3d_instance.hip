@@ -807,7 +807,7 @@ __global__ __launch_bounds__(NTP) void hull_finish_kernel(const FitParams p, uns
   const int n = sh.fill;
   double* out = p.out + (long long)inst * LA3D_REC;
   double* aux = p.aux ? p.aux + (long long)inst * LA3D_AUX : nullptr;
-  if (n > HCAP) {   // uniform: more than HCAP / 2 occupied columns - refused, never fitted as PCA
+  if (n > HCAP) {   // uniform: more than HCAP candidates (one per column whose two ends coincide, two otherwise) - refused, never fitted as PCA
     if (tid == 0) {
       if (aux) { aux[0] = NAN; aux[1] = hh[HH_NVALID]; aux[2] = hh[HH_NM]; aux[3] = NAN; }
       p.status[inst] = LA3D_BOX_UNSUPPORTED;

@@ -236,6 +236,33 @@ def yaw_convex_hull(rotated_pc):
     return best_yaw
 
 
+def hull_edge_table(rotated_pc, chunk=1 << 22):
+    """(yaws, areas) of EVERY hull edge, in the order and with the arithmetic of yaw_convex_hull's walk (which returns the yaw of
+    the first strict minimum of `areas`); None where yaw_convex_hull falls back to PCA (a non-finite coordinate, fewer than 3
+    hull vertices).  For the checkers: which edges tie with the minimum, and what the runner-up is.  The hull comes from
+    _monotone_chain_presorted (the same chain over the same order, pinned in tests/test_oracle_hull_helpers.py); the per-edge
+    products are the element-wise ones of the loop above, several edges at a time."""
+    pts = np.asarray(rotated_pc)[:, [0, 2]]
+    if len(pts) == 0 or not np.isfinite(pts).all():
+        return None
+    hull = _monotone_chain_presorted(pts)
+    if len(hull) < 3:
+        return None
+    hp = pts[hull]
+    e = np.roll(hp, -1, axis=0) - hp
+    yaws = np.arctan2(e[:, 1], e[:, 0])
+    cs, sn = np.cos(yaws), np.sin(yaws)
+    areas = np.empty(len(hp))
+    x, z = pts[:, 0][None, :], pts[:, 1][None, :]
+    step = max(1, chunk // max(len(pts), 1))
+    for i in range(0, len(hp), step):
+        c_, s_ = cs[i:i + step, None], sn[i:i + step, None]
+        rx = c_ * x - s_ * z
+        rz = s_ * x + c_ * z
+        areas[i:i + step] = (rx.max(axis=1) - rx.min(axis=1)) * (rz.max(axis=1) - rz.min(axis=1))
+    return yaws, areas
+
+
 def _monotone_chain(pts):
     idx = sorted(range(len(pts)), key=lambda i: (pts[i, 0], pts[i, 1]))
 
@@ -255,6 +282,31 @@ def _monotone_chain(pts):
     return lower[:-1] + upper[:-1]
 
 
+def _monotone_chain_presorted(pts):
+    """_monotone_chain for large clouds: the same chain over EVERY point in the same order - a stable NumPy sort by (x, z) instead of
+    a Python key function, coordinates as Python floats (IEEE doubles either way: every cross product rounds as above).  No point
+    is left out beforehand."""
+    idx = np.lexsort((pts[:, 1], pts[:, 0])).tolist()
+    xs, zs = pts[:, 0].tolist(), pts[:, 1].tolist()
+
+    def half(order):
+        st = []
+        for i in order:
+            xi, zi = xs[i], zs[i]
+            while len(st) >= 2:
+                o, a = st[-2], st[-1]
+                if (xs[a] - xs[o]) * (zi - zs[o]) - (zs[a] - zs[o]) * (xi - xs[o]) <= 0:
+                    st.pop()
+                else:
+                    break
+            st.append(i)
+        return st
+
+    lower = half(idx)
+    upper = half(reversed(idx))
+    return lower[:-1] + upper[:-1]
+
+
 # --------------------------------------------------------------------------------------
 # A3  estimate_bbox  (src/util_3dbox.py:106-178)
 # --------------------------------------------------------------------------------------
@@ -268,7 +320,7 @@ def ground_rotation(ground_equ):
     return rotation_matrix_from_vectors([0, -1, 0], g[:3])
 
 
-def estimate_bbox(in_pc, cat_name=None, ground_equ=None, method="pca", rand_ind=None, return_aux=False):
+def estimate_bbox(in_pc, cat_name=None, ground_equ=None, method="pca", rand_ind=None, return_aux=False, yaw=None):
     """src/util_3dbox.py:106-178.
 
     ``rand_ind``: the 500 indices the reference would draw at :124; ``None`` draws them
@@ -278,6 +330,8 @@ def estimate_bbox(in_pc, cat_name=None, ground_equ=None, method="pca", rand_ind=
     reference takes when N <= 500, applied to any N).
     Silent: the reference's per-box ``print`` (:162) is a side effect of the scalar shim,
     not of the arithmetic.
+    ``yaw``: not the reference's - a yaw to take instead of the estimator's (:146-151), everything else unchanged: "the box the
+    reference would have written had it picked this hull edge", for the checkers of tied minimum-area edges.
     """
     in_pc = np.asarray(in_pc)
     if rand_ind is not False and in_pc.shape[0] > SUBSAMPLE:
@@ -290,7 +344,9 @@ def estimate_bbox(in_pc, cat_name=None, ground_equ=None, method="pca", rand_ind=
     rotated = rotated[~np.isnan(rotated).any(axis=1)]  # :139-140
     if len(rotated) == 0:
         raise ValueError("No valid points after removing NaN values")  # :143
-    if method == "convex_hull":
+    if yaw is not None:
+        yaw = float(yaw)
+    elif method == "convex_hull":
         yaw = yaw_convex_hull(rotated)
     elif method == "pca":
         yaw = yaw_pca_closed_form(rotated)
@@ -334,11 +390,11 @@ def fit_instance(depth, mask, K, ground=None, rand_ind=False, method="pca", refs
     return fit_points(pts, ground, rand_ind, method)
 
 
-def fit_points(pts, ground=None, rand_ind=False, method="pca"):
+def fit_points(pts, ground=None, rand_ind=False, method="pca", yaw=None):
     rec = np.full(39, np.nan)
     aux = dict(yaw=float("nan"), n_valid=0, n_in=int(len(pts)))
     try:
-        v, c, d, R, a = estimate_bbox(pts, None, ground, method, rand_ind=rand_ind, return_aux=True)
+        v, c, d, R, a = estimate_bbox(pts, None, ground, method, rand_ind=rand_ind, return_aux=True, yaw=yaw)
     except ValueError as e:
         msg = str(e)
         if "No valid points" in msg:

@@ -1,14 +1,18 @@
 """The committed slices of the differential campaigns that tests/test_gpu_differential.py runs on every GPU test run.
 
 The seeds were picked once, by scanning the campaigns' make_case on the CPU for what the slice must cover (tests/test_differential_
-checkers.py::test_slices_cover asserts it), and all lie in the seed ranges of the committed round-6 records: a failure on one of them
-is a regression since then.
+checkers.py::test_slices_cover asserts it), and - HULL_SEEDS excepted, see there - all lie in the seed ranges of the committed round-6 records: a
+failure on one of them is a regression since then.
   ENGINE_SEEDS        profiles/r06/fuzz_engines_s10000.txt (seeds 10000 ... 13999; five polygon cases added for the fused filter
                       on polygons, whose thresholds drop most instances of the others)
   ENGINE_TINY_SEEDS   profiles/r06/fuzz_engines_tiny.txt (seeds 20000 ... 21499, make_case(seed, tiny=True))
   POINT_SEEDS         profiles/r06/fuzz_points.txt (0 ... 2999)
   ANNOTATION_SEEDS    profiles/r06/fuzz_annotations.txt (0 ... 3999)
-  AUX_SEEDS           profiles/r06/fuzz_aux.txt (0 ... 1999)"""
+  AUX_SEEDS           profiles/r06/fuzz_aux.txt (0 ... 1999)
+  HULL_SEEDS          NO campaign record yet (oracle/campaigns/hull.py: the convex-hull yaw of the depth + mask fit): picked by the
+                      CPU scan of seeds 70000 ... 70499 alone.  The slice itself has passed on an MI355X; the range as a whole has
+                      not run, so a failure on another seed of it need not be a regression.  profiles/hull/fuzz_hull.py writes the
+                      record (profiles/hull/fuzz_hull.txt) - commit it with the first run of the range"""
 
 ENGINE_SEEDS = [
     10018, 10023, 10025, 10032, 10034, 10046, 10050, 10051, 10056, 10058,
@@ -32,3 +36,14 @@ KAPPA_SEEDS = [10023, 10571]
 POINT_SEEDS = list(range(40))
 ANNOTATION_SEEDS = list(range(40))
 AUX_SEEDS = list(range(36)) + [41, 43, 45, 48]   # (41 / 48: one-row frames, 43 / 45: one-column frames)
+
+# the convex-hull campaign (oracle/campaigns/hull.py): every frame class, every refusal reason of full-mask mode, candidate counts of
+# 2047 ... 2050, active-tile counts of room - 1 / room / room + 1 on every tiled frame, B = 161 / 300
+HULL_SEEDS = [
+    70007, 70011, 70015, 70018, 70037, 70038, 70043, 70080, 70101, 70103,
+    70106, 70110, 70112, 70125, 70132, 70134, 70143, 70145, 70161, 70169,
+    70173, 70179, 70194, 70195, 70199, 70202, 70207, 70208, 70209, 70213,
+    70218, 70225, 70235, 70237, 70244, 70246, 70262, 70268, 70279, 70285,
+    70329, 70350, 70354, 70368, 70380, 70386, 70404, 70405, 70411, 70432,
+    70450, 70452, 70455, 70456, 70469, 70470, 70475, 70483, 70487, 70493,
+]

@@ -9,6 +9,7 @@ from oracle import la3d_oracle as O
 from oracle.campaigns import annotations as A
 from oracle.campaigns import aux as X
 from oracle.campaigns import engines as E
+from oracle.campaigns import hull as HU
 from oracle.campaigns import points as PT
 from tests import campaign_slices as S
 
@@ -69,6 +70,115 @@ def test_slices_cover():
     aux = [X.make_case(s) for s in S.AUX_SEEDS]
     assert any(c["poly"] is not None for c in aux) and any(c["depth_stats"] is not None for c in aux) and any(c["H"] == 1 for c in aux) \
         and any(c["W"] == 1 for c in aux)
+
+
+def test_hull_slice_covers():
+    """The convex-hull slice, from generator and oracle alone: every frame class, every refusal reason, both sides of the candidate
+    and of the active-tile boundary, enough fitted instances in either mode and - a condition on the INPUTS, not a tolerance: a slice
+    that misses it gets other seeds - at least 70 % of the hull-decided instances sharply decided (the reference alone: 79 % of the
+    campaign's masks; the rest are parallel / perpendicular twins within 1e-9 of the minimum area)."""
+    assert 55 <= len(S.HULL_SEEDS) <= 70 and all(70000 <= s < 70500 for s in S.HULL_SEEDS)
+    cases = [HU.make_case(s) for s in S.HULL_SEEDS]
+    refs = [HU.oracle_case(s) for s in S.HULL_SEEDS]
+    full = [c for c in cases if c["full"]]
+    samp = [c for c in cases if not c["full"]]
+    frames = {(c["H"], c["W"]) for c in full}
+    assert set(HU.TILED) | {HU.BIG, HU.ZERO_ROOM, HU.WIDE, HU.SMALL_OFF} <= frames and any(c["H"] < 10 for c in full)
+    assert any(c["B"] <= 3 for c in full if (c["H"], c["W"]) == HU.BIG)
+    sframes = {(c["H"], c["W"]) for c in samp}
+    assert {HU.BIG, HU.ZERO_ROOM, HU.WIDE, HU.ODD_OFF, HU.SMALL_OFF, (96, 224), (240, 320), (100, 214)} <= sframes and any(c["H"] < 10 for c in samp)
+    assert {c["B"] for c in cases} >= set(HU.BS) | {161, 300}
+    for group in (full, samp):
+        assert any(c["segs"] is not None for c in group) and any(c["skew"] for c in group)
+        assert {"none", "some", "all"} == {"none" if c["ground"] is None else ("some" if np.isnan(c["ground"][:, 0]).any() else "all") for c in group}
+        assert {"indexed", "shared", "private"} == {"indexed" if c["image_index"] is not None else ("shared" if c["P"] == 1 else "private") for c in group}
+        assert any(_degenerate_ground(c["ground"]) for c in group)
+    assert any(5 in c["dkind"] for c in full) and any(5 in c["dkind"] for c in samp)   # constant planes with zero / negative depths
+    # every refusal reason; the candidate count on both sides of the hold, the active tiles on both sides of the room, per frame
+    why, cands, tiles, early = set(), set(), set(), []
+    redo = 0
+    for c, ref in zip(full, [r for c, r in zip(cases, refs) if c["full"]]):
+        Wp = HU.padded_width(c["W"])
+        for n in range(c["B"]):
+            ok, reason = HU.covered(c, n)
+            why.add(reason)
+            if reason in ("ground", "skew", "tiles"):                                # what the reference would have said of this instance
+                g = c["ground"][n] if c["ground"] is not None and not np.isnan(c["ground"][n, 0]) else None
+                early.append((reason, int(c["masks"][n].sum()), _degenerate_ground(None if g is None else g[None])))
+            if reason in (None, "candidates"):
+                cands.add(HU.candidate_count(c["masks"][n], c["depth"][HU.plane_of(c, n)]))
+            if reason in (None, "tiles", "candidates") and c["fclass"] in ("tiled", "big"):
+                tiles.add((c["H"], c["W"], HU.active_tiles(c["masks"][n]) - HU.tile_room(c["H"], Wp)))
+            redo += bool(ok and ref.st[n] == 0 and ref.kap[n] > 2.0 ** 17)
+        assert any(HU.applies(c, r) for r in HU.RUNS)
+    assert why == set(HU.REASONS) | {None}
+    assert {2047, 2048, 2049, 2050} <= cands
+    for H, W in HU.TILED + [HU.BIG]:
+        assert {(H, W, -1), (H, W, 0), (H, W, 1)} <= tiles, (H, W)
+    # status 5 by ground row, skew or tiles comes before the reference's own statuses 1 / 2: empty masks, one-pixel masks and
+    # degenerate ground rows among the instances refused for them
+    assert {("ground", 0), ("skew", 0), ("ground", 1), ("tiles", 1)} <= {(reason, npx) for reason, npx, _ in early}
+    assert sum(deg for _, _, deg in early) >= 5
+    assert redo >= 3                                                                 # the second moments pass about the pivot
+    # single columns and clouds of one to three points, fitted in full-mask mode
+    kinds = {c["mkind"][n] for c in full for n in range(c["B"]) if HU.covered(c, n)[0]}
+    assert {8, 10, 15, 16, 17, 18} <= kinds
+    for mode in (True, False):
+        cls = [k for c, ref in zip(cases, refs) if c["full"] == mode for k in ref.cls if k is not None]
+        decided, tied, flat = cls.count("decided"), cls.count("tied"), cls.count("flat")
+        assert len(cls) >= 150, (mode, len(cls))
+        assert decided >= 0.7 * (decided + tied + flat), (mode, decided, tied, flat)
+    st = np.concatenate([ref.st for ref in refs])
+    cls = [k for ref in refs for k in ref.cls]
+    assert (st == 1).sum() >= 5 and (st == 2).sum() >= 5 and cls.count("fallback") >= 5 and cls.count("tied") >= 5
+    for r in HU.RUNS:
+        assert sum(HU.applies(c, r) for c in cases) >= 5, r
+
+
+def _frame_case(H, W, mask, depth=None, ground=None, skew=0.0):
+    K = np.array([[[0.8 * W, skew, W / 2.0], [0, 0.8 * W, H / 2.0], [0, 0, 1]]])
+    d = np.full((1, H, W), 2.0, np.float32) if depth is None else depth[None]
+    return dict(H=H, W=W, B=1, P=1, K=K, depth=d, masks=mask[None], ground=ground, image_index=None, full=True)
+
+
+def test_hull_coverage_rule_pins():
+    """HU.covered against the figures the suite states (tests/test_gpu_hull_instances.py) and the limits of include/la3d.h."""
+    rs = np.random.RandomState(1)
+    for (H, W), room in (((96, 224), 28), ((128, 160), 40), ((200, 160), 85), ((240, 320), 220), ((64, 256), 0), ((96, 1056), 132)):
+        assert HU.column_room(H, W) == HU.tile_room(H, W) == room
+        for n, want in ((room, (True, None)), (room + 1, (False, "tiles"))):
+            if n:
+                assert HU.covered(_frame_case(H, W, HU.tile_rect_mask(rs, H, W, n)), 0) == want, (H, W, n)
+    assert HU.covered(_frame_case(64, 256, np.zeros((64, 256), bool)), 0) == (True, None)      # (an empty mask has no tiles: status 1)
+    # 640 x 480: the column arrays would fit behind 1040 of the 1200 tiles, but the tile list of four workgroups per CU holds 904,
+    # and the compacted tiles with their range words fit up to 950
+    assert HU.column_room(480, 640) == 1040 and HU.list_capacity(480, 640) == 904 and HU.tile_room(480, 640) == 904
+    assert HU.covered(_frame_case(480, 640, HU.tile_rect_mask(rs, 480, 640, 904)), 0) == (True, None)
+    assert HU.covered(_frame_case(480, 640, HU.tile_rect_mask(rs, 480, 640, 905)), 0) == (False, "tiles")
+    # frames off the tiled path; the padded widths
+    assert not HU.on_tiled_path(64, 96) and not HU.on_tiled_path(37, 64) and not HU.on_tiled_path(100, 214) and HU.on_tiled_path(100, 224)
+    assert HU.tile_room(100, 224) == 31 and HU.tile_room(120, 256) == 56
+    c = _frame_case(100, 214, HU.tile_rect_mask(rs, 100, 214, 5))
+    assert HU.covered(c, 0, {}) == (True, None) and HU.covered(c, 0, dict(entry="ex_u8")) == (False, "frame")
+    # ground row, skew, and their precedence over the mask
+    m = HU.tile_rect_mask(rs, 96, 224, 3)
+    assert HU.covered(_frame_case(96, 224, m, ground=np.array([[0.0, -1, 0, 1]])), 0) == (False, "ground")
+    assert HU.covered(_frame_case(96, 224, m, ground=np.array([[np.nan, -1, 0, 1]])), 0) == (True, None)
+    assert HU.covered(_frame_case(96, 224, m, skew=1e-3), 0) == (False, "skew")
+    assert HU.covered(_frame_case(96, 224, np.zeros((96, 224), bool), skew=1e-3), 0) == (False, "skew")
+    # candidates: one per column whose two ends coincide, two otherwise; 2048 are held
+    H, W = 96, 1056
+    one = np.zeros((H, W), bool); one[5, :] = True
+    two = np.zeros((H, W), bool); two[5:7, :1025] = True
+    d = np.full((H, W), 2.0, np.float32)
+    assert HU.candidate_count(one, d) == 1056 and HU.candidate_count(two, d) == 1025
+    assert HU.covered(_frame_case(H, W, two, d), 0) == (True, None)
+    d2 = d.copy(); d2[6] = 3.0
+    assert HU.candidate_count(two, d2) == 2050 and HU.covered(_frame_case(H, W, two, d2), 0) == (False, "candidates")
+    d2[6, 0] = 2.0; d2[6, 1] = np.nan
+    assert HU.candidate_count(two, d2) == 2048 and HU.covered(_frame_case(H, W, two, d2), 0) == (True, None)
+    d2[5, 3] = -0.0; d2[6, 3] = 0.0
+    assert HU.candidate_count(two, d2) == 2048                                       # (-0 and +0 are two floats)
 
 
 def test_every_run_has_cases():
@@ -247,3 +357,163 @@ def test_aux_checker_sensitivity():
     assert plant(lambda g: g["median"][1].__setitem__(0, g["median"][1][0] + 1))
     assert plant(lambda g: g.__setitem__("align_apply", g["align_apply"] + 1))
     assert plant(lambda g: g["unproject"][0].__setitem__(np.isfinite(g["unproject"][0]).nonzero()[0][:1], 1e30))
+
+
+def _hull_output(c, ref, r):
+    """What a correct GPU run gives, from the oracle's result and the coverage rule."""
+    st, why = HU.expected_status(c, ref, r)
+    B = c["B"]
+    nm = c["masks"].reshape(B, -1).sum(1).astype(float)
+    boxes = np.where((st == 0)[:, None], ref.rec, np.nan)
+    a3 = np.array([-float(len(ref.table[n][0])) if st[n] == 0 and ref.table[n] is not None else 1.0 for n in range(B)])
+    aux = np.stack([ref.yaw, ref.nv.astype(float), nm, a3], 1)
+    aux[st == 5] = [np.nan, 0.0, np.nan, np.nan]                                      # (refused before the mask was counted ...
+    late = np.array([w == "candidates" for w in why])                                # ... or behind the fit stage: both counts)
+    aux[late] = np.stack([np.full(B, np.nan), ref.nv.astype(float), nm, np.full(B, np.nan)], 1)[late]
+    got = dict(boxes=boxes, status=st.copy(), aux=aux)
+    if r.get("entry") in HU.EX_ENTRIES:
+        hint, size, flt = E.ex_params(c, r["entry"])
+        stats = None
+        if flt is not None:
+            stats = np.array([O.mask_stats(m, flt["boundary_threshold"]) for m in c["masks"]]).reshape(B, 4)
+            keep = np.array([O.keep_instance(q, c["H"], True, flt["scale_threshold"]) for q in stats], bool)
+            got["status"] = np.where(keep, st, 6).astype(np.int32)
+            got["boxes"][~keep] = np.nan
+            got["aux"][~keep] = np.stack([np.full(B, np.nan), np.zeros(B), nm, np.full(B, np.nan)], 1)[~keep]
+        Kp = c["K"] if c["image_index"] is None else c["K"][c["image_index"]]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            b2d = O.project_boxes(got["boxes"], Kp if (c["P"] > 1 or c["image_index"] is not None) else c["K"][0], size)
+        b2d[got["status"] != 0] = np.nan
+        got.update(boxes2d=b2d, stats=stats, flt=flt, size=size)
+    return got
+
+
+def _hull_case(want):
+    """The first case of the slice in full-mask mode on the tiled path with a decided, a tied and a refused instance (want) ..."""
+    for s in S.HULL_SEEDS:
+        c = HU.make_case(s)
+        if c["full"] and HU.on_tiled_path(c["H"], HU.padded_width(c["W"])):
+            ref = HU.oracle_case(s)
+            st, _ = HU.expected_status(c, ref, {})
+            if all(k in [ref.cls[n] for n in np.flatnonzero(st == 0)] for k in want) and (st == 5).any():
+                return c, ref, st
+    raise AssertionError("no such case in the slice")
+
+
+def test_hull_checker_passes_the_oracle_in_every_run():
+    seen = set()
+    for s in S.HULL_SEEDS[::4]:
+        c, ref = HU.make_case(s), HU.oracle_case(s)
+        for r in HU.RUNS:
+            if HU.applies(c, r):
+                assert HU.check_run(c, ref, r, _hull_output(c, ref, r)) == [], (s, r)
+                seen.add(repr(r))
+    assert len(seen) == len(HU.RUNS)
+
+
+def test_hull_checker_sensitivity():
+    c, ref, st = _hull_case(("decided", "tied"))
+    good = _hull_output(c, ref, {})
+    tally = HU.new_tally()
+    assert HU.check_run(c, ref, {}, good, tally) == []
+    assert tally["full"]["decided"] and tally["full"]["tied"] and sum(tally["full"]["refused"].values())
+    ok = np.flatnonzero(st == 0)
+    dec = next(n for n in ok if ref.cls[n] == "decided")
+    tie = next(n for n in ok if ref.cls[n] == "tied")
+    why = HU.expected_status(c, ref, {})[1]
+    ref5 = int(next(n for n in np.flatnonzero(st == 5) if why[n] != "candidates"))   # refused before its mask was counted
+    plants = {}
+    # a decided record turned by a quarter: the same rectangle, length and width exchanged
+    g = copy.deepcopy(good); g["boxes"][dec] = ref.box_under(dec, ref.yaw[dec] + np.pi / 2); g["aux"][dec, 0] += np.pi / 2; plants["decided, turned by 90 degrees"] = g
+    # a PCA box where the call must refuse - with the status of a fit, and under the refusal's own status
+    pts, gr = ref._pts.get(ref5, (None, None))
+    pca = O.fit_instances(c["depth"][HU.plane_of(c, ref5)], c["masks"][ref5:ref5 + 1], c["K"][HU.plane_of(c, ref5)])[0][0] if pts is None else O.fit_points(pts, gr)[0]
+    pca = np.where(np.isnan(pca), 1.0, pca)
+    g = copy.deepcopy(good); g["boxes"][ref5] = pca; g["status"][ref5] = 0; g["aux"][ref5] = [0.1, 10, good["aux"][ref5, 2], 0.5]; plants["a PCA box in place of a refusal"] = g
+    g = copy.deepcopy(good); g["boxes"][ref5] = pca; plants["a record under status 5"] = g
+    g = copy.deepcopy(good); g["aux"][ref5, 0] = 0.3; plants["a yaw under status 5"] = g
+    # a refusal in place of a fit
+    g = copy.deepcopy(good); g["boxes"][dec] = np.nan; g["status"][dec] = 5; g["aux"][dec] = [np.nan, 0, np.nan, np.nan]; plants["a refusal in place of a fit"] = g
+    # a tied record under a yaw that is no edge's (its own box under that yaw: consistent in itself, equal in area to 1e-4)
+    g = copy.deepcopy(good); g["aux"][tie, 0] += 1e-2; g["boxes"][tie] = ref.box_under(tie, g["aux"][tie, 0]); plants["tied, the yaw of no edge"] = g
+    g = copy.deepcopy(good); g["aux"][tie, 0] += 1e-2; plants["tied, the right box under a reported yaw that is no edge's"] = g
+    g = copy.deepcopy(good); g["status"][ref5] = 1; plants["a refusal reported as the reference's empty cloud"] = g
+    # ... and under a tied edge's yaw with another yaw's box
+    twin = int(next(i for i in ref.near[tie] if HU._ang(ref.table[tie][0][i], ref.yaw[tie]) > 1e-6))
+    g = copy.deepcopy(good); g["aux"][tie, 0] = ref.table[tie][0][twin]; plants["tied, the twin's yaw with the first edge's box"] = g
+    # a column end lost: one extent of the footprint 1e-6 of the scale short
+    scale = max(1.0, np.abs(ref.rec[dec, :6]).max())
+    g = copy.deepcopy(good); g["boxes"][dec, 5] -= 1e-6 * scale; plants["decided, dx short by 1e-6"] = g
+    g = copy.deepcopy(good); g["boxes"][dec, 3] -= 1e-6 * scale; plants["decided, dz short by 1e-6"] = g
+    g = copy.deepcopy(good); g["boxes"][tie, 5] -= 1e-6 * max(1.0, np.abs(ref.rec[tie, :6]).max()); plants["tied, dx short by 1e-6"] = g
+    g = copy.deepcopy(good); g["aux"][dec, 3] = 0.5; plants["decided, reported as a PCA fallback"] = g
+    g = copy.deepcopy(good); g["aux"][dec, 1] += 1; plants["n_valid"] = g
+    g = copy.deepcopy(good); g["aux"][dec, 2] -= 1; plants["n_masked"] = g
+    g = copy.deepcopy(good); g["aux"][ref5, 2] = 1e9; plants["n_masked of a refused instance"] = g
+    # refused by the ground row, the skew or the tiles: (n_valid, n_masked) = (0, NaN), not a count from somewhere else
+    g = copy.deepcopy(good); g["aux"][ref5, 2] = c["masks"][ref5].sum(); plants["the mask count of an instance refused before the count"] = g
+    g = copy.deepcopy(good); g["aux"][ref5, 1] = 3; plants["n_valid of an instance refused before the count"] = g
+    for name, g in plants.items():
+        assert HU.check_run(c, ref, {}, g), f"planted error not reported: {name}"
+    # the tied record switched to its twin - that edge's yaw and the oracle's box under it - passes
+    g = copy.deepcopy(good); g["aux"][tie, 0] = ref.table[tie][0][twin]; g["boxes"][tie] = ref.box_under(tie, ref.table[tie][0][twin])
+    assert not np.allclose(g["boxes"][tie, 6:15], good["boxes"][tie, 6:15], atol=1e-6)
+    assert HU.check_run(c, ref, {}, g) == []
+    # pins: byte for byte
+    assert HU.check_pin(good, copy.deepcopy(good)) == []
+    g = copy.deepcopy(good); g["boxes"][dec, 0] = np.nextafter(g["boxes"][dec, 0], np.inf)
+    assert HU.check_pin(good, g)
+
+
+def test_hull_checker_counts_of_refused_instances():
+    """include/la3d.h: an instance refused for its candidate count reports n_valid and n_masked exactly (it has been through the fit
+    stage), every other refused instance n_valid 0 and n_masked NaN."""
+    for s in S.HULL_SEEDS:
+        c = HU.make_case(s)
+        late = [n for n in range(c["B"]) if c["full"] and HU.covered(c, n)[1] == "candidates"]
+        if late:
+            break
+    ref = HU.oracle_case(s)
+    good = _hull_output(c, ref, {})
+    assert HU.check_run(c, ref, {}, good) == []
+    n = late[0]
+    assert good["aux"][n, 1] > 1024 and good["aux"][n, 2] == c["masks"][n].sum() >= good["aux"][n, 1]
+    plants = {}
+    g = copy.deepcopy(good); g["aux"][n, 2] = np.nan; plants["n_masked NaN behind the fit stage"] = g
+    g = copy.deepcopy(good); g["aux"][n, 1] = 0; plants["n_valid 0 behind the fit stage"] = g
+    g = copy.deepcopy(good); g["aux"][n, 1:3] = [0, np.nan]; plants["the counts of an early refusal behind the fit stage"] = g
+    g = copy.deepcopy(good); g["aux"][n, 2] += 1; plants["n_masked off by one"] = g
+    g = copy.deepcopy(good); g["aux"][n, 1] -= 1; plants["n_valid off by one"] = g
+    for name, g in plants.items():
+        assert HU.check_run(c, ref, {}, g), f"planted error not reported: {name}"
+
+
+def test_hull_checker_flat_rule_holds_the_footprint():
+    """A flat record (the oracle's footprint has no area) whose GPU box has one fails, height and centre y right or not."""
+    for s in S.HULL_SEEDS:
+        ref = HU.oracle_case(s)
+        flat = [i for i, k in enumerate(ref.cls) if k == "flat" and np.abs(ref.rec[i, 3:6]).max() > 0]
+        if flat:
+            break
+    c, n = HU.make_case(s), flat[0]
+    good = _hull_output(c, ref, {})
+    assert HU.check_run(c, ref, {}, good) == []
+    ext = np.abs(ref.rec[n, 3:6]).max()
+    g = copy.deepcopy(good); g["boxes"][n, 3] = g["boxes"][n, 5] = ext
+    assert any("footprint" in m for m in HU.check_run(c, ref, {}, g))
+
+
+def test_hull_checker_flat_and_fallback_rules():
+    """A fallback record is held to height and centre y whatever the hull did, and to the PCA rule where both sides took the PCA axis."""
+    s = next(s for s in S.HULL_SEEDS if "fallback" in HU.oracle_case(s).cls and (not HU.make_case(s)["full"]))
+    c, ref = HU.make_case(s), HU.oracle_case(s)
+    good = _hull_output(c, ref, {})
+    assert HU.check_run(c, ref, {}, good) == []
+    n = ref.cls.index("fallback")
+    scale = max(1.0, np.abs(ref.rec[n, :6]).max())
+    g = copy.deepcopy(good); g["boxes"][n, 4] += 1e-8 * scale
+    assert HU.check_run(c, ref, {}, g)
+    g = copy.deepcopy(good); g["boxes"][n, 1] += 1e-8 * max(scale, abs(ref.rec[n, 1]))
+    assert HU.check_run(c, ref, {}, g)
+    g = copy.deepcopy(good); g["boxes"][n, 0] += 1e-6 * scale       # (both on the PCA axis, resolved gap: the centre is held too)
+    assert HU.check_run(c, ref, {}, g)

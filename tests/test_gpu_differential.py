@@ -6,6 +6,8 @@
                 and 40 tiny-frame cases
   points        both yaw methods, every launch form of RUNS and the scalar drop-in, 40 cases
   annotations   fit_annotations (GPU-resident and through the host entry) and fit_annotations_all with three filters, 40 images
+  hull          the convex-hull yaw of the depth + mask fit (oracle/campaigns/hull.py): every mask source, the pins hull calls ignore
+                (the same bytes as the default run), full-mask and subsample mode, 60 cases
   aux           unproject, decoders, mask statistics, filters, consumers, depth statistics, matcher, 40 cases
 A case fails with the campaign's own message, which names its seed."""
 import numpy as np
@@ -14,6 +16,7 @@ import pytest
 from oracle.campaigns import annotations as A
 from oracle.campaigns import aux as X
 from oracle.campaigns import engines as E
+from oracle.campaigns import hull as HU
 from oracle.campaigns import points as PT
 from tests import campaign_slices as S
 
@@ -98,6 +101,33 @@ def test_aux_campaign_slice(gpu, seeds):
     for s in seeds:
         c = X.make_case(s)
         fails += [f"seed {s} {c['H']}x{c['W']}: {m}" for m in X.check(c, X.expected(c), X.run_gpu(c))]
+    assert not fails, _report(fails)
+
+
+@pytest.mark.parametrize("seeds", _groups(S.HULL_SEEDS, 6), ids=lambda v: str(v[0]))
+def test_hull_campaign_slice(gpu, seeds):
+    """method="convex_hull": status against the oracle and the documented coverage rule (HU.covered), every fitted record by its
+    class (decided / tied / flat or fallback, from the oracle alone); the pinned runs equal the default run byte for byte."""
+    fails = []
+    tally = HU.new_tally()
+    for s in seeds:
+        c = HU.make_case(s)
+        ref = HU.oracle_case(s)
+        cache, default = {}, None
+        for r in HU.RUNS:
+            if not HU.applies(c, r):
+                continue
+            try:
+                got = HU.run_gpu(c, r, cache)
+            except Exception as e:   # noqa: BLE001 - every failure of the slice is reported, not only the first
+                fails.append(f"seed {s} {r}: call failed: {e!r}")
+                continue
+            if not r:
+                default = got
+            if r in HU.PINS:
+                fails += [f"seed {s} {r}: {m}" for m in (HU.check_pin(default, got) if default is not None else ["no default run to compare with"])]
+            fails += [f"seed {s} {r}: {m}" for m in HU.check_run(c, ref, r, got, tally)]
+    print("\n".join(HU.tally_lines(tally)))
     assert not fails, _report(fails)
 
 

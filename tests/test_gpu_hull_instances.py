@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 def hull_scene(*a, **k):
     """tests/test_hull_contract.py's scenes with masks that leave room for the column arrays behind their tile list on the small
     frames too (full-mask hull: active tiles x 32 B + 8 W bytes within the bit image's H W / 8 bytes - 28 of the 84 tiles of a
-    224 x 96 frame, 1040 of the 1200 of a 640 x 480 one; larger masks are refused, test_full_mask_refuses_...)"""
+    224 x 96 frame, 904 of the 1200 of a 640 x 480 one, where the tile list is the limit; larger masks are refused, test_full_mask_refuses_...)"""
     k.setdefault("rmax", 0.2)
     return _hull_scene(*a, **k)
 
