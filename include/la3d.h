@@ -361,6 +361,59 @@ int la3d_unpack_mask_bits(const uint32_t* bits, int64_t bits_plane_stride, int B
 int la3d_mask_stats_bits(const uint32_t* bits, int64_t bits_plane_stride, int B, int H, int W, int frame_width, int boundary,
                          int32_t* stats, void* stream);
 
+/* ---- 16-bit depth planes ----------------------------------------------------------------------------------------------
+ * Sensor depth is uint16 with a metric scale (millimetres: SUN RGB-D, ScanNet, ARKitScenes, every RealSense / Kinect stream); depth
+ * networks run in half precision.  la3d_fit_instances_depth16 fits straight from such planes - no float32 copy is made or read.
+ *
+ * VALUES.  The float32 value the kernels fit for a stored 16-bit word x:
+ *   LA3D_DTYPE_F16   float32(x): exact.  Subnormal halves, +-inf, NaN and -0 convert as IEEE says.
+ *   LA3D_DTYPE_U16   float32(x) * scale: ONE float32 multiplication, rounded to float32 before any other use (never contracted
+ *                    into a following fma).  With LA3D_DEPTH_ZERO_IS_HOLE a stored 0 becomes a quiet NaN: a hole, dropped exactly
+ *                    as the float32 entries drop a NaN depth under the mask; without the flag 0 is the valid depth 0.0.
+ * From that value on nothing changes: statuses, aux, proj, stats, the NaN / inf / negative-depth rules and the refusal rules of a
+ * hull call apply to the up-converted value - a 16-bit call gives the records the float32 call gives on the up-converted planes
+ * (to the rounding of a changed summation order where the engines differ, bit for bit against the instance engine).
+ *
+ * la3d_fit_instances_depth16(args, depth, mask_bits, bits_plane_stride, bits_flags):
+ *   - args->depth must be NULL and args->depth_plane_stride 0: the planes come in `depth` (struct_size = sizeof(la3d_depth16)).
+ *     planes: device pointer, 2-byte aligned; plane of instance n = image_index[n] or n, plane_stride ELEMENTS apart (>= H*W;
+ *     0 = one shared plane).  Any 2-byte aligned base and any stride are fitted; an 8-byte aligned base with plane_stride % 4 == 0
+ *     takes the vector forms (what a 16-byte aligned base and stride % 4 == 0 are to float32 planes).
+ *   - the masks: exactly one of args->mask, args->rle_counts, args->poly_xy, or mask_bits != NULL with all three NULL;
+ *     bits_plane_stride and bits_flags mean what they mean in la3d_fit_instances_bits (ignored when mask_bits is NULL).
+ *   - every other field of the block means what it means in la3d_fit_instances_ex: ground, sample_idx, image_index, k_stride,
+ *     filter_* + stats, proj, aux, area_hint, opt_*, frame_width, method (LA3D_METHOD_CONVEX_HULL included), stream.  Workspace:
+ *     la3d_fit_workspace_bytes(args).
+ *   - the call runs on the instance engine at every batch size (opt_engine pins give way, as for bit planes); the rows, band and
+ *     split engines have no 16-bit form.  Every frame the float32 entry fits is fitted: the tiled form, the untiled forms, padded
+ *     rows (frame_width).
+ *   - refused before any launch (LA3D_ERR_ARG): NULL block or NULL planes, a bad struct_size, a dtype other than F16 / U16,
+ *     args->depth != NULL or depth_plane_stride != 0, a U16 scale that is not finite or <= 0, flags set for F16 or unknown flag
+ *     bits, no mask source or two of them.
+ * la3d_fit_instances_frames, la3d_fit_annotations_host and the positional entries take float32 planes only.
+ *
+ * Packers (streaming kernels; any plane stride, any element alignment):
+ *   la3d_pack_depth16    depth dev f32, plane p at depth + p*plane_stride floats -> planes of H x W_out 16-bit words, out_plane_stride
+ *                        ELEMENTS apart, rows padded from W to W_out >= W columns with zeros; only the words of a plane are written.
+ *                        F16: round to nearest even, overflow to inf, subnormals kept (numpy astype(float16)).  U16: q = rint(d / scale)
+ *                        in float32; NaN, +-inf and d <= 0 give 0; q > 65535 gives 65535.
+ *   la3d_unpack_depth16  planes stored W_in pixels wide -> out dev f32 [P][H][W], the first W <= W_in columns, by the value rule above. */
+#define LA3D_DTYPE_U16 3
+#define LA3D_DEPTH_ZERO_IS_HOLE 1
+typedef struct la3d_depth16 {
+  int32_t struct_size;      /* sizeof(la3d_depth16) of the caller */
+  int32_t dtype;            /* LA3D_DTYPE_F16 | LA3D_DTYPE_U16 */
+  const void* planes;       /* device, 2-byte aligned; plane of instance n = image_index[n] or n */
+  int64_t plane_stride;     /* ELEMENTS between planes, >= H*W; 0 = one shared plane */
+  float scale;              /* U16: metres per unit, finite and > 0; F16: ignored */
+  int32_t flags;            /* U16: LA3D_DEPTH_ZERO_IS_HOLE or 0; F16: must be 0 */
+} la3d_depth16;
+int la3d_fit_instances_depth16(const la3d_fit_args* args, const la3d_depth16* depth, const uint32_t* mask_bits,
+                               int64_t bits_plane_stride, int32_t bits_flags);
+int la3d_pack_depth16(const float* depth, int64_t plane_stride, int P, int H, int W, int W_out, int dtype, float scale, void* out,
+                      int64_t out_plane_stride, void* stream);
+int la3d_unpack_depth16(const la3d_depth16* src, int P, int H, int W_in, int W, float* out, void* stream);
+
 /* ---- images of different sizes in one call ---------------------------------------------------------------------------
  * Every entry above takes ONE (H, W) per call; a COCO shard comes in hundreds of frame sizes.  la3d_fit_instances_frames fits
  * instances of images of DIFFERENT sizes in one launch: the depth planes lie in one buffer, each at its own offset and pitch, and a

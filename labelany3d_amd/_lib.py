@@ -15,6 +15,8 @@ HINT_HULL_512 = 0x200
 ERR_UNSUPPORTED = -2
 BITS_HEIGHT_ROWS, BITS_HEIGHT_SPAN = 0, 1          # flags of la3d_fit_instances_bits: the height rule of the fused filter
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2        # la3d_pack_logits_bits
+DTYPE_U16 = 3                                     # la3d_depth16 (with DTYPE_F16): uint16 x scale depth planes
+DEPTH_ZERO_IS_HOLE = 1                            # la3d_depth16.flags (U16): a stored 0 is a hole (NaN)
 
 class FitArgs(C.Structure):
     """``la3d_fit_args`` of include/la3d.h (argument block of la3d_fit_instances_ex); field order is the header's."""
@@ -35,6 +37,12 @@ class FitArgs(C.Structure):
                 ("method", C.c_int32)]
 
 
+class Depth16Block(C.Structure):
+    """``la3d_depth16`` of include/la3d.h: the 16-bit depth planes of la3d_fit_instances_depth16 (32 bytes)."""
+    _fields_ = [("struct_size", C.c_int32), ("dtype", C.c_int32), ("planes", C.c_void_p), ("plane_stride", C.c_int64),
+                ("scale", C.c_float), ("flags", C.c_int32)]
+
+
 class Frame(C.Structure):
     """``la3d_frame`` of include/la3d.h: one row per image of a frames call (la3d_fit_instances_frames)."""
     _fields_ = [("depth_offset", C.c_int64), ("H", C.c_int32), ("W", C.c_int32), ("frame_width", C.c_int32), ("reserved", C.c_int32)]
@@ -45,6 +53,10 @@ _SIGS = {
     "la3d_fit_instances_frames": (C.c_int, [C.POINTER(FitArgs), C.c_void_p, C.c_int32]),
     "la3d_fit_workspace_bytes": (C.c_size_t, [C.POINTER(FitArgs)]),
     "la3d_fit_instances_bits": (C.c_int, [C.POINTER(FitArgs), C.c_void_p, C.c_int64, C.c_int32]),
+    "la3d_fit_instances_depth16": (C.c_int, [C.POINTER(FitArgs), C.POINTER(Depth16Block), C.c_void_p, C.c_int64, C.c_int32]),
+    "la3d_pack_depth16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int64,
+                                    C.c_void_p]),
+    "la3d_unpack_depth16": (C.c_int, [C.POINTER(Depth16Block), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "la3d_mask_bits_words": (C.c_size_t, [C.c_int, C.c_int]),
     "la3d_pack_mask_bits": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "la3d_pack_logits_bits": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,

@@ -11,7 +11,7 @@ src/util_3dbox.py:106-178.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -118,6 +118,78 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+class Depth16(NamedTuple):
+    """Depth planes stored in 16 bits (include/la3d.h "16-bit depth planes"; C-ABI ``la3d_fit_instances_depth16``), fitted where they
+    lie - no float32 copy: ``data`` a resident (P,H,W) or (H,W) tensor of ``torch.float16`` (the value is float32(x), exact) or
+    ``torch.uint16`` (the value is float32(x) * float32(scale), one rounding; with ``zero_is_hole`` a stored 0 is a hole - NaN -,
+    dropped as a NaN depth is).  Planes may lie further apart than H*W elements (a slice of a larger tensor) and need only their
+    element alignment.  ``frame_width``: the image columns when the rows are padded (what ``la3d_fit_args::frame_width`` says; 0 =
+    all).  Accepted wherever ``fit_instances`` / ``fit_instances_ex`` / ``fit_instances_rle`` / ``fit_instances_poly`` /
+    ``fit_instances_bits`` / ``InstanceFitter.run`` / ``run_bits`` take ``depth``; a plain float16 / uint16 array there is
+    up-converted to float32 as before."""
+    data: torch.Tensor
+    scale: float = 1.0
+    zero_is_hole: bool = True
+    frame_width: int = 0
+
+
+def _depth16_check(d16: Depth16, HW=None, frame: str = "masks") -> None:
+    """The argument errors of a ``Depth16`` that need no device: dtype, scale, dimensions, the frame of the masks."""
+    t = d16.data
+    if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float16, torch.uint16):
+        raise ValueError(f"Depth16 needs a torch.float16 or torch.uint16 tensor, not {getattr(t, 'dtype', type(t).__name__)}")
+    if t.dtype == torch.uint16 and not (np.isfinite(np.float32(d16.scale)) and np.float32(d16.scale) > 0):
+        raise ValueError(f"Depth16: scale must be finite and > 0 (as float32), not {d16.scale!r}")
+    if t.dim() not in (2, 3):
+        raise ValueError("Depth16 data must be (P,H,W) or (H,W)")
+    if int(d16.frame_width) < 0 or int(d16.frame_width) > t.shape[-1]:
+        raise ValueError("Depth16: frame_width must lie in [0, W]")
+    if HW is not None and tuple(t.shape[-2:]) != tuple(HW):
+        raise ValueError(f"depth planes {tuple(t.shape[-2:])} do not match {frame} {tuple(HW)}")
+
+
+def _depth16_block(d16: Depth16, H: int, W: int) -> _lib.Depth16Block:
+    """``la3d_depth16`` of a checked, resident ``Depth16`` whose planes are H x W: dense rows, planes >= H*W elements apart."""
+    t = d16.data
+    if not t.is_cuda:
+        raise ValueError("Depth16 data must be resident on the GPU (it is fitted where it lies)")
+    P = t.shape[0] if t.dim() == 3 else 1
+    if (W > 1 and t.stride(-1) != 1) or (H > 1 and t.stride(-2) != W) or (t.dim() == 3 and P > 1 and t.stride(0) < H * W):
+        raise ValueError(f"Depth16 planes must have dense rows and lie >= H*W elements apart (strides {t.stride()})")
+    u16 = t.dtype == torch.uint16
+    return _lib.Depth16Block(struct_size=C.sizeof(_lib.Depth16Block), dtype=_lib.DTYPE_U16 if u16 else _lib.DTYPE_F16,
+                             planes=t.data_ptr(), plane_stride=int(t.stride(0)) if t.dim() == 3 and P > 1 else 0,
+                             scale=float(d16.scale) if u16 else 1.0,
+                             flags=_lib.DEPTH_ZERO_IS_HOLE if (u16 and d16.zero_is_hole) else 0)
+
+
+def refuse_depth16(depth, who: str) -> None:
+    """The entries without a 16-bit form say so before any device work."""
+    if isinstance(depth, Depth16):
+        raise ValueError(f"{who} takes float32 depth planes only: Depth16 planes are fitted by fit_instances / fit_instances_ex / "
+                         "fit_instances_rle / fit_instances_poly / fit_instances_bits / InstanceFitter.run (instance engine only)")
+
+
+def _depth_arg(depth):
+    """(what ``_fit_args`` takes as ``depth``, planes) of a device tensor (P,H,W) | (H,W) or a ``Depth16``."""
+    if isinstance(depth, Depth16):
+        return depth, (depth.data.shape[0] if depth.data.dim() == 3 else 1)
+    return _ptr(depth), (depth.shape[0] if depth.dim() == 3 else 1)
+
+
+def _launch(a: FitArgs, bits=None) -> None:
+    """The C entry of a block built by ``_fit_args``: 16-bit depth planes (``a.d16``), bit planes (``bits`` = (pointer, stride,
+    flags)), or the plain block."""
+    d16 = getattr(a, "d16", None)
+    if d16 is not None:
+        b = bits if bits is not None else (None, 0, 0)
+        check(lib.la3d_fit_instances_depth16(C.byref(a), C.byref(d16), b[0], b[1], b[2]), "la3d_fit_instances_depth16")
+    elif bits is not None:
+        check(lib.la3d_fit_instances_bits(C.byref(a), bits[0], bits[1], bits[2]), "la3d_fit_instances_bits")
+    else:
+        check(lib.la3d_fit_instances_ex(C.byref(a)), "la3d_fit_instances_ex")
+
+
 def _order(stream) -> None:
     """A caller-supplied stream that is not the current one is ordered behind the current stream: the convenience wrappers
     upload / convert their arguments (and reuse the cached small uploads of _as_dev) on the CURRENT stream."""
@@ -142,6 +214,8 @@ def _record(stream, *tensors):
     if stream is None or stream == torch.cuda.current_stream():
         return
     for t in tensors:
+        if isinstance(t, Depth16):
+            t = t.data
         if isinstance(t, torch.Tensor) and t.is_cuda:
             t.record_stream(stream)
 
@@ -207,15 +281,17 @@ class InstanceFitter:
             image_index=None, slot: int = 0, stream=None, ws_slot: int = 0, engine=None, launch_order=None, build=None,
             area_hint=None, method=None):
         """All arguments already on the device with the ABI's dtypes (f32 / u8 / f64 / f64 / i32 / i32).
+        ``depth``: float32 planes, or a ``Depth16`` (fitted from its 16-bit planes: C-ABI ``la3d_fit_instances_depth16``).
         ``engine`` / ``launch_order`` / ``build``: scheduling of THIS call (labelany3d_amd.options; speed only).
         ``method``: "pca" | "convex_hull" (None: what the fitter was built for)."""
         meth = self._method(method)
-        a = _fit_args(self.B, self.H, self.W, _ptr(depth), depth.shape[0] if depth.dim() == 3 else 1, _ptr(K),
+        darg, planes = _depth_arg(depth)
+        a = _fit_args(self.B, self.H, self.W, darg, planes, _ptr(K),
                       K.shape[0] if K.dim() == 3 else 1, _ptr(self.boxes[slot]), _ptr(self.status[slot]), _ptr(self.aux[slot]),
                       _ptr(self.workspace[ws_slot]), _stream(stream, raw=True), mask=_ptr(masks), image_index=_ptr(image_index),
                       ground=_ptr(ground), sample_idx=_ptr(sample_idx), area_hint=_ptr(area_hint),
                       opts=options.codes(engine, launch_order, build), method=meth)
-        check(lib.la3d_fit_instances_ex(C.byref(a)), "la3d_fit_instances_ex")
+        _launch(a)
         return self.boxes[slot], self.status[slot], self.aux[slot]
 
     def run_bits(self, depth: torch.Tensor, bits, K: torch.Tensor, ground=None, sample_idx=None, image_index=None, slot: int = 0,
@@ -230,12 +306,13 @@ class InstanceFitter:
         if isinstance(bits, tuple) and (bits[1], bits[2]) != (self.H, self.W):
             raise ValueError(f"bit planes of a {bits[1]} x {bits[2]} frame do not match the fitter's {self.H} x {self.W}")
         stride = _bits_stride(t, self.B, self.H, self.W)
-        a = _fit_args(self.B, self.H, self.W, _ptr(depth), depth.shape[0] if depth.dim() == 3 else 1, _ptr(K),
+        darg, planes = _depth_arg(depth)
+        a = _fit_args(self.B, self.H, self.W, darg, planes, _ptr(K),
                       K.shape[0] if K.dim() == 3 else 1, _ptr(self.boxes[slot]), _ptr(self.status[slot]), _ptr(self.aux[slot]),
                       _ptr(self.workspace[ws_slot]), _stream(stream, raw=True), image_index=_ptr(image_index),
                       ground=_ptr(ground), sample_idx=_ptr(sample_idx), area_hint=_ptr(area_hint),
                       opts=options.codes(engine, launch_order, build), frame_width=0 if fw == self.W else fw, method=meth)
-        check(lib.la3d_fit_instances_bits(C.byref(a), _ptr(t), stride, height_rule_code(height_rule)), "la3d_fit_instances_bits")
+        _launch(a, (_ptr(t), stride, height_rule_code(height_rule)))
         return self.boxes[slot], self.status[slot], self.aux[slot]
 
     def _method(self, method) -> int:
@@ -288,7 +365,13 @@ def _fit_args(B, H, W, depth, planes, K, nk, out, status, aux, workspace, stream
     pointers for ``la3d_fit_annotations_host``) and sizes: ``planes`` depth planes of H*W floats, ``nk`` intrinsics matrices (one
     of either is shared by every instance).  rle = (counts, offsets), poly = (xy, ring_offsets, inst_rings); ``filter`` as in
     ``fit_instances_rle`` (None: no filter); ``proj`` with ``image_size`` = (width, height); ``opts`` = options.codes().
+    ``depth`` may be a ``Depth16``: the block then carries no depth (C-ABI ``la3d_fit_instances_depth16`` takes the planes beside
+    it) and the ``la3d_depth16`` block rides along as ``a.d16`` - ``_launch`` picks the entry by it.
     Built fresh for every call: one InstanceFitter may be driven from several threads and streams."""
+    d16 = None
+    if isinstance(depth, Depth16):
+        _depth16_check(depth, (H, W), "the call's frame")
+        d16, depth, planes = _depth16_block(depth, H, W), None, 1
     a = FitArgs(struct_size=C.sizeof(FitArgs), B=B, H=H, W=W, depth=depth, depth_plane_stride=H * W if planes > 1 else 0,
                 image_index=image_index, mask=mask, K=K, k_stride=9 if nk > 1 else 0, ground=ground, sample_idx=sample_idx,
                 out=out, status=status, aux=aux, workspace=workspace, stream=stream, area_hint=area_hint, frame_width=frame_width,
@@ -303,6 +386,8 @@ def _fit_args(B, H, W, depth, planes, K, nk, out, status, aux, workspace, stream
     if image_size is not None:
         a.proj, a.image_width, a.image_height = proj, float(image_size[0]), float(image_size[1])
     a.opt_engine, a.opt_launch_order, a.opt_build = opts
+    if d16 is not None:
+        a.d16 = d16   # (a Python attribute beside the C fields: it keeps the block alive as long as ``a``)
     return a
 
 
@@ -329,16 +414,26 @@ def _fit_inputs(depth, K, image_index, ground, sample_idx, B, H, W, dev, frame, 
     float32, K (P,3,3) | (3,3) float64 (a shared matrix is expanded to P), image_index (B,) int32, ground (B,4) float64,
     sample_idx (B,500) int32; None stays None.  ``frame`` names the masks in the error text.  The range of a host image_index is
     checked on the host (``given_index``: the array as the caller gave it, when it has been uploaded already); a device tensor's
-    only with ``check_device_index`` (a ~40 us read-back).  Returns (depth, K, image_index, ground, sample_idx, P)."""
-    d = _as_dev(depth, torch.float32, dev)
-    if d.dim() == 2:
-        d = d[None]
-    if d.shape[1:] != (H, W):
-        raise ValueError(f"depth planes {tuple(d.shape[1:])} do not match {frame} {(H, W)}")
+    only with ``check_device_index`` (a ~40 us read-back).  Returns (depth, K, image_index, ground, sample_idx, P).
+    A ``Depth16`` stays what it is - 16-bit planes where they lie, checked, ``data`` as (P,H,W) -; anything else becomes float32."""
+    if isinstance(depth, Depth16):
+        _depth16_check(depth, (H, W), frame)
+        if depth.data.is_cuda and depth.data.device != dev:
+            raise ValueError("the Depth16 planes live on another device")
+        d = depth._replace(data=depth.data if depth.data.dim() == 3 else depth.data[None])
+        _depth16_block(d, H, W)   # (residency and strides, before anything is uploaded)
+        dshape = d.data.shape
+    else:
+        d = _as_dev(depth, torch.float32, dev)
+        if d.dim() == 2:
+            d = d[None]
+        dshape = d.shape
+    if dshape[1:] != (H, W):
+        raise ValueError(f"depth planes {tuple(dshape[1:])} do not match {frame} {(H, W)}")
     k = _as_dev(K, torch.float64, dev, cache=True)
     if k.dim() == 2:
         k = k[None]
-    P = d.shape[0]
+    P = dshape[0]
     if k.shape[0] not in (1, P) or k.shape[1:] != (3, 3):
         raise ValueError("K must be (3,3) or (P,3,3)")
     if k.shape[0] == 1 and P > 1:
@@ -364,6 +459,17 @@ def _fit_inputs(depth, K, image_index, ground, sample_idx, B, H, W, dev, frame, 
         if si.shape != (B, NSAMPLE):
             raise ValueError("sample_idx must be (B,500)")
     return d, k, ii, g, si, P
+
+
+def _pad_rows16(d: Depth16, Wp: int) -> Depth16:
+    """A ``Depth16`` whose rows are padded on the right to Wp columns with zero words (outside every mask: never fitted); the
+    image columns stay in ``frame_width``.  A copy, for the small odd-width batches ``fit_instances`` pads - callers that care keep
+    their planes padded (``pack_depth16(frame_pad=True)``)."""
+    t = d.data
+    W = int(t.shape[-1])
+    out = torch.zeros(t.shape[:-1] + (Wp,), dtype=torch.int16, device=t.device)   # (bit patterns: uint16 has few kernels)
+    out[..., :W].copy_(t.view(torch.int16))
+    return d._replace(data=out.view(t.dtype), frame_width=int(d.frame_width) or W)
 
 
 def pad_rows_f32(d: torch.Tensor, Wp: int) -> torch.Tensor:
@@ -393,6 +499,8 @@ def fit_instances(depth, masks, K, ground=None, sample_idx=None, image_index=Non
     Returns (boxes (B,39) f64, status (B,) i32, aux (B,4) f64 = yaw, n_valid, n_masked, eigen-gap), on the GPU.
     """
     _lib.method_code(method)   # (the reference's error for an unknown method, before any device work)
+    if isinstance(depth, Depth16):
+        _depth16_check(depth, tuple(np.shape(masks))[-2:] if np.ndim(masks) == 3 else None)
     if device is None and isinstance(masks, torch.Tensor) and masks.is_cuda:
         device = masks.device
     dev = _dev(device)
@@ -414,17 +522,17 @@ def fit_instances(depth, masks, K, ground=None, sample_idx=None, image_index=Non
                 # a large resident stack of planes of which this call references at most B: pad the referenced planes only
                 # (P = 1000 planes of 640x427 would otherwise be copied - 1 GB - on every call)
                 sel = ii.long()
-                d = d.index_select(0, sel)
+                d = d._replace(data=d.data.view(torch.int16).index_select(0, sel).view(d.data.dtype)) if isinstance(d, Depth16) else d.index_select(0, sel)
                 if k.shape[0] > 1:
                     k = k.index_select(0, sel)
                 ii, P = None, B
-            d = pad_rows_f32(d, Wp)
+            d = _pad_rows16(d, Wp) if isinstance(d, Depth16) else pad_rows_f32(d, Wp)
             W = Wp
         f = InstanceFitter(B, H, W, dev, method=method)
         if B == 0:
             return f.boxes[0], f.status[0], f.aux[0]
         _order(stream)   # the arguments were uploaded / converted on the current stream
-        out = f.run(d if P > 1 else d[0], m, k, g, si, ii, stream=stream)
+        out = f.run(d if (P > 1 or isinstance(d, Depth16)) else d[0], m, k, g, si, ii, stream=stream)
         _record(stream, d, m, k, g, si, ii, f.workspace, f.boxes, f.status, f.aux)
         return out
 

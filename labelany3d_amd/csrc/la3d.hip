@@ -176,13 +176,15 @@ size_t la3d_fit_workspace_bytes(const la3d_fit_args* args) {
 
 struct BitsSource { const uint32_t* planes; int64_t plane_stride; int32_t flags; };   // la3d_fit_instances_bits' own arguments
 struct FramesSource { const la3d_frame* rows; int32_t P; };                           // la3d_fit_instances_frames' own arguments
+struct Depth16Source { const la3d_depth16* d; };                                      // la3d_fit_instances_depth16's own argument (checked there)
 
 // Every fit entry ends here with its arguments in one block.  filter_on: the fused instance filter runs (the *_filtered entries
 // always; la3d_fit_instances_ex when filter_boundary >= 0 and filter_max_edge > 0).  who: the entry named in la3d_last_error().
 // bs: the bit planes of la3d_fit_instances_bits (an internal parameter: the public block is frozen), null for every other entry.
 // fr: the frame table of la3d_fit_instances_frames (H, W of the block are then bounds), null for every other entry.
+// ds: the 16-bit depth planes of la3d_fit_instances_depth16 (a.depth is then null), null for every other entry.
 static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who, const BitsSource* bs = nullptr,
-                        const FramesSource* fr = nullptr) {
+                        const FramesSource* fr = nullptr, const Depth16Source* ds = nullptr) {
   const int B = a.B;
   int H = a.H, W = a.W;
   if (fr && H > 0 && W > 0 && W <= (1 << 20)) {
@@ -193,7 +195,7 @@ static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who,
     if ((H + 7) / 8 < need) H = need * 8;
   }
   const bool rle = a.rle_counts != nullptr || a.poly_xy != nullptr || bs != nullptr;   // "no u8 plane": the mask is decoded into the LDS bit image
-  if (!a.depth || (!a.mask && !rle) || (a.rle_counts && !a.rle_offsets) || (a.poly_xy && (!a.ring_offsets || !a.inst_rings)) ||
+  if ((!a.depth && !ds) || (!a.mask && !rle) || (a.rle_counts && !a.rle_offsets) || (a.poly_xy && (!a.ring_offsets || !a.inst_rings)) ||
       !a.K || !a.out || !a.status || B < 0 || H <= 0 || W <= 0 ||
       a.depth_plane_stride < 0 || (a.k_stride != 0 && a.k_stride < 9) || (long long)H * W > (1LL << 28)) {
     snprintf(g_err, sizeof(g_err), "%s: bad argument", who);
@@ -211,7 +213,7 @@ static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who,
   }
   FitParams p;   // (every other field keeps its default: see FitParams)
   p.geo = static_cast<double*>(a.workspace);
-  p.depth = a.depth; p.depth_plane_stride = a.depth_plane_stride; p.image_index = a.image_index;
+  p.depth = a.depth; p.depth_plane_stride = ds ? ds->d->plane_stride : a.depth_plane_stride; p.image_index = a.image_index;
   p.mask = a.mask; p.K = a.K; p.k_stride = a.k_stride; p.ground = a.ground; p.sample_idx = a.sample_idx;
   p.rle_counts = a.rle_counts; p.rle_offsets = reinterpret_cast<const long long*>(a.rle_offsets);
   p.poly_xy = a.poly_xy;
@@ -265,8 +267,10 @@ static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who,
     return LA3D_ERR_UNSUPPORTED;
   }
   // 16-byte vector path: every plane base 16-aligned (the u8 mask only when it is read at all)
+  // (16-bit planes: a lane's quad is 8 bytes - base 8-aligned, stride a multiple of four elements)
   f.vec = (p.HW % 16 == 0) && (rle || (reinterpret_cast<uintptr_t>(a.mask) & 15) == 0) &&
-          ((reinterpret_cast<uintptr_t>(a.depth) & 15) == 0) && (a.depth_plane_stride % 4 == 0);
+          (ds ? (reinterpret_cast<uintptr_t>(ds->d->planes) & 7) == 0 : (reinterpret_cast<uintptr_t>(a.depth) & 15) == 0) &&
+          (p.depth_plane_stride % 4 == 0);
   f.sample = a.sample_idx != nullptr;
   f.method = a.method;
   f.frames = fr != nullptr;
@@ -279,6 +283,15 @@ static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who,
   hipStream_t s = static_cast<hipStream_t>(a.stream);
   // frames of different sizes: the instance engine at every batch size (no other engine reads a frame table); pins give way
   if (fr) return instance_fit(p, f, s, a.workspace, who);
+  if (ds) {
+    // 16-bit depth planes: the instance engine at every batch size (no other engine has a 16-bit form); pins give way
+    FitParams16 q;
+    static_cast<FitParams&>(q) = p;
+    q.depth16 = static_cast<const unsigned short*>(ds->d->planes);
+    q.d16_scale = ds->d->scale;
+    q.d16_hole = (ds->d->flags & LA3D_DEPTH_ZERO_IS_HOLE) ? 1 : 0;
+    return ds->d->dtype == LA3D_DTYPE_F16 ? instance_fit_f16(q, f, s, a.workspace, who) : instance_fit_u16(q, f, s, a.workspace, who);
+  }
   switch (choose_engine(p, f, pin)) {
   case LA3D_ENGINE_ROWS:   // (two launches when pinned so, and for a call captured into a HIP graph: it would replay with the same tag)
     return rows_fit(p, pin == LA3D_ENGINE_ROWS2 || stream_capturing(s), s, a.workspace);
@@ -462,6 +475,85 @@ int la3d_fit_instances_bits(const la3d_fit_args* args, const uint32_t* mask_bits
   if (rc != LA3D_SUCCESS) return rc;
   const BitsSource bs{mask_bits, bits_plane_stride, flags};
   return fit_dispatch(a, a.filter_boundary >= 0 && a.filter_max_edge > 0, "la3d_fit_instances_bits", &bs);
+}
+
+int la3d_fit_instances_depth16(const la3d_fit_args* args, const la3d_depth16* depth, const uint32_t* mask_bits,
+                               int64_t bits_plane_stride, int32_t bits_flags) {
+  constexpr int32_t V1_SIZE = (int32_t)offsetof(la3d_fit_args, area_hint);
+  static_assert(sizeof(la3d_depth16) == 32, "la3d_depth16 is part of the ABI");
+  const char* who = "la3d_fit_instances_depth16";
+  if (!args || args->struct_size < V1_SIZE) {
+    set_err("la3d_fit_instances_depth16: bad struct_size");
+    return LA3D_ERR_ARG;
+  }
+  if (!depth) {
+    set_err("la3d_fit_instances_depth16: depth (the la3d_depth16 block) is NULL");
+    return LA3D_ERR_ARG;
+  }
+  if (depth->struct_size < (int32_t)sizeof(la3d_depth16)) {
+    set_err("la3d_fit_instances_depth16: bad struct_size of la3d_depth16");
+    return LA3D_ERR_ARG;
+  }
+  if (depth->dtype != LA3D_DTYPE_F16 && depth->dtype != LA3D_DTYPE_U16) {
+    set_err("la3d_fit_instances_depth16: unknown dtype (LA3D_DTYPE_F16 or LA3D_DTYPE_U16)");
+    return LA3D_ERR_ARG;
+  }
+  if (!depth->planes || (reinterpret_cast<uintptr_t>(depth->planes) & 1)) {
+    set_err("la3d_fit_instances_depth16: planes must be a 2-byte aligned device pointer");
+    return LA3D_ERR_ARG;
+  }
+  la3d_fit_args a;
+  memset(&a, 0, sizeof(a));
+  memcpy(&a, args, (size_t)args->struct_size < sizeof(a) ? (size_t)args->struct_size : sizeof(a));
+  if (a.depth || a.depth_plane_stride != 0) {
+    set_err("la3d_fit_instances_depth16: the depth planes come in the la3d_depth16 block - args->depth must be NULL and depth_plane_stride 0");
+    return LA3D_ERR_ARG;
+  }
+  if (depth->dtype == LA3D_DTYPE_U16) {
+    if (!(depth->scale > 0.0f && depth->scale <= 3.4028234663852886e38f)) {   // (false for NaN)
+      set_err("la3d_fit_instances_depth16: the scale of LA3D_DTYPE_U16 planes must be finite and > 0");
+      return LA3D_ERR_ARG;
+    }
+    if (depth->flags & ~(int32_t)LA3D_DEPTH_ZERO_IS_HOLE) {
+      set_err("la3d_fit_instances_depth16: unknown flags (LA3D_DEPTH_ZERO_IS_HOLE or 0)");
+      return LA3D_ERR_ARG;
+    }
+  } else if (depth->flags != 0) {
+    set_err("la3d_fit_instances_depth16: flags must be 0 for LA3D_DTYPE_F16 planes");
+    return LA3D_ERR_ARG;
+  }
+  if (depth->plane_stride < 0 || (depth->plane_stride != 0 && a.H > 0 && a.W > 0 && depth->plane_stride < (int64_t)a.H * a.W)) {
+    set_err("la3d_fit_instances_depth16: plane_stride must be 0 (one shared plane) or >= H*W elements");
+    return LA3D_ERR_ARG;
+  }
+  const int kinds = (a.mask ? 1 : 0) + (a.rle_counts ? 1 : 0) + (a.poly_xy ? 1 : 0) + (mask_bits ? 1 : 0);
+  if (kinds != 1) {
+    set_err("la3d_fit_instances_depth16: give exactly one mask source: mask / rle_counts / poly_xy in the block, or mask_bits");
+    return LA3D_ERR_ARG;
+  }
+  if (a.poly_xy && (!a.ring_offsets || !a.inst_rings)) {
+    set_err("la3d_fit_instances_depth16: polygon masks need ring_offsets and inst_rings");
+    return LA3D_ERR_ARG;
+  }
+  if (mask_bits) {
+    if (bits_flags & ~(int32_t)LA3D_BITS_HEIGHT_SPAN) {
+      set_err("la3d_fit_instances_depth16: unknown bits_flags (LA3D_BITS_HEIGHT_ROWS or LA3D_BITS_HEIGHT_SPAN)");
+      return LA3D_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(mask_bits) & 3) {
+      set_err("la3d_fit_instances_depth16: mask_bits must be a 4-byte aligned device pointer");
+      return LA3D_ERR_ARG;
+    }
+    if (a.B > 0 && a.H > 0 && a.W > 0 && bits_plane_stride < (int64_t)la3d_mask_bits_words(a.H, a.W)) {
+      set_err("la3d_fit_instances_depth16: bits_plane_stride is smaller than la3d_mask_bits_words(H, W)");
+      return LA3D_ERR_ARG;
+    }
+  }
+  const int rc = check_block_options(a, who);
+  if (rc != LA3D_SUCCESS) return rc;
+  const BitsSource bs{mask_bits, bits_plane_stride, bits_flags};
+  const Depth16Source ds{depth};
+  return fit_dispatch(a, a.filter_boundary >= 0 && a.filter_max_edge > 0, who, mask_bits ? &bs : nullptr, nullptr, &ds);
 }
 
 int la3d_fit_instances_frames(const la3d_fit_args* args, const la3d_frame* frames, int32_t P) {

@@ -544,6 +544,67 @@ struct FitParams {
   int frames_max_h = 0, frames_max_w = 0;
 };
 
+// ------------------------------------------------------------------------------------------
+// 16-bit depth planes (la3d_fit_instances_depth16; include/la3d.h "16-bit depth planes").  The walks are templates over the
+// ELEMENT type of the depth planes - float (every older entry: the code it always was), d_f16, d_u16 - and take a DepthCvt of
+// that type: what turns a stored element into the float32 value that is fitted.  From that value on nothing differs.
+//   d_f16  IEEE half -> float32, exact (subnormals, infinities, NaN, -0 as IEEE says)
+//   d_u16  float32(x) * scale: ONE float32 multiplication (rounded before any other use; never contracted); with `hole` a
+//          stored 0 is a quiet NaN - a hole, dropped as the float32 path drops a NaN depth under the mask
+// ------------------------------------------------------------------------------------------
+struct d_f16 { unsigned short b; };
+struct d_u16 { unsigned short b; };
+template <typename DT> struct DepthCvt {};                                   // float / half planes: nothing to carry
+template <> struct DepthCvt<d_u16> { float scale = 1.0f; int hole = 0; };   // (wave-uniform: scalar registers)
+
+// The kernel argument of a 16-bit call: the block of every call plus the planes and their value rule.  FitParams::depth stays
+// null; depth_plane_stride counts ELEMENTS of the 16-bit planes.
+struct FitParams16 : FitParams {
+  const unsigned short* depth16 = nullptr;
+  float d16_scale = 1.0f;
+  int d16_hole = 0;
+};
+
+// the float32 bit pattern of one stored element (raw: the element zero-extended; for float planes the pattern itself)
+template <typename DT>
+__device__ inline unsigned depth_bits(unsigned raw, const DepthCvt<DT>& cv) {
+  if constexpr (sizeof(DT) == 4) {
+    return raw;
+  } else if constexpr (sizeof(DT) == 2 && __is_same(DT, d_f16)) {
+    // (one v_cvt_f32_f16 on the low half of the register, kept out of the optimiser's sight: left to it, the conversions of a step are
+    // hoisted to the loads and the tiled kernels - at their 64-register budget - spill)
+    float f;
+    asm("v_cvt_f32_f16 %0, %1" : "=v"(f) : "v"(raw));
+    return __float_as_uint(f);
+  } else {
+    const float f = __fmul_rn((float)(raw & 0xffffu), cv.scale);
+    return (cv.hole && (raw & 0xffffu) == 0u) ? 0x7fc00000u : __float_as_uint(f);
+  }
+}
+// one element from memory, as the float32 that is fitted
+template <typename DT>
+__device__ inline float depth_at(const DT* __restrict__ dpl, long long i, const DepthCvt<DT>& cv) {
+  if constexpr (sizeof(DT) == 4) return dpl[i];
+  else return __uint_as_float(depth_bits<DT>((unsigned)dpl[i].b, cv));
+}
+// a lane's quad as it was loaded (float planes: 16 bytes in x..w; 16-bit planes: 8 bytes in x, y - z and w are not read) -> the
+// four float32 bit patterns.  Called where a quad is CONSUMED: the loads of a step stay in flight until then.
+template <typename DT>
+__device__ inline void quad_bits(const uint4& q, const DepthCvt<DT>& cv, unsigned* db) {
+  if constexpr (sizeof(DT) == 4) {
+    db[0] = q.x; db[1] = q.y; db[2] = q.z; db[3] = q.w;
+  } else {
+    db[0] = depth_bits<DT>(q.x & 0xffffu, cv); db[1] = depth_bits<DT>(q.x >> 16, cv);
+    db[2] = depth_bits<DT>(q.y & 0xffffu, cv); db[3] = depth_bits<DT>(q.y >> 16, cv);
+  }
+}
+// the quad of four consecutive elements at p (16-byte / 8-byte aligned), as loaded
+template <typename DT>
+__device__ inline uint4 quad_load(const void* p) {
+  if constexpr (sizeof(DT) == 4) return *reinterpret_cast<const uint4*>(p);
+  else { const uint2 t = *reinterpret_cast<const uint2*>(p); return make_uint4(t.x, t.y, 0u, 0u); }
+}
+
 // Bit plane (global) -> LDS bit image, by all NTH threads of the workgroup: a straight copy - 16-byte non-temporal loads and 16-byte
 // LDS stores where base and stride allow, single words otherwise - plus the popcount; bits of the last word past H*W are cleared in
 // LDS (they are not trusted).  Returns this thread's share of the mask pixels.  No barrier: the caller's follows.

@@ -22,6 +22,13 @@ struct CallFacts {
 // instance engine (la3d_instance.hip): one workgroup per instance - takes every call; picks the instantiation of
 // fit_instances_kernel for the frame and launches it
 int instance_fit(FitParams p, const CallFacts& f, hipStream_t s, void* workspace, const char* who);
+// the same engine on 16-bit depth planes (la3d_instance_f16.hip / la3d_instance_u16.hip: la3d_instance.hip compiled for IEEE half /
+// uint16 x scale elements; la3d_fit_instances_depth16)
+int instance_fit_f16(FitParams16 p, const CallFacts& f, hipStream_t s, void* workspace, const char* who);
+int instance_fit_u16(FitParams16 p, const CallFacts& f, hipStream_t s, void* workspace, const char* who);
+// the launches behind the fit kernel of a hull call, which read no depth (la3d_instance.hip, shared by its 16-bit forms)
+int hull_finish_launch(const FitParams& p, bool sample, hipStream_t s);
+int hull_refuse_launch(const FitParams& p, hipStream_t s);
 // band engine (la3d_band.hip): two / four / eight workgroups per instance that meet through the workspace
 bool band_applies(const FitParams& p, const CallFacts& f);
 bool band_frame_ok(int H, int W, int nb);

@@ -17,8 +17,43 @@
 #include "la3d_stages.hpp"
 #include "la3d_hull.hpp"
 
+// This file is compiled three times: as itself for float32 depth planes, and - included by la3d_instance_f16.hip /
+// la3d_instance_u16.hip, which set LA3D_INSTANCE_DT - for the 16-bit planes of la3d_fit_instances_depth16 (translation units of
+// their own: they compile side by side with this one).  Everything that differs sits behind DepthT / KParams / the DepthCvt the
+// walks take; with LA3D_INSTANCE_DT == 0 the kernels are the ones they were.
+#ifndef LA3D_INSTANCE_DT
+#define LA3D_INSTANCE_DT 0
+#endif
+#if LA3D_INSTANCE_DT == 0
+using DepthT = float;
+using KParams = la3d::FitParams;
+#define LA3D_INSTANCE_FIT instance_fit
+#elif LA3D_INSTANCE_DT == 1
+using DepthT = la3d::d_f16;
+using KParams = la3d::FitParams16;
+#define LA3D_INSTANCE_FIT instance_fit_f16
+#define fit_instances_kernel fit_instances_f16_kernel
+#else
+using DepthT = la3d::d_u16;
+using KParams = la3d::FitParams16;
+#define LA3D_INSTANCE_FIT instance_fit_u16
+#define fit_instances_kernel fit_instances_u16_kernel
+#endif
 
 namespace {
+// the planes of a call and what turns their elements into the float32 that is fitted
+__device__ inline const float* depth_planes(const FitParams& p, const FitParams&) { return p.depth; }
+__device__ inline DepthCvt<float> depth_cvt(const FitParams&) { return {}; }
+#if LA3D_INSTANCE_DT != 0
+__device__ inline const DepthT* depth_planes(const FitParams&, const FitParams16& call) { return reinterpret_cast<const DepthT*>(call.depth16); }
+__device__ inline DepthCvt<DepthT> depth_cvt(const FitParams16& call) {
+  DepthCvt<DepthT> cv;
+#if LA3D_INSTANCE_DT == 2
+  cv.scale = call.d16_scale; cv.hole = call.d16_hole;
+#endif
+  return cv;
+}
+#endif
 // ------------------------------------------------------------------------------------------
 // instance engine: one workgroup per instance
 // ------------------------------------------------------------------------------------------
@@ -29,9 +64,9 @@ namespace {
 // real depth map: dropped, as the reference drops them, src/util_3dbox.py:139) and range keys that order negative depths too
 // (hull_key).  Moments about (px0, pz0).  col = colmin[W] | colmax[W], initialised to 0xffffffff / 0.  One tile per wave and step;
 // lane = (column c of the tile, four rows from h4).
-__device__ inline void sweep_sep_hull(const FitParams& p, const float* __restrict__ dpl, const unsigned* bits, const unsigned short* list,
+__device__ inline void sweep_sep_hull(const FitParams& p, const DepthT* __restrict__ dpl, const unsigned* bits, const unsigned short* list,
                                       int nactive, const double* Mg, unsigned* col, int wave, int lane, double px0, double pz0,
-                                      double* acc, double* yext, int* cnt) {
+                                      double* acc, double* yext, int* cnt, const DepthCvt<DepthT> cv) {
   const int c = lane & 31, h4 = (lane >> 5) * 4;
   const double a00 = Mg[0], a02 = Mg[2], a11 = Mg[4], a12 = Mg[5];
   double s0 = acc[0], s1 = acc[1], s2 = acc[2], s3 = acc[3], s4 = acc[4], ylo = yext[0], yhi = yext[1];
@@ -47,7 +82,7 @@ __device__ inline void sweep_sep_hull(const FitParams& p, const float* __restric
     for (int k = 0; k < 4; ++k) {
       const int v = v0 + k;
       if (((nib >> k) & 1u) && v < p.H) {   // (rows past the frame carry no mask bit; the test keeps the load inside the plane regardless)
-        const float df = dpl[(long long)v * p.W + u];
+        const float df = depth_at<DepthT>(dpl, (long long)v * p.W + u, cv);
         if (finite_f32(df)) {
           const unsigned key = hull_key(__float_as_uint(df));
           kmin = min(kmin, key); kmax = max(kmax, key);
@@ -73,11 +108,13 @@ __device__ inline void sweep_sep_hull(const FitParams& p, const float* __restric
 // frame geometry in ITS copy of the parameters (frame_geometry, la3d_device.hpp), which everything below reads.  Every difference sits behind the
 // constant FRAMES: the other instantiations read the kernel argument itself, as they did.
 template <bool VEC, bool LDSMASK, bool SAMPLE, bool TILED, int SRC, bool HULL = false, bool FRAMES = false>
-__global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitParams p_call) {
+__global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const KParams p_call) {
   static_assert(!FRAMES || (VEC && LDSMASK && TILED && !HULL && (SRC == 1 || SRC == 2)), "frames calls: run lengths / polygons, tiled form");
+  static_assert(!FRAMES || LA3D_INSTANCE_DT == 0, "frames calls: float32 planes");
   FitParams p_frame;   // FRAMES only: this workgroup's parameters (dead otherwise)
   if constexpr (FRAMES) p_frame = p_call;
-  const FitParams& p = FRAMES ? p_frame : p_call;   // (the LDS LAYOUT below is always the call's: p_call.mask_lds_bytes)
+  const FitParams& p_block = p_call;
+  const FitParams& p = FRAMES ? p_frame : p_block;   // (the LDS LAYOUT below is always the call's: p_call.mask_lds_bytes)
   constexpr bool RLE = SRC == 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned* bits = reinterpret_cast<unsigned*>(smem);
@@ -128,7 +165,8 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
     }
   }
   const int HW = p.HW;
-  const float* dpl = p.depth + (long long)img * p.depth_plane_stride;
+  const DepthT* dpl = depth_planes(p, p_call) + (long long)img * p.depth_plane_stride;
+  const DepthCvt<DepthT> cv = depth_cvt(p_call);
   const unsigned char* mpl = p.mask ? p.mask + (long long)inst * HW : nullptr;
 
   if (tid == NT - 1) {
@@ -462,7 +500,7 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
     unsigned* col = bits + nactive * 8;
     double hacc[5] = {0, 0, 0, 0, 0}, yx[2] = {INFINITY, -INFINITY};
     int hcnt = 0;
-    sweep_sep_hull(p, dpl, bits, list, nactive, Mg, col, wave, lane, 0.0, 0.0, hacc, yx, &hcnt);
+    sweep_sep_hull(p, dpl, bits, list, nactive, Mg, col, wave, lane, 0.0, 0.0, hacc, yx, &hcnt, cv);
     stage_moments_to_axis(sh, p, inst_p, hacc, hcnt, nmask, tid, wave, lane, true);
     if (sh->redo) {   // uniform: ill-conditioned raw sums - the moments once more about the pivot the stage left (the ranges stand)
       __syncthreads();
@@ -471,7 +509,7 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
 #pragma unroll
       for (int i = 0; i < 5; ++i) hacc[i] = 0;
       hcnt = 0;
-      sweep_sep_hull(p, dpl, bits, list, nactive, Mg, col, wave, lane, piv[0], piv[1], hacc, yx, &hcnt);
+      sweep_sep_hull(p, dpl, bits, list, nactive, Mg, col, wave, lane, piv[0], piv[1], hacc, yx, &hcnt, cv);
       stage_moments_to_axis(sh, p, inst_p, hacc, hcnt, nmask, tid, wave, lane, false);
     }
     if (sh->st != LA3D_BOX_OK) return;   // (the stage wrote status and the NaN record; nothing to finish)
@@ -500,8 +538,8 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
       unsigned* col = bits + nactive * 8;
       double sacc[5] = {0, 0, 0, 0, 0}, yx[2] = {INFINITY, -INFINITY};
       unsigned unsafe = 0u;
-      if (p.H & 7) sweep_sep<true>(p, dpl, bits, list, nactive, Mg, col, wave, lane, sacc, yx, &unsafe, 0, nfull);   // uniform
-      else sweep_sep<false>(p, dpl, bits, list, nactive, Mg, col, wave, lane, sacc, yx, &unsafe, 0, nfull);
+      if (p.H & 7) sweep_sep<true>(p, dpl, bits, list, nactive, Mg, col, wave, lane, sacc, yx, &unsafe, 0, nfull, cv);   // uniform
+      else sweep_sep<false>(p, dpl, bits, list, nactive, Mg, col, wave, lane, sacc, yx, &unsafe, 0, nfull, cv);
       if (__ballot(unsafe >= 0x7f800000u) != 0ull && lane == 0) sh->sep_bad = 1;   // NaN / inf / negative depth under the mask
       // (the wave's y extent waits in scalar registers while the axis is computed: four vector registers fewer across that stage)
       const double ylo_w = uniform_f64(wave_min(yx[0])), yhi_w = uniform_f64(wave_max(yx[1]));
@@ -622,7 +660,7 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
         }
         for (; k > 0; --k) w &= w - 1;  // drop k lowest set bits
         const unsigned i = (unsigned)lo * 32u + (unsigned)(__ffs((int)w) - 1);
-        const float df = dpl[i];
+        const float df = depth_at<DepthT>(dpl, i, cv);
         unsigned u, v;
         if constexpr (FRAMES) p_frame.rcpW = 1.0f / (float)p.W;
         pix_uv(i, p.W, p.rcpW, &u, &v);
@@ -649,15 +687,15 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
       constexpr bool SP = !SAMPLE;
       const bool specA = SP && Mg[6] == 0.0 && Mg[7] == 0.0 && Mg[8] == 1.0;   // uniform
       if (LK && cull) {
-        if (specA) sweep_tiled<0, false, true, SP>(p, dpl, bits, list, nactive, Mg, Mg + 3, Mg + 6, wave, lane, acc, &cnt, nullptr, compact, rng_words, -1, nfull);
-        else sweep_tiled<0, false, true>(p, dpl, bits, list, nactive, Mg, Mg + 3, Mg + 6, wave, lane, acc, &cnt, nullptr, compact, rng_words, -1, nfull);
+        if (specA) sweep_tiled<0, false, true, SP>(p, dpl, bits, list, nactive, Mg, Mg + 3, Mg + 6, wave, lane, acc, &cnt, nullptr, compact, rng_words, -1, nfull, cv);
+        else sweep_tiled<0, false, true>(p, dpl, bits, list, nactive, Mg, Mg + 3, Mg + 6, wave, lane, acc, &cnt, nullptr, compact, rng_words, -1, nfull, cv);
       } else {
-        if (specA) sweep_tiled<0, false, false, SP>(p, dpl, bits, list, nactive, Mg, Mg + 3, Mg + 6, wave, lane, acc, &cnt, nullptr, compact, rng_words, -1, nfull);
-        else sweep_tiled<0, false>(p, dpl, bits, list, nactive, Mg, Mg + 3, Mg + 6, wave, lane, acc, &cnt, nullptr, compact, rng_words, -1, nfull);
+        if (specA) sweep_tiled<0, false, false, SP>(p, dpl, bits, list, nactive, Mg, Mg + 3, Mg + 6, wave, lane, acc, &cnt, nullptr, compact, rng_words, -1, nfull, cv);
+        else sweep_tiled<0, false>(p, dpl, bits, list, nactive, Mg, Mg + 3, Mg + 6, wave, lane, acc, &cnt, nullptr, compact, rng_words, -1, nfull, cv);
       }
       cnt = nmask;   // the optimistic pass does not count: with every masked depth finite, valid pixels = mask pixels
     }
-    else sweep<VEC, LDSMASK, 0>(p, dpl, mpl, bits, Mg, Mg + 3, Mg + 6, wave, lane, acc, &cnt, &nmask);
+    else sweep<VEC, LDSMASK, 0>(p, dpl, mpl, bits, Mg, Mg + 3, Mg + 6, wave, lane, acc, &cnt, &nmask, nullptr, cv);
   }
 
   LA3D_STAMP(3);
@@ -676,16 +714,16 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
       }
     } else if (TILED) {
       if (sh->redo == 2) {   // ill-conditioned sums: the moments about the pivot; the optimistic pass's tile ranges and pass B stand
-        pivot_pass(p, dpl, bits, list, nactive, Mg, Mg + 6, wave, lane, compact, pivot_ptr(sh), acc, &cnt);
+        pivot_pass(p, dpl, bits, list, nactive, Mg, Mg + 6, wave, lane, compact, pivot_ptr(sh), acc, &cnt, cv);
       } else {
         checked = true;
-        if (LK && cull) sweep_tiled<0, true, true>(p, dpl, bits, list, nactive, Mg, Mg + 3, Mg + 6, wave, lane, acc, &cnt, nullptr, compact, rng_words, -1, nfull);
-        else sweep_tiled<0, true>(p, dpl, bits, list, nactive, Mg, Mg + 3, Mg + 6, wave, lane, acc, &cnt, nullptr, compact, rng_words, -1, nfull);
+        if (LK && cull) sweep_tiled<0, true, true>(p, dpl, bits, list, nactive, Mg, Mg + 3, Mg + 6, wave, lane, acc, &cnt, nullptr, compact, rng_words, -1, nfull, cv);
+        else sweep_tiled<0, true>(p, dpl, bits, list, nactive, Mg, Mg + 3, Mg + 6, wave, lane, acc, &cnt, nullptr, compact, rng_words, -1, nfull, cv);
       }
     } else {
       double piv[2];
       get_pivot(sh, piv);
-      sweep<VEC, LDSMASK, 0, true>(p, dpl, mpl, bits, Mg, Mg + 3, Mg + 6, wave, lane, acc, &cnt, &nmask, piv);
+      sweep<VEC, LDSMASK, 0, true>(p, dpl, mpl, bits, Mg, Mg + 3, Mg + 6, wave, lane, acc, &cnt, &nmask, piv, cv);
     }
     stage_moments_to_axis(sh, p, inst_p, acc, cnt, nmask, tid, wave, lane, false);
   }
@@ -731,15 +769,15 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
       if constexpr (LK) {
         if (compact) nsurv = nactive;   // the identity list written before the axis stage
         if (cull) {   // uniform
-          nsurv = checked ? cull_plan<true>(sh, p, dpl, bits, list, nactive, rng_words, N0, Mg + 3, N2, tid, wave, lane, ext)
-                          : cull_plan<false>(sh, p, dpl, bits, list, nactive, rng_words, N0, Mg + 3, N2, tid, wave, lane, ext);
+          nsurv = checked ? cull_plan<true>(sh, p, dpl, bits, list, nactive, rng_words, N0, Mg + 3, N2, tid, wave, lane, ext, cv)
+                          : cull_plan<false>(sh, p, dpl, bits, list, nactive, rng_words, N0, Mg + 3, N2, tid, wave, lane, ext, cv);
         }
       }
-      if (checked) sweep_tiled<1, true>(p, dpl, bits, list, nactive, N0, Mg + 3, N2, wave, lane, ext, &d0, qh, compact, rng_words, nsurv);
-      else if (!SAMPLE && Mg[3] == 0.0) sweep_tiled<1, false, false, !SAMPLE>(p, dpl, bits, list, nactive, N0, Mg + 3, N2, wave, lane, ext, &d0, qh, compact, rng_words, nsurv);
-      else sweep_tiled<1, false>(p, dpl, bits, list, nactive, N0, Mg + 3, N2, wave, lane, ext, &d0, qh, compact, rng_words, nsurv);
+      if (checked) sweep_tiled<1, true>(p, dpl, bits, list, nactive, N0, Mg + 3, N2, wave, lane, ext, &d0, qh, compact, rng_words, nsurv, 0, cv);
+      else if (!SAMPLE && Mg[3] == 0.0) sweep_tiled<1, false, false, !SAMPLE>(p, dpl, bits, list, nactive, N0, Mg + 3, N2, wave, lane, ext, &d0, qh, compact, rng_words, nsurv, 0, cv);
+      else sweep_tiled<1, false>(p, dpl, bits, list, nactive, N0, Mg + 3, N2, wave, lane, ext, &d0, qh, compact, rng_words, nsurv, 0, cv);
     }
-    else sweep<VEC, LDSMASK, 1>(p, dpl, mpl, bits, N0, Mg + 3, N2, wave, lane, ext, &d0, &d1);
+    else sweep<VEC, LDSMASK, 1>(p, dpl, mpl, bits, N0, Mg + 3, N2, wave, lane, ext, &d0, &d1, nullptr, cv);
   }
   LA3D_STAMP(5);
   if constexpr (FRAMES) frame_proj(p_frame, p_call, inst_p);
@@ -751,6 +789,7 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const FitPar
 
 
 
+#if LA3D_INSTANCE_DT == 0   // (the kernels behind the fit - they read no depth - exist once: the 16-bit units launch them through hull_finish_launch / hull_refuse_launch)
 // ------------------------------------------------------------------------------------------
 // hull finish: one workgroup of NTP threads per instance - candidates -> hull_yaw -> extents over the candidates under the hull yaw
 // (the extents of a point set along ANY direction are taken at hull vertices, and every hull vertex is a candidate) -> record.
@@ -873,22 +912,21 @@ __global__ __launch_bounds__(256) void hull_refuse_kernel(const FitParams p) {
   if (p.proj) { for (int j = 0; j < 8; ++j) p.proj[(long long)inst * 8 + j] = NAN; }
 }
 
+#endif   // LA3D_INSTANCE_DT == 0
+
 // the two launches of a hull call, one linear chain on the caller's stream (no launch order: workgroup b fits instance xcd_remap(b))
 template <bool VEC, bool SAMPLE, int SRC>
-int launch_hull_inst(const FitParams& p, size_t lds, hipStream_t s) {
+int launch_hull_inst(const KParams& p, size_t lds, hipStream_t s) {
   // (full-mask mode = the tiled vector build, subsample mode = the build without tile list)
   auto kern = fit_instances_kernel<VEC, true, SAMPLE, !SAMPLE, SRC, true>;
   allow_big_lds(reinterpret_cast<const void*>(kern));
   hipLaunchKernelGGL(kern, dim3(p.B), dim3(NT), lds, s, p);
   const int rc = check_launch("fit_instances_kernel (hull)");
   if (rc != LA3D_SUCCESS) return rc;
-  const unsigned long long stride = hull_stride_bytes(SAMPLE, p.W);
-  if (SAMPLE) hipLaunchKernelGGL((hull_finish_kernel<true, HULL_SMALL>), dim3(p.B), dim3(NTP), 0, s, p, stride);
-  else hipLaunchKernelGGL((hull_finish_kernel<false, HULL_MAX>), dim3(p.B), dim3(NTP), 0, s, p, stride);
-  return check_launch("hull_finish_kernel");
+  return la3d::hull_finish_launch(p, SAMPLE, s);
 }
 template <bool VEC, bool SAMPLE>
-int launch_hull(const FitParams& p, size_t lds, hipStream_t s) {
+int launch_hull(const KParams& p, size_t lds, hipStream_t s) {
   if (p.mask_bits != nullptr) return launch_hull_inst<true, SAMPLE, 3>(p, lds, s);
   if (p.rle_counts != nullptr) return launch_hull_inst<true, SAMPLE, 1>(p, lds, s);
   if (p.poly_xy != nullptr) return launch_hull_inst<true, SAMPLE, 2>(p, lds, s);
@@ -896,10 +934,10 @@ int launch_hull(const FitParams& p, size_t lds, hipStream_t s) {
 }
 
 template <bool VEC, bool LDSMASK, bool SAMPLE, bool TILED, int SRC, bool FRAMES = false>
-int launch_fit_inst(const FitParams& p_in, size_t lds, hipStream_t s, void* workspace) {
+int launch_fit_inst(const KParams& p_in, size_t lds, hipStream_t s, void* workspace) {
   auto kern = fit_instances_kernel<VEC, LDSMASK, SAMPLE, TILED, SRC, false, FRAMES>;
   allow_big_lds(reinterpret_cast<const void*>(kern));
-  FitParams p = p_in;
+  KParams p = p_in;
   // size-balanced launch order: needs the 16-byte mask groups (VEC), more than one workgroup per CU, and a batch
   // the O(B^2) ranking is cheap for
   // (a frames call orders by the caller's area_hint only: the estimates know one frame size per call)
@@ -931,7 +969,7 @@ int launch_fit_inst(const FitParams& p_in, size_t lds, hipStream_t s, void* work
           const unsigned long long t = (unsigned long long)std::chrono::steady_clock::now().time_since_epoch().count();
           p.order_nonce = (t * 0x9E3779B97F4A7C15ull) ^ (unsigned long long)reinterpret_cast<uintptr_t>(workspace) ^ 0xA5A5A5A55A5A5A5Aull;
         } else if (SRC == 3) {
-          hipLaunchKernelGGL(size_estimate_bits_kernel, dim3((p.B + 3) / 4), dim3(256), 0, s, p, k.shift, est);
+          hipLaunchKernelGGL(size_estimate_bits_kernel, dim3((p.B + 3) / 4), dim3(256), 0, s, static_cast<const FitParams&>(p), k.shift, est);
         } else {
           hipLaunchKernelGGL(size_estimate_kernel, dim3((p.B + 3) / 4), dim3(256), 0, s, p.mask, p.rle_counts, p.rle_offsets, p.poly_xy,
                              p.poly_ring_off, p.poly_inst_rings, p.B, p.HW, k.step, k.shift, est, nullptr);
@@ -946,7 +984,7 @@ int launch_fit_inst(const FitParams& p_in, size_t lds, hipStream_t s, void* work
 
 // run-length input is its own instantiation (it needs the LDS bit image), so the u8 kernels carry no decode code
 template <bool VEC, bool LDSMASK, bool SAMPLE, bool TILED = false>
-int launch_fit(const FitParams& p, size_t lds, hipStream_t s, void* workspace = nullptr) {
+int launch_fit(const KParams& p, size_t lds, hipStream_t s, void* workspace = nullptr) {
   if (LDSMASK && p.mask_bits != nullptr) return launch_fit_inst<VEC, LDSMASK, SAMPLE, TILED, LDSMASK ? 3 : 0>(p, lds, s, workspace);
   if (LDSMASK && p.rle_counts != nullptr) return launch_fit_inst<VEC, LDSMASK, SAMPLE, TILED, LDSMASK ? 1 : 0>(p, lds, s, workspace);
   if (LDSMASK && p.poly_xy != nullptr) return launch_fit_inst<VEC, LDSMASK, SAMPLE, TILED, LDSMASK ? 2 : 0>(p, lds, s, workspace);
@@ -956,15 +994,33 @@ int launch_fit(const FitParams& p, size_t lds, hipStream_t s, void* workspace = 
 
 // la3d_fit_instances_frames: run lengths or polygon parts, the tiled form (full-mask or subsample)
 template <bool SAMPLE>
-int launch_fit_frames(const FitParams& p, size_t lds, hipStream_t s, void* workspace) {
+int launch_fit_frames(const KParams& p, size_t lds, hipStream_t s, void* workspace) {
+#if LA3D_INSTANCE_DT == 0
   if (p.rle_counts != nullptr) return launch_fit_inst<true, true, SAMPLE, true, 1, true>(p, lds, s, workspace);
   return launch_fit_inst<true, true, SAMPLE, true, 2, true>(p, lds, s, workspace);
+#else
+  set_err("frames of different sizes: float32 depth planes only");   // (never reached: the 16-bit entry has no frame table)
+  return LA3D_ERR_UNSUPPORTED;
+#endif
 }
 
 }  // namespace
 
 namespace la3d {
-int instance_fit(FitParams p, const CallFacts& f, hipStream_t s, void* workspace, const char* who) {
+#if LA3D_INSTANCE_DT == 0
+int hull_finish_launch(const FitParams& p, bool sample, hipStream_t s) {
+  const unsigned long long stride = hull_stride_bytes(sample, p.W);
+  if (sample) hipLaunchKernelGGL((hull_finish_kernel<true, HULL_SMALL>), dim3(p.B), dim3(NTP), 0, s, p, stride);
+  else hipLaunchKernelGGL((hull_finish_kernel<false, HULL_MAX>), dim3(p.B), dim3(NTP), 0, s, p, stride);
+  return check_launch("hull_finish_kernel");
+}
+int hull_refuse_launch(const FitParams& p, hipStream_t s) {
+  hipLaunchKernelGGL(hull_refuse_kernel, dim3((p.B + 255) / 256), dim3(256), 0, s, p);
+  return check_launch("hull_refuse_kernel");
+}
+#endif
+
+int LA3D_INSTANCE_FIT(KParams p, const CallFacts& f, hipStream_t s, void* workspace, const char* who) {
   const int H = p.H, W = p.W, B = p.B;
   const bool vec = f.vec, ldsmask = f.ldsmask;
   const size_t poly_stage = f.poly_stage;
@@ -1046,8 +1102,7 @@ int instance_fit(FitParams p, const CallFacts& f, hipStream_t s, void* workspace
   if (f.method == LA3D_METHOD_CONVEX_HULL) {
     // full-mask hull on a frame outside the tiled vector path: no per-column structure to take the hull from - every instance is
     // refused (LA3D_BOX_UNSUPPORTED); reference-subsample mode (sample_idx) covers such frames
-    hipLaunchKernelGGL(hull_refuse_kernel, dim3((B + 255) / 256), dim3(256), 0, s, p);
-    return check_launch("hull_refuse_kernel");
+    return hull_refuse_launch(p, s);
   }
   lds += poly_stage;
   if (ldsmask) return vec ? launch_fit<true, true, false>(p, lds, s, workspace) : launch_fit<false, true, false>(p, lds, s);

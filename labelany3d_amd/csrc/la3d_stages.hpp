@@ -480,10 +480,10 @@ __device__ inline void cull_bound1(double u0, double v0, double dlo, double dhi,
 
 // Every thread of the workgroup calls it (four barriers).  On return ext[] holds the champions' extents (the start values of
 // pass B, the same in every lane) and the survivor list sits in the range area; returns the number of survivors (uniform).
-template <bool CHK>
-__device__ inline int cull_plan(Shared* sh, const FitParams& p, const float* __restrict__ dpl, unsigned* bits,
+template <bool CHK, typename DT = float>
+__device__ inline int cull_plan(Shared* sh, const FitParams& p, const DT* __restrict__ dpl, unsigned* bits,
                                 const unsigned short* list, int nactive, int rng_words, const double* N0, const double* M1,
-                                const double* N2, int tid, int wave, int lane, double* ext) {
+                                const double* N2, int tid, int wave, int lane, double* ext, const DepthCvt<DT> cv = {}) {
   const unsigned* rng = bits + nactive * 8;
   unsigned short* surv = reinterpret_cast<unsigned short*>(bits + nactive * 8);
   float* cval = reinterpret_cast<float*>(bits + nactive * 8 + rng_words - CULL_SCRATCH_WORDS);   // [NWAVE][6]
@@ -560,9 +560,10 @@ __device__ inline int cull_plan(Shared* sh, const FitParams& p, const float* __r
     const int tx = (int)(tt & 0xffu), ty = (int)(tt >> 8);
     const unsigned nib = (bits[e * 8 + c.r] >> (c.cq * 4)) & 0xFu;
     uint4 dq = make_uint4(0u, 0u, 0u, 0u);
-    if (e < c.keepn) dq = c.keep[e * 64 + lane];
-    else if (nib) dq = *reinterpret_cast<const uint4*>(dpl + (long long)(ty * 8 + c.r) * c.W + tx * 32 + c.cq * 4);
-    const unsigned db[4] = {dq.x, dq.y, dq.z, dq.w};
+    if (e < c.keepn) dq = keep_get<DT>(c.keep + (e * 64 + lane));
+    else if (nib) dq = quad_load<DT>(dpl + (long long)(ty * 8 + c.r) * c.W + tx * 32 + c.cq * 4);
+    unsigned db[4];
+    quad_bits<DT>(dq, cv, db);   // (a kept tile holds quads as loaded)
     const double vd = (double)(ty * 8 + c.r), ud = (double)(tx * 32 + c.cq * 4);
     const double r0 = fma(c.a00, ud, fma(c.a01, vd, c.a02));
     const double r1 = fma(c.a10, ud, fma(c.a11, vd, c.a12));

@@ -11,10 +11,13 @@ namespace {
 // axes in the yaw frame.  A0/A1/A2 are the rows mapping [u,v,1] to the ray components: PASS 0 uses rows 0
 // and 2 of M; PASS 1 uses N0, M row 1, N2.
 // PIV (pass 0): the moments about pivot[0 .. 2) - the re-run of an ill-conditioned instance (axis_from_sums).
-template <bool VEC, bool LDSMASK, int PASS, bool PIV = false>
-__device__ inline void sweep(const FitParams& p, const float* __restrict__ dpl, const unsigned char* __restrict__ mpl,
+// DT: the element type of the depth planes (float, or d_f16 / d_u16 with their DepthCvt: la3d_device.hpp); the 16-bit vector form
+// loads a quad as 8 bytes.
+template <bool VEC, bool LDSMASK, int PASS, bool PIV = false, typename DT = float>
+__device__ inline void sweep(const FitParams& p, const DT* __restrict__ dpl, const unsigned char* __restrict__ mpl,
                              const unsigned* bits, const double* A0, const double* A1, const double* A2,
-                             int wave, int lane, double* acc, int* cnt, int* nmask, const double* pivot = nullptr) {
+                             int wave, int lane, double* acc, int* cnt, int* nmask, const double* pivot = nullptr,
+                             const DepthCvt<DT> cv = {}) {
   double px0 = 0, pz0 = 0;
   if constexpr (PIV) { px0 = pivot[0]; pz0 = pivot[1]; }
   const int HW = p.HW, W = p.W;
@@ -49,11 +52,18 @@ __device__ inline void sweep(const FitParams& p, const float* __restrict__ dpl, 
       const unsigned i0 = (unsigned)q * 4u;
       float dk[4];
       if (VEC) {
-        const float4 t = *(const float4*)(dpl + i0);
-        dk[0] = t.x; dk[1] = t.y; dk[2] = t.z; dk[3] = t.w;
+        if constexpr (sizeof(DT) == 4) {
+          const float4 t = *(const float4*)(dpl + i0);
+          dk[0] = t.x; dk[1] = t.y; dk[2] = t.z; dk[3] = t.w;
+        } else {
+          unsigned db[4];
+          quad_bits<DT>(quad_load<DT>(dpl + i0), cv, db);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) dk[k] = __uint_as_float(db[k]);
+        }
       } else {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) dk[k] = ((int)(i0 + k) < HW && ((nib >> k) & 1u)) ? dpl[i0 + k] : 0.f;
+        for (int k = 0; k < 4; ++k) dk[k] = ((int)(i0 + k) < HW && ((nib >> k) & 1u)) ? depth_at<DT>(dpl, i0 + k, cv) : 0.f;
       }
       unsigned u0, v0;
       pix_uv(i0, W, p.rcpW, &u0, &v0);
@@ -126,6 +136,19 @@ struct TileCtx {
   double a00, a01, a02, a10, a11, a12, a20, a21, a22;
 };
 
+// A lane's quad in its slot of the LDS-kept tiles, as loaded: 16 bytes of float planes; of 16-bit planes the 8 bytes that exist (the
+// slot keeps its 16-byte pitch: the layout of the kept area does not depend on the element type)
+template <typename DT>
+__device__ inline void keep_put(uint4* slot, const uint4& q) {
+  if constexpr (sizeof(DT) == 4) *slot = q;
+  else *reinterpret_cast<uint2*>(slot) = make_uint2(q.x, q.y);
+}
+template <typename DT>
+__device__ inline uint4 keep_get(const uint4* slot) {
+  if constexpr (sizeof(DT) == 4) return *slot;
+  else { const uint2 t = *reinterpret_cast<const uint2*>(slot); return make_uint4(t.x, t.y, 0u, 0u); }   // (z, w: never read)
+}
+
 // list entry j of this walk -> tile coordinates (wave-uniform, in SGPRs)
 template <bool SURV = false>
 __device__ inline void tile_coords(const TileCtx& c, const unsigned short* list, bool dense, int j, int rev_base, int* tx, int* ty) {
@@ -149,8 +172,10 @@ __device__ inline void tile_coords(const TileCtx& c, const unsigned short* list,
 // "defines" the quad without an instruction).  That is harmless by construction: every consumer gates a quad through its
 // nibble (pass A ANDs the validity word into the bits, pass B ORs its complement, tile_range does both), and saves four moves
 // per tile.
-template <int PASS, bool LK, bool SURV = false, bool ZERO = true, bool FULLC = false>
-__device__ inline unsigned tile_fetch(const TileCtx& c, const float* __restrict__ dpl, const unsigned* bits,
+// (16-bit planes: a quad is 8 bytes and lands in dq.x / dq.y AS STORED - tile_compute converts it where it is consumed, so the TG
+// loads of a step stay in flight; c.loff counts bytes of the plane's element type)
+template <int PASS, bool LK, bool SURV = false, bool ZERO = true, bool FULLC = false, typename DT = float>
+__device__ inline unsigned tile_fetch(const TileCtx& c, const DT* __restrict__ dpl, const unsigned* bits,
                                       const unsigned short* list, int nsteps, bool dense, int j0, int rev_base, uint4* dq,
                                       int* tcs = nullptr) {   // tcs (SURV): the tiles' coordinates for tile_compute, which then need not look them up again
   unsigned nib[TG];
@@ -160,10 +185,14 @@ __device__ inline unsigned tile_fetch(const TileCtx& c, const float* __restrict_
     const int j = j0 + g;
     nib[g] = 0; txs[g] = 0; tys[g] = 0; ent[g] = 0x7fffffff;
     if (ZERO) dq[g] = make_uint4(0u, 0u, 0u, 0u);
-    else {
+    else if constexpr (sizeof(DT) == 4) {
       u32x4 t;
       asm volatile("" : "=v"(t));
       dq[g] = make_uint4(t.x, t.y, t.z, t.w);
+    } else {   // (a 16-bit quad lives in x, y only: z and w are never read - not by the kept tiles either, see keep_put)
+      unsigned a, b;
+      asm volatile("" : "=v"(a), "=v"(b));
+      dq[g].x = a; dq[g].y = b;
     }
     if (j < nsteps) {
       if (SURV) {   // survivor j -> list entry -> tile: two dependent LDS reads, done once per tile
@@ -189,11 +218,16 @@ __device__ inline unsigned tile_fetch(const TileCtx& c, const float* __restrict_
   unsigned pk = 0;
 #pragma unroll
   for (int g = 0; g < TG; ++g) {
-    if (LK && PASS == 1 && ent[g] < c.keepn) dq[g] = c.keep[ent[g] * 64 + (c.r * 8 + c.cq)];   // kept by pass A
+    if (LK && PASS == 1 && ent[g] < c.keepn) dq[g] = keep_get<DT>(c.keep + (ent[g] * 64 + (c.r * 8 + c.cq)));   // kept by pass A
     else if (nib[g]) {
       // uniform tile origin (scalar registers) + the lane's constant byte offset: the load takes its address as SGPR base + VGPR offset
-      const float* tp = dpl + ((long long)(tys[g] * 8) * c.W + txs[g] * 32);
-      dq[g] = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(tp) + c.loff);
+      const DT* tp = dpl + ((long long)(tys[g] * 8) * c.W + txs[g] * 32);
+      if constexpr (sizeof(DT) == 4) {
+        dq[g] = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(tp) + c.loff);
+      } else {
+        const uint2 t = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned char*>(tp) + c.loff);
+        dq[g].x = t.x; dq[g].y = t.y;
+      }
     }
     pk |= nib[g] << (4 * g);
   }
@@ -233,20 +267,22 @@ __device__ inline void tile_range(const TileCtx& c, int e, unsigned nib, const u
 }
 
 // stage 2: the pixel math of a step on quads dq / nibbles pk (all lanes; unmasked lanes carry zeros / NaNs)
-template <int PASS, bool CHK, bool LK = false, bool SURV = false, bool RNG = false, bool SPEC = false, bool FULLC = false>
+template <int PASS, bool CHK, bool LK = false, bool SURV = false, bool RNG = false, bool SPEC = false, bool FULLC = false, typename DT = float>
 __device__ inline void tile_compute(const TileCtx& c, const unsigned short* list, int nsteps, bool dense, int j0, int rev_base,
-                                    const uint4* dq, unsigned pk, double* sv, int* n, const int* tcs = nullptr) {
+                                    const uint4* dq, unsigned pk, double* sv, int* n, const int* tcs = nullptr,
+                                    const DepthCvt<DT> cv = {}) {
 #pragma unroll
   for (int g = 0; g < TG; ++g) {
     const int j = j0 + g;
     if (j >= nsteps) continue;   // wave-uniform
-    if (LK && PASS == 0 && j < c.keepn) c.keep[j * 64 + (c.r * 8 + c.cq)] = dq[g];   // (pass A walks the list forwards: entry = j)
+    if (LK && PASS == 0 && j < c.keepn) keep_put<DT>(c.keep + (j * 64 + (c.r * 8 + c.cq)), dq[g]);   // (pass A walks the list forwards: entry = j)
     const unsigned nib = FULLC ? 0xFu : (pk >> (4 * g)) & 0xFu;
     if (!FULLC && dense && __ballot(nib != 0) == 0) continue;
     int tx, ty;
     if (SURV && tcs) { tx = tcs[g] & 0xff; ty = tcs[g] >> 8; }
     else tile_coords<SURV>(c, list, dense, j, rev_base, &tx, &ty);
-    const unsigned db[4] = {dq[g].x, dq[g].y, dq[g].z, dq[g].w};
+    unsigned db[4];
+    quad_bits<DT>(dq[g], cv, db);   // (the LDS-kept tiles hold quads as loaded: converted here in either pass)
     const double vd = (double)(ty * 8 + c.r), ud = (double)(tx * 32 + c.cq * 4);
     const double r0 = fma(c.a00, ud, fma(c.a01, vd, c.a02));
     const double r2 = fma(c.a20, ud, fma(c.a21, vd, c.a22));
@@ -268,17 +304,18 @@ __device__ inline int cull_rng_words(int nactive) { return ((2 * nactive + 3) & 
 // nsurv >= 0 (pass B): walk only the culling survivors surv[0 .. nsurv) (fit_instances_kernel builds the list).
 // SPEC: the un-grounded, skew-free forms of the pixel math (quad_math): the caller checks M's row 2 == (0, 0, 1) for pass A,
 // M[1][0] == 0 for pass B.
-template <int PASS, bool CHK, bool RNG = false, bool SPEC = false>
-__device__ inline void sweep_tiled(const FitParams& p, const float* __restrict__ dpl, const unsigned* bits,
+template <int PASS, bool CHK, bool RNG = false, bool SPEC = false, typename DT = float>
+__device__ inline void sweep_tiled(const FitParams& p, const DT* __restrict__ dpl, const unsigned* bits,
                                    const unsigned short* list, int nactive, const double* A0, const double* A1,
                                    const double* A2, int wave, int lane, double* acc, int* cnt,
-                                   unsigned* qhead = nullptr, int compact = 0, int rng_words = 0, int nsurv = -1, int nfull = 0) {
+                                   unsigned* qhead = nullptr, int compact = 0, int rng_words = 0, int nsurv = -1, int nfull = 0,
+                                   const DepthCvt<DT> cv = {}) {
   // nfull (pass A, compact image): list entries [0, nfull) are tiles completely inside the mask - walked by a loop of their own whose
   // body fetches no row words and gates no pixel (round 6: what the separable pass does, for the calls that need two passes)
   constexpr bool LK = true;   // (the compact image / LDS-kept tiles / survivor walk apply whenever the caller hands over `compact`)
   TileCtx c;
   c.W = p.W; c.H = p.H; c.ntx = p.ntx; c.r = lane >> 3; c.cq = lane & 7;
-  c.loff = (unsigned)(c.r * p.W + c.cq * 4) * 4u;
+  c.loff = (unsigned)(c.r * p.W + c.cq * 4) * (unsigned)sizeof(DT);
   c.compact = LK ? compact : 0; c.keepn = 0; c.keep = nullptr;
   c.rng = nullptr; c.surv = nullptr;
   if (LK && compact) {   // uniform: the image region behind the compacted entries holds depth tiles between the passes
@@ -309,7 +346,7 @@ __device__ inline void sweep_tiled(const FitParams& p, const float* __restrict__
       uint4 dq[TG];
       int tcs[TG];
       const unsigned pk = tile_fetch<PASS, LK, true, false>(c, dpl, bits, list, nsurv, false, j0, -1, dq, tcs);
-      tile_compute<PASS, CHK, LK, true, false, SPEC>(c, list, nsurv, false, j0, -1, dq, pk, sv, &n, tcs);
+      tile_compute<PASS, CHK, LK, true, false, SPEC, false, DT>(c, list, nsurv, false, j0, -1, dq, pk, sv, &n, tcs, cv);
     }
   } else {
     int jfirst = jstart;
@@ -317,14 +354,14 @@ __device__ inline void sweep_tiled(const FitParams& p, const float* __restrict__
       for (int j0 = jstart; j0 < nfull; j0 += NWAVE * TG) {
         uint4 dq[TG];
         const unsigned pk = tile_fetch<PASS, LK, false, false, true>(c, dpl, bits, list, nfull, false, j0, -1, dq);
-        tile_compute<PASS, CHK, LK, false, RNG && LK, SPEC, true>(c, list, nfull, false, j0, -1, dq, pk, sv, &n);
+        tile_compute<PASS, CHK, LK, false, RNG && LK, SPEC, true, DT>(c, list, nfull, false, j0, -1, dq, pk, sv, &n, nullptr, cv);
       }
       jfirst = nfull + jstart;
     }
     for (int j0 = jfirst; j0 < nsteps; j0 += NWAVE * TG) {
       uint4 dq[TG];
       const unsigned pk = tile_fetch<PASS, LK, false, false>(c, dpl, bits, list, nsteps, dense, j0, rev_base, dq);
-      tile_compute<PASS, CHK, LK, false, RNG && LK, SPEC>(c, list, nsteps, dense, j0, rev_base, dq, pk, sv, &n);
+      tile_compute<PASS, CHK, LK, false, RNG && LK, SPEC, false, DT>(c, list, nsteps, dense, j0, rev_base, dq, pk, sv, &n, nullptr, cv);
     }
   }
 #pragma unroll
@@ -335,9 +372,10 @@ __device__ inline void sweep_tiled(const FitParams& p, const float* __restrict__
 // The moments of an ILL-CONDITIONED instance about a pivot (axis_from_sums; round 6): one tile per wave and step, one quad per lane,
 // the checked pixel math - written for few registers, not for speed (the walk is rare and must not cost the common path a register:
 // the tiled kernels sit at their 64-register budget).  The tile list / compact image as pass A left them; depth from memory (L2).
-__device__ inline void pivot_pass(const FitParams& p, const float* __restrict__ dpl, const unsigned* bits, const unsigned short* list,
+template <typename DT = float>
+__device__ inline void pivot_pass(const FitParams& p, const DT* __restrict__ dpl, const unsigned* bits, const unsigned short* list,
                                   int nactive, const double* A0, const double* A2, int wave, int lane, int compact,
-                                  const double* piv, double* acc, int* cnt) {
+                                  const double* piv, double* acc, int* cnt, const DepthCvt<DT> cv = {}) {
   const int r = lane >> 3, cq = lane & 7;
   const bool dense = nactive < 0;
   const int nsteps = dense ? p.ntx * p.nty : nactive;
@@ -352,8 +390,9 @@ __device__ inline void pivot_pass(const FitParams& p, const float* __restrict__ 
     if (compact) nib = (bits[j * 8 + r] >> (cq * 4)) & 0xFu;
     else if (row < p.H) nib = (bits[row * p.ntx + tx] >> (cq * 4)) & 0xFu;
     if (nib) {
-      const uint4 dq = *reinterpret_cast<const uint4*>(dpl + (long long)row * p.W + tx * 32 + cq * 4);
-      const unsigned db[4] = {dq.x, dq.y, dq.z, dq.w};
+      const uint4 dq = quad_load<DT>(dpl + (long long)row * p.W + tx * 32 + cq * 4);
+      unsigned db[4];
+      quad_bits<DT>(dq, cv, db);
       const double vd = (double)row, ud = (double)(tx * 32 + cq * 4);
       quad_math<0, true, false, true>(nib, db, fma(A0[0], ud, fma(A0[1], vd, A0[2])), 0.0, fma(A2[0], ud, fma(A2[1], vd, A2[2])),
                                       A0[0], 0.0, A2[0], acc, &n, piv[0], piv[1]);
@@ -407,11 +446,17 @@ __device__ __host__ inline int sep_col_words(int W) { return (2 * W + 3) & ~3; }
 // gating - 8 instead of 16 instructions per pixel on ~60 % of config 2's active tiles; the same values in the same operations, so a
 // tile gives the same contributions whichever class walks it.  (A class per LOOP, not a branch per tile: two bodies inside one
 // unrolled step cost 12-19 spilled vector registers.)
-template <bool EDGE, bool FULL>
-__device__ inline void sep_steps(const FitParams& p, const float* __restrict__ dpl, const unsigned* bits, const unsigned short* list,
+// (16-bit planes: a pixel is one 2-byte load, kept as stored and converted where stage 2 consumes it)
+template <bool EDGE, bool FULL, typename DT = float>
+__device__ inline void sep_steps(const FitParams& p, const DT* __restrict__ dpl, const unsigned* bits, const unsigned short* list,
                                  int jbeg, int jend, double a00, double a02, double a11, double a12, unsigned* colq, int wave, int c, int h4,
                                  const unsigned* loff, int row0, double& s0, double& s1, double& s2, double& s3, double& s4, double& ylo,
-                                 double& yhi, unsigned& bad) {
+                                 double& yhi, unsigned& bad, const DepthCvt<DT> cv = {}) {
+  // one pixel as stored, zero-extended (float planes: the pattern itself)
+  auto px_load = [](const unsigned char* q) -> unsigned {
+    if constexpr (sizeof(DT) == 4) return *reinterpret_cast<const unsigned*>(q);
+    else return (unsigned)*reinterpret_cast<const unsigned short*>(q);
+  };
   for (int j0 = jbeg + wave * TG; j0 < jend; j0 += NWAVE * TG) {
     unsigned dq[TG][4];
     unsigned pk = 0;
@@ -430,7 +475,7 @@ __device__ inline void sep_steps(const FitParams& p, const float* __restrict__ d
         const unsigned char* tp = reinterpret_cast<const unsigned char*>(dpl + ((long long)((t >> 8) * 8u) * p.W + (t & 0xffu) * 32u));
         if (FULL) {
 #pragma unroll
-          for (int k = 0; k < 4; ++k) dq[g][k] = *reinterpret_cast<const unsigned*>(tp + loff[k]);
+          for (int k = 0; k < 4; ++k) dq[g][k] = px_load(tp + loff[k]);
           continue;
         }
         const uint4 w = *reinterpret_cast<const uint4*>(bits + e * 8 + h4);
@@ -439,14 +484,14 @@ __device__ inline void sep_steps(const FitParams& p, const float* __restrict__ d
         if (!EDGE || (t >> 8) * 8u + 8u <= (unsigned)p.H) {   // uniform: every row of the tile lies inside the frame
           if (nib) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) dq[g][k] = *reinterpret_cast<const unsigned*>(tp + loff[k]);
+            for (int k = 0; k < 4; ++k) dq[g][k] = px_load(tp + loff[k]);
           }
         } else {
           // the last tile row of a frame whose height is not a multiple of 8: a lane loads only the rows it holds a mask bit for
           // (rows past the frame carry none) - the block load above would read up to seven rows past the end of the depth plane
 #pragma unroll
           for (int k = 0; k < 4; ++k)
-            if ((nib >> k) & 1u) dq[g][k] = *reinterpret_cast<const unsigned*>(tp + loff[k]);
+            if ((nib >> k) & 1u) dq[g][k] = px_load(tp + loff[k]);
         }
       }
     }
@@ -462,15 +507,16 @@ __device__ inline void sep_steps(const FitParams& p, const float* __restrict__ d
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         double d, ym;
+        const unsigned dv = depth_bits<DT>(dq[g][k], cv);   // the float32 that is fitted (float planes: dq itself)
         if (FULL) {
-          cmin = min(cmin, dq[g][k]); cmax = max(cmax, dq[g][k]);
-          d = (double)__uint_as_float(dq[g][k]);
+          cmin = min(cmin, dv); cmax = max(cmax, dv);
+          d = (double)__uint_as_float(dv);
           ym = d * ry;
         } else {
           const int m = __builtin_amdgcn_sbfe((int)pk, 4 * g + k, 1);   // the pixel's mask bit as 0 / -1: ONE v_bfe_i32
-          const unsigned v = dq[g][k] & (unsigned)m;                 // invalid -> +0.0 (sums), 0 (unsigned max)
+          const unsigned v = dv & (unsigned)m;                 // invalid -> +0.0 (sums), 0 (unsigned max)
           unsigned w;
-          asm("v_bfi_b32 %0, %1, %2, -1" : "=v"(w) : "v"(m), "v"(dq[g][k]));   // invalid -> 0xffffffff (unsigned min)
+          asm("v_bfi_b32 %0, %1, %2, -1" : "=v"(w) : "v"(m), "v"(dv));   // invalid -> 0xffffffff (unsigned min)
           cmin = min(cmin, w); cmax = max(cmax, v);
           d = (double)__uint_as_float(v);
           // y extent: per pixel (the row ray), invalid pixels as NaN (ignored by v_min / v_max_f64): the high word through one v_bfi
@@ -498,23 +544,23 @@ __device__ inline void sep_steps(const FitParams& p, const float* __restrict__ d
 }
 
 // nfull: list entries [0, nfull) are tiles that lie completely inside the mask (0: the list is not sorted by class)
-template <bool EDGE = false>
-__device__ inline void sweep_sep(const FitParams& p, const float* __restrict__ dpl, const unsigned* bits,
+template <bool EDGE = false, typename DT = float>
+__device__ inline void sweep_sep(const FitParams& p, const DT* __restrict__ dpl, const unsigned* bits,
                                  const unsigned short* list, int nactive, const double* Mg, unsigned* col, int wave, int lane,
-                                 double* acc, double* yext, unsigned* unsafe, int row0 = 0, int nfull = 0) {
+                                 double* acc, double* yext, unsigned* unsafe, int row0 = 0, int nfull = 0, const DepthCvt<DT> cv = {}) {
   // (row0: the frame row of tile row 0 - the row engine hands every workgroup a band of rows, dpl / bits / list band-local;
   // the instance engine passes the literal 0)
   const int c = lane & 31, h4 = (lane >> 5) * 4;
   const double a00 = Mg[0], a02 = Mg[2], a11 = Mg[4], a12 = Mg[5];
   unsigned loff[4];   // byte offsets of this lane's four pixels inside a tile (uniform tile origin + 32-bit vector offset: the saddr form)
 #pragma unroll
-  for (int k = 0; k < 4; ++k) loff[k] = (unsigned)((h4 + k) * p.W + c) * 4u;
+  for (int k = 0; k < 4; ++k) loff[k] = (unsigned)((h4 + k) * p.W + c) * (unsigned)sizeof(DT);
   unsigned* colq = col + c;
   double s0 = acc[0], s1 = acc[1], s2 = acc[2], s3 = acc[3], s4 = acc[4];
   double ylo = yext[0], yhi = yext[1];
   unsigned bad = *unsafe;
-  if (nfull > 0) sep_steps<EDGE, true>(p, dpl, bits, list, 0, nfull, a00, a02, a11, a12, colq, wave, c, h4, loff, row0, s0, s1, s2, s3, s4, ylo, yhi, bad);   // uniform
-  sep_steps<EDGE, false>(p, dpl, bits, list, nfull, nactive, a00, a02, a11, a12, colq, wave, c, h4, loff, row0, s0, s1, s2, s3, s4, ylo, yhi, bad);
+  if (nfull > 0) sep_steps<EDGE, true, DT>(p, dpl, bits, list, 0, nfull, a00, a02, a11, a12, colq, wave, c, h4, loff, row0, s0, s1, s2, s3, s4, ylo, yhi, bad, cv);   // uniform
+  sep_steps<EDGE, false, DT>(p, dpl, bits, list, nfull, nactive, a00, a02, a11, a12, colq, wave, c, h4, loff, row0, s0, s1, s2, s3, s4, ylo, yhi, bad, cv);
   acc[0] = s0; acc[1] = s1; acc[2] = s2; acc[3] = s3; acc[4] = s4;
   yext[0] = ylo; yext[1] = yhi;
   *unsafe = bad;

@@ -40,7 +40,7 @@ import numpy as np
 import torch
 
 from ._lib import lib, method_code
-from .batched import _dev, _upload_many, draw_sample_idx
+from .batched import _dev, _upload_many, draw_sample_idx, refuse_depth16
 from .jsonout import SceneRecords, format_scenes
 from .masks import (PackedFrames, fit_instances_ex, fit_instances_frames, frame_table, mask_stats_poly, mask_stats_rle, pack_polygons, pack_rle,
                     pack_rle_frames, pad_depth_rows, padded_width)
@@ -538,6 +538,7 @@ class ScenePipeline:
         if self.mixed_frames:   # arrival order, whatever the sizes
             batch: list = []
             for sc in scenes:
+                refuse_depth16(sc.get("depth"), "ScenePipeline")
                 batch.append(sc)
                 if len(batch) >= self.batch_images:
                     yield batch
@@ -547,6 +548,7 @@ class ScenePipeline:
             return
         pending: Dict[tuple, list] = {}
         for sc in scenes:
+            refuse_depth16(sc.get("depth"), "ScenePipeline")
             key = (sc["height"], sc["width"])
             pending.setdefault(key, []).append(sc)
             if len(pending[key]) >= self.batch_images:

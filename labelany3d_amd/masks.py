@@ -32,7 +32,8 @@ import torch
 from . import _lib, options
 from ._lib import AUX, BOX_FILTERED, REC, check, lib
 from .batched import (InstanceFitter, _as_dev, _bits_stride, _bulk, _dev, _filter_args, _fit_args, _fit_inputs, _ptr, _record, _stream,  # noqa: F401
-                      _upload_many, height_rule_code, pad_rows_f32)
+                      _upload_many, height_rule_code, pad_rows_f32, Depth16, _depth16_block, _depth16_check, _launch, _pad_rows16,
+                      refuse_depth16)
 
 
 def rle_from_string(s) -> np.ndarray:
@@ -262,6 +263,11 @@ def fit_instances_ex(depth, K, masks=None, rles=None, polys=None, ground=None, s
     width) and the masks' frame is ``frame_width`` columns wide.  ``method``: "pca" | "convex_hull" (see ``fit_instances``).
     Returns a dict: boxes, status, aux, and stats / boxes2d when asked."""
     meth = _lib.method_code(method)   # (the reference's error for an unknown method, before any device work)
+    is16 = isinstance(depth, Depth16)   # 16-bit planes, fitted where they lie (C-ABI ``la3d_fit_instances_depth16``)
+    if is16:
+        _depth16_check(depth)
+        if frame_width is None and depth.frame_width:
+            frame_width = int(depth.frame_width)
     dev = _dev(device)
     if (masks is not None) + (rles is not None) + (polys is not None) != 1:
         raise ValueError("give exactly one of masks / rles / polys")
@@ -293,12 +299,16 @@ def fit_instances_ex(depth, K, masks=None, rles=None, polys=None, ground=None, s
         if frame_width is None:
             if W % 32 != 0:
                 with torch.cuda.device(dev):
-                    depth, fw = pad_depth_rows(depth, dev)
+                    if is16:
+                        _depth16_check(depth, (H, W), f"the {what} frame")
+                        depth, fw = _pad_rows16(depth, padded_width(W)), W
+                    else:
+                        depth, fw = pad_depth_rows(depth, dev)
                 W = padded_width(W)
         else:
             if int(frame_width) != W:
                 raise ValueError(f"frame_width {frame_width} does not match the {what} frame width {W}")
-            Wd = int(depth.shape[-1])
+            Wd = int((depth.data if is16 else depth).shape[-1])
             if Wd != W:
                 if Wd < W or Wd % 32 != 0:
                     raise ValueError("padded depth rows must be a multiple of 32 wide and at least frame_width")
@@ -324,11 +334,11 @@ def fit_instances_ex(depth, K, masks=None, rles=None, polys=None, ground=None, s
             if ah.numel() != B:
                 raise ValueError("area_hint must have one entry per instance")
             keep.append(ah)
-        a = _fit_args(B, H, W, _ptr(d), P, _ptr(k), k.shape[0], _ptr(f.boxes[0]), _ptr(f.status[0]), _ptr(f.aux[0]),
+        a = _fit_args(B, H, W, d if is16 else _ptr(d), P, _ptr(k), k.shape[0], _ptr(f.boxes[0]), _ptr(f.status[0]), _ptr(f.aux[0]),
                       _ptr(f.workspace[0]), _stream(stream), image_index=_ptr(ii), ground=_ptr(g), sample_idx=_ptr(si), filter=filter,
                       stats=_ptr(out.get("stats")), proj=_ptr(out.get("boxes2d")), image_size=image_size, area_hint=_ptr(ah),
                       opts=options.codes(), frame_width=fw, method=meth, **kind)
-        check(lib.la3d_fit_instances_ex(C.byref(a)), "la3d_fit_instances_ex")
+        _launch(a)
     _record(stream, d, k, ii, g, si, *keep, f.workspace, *out.values())
     return out
 
@@ -370,6 +380,7 @@ def fit_annotations(annotations, image_size, depth, K, ground=None, boundary_thr
     further device work, which is what a caller writing JSON wants.  Output buffers, workspace and the pinned buffer are kept per
     (B, H, W) between calls (the per-image pattern repeats a handful of shapes).  ``method``: "pca" | "convex_hull" (see
     ``fit_instances``)."""
+    refuse_depth16(depth, "fit_annotations")
     _lib.method_code(method)   # (the reference's error for an unknown method, before any device work)
     W_img, H_img = int(image_size[0]), int(image_size[1])
     dev = _dev(device)
@@ -469,6 +480,7 @@ def fit_annotations_all(annotations, image_size, depth, K, ground=None, image_in
     ``scale_threshold``, or True for the reference's 10 / 100) - the ones the keep rule drops carry status 6 and a NaN record.
     One launch per segmentation kind present; the segmentations are decoded / rasterised inside the fit kernel (no u8 plane
     exists anywhere).  This is the rank-local step of ``shard.fit_annotations_sharded``.  ``method``: "pca" | "convex_hull"."""
+    refuse_depth16(depth, "fit_annotations_all")
     _lib.method_code(method)   # (the reference's error for an unknown method, before any device work)
     W_img, H_img = int(image_size[0]), int(image_size[1])
     dev = _dev(device)
@@ -738,6 +750,9 @@ def fit_instances_bits(depth, bits, K, ground=None, sample_idx=None, image_index
     its rule for polygons); a bit plane does not say where it came from."""
     meth = _lib.method_code(method)   # (the reference's error for an unknown method, before any device work)
     flags = height_rule_code(height_rule)
+    is16 = isinstance(depth, Depth16)
+    if is16:
+        _depth16_check(depth)
     mb = _mask_bits(bits)
     dev = mb.bits.device if device is None else _dev(device)
     if mb.bits.device != dev:
@@ -745,12 +760,15 @@ def fit_instances_bits(depth, bits, K, ground=None, sample_idx=None, image_index
     B, H, W, fw = mb.bits.shape[0], mb.H, mb.W, mb.frame_width
     if frame_width is not None and int(frame_width) != fw:
         raise ValueError(f"frame_width {frame_width} does not match the bit planes' frame width {fw}")
-    Wd = int(depth.shape[-1])
+    Wd = int((depth.data if is16 else depth).shape[-1])
     if Wd != W:
         if Wd != fw or padded_width(fw) != W:
             raise ValueError(f"depth rows of {Wd} pixels match neither the stored width {W} nor the frame width {fw} of the bit planes")
         with torch.cuda.device(dev):
-            depth, _ = pad_depth_rows(depth, dev)
+            if is16:
+                depth = _pad_rows16(depth, W)
+            else:
+                depth, _ = pad_depth_rows(depth, dev)
     d, k, ii, g, si, P = _fit_inputs(depth, K, image_index, ground, sample_idx, B, H, W, dev, "the bit-plane frame")
     with torch.cuda.device(dev):
         f = InstanceFitter(B, H, W, dev, method=method)
@@ -764,13 +782,68 @@ def fit_instances_bits(depth, bits, K, ground=None, sample_idx=None, image_index
             ah = _as_dev(area_hint, torch.int32, dev).reshape(-1)
             if ah.numel() != B:
                 raise ValueError("area_hint must have one entry per instance")
-        a = _fit_args(B, H, W, _ptr(d), P, _ptr(k), k.shape[0], _ptr(f.boxes[0]), _ptr(f.status[0]), _ptr(f.aux[0]),
+        a = _fit_args(B, H, W, d if is16 else _ptr(d), P, _ptr(k), k.shape[0], _ptr(f.boxes[0]), _ptr(f.status[0]), _ptr(f.aux[0]),
                       _ptr(f.workspace[0]), _stream(stream), image_index=_ptr(ii), ground=_ptr(g), sample_idx=_ptr(si), filter=filter,
                       stats=_ptr(stats), proj=_ptr(boxes2d), image_size=image_size, area_hint=_ptr(ah), opts=options.codes(),
                       frame_width=0 if fw == W else fw, method=meth)
-        check(lib.la3d_fit_instances_bits(C.byref(a), _ptr(mb.bits), _bits_stride(mb.bits, B, H, W), flags), "la3d_fit_instances_bits")
+        _launch(a, (_ptr(mb.bits), _bits_stride(mb.bits, B, H, W), flags))
     _record(stream, d, k, ii, g, si, ah, mb.bits, f.workspace, *res)
     return res
+
+
+_D16_DTYPES = {"f16": (torch.float16, _lib.DTYPE_F16), "u16": (torch.uint16, _lib.DTYPE_U16)}
+
+
+def pack_depth16(depth, dtype: str = "f16", scale: float = 0.001, frame_pad: bool = False, device=None, stream=None, out=None) -> Depth16:
+    """(P,H,W) or (H,W) float32 depth -> ``Depth16`` on the GPU (C-ABI ``la3d_pack_depth16``).  ``dtype`` "f16": IEEE half, round to
+    nearest even, overflow to inf, subnormals kept (``astype(np.float16)``); "u16": ``rint(d / scale)`` in float32 - NaN, +-inf and
+    d <= 0 give 0 (a hole: the result has ``zero_is_hole=True``), more than 65535 units give 65535 -, ``scale`` metres per unit
+    (0.001: millimetres; ignored for "f16").  ``frame_pad``: rows of a width that is not a multiple of 32 are padded with zeros to
+    ``padded_width(W)`` (``frame_width`` of the result keeps W), which is what the tiled forms of the fit want with run-length /
+    polygon / bit-plane masks.  A device tensor with dense planes is read in place.  ``out``: a float16 / uint16 device tensor
+    (P,H,W_out) to fill, whose planes may lie further apart (only the words of each plane are written)."""
+    if dtype not in _D16_DTYPES:
+        raise ValueError(f"unknown dtype: {dtype!r}. Use 'f16' or 'u16'")
+    tdt, code = _D16_DTYPES[dtype]
+    if dtype == "u16" and not (np.isfinite(np.float32(scale)) and np.float32(scale) > 0):
+        raise ValueError(f"scale must be finite and > 0 (as float32), not {scale!r}")
+    if device is None and isinstance(depth, torch.Tensor) and depth.is_cuda:
+        device = depth.device
+    dev = _dev(device)
+    two_d = np.ndim(depth) == 2
+    x, ps = _plane_source(depth[None] if two_d else depth, dev, (torch.float32,))
+    P, H, W = x.shape
+    W_out = padded_width(W) if frame_pad else W
+    if out is None:
+        o = torch.empty((P, H, W_out), dtype=tdt, device=dev)
+    else:
+        o = out[None] if out.dim() == 2 else out
+        if not (o.is_cuda and o.dtype == tdt and tuple(o.shape) == (P, H, W_out)):
+            raise ValueError(f"out must be a {tdt} device tensor of shape {(P, H, W_out)}")
+        _depth16_block(Depth16(o), H, W_out)   # (dense rows, planes >= H*W_out elements apart)
+    with torch.cuda.device(dev):
+        check(lib.la3d_pack_depth16(_ptr(x), ps, P, H, W, W_out, code, float(scale), _ptr(o), int(o.stride(0)) if P > 1 else H * W_out,
+                                    _stream(stream)), "la3d_pack_depth16")
+    _record(stream, x, o)
+    return Depth16(o[0] if two_d else o, float(scale) if dtype == "u16" else 1.0, True, W if W_out != W else 0)
+
+
+def unpack_depth16(d16: Depth16, stream=None) -> torch.Tensor:
+    """``Depth16`` -> the float32 planes the fit sees, (P,H,W) or (H,W) like ``d16.data`` (the first ``frame_width`` columns when
+    the rows are padded), on the GPU (C-ABI ``la3d_unpack_depth16``): float32(x) for float16 planes, float32(x) * float32(scale)
+    for uint16 planes, a stored 0 as NaN with ``zero_is_hole``."""
+    if not isinstance(d16, Depth16):
+        raise ValueError("unpack_depth16 takes a Depth16")
+    _depth16_check(d16)
+    t = d16.data if d16.data.dim() == 3 else d16.data[None]
+    P, H, W_in = t.shape
+    blk = _depth16_block(d16._replace(data=t), H, W_in)
+    W = int(d16.frame_width) or W_in
+    out = torch.empty((P, H, W), dtype=torch.float32, device=t.device)
+    with torch.cuda.device(t.device):
+        check(lib.la3d_unpack_depth16(C.byref(blk), P, H, W_in, W, _ptr(out), _stream(stream)), "la3d_unpack_depth16")
+    _record(stream, t, out)
+    return out if d16.data.dim() == 3 else out[0]
 
 
 FRAME_DTYPE = np.dtype([("depth_offset", "<i8"), ("H", "<i4"), ("W", "<i4"), ("frame_width", "<i4"), ("reserved", "<i4")])
@@ -867,6 +940,8 @@ def fit_instances_frames(frames, K, rles=None, polys=None, image_index=None, gro
     back with status 5 and a NaN record - decided on the device, never an exception.  ``method="convex_hull"`` is not offered in
     this form (ValueError).  Returns the dict of ``fit_instances_ex``.  The size-balanced launch order of large batches runs when
     ``area_hint`` is given."""
+    refuse_depth16(frames, "fit_instances_frames")
+    refuse_depth16(getattr(frames, "depth", None), "fit_instances_frames")
     if _lib.method_code(method) != _lib.METHOD_PCA:   # (the reference's error for an unknown method; before any device work)
         raise ValueError("fit_instances_frames: method='convex_hull' is not supported for frames of different sizes; group by size and use fit_instances_ex")
     if not isinstance(frames, PackedFrames):

@@ -19,6 +19,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .batched import refuse_depth16
+
 
 def partition_contiguous(costs: Sequence[float], world: int) -> List[Tuple[int, int]]:
     """Split items 0..n-1 into ``world`` contiguous [start, end) ranges with balanced total cost
@@ -160,6 +162,7 @@ def fit_instances_sharded(depth, masks, K, image_index, ground=None, sample_idx=
     filled with this rank's ``load_s`` / ``fit_s`` / ``gather_s`` wall-clock seconds (the device is synchronised around each
     stage then, which a production call has no reason to do) and its shard.  ``method``: "pca" | "convex_hull", handed to
     ``fit_fn`` as a keyword when it is not "pca"."""
+    refuse_depth16(depth, "shard.fit_instances_sharded")
     _check_method(method)
     if fit_fn is None:
         from .batched import fit_instances as fit_fn
@@ -244,6 +247,7 @@ def fit_annotations_sharded(annotations, image_size, image_index, num_images: in
         return time.perf_counter()
     t0 = _sync()
     depth, K = depth_loader(sh)
+    refuse_depth16(depth, "shard.fit_annotations_sharded")
     t1 = _sync()
     n = sh.inst_hi - sh.inst_lo
     if n > 0:
