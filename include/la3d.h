@@ -390,7 +390,8 @@ int la3d_mask_stats_bits(const uint32_t* bits, int64_t bits_plane_stride, int B,
  *   - refused before any launch (LA3D_ERR_ARG): NULL block or NULL planes, a bad struct_size, a dtype other than F16 / U16,
  *     args->depth != NULL or depth_plane_stride != 0, a U16 scale that is not finite or <= 0, flags set for F16 or unknown flag
  *     bits, no mask source or two of them.
- * la3d_fit_instances_frames, la3d_fit_annotations_host and the positional entries take float32 planes only.
+ * la3d_fit_instances_frames takes float32 planes; its 16-bit form is la3d_fit_instances_frames_depth16 (below, "images of different
+ * sizes in one call").  la3d_fit_annotations_host and the positional entries take float32 planes only.
  *
  * Packers (streaming kernels; any plane stride, any element alignment):
  *   la3d_pack_depth16    depth dev f32, plane p at depth + p*plane_stride floats -> planes of H x W_out 16-bit words, out_plane_stride
@@ -418,7 +419,9 @@ int la3d_unpack_depth16(const la3d_depth16* src, int P, int H, int W_in, int W, 
  * Every entry above takes ONE (H, W) per call; a COCO shard comes in hundreds of frame sizes.  la3d_fit_instances_frames fits
  * instances of images of DIFFERENT sizes in one launch: the depth planes lie in one buffer, each at its own offset and pitch, and a
  * device-resident table says where - one la3d_frame row per IMAGE:
- *   depth_offset  floats from args->depth to the image's plane (>= 0, a multiple of 4: 16-byte aligned planes)
+ *   depth_offset  ELEMENTS of the depth buffer from its base to the image's plane, >= 0 and a multiple of 4: floats from
+ *                 args->depth for la3d_fit_instances_frames (16-byte aligned planes), 16-bit words from depth->planes for
+ *                 la3d_fit_instances_frames_depth16 (8-byte aligned planes)
  *   H, W          rows, and pixels per row IN MEMORY (the pitch), W % 32 == 0
  *   frame_width   image columns, 0 < frame_width <= W; the columns beyond are padding (what la3d_fit_args::frame_width says for a
  *                 uniform call, here per image)
@@ -446,14 +449,31 @@ int la3d_unpack_depth16(const la3d_depth16* src, int P, int H, int W_in, int W, 
  * Covered frames: EVERY frame inside the contract is fitted, small ones included (a frame of fewer than 64 tiles of 32 x 8 pixels,
  * the floor of the uniform entry's tiled form, is fitted too: the call's LDS is sized for at least 64 tiles whatever the bounds).
  * A call whose bounds exceed what the tiled form holds (H > 2040, W > 8160, or - subsample mode - a bit image + rank prefix beyond
- * one workgroup's LDS) returns LA3D_ERR_UNSUPPORTED as a whole. */
+ * one workgroup's LDS) returns LA3D_ERR_UNSUPPORTED as a whole.
+ *
+ * la3d_fit_instances_frames_depth16(args, depth, frames, P): the same call on 16-bit depth planes ("16-bit depth planes" above) - a
+ * shard of sensor or network depth in many frame sizes, fitted where it lies: no float32 copy is made or read.  args and frames mean
+ * what they mean in la3d_fit_instances_frames, depth what it means in la3d_fit_instances_depth16, except:
+ *   - args->depth must be NULL and args->depth_plane_stride 0; depth->plane_stride must be 0 (the frame table says where every plane
+ *     lies); depth->planes is the base of the ragged buffer and must be 8-byte aligned;
+ *   - la3d_frame::depth_offset counts 16-BIT ELEMENTS from depth->planes; a multiple of 4 is then an 8-byte aligned plane, which is what
+ *     the 16-bit vector forms need.  The on-device contract check is the same one (a depth_offset of 2 - 4 bytes - is refused with
+ *     LA3D_BOX_UNSUPPORTED like any other misaligned row); a conforming row addresses H * W 16-bit words from depth_offset on;
+ *   - the value rules are those of the 16-bit planes, unchanged: exact float16, ONE rounded float32(x) * scale, LA3D_DEPTH_ZERO_IS_HOLE.
+ *     A call gives the records la3d_fit_instances_frames gives on the up-converted planes in the same layout, bit for bit.
+ * Refused before any launch (LA3D_ERR_ARG / LA3D_ERR_UNSUPPORTED) is what either parent entry refuses: a bad block or la3d_depth16
+ * (struct_size, dtype, scale, flags), a non-zero plane_stride, a misaligned base, u8 or bit-plane masks, LA3D_METHOD_CONVEX_HULL, a
+ * missing image_index, a non-zero depth_plane_stride or frame_width in the block, bounds beyond the tiled form.  Workspace:
+ * la3d_fit_workspace_bytes(args). */
 typedef struct la3d_frame {      /* one row per IMAGE, device-resident */
-  int64_t depth_offset;          /* floats from args->depth to this image's plane; % 4 == 0 */
+  int64_t depth_offset;          /* elements from the base of the depth buffer to this image's plane, % 4 == 0: floats from args->depth
+                                    (la3d_fit_instances_frames), 16-bit words from depth->planes (la3d_fit_instances_frames_depth16) */
   int32_t H, W;                  /* rows; pixels per row IN MEMORY (the pitch), W % 32 == 0 */
   int32_t frame_width;           /* image columns, 0 < frame_width <= W; columns beyond are padding */
   int32_t reserved;              /* 0 */
 } la3d_frame;
 int la3d_fit_instances_frames(const la3d_fit_args* args, const la3d_frame* frames, int32_t P);
+int la3d_fit_instances_frames_depth16(const la3d_fit_args* args, const la3d_depth16* depth, const la3d_frame* frames, int32_t P);
 
 /* create_boolean_mask_from_polygon for a batch: polygon parts -> u8 planes mask_out dev [B][H*W] (0/1). */
 int la3d_poly_decode(const int32_t* poly_xy, const int64_t* ring_offsets, const int64_t* inst_rings, int B, int H, int W,

@@ -51,6 +51,7 @@ class Frame(C.Structure):
 _SIGS = {
     "la3d_fit_instances_ex": (C.c_int, [C.POINTER(FitArgs)]),
     "la3d_fit_instances_frames": (C.c_int, [C.POINTER(FitArgs), C.c_void_p, C.c_int32]),
+    "la3d_fit_instances_frames_depth16": (C.c_int, [C.POINTER(FitArgs), C.POINTER(Depth16Block), C.c_void_p, C.c_int32]),
     "la3d_fit_workspace_bytes": (C.c_size_t, [C.POINTER(FitArgs)]),
     "la3d_fit_instances_bits": (C.c_int, [C.POINTER(FitArgs), C.c_void_p, C.c_int64, C.c_int32]),
     "la3d_fit_instances_depth16": (C.c_int, [C.POINTER(FitArgs), C.POINTER(Depth16Block), C.c_void_p, C.c_int64, C.c_int32]),

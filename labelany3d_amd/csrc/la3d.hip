@@ -182,7 +182,8 @@ struct Depth16Source { const la3d_depth16* d; };                                
 // always; la3d_fit_instances_ex when filter_boundary >= 0 and filter_max_edge > 0).  who: the entry named in la3d_last_error().
 // bs: the bit planes of la3d_fit_instances_bits (an internal parameter: the public block is frozen), null for every other entry.
 // fr: the frame table of la3d_fit_instances_frames (H, W of the block are then bounds), null for every other entry.
-// ds: the 16-bit depth planes of la3d_fit_instances_depth16 (a.depth is then null), null for every other entry.
+// ds: the 16-bit depth planes of la3d_fit_instances_depth16 (a.depth is then null), null for every other entry but
+// la3d_fit_instances_frames_depth16, which gives fr AND ds: the frame rows then count their depth_offset in 16-bit elements.
 static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who, const BitsSource* bs = nullptr,
                         const FramesSource* fr = nullptr, const Depth16Source* ds = nullptr) {
   const int B = a.B;
@@ -282,9 +283,10 @@ static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who,
   const int pin = a.opt_engine != LA3D_ENGINE_DEFAULT ? a.opt_engine : config().engine;   // per-call pin, else the process default
   hipStream_t s = static_cast<hipStream_t>(a.stream);
   // frames of different sizes: the instance engine at every batch size (no other engine reads a frame table); pins give way
-  if (fr) return instance_fit(p, f, s, a.workspace, who);
+  if (fr && !ds) return instance_fit(p, f, s, a.workspace, who);
   if (ds) {
     // 16-bit depth planes: the instance engine at every batch size (no other engine has a 16-bit form); pins give way
+    // (with a frame table - la3d_fit_instances_frames_depth16 - the 16-bit units launch their FRAMES instantiations: f.frames)
     FitParams16 q;
     static_cast<FitParams&>(q) = p;
     q.depth16 = static_cast<const unsigned short*>(ds->d->planes);
@@ -477,31 +479,55 @@ int la3d_fit_instances_bits(const la3d_fit_args* args, const uint32_t* mask_bits
   return fit_dispatch(a, a.filter_boundary >= 0 && a.filter_max_edge > 0, "la3d_fit_instances_bits", &bs);
 }
 
-int la3d_fit_instances_depth16(const la3d_fit_args* args, const la3d_depth16* depth, const uint32_t* mask_bits,
-                               int64_t bits_plane_stride, int32_t bits_flags) {
+// what la3d_fit_instances_depth16 and la3d_fit_instances_frames_depth16 check alike, in two steps (the entry copies its block between
+// them): the two blocks and the planes pointer, then the value rule of the la3d_depth16 block
+static int depth16_block_head(const la3d_fit_args* args, const la3d_depth16* depth, const char* who) {
   constexpr int32_t V1_SIZE = (int32_t)offsetof(la3d_fit_args, area_hint);
   static_assert(sizeof(la3d_depth16) == 32, "la3d_depth16 is part of the ABI");
-  const char* who = "la3d_fit_instances_depth16";
   if (!args || args->struct_size < V1_SIZE) {
-    set_err("la3d_fit_instances_depth16: bad struct_size");
+    snprintf(g_err, sizeof(g_err), "%s: bad struct_size", who);
     return LA3D_ERR_ARG;
   }
   if (!depth) {
-    set_err("la3d_fit_instances_depth16: depth (the la3d_depth16 block) is NULL");
+    snprintf(g_err, sizeof(g_err), "%s: depth (the la3d_depth16 block) is NULL", who);
     return LA3D_ERR_ARG;
   }
   if (depth->struct_size < (int32_t)sizeof(la3d_depth16)) {
-    set_err("la3d_fit_instances_depth16: bad struct_size of la3d_depth16");
+    snprintf(g_err, sizeof(g_err), "%s: bad struct_size of la3d_depth16", who);
     return LA3D_ERR_ARG;
   }
   if (depth->dtype != LA3D_DTYPE_F16 && depth->dtype != LA3D_DTYPE_U16) {
-    set_err("la3d_fit_instances_depth16: unknown dtype (LA3D_DTYPE_F16 or LA3D_DTYPE_U16)");
+    snprintf(g_err, sizeof(g_err), "%s: unknown dtype (LA3D_DTYPE_F16 or LA3D_DTYPE_U16)", who);
     return LA3D_ERR_ARG;
   }
   if (!depth->planes || (reinterpret_cast<uintptr_t>(depth->planes) & 1)) {
-    set_err("la3d_fit_instances_depth16: planes must be a 2-byte aligned device pointer");
+    snprintf(g_err, sizeof(g_err), "%s: planes must be a 2-byte aligned device pointer", who);
     return LA3D_ERR_ARG;
   }
+  return LA3D_SUCCESS;
+}
+static int depth16_block_values(const la3d_depth16* depth, const char* who) {
+  if (depth->dtype == LA3D_DTYPE_U16) {
+    if (!(depth->scale > 0.0f && depth->scale <= 3.4028234663852886e38f)) {   // (false for NaN)
+      snprintf(g_err, sizeof(g_err), "%s: the scale of LA3D_DTYPE_U16 planes must be finite and > 0", who);
+      return LA3D_ERR_ARG;
+    }
+    if (depth->flags & ~(int32_t)LA3D_DEPTH_ZERO_IS_HOLE) {
+      snprintf(g_err, sizeof(g_err), "%s: unknown flags (LA3D_DEPTH_ZERO_IS_HOLE or 0)", who);
+      return LA3D_ERR_ARG;
+    }
+  } else if (depth->flags != 0) {
+    snprintf(g_err, sizeof(g_err), "%s: flags must be 0 for LA3D_DTYPE_F16 planes", who);
+    return LA3D_ERR_ARG;
+  }
+  return LA3D_SUCCESS;
+}
+
+int la3d_fit_instances_depth16(const la3d_fit_args* args, const la3d_depth16* depth, const uint32_t* mask_bits,
+                               int64_t bits_plane_stride, int32_t bits_flags) {
+  const char* who = "la3d_fit_instances_depth16";
+  int rc = depth16_block_head(args, depth, who);
+  if (rc != LA3D_SUCCESS) return rc;
   la3d_fit_args a;
   memset(&a, 0, sizeof(a));
   memcpy(&a, args, (size_t)args->struct_size < sizeof(a) ? (size_t)args->struct_size : sizeof(a));
@@ -509,19 +535,8 @@ int la3d_fit_instances_depth16(const la3d_fit_args* args, const la3d_depth16* de
     set_err("la3d_fit_instances_depth16: the depth planes come in the la3d_depth16 block - args->depth must be NULL and depth_plane_stride 0");
     return LA3D_ERR_ARG;
   }
-  if (depth->dtype == LA3D_DTYPE_U16) {
-    if (!(depth->scale > 0.0f && depth->scale <= 3.4028234663852886e38f)) {   // (false for NaN)
-      set_err("la3d_fit_instances_depth16: the scale of LA3D_DTYPE_U16 planes must be finite and > 0");
-      return LA3D_ERR_ARG;
-    }
-    if (depth->flags & ~(int32_t)LA3D_DEPTH_ZERO_IS_HOLE) {
-      set_err("la3d_fit_instances_depth16: unknown flags (LA3D_DEPTH_ZERO_IS_HOLE or 0)");
-      return LA3D_ERR_ARG;
-    }
-  } else if (depth->flags != 0) {
-    set_err("la3d_fit_instances_depth16: flags must be 0 for LA3D_DTYPE_F16 planes");
-    return LA3D_ERR_ARG;
-  }
+  rc = depth16_block_values(depth, who);
+  if (rc != LA3D_SUCCESS) return rc;
   if (depth->plane_stride < 0 || (depth->plane_stride != 0 && a.H > 0 && a.W > 0 && depth->plane_stride < (int64_t)a.H * a.W)) {
     set_err("la3d_fit_instances_depth16: plane_stride must be 0 (one shared plane) or >= H*W elements");
     return LA3D_ERR_ARG;
@@ -549,16 +564,50 @@ int la3d_fit_instances_depth16(const la3d_fit_args* args, const la3d_depth16* de
       return LA3D_ERR_ARG;
     }
   }
-  const int rc = check_block_options(a, who);
+  rc = check_block_options(a, who);
   if (rc != LA3D_SUCCESS) return rc;
   const BitsSource bs{mask_bits, bits_plane_stride, bits_flags};
   const Depth16Source ds{depth};
   return fit_dispatch(a, a.filter_boundary >= 0 && a.filter_max_edge > 0, who, mask_bits ? &bs : nullptr, nullptr, &ds);
 }
 
+// what la3d_fit_instances_frames and la3d_fit_instances_frames_depth16 check alike on the copied block and the frame table
+static int check_frames_call(la3d_fit_args& a, const la3d_frame* frames, int32_t P, const char* who) {
+  static_assert(sizeof(la3d_frame) == 24, "la3d_frame is part of the ABI");
+  if (a.mask) {
+    snprintf(g_err, sizeof(g_err), "%s: u8 mask planes are not supported - run lengths or polygon parts", who);
+    return LA3D_ERR_UNSUPPORTED;
+  }
+  if (a.method == LA3D_METHOD_CONVEX_HULL) {
+    snprintf(g_err, sizeof(g_err), "%s: method = LA3D_METHOD_CONVEX_HULL is not supported in this form", who);
+    return LA3D_ERR_UNSUPPORTED;
+  }
+  const int kinds = (a.rle_counts ? 1 : 0) + (a.poly_xy ? 1 : 0);
+  if (kinds != 1 && a.B > 0) {
+    snprintf(g_err, sizeof(g_err), "%s: give exactly one of rle_counts / poly_xy", who);
+    return LA3D_ERR_ARG;
+  }
+  if (a.poly_xy && (!a.ring_offsets || !a.inst_rings)) {
+    snprintf(g_err, sizeof(g_err), "%s: polygon masks need ring_offsets and inst_rings", who);
+    return LA3D_ERR_ARG;
+  }
+  if (P < 0 || (a.B > 0 && (!frames || P == 0 || (reinterpret_cast<uintptr_t>(frames) & 7)))) {
+    snprintf(g_err, sizeof(g_err), "%s: frames must be an 8-byte aligned device pointer to P >= 1 rows", who);
+    return LA3D_ERR_ARG;
+  }
+  if (a.B > 0 && !a.image_index) {
+    snprintf(g_err, sizeof(g_err), "%s: image_index is required (instance n belongs to frame row image_index[n])", who);
+    return LA3D_ERR_ARG;
+  }
+  if (a.depth_plane_stride != 0 || a.frame_width != 0) {
+    snprintf(g_err, sizeof(g_err), "%s: depth_plane_stride and frame_width must be 0 (the frame table holds them per image)", who);
+    return LA3D_ERR_ARG;
+  }
+  return LA3D_SUCCESS;
+}
+
 int la3d_fit_instances_frames(const la3d_fit_args* args, const la3d_frame* frames, int32_t P) {
   constexpr int32_t V1_SIZE = (int32_t)offsetof(la3d_fit_args, area_hint);
-  static_assert(sizeof(la3d_frame) == 24, "la3d_frame is part of the ABI");
   if (!args || args->struct_size < V1_SIZE) {
     set_err("la3d_fit_instances_frames: bad struct_size");
     return LA3D_ERR_ARG;
@@ -566,44 +615,50 @@ int la3d_fit_instances_frames(const la3d_fit_args* args, const la3d_frame* frame
   la3d_fit_args a;
   memset(&a, 0, sizeof(a));
   memcpy(&a, args, (size_t)args->struct_size < sizeof(a) ? (size_t)args->struct_size : sizeof(a));
-  if (a.mask) {
-    set_err("la3d_fit_instances_frames: u8 mask planes are not supported - run lengths or polygon parts");
-    return LA3D_ERR_UNSUPPORTED;
-  }
-  if (a.method == LA3D_METHOD_CONVEX_HULL) {
-    set_err("la3d_fit_instances_frames: method = LA3D_METHOD_CONVEX_HULL is not supported in this form");
-    return LA3D_ERR_UNSUPPORTED;
-  }
-  const int kinds = (a.rle_counts ? 1 : 0) + (a.poly_xy ? 1 : 0);
-  if (kinds != 1 && a.B > 0) {
-    set_err("la3d_fit_instances_frames: give exactly one of rle_counts / poly_xy");
-    return LA3D_ERR_ARG;
-  }
-  if (a.poly_xy && (!a.ring_offsets || !a.inst_rings)) {
-    set_err("la3d_fit_instances_frames: polygon masks need ring_offsets and inst_rings");
-    return LA3D_ERR_ARG;
-  }
-  if (P < 0 || (a.B > 0 && (!frames || P == 0 || (reinterpret_cast<uintptr_t>(frames) & 7)))) {
-    set_err("la3d_fit_instances_frames: frames must be an 8-byte aligned device pointer to P >= 1 rows");
-    return LA3D_ERR_ARG;
-  }
-  if (a.B > 0 && !a.image_index) {
-    set_err("la3d_fit_instances_frames: image_index is required (instance n belongs to frame row image_index[n])");
-    return LA3D_ERR_ARG;
-  }
-  if (a.depth_plane_stride != 0 || a.frame_width != 0) {
-    set_err("la3d_fit_instances_frames: depth_plane_stride and frame_width must be 0 (the frame table holds them per image)");
-    return LA3D_ERR_ARG;
-  }
+  int rc = check_frames_call(a, frames, P, "la3d_fit_instances_frames");
+  if (rc != LA3D_SUCCESS) return rc;
   if (reinterpret_cast<uintptr_t>(a.depth) & 15) {
     set_err("la3d_fit_instances_frames: depth must be 16-byte aligned");
     return LA3D_ERR_ARG;
   }
   a.image_width = a.image_height = 1.0;   // (ignored: proj clamps to the instance's own frame)
-  const int rc = check_block_options(a, "la3d_fit_instances_frames");
+  rc = check_block_options(a, "la3d_fit_instances_frames");
   if (rc != LA3D_SUCCESS) return rc;
   const FramesSource fs{frames, P};
   return fit_dispatch(a, a.filter_boundary >= 0 && a.filter_max_edge > 0, "la3d_fit_instances_frames", nullptr, &fs);
+}
+
+// the frames call on 16-bit planes: the checks of both parents, then fit_dispatch with both sources (it launches the FRAMES
+// instantiations of the 16-bit units); depth_offset of the frame rows counts 16-bit ELEMENTS
+int la3d_fit_instances_frames_depth16(const la3d_fit_args* args, const la3d_depth16* depth, const la3d_frame* frames, int32_t P) {
+  const char* who = "la3d_fit_instances_frames_depth16";
+  int rc = depth16_block_head(args, depth, who);
+  if (rc != LA3D_SUCCESS) return rc;
+  la3d_fit_args a;
+  memset(&a, 0, sizeof(a));
+  memcpy(&a, args, (size_t)args->struct_size < sizeof(a) ? (size_t)args->struct_size : sizeof(a));
+  if (a.depth) {
+    snprintf(g_err, sizeof(g_err), "%s: the depth planes come in the la3d_depth16 block - args->depth must be NULL", who);
+    return LA3D_ERR_ARG;
+  }
+  rc = depth16_block_values(depth, who);
+  if (rc != LA3D_SUCCESS) return rc;
+  if (depth->plane_stride != 0) {
+    snprintf(g_err, sizeof(g_err), "%s: plane_stride of the la3d_depth16 block must be 0 (the frame table says where every plane lies)", who);
+    return LA3D_ERR_ARG;
+  }
+  rc = check_frames_call(a, frames, P, who);
+  if (rc != LA3D_SUCCESS) return rc;
+  if (reinterpret_cast<uintptr_t>(depth->planes) & 7) {
+    snprintf(g_err, sizeof(g_err), "%s: planes (the base of the ragged buffer) must be 8-byte aligned", who);
+    return LA3D_ERR_ARG;
+  }
+  a.image_width = a.image_height = 1.0;   // (ignored: proj clamps to the instance's own frame)
+  rc = check_block_options(a, who);
+  if (rc != LA3D_SUCCESS) return rc;
+  const FramesSource fs{frames, P};
+  const Depth16Source ds{depth};
+  return fit_dispatch(a, a.filter_boundary >= 0 && a.filter_max_edge > 0, who, nullptr, &fs, &ds);
 }
 
 }  // extern "C"

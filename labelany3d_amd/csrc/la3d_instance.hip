@@ -53,6 +53,13 @@ __device__ inline DepthCvt<DepthT> depth_cvt(const FitParams16& call) {
 #endif
   return cv;
 }
+// the depth_offset of a frame row that frame_geometry has accepted (wave-uniform: scalar registers).  A second load of the word
+// frame_geometry checked - FitParams has no field to carry it in, and does not grow for it: the frame table is an INPUT of the call,
+// which nothing writes while the call runs (include/la3d.h: frames), so both loads see the same value
+__device__ inline long long frame_depth_offset(const FitParams& call, int img) {
+  const long long off_v = call.frames[img].depth_offset;
+  return ((long long)__builtin_amdgcn_readfirstlane((int)(off_v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)off_v);
+}
 #endif
 // ------------------------------------------------------------------------------------------
 // instance engine: one workgroup per instance
@@ -103,14 +110,13 @@ __device__ inline void sweep_sep_hull(const FitParams& p, const DepthT* __restri
 // HULL: the instantiations of a convex-hull call (la3d_fit_args::method) - everything a PCA call does up to
 // and including the axis, then, instead of extents and record, the hand-off of hull_finish_kernel through the workspace (p.geo
 // points at the call's hand-off area).  Every difference sits behind the constant HULL: the PCA instantiations (HULL = false) compile to the code they were.
-// FRAMES: the instantiations of la3d_fit_instances_frames - images of different sizes in one call.  The kernel argument then holds
-// the call's sizing bounds; once the workgroup knows its instance and image it reads the image's la3d_frame row and replaces the
+// FRAMES: the instantiations of la3d_fit_instances_frames (in the 16-bit units: of la3d_fit_instances_frames_depth16) - images of
+// different sizes in one call.  The kernel argument then holds the call's sizing bounds; once the workgroup knows its instance and image it reads the image's la3d_frame row and replaces the
 // frame geometry in ITS copy of the parameters (frame_geometry, la3d_device.hpp), which everything below reads.  Every difference sits behind the
 // constant FRAMES: the other instantiations read the kernel argument itself, as they did.
 template <bool VEC, bool LDSMASK, bool SAMPLE, bool TILED, int SRC, bool HULL = false, bool FRAMES = false>
 __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const KParams p_call) {
   static_assert(!FRAMES || (VEC && LDSMASK && TILED && !HULL && (SRC == 1 || SRC == 2)), "frames calls: run lengths / polygons, tiled form");
-  static_assert(!FRAMES || LA3D_INSTANCE_DT == 0, "frames calls: float32 planes");
   FitParams p_frame;   // FRAMES only: this workgroup's parameters (dead otherwise)
   if constexpr (FRAMES) p_frame = p_call;
   const FitParams& p_block = p_call;
@@ -166,6 +172,12 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const KParam
   }
   const int HW = p.HW;
   const DepthT* dpl = depth_planes(p, p_call) + (long long)img * p.depth_plane_stride;
+#if LA3D_INSTANCE_DT != 0
+  // frames call on 16-bit planes (la3d_fit_instances_frames_depth16): depth_planes() is the base of the ragged buffer and the frame
+  // row's depth_offset - which has passed frame_geometry's check above: >= 0, % 4 == 0, so the plane is 8-byte aligned - counts
+  // ELEMENTS of it (frame_geometry left depth_plane_stride 0; its p.depth is not read in these units)
+  if constexpr (FRAMES) dpl += frame_depth_offset(p_call, img);
+#endif
   const DepthCvt<DepthT> cv = depth_cvt(p_call);
   const unsigned char* mpl = p.mask ? p.mask + (long long)inst * HW : nullptr;
 
@@ -992,16 +1004,11 @@ int launch_fit(const KParams& p, size_t lds, hipStream_t s, void* workspace = nu
 }
 
 
-// la3d_fit_instances_frames: run lengths or polygon parts, the tiled form (full-mask or subsample)
+// la3d_fit_instances_frames / la3d_fit_instances_frames_depth16: run lengths or polygon parts, the tiled form (full-mask or subsample)
 template <bool SAMPLE>
 int launch_fit_frames(const KParams& p, size_t lds, hipStream_t s, void* workspace) {
-#if LA3D_INSTANCE_DT == 0
   if (p.rle_counts != nullptr) return launch_fit_inst<true, true, SAMPLE, true, 1, true>(p, lds, s, workspace);
   return launch_fit_inst<true, true, SAMPLE, true, 2, true>(p, lds, s, workspace);
-#else
-  set_err("frames of different sizes: float32 depth planes only");   // (never reached: the 16-bit entry has no frame table)
-  return LA3D_ERR_UNSUPPORTED;
-#endif
 }
 
 }  // namespace

@@ -40,9 +40,9 @@ import numpy as np
 import torch
 
 from ._lib import lib, method_code
-from .batched import _dev, _upload_many, draw_sample_idx, refuse_depth16
+from .batched import Depth16, _dev, _upload_many, draw_sample_idx, refuse_depth16
 from .jsonout import SceneRecords, format_scenes
-from .masks import (PackedFrames, fit_instances_ex, fit_instances_frames, frame_table, mask_stats_poly, mask_stats_rle, pack_polygons, pack_rle,
+from .masks import (PackedFrames, PackedFrames16, fit_instances_ex, fit_instances_frames, frame_table, mask_stats_poly, mask_stats_rle, pack_polygons, pack_rle,
                     pack_rle_frames, pad_depth_rows, padded_width)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -113,17 +113,46 @@ def scenes_from_disk(scenes_dir: str, annotations, start_index: int = 0, end_ind
                "annotations": by_image.get(im["id"], []), "names": names}
 
 
-def _load_scene(scene: dict, depth_out: np.ndarray, k_out: np.ndarray) -> None:
-    """depth plane and K of one scene into row slots of the batch's pinned buffers (runs on a loader thread)."""
+DEPTH_DTYPES = {"f16": (np.dtype(np.float16), torch.float16), "u16": (np.dtype(np.uint16), torch.uint16)}
+"""``depth_dtype`` of ``ScenePipeline`` / ``synthetic_scenes`` -> (the NumPy dtype the scenes' depth must have, the torch dtype it keeps)."""
+
+
+def quantise_depth(depth, depth_dtype: str, scale: float = 0.001) -> np.ndarray:
+    """float32 depth -> the 16-bit planes a sensor / a half-precision network would have stored, in plain NumPy: "f16" =
+    ``astype(np.float16)``; "u16" = ``rint(d / scale)`` in float32, NaN / +-inf / d <= 0 -> 0 (a hole), more than 65535 units -> 65535
+    (the rule of ``pack_depth16``)."""
+    d32 = np.asarray(depth, np.float32)
+    if depth_dtype == "f16":
+        with np.errstate(over="ignore"):
+            return d32.astype(np.float16)
+    if depth_dtype != "u16":
+        raise ValueError(f"unknown depth_dtype: {depth_dtype!r}. Use 'f16' or 'u16'")
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        q = np.rint(d32 / np.float32(scale))
+        q = np.where(np.isfinite(d32) & (d32 > 0), np.minimum(q, np.float32(65535)), np.float32(0))
+    return q.astype(np.uint16)
+
+
+def _host_view(t: torch.Tensor) -> np.ndarray:
+    """the NumPy view of a host tensor (uint16 through its int16 bit patterns)"""
+    return t.view(torch.int16).numpy().view(np.uint16) if t.dtype == torch.uint16 else t.numpy()
+
+
+def _load_scene(scene: dict, depth_out: np.ndarray, k_out: np.ndarray, want: Optional[np.dtype] = None) -> None:
+    """depth plane and K of one scene into row slots of the batch's pinned buffers (runs on a loader thread).  ``want``: the 16-bit
+    dtype the pipeline was built for (``depth_dtype``) - the scene's depth must then be a host array of exactly that dtype."""
     if "depth" in scene:
         d, K = scene["depth"], scene["K"]
     else:
         d = np.load(os.path.join(scene["dir"], "depth_map.npy"))
         with open(os.path.join(scene["dir"], "cam_params.json")) as f:
             K = json.load(f)["K"]
+    if want is not None and not (isinstance(d, np.ndarray) and d.dtype == want):
+        raise ValueError(f"{scene['name']}: the pipeline was built with depth_dtype={'f16' if want == np.float16 else 'u16'!r} and takes host "
+                         f"arrays of {want.name}; this scene's depth is {getattr(d, 'dtype', type(d).__name__)}")
     if d.shape != depth_out.shape:
         raise ValueError(f"{scene['name']}: depth_map {d.shape} does not match the image size {depth_out.shape} of the annotation file")
-    if isinstance(d, np.ndarray) and d.dtype == np.float32 and d.flags.c_contiguous and depth_out.flags.c_contiguous:
+    if isinstance(d, np.ndarray) and d.dtype == (np.float32 if want is None else want) and d.flags.c_contiguous and depth_out.flags.c_contiguous:
         # one memmove through ctypes: foreign calls release the GIL, np.copyto does not for this case - sixteen loader threads then
         # copy in PARALLEL instead of taking turns (round 5: the staging copies ran at 21 GB/s in aggregate, 1.3 GB/s per thread)
         C.memmove(depth_out.ctypes.data, d.ctypes.data, d.nbytes)
@@ -178,12 +207,26 @@ class ScenePipeline:
 
     def __init__(self, device=None, batch_images: int = 256, subsample: bool = False, boundary_threshold: int = 10,
                  scale_threshold: int = 100, loader_threads: int = 16, write: bool = True, out_name: str = OUT_NAME, rng=None,
-                 timings: Optional[dict] = None, method: str = "pca", mixed_frames: bool = False):
+                 timings: Optional[dict] = None, method: str = "pca", mixed_frames: bool = False, depth_dtype: Optional[str] = None,
+                 depth_scale: float = 0.001, depth_zero_is_hole: bool = True):
         """``method``: "pca" | "convex_hull" - the reference's ``bbox_method`` (save_3d_with_ground_alignment_bbox); see
         ``fit_instances`` for what the hull method covers in full-mask mode.  ``mixed_frames``: batches hold images of DIFFERENT
         sizes in arrival order, ``batch_images`` each, and every batch is one frames call per annotation kind
-        (``fit_instances_frames``) instead of one call per frame size ("pca" only).  Off: batches are keyed by frame size."""
+        (``fit_instances_frames``) instead of one call per frame size ("pca" only).  Off: batches are keyed by frame size.
+        ``depth_dtype`` "f16" / "u16": every scene's depth (``scene["depth"]`` or its ``depth_map.npy``) is a host array of
+        ``np.float16`` / ``np.uint16`` (anything else: ValueError naming the scene) and stays 16-bit all the way - pinned staging,
+        upload, device buffer, fit (``PackedFrames16`` in mixed mode, a padded ``Depth16`` otherwise): half the bytes over the host
+        link, the records of the float32 pipeline on the up-converted planes.  ``depth_scale`` / ``depth_zero_is_hole``: the value
+        rule of uint16 planes (``Depth16``)."""
         method_code(method)   # (the reference's error for an unknown method, before any device work)
+        if depth_dtype is not None and depth_dtype not in DEPTH_DTYPES:
+            raise ValueError(f"unknown depth_dtype: {depth_dtype!r}. Use None (float32), 'f16' or 'u16'")
+        if depth_dtype == "u16" and not (np.isfinite(np.float32(depth_scale)) and np.float32(depth_scale) > 0):
+            raise ValueError(f"depth_scale must be finite and > 0 (as float32), not {depth_scale!r}")
+        self.depth_dtype = depth_dtype
+        self.depth_scale = float(depth_scale) if depth_dtype == "u16" else 1.0
+        self.depth_hole = bool(depth_zero_is_hole)
+        self._np16, self._t16 = DEPTH_DTYPES[depth_dtype] if depth_dtype is not None else (None, None)
         if mixed_frames and method != "pca":
             raise ValueError("mixed_frames fits with method='pca' only (the frames call has no convex-hull form)")
         self.method = method
@@ -206,8 +249,9 @@ class ScenePipeline:
         ev = self._busy.get(parity)
         if ev is not None:
             ev.synchronize()   # the upload that last read this ring slot's buffers (three batches ago) has long finished; make it certain
-        flat = _pinned_bytes(("depth", parity), P * H * W * 4)
-        return flat[:P * H * W * 4].view(torch.float32).view(P, H, W), _pinned_rows(("K", parity), P, (9,), torch.float64)
+        esize, tdt = (4, torch.float32) if self._t16 is None else (2, self._t16)
+        flat = _pinned_bytes(("depth", parity), P * H * W * esize)
+        return flat[:P * H * W * esize].view(tdt).view(P, H, W), _pinned_rows(("K", parity), P, (9,), torch.float64)
 
     def _prepare_mixed(self, scenes: List[dict], parity: int) -> _Prepared:
         """``_prepare`` for a batch of images of different sizes: the depth planes go into ONE ragged pinned buffer (each at its own
@@ -222,9 +266,10 @@ class ScenePipeline:
         ev = self._busy.get(parity)
         if ev is not None:
             ev.synchronize()
-        dpin = _pinned_bytes(("depth", parity), total * 4)[:total * 4].view(torch.float32)
+        esize, tdt = (4, torch.float32) if self._t16 is None else (2, self._t16)   # (the table counts ELEMENTS either way)
+        dpin = _pinned_bytes(("depth", parity), total * esize)[:total * esize].view(tdt)
         kpin = _pinned_rows(("K", parity), P, (9,), torch.float64)
-        dnp, knp = dpin.numpy(), kpin.numpy()
+        dnp, knp = _host_view(dpin), kpin.numpy()
         nthr = max(1, min(self.pool._max_workers, P))
         cuts = [P * t // nthr for t in range(nthr + 1)]
 
@@ -232,8 +277,8 @@ class ScenePipeline:
             for i in range(cuts[t], cuts[t + 1]):
                 o, h, wp, w = int(table["depth_offset"][i]), int(table["H"][i]), int(table["W"][i]), int(table["frame_width"][i])
                 plane = dnp[o:o + h * wp].reshape(h, wp)
-                _load_scene(scenes[i], plane[:, :w], knp[i])
-                plane[:, w:] = 0.0
+                _load_scene(scenes[i], plane[:, :w], knp[i], self._np16)
+                plane[:, w:] = 0
         loads = [self.pool.submit(load_range, t) for t in range(nthr)]
         tp0 = time.perf_counter()
         groups = {"rle": {"seg": [], "img": [], "ann": [], "area": [], "cat": []}, "poly": {"seg": [], "img": [], "ann": [], "area": [], "cat": []}}
@@ -268,14 +313,19 @@ class ScenePipeline:
         for f in loads:
             f.result()
         pr.t_load = time.perf_counter() - t0
-        pr.nbytes = total * 4
+        pr.nbytes = total * esize
         with torch.cuda.stream(self.copy_stream):
             pr.h2d0 = torch.cuda.Event(enable_timing=True)
             pr.h2d0.record(self.copy_stream)
-            depth = torch.empty((total,), dtype=torch.float32, device=self.dev)
-            depth.copy_(dpin, non_blocking=True)
             words = torch.as_tensor(np.ascontiguousarray(table).view(np.int32).reshape(P, 6).copy(), device=self.dev)
-            pr.depth = PackedFrames(depth, words, table, pr.H, pr.W, sizes)
+            if self._t16 is None:
+                depth = torch.empty((total,), dtype=torch.float32, device=self.dev)
+                depth.copy_(dpin, non_blocking=True)
+                pr.depth = PackedFrames(depth, words, table, pr.H, pr.W, sizes)
+            else:   # the 16-bit words go up as they are (as int16 bit patterns) and are fitted where they land
+                depth = torch.empty((total,), dtype=torch.int16, device=self.dev)
+                depth.copy_(dpin.view(torch.int16), non_blocking=True)
+                pr.depth = PackedFrames16(depth.view(tdt), words, table, pr.H, pr.W, sizes, self.depth_scale, self.depth_hole)
             pr.K = torch.empty((P, 9), dtype=torch.float64, device=self.dev)
             pr.K.copy_(kpin, non_blocking=True)
             pr.groups = {}
@@ -298,24 +348,31 @@ class ScenePipeline:
         pr = _Prepared()
         pr.scenes, pr.H, pr.W = scenes, H, W
         t0 = time.perf_counter()
-        dpin, kpin = self._pinned_depth(P, H, W, parity)
-        dnp, knp = dpin.numpy(), kpin.numpy()
+        # (16-bit planes go up PADDED to the pitch the tiled forms want - the padding costs less over the link than the float32 rows
+        # did unpadded - and are fitted where they land, as a Depth16 with its frame_width)
+        Wd = W if self._t16 is None else padded_width(W)
+        esize = 4 if self._t16 is None else 2
+        dpin, kpin = self._pinned_depth(P, H, Wd, parity)
+        dnp, knp = _host_view(dpin), kpin.numpy()
+        if Wd != W:
+            dnp[:, :, W:] = 0
+            dnp = dnp[:, :, :W]
         # one task per loader thread over a contiguous run of images (a task per image spends its time handing the GIL around)
         nthr = max(1, min(self.pool._max_workers, P))
         cuts = [P * t // nthr for t in range(nthr + 1)]
 
         def load_range(t):
             for i in range(cuts[t], cuts[t + 1]):
-                _load_scene(scenes[i], dnp[i], knp[i])
-        inmem = all("depth" in sc and isinstance(sc["depth"], np.ndarray) and sc["depth"].dtype == np.float32 and sc["depth"].flags.c_contiguous
-                    and sc["depth"].shape == (H, W) for sc in scenes)
+                _load_scene(scenes[i], dnp[i], knp[i], self._np16)
+        inmem = Wd == W and all("depth" in sc and isinstance(sc["depth"], np.ndarray) and sc["depth"].dtype == (self._np16 or np.float32)
+                                and sc["depth"].flags.c_contiguous and sc["depth"].shape == (H, W) for sc in scenes)
         if inmem:
             # planes already in host memory: ONE foreign call copies them into the pinned batch buffer on native threads - no Python
             # task per loader thread, nothing that takes the interpreter lock while this thread packs
             ptrs = (C.c_void_p * P)(*[sc["depth"].ctypes.data for sc in scenes])
             for i, sc in enumerate(scenes):
                 knp[i] = np.asarray(sc["K"], dtype=np.float64).reshape(9)
-            loads = [self.pool.submit(lib.la3d_gather_planes_host, ptrs, P, H * W * 4, dnp.ctypes.data, nthr)]
+            loads = [self.pool.submit(lib.la3d_gather_planes_host, ptrs, P, H * W * esize, dnp.ctypes.data, nthr)]
         else:
             loads = [self.pool.submit(load_range, t) for t in range(nthr)]   # np.load / memmove release the GIL: they run WHILE this thread packs
         tp0 = time.perf_counter()
@@ -351,13 +408,18 @@ class ScenePipeline:
             f.result()
         pr.t_load = time.perf_counter() - t0      # (wall time of the loads, the packing above included: they overlap)
         # uploads on the copy stream: the depth planes from pinned memory (asynchronous), the small arrays in one copy per kind
-        pr.nbytes = dpin.numel() * 4
+        pr.nbytes = dpin.numel() * esize
         with torch.cuda.stream(self.copy_stream):
             pr.h2d0 = torch.cuda.Event(enable_timing=True)
             pr.h2d0.record(self.copy_stream)
-            pr.depth = torch.empty((P, H, W), dtype=torch.float32, device=self.dev)
-            pr.depth.copy_(dpin, non_blocking=True)
-            if W % 32 != 0:
+            if self._t16 is not None:
+                d16 = torch.empty((P, H, Wd), dtype=torch.int16, device=self.dev)
+                d16.copy_(dpin.view(torch.int16), non_blocking=True)
+                pr.depth = Depth16(d16.view(self._t16), self.depth_scale, self.depth_hole, W if Wd != W else 0)
+            else:
+                pr.depth = torch.empty((P, H, W), dtype=torch.float32, device=self.dev)
+                pr.depth.copy_(dpin, non_blocking=True)
+            if self._t16 is None and W % 32 != 0:
                 # a frame of odd width (COCO: 427, 500, 375, 333 ...): the rows are padded to the next multiple of 32 ON THE DEVICE
                 # (the upload stays W wide) and the fit is told where the image ends (frame_width): the tiled / single-pass forms
                 # instead of the row-linear one, 3-6 x faster (profiles/r05/r05_frame_sizes.txt)
@@ -397,8 +459,8 @@ class ScenePipeline:
         H, W, P = pr.H, pr.W, len(pr.scenes)
         cur = torch.cuda.current_stream(self.dev)
         cur.wait_event(pr.ready)
-        for t in ((pr.depth.depth, pr.depth.table, pr.K) if self.mixed_frames else (pr.depth, pr.K)):
-            t.record_stream(cur)
+        for t in ((pr.depth[0], pr.depth.table, pr.K) if self.mixed_frames else (pr.depth, pr.K)):   # ([0]: the flat depth buffer)
+            (t.data if isinstance(t, Depth16) else t).record_stream(cur)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(cur)
         K = pr.K.view(P, 3, 3)
@@ -608,11 +670,15 @@ class ScenePipeline:
 # synthetic scene trees (tests, bench.py --end-to-end): the reference's real tensors are pipeline products that are not in the repo
 # ---------------------------------------------------------------------------------------------------------------------------------
 def synthetic_scenes(n_scenes: int, seed: int = 0, H: int = 480, W: int = 640, mean_instances: float = 7.0, rle_fraction: float = 0.25,
-                     root: Optional[str] = None, with_ground: bool = False):
+                     root: Optional[str] = None, with_ground: bool = False, depth_dtype: Optional[str] = None, depth_scale: float = 0.001):
     """COCO-like scenes: one smooth random depth plane per image, ~Poisson(mean_instances) instances with log-uniform area, each as a
     polygon (ellipse outline, 24 vertices, half-pixel coordinates like the COCONut converter writes) or an uncompressed COCO RLE;
     some crowd / tiny / border-touching annotations for the filter.  ``root``: also write the tree (depth_map.npy, cam_params.json,
-    optional reconstruction/*_canonical_upright.npy) and ``annotations.json`` there.  Returns (scenes, annotation dict)."""
+    optional reconstruction/*_canonical_upright.npy) and ``annotations.json`` there.  ``depth_dtype`` "f16" / "u16": the planes - in the
+    scenes and in ``depth_map.npy`` - are the 16-bit ones ``quantise_depth`` makes of them (``depth_scale`` metres per unit for
+    "u16"), what ``ScenePipeline(depth_dtype=...)`` takes.  Returns (scenes, annotation dict)."""
+    if depth_dtype is not None and depth_dtype not in DEPTH_DTYPES:
+        raise ValueError(f"unknown depth_dtype: {depth_dtype!r}. Use None (float32), 'f16' or 'u16'")
     rs = np.random.RandomState(seed)
     vv, uu = np.mgrid[0:H, 0:W]
     images, annos, scenes = [], [], []
@@ -622,6 +688,8 @@ def synthetic_scenes(n_scenes: int, seed: int = 0, H: int = 480, W: int = 640, m
         fn = f"val/{i:06d}-img.jpg"
         images.append({"id": 1000 + i, "file_name": fn, "width": W, "height": H})
         depth = (rs.uniform(2, 6) + rs.uniform(-1e-3, 1e-3) * uu + rs.uniform(0, 3e-3) * vv + 0.02 * rs.randn(H, W)).astype(np.float32)
+        if depth_dtype is not None:
+            depth = quantise_depth(depth, depth_dtype, depth_scale)
         f = rs.uniform(450, 650)
         K = [[f, 0.0, W / 2 + rs.uniform(-5, 5)], [0.0, f, H / 2 + rs.uniform(-5, 5)], [0.0, 0.0, 1.0]]
         anns = []
@@ -696,6 +764,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--make-synthetic", type=int, default=0, metavar="N", help="first write a synthetic tree of N scenes into --scenes")
     ap.add_argument("--mixed-frames", action="store_true", help="batch images of different sizes together, in arrival order: one frames "
                     "call per annotation kind and batch instead of one call per frame size (pca only)")
+    ap.add_argument("--depth-dtype", choices=("f32", "f16", "u16"), default="f32",
+                    help="dtype of every depth_map.npy: f16 / u16 planes are uploaded and fitted as stored, never converted to float32")
+    ap.add_argument("--depth-scale", type=float, default=0.001, help="u16 depth: metres per unit (default: millimetres)")
+    ap.add_argument("--depth-keep-zero", action="store_true", help="u16 depth: a stored 0 is the valid depth 0.0 (default: a hole)")
     ap.add_argument("--bbox-method", choices=("pca", "convex_hull"), default="pca",
                     help="yaw estimator (the reference's bbox_method): principal axis, or the minimum-area rectangle over the hull edges")
     return ap
@@ -704,14 +776,16 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     if args.make_synthetic:
-        synthetic_scenes(args.make_synthetic, seed=0, root=args.scenes)
+        synthetic_scenes(args.make_synthetic, seed=0, root=args.scenes, depth_dtype=None if args.depth_dtype == "f32" else args.depth_dtype,
+                         depth_scale=args.depth_scale)
     ann = args.annotations or os.path.join(args.scenes, "annotations.json")
     if args.seed is not None:
         np.random.seed(args.seed)
     torch.cuda.set_device(args.gpu_idx)
     timings: dict = {}
     pipe = ScenePipeline(device=torch.device("cuda", args.gpu_idx), batch_images=args.batch_images, subsample=args.subsample, timings=timings,
-                         method=args.bbox_method, mixed_frames=args.mixed_frames)
+                         method=args.bbox_method, mixed_frames=args.mixed_frames, depth_dtype=None if args.depth_dtype == "f32" else args.depth_dtype,
+                         depth_scale=args.depth_scale, depth_zero_is_hole=not args.depth_keep_zero)
     t0 = time.perf_counter()
     n_scenes = n_boxes = 0
     for sc, recs in pipe.run(scenes_from_disk(args.scenes, ann, args.start_index, args.end_index, args.skip_done,

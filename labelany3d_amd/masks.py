@@ -864,6 +864,22 @@ class PackedFrames(NamedTuple):
     sizes: list
 
 
+class PackedFrames16(NamedTuple):
+    """16-bit depth maps of different sizes in one buffer (``pack_frames(dtype=...)``; C-ABI ``la3d_fit_instances_frames_depth16``):
+    ``data`` flat ``torch.float16`` / ``torch.uint16`` - the layout of ``PackedFrames`` counted in 16-bit ELEMENTS: plane p starts
+    ``table_host["depth_offset"][p]`` words in (a multiple of 4: 8-byte aligned), its rows ``padded_width(W_p)`` words apart, the
+    columns past ``W_p`` zero words -; ``table`` / ``table_host`` / ``H`` / ``W`` / ``sizes`` as in ``PackedFrames``; ``scale`` /
+    ``zero_is_hole``: the value rule of uint16 planes (``Depth16``; 1.0 / ignored for float16)."""
+    data: torch.Tensor
+    table: torch.Tensor
+    table_host: np.ndarray
+    H: int
+    W: int
+    sizes: list
+    scale: float = 1.0
+    zero_is_hole: bool = True
+
+
 def frame_table(sizes) -> np.ndarray:
     """The frame table (``FRAME_DTYPE``) of images of the given unpadded (H, W) sizes packed back to back: pitch =
     ``padded_width(W)``, planes 16-byte aligned (every pitch is a multiple of 32 floats, so they follow each other directly)."""
@@ -878,14 +894,74 @@ def frame_table(sizes) -> np.ndarray:
     return t
 
 
-def pack_frames(depth_maps, device=None, pinned=None) -> PackedFrames:
+def _words16(m, p: int, dtype: str):
+    """depth map p of a 16-bit ``pack_frames`` as its int16 bit patterns (a view where the map is contiguous): the map must already
+    HAVE the 16-bit dtype - nothing is converted or rounded here"""
+    tdt = _D16_DTYPES[dtype][0]
+    ndt = np.float16 if dtype == "f16" else np.uint16
+    if isinstance(m, torch.Tensor):
+        if m.dtype != tdt:
+            raise ValueError(f"depth map {p}: pack_frames(dtype={dtype!r}) takes maps of {tdt} / numpy {np.dtype(ndt).name}, not {m.dtype}")
+        return m.contiguous().view(torch.int16)
+    a = np.asarray(m)
+    if a.dtype != ndt:
+        raise ValueError(f"depth map {p}: pack_frames(dtype={dtype!r}) takes maps of numpy {np.dtype(ndt).name} / {tdt}, not {a.dtype}")
+    return np.ascontiguousarray(a).view(np.int16)
+
+
+def _pack_frames16(maps, dev, pinned, dtype, scale, zero_is_hole) -> PackedFrames16:
+    if dtype not in _D16_DTYPES:
+        raise ValueError(f"unknown dtype: {dtype!r}. Use None (float32), 'f16' or 'u16'")
+    tdt = _D16_DTYPES[dtype][0]
+    if dtype == "u16" and not (np.isfinite(np.float32(scale)) and np.float32(scale) > 0):
+        raise ValueError(f"scale must be finite and > 0 (as float32), not {scale!r}")
+    for p, m in enumerate(maps):
+        if len(m.shape) != 2:
+            raise ValueError(f"depth map {p} must be (H, W), got {tuple(m.shape)}")
+    words = [_words16(m, p, dtype) for p, m in enumerate(maps)]
+    sizes = [(int(m.shape[0]), int(m.shape[1])) for m in maps]
+    table = frame_table(sizes)   # (offsets in ELEMENTS: multiples of 32, so every 16-bit plane is 8-byte aligned)
+    total = int(sum(int(r["H"]) * int(r["W"]) for r in table))
+    n = max(total, 4)
+    if any(isinstance(w, torch.Tensor) and w.is_cuda for w in words):
+        flat = torch.zeros(n, dtype=torch.int16, device=dev)
+        for w16, r in zip(words, table):
+            o, h, wp, w = int(r["depth_offset"]), int(r["H"]), int(r["W"]), int(r["frame_width"])
+            flat[o:o + h * wp].view(h, wp)[:, :w].copy_(torch.as_tensor(w16).to(dev))
+        flat = flat.view(tdt)
+    else:
+        if pinned is not None and pinned.dtype == tdt and pinned.numel() >= n:
+            host_t = pinned[:n]
+        else:
+            pinned, host_t = None, torch.empty(n, dtype=tdt)
+        host = host_t.view(torch.int16).numpy()
+        for w16, r in zip(words, table):
+            o, h, wp, w = int(r["depth_offset"]), int(r["H"]), int(r["W"]), int(r["frame_width"])
+            dst = host[o:o + h * wp].reshape(h, wp)
+            dst[:, :w] = w16.numpy() if isinstance(w16, torch.Tensor) else w16
+            dst[:, w:] = 0
+        host[total:] = 0
+        flat = host_t if dev.type == "cpu" else host_t.view(torch.int16).to(dev, non_blocking=pinned is not None).view(tdt)
+    rows = np.ascontiguousarray(table).view(np.int32).reshape(len(maps), 6) if len(maps) else np.zeros((0, 6), np.int32)
+    tab = torch.as_tensor(rows.copy(), device=dev)
+    return PackedFrames16(flat, tab, table, max((h for h, _ in sizes), default=0), max((int(r["W"]) for r in table), default=0), sizes,
+                          float(scale) if dtype == "u16" else 1.0, bool(zero_is_hole))
+
+
+def pack_frames(depth_maps, device=None, pinned=None, dtype=None, scale: float = 0.001, zero_is_hole: bool = True):
     """Depth maps of DIFFERENT sizes -> ``PackedFrames``: one flat float32 buffer on the device, each plane at its own pitch
     (``padded_width``) and 16-byte aligned offset, the padding zero, plus the device frame table ``fit_instances_frames`` takes.
     ``depth_maps``: a sequence of (H_p, W_p) arrays / tensors.  ``pinned``: a pinned float32 staging tensor of at least the packed size
     (host maps only) - the upload is then asynchronous on the current stream and the caller keeps the buffer untouched until that
-    stream has passed it.  ``device="cpu"`` gives the layout on the host (no GPU needed)."""
+    stream has passed it.  ``device="cpu"`` gives the layout on the host (no GPU needed).
+    ``dtype`` "f16" / "u16": the maps already ARE 16-bit (``np.float16`` / ``np.uint16``, ``torch.float16`` / ``torch.uint16``; any
+    other dtype: ValueError naming the map) and their words are copied as stored - nothing is converted or rounded - into one flat
+    16-bit buffer of the same layout counted in elements: a ``PackedFrames16`` (``scale`` / ``zero_is_hole``: the value rule of uint16
+    planes, see ``Depth16``; ``pinned``: a pinned staging tensor of the 16-bit dtype), fitted where it lies by ``fit_instances_frames``."""
     dev = torch.device(device) if device is not None and torch.device(device).type == "cpu" else _dev(device)
     maps = list(depth_maps)
+    if dtype is not None:
+        return _pack_frames16(maps, dev, pinned, dtype, scale, zero_is_hole)
     for p, m in enumerate(maps):
         if len(m.shape) != 2:
             raise ValueError(f"depth map {p} must be (H, W), got {tuple(m.shape)}")
@@ -932,7 +1008,8 @@ def pack_rle_frames(rles):
 def fit_instances_frames(frames, K, rles=None, polys=None, image_index=None, ground=None, sample_idx=None, filter=None, proj: bool = False,
                          area_hint=None, stream=None, method: str = "pca", _fitter=None):
     """The fit for instances of images of DIFFERENT sizes in one call (C-ABI ``la3d_fit_instances_frames``): ``frames`` is what
-    ``pack_frames`` returns; instance n belongs to image ``image_index[n]`` (required), whose K is ``K[image_index[n]]`` (K: (P,3,3),
+    ``pack_frames`` returns - a ``PackedFrames``, or a ``PackedFrames16`` (16-bit planes fitted where they lie, C-ABI
+    ``la3d_fit_instances_frames_depth16``: the records of the float32 call on the up-converted planes); instance n belongs to image ``image_index[n]`` (required), whose K is ``K[image_index[n]]`` (K: (P,3,3),
     or (3,3) shared).  Exactly one of ``rles`` - a list of COCO RLE objects, each of its own image's size, or a ``(counts, offsets)``
     tuple - and ``polys`` - the tuple of ``pack_polygons`` (its H, W are ignored: every instance is clipped to its own frame) - gives
     the masks.  ``ground`` / ``sample_idx`` / ``filter`` / ``area_hint`` as in ``fit_instances_ex``; ``proj=True`` adds ``boxes2d``,
@@ -944,15 +1021,22 @@ def fit_instances_frames(frames, K, rles=None, polys=None, image_index=None, gro
     refuse_depth16(getattr(frames, "depth", None), "fit_instances_frames")
     if _lib.method_code(method) != _lib.METHOD_PCA:   # (the reference's error for an unknown method; before any device work)
         raise ValueError("fit_instances_frames: method='convex_hull' is not supported for frames of different sizes; group by size and use fit_instances_ex")
-    if not isinstance(frames, PackedFrames):
+    is16 = isinstance(frames, PackedFrames16)
+    if is16:
+        t = frames.data   # (dtype, scale: the argument errors of a Depth16, before any device work)
+        if not isinstance(t, torch.Tensor) or t.dim() != 1:
+            raise ValueError("PackedFrames16.data must be the flat tensor of pack_frames(dtype=...)")
+        _depth16_check(Depth16(t[None], frames.scale, frames.zero_is_hole))
+    elif not isinstance(frames, PackedFrames):
         raise ValueError("frames must be the PackedFrames of pack_frames")
     if (rles is not None) + (polys is not None) != 1:
         raise ValueError("give exactly one of rles / polys")
     if image_index is None:
         raise ValueError("image_index is required: instance n belongs to frame image_index[n]")
-    if not frames.depth.is_cuda:
+    fdepth = frames.data if is16 else frames.depth
+    if not fdepth.is_cuda:
         raise ValueError("frames must live on the GPU (pack_frames with a GPU device)")
-    dev = frames.depth.device
+    dev = fdepth.device
     P = int(frames.table.shape[0])
     if rles is not None:
         counts, offsets, sizes = pack_rle_frames(rles)
@@ -1015,12 +1099,19 @@ def fit_instances_frames(frames, K, rles=None, polys=None, image_index=None, gro
             if ah.numel() != B:
                 raise ValueError("area_hint must have one entry per instance")
             keep.append(ah)
-        a = _fit_args(B, H, W, _ptr(frames.depth), 1, _ptr(k), k.shape[0], _ptr(f.boxes[0]), _ptr(f.status[0]), _ptr(f.aux[0]),
+        a = _fit_args(B, H, W, None if is16 else _ptr(fdepth), 1, _ptr(k), k.shape[0], _ptr(f.boxes[0]), _ptr(f.status[0]), _ptr(f.aux[0]),
                       _ptr(f.workspace[0]), _stream(stream), image_index=_ptr(ii), ground=_ptr(g), sample_idx=_ptr(si), filter=filter,
                       stats=_ptr(out.get("stats")), proj=_ptr(out.get("boxes2d")), image_size=(1, 1) if proj else None,
                       area_hint=_ptr(ah), opts=options.codes(), **kind)
-        check(lib.la3d_fit_instances_frames(C.byref(a), _ptr(frames.table), P), "la3d_fit_instances_frames")
-    _record(stream, frames.depth, frames.table, k, ii, g, si, *keep, f.workspace, *out.values())
+        if is16:
+            u16 = fdepth.dtype == torch.uint16
+            blk = _lib.Depth16Block(struct_size=C.sizeof(_lib.Depth16Block), dtype=_lib.DTYPE_U16 if u16 else _lib.DTYPE_F16,
+                                    planes=fdepth.data_ptr(), plane_stride=0, scale=float(frames.scale) if u16 else 1.0,
+                                    flags=_lib.DEPTH_ZERO_IS_HOLE if (u16 and frames.zero_is_hole) else 0)
+            check(lib.la3d_fit_instances_frames_depth16(C.byref(a), C.byref(blk), _ptr(frames.table), P), "la3d_fit_instances_frames_depth16")
+        else:
+            check(lib.la3d_fit_instances_frames(C.byref(a), _ptr(frames.table), P), "la3d_fit_instances_frames")
+    _record(stream, fdepth, frames.table, k, ii, g, si, *keep, f.workspace, *out.values())
     return out
 
 
