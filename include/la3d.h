@@ -361,6 +361,37 @@ int la3d_unpack_mask_bits(const uint32_t* bits, int64_t bits_plane_stride, int B
 int la3d_mask_stats_bits(const uint32_t* bits, int64_t bits_plane_stride, int B, int H, int W, int frame_width, int boundary,
                          int32_t* stats, void* stream);
 
+/* ---- masks as label maps ----------------------------------------------------------------------------------------------
+ * The form instance masks have before they become planes, run lengths or polygons: ONE plane of segment ids per image (a panoptic
+ * PNG, the output of a panoptic / entity segmentation network), every instance mask being `labels == id`.  la3d_pack_label_bits
+ * turns P label planes into the B bit planes of the (image, id) rows the caller lists - the labels of an image are read once,
+ * however many instances it has - and la3d_fit_instances_bits fits them (image_index = the image of each row).
+ *
+ * labels: dev, plane p at labels + p*plane_stride ELEMENTS (pixels for RGB8; >= H*W), rows W elements apart, aligned to the element.
+ *   LA3D_LABEL_U8 / LA3D_LABEL_U16: zero-extended; LA3D_LABEL_I32: as it is; LA3D_LABEL_RGB8: 3 bytes per pixel,
+ *   id = R + 256 G + 65536 B (the COCO panoptic PNG).
+ * inst_offsets dev [P+1]: the instances of image p are the rows inst_offsets[p] .. inst_offsets[p+1]-1 (non-decreasing, from 0 to B;
+ *   rows outside [0, B) are never touched); inst_label dev [B]: the id of each row.  An image without rows is never read.
+ * VALUE.  Bit (v, u) of plane b = (label(image of b, v, u) == inst_label[b]), both sides as int32: an id outside the dtype's range
+ *   matches nothing (an all-zero plane, not an error); rows that repeat an (image, id) pair each get the plane.
+ * Output: B planes in exactly the format of la3d_pack_mask_bits (la3d_mask_bits_words(H, W_out) words each, bits_plane_stride words
+ *   apart, rows padded from W to W_out >= W with zero bits; only the words of a plane are written, and every word of every plane).
+ * area: dev [B] or NULL - the popcount of each plane (what area_hint and draw_sample_idx want); cleared by the call itself on
+ *   `stream` (the call is capturable) and accumulated with one integer atomic per wave and instance.
+ * LA3D_ERR_ARG: an unknown dtype, W_out < W, negative sizes, plane_stride < H*W, bits_plane_stride < la3d_mask_bits_words(H, W_out),
+ *   misaligned pointers, NULL pointers with work to do.  B == 0 or P == 0: success, nothing is done.
+ * A 16-byte form stands in front of a general one as for the packers above: U8 / U16 / I32 with W_out == W, H*W % 32 == 0 and every
+ * label plane 16-byte aligned (base and stride) take it; everything else (RGB8 included) the general form. */
+#define LA3D_LABEL_U8   0   /* zero-extended */
+#define LA3D_LABEL_U16  1   /* zero-extended */
+#define LA3D_LABEL_I32  2
+#define LA3D_LABEL_RGB8 3   /* 3 bytes per pixel, id = R + 256 G + 65536 B (COCO panoptic PNG) */
+int la3d_pack_label_bits(const void* labels, int dtype, int64_t plane_stride /* elements; pixels for RGB8 */,
+                         int P, int H, int W, int W_out,
+                         const int32_t* inst_offsets /* dev [P+1]: instances of image p are rows inst_offsets[p] .. inst_offsets[p+1]-1 */,
+                         const int32_t* inst_label   /* dev [B] */, int B,
+                         uint32_t* bits, int64_t bits_plane_stride, int32_t* area /* dev [B] or NULL */, void* stream);
+
 /* ---- 16-bit depth planes ----------------------------------------------------------------------------------------------
  * Sensor depth is uint16 with a metric scale (millimetres: SUN RGB-D, ScanNet, ARKitScenes, every RealSense / Kinect stream); depth
  * networks run in half precision.  la3d_fit_instances_depth16 fits straight from such planes - no float32 copy is made or read.

@@ -16,6 +16,7 @@ ERR_UNSUPPORTED = -2
 BITS_HEIGHT_ROWS, BITS_HEIGHT_SPAN = 0, 1          # flags of la3d_fit_instances_bits: the height rule of the fused filter
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2        # la3d_pack_logits_bits
 DTYPE_U16 = 3                                     # la3d_depth16 (with DTYPE_F16): uint16 x scale depth planes
+LABEL_U8, LABEL_U16, LABEL_I32, LABEL_RGB8 = 0, 1, 2, 3   # la3d_pack_label_bits: the element of a label map
 DEPTH_ZERO_IS_HOLE = 1                            # la3d_depth16.flags (U16): a stored 0 is a hole (NaN)
 
 class FitArgs(C.Structure):
@@ -62,6 +63,8 @@ _SIGS = {
     "la3d_pack_mask_bits": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "la3d_pack_logits_bits": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                         C.c_int64, C.c_void_p]),
+    "la3d_pack_label_bits": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "la3d_unpack_mask_bits": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "la3d_mask_stats_bits": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "la3d_version": (C.c_int, []),

@@ -878,3 +878,192 @@ int la3d_mask_stats_bits(const uint32_t* bits, int64_t bits_plane_stride, int B,
 }
 
 }  // extern "C"
+
+// ---- masks as label maps ------------------------------------------------------------------
+// include/la3d.h "masks as label maps": one (H, W) plane of segment ids per image -> one bit plane per (image, id) row, in the
+// format of the packers above.  Both forms hold the 32 labels of an output word in registers and loop over the image's instances,
+// so the labels of an image are read once however many instances it has.
+namespace {
+enum { LB_U8 = LA3D_LABEL_U8, LB_U16 = LA3D_LABEL_U16, LB_I32 = LA3D_LABEL_I32, LB_RGB8 = LA3D_LABEL_RGB8 };
+template <int KIND> struct LabelElem;
+template <> struct LabelElem<LB_U8>   { typedef unsigned char T;  static constexpr int BYTES = 1; };
+template <> struct LabelElem<LB_U16>  { typedef unsigned short T; static constexpr int BYTES = 2; };
+template <> struct LabelElem<LB_I32>  { typedef int T;            static constexpr int BYTES = 4; };
+template <> struct LabelElem<LB_RGB8> { typedef unsigned char T;  static constexpr int BYTES = 3; };
+
+// the rows [i0, i1) of image p, clamped to [0, B): whatever the offsets hold, no row outside the call's planes is written
+__device__ inline void label_rows(const int* __restrict__ inst_offsets, int p, int B, int* i0, int* i1) {
+  const int a = __builtin_amdgcn_readfirstlane(inst_offsets[p]), b = __builtin_amdgcn_readfirstlane(inst_offsets[p + 1]);
+  *i0 = a < 0 ? 0 : a;
+  *i1 = b > B ? B : b;
+}
+
+__global__ __launch_bounds__(256) void clear_area_kernel(int* __restrict__ area, int B) {
+  const int i = blockIdx.x * 256 + (int)threadIdx.x;
+  if (i < B) area[i] = 0;
+}
+
+// area[b] += popcount over the wave: one vector atomic per wave and instance (none for a wave that holds no pixel of it)
+__device__ inline void label_area(int* __restrict__ area, int b, unsigned pat) {
+  const int n = wave_sum_i(__popc(pat));
+  if (area && n && (threadIdx.x & 63) == 0) atomicAdd(area + b, n);
+}
+
+// Vector form (chosen on the host: U8 / U16 / I32, W_out == W, H*W % 32 == 0, every label plane 16-byte aligned): a workgroup owns
+// 256 consecutive output words of one image; each lane loads the 32 labels of its word once (2 / 4 / 8 loads of 16 bytes) and
+// stores one word per instance - 256 contiguous bytes per wave.  blockIdx.x = image * chunks + chunk.
+template <int KIND>
+__global__ __launch_bounds__(256) void pack_labels_vec_kernel(const void* __restrict__ labels, long long plane_stride_bytes, int nwords,
+                                                              int chunks, const int* __restrict__ inst_offsets,
+                                                              const int* __restrict__ inst_label, int B, unsigned* __restrict__ out,
+                                                              long long out_stride, int* __restrict__ area) {
+  constexpr int NQ = 2 * LabelElem<KIND>::BYTES;   // 16-byte groups per output word
+  const int p = blockIdx.x / chunks, chunk = blockIdx.x - p * chunks;
+  int i0, i1;
+  label_rows(inst_offsets, p, B, &i0, &i1);
+  if (i0 >= i1) return;   // (uniform) an image without instances is never read
+  const int w = chunk * 256 + (int)threadIdx.x;
+  const bool live = w < nwords;
+  u32x4 q[NQ];
+  const u32x4* s4 = reinterpret_cast<const u32x4*>(static_cast<const unsigned char*>(labels) + (long long)p * plane_stride_bytes) +
+                    (long long)w * NQ;
+#pragma unroll
+  for (int k = 0; k < NQ; ++k) q[k] = live ? __builtin_nontemporal_load(s4 + k) : u32x4{0u, 0u, 0u, 0u};
+  unsigned* o = out + w;
+  for (int b = i0; b < i1; ++b) {   // uniform trip count: every lane takes part in the reduction
+    const int id = inst_label[b];   // (wave-uniform)
+    unsigned pat = 0;
+    if constexpr (KIND == LB_U8) {
+      const unsigned s = (unsigned)(id & 255) * 0x01010101u;
+      pat = ~(nz16(q[0].x ^ s, q[0].y ^ s, q[0].z ^ s, q[0].w ^ s) | (nz16(q[1].x ^ s, q[1].y ^ s, q[1].z ^ s, q[1].w ^ s) << 16));
+      if ((unsigned)id > 255u) pat = 0;
+    } else if constexpr (KIND == LB_U16) {
+      const unsigned s = (unsigned)(id & 0xffff) * 0x00010001u;
+#pragma unroll
+      for (int k = 0; k < NQ; ++k) {
+        const unsigned x[4] = {q[k].x ^ s, q[k].y ^ s, q[k].z ^ s, q[k].w ^ s};
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          pat |= ((x[j] & 0xffffu) == 0 ? 1u : 0u) << (8 * k + 2 * j) | ((x[j] >> 16) == 0 ? 1u : 0u) << (8 * k + 2 * j + 1);
+      }
+      if ((unsigned)id > 65535u) pat = 0;
+    } else {
+#pragma unroll
+      for (int k = 0; k < NQ; ++k)
+        pat |= ((int)q[k].x == id ? 1u : 0u) << (4 * k) | ((int)q[k].y == id ? 1u : 0u) << (4 * k + 1) |
+               ((int)q[k].z == id ? 1u : 0u) << (4 * k + 2) | ((int)q[k].w == id ? 1u : 0u) << (4 * k + 3);
+    }
+    if (!live) pat = 0;
+    if (live) o[(long long)b * out_stride] = pat;
+    label_area(area, b, pat);
+  }
+}
+
+// General form: one thread per output word, any stride / alignment / row padding, a ragged last word, RGB8; element (v, u) is read
+// when v < H and u < W, zero-extended (RGB8: R + 256 G + 65536 B).
+template <int KIND>
+__global__ __launch_bounds__(256) void pack_labels_kernel(const void* __restrict__ labels, long long plane_stride_elems, int H, int W,
+                                                          int W_out, int nwords, int chunks, const int* __restrict__ inst_offsets,
+                                                          const int* __restrict__ inst_label, int B, unsigned* __restrict__ out,
+                                                          long long out_stride, int* __restrict__ area) {
+  typedef typename LabelElem<KIND>::T T;
+  const int p = blockIdx.x / chunks, chunk = blockIdx.x - p * chunks;
+  int i0, i1;
+  label_rows(inst_offsets, p, B, &i0, &i1);
+  if (i0 >= i1) return;   // (uniform)
+  const int w = chunk * 256 + (int)threadIdx.x;
+  const bool live = w < nwords;
+  const T* sp = static_cast<const T*>(labels) + (long long)p * plane_stride_elems * (KIND == LB_RGB8 ? 3 : 1);
+  const long long total = (long long)H * W_out, j0 = (long long)w * 32;
+  int v = (int)(j0 / W_out), u = (int)(j0 - (long long)v * W_out);
+  int lab[32];
+  unsigned have = 0;   // bit k: pixel k of the word lies inside the image
+#pragma unroll
+  for (int k = 0; k < 32; ++k) {
+    lab[k] = 0;
+    if (live && j0 + k < total && u < W) {
+      const long long e = (long long)v * W + u;
+      if constexpr (KIND == LB_RGB8) lab[k] = (int)sp[e * 3] | (int)sp[e * 3 + 1] << 8 | (int)sp[e * 3 + 2] << 16;
+      else lab[k] = (int)sp[e];
+      have |= 1u << k;
+    }
+    if (++u == W_out) { u = 0; ++v; }
+  }
+  unsigned* o = out + w;
+  for (int b = i0; b < i1; ++b) {   // uniform trip count
+    const int id = inst_label[b];
+    unsigned pat = 0;
+#pragma unroll
+    for (int k = 0; k < 32; ++k) pat |= (lab[k] == id ? 1u : 0u) << k;
+    pat &= have;
+    if (live) o[(long long)b * out_stride] = pat;
+    label_area(area, b, pat);
+  }
+}
+
+template <int KIND>
+int pack_labels_launch(const void* labels, long long plane_stride, int P, int H, int W, int W_out, const int* inst_offsets,
+                       const int* inst_label, int B, uint32_t* bits, long long bits_plane_stride, int* area, hipStream_t s) {
+  constexpr long long ES = LabelElem<KIND>::BYTES;
+  const long long HW = (long long)H * W;
+  const int nwords = (int)la3d_mask_bits_words(H, W_out);
+  const int chunks = (nwords + 255) / 256;
+  const bool vec = KIND != LB_RGB8 && W_out == W && HW % 32 == 0 && (reinterpret_cast<uintptr_t>(labels) & 15) == 0 &&
+                   (plane_stride * ES) % 16 == 0;
+  const dim3 grid((unsigned)((long long)P * chunks));
+  if constexpr (KIND != LB_RGB8) {
+    if (vec) {
+      hipLaunchKernelGGL(pack_labels_vec_kernel<KIND>, grid, dim3(256), 0, s, labels, plane_stride * ES, nwords, chunks, inst_offsets,
+                         inst_label, B, bits, bits_plane_stride, area);
+      return check_launch("pack_labels_vec_kernel");
+    }
+  }
+  hipLaunchKernelGGL(pack_labels_kernel<KIND>, grid, dim3(256), 0, s, labels, plane_stride, H, W, W_out, nwords, chunks, inst_offsets,
+                     inst_label, B, bits, bits_plane_stride, area);
+  return check_launch("pack_labels_kernel");
+}
+}  // namespace
+
+extern "C" {
+
+int la3d_pack_label_bits(const void* labels, int dtype, int64_t plane_stride, int P, int H, int W, int W_out,
+                         const int32_t* inst_offsets, const int32_t* inst_label, int B, uint32_t* bits, int64_t bits_plane_stride,
+                         int32_t* area, void* stream) {
+  const char* bad = nullptr;
+  const bool work = B > 0 && P > 0;
+  if (dtype != LA3D_LABEL_U8 && dtype != LA3D_LABEL_U16 && dtype != LA3D_LABEL_I32 && dtype != LA3D_LABEL_RGB8)
+    bad = "unknown dtype (LA3D_LABEL_U8, LA3D_LABEL_U16, LA3D_LABEL_I32 or LA3D_LABEL_RGB8)";
+  else if (B < 0 || P < 0 || H <= 0 || W <= 0 || W_out < W) bad = "bad argument (B, P >= 0, H, W > 0, W_out >= W)";
+  else if ((long long)H * W_out > (1LL << 28) || (long long)P * (((long long)H * W_out + 8191) / 8192) > 0x7fffffffLL)
+    bad = "frame or batch too large (H*W_out <= 2^28, P * ceil(H*W_out / 8192) < 2^31)";
+  else if (work && (!labels || !inst_offsets || !inst_label || !bits)) bad = "NULL labels, inst_offsets, inst_label or bits";
+  else if (work && (reinterpret_cast<uintptr_t>(bits) & 3)) bad = "bits not a 4-byte aligned pointer";
+  else if (work && (reinterpret_cast<uintptr_t>(labels) & (dtype == LA3D_LABEL_I32 ? 3 : dtype == LA3D_LABEL_U16 ? 1 : 0)))
+    bad = "labels not aligned to their element size";
+  else if (work && ((reinterpret_cast<uintptr_t>(inst_offsets) | reinterpret_cast<uintptr_t>(inst_label) | reinterpret_cast<uintptr_t>(area)) & 3))
+    bad = "inst_offsets, inst_label or area not a 4-byte aligned pointer";
+  else if (work && plane_stride < (long long)H * W) bad = "label plane stride smaller than H*W";
+  else if (work && bits_plane_stride < (long long)la3d_mask_bits_words(H, W_out))
+    bad = "bits_plane_stride is smaller than la3d_mask_bits_words(H, W_out)";
+  if (bad) {
+    char msg[200];
+    snprintf(msg, sizeof(msg), "la3d_pack_label_bits: %s", bad);
+    set_err(msg);
+    return LA3D_ERR_ARG;
+  }
+  if (!work) return LA3D_SUCCESS;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (area) {   // cleared by a kernel of the call's own on the call's stream: a kernel node like the packer's when captured
+    hipLaunchKernelGGL(clear_area_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, area, B);
+    const int rc = check_launch("clear_area_kernel");
+    if (rc != LA3D_SUCCESS) return rc;
+  }
+  switch (dtype) {
+    case LA3D_LABEL_U8: return pack_labels_launch<LB_U8>(labels, plane_stride, P, H, W, W_out, inst_offsets, inst_label, B, bits, bits_plane_stride, area, s);
+    case LA3D_LABEL_U16: return pack_labels_launch<LB_U16>(labels, plane_stride, P, H, W, W_out, inst_offsets, inst_label, B, bits, bits_plane_stride, area, s);
+    case LA3D_LABEL_I32: return pack_labels_launch<LB_I32>(labels, plane_stride, P, H, W, W_out, inst_offsets, inst_label, B, bits, bits_plane_stride, area, s);
+    default: return pack_labels_launch<LB_RGB8>(labels, plane_stride, P, H, W, W_out, inst_offsets, inst_label, B, bits, bits_plane_stride, area, s);
+  }
+}
+
+}  // extern "C"
