@@ -185,10 +185,13 @@ class La3dError(RuntimeError):
     pass
 
 
+_METHODS = {"pca": METHOD_PCA, "convex_hull": METHOD_CONVEX_HULL}
+
+
 def method_code(method) -> int:
     """``method`` of the fit entries ("pca" | "convex_hull", the reference's estimate_bbox argument) -> LA3D_METHOD_*; anything else
     raises the reference's error (src/util_3dbox.py:151) - before any device work."""
-    code = {"pca": METHOD_PCA, "convex_hull": METHOD_CONVEX_HULL}.get(method) if isinstance(method, str) else None
+    code = _METHODS.get(method) if isinstance(method, str) else None
     if code is None:
         raise ValueError(f"Unknown method: {method}. Use 'pca' or 'convex_hull'")
     return code

@@ -156,11 +156,16 @@ def _depth16_block(d16: Depth16, H: int, W: int) -> _lib.Depth16Block:
     P = t.shape[0] if t.dim() == 3 else 1
     if (W > 1 and t.stride(-1) != 1) or (H > 1 and t.stride(-2) != W) or (t.dim() == 3 and P > 1 and t.stride(0) < H * W):
         raise ValueError(f"Depth16 planes must have dense rows and lie >= H*W elements apart (strides {t.stride()})")
+    return _d16_block(t, d16.scale, d16.zero_is_hole, int(t.stride(0)) if t.dim() == 3 and P > 1 else 0)
+
+
+def _d16_block(t: torch.Tensor, scale, zero_is_hole, plane_stride: int = 0) -> _lib.Depth16Block:
+    """``la3d_depth16`` of resident float16 / uint16 words: planes ``plane_stride`` elements apart, or - 0 - one plane / the flat
+    buffer of a ``PackedFrames16``.  Scale and hole rule count for uint16 only."""
     u16 = t.dtype == torch.uint16
     return _lib.Depth16Block(struct_size=C.sizeof(_lib.Depth16Block), dtype=_lib.DTYPE_U16 if u16 else _lib.DTYPE_F16,
-                             planes=t.data_ptr(), plane_stride=int(t.stride(0)) if t.dim() == 3 and P > 1 else 0,
-                             scale=float(d16.scale) if u16 else 1.0,
-                             flags=_lib.DEPTH_ZERO_IS_HOLE if (u16 and d16.zero_is_hole) else 0)
+                             planes=t.data_ptr(), plane_stride=plane_stride, scale=float(scale) if u16 else 1.0,
+                             flags=_lib.DEPTH_ZERO_IS_HOLE if (u16 and zero_is_hole) else 0)
 
 
 def refuse_depth16(depth, who: str) -> None:
@@ -170,18 +175,17 @@ def refuse_depth16(depth, who: str) -> None:
                          "fit_instances_rle / fit_instances_poly / fit_instances_bits / InstanceFitter.run (instance engine only)")
 
 
-def _depth_arg(depth):
-    """(what ``_fit_args`` takes as ``depth``, planes) of a device tensor (P,H,W) | (H,W) or a ``Depth16``."""
-    if isinstance(depth, Depth16):
-        return depth, (depth.data.shape[0] if depth.data.dim() == 3 else 1)
-    return _ptr(depth), (depth.shape[0] if depth.dim() == 3 else 1)
-
-
-def _launch(a: FitArgs, bits=None) -> None:
-    """The C entry of a block built by ``_fit_args``: 16-bit depth planes (``a.d16``), bit planes (``bits`` = (pointer, stride,
-    flags)), or the plain block."""
+def _enqueue(a: FitArgs, bits=None, frames=None) -> None:
+    """The C entry of a block built by ``_fit_args``, picked from what the call carries: a frame table (``frames`` = (pointer, P);
+    with 16-bit depth - ``a.d16`` - its depth16 form), 16-bit depth planes, bit planes (``bits`` = (pointer, stride, flags)), or the
+    plain block."""
     d16 = getattr(a, "d16", None)
-    if d16 is not None:
+    if frames is not None:
+        if d16 is not None:
+            check(lib.la3d_fit_instances_frames_depth16(C.byref(a), C.byref(d16), frames[0], frames[1]), "la3d_fit_instances_frames_depth16")
+        else:
+            check(lib.la3d_fit_instances_frames(C.byref(a), frames[0], frames[1]), "la3d_fit_instances_frames")
+    elif d16 is not None:
         b = bits if bits is not None else (None, 0, 0)
         check(lib.la3d_fit_instances_depth16(C.byref(a), C.byref(d16), b[0], b[1], b[2]), "la3d_fit_instances_depth16")
     elif bits is not None:
@@ -284,15 +288,8 @@ class InstanceFitter:
         ``depth``: float32 planes, or a ``Depth16`` (fitted from its 16-bit planes: C-ABI ``la3d_fit_instances_depth16``).
         ``engine`` / ``launch_order`` / ``build``: scheduling of THIS call (labelany3d_amd.options; speed only).
         ``method``: "pca" | "convex_hull" (None: what the fitter was built for)."""
-        meth = self._method(method)
-        darg, planes = _depth_arg(depth)
-        a = _fit_args(self.B, self.H, self.W, darg, planes, _ptr(K),
-                      K.shape[0] if K.dim() == 3 else 1, _ptr(self.boxes[slot]), _ptr(self.status[slot]), _ptr(self.aux[slot]),
-                      _ptr(self.workspace[ws_slot]), _stream(stream, raw=True), mask=_ptr(masks), image_index=_ptr(image_index),
-                      ground=_ptr(ground), sample_idx=_ptr(sample_idx), area_hint=_ptr(area_hint),
-                      opts=options.codes(engine, launch_order, build), method=meth)
-        _launch(a)
-        return self.boxes[slot], self.status[slot], self.aux[slot]
+        return self._run(self._method(method), depth, K, ground, sample_idx, image_index, slot, stream, ws_slot, (engine, launch_order, build),
+                         area_hint, mask=_ptr(masks))
 
     def run_bits(self, depth: torch.Tensor, bits, K: torch.Tensor, ground=None, sample_idx=None, image_index=None, slot: int = 0,
                  stream=None, ws_slot: int = 0, engine=None, launch_order=None, build=None, area_hint=None, method=None,
@@ -305,14 +302,20 @@ class InstanceFitter:
         t, fw = (bits[0], bits[3]) if isinstance(bits, tuple) else (bits, int(frame_width))
         if isinstance(bits, tuple) and (bits[1], bits[2]) != (self.H, self.W):
             raise ValueError(f"bit planes of a {bits[1]} x {bits[2]} frame do not match the fitter's {self.H} x {self.W}")
-        stride = _bits_stride(t, self.B, self.H, self.W)
-        darg, planes = _depth_arg(depth)
+        return self._run(meth, depth, K, ground, sample_idx, image_index, slot, stream, ws_slot, (engine, launch_order, build), area_hint,
+                         bits=(_ptr(t), _bits_stride(t, self.B, self.H, self.W), height_rule), frame_width=0 if fw == self.W else fw)
+
+    def _run(self, meth, depth, K, ground, sample_idx, image_index, slot, stream, ws_slot, sched, area_hint, mask=None, bits=None,
+             frame_width=0):
+        """The enqueue ``run`` and ``run_bits`` share - block, C entry, nothing else.  ``bits``: (pointer, stride, height rule)."""
+        t = depth.data if isinstance(depth, Depth16) else depth   # (a Depth16 goes to _fit_args as it is, a tensor as its pointer)
+        darg, planes = (depth if t is not depth else _ptr(t)), (t.shape[0] if t.dim() == 3 else 1)
         a = _fit_args(self.B, self.H, self.W, darg, planes, _ptr(K),
                       K.shape[0] if K.dim() == 3 else 1, _ptr(self.boxes[slot]), _ptr(self.status[slot]), _ptr(self.aux[slot]),
-                      _ptr(self.workspace[ws_slot]), _stream(stream, raw=True), image_index=_ptr(image_index),
-                      ground=_ptr(ground), sample_idx=_ptr(sample_idx), area_hint=_ptr(area_hint),
-                      opts=options.codes(engine, launch_order, build), frame_width=0 if fw == self.W else fw, method=meth)
-        _launch(a, (_ptr(t), stride, height_rule_code(height_rule)))
+                      _ptr(self.workspace[ws_slot]), _stream(stream, raw=True), mask=mask, image_index=_ptr(image_index),
+                      ground=_ptr(ground), sample_idx=_ptr(sample_idx), area_hint=_ptr(area_hint), opts=options.codes(*sched),
+                      frame_width=frame_width, method=meth)
+        _enqueue(a, bits and (bits[0], bits[1], height_rule_code(bits[2])))
         return self.boxes[slot], self.status[slot], self.aux[slot]
 
     def _method(self, method) -> int:
@@ -366,12 +369,15 @@ def _fit_args(B, H, W, depth, planes, K, nk, out, status, aux, workspace, stream
     of either is shared by every instance).  rle = (counts, offsets), poly = (xy, ring_offsets, inst_rings); ``filter`` as in
     ``fit_instances_rle`` (None: no filter); ``proj`` with ``image_size`` = (width, height); ``opts`` = options.codes().
     ``depth`` may be a ``Depth16``: the block then carries no depth (C-ABI ``la3d_fit_instances_depth16`` takes the planes beside
-    it) and the ``la3d_depth16`` block rides along as ``a.d16`` - ``_launch`` picks the entry by it.
+    it) and the ``la3d_depth16`` block rides along as ``a.d16`` - ``_enqueue`` picks the entry by it -, or that block itself, ready made
+    (the flat buffer of a frames call).
     Built fresh for every call: one InstanceFitter may be driven from several threads and streams."""
     d16 = None
     if isinstance(depth, Depth16):
         _depth16_check(depth, (H, W), "the call's frame")
         d16, depth, planes = _depth16_block(depth, H, W), None, 1
+    elif isinstance(depth, _lib.Depth16Block):
+        d16, depth, planes = depth, None, 1
     a = FitArgs(struct_size=C.sizeof(FitArgs), B=B, H=H, W=W, depth=depth, depth_plane_stride=H * W if planes > 1 else 0,
                 image_index=image_index, mask=mask, K=K, k_stride=9 if nk > 1 else 0, ground=ground, sample_idx=sample_idx,
                 out=out, status=status, aux=aux, workspace=workspace, stream=stream, area_hint=area_hint, frame_width=frame_width,
@@ -409,14 +415,21 @@ def _check_image_index(given, ii, B, P):
         raise ValueError("image_index out of range")
 
 
-def _fit_inputs(depth, K, image_index, ground, sample_idx, B, H, W, dev, frame, check_device_index=False, given_index=None):
+def _fit_inputs(depth, K, image_index, ground, sample_idx, B, H, W, dev, frame, check_device_index=False, given_index=None, planes=None,
+                expand_K=True, check_host_index=True):
     """The inputs every fit entry shares, checked against the call's B masks of H x W and on the device: depth (P,H,W) | (H,W)
     float32, K (P,3,3) | (3,3) float64 (a shared matrix is expanded to P), image_index (B,) int32, ground (B,4) float64,
     sample_idx (B,500) int32; None stays None.  ``frame`` names the masks in the error text.  The range of a host image_index is
     checked on the host (``given_index``: the array as the caller gave it, when it has been uploaded already); a device tensor's
     only with ``check_device_index`` (a ~40 us read-back).  Returns (depth, K, image_index, ground, sample_idx, P).
-    A ``Depth16`` stays what it is - 16-bit planes where they lie, checked, ``data`` as (P,H,W) -; anything else becomes float32."""
-    if isinstance(depth, Depth16):
+    A ``Depth16`` stays what it is - 16-bit planes where they lie, checked, ``data`` as (P,H,W) -; anything else becomes float32.
+    ``planes``: the frames call - P comes from its frame table and ``depth`` (the flat buffer, checked by its wrapper) is passed through
+    untouched.  That call differs in two more ways, kept as they are: ``expand_K=False`` - a shared K stays one matrix (``k_stride``
+    0) instead of one per plane -, and ``check_host_index=False`` - the range of a host image_index is left to the device as well,
+    where an index outside gives status 5 instead of an exception."""
+    if planes is not None:
+        d, dshape = depth, (planes, H, W)
+    elif isinstance(depth, Depth16):
         _depth16_check(depth, (H, W), frame)
         if depth.data.is_cuda and depth.data.device != dev:
             raise ValueError("the Depth16 planes live on another device")
@@ -436,7 +449,7 @@ def _fit_inputs(depth, K, image_index, ground, sample_idx, B, H, W, dev, frame, 
     P = dshape[0]
     if k.shape[0] not in (1, P) or k.shape[1:] != (3, 3):
         raise ValueError("K must be (3,3) or (P,3,3)")
-    if k.shape[0] == 1 and P > 1:
+    if expand_K and k.shape[0] == 1 and P > 1:
         k = k.expand(P, 3, 3).contiguous()
     ii = None
     if image_index is not None:
@@ -444,7 +457,7 @@ def _fit_inputs(depth, K, image_index, ground, sample_idx, B, H, W, dev, frame, 
         if ii.shape != (B,):
             raise ValueError("image_index must be (B,)")
         given = image_index if given_index is None else given_index
-        if check_device_index or not (isinstance(given, torch.Tensor) and given.is_cuda):
+        if check_device_index or (check_host_index and not (isinstance(given, torch.Tensor) and given.is_cuda)):
             _check_image_index(given, ii, B, P)
     elif P not in (1, B):
         raise ValueError("without image_index, depth must have 1 or B planes")
@@ -480,6 +493,27 @@ def pad_rows_f32(d: torch.Tensor, Wp: int) -> torch.Tensor:
         out = torch.empty(d.shape[:-1] + (Wp,), dtype=torch.float32, device=d.device)
         check(lib.la3d_pad_rows(_ptr(d), d.numel() // W, W, Wp, _ptr(out), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "la3d_pad_rows")
     return out
+
+
+def padded_width(W: int) -> int:
+    """The row length the tiled / single-pass forms of the fit want: the next multiple of 32."""
+    return (int(W) + 31) // 32 * 32
+
+
+def pad_depth_rows(depth, device=None):
+    """Depth plane(s) (..., H, W) -> ((..., H, padded_width(W)) float32 on the device, W): rows padded on the right with zeros.
+    COCO frames come in widths like 427, 500, 375, 333; with run-length / polygon masks such a frame is fitted as a frame of the
+    padded width whose first W columns are image (C-ABI ``la3d_fit_args::frame_width``): 4-5 x faster than the row-linear form
+    that odd widths otherwise take (profiles/r05/r05_frame_sizes.txt).  ``fit_instances_ex`` / ``fit_instances_rle`` /
+    ``fit_instances_poly`` / ``fit_annotations*`` do this themselves; a caller that fits the same planes many times pads once and
+    passes ``frame_width=W``."""
+    dev = _dev(device)
+    d = _as_dev(depth, torch.float32, dev)
+    W = int(d.shape[-1])
+    Wp = padded_width(W)
+    if Wp == W:
+        return d, W
+    return pad_rows_f32(d, Wp), W
 
 
 def fit_instances(depth, masks, K, ground=None, sample_idx=None, image_index=None, stream=None, device=None, method: str = "pca"):

@@ -43,7 +43,7 @@ from ._lib import lib, method_code
 from .batched import Depth16, _dev, _upload_many, draw_sample_idx, refuse_depth16
 from .jsonout import SceneRecords, format_scenes
 from .masks import (PackedFrames, PackedFrames16, fit_instances_ex, fit_instances_frames, frame_table, mask_stats_poly, mask_stats_rle, pack_polygons, pack_rle,
-                    pack_rle_frames, pad_depth_rows, padded_width)
+                    pack_rle_frames, pad_depth_rows, padded_width, area_hint_of, split_annotations)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 OUT_NAME = "3dbbox.json"
@@ -200,6 +200,20 @@ class _Prepared:
     __slots__ = ("scenes", "H", "W", "depth", "K", "groups", "ready", "h2d0", "parity", "t_pack", "t_load", "nbytes", "grounds")
 
 
+def _group_annotations(scenes: List[dict]) -> dict:
+    """The annotations of a batch of scenes by segmentation kind, as the reference's reader takes them (``split_annotations``: crowd
+    annotations and annotations without a segmentation are skipped, src/util.py:355-358): per kind the segmentations in scene order
+    with each one's image, annotation index, ``area`` and category."""
+    groups = {kind: {"seg": [], "img": [], "ann": [], "area": [], "cat": []} for kind in ("rle", "poly")}
+    for p, sc in enumerate(scenes):
+        ann = sc["annotations"]
+        for kind, (idx, segs) in split_annotations(ann).items():
+            g = groups[kind]
+            g["seg"] += segs; g["img"] += [p] * len(idx); g["ann"] += idx
+            g["area"] += [ann[j].get("area") for j in idx]; g["cat"] += [int(ann[j]["category_id"]) for j in idx]
+    return groups
+
+
 class ScenePipeline:
     """See the module docstring.  ``run(scenes)`` yields ``(scene, records)`` with ``records`` a ``SceneRecords``: the text of the scene's
     ``3dbbox.json`` (``.text``, also written to ``scene['dir']`` when the scene has one and ``write=True``) that behaves like the list
@@ -281,22 +295,13 @@ class ScenePipeline:
                 plane[:, w:] = 0
         loads = [self.pool.submit(load_range, t) for t in range(nthr)]
         tp0 = time.perf_counter()
-        groups = {"rle": {"seg": [], "img": [], "ann": [], "area": [], "cat": []}, "poly": {"seg": [], "img": [], "ann": [], "area": [], "cat": []}}
-        for p, sc in enumerate(scenes):
-            for j, a in enumerate(sc["annotations"]):
-                if a.get("iscrowd") or "segmentation" not in a:
-                    continue
-                seg = a["segmentation"]
-                kind = "rle" if isinstance(seg, dict) and "counts" in seg else "poly"
-                g = groups[kind]
-                g["seg"].append({"size": seg["size"], "counts": seg["counts"]} if kind == "rle" else seg)
-                g["img"].append(p); g["ann"].append(j); g["area"].append(a.get("area")); g["cat"].append(int(a["category_id"]))
+        groups = _group_annotations(scenes)
         pr.grounds = [(_ground_files(sc["dir"]) if "dir" in sc else {}) if "ground" not in sc else sc["ground"] for sc in scenes]
         packed = {}
         for kind, g in groups.items():
             if not g["seg"]:
                 continue
-            hint = None if any(v is None for v in g["area"]) else np.clip(np.asarray(g["area"], dtype=np.float64), 0, 2**31 - 1).astype(np.int32)
+            hint = area_hint_of(g["area"])
             if kind == "rle":
                 counts, offsets, rsz = pack_rle_frames(g["seg"])
                 want = np.asarray(sizes, np.int64)[np.asarray(g["img"], np.int64)]
@@ -376,23 +381,13 @@ class ScenePipeline:
         else:
             loads = [self.pool.submit(load_range, t) for t in range(nthr)]   # np.load / memmove release the GIL: they run WHILE this thread packs
         tp0 = time.perf_counter()
-        # the reference's reader: crowd annotations and annotations without a segmentation are skipped (src/util.py:355-358)
-        groups = {"rle": {"seg": [], "img": [], "ann": [], "area": [], "cat": []}, "poly": {"seg": [], "img": [], "ann": [], "area": [], "cat": []}}
-        for p, sc in enumerate(scenes):
-            for j, a in enumerate(sc["annotations"]):
-                if a.get("iscrowd") or "segmentation" not in a:
-                    continue
-                seg = a["segmentation"]
-                kind = "rle" if isinstance(seg, dict) and "counts" in seg else "poly"
-                g = groups[kind]
-                g["seg"].append({"size": seg["size"], "counts": seg["counts"]} if kind == "rle" else seg)
-                g["img"].append(p); g["ann"].append(j); g["area"].append(a.get("area")); g["cat"].append(int(a["category_id"]))
+        groups = _group_annotations(scenes)
         pr.grounds = [(_ground_files(sc["dir"]) if "dir" in sc else {}) if "ground" not in sc else sc["ground"] for sc in scenes]
         packed = {}
         for kind, g in groups.items():
             if not g["seg"]:
                 continue
-            hint = None if any(v is None for v in g["area"]) else np.clip(np.asarray(g["area"], dtype=np.float64), 0, 2**31 - 1).astype(np.int32)
+            hint = area_hint_of(g["area"])
             if kind == "rle":
                 counts, offsets, Hh, Ww = pack_rle(g["seg"])
                 if (Hh, Ww) != (H, W):

@@ -29,11 +29,11 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import _lib, options
+from . import _lib
 from ._lib import AUX, BOX_FILTERED, REC, check, lib
-from .batched import (InstanceFitter, _as_dev, _bits_stride, _bulk, _dev, _filter_args, _fit_args, _fit_inputs, _ptr, _record, _stream,  # noqa: F401
-                      _upload_many, height_rule_code, pad_rows_f32, Depth16, _depth16_block, _depth16_check, _launch, _pad_rows16,
-                      refuse_depth16)
+from .batched import (Depth16, InstanceFitter, _as_dev, _bits_stride, _d16_block, _depth16_block, _depth16_check, _dev, _fit_args, _ptr, _record,
+                      _stream, _upload_many, height_rule_code, pad_depth_rows, padded_width, refuse_depth16)
+from .fitcall import FramesDepth, depth_rows, fit_call, mask_source
 
 
 def rle_from_string(s) -> np.ndarray:
@@ -57,7 +57,13 @@ def pack_rle(rles):
     if len(sizes) > 1:
         raise ValueError("all masks of one batch must share the frame size")
     H, W = sizes.pop() if sizes else (0, 0)
-    cs = [r["counts"] for r in rles]
+    counts, offsets = _rle_counts([r["counts"] for r in rles])
+    return counts, offsets, int(H), int(W)
+
+
+def _rle_counts(cs):
+    """The ``counts`` of a batch of COCO RLE objects (lists, compressed strings, arrays) -> (counts int32 (T,), offsets int64 (B+1,));
+    an empty batch gives one zero count (the kernels take no NULL)."""
     if cs and all(type(c) is list for c in cs):   # uncompressed run lengths as the JSON holds them: one conversion loop for the batch
         lens = np.fromiter(map(len, cs), np.int64, len(cs))
         counts = np.fromiter(itertools.chain.from_iterable(cs), np.int64, int(lens.sum())).astype(np.int32)
@@ -69,7 +75,7 @@ def pack_rle(rles):
         counts = np.concatenate(parts).astype(np.int32) if parts and offsets[-1] else np.zeros(1, np.int32)
     if not len(counts):
         counts = np.zeros(1, np.int32)
-    return counts, offsets, int(H), int(W)
+    return counts, offsets
 
 
 def rle_decode(rles, device=None, stream=None) -> torch.Tensor:
@@ -201,52 +207,17 @@ def filter_annotations(annotations, image_size, boundary_threshold: int = 10, sc
     ``annotations`` and their raw COCO category ids (the reference maps those to super-category names with a table that is
     not part of this path)."""
     W_img, H_img = int(image_size[0]), int(image_size[1])
-    rle_c, rle_i, poly_c, poly_i = [], [], [], []
-    for i, a in enumerate(annotations):
-        if a.get("iscrowd"):
-            continue
-        if "segmentation" not in a:
-            continue
-        seg = a["segmentation"]
-        if isinstance(seg, dict) and "counts" in seg:
-            rle_c.append({"size": seg["size"], "counts": seg["counts"]})
-            rle_i.append(i)
-        else:
-            poly_c.append(seg)
-            poly_i.append(i)
     keep = {}
-    if rle_c:
-        k = keep_instances(mask_stats_rle(rle_c, boundary_threshold, device=device), H_img, from_rle=True,
-                           scale_threshold=scale_threshold).cpu().numpy()
-        keep.update({i: (bool(f), c) for i, f, c in zip(rle_i, k, rle_c)})
-    if poly_c:
-        k = keep_instances(mask_stats_poly(pack_polygons(poly_c, H_img, W_img), boundary_threshold, device=device), H_img,
-                           from_rle=False, scale_threshold=scale_threshold).cpu().numpy()
-        keep.update({i: (bool(f), c) for i, f, c in zip(poly_i, k, poly_c)})
+    for kind, (idx, segs) in split_annotations(annotations).items():
+        if not idx:
+            continue
+        st = (mask_stats_rle(segs, boundary_threshold, device=device) if kind == "rle"
+              else mask_stats_poly(pack_polygons(segs, H_img, W_img), boundary_threshold, device=device))
+        k = keep_instances(st, H_img, from_rle=kind == "rle", scale_threshold=scale_threshold).cpu().numpy()
+        keep.update({i: (bool(f), c) for i, f, c in zip(idx, k, segs)})
     kept = [i for i in sorted(keep) if keep[i][0]]
     return ([annotations[i]["bbox"] for i in kept], [keep[i][1] for i in kept], np.asarray(kept, np.int64),
             [annotations[i]["category_id"] for i in kept])
-
-
-def padded_width(W: int) -> int:
-    """The row length the tiled / single-pass forms of the fit want: the next multiple of 32."""
-    return (int(W) + 31) // 32 * 32
-
-
-def pad_depth_rows(depth, device=None):
-    """Depth plane(s) (..., H, W) -> ((..., H, padded_width(W)) float32 on the device, W): rows padded on the right with zeros.
-    COCO frames come in widths like 427, 500, 375, 333; with run-length / polygon masks such a frame is fitted as a frame of the
-    padded width whose first W columns are image (C-ABI ``la3d_fit_args::frame_width``): 4-5 x faster than the row-linear form
-    that odd widths otherwise take (profiles/r05/r05_frame_sizes.txt).  ``fit_instances_ex`` / ``fit_instances_rle`` /
-    ``fit_instances_poly`` / ``fit_annotations*`` do this themselves; a caller that fits the same planes many times pads once and
-    passes ``frame_width=W``."""
-    dev = _dev(device)
-    d = _as_dev(depth, torch.float32, dev)
-    W = int(d.shape[-1])
-    Wp = padded_width(W)
-    if Wp == W:
-        return d, W
-    return pad_rows_f32(d, Wp), W
 
 
 def fit_instances_ex(depth, K, masks=None, rles=None, polys=None, ground=None, sample_idx=None, image_index=None, filter=None,
@@ -262,7 +233,7 @@ def fit_instances_ex(depth, K, masks=None, rles=None, polys=None, ground=None, s
     of 32 has its depth rows padded here (``pad_depth_rows``); an int - ``depth`` already IS padded (its last dimension is the padded
     width) and the masks' frame is ``frame_width`` columns wide.  ``method``: "pca" | "convex_hull" (see ``fit_instances``).
     Returns a dict: boxes, status, aux, and stats / boxes2d when asked."""
-    meth = _lib.method_code(method)   # (the reference's error for an unknown method, before any device work)
+    _lib.method_code(method)   # (the reference's error for an unknown method, before any device work)
     is16 = isinstance(depth, Depth16)   # 16-bit planes, fitted where they lie (C-ABI ``la3d_fit_instances_depth16``)
     if is16:
         _depth16_check(depth)
@@ -271,76 +242,29 @@ def fit_instances_ex(depth, K, masks=None, rles=None, polys=None, ground=None, s
     dev = _dev(device)
     if (masks is not None) + (rles is not None) + (polys is not None) != 1:
         raise ValueError("give exactly one of masks / rles / polys")
-    given_index = image_index   # (a host image_index is range-checked on the host, before the upload below)
-    if masks is not None:
-        m = _as_dev(masks, torch.uint8, dev)
-        B, H, W = m.shape
-        kind, keep, what = dict(mask=_ptr(m)), [m], "mask"
-    elif rles is not None:
-        counts, offsets, H, W = pack_rle(rles)
-        counts, offsets, ground, image_index, sample_idx, area_hint = _bulk(
-            dev, (counts, torch.int32), (offsets, torch.int64), (ground, torch.float64), (image_index, torch.int32), (sample_idx, torch.int32),
-            (area_hint, torch.int32))
-        c, o = _as_dev(counts, torch.int32, dev), _as_dev(offsets, torch.int64, dev)
-        B = o.numel() - 1
-        kind, keep, what = dict(rle=(_ptr(c), _ptr(o))), [c, o], "RLE"
-    else:
-        pxy, pro, pir, H, W = polys
-        pxy, pro, pir, ground, image_index, sample_idx, area_hint = _bulk(
-            dev, (pxy, torch.int32), (pro, torch.int64), (pir, torch.int64), (ground, torch.float64), (image_index, torch.int32),
-            (sample_idx, torch.int32), (area_hint, torch.int32))
-        xy, ro, ir, H, W = _poly_dev((pxy, pro, pir, H, W), dev)
-        B = ir.numel() - 1
-        kind, keep, what = dict(poly=(_ptr(xy), _ptr(ro), _ptr(ir))), [xy, ro, ir], "polygon"
+    # (a host image_index is range-checked on the host as the caller gave it: ``given_index`` below; it goes up with the masks here)
+    src, ground, ii, sample_idx, area_hint = mask_source(dev, masks=masks, rles=None if rles is None else pack_rle(rles), polys=polys,
+                                                         small=(ground, image_index, sample_idx, area_hint))
     if filter and masks is not None:
         raise ValueError("the fused filter needs run-length or polygon masks")
-    fw = 0
+    H, W, fw = src.H, src.W, 0
     if masks is None:
-        if frame_width is None:
-            if W % 32 != 0:
-                with torch.cuda.device(dev):
-                    if is16:
-                        _depth16_check(depth, (H, W), f"the {what} frame")
-                        depth, fw = _pad_rows16(depth, padded_width(W)), W
-                    else:
-                        depth, fw = pad_depth_rows(depth, dev)
-                W = padded_width(W)
-        else:
+        if frame_width is None:   # rows of a width that is no multiple of 32 are padded here
+            if is16 and W % 32 != 0:
+                _depth16_check(depth, (H, W), f"the {src.what} frame")
+            stored = padded_width(W)
+        else:                     # the depth IS padded already: its last dimension is the stored width
             if int(frame_width) != W:
-                raise ValueError(f"frame_width {frame_width} does not match the {what} frame width {W}")
-            Wd = int((depth.data if is16 else depth).shape[-1])
-            if Wd != W:
-                if Wd < W or Wd % 32 != 0:
-                    raise ValueError("padded depth rows must be a multiple of 32 wide and at least frame_width")
-                fw, W = W, Wd
-    d, k, ii, g, si, P = _fit_inputs(depth, K, image_index, ground, sample_idx, B, H, W, dev, f"the {what} frame",
-                                     given_index=given_index)
-    out = {}
-    with torch.cuda.device(dev):
-        # (_fitter / _stats: buffers a per-image caller keeps between calls - fit_annotations - instead of allocating them per call)
-        f = _fitter if _fitter is not None else InstanceFitter(B, H, W, dev, method=method)
-        if f.B < B or (f.H, f.W) != (H, W) or (meth != f.method and meth != _lib.METHOD_PCA):
-            raise ValueError("_fitter too small for this call")
-        out.update(boxes=f.boxes[0][:B], status=f.status[0][:B], aux=f.aux[0][:B])   # (a kept fitter may have more rows than this call)
-        if filter:
-            out["stats"] = _stats if _stats is not None else torch.zeros((B, 4), dtype=torch.int32, device=dev)
-        if image_size is not None:
-            out["boxes2d"] = torch.full((B, 8), float("nan"), dtype=torch.float64, device=dev)
-        if B == 0:
-            return out
-        ah = None
-        if area_hint is not None:
-            ah = _as_dev(area_hint, torch.int32, dev).reshape(-1)
-            if ah.numel() != B:
-                raise ValueError("area_hint must have one entry per instance")
-            keep.append(ah)
-        a = _fit_args(B, H, W, d if is16 else _ptr(d), P, _ptr(k), k.shape[0], _ptr(f.boxes[0]), _ptr(f.status[0]), _ptr(f.aux[0]),
-                      _ptr(f.workspace[0]), _stream(stream), image_index=_ptr(ii), ground=_ptr(g), sample_idx=_ptr(si), filter=filter,
-                      stats=_ptr(out.get("stats")), proj=_ptr(out.get("boxes2d")), image_size=image_size, area_hint=_ptr(ah),
-                      opts=options.codes(), frame_width=fw, method=meth, **kind)
-        _launch(a)
-    _record(stream, d, k, ii, g, si, *keep, f.workspace, *out.values())
-    return out
+                raise ValueError(f"frame_width {frame_width} does not match the {src.what} frame width {W}")
+            stored = int((depth.data if is16 else depth).shape[-1])
+            if stored != W and (stored < W or stored % 32 != 0):
+                raise ValueError("padded depth rows must be a multiple of 32 wide and at least frame_width")
+        depth, fw = depth_rows(depth, stored, W, dev, pad=frame_width is None)
+        W = stored
+    # (_fitter / _stats: buffers a per-image caller keeps between calls - fit_annotations - instead of allocating them per call)
+    return fit_call(src, depth, K, dev, H, W, image_index=ii, ground=ground, sample_idx=sample_idx, area_hint=area_hint, filter=filter,
+                    image_size=image_size, stream=stream, method=method, frame_width=fw, given_index=image_index, fitter=_fitter,
+                    stats=_stats)
 
 
 _ANN_CACHE: dict = {}   # (B, H, W, device) -> (InstanceFitter, stats, pinned read-back buffer): the per-image pattern repeats a few shapes
@@ -384,49 +308,30 @@ def fit_annotations(annotations, image_size, depth, K, ground=None, boundary_thr
     _lib.method_code(method)   # (the reference's error for an unknown method, before any device work)
     W_img, H_img = int(image_size[0]), int(image_size[1])
     dev = _dev(device)
-    groups = split_annotations(annotations)
+    split = split_annotations(annotations)
     flt = {"boundary_threshold": boundary_threshold, "scale_threshold": scale_threshold}
     if (to_host and isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous()
             and not isinstance(K, torch.Tensor) and not isinstance(ground, torch.Tensor) and not isinstance(image_index, torch.Tensor)):
-        return _fit_annotations_host(annotations, groups, W_img, H_img, depth, K, ground, image_index, flt, method)
-    Wp = padded_width(W_img)
-    if Wp != W_img and any(idx for idx, _ in groups.values()):   # a frame of odd width: rows padded once for both segmentation kinds
+        return _fit_annotations_host(annotations, split, W_img, H_img, depth, K, ground, image_index, flt, method)
+    groups = _annotation_groups(annotations, ground, image_index, split=split)
+    if padded_width(W_img) != W_img and groups:   # a frame of odd width: rows padded once for both segmentation kinds
         with torch.cuda.device(dev):
             depth, _ = pad_depth_rows(depth, dev)
     sels, box_all, st_all, pins = [], [], [], []
-    for kind, (idx, segs) in groups.items():
-        if not idx:
-            continue
-        sel = np.asarray(idx, np.int64)
-        g = None if ground is None else (ground[torch.as_tensor(sel, device=ground.device)] if isinstance(ground, torch.Tensor)
-                                         else np.asarray(ground, dtype=np.float64)[sel])
-        ii = None if image_index is None else (image_index[torch.as_tensor(sel, device=image_index.device)]
-                                               if isinstance(image_index, torch.Tensor) else np.asarray(image_index)[sel])
-        # the annotation's own "area" (COCO: the mask area in pixels), when every annotation of the group has one, spares the launch
-        # order its estimate pass
-        ar = [annotations[i].get("area") for i in idx]
-        hint = None if any(v is None for v in ar) else np.clip(np.asarray(ar, dtype=np.float64), 0, 2**31 - 1).astype(np.int32)
+    for kind, sel, segs, g, ii, hint, _ in groups:
         # every small host array of the group goes up in ONE copy (six to eight separate uploads cost ~100 us per image)
         host = lambda v: None if isinstance(v, torch.Tensor) else v     # noqa: E731   (device tensors pass through as they are)
-        if kind == "rle":
-            counts, offsets, Hh, Ww = pack_rle(segs)
-            up = _upload_many([(counts, torch.int32), (offsets, torch.int64), (host(g), torch.float64), (host(ii), torch.int32),
-                               (hint, torch.int32), (host(K), torch.float64)], dev)
-            kw = dict(rles=(up[0], up[1], Hh, Ww))
-        else:
-            xy, ro, ir, Hh, Ww = pack_polygons(segs, H_img, W_img)
-            up = _upload_many([(xy, torch.int32), (ro, torch.int64), (ir, torch.int64), (host(g), torch.float64), (host(ii), torch.int32),
-                               (hint, torch.int32), (host(K), torch.float64)], dev)
-            kw = dict(polys=(up[0], up[1], up[2], Hh, Ww))
-        g_d = up[-4] if up[-4] is not None else g
-        ii_d = up[-3] if up[-3] is not None else ii
-        K_d = up[-1] if up[-1] is not None else K
-        fitter, stats_buf, pin = _ann_buffers(len(idx), Hh, padded_width(Ww), dev, kind, method)
-        res = fit_instances_ex(depth, K_d, ground=g_d, image_index=ii_d, device=dev, filter=flt, area_hint=up[-2], _fitter=fitter,
-                               _stats=stats_buf, frame_width=Ww, method=method, **kw)
+        packed = pack_rle(segs) if kind == "rle" else pack_polygons(segs, H_img, W_img)
+        *arrays, Hh, Ww = packed
+        *up, g_u, ii_u, hint_u, K_u = _upload_many(list(zip(arrays, (torch.int32, torch.int64, torch.int64))) + [
+            (host(g), torch.float64), (host(ii), torch.int32), (hint, torch.int32), (host(K), torch.float64)], dev)
+        fitter, stats_buf, pin = _ann_buffers(len(sel), Hh, padded_width(Ww), dev, kind, method)
+        res = fit_instances_ex(depth, K_u if K_u is not None else K, ground=g_u if g_u is not None else g,
+                               image_index=ii_u if ii_u is not None else ii, device=dev, filter=flt, area_hint=hint_u, _fitter=fitter,
+                               _stats=stats_buf, frame_width=Ww, method=method, **{"rles" if kind == "rle" else "polys": (*up, Hh, Ww)})
         head = fitter._arena[:pin.numel()]
         pin.copy_(head, non_blocking=True)      # records | aux | status of this group: one copy, read after the one synchronisation
-        sels.append(sel); box_all.append(res["boxes"]); st_all.append(res["status"]); pins.append((pin, len(idx)))
+        sels.append(sel); box_all.append(res["boxes"]); st_all.append(res["status"]); pins.append((pin, len(sel)))
     if not sels:
         return [], np.zeros(0, np.int64), [], torch.zeros((0, 39), dtype=torch.float64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev)
     torch.cuda.current_stream(dev).synchronize()          # the one synchronisation of the call
@@ -437,19 +342,14 @@ def fit_annotations(annotations, image_size, depth, K, ground=None, boundary_thr
         nb, na = n * REC * 8, n * AUX * 8
         hb.append(raw[:nb].view(np.float64).reshape(n, REC))
         hs.append(raw[up8(nb) + up8(na):up8(nb) + up8(na) + n * 4].view(np.int32))
-    st_host = hs[0] if len(hs) == 1 else np.concatenate(hs)
-    sel_c = np.concatenate(sels)
-    pos = np.nonzero(st_host != 6)[0]                     # kept rows of the concatenated results ...
-    pos = pos[np.argsort(sel_c[pos], kind="stable")]      # ... in annotation order
-    kept = sel_c[pos]
+    pos, st_host, head = _annotation_order(annotations, sels, hs)
     if to_host:
         bh = hb[0] if len(hb) == 1 else np.concatenate(hb)
-        return ([annotations[i]["bbox"] for i in kept], kept, [annotations[i]["category_id"] for i in kept], bh[pos].copy(), st_host[pos].copy())
+        return head + (bh[pos].copy(), st_host[pos].copy())
     boxes_c = box_all[0] if len(box_all) == 1 else torch.cat(box_all)
     status_c = st_all[0] if len(st_all) == 1 else torch.cat(st_all)
     pt = torch.as_tensor(pos, device=dev)
-    return ([annotations[i]["bbox"] for i in kept], kept, [annotations[i]["category_id"] for i in kept],
-            boxes_c.index_select(0, pt), status_c.index_select(0, pt))
+    return head + (boxes_c.index_select(0, pt), status_c.index_select(0, pt))
 
 
 def split_annotations(annotations):
@@ -465,6 +365,46 @@ def split_annotations(annotations):
         groups[kind][0].append(i)
         groups[kind][1].append({"size": seg["size"], "counts": seg["counts"]} if kind == "rle" else seg)
     return groups
+
+
+def area_hint_of(areas):
+    """The ``area`` fields of a group of annotations (COCO: the mask area in pixels) as the ``area_hint`` of its fit call - it spares
+    the launch order its estimate pass -, or None unless every annotation of the group has one."""
+    return None if None in areas else np.clip(np.asarray(areas, dtype=np.float64), 0, 2**31 - 1).astype(np.int32)
+
+
+def _annotation_groups(annotations, ground=None, image_index=None, dev=None, split=None):
+    """THE walk over the annotations by segmentation kind (``split_annotations``): per kind present, ``(kind, sel, segmentations,
+    ground rows, image_index rows, area_hint, sel_t)`` - ``sel`` the int64 annotation indices of the kind, the rows of ``ground`` /
+    ``image_index`` they select (NumPy for host arrays; a tensor is indexed where it lies, or - ``dev`` given, as
+    ``fit_annotations_all`` does - on ``dev``), the hint from the annotations' ``area``, and with ``dev`` the indices on it.  ``split``: the result of
+    ``split_annotations`` where the caller has it already."""
+    groups = []
+    for kind, (idx, segs) in (split_annotations(annotations) if split is None else split).items():
+        if idx:
+            sel = np.asarray(idx, np.int64)
+            sel_t = None if dev is None else torch.as_tensor(sel, device=dev)
+            groups.append((kind, sel, segs, None if ground is None else _rows(ground, sel, sel_t),
+                           None if image_index is None else _rows(image_index, sel, sel_t),
+                           area_hint_of([annotations[i].get("area") for i in idx]), sel_t))
+    return groups
+
+
+def _rows(v, sel, sel_t):
+    if not isinstance(v, torch.Tensor):
+        return np.asarray(v)[sel]
+    return v.to(sel_t.device)[sel_t] if sel_t is not None else v[torch.as_tensor(sel, device=v.device)]
+
+
+def _annotation_order(annotations, sels, statuses):
+    """The kept rows of per-kind results, back in annotation order: -> (positions in the concatenated results, the concatenated
+    status, (bboxes, kept_index, category_ids)) - what ``fit_annotations`` returns ahead of the records."""
+    sel_c = sels[0] if len(sels) == 1 else np.concatenate(sels)
+    st = statuses[0] if len(statuses) == 1 else np.concatenate(statuses)
+    pos = np.nonzero(st != BOX_FILTERED)[0]               # kept rows of the concatenated results ...
+    pos = pos[np.argsort(sel_c[pos], kind="stable")]      # ... in annotation order
+    kept = sel_c[pos]
+    return pos, st, ([annotations[i]["bbox"] for i in kept], kept, [annotations[i]["category_id"] for i in kept])
 
 
 def annotation_areas(annotations, default: float = 0.0) -> np.ndarray:
@@ -490,21 +430,14 @@ def fit_annotations_all(annotations, image_size, depth, K, ground=None, image_in
     flt = None
     if filter:
         flt = {"boundary_threshold": 10, "scale_threshold": 100} if filter is True else dict(filter)
-    groups = split_annotations(annotations)
-    if W_img % 32 != 0 and any(idx for idx, _ in groups.values()):   # a frame of odd width: rows padded once for both kinds
+    groups = _annotation_groups(annotations, ground, image_index, dev)
+    if W_img % 32 != 0 and groups:   # a frame of odd width: rows padded once for both kinds
         with torch.cuda.device(dev):
             depth, _ = pad_depth_rows(depth, dev)
-    for kind, (idx, segs) in groups.items():
-        if not idx:
-            continue
-        sel = np.asarray(idx, np.int64)
-        sel_t = torch.as_tensor(sel, device=dev)
-        take = lambda v: None if v is None else (v.to(dev)[sel_t] if isinstance(v, torch.Tensor) else np.asarray(v)[sel])  # noqa: E731
-        ar = [annotations[i].get("area") for i in idx]
-        hint = None if any(v is None for v in ar) else np.clip(np.asarray(ar, dtype=np.float64), 0, 2**31 - 1).astype(np.int32)
+    for kind, _, segs, g, ii, hint, sel_t in groups:
         kw = dict(rles=segs) if kind == "rle" else dict(polys=pack_polygons(segs, H_img, W_img))
-        res = fit_instances_ex(depth, K, ground=take(ground), image_index=take(image_index), device=dev, filter=flt, area_hint=hint,
-                               frame_width=W_img, method=method, **kw)
+        res = fit_instances_ex(depth, K, ground=g, image_index=ii, device=dev, filter=flt, area_hint=hint, frame_width=W_img,
+                               method=method, **kw)
         boxes.index_copy_(0, sel_t, res["boxes"])
         status.index_copy_(0, sel_t, res["status"])
     return boxes, status
@@ -519,7 +452,7 @@ def _raw_stream(dev_index: int) -> int:
         return torch.cuda.current_stream(dev_index).cuda_stream
 
 
-def _fit_annotations_host(annotations, groups, W_img, H_img, depth, K, ground, image_index, flt, method="pca"):
+def _fit_annotations_host(annotations, split, W_img, H_img, depth, K, ground, image_index, flt, method="pca"):
     """``fit_annotations(to_host=True)`` with the depth plane(s) resident and everything else on the host: ONE foreign call per
     segmentation kind (``la3d_fit_annotations_host``: the small arrays go up through the library's pinned block, the records come back
     through it, the call polls a completion flag) - no torch tensor, no wrapper layers in between."""
@@ -531,13 +464,16 @@ def _fit_annotations_host(annotations, groups, W_img, H_img, depth, K, ground, i
     Kh = np.ascontiguousarray(np.asarray(K, dtype=np.float64).reshape(-1, 9))
     if Kh.shape[0] not in (1, P):
         raise ValueError("K must be (3,3) or (P,3,3)")
+    groups = _annotation_groups(annotations, None, image_index, split=split)
+    if not groups:
+        return [], np.zeros(0, np.int64), [], np.zeros((0, REC)), np.zeros(0, np.int32)
     host = lambda v: None if v is None else v.ctypes.data   # noqa: E731
+    # the C entry enqueues on the stream it is handed, on the thread's CURRENT device: the depth's device, and the stream the
+    # depth (and the padding above) was produced on - torch's current stream of that device
+    meth, stream, elsewhere = _lib.method_code(method), _raw_stream(dev_index), dev_index != torch.cuda.current_device()
     sels, recs, sts = [], [], []
-    for kind, (idx, segs) in groups.items():
-        if not idx:
-            continue
-        sel = np.asarray(idx, np.int64)
-        B = len(idx)
+    for kind, sel, segs, g, ii, hint, _ in groups:
+        B = len(sel)
         if kind == "rle":
             counts, offsets, Hh, Ww = pack_rle(segs)
             masks_kw = dict(rle=(counts.ctypes.data, offsets.ctypes.data))
@@ -546,9 +482,8 @@ def _fit_annotations_host(annotations, groups, W_img, H_img, depth, K, ground, i
             masks_kw = dict(poly=(xy.ctypes.data, ro.ctypes.data, ir.ctypes.data))
         if (Hh, Ww) != (H_img, W_img) or depth.shape[-2:] != (Hh, Wp):
             raise ValueError(f"depth {tuple(depth.shape[-2:])} / image size {(H_img, W_img)} do not match the mask size {(Hh, Ww)}")
-        ii = g = hint = None
-        if image_index is not None:
-            ii = np.ascontiguousarray(np.asarray(image_index)[sel], np.int32)
+        if ii is not None:
+            ii = np.ascontiguousarray(ii, np.int32)
             if ii.size and (ii.min() < 0 or ii.max() >= P):
                 raise ValueError("image_index out of range")
         elif P > 1:
@@ -558,31 +493,20 @@ def _fit_annotations_host(annotations, groups, W_img, H_img, depth, K, ground, i
             ii = sel.astype(np.int32)
         if ground is not None:
             g = np.ascontiguousarray(np.asarray(ground, dtype=np.float64).reshape(-1, 4)[sel])
-        ar = [annotations[i].get("area") for i in idx]
-        if not any(v is None for v in ar):
-            hint = np.clip(np.asarray(ar, dtype=np.float64), 0, 2**31 - 1).astype(np.int32)
         out = np.empty((B, REC), np.float64)
         st = np.empty(B, np.int32)
-        # the C entry enqueues on the stream it is handed, on the thread's CURRENT device: the depth's device, and the stream the
-        # depth (and the padding above) was produced on - torch's current stream of that device
         a = _fit_args(B, Hh, Wp, depth.data_ptr(), P, Kh.ctypes.data, Kh.shape[0], out.ctypes.data, st.ctypes.data, None, None,
-                      _raw_stream(dev_index), image_index=host(ii), ground=host(g), area_hint=host(hint), filter=flt,
-                      frame_width=Ww if Wp != Ww else 0, method=_lib.method_code(method), **masks_kw)
-        if dev_index == torch.cuda.current_device():
-            check(lib.la3d_fit_annotations_host(C.byref(a)), "la3d_fit_annotations_host")
-        else:
+                      stream, image_index=host(ii), ground=host(g), area_hint=host(hint), filter=flt,
+                      frame_width=Ww if Wp != Ww else 0, method=meth, **masks_kw)
+        if elsewhere:
             with torch.cuda.device(dev_index):
                 check(lib.la3d_fit_annotations_host(C.byref(a)), "la3d_fit_annotations_host")
+        else:
+            check(lib.la3d_fit_annotations_host(C.byref(a)), "la3d_fit_annotations_host")
         sels.append(sel); recs.append(out); sts.append(st)
-    if not sels:
-        return [], np.zeros(0, np.int64), [], np.zeros((0, REC)), np.zeros(0, np.int32)
-    sel_c = sels[0] if len(sels) == 1 else np.concatenate(sels)
-    st_c = sts[0] if len(sts) == 1 else np.concatenate(sts)
+    pos, st_c, head = _annotation_order(annotations, sels, sts)
     rec_c = recs[0] if len(recs) == 1 else np.concatenate(recs)
-    pos = np.nonzero(st_c != BOX_FILTERED)[0]
-    pos = pos[np.argsort(sel_c[pos], kind="stable")]
-    kept = sel_c[pos]
-    return ([annotations[i]["bbox"] for i in kept], kept, [annotations[i]["category_id"] for i in kept], rec_c[pos], st_c[pos])
+    return head + (rec_c[pos], st_c[pos])
 
 
 def segmentations_to_masks(segmentations, H: int, W: int, device=None) -> torch.Tensor:
@@ -748,7 +672,7 @@ def fit_instances_bits(depth, bits, K, ground=None, sample_idx=None, image_index
     (``pad_depth_rows``).  ``frame_width``: None, or the image width, checked against the planes'.  ``height_rule``: the height the
     fused filter uses - "rows" (rows holding a pixel, the reference's rule for run-length annotations) or "span" (last - first + 1,
     its rule for polygons); a bit plane does not say where it came from."""
-    meth = _lib.method_code(method)   # (the reference's error for an unknown method, before any device work)
+    _lib.method_code(method)   # (the reference's error for an unknown method, before any device work)
     flags = height_rule_code(height_rule)
     is16 = isinstance(depth, Depth16)
     if is16:
@@ -757,38 +681,17 @@ def fit_instances_bits(depth, bits, K, ground=None, sample_idx=None, image_index
     dev = mb.bits.device if device is None else _dev(device)
     if mb.bits.device != dev:
         raise ValueError("the bit planes live on another device")
-    B, H, W, fw = mb.bits.shape[0], mb.H, mb.W, mb.frame_width
+    W, fw = mb.W, mb.frame_width
     if frame_width is not None and int(frame_width) != fw:
         raise ValueError(f"frame_width {frame_width} does not match the bit planes' frame width {fw}")
     Wd = int((depth.data if is16 else depth).shape[-1])
-    if Wd != W:
-        if Wd != fw or padded_width(fw) != W:
-            raise ValueError(f"depth rows of {Wd} pixels match neither the stored width {W} nor the frame width {fw} of the bit planes")
-        with torch.cuda.device(dev):
-            if is16:
-                depth = _pad_rows16(depth, W)
-            else:
-                depth, _ = pad_depth_rows(depth, dev)
-    d, k, ii, g, si, P = _fit_inputs(depth, K, image_index, ground, sample_idx, B, H, W, dev, "the bit-plane frame")
-    with torch.cuda.device(dev):
-        f = InstanceFitter(B, H, W, dev, method=method)
-        stats = torch.zeros((B, 4), dtype=torch.int32, device=dev) if filter else None
-        boxes2d = torch.full((B, 8), float("nan"), dtype=torch.float64, device=dev) if image_size is not None else None
-        res = (f.boxes[0], f.status[0], f.aux[0]) + ((stats,) if filter else ()) + ((boxes2d,) if image_size is not None else ())
-        if B == 0:
-            return res
-        ah = None
-        if area_hint is not None:
-            ah = _as_dev(area_hint, torch.int32, dev).reshape(-1)
-            if ah.numel() != B:
-                raise ValueError("area_hint must have one entry per instance")
-        a = _fit_args(B, H, W, d if is16 else _ptr(d), P, _ptr(k), k.shape[0], _ptr(f.boxes[0]), _ptr(f.status[0]), _ptr(f.aux[0]),
-                      _ptr(f.workspace[0]), _stream(stream), image_index=_ptr(ii), ground=_ptr(g), sample_idx=_ptr(si), filter=filter,
-                      stats=_ptr(stats), proj=_ptr(boxes2d), image_size=image_size, area_hint=_ptr(ah), opts=options.codes(),
-                      frame_width=0 if fw == W else fw, method=meth)
-        _launch(a, (_ptr(mb.bits), _bits_stride(mb.bits, B, H, W), flags))
-    _record(stream, d, k, ii, g, si, ah, mb.bits, f.workspace, *res)
-    return res
+    if Wd != W and (Wd != fw or padded_width(fw) != W):
+        raise ValueError(f"depth rows of {Wd} pixels match neither the stored width {W} nor the frame width {fw} of the bit planes")
+    depth, fw = depth_rows(depth, W, fw, dev, pad=Wd != W)
+    out = fit_call(mask_source(dev, bits=(mb, flags))[0], depth, K, dev, mb.H, W, image_index=image_index, ground=ground,
+                   sample_idx=sample_idx, area_hint=area_hint, filter=filter, image_size=image_size, stream=stream, method=method,
+                   frame_width=fw)
+    return tuple(out.values())
 
 
 class LabelBits(NamedTuple):
@@ -1084,45 +987,6 @@ def _words16(m, p: int, dtype: str):
     return np.ascontiguousarray(a).view(np.int16)
 
 
-def _pack_frames16(maps, dev, pinned, dtype, scale, zero_is_hole) -> PackedFrames16:
-    if dtype not in _D16_DTYPES:
-        raise ValueError(f"unknown dtype: {dtype!r}. Use None (float32), 'f16' or 'u16'")
-    tdt = _D16_DTYPES[dtype][0]
-    if dtype == "u16" and not (np.isfinite(np.float32(scale)) and np.float32(scale) > 0):
-        raise ValueError(f"scale must be finite and > 0 (as float32), not {scale!r}")
-    for p, m in enumerate(maps):
-        if len(m.shape) != 2:
-            raise ValueError(f"depth map {p} must be (H, W), got {tuple(m.shape)}")
-    words = [_words16(m, p, dtype) for p, m in enumerate(maps)]
-    sizes = [(int(m.shape[0]), int(m.shape[1])) for m in maps]
-    table = frame_table(sizes)   # (offsets in ELEMENTS: multiples of 32, so every 16-bit plane is 8-byte aligned)
-    total = int(sum(int(r["H"]) * int(r["W"]) for r in table))
-    n = max(total, 4)
-    if any(isinstance(w, torch.Tensor) and w.is_cuda for w in words):
-        flat = torch.zeros(n, dtype=torch.int16, device=dev)
-        for w16, r in zip(words, table):
-            o, h, wp, w = int(r["depth_offset"]), int(r["H"]), int(r["W"]), int(r["frame_width"])
-            flat[o:o + h * wp].view(h, wp)[:, :w].copy_(torch.as_tensor(w16).to(dev))
-        flat = flat.view(tdt)
-    else:
-        if pinned is not None and pinned.dtype == tdt and pinned.numel() >= n:
-            host_t = pinned[:n]
-        else:
-            pinned, host_t = None, torch.empty(n, dtype=tdt)
-        host = host_t.view(torch.int16).numpy()
-        for w16, r in zip(words, table):
-            o, h, wp, w = int(r["depth_offset"]), int(r["H"]), int(r["W"]), int(r["frame_width"])
-            dst = host[o:o + h * wp].reshape(h, wp)
-            dst[:, :w] = w16.numpy() if isinstance(w16, torch.Tensor) else w16
-            dst[:, w:] = 0
-        host[total:] = 0
-        flat = host_t if dev.type == "cpu" else host_t.view(torch.int16).to(dev, non_blocking=pinned is not None).view(tdt)
-    rows = np.ascontiguousarray(table).view(np.int32).reshape(len(maps), 6) if len(maps) else np.zeros((0, 6), np.int32)
-    tab = torch.as_tensor(rows.copy(), device=dev)
-    return PackedFrames16(flat, tab, table, max((h for h, _ in sizes), default=0), max((int(r["W"]) for r in table), default=0), sizes,
-                          float(scale) if dtype == "u16" else 1.0, bool(zero_is_hole))
-
-
 def pack_frames(depth_maps, device=None, pinned=None, dtype=None, scale: float = 0.001, zero_is_hole: bool = True):
     """Depth maps of DIFFERENT sizes -> ``PackedFrames``: one flat float32 buffer on the device, each plane at its own pitch
     (``padded_width``) and 16-byte aligned offset, the padding zero, plus the device frame table ``fit_instances_frames`` takes.
@@ -1135,35 +999,46 @@ def pack_frames(depth_maps, device=None, pinned=None, dtype=None, scale: float =
     planes, see ``Depth16``; ``pinned``: a pinned staging tensor of the 16-bit dtype), fitted where it lies by ``fit_instances_frames``."""
     dev = torch.device(device) if device is not None and torch.device(device).type == "cpu" else _dev(device)
     maps = list(depth_maps)
-    if dtype is not None:
-        return _pack_frames16(maps, dev, pinned, dtype, scale, zero_is_hole)
+    if dtype is not None and dtype not in _D16_DTYPES:
+        raise ValueError(f"unknown dtype: {dtype!r}. Use None (float32), 'f16' or 'u16'")
+    tdt = torch.float32 if dtype is None else _D16_DTYPES[dtype][0]
+    if dtype == "u16" and not (np.isfinite(np.float32(scale)) and np.float32(scale) > 0):
+        raise ValueError(f"scale must be finite and > 0 (as float32), not {scale!r}")
     for p, m in enumerate(maps):
         if len(m.shape) != 2:
             raise ValueError(f"depth map {p} must be (H, W), got {tuple(m.shape)}")
+    # the element the copies move: float32 (anything is converted), or the int16 bit pattern of a 16-bit map (nothing is)
+    wdt = torch.float32 if dtype is None else torch.int16
+    if dtype is not None:
+        maps = [_words16(m, p, dtype) for p, m in enumerate(maps)]
     sizes = [(int(m.shape[0]), int(m.shape[1])) for m in maps]
-    table = frame_table(sizes)
+    table = frame_table(sizes)   # (offsets in ELEMENTS: multiples of 32, so a float32 plane is 16-byte and a 16-bit plane 8-byte aligned)
     total = int(sum(int(r["H"]) * int(r["W"]) for r in table))
+    n = max(total, 4)
+    rows = [(int(r["depth_offset"]), int(r["H"]), int(r["W"]), int(r["frame_width"])) for r in table]
     if any(isinstance(m, torch.Tensor) and m.is_cuda for m in maps):
-        flat = torch.zeros(max(total, 4), dtype=torch.float32, device=dev)
-        for m, r in zip(maps, table):
-            o, h, wp, w = int(r["depth_offset"]), int(r["H"]), int(r["W"]), int(r["frame_width"])
-            flat[o:o + h * wp].view(h, wp)[:, :w].copy_(torch.as_tensor(m).to(device=dev, dtype=torch.float32))
+        flat = torch.zeros(n, dtype=wdt, device=dev)
+        for m, (o, h, wp, w) in zip(maps, rows):
+            flat[o:o + h * wp].view(h, wp)[:, :w].copy_(torch.as_tensor(m).to(device=dev, dtype=wdt))
+        flat = flat.view(tdt)
     else:
-        if pinned is not None and pinned.dtype == torch.float32 and pinned.numel() >= max(total, 4):
-            host_t = pinned[:max(total, 4)]
+        if pinned is not None and pinned.dtype == tdt and pinned.numel() >= n:
+            host_t = pinned[:n]
         else:
-            pinned, host_t = None, torch.empty(max(total, 4), dtype=torch.float32)
-        host = host_t.numpy()
-        for m, r in zip(maps, table):
-            o, h, wp, w = int(r["depth_offset"]), int(r["H"]), int(r["W"]), int(r["frame_width"])
+            pinned, host_t = None, torch.empty(n, dtype=tdt)
+        host = host_t.view(wdt).numpy()
+        for m, (o, h, wp, w) in zip(maps, rows):
             dst = host[o:o + h * wp].reshape(h, wp)
             dst[:, :w] = m.numpy() if isinstance(m, torch.Tensor) else np.asarray(m)
-            dst[:, w:] = 0.0
-        host[total:] = 0.0
-        flat = host_t if dev.type == "cpu" else host_t.to(dev, non_blocking=pinned is not None)
+            dst[:, w:] = 0
+        host[total:] = 0
+        flat = host_t if dev.type == "cpu" else host_t.view(wdt).to(dev, non_blocking=pinned is not None).view(tdt)
     words = np.ascontiguousarray(table).view(np.int32).reshape(len(maps), 6) if len(maps) else np.zeros((0, 6), np.int32)
     tab = torch.as_tensor(words.copy(), device=dev)
-    return PackedFrames(flat, tab, table, max((h for h, _ in sizes), default=0), max((int(r["W"]) for r in table), default=0), sizes)
+    bounds = (max((h for h, _ in sizes), default=0), max((wp for _, _, wp, _ in rows), default=0))
+    if dtype is None:
+        return PackedFrames(flat, tab, table, *bounds, sizes)
+    return PackedFrames16(flat, tab, table, *bounds, sizes, float(scale) if dtype == "u16" else 1.0, bool(zero_is_hole))
 
 
 def pack_rle_frames(rles):
@@ -1172,10 +1047,7 @@ def pack_rle_frames(rles):
     if isinstance(rles, tuple):
         counts, offsets = rles[0], rles[1]
         return counts, offsets, None
-    parts = [rle_from_string(r["counts"]) if isinstance(r["counts"], (str, bytes)) else np.asarray(r["counts"], dtype=np.int32) for r in rles]
-    offsets = np.zeros(len(parts) + 1, np.int64)
-    np.cumsum([len(p) for p in parts], out=offsets[1:])
-    counts = np.concatenate(parts).astype(np.int32) if parts and offsets[-1] else np.zeros(1, np.int32)
+    counts, offsets = _rle_counts([r["counts"] for r in rles])
     sizes = np.asarray([tuple(r["size"]) for r in rles], np.int64).reshape(-1, 2)
     return counts, offsets, sizes
 
@@ -1212,82 +1084,23 @@ def fit_instances_frames(frames, K, rles=None, polys=None, image_index=None, gro
     if not fdepth.is_cuda:
         raise ValueError("frames must live on the GPU (pack_frames with a GPU device)")
     dev = fdepth.device
-    P = int(frames.table.shape[0])
     if rles is not None:
         counts, offsets, sizes = pack_rle_frames(rles)
         if sizes is not None and not (isinstance(image_index, torch.Tensor) and image_index.is_cuda):
             ii_h = np.asarray(image_index.numpy() if isinstance(image_index, torch.Tensor) else image_index).reshape(-1)
-            ok = (ii_h >= 0) & (ii_h < P)
+            ok = (ii_h >= 0) & (ii_h < int(frames.table.shape[0]))
             if len(ii_h) == len(sizes) and ok.any():
                 want = np.asarray(frames.sizes, np.int64).reshape(-1, 2)[ii_h[ok]]
                 if (sizes[ok] != want).any():
                     raise ValueError("an RLE annotation's size differs from the size of its image")
-        counts, offsets, ground, image_index, sample_idx, area_hint = _bulk(
-            dev, (counts, torch.int32), (offsets, torch.int64), (ground, torch.float64), (image_index, torch.int32), (sample_idx, torch.int32),
-            (area_hint, torch.int32))
-        c, o = _as_dev(counts, torch.int32, dev), _as_dev(offsets, torch.int64, dev)
-        B = o.numel() - 1
-        kind, keep = dict(rle=(_ptr(c), _ptr(o))), [c, o]
+        given = dict(rles=(counts, offsets, None, None))
     else:
-        pxy, pro, pir = polys[0], polys[1], polys[2]
-        pxy, pro, pir, ground, image_index, sample_idx, area_hint = _bulk(
-            dev, (pxy, torch.int32), (pro, torch.int64), (pir, torch.int64), (ground, torch.float64), (image_index, torch.int32),
-            (sample_idx, torch.int32), (area_hint, torch.int32))
-        xy, ro, ir = _as_dev(pxy, torch.int32, dev), _as_dev(pro, torch.int64, dev), _as_dev(pir, torch.int64, dev)
-        B = ir.numel() - 1
-        kind, keep = dict(poly=(_ptr(xy), _ptr(ro), _ptr(ir))), [xy, ro, ir]
-    k = _as_dev(K, torch.float64, dev, cache=True)
-    if k.dim() == 2:
-        k = k[None]
-    if k.shape[0] not in (1, P) or k.shape[1:] != (3, 3):
-        raise ValueError("K must be (3,3) or (P,3,3)")
-    ii = _as_dev(image_index, torch.int32, dev)
-    if ii.shape != (B,):
-        raise ValueError("image_index must be (B,)")
-    g = None
-    if ground is not None:
-        g = _as_dev(ground, torch.float64, dev)
-        if g.shape != (B, 4):
-            raise ValueError("ground must be (B,4)")
-    si = None
-    if sample_idx is not None:
-        si = _as_dev(sample_idx, torch.int32, dev)
-        if si.shape != (B, _lib.NSAMPLE):
-            raise ValueError("sample_idx must be (B,500)")
-    H, W = max(int(frames.H), 1), max(int(frames.W), 1)
-    out = {}
-    with torch.cuda.device(dev):
-        # (_fitter: buffers a caller keeps between calls - fit_scenes -, sized for at least this call's B and bounds)
-        f = _fitter if _fitter is not None else InstanceFitter(B, H, W, dev)
-        if f.B < B or f.H < H or f.W < W:
-            raise ValueError("_fitter too small for this call")
-        out.update(boxes=f.boxes[0][:B], status=f.status[0][:B], aux=f.aux[0][:B])
-        if filter:
-            out["stats"] = torch.zeros((B, 4), dtype=torch.int32, device=dev)
-        if proj:
-            out["boxes2d"] = torch.full((B, 8), float("nan"), dtype=torch.float64, device=dev)
-        if B == 0:
-            return out
-        ah = None
-        if area_hint is not None:
-            ah = _as_dev(area_hint, torch.int32, dev).reshape(-1)
-            if ah.numel() != B:
-                raise ValueError("area_hint must have one entry per instance")
-            keep.append(ah)
-        a = _fit_args(B, H, W, None if is16 else _ptr(fdepth), 1, _ptr(k), k.shape[0], _ptr(f.boxes[0]), _ptr(f.status[0]), _ptr(f.aux[0]),
-                      _ptr(f.workspace[0]), _stream(stream), image_index=_ptr(ii), ground=_ptr(g), sample_idx=_ptr(si), filter=filter,
-                      stats=_ptr(out.get("stats")), proj=_ptr(out.get("boxes2d")), image_size=(1, 1) if proj else None,
-                      area_hint=_ptr(ah), opts=options.codes(), **kind)
-        if is16:
-            u16 = fdepth.dtype == torch.uint16
-            blk = _lib.Depth16Block(struct_size=C.sizeof(_lib.Depth16Block), dtype=_lib.DTYPE_U16 if u16 else _lib.DTYPE_F16,
-                                    planes=fdepth.data_ptr(), plane_stride=0, scale=float(frames.scale) if u16 else 1.0,
-                                    flags=_lib.DEPTH_ZERO_IS_HOLE if (u16 and frames.zero_is_hole) else 0)
-            check(lib.la3d_fit_instances_frames_depth16(C.byref(a), C.byref(blk), _ptr(frames.table), P), "la3d_fit_instances_frames_depth16")
-        else:
-            check(lib.la3d_fit_instances_frames(C.byref(a), _ptr(frames.table), P), "la3d_fit_instances_frames")
-    _record(stream, fdepth, frames.table, k, ii, g, si, *keep, f.workspace, *out.values())
-    return out
+        given = dict(polys=(polys[0], polys[1], polys[2], None, None))   # (their H, W are ignored: every instance has its own frame)
+    src, ground, ii, sample_idx, area_hint = mask_source(dev, small=(ground, image_index, sample_idx, area_hint), **given)
+    depth = FramesDepth(fdepth, frames.table, _d16_block(fdepth, frames.scale, frames.zero_is_hole) if is16 else None)
+    # (_fitter: buffers a caller keeps between calls - fit_scenes -, sized for at least this call's B and bounds)
+    return fit_call(src, depth, K, dev, frames.H, frames.W, image_index=ii, ground=ground, sample_idx=sample_idx, area_hint=area_hint,
+                    filter=filter, image_size=(1, 1) if proj else None, stream=stream, method=method, fitter=_fitter)
 
 
 def masked_ratio_median(depth_map, depth_render, mask, render_mask=None, image_index=None, stream=None):
