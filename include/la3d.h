@@ -466,7 +466,8 @@ int la3d_unpack_depth16(const la3d_depth16* src, int P, int H, int W_in, int W, 
  *   - run lengths are column-major over the instance's own (H, frame_width); polygon sides are clipped to the instance's own
  *     frame_width x H; the fused filter takes H and the right and bottom borders from the instance's frame;
  *   - masks: rle_counts (+ rle_offsets) or poly_xy (+ ring_offsets, inst_rings) - the annotation formats.  mask (u8 planes) and
- *     bit planes: LA3D_ERR_UNSUPPORTED.  method = LA3D_METHOD_CONVEX_HULL: LA3D_ERR_UNSUPPORTED in this first form;
+ *     bit planes: LA3D_ERR_UNSUPPORTED (bit planes - and with them label maps - have an entry of their own:
+ *     la3d_fit_instances_frames_bits, below).  method = LA3D_METHOD_CONVEX_HULL: LA3D_ERR_UNSUPPORTED in this first form;
  *   - ground, sample_idx (reference-subsample mode), filter_* + stats, proj, aux, area_hint, opt_launch_order, stream mean what they
  *     mean in la3d_fit_instances_ex.  The call runs on the instance engine (opt_engine pins give way, as for bit planes), in its
  *     tiled form.  The size-balanced launch order runs when area_hint is given (same batch range as elsewhere); without a hint
@@ -495,7 +496,50 @@ int la3d_unpack_depth16(const la3d_depth16* src, int P, int H, int W_in, int W, 
  * Refused before any launch (LA3D_ERR_ARG / LA3D_ERR_UNSUPPORTED) is what either parent entry refuses: a bad block or la3d_depth16
  * (struct_size, dtype, scale, flags), a non-zero plane_stride, a misaligned base, u8 or bit-plane masks, LA3D_METHOD_CONVEX_HULL, a
  * missing image_index, a non-zero depth_plane_stride or frame_width in the block, bounds beyond the tiled form.  Workspace:
- * la3d_fit_workspace_bytes(args). */
+ * la3d_fit_workspace_bytes(args).
+ *
+ * la3d_fit_instances_frames_bits(args, depth16, frames, P, mask_bits, bits_offsets, bits_flags): the same call with the masks given as
+ * bit planes ("masks as bit planes" above), one plane per instance, each as large as its OWN frame - what a panoptic dataset needs: one
+ * label map per image (la3d_pack_label_bits_frames below makes the planes) and hundreds of frame sizes.
+ *   - args, frames and P mean what they mean in la3d_fit_instances_frames (H, W are bounds; image_index is required;
+ *     depth_plane_stride and frame_width of the block must be 0; proj clamps to the instance's own frame; the fused filter takes its
+ *     borders from the instance's frame).  depth16 == NULL: float32 planes in args->depth, 16-byte aligned.  depth16 != NULL: the rules
+ *     of la3d_fit_instances_frames_depth16 - args->depth NULL, plane_stride 0, an 8-byte aligned base, depth_offset in 16-bit elements;
+ *   - args->mask, rle_counts and poly_xy must be NULL (LA3D_ERR_ARG): the masks are the bit planes;
+ *   - the plane of instance n starts bits_offsets[n] words behind mask_bits (bits_offsets: DEVICE i64 [B]) and holds the
+ *     H_f * W_f / 32 words of the frame of instance n, W_f being the pitch - a multiple of 32, so rows are whole words -, in the bit
+ *     layout of la3d_fit_instances_bits.  The bits of columns >= frame_width MUST be zero (la3d_pack_label_bits_frames guarantees it).
+ *     mask_bits must be 16-byte aligned - checked before any launch: LA3D_ERR_ARG -, and every bits_offsets[n] >= 0 and a multiple of
+ *     4: every plane then streams into LDS in 16-byte groups.  Planes may repeat, overlap or lie in any order;
+ *   - the offsets are checked ON THE DEVICE, next to the frame row and by the same rule: an instance whose offset is negative or not a
+ *     multiple of 4 gets LA3D_BOX_UNSUPPORTED and the NaN record / aux / proj a broken frame row gives, decided before any address is
+ *     formed from the offset; the call and every other instance are unaffected.  An instance whose frame row is broken is refused
+ *     before its offset is even loaded.  What a conforming offset addresses must lie inside the caller's buffer;
+ *   - ground, sample_idx (reference-subsample mode), filter_* + stats, proj, aux, area_hint, opt_launch_order and stream mean what they
+ *     mean in la3d_fit_instances_frames; the height rule of the fused filter comes from bits_flags (LA3D_BITS_HEIGHT_ROWS /
+ *     LA3D_BITS_HEIGHT_SPAN; other bits: LA3D_ERR_ARG).  The size-balanced launch order runs only with area_hint, as there;
+ *   - method = LA3D_METHOD_CONVEX_HULL: LA3D_ERR_UNSUPPORTED, as for every frames call.  Everything else either parent entry refuses
+ *     before a launch is refused here.  Workspace: la3d_fit_workspace_bytes(args).
+ * The records are those of la3d_fit_instances_frames on run lengths of the same masks, bit for bit: the same kernel on the same bit
+ * image in LDS.
+ *
+ * la3d_pack_label_bits_frames: la3d_pack_label_bits ("masks as label maps" above) for label maps of DIFFERENT sizes in one buffer.
+ *   labels: dev, 16-byte aligned; image p lies frames[p].depth_offset ELEMENTS (pixels for RGB8) behind it, its rows frames[p].W
+ *     elements apart, frames[p].H rows of frames[p].frame_width image columns - a label buffer packed the way the depth is packed has
+ *     exactly the depth's table: ONE table serves this packer and the fit.  H, W: the bounds of the table (as in the fit);
+ *   inst_offsets dev [P+1], inst_label dev [B], area dev [B] | NULL: as in la3d_pack_label_bits;
+ *   bits, bits_offsets dev i64 [B]: the plane of row b is written at bits + bits_offsets[b]: the H_f * W_f / 32 words of its image's
+ *     frame, every word of them and nothing else.
+ * VALUE: the rule of la3d_pack_label_bits (compared as int32; an id outside the dtype: an all-zero plane; repeated rows each get their
+ *   plane), and: bits of columns >= frame_width are ZERO WHATEVER THE PADDING ELEMENTS HOLD (RGB8: they are not even read) - id 0
+ *   asked of a zero-padded map marks image pixels only.
+ * Rows of an image whose frame row breaks the la3d_frame contract (the check of the fit, made on the device), and rows whose
+ *   bits_offsets entry is negative or not a multiple of 4, are NOT written and nothing is read through either: exactly the instances
+ *   the fit then refuses.  Their area stays 0.
+ * U8 / U16 / I32 planes are read in 16-byte groups where they are 16-byte aligned (every I32 plane; U8 / U16 planes at offsets that are
+ *   multiples of 16 / 8 elements - what back-to-back packing gives) and in 4-byte loads otherwise; RGB8 byte by byte.
+ * LA3D_ERR_ARG: an unknown dtype, negative sizes, bounds beyond H * roundup32(W) <= 2^28, misaligned or NULL pointers with work to do.
+ *   B == 0 or P == 0: success, nothing is done.  The call is capturable (area is cleared by a kernel of the call). */
 typedef struct la3d_frame {      /* one row per IMAGE, device-resident */
   int64_t depth_offset;          /* elements from the base of the depth buffer to this image's plane, % 4 == 0: floats from args->depth
                                     (la3d_fit_instances_frames), 16-bit words from depth->planes (la3d_fit_instances_frames_depth16) */
@@ -505,6 +549,12 @@ typedef struct la3d_frame {      /* one row per IMAGE, device-resident */
 } la3d_frame;
 int la3d_fit_instances_frames(const la3d_fit_args* args, const la3d_frame* frames, int32_t P);
 int la3d_fit_instances_frames_depth16(const la3d_fit_args* args, const la3d_depth16* depth, const la3d_frame* frames, int32_t P);
+int la3d_fit_instances_frames_bits(const la3d_fit_args* args, const la3d_depth16* depth16 /* NULL: float32 planes in args->depth */,
+                                   const la3d_frame* frames, int32_t P,
+                                   const uint32_t* mask_bits, const int64_t* bits_offsets /* dev [B] */, int32_t bits_flags);
+int la3d_pack_label_bits_frames(const void* labels, int dtype, const la3d_frame* frames, int32_t P, int H, int W /* bounds */,
+                                const int32_t* inst_offsets /* dev [P+1] */, const int32_t* inst_label /* dev [B] */, int B,
+                                uint32_t* bits, const int64_t* bits_offsets /* dev [B] */, int32_t* area /* dev [B] or NULL */, void* stream);
 
 /* create_boolean_mask_from_polygon for a batch: polygon parts -> u8 planes mask_out dev [B][H*W] (0/1). */
 int la3d_poly_decode(const int32_t* poly_xy, const int64_t* ring_offsets, const int64_t* inst_rings, int B, int H, int W,

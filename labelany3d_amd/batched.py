@@ -177,11 +177,14 @@ def refuse_depth16(depth, who: str) -> None:
 
 def _enqueue(a: FitArgs, bits=None, frames=None) -> None:
     """The C entry of a block built by ``_fit_args``, picked from what the call carries: a frame table (``frames`` = (pointer, P);
-    with 16-bit depth - ``a.d16`` - its depth16 form), 16-bit depth planes, bit planes (``bits`` = (pointer, stride, flags)), or the
-    plain block."""
+    with 16-bit depth - ``a.d16`` - its depth16 form; with ``bits`` = (pointer, offsets pointer, flags) its bit-plane form), 16-bit
+    depth planes, bit planes (``bits`` = (pointer, stride, flags)), or the plain block."""
     d16 = getattr(a, "d16", None)
     if frames is not None:
-        if d16 is not None:
+        if bits is not None:
+            check(lib.la3d_fit_instances_frames_bits(C.byref(a), None if d16 is None else C.byref(d16), frames[0], frames[1], bits[0], bits[1],
+                                                     bits[2]), "la3d_fit_instances_frames_bits")
+        elif d16 is not None:
             check(lib.la3d_fit_instances_frames_depth16(C.byref(a), C.byref(d16), frames[0], frames[1]), "la3d_fit_instances_frames_depth16")
         else:
             check(lib.la3d_fit_instances_frames(C.byref(a), frames[0], frames[1]), "la3d_fit_instances_frames")

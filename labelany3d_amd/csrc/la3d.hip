@@ -174,7 +174,8 @@ size_t la3d_fit_workspace_bytes(const la3d_fit_args* args) {
   return up256(base) + (size_t)args->B * (full > samp ? full : samp);
 }
 
-struct BitsSource { const uint32_t* planes; int64_t plane_stride; int32_t flags; };   // la3d_fit_instances_bits' own arguments
+// la3d_fit_instances_bits' own arguments; offsets: the per-instance plane offsets of la3d_fit_instances_frames_bits (plane_stride is then 0)
+struct BitsSource { const uint32_t* planes; int64_t plane_stride; int32_t flags; const int64_t* offsets = nullptr; };
 struct FramesSource { const la3d_frame* rows; int32_t P; };                           // la3d_fit_instances_frames' own arguments
 struct Depth16Source { const la3d_depth16* d; };                                      // la3d_fit_instances_depth16's own argument (checked there)
 
@@ -184,6 +185,7 @@ struct Depth16Source { const la3d_depth16* d; };                                
 // fr: the frame table of la3d_fit_instances_frames (H, W of the block are then bounds), null for every other entry.
 // ds: the 16-bit depth planes of la3d_fit_instances_depth16 (a.depth is then null), null for every other entry but
 // la3d_fit_instances_frames_depth16, which gives fr AND ds: the frame rows then count their depth_offset in 16-bit elements.
+// la3d_fit_instances_frames_bits gives bs (with its offsets) AND fr, and ds for 16-bit planes.
 static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who, const BitsSource* bs = nullptr,
                         const FramesSource* fr = nullptr, const Depth16Source* ds = nullptr) {
   const int B = a.B;
@@ -224,6 +226,7 @@ static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who,
     p.mask_bits = bs->planes; p.bits_plane_stride = bs->plane_stride;
     p.bits_vec = ((reinterpret_cast<uintptr_t>(bs->planes) & 15) == 0 && bs->plane_stride % 4 == 0) ? 1 : 0;
     p.bits_span = (bs->flags & LA3D_BITS_HEIGHT_SPAN) ? 1 : 0;
+    p.bits_offsets = reinterpret_cast<const long long*>(bs->offsets);
   }
   p.B = B; p.H = H; p.W = W; p.HW = H * W;
   p.nwords = (p.HW + 31) / 32;
@@ -572,7 +575,8 @@ int la3d_fit_instances_depth16(const la3d_fit_args* args, const la3d_depth16* de
 }
 
 // what la3d_fit_instances_frames and la3d_fit_instances_frames_depth16 check alike on the copied block and the frame table
-static int check_frames_call(la3d_fit_args& a, const la3d_frame* frames, int32_t P, const char* who) {
+// (bits: la3d_fit_instances_frames_bits, whose masks are its own arguments - it has refused mask / rle_counts / poly_xy itself)
+static int check_frames_call(la3d_fit_args& a, const la3d_frame* frames, int32_t P, const char* who, bool bits = false) {
   static_assert(sizeof(la3d_frame) == 24, "la3d_frame is part of the ABI");
   if (a.mask) {
     snprintf(g_err, sizeof(g_err), "%s: u8 mask planes are not supported - run lengths or polygon parts", who);
@@ -583,7 +587,7 @@ static int check_frames_call(la3d_fit_args& a, const la3d_frame* frames, int32_t
     return LA3D_ERR_UNSUPPORTED;
   }
   const int kinds = (a.rle_counts ? 1 : 0) + (a.poly_xy ? 1 : 0);
-  if (kinds != 1 && a.B > 0) {
+  if (!bits && kinds != 1 && a.B > 0) {
     snprintf(g_err, sizeof(g_err), "%s: give exactly one of rle_counts / poly_xy", who);
     return LA3D_ERR_ARG;
   }
@@ -659,6 +663,66 @@ int la3d_fit_instances_frames_depth16(const la3d_fit_args* args, const la3d_dept
   const FramesSource fs{frames, P};
   const Depth16Source ds{depth};
   return fit_dispatch(a, a.filter_boundary >= 0 && a.filter_max_edge > 0, who, nullptr, &fs, &ds);
+}
+
+// the frames call on bit planes, one plane per instance at its own offset: the checks of la3d_fit_instances_frames (with depth16: of
+// la3d_fit_instances_frames_depth16) and of la3d_fit_instances_bits, then fit_dispatch with the sources of both
+int la3d_fit_instances_frames_bits(const la3d_fit_args* args, const la3d_depth16* depth16, const la3d_frame* frames, int32_t P,
+                                   const uint32_t* mask_bits, const int64_t* bits_offsets, int32_t bits_flags) {
+  const char* who = "la3d_fit_instances_frames_bits";
+  constexpr int32_t V1_SIZE = (int32_t)offsetof(la3d_fit_args, area_hint);
+  int rc = LA3D_SUCCESS;
+  if (depth16) {
+    rc = depth16_block_head(args, depth16, who);
+    if (rc != LA3D_SUCCESS) return rc;
+  } else if (!args || args->struct_size < V1_SIZE) {
+    snprintf(g_err, sizeof(g_err), "%s: bad struct_size", who);
+    return LA3D_ERR_ARG;
+  }
+  la3d_fit_args a;
+  memset(&a, 0, sizeof(a));
+  memcpy(&a, args, (size_t)args->struct_size < sizeof(a) ? (size_t)args->struct_size : sizeof(a));
+  if (depth16) {
+    if (a.depth) {
+      snprintf(g_err, sizeof(g_err), "%s: the depth planes come in the la3d_depth16 block - args->depth must be NULL", who);
+      return LA3D_ERR_ARG;
+    }
+    rc = depth16_block_values(depth16, who);
+    if (rc != LA3D_SUCCESS) return rc;
+    if (depth16->plane_stride != 0) {
+      snprintf(g_err, sizeof(g_err), "%s: plane_stride of the la3d_depth16 block must be 0 (the frame table says where every plane lies)", who);
+      return LA3D_ERR_ARG;
+    }
+  }
+  if (a.mask || a.rle_counts || a.poly_xy) {
+    snprintf(g_err, sizeof(g_err), "%s: the masks are the bit planes - mask, rle_counts and poly_xy must be NULL", who);
+    return LA3D_ERR_ARG;
+  }
+  if (bits_flags & ~(int32_t)LA3D_BITS_HEIGHT_SPAN) {
+    snprintf(g_err, sizeof(g_err), "%s: unknown bits_flags (LA3D_BITS_HEIGHT_ROWS or LA3D_BITS_HEIGHT_SPAN)", who);
+    return LA3D_ERR_ARG;
+  }
+  rc = check_frames_call(a, frames, P, who, true);
+  if (rc != LA3D_SUCCESS) return rc;
+  if (a.B > 0 && (!mask_bits || (reinterpret_cast<uintptr_t>(mask_bits) & 15))) {
+    snprintf(g_err, sizeof(g_err), "%s: mask_bits must be a 16-byte aligned device pointer", who);
+    return LA3D_ERR_ARG;
+  }
+  if (a.B > 0 && (!bits_offsets || (reinterpret_cast<uintptr_t>(bits_offsets) & 7))) {
+    snprintf(g_err, sizeof(g_err), "%s: bits_offsets must be an 8-byte aligned device pointer to B plane offsets", who);
+    return LA3D_ERR_ARG;
+  }
+  if (depth16 ? (reinterpret_cast<uintptr_t>(depth16->planes) & 7) != 0 : (reinterpret_cast<uintptr_t>(a.depth) & 15) != 0) {
+    snprintf(g_err, sizeof(g_err), depth16 ? "%s: planes (the base of the ragged buffer) must be 8-byte aligned" : "%s: depth must be 16-byte aligned", who);
+    return LA3D_ERR_ARG;
+  }
+  a.image_width = a.image_height = 1.0;   // (ignored: proj clamps to the instance's own frame)
+  rc = check_block_options(a, who);
+  if (rc != LA3D_SUCCESS) return rc;
+  const BitsSource bs{mask_bits, 0, bits_flags, bits_offsets};
+  const FramesSource fs{frames, P};
+  const Depth16Source ds{depth16};
+  return fit_dispatch(a, a.filter_boundary >= 0 && a.filter_max_edge > 0, who, &bs, &fs, depth16 ? &ds : nullptr);
 }
 
 }  // extern "C"

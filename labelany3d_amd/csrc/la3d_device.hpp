@@ -542,6 +542,9 @@ struct FitParams {
   const la3d_frame* frames = nullptr;
   int frames_P = 0;
   int frames_max_h = 0, frames_max_w = 0;
+  // bit planes of a frames call (la3d_fit_instances_frames_bits): the plane of instance n starts bits_offsets[n] words behind
+  // mask_bits and holds the H*W/32 words of the instance's own frame (bits_plane_stride is then not read)
+  const long long* bits_offsets = nullptr;
 };
 
 // ------------------------------------------------------------------------------------------
@@ -720,6 +723,23 @@ __host__ __device__ inline int tiled_list_cap(int bit_bytes, int nwords, int nti
   if (budget_out) *budget_out = budget;
   return cap > ntiles ? ntiles : cap;
 }
+// one la3d_frame row as the label packer of a frames call (la3d_pack_label_bits_frames) holds it (wave-uniform: read with scalar
+// loads), and the contract of include/la3d.h ("images of different sizes in one call") it must keep before any address is formed from
+// it: the rule of frame_geometry below, term for term, so that packer and fit refuse exactly the same rows - a change of either is a
+// change of both.  (frame_geometry keeps its own text: calling frame_row_ok from it re-schedules the scalar compares of every frames
+// instantiation, and those keep the instruction streams they had.)
+struct FrameRow { long long off; int H, W, fw; };
+__device__ inline FrameRow frame_row_load(const la3d_frame* fr) {
+  const long long off_v = fr->depth_offset;
+  FrameRow r;
+  r.off = ((long long)__builtin_amdgcn_readfirstlane((int)(off_v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)off_v);
+  r.H = __builtin_amdgcn_readfirstlane(fr->H); r.W = __builtin_amdgcn_readfirstlane(fr->W);
+  r.fw = __builtin_amdgcn_readfirstlane(fr->frame_width);
+  return r;
+}
+__device__ inline bool frame_row_ok(const FrameRow& r, int max_h, int max_w) {
+  return !(r.H <= 0 || r.W <= 0 || (r.W & 31) != 0 || r.H > max_h || r.W > max_w || r.fw <= 0 || r.fw > r.W || r.off < 0 || (r.off & 3) != 0);
+}
 template <bool CHECKED, bool SAMPLE>
 __device__ inline bool frame_geometry(FitParams& p, const FitParams& call, int img) {
   if (CHECKED && (unsigned)img >= (unsigned)call.frames_P) return false;
@@ -754,6 +774,19 @@ __device__ inline void frame_proj(FitParams& p, const FitParams& call, int inst)
   if (!call.proj) return;
   const la3d_frame* fr = call.frames + call.image_index[inst];
   p.proj_w = (double)__builtin_amdgcn_readfirstlane(fr->frame_width); p.proj_h = (double)__builtin_amdgcn_readfirstlane(fr->H);
+}
+
+// frames call on bit planes (la3d_fit_instances_frames_bits): the offset, in words from mask_bits, of the instance's plane (wave-uniform:
+// scalar registers).  Loaded only behind a frame row that frame_geometry<true> has accepted, checked by the rule of the row's
+// depth_offset (>= 0, a multiple of 4: a 16-byte aligned plane) before any address is formed from it, and loaded AGAIN where the plane
+// is streamed - like frame_depth_offset, and for the reason given there: the table is an input of the call that nothing writes
+__device__ inline long long frame_bits_offset(const FitParams& call, int inst) {
+  const long long off_v = call.bits_offsets[inst];
+  return ((long long)__builtin_amdgcn_readfirstlane((int)(off_v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)off_v);
+}
+__device__ inline bool frame_bits_offset_ok(const FitParams& call, int inst) {
+  const long long off = frame_bits_offset(call, inst);
+  return off >= 0 && (off & 3) == 0;
 }
 
 __device__ inline void pix_uv(unsigned i, int W, float rcpW, unsigned* u, unsigned* v) {

@@ -116,7 +116,7 @@ __device__ inline void sweep_sep_hull(const FitParams& p, const DepthT* __restri
 // constant FRAMES: the other instantiations read the kernel argument itself, as they did.
 template <bool VEC, bool LDSMASK, bool SAMPLE, bool TILED, int SRC, bool HULL = false, bool FRAMES = false>
 __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const KParams p_call) {
-  static_assert(!FRAMES || (VEC && LDSMASK && TILED && !HULL && (SRC == 1 || SRC == 2)), "frames calls: run lengths / polygons, tiled form");
+  static_assert(!FRAMES || (VEC && LDSMASK && TILED && !HULL && (SRC == 1 || SRC == 2 || SRC == 3)), "frames calls: run lengths / polygons / bit planes, tiled form");
   FitParams p_frame;   // FRAMES only: this workgroup's parameters (dead otherwise)
   if constexpr (FRAMES) p_frame = p_call;
   const FitParams& p_block = p_call;
@@ -157,7 +157,9 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const KParam
   if constexpr (HULL) { if (tid == 0) hull_slot(p.geo, inst, hull_stride_bytes(SAMPLE, p.W))[HH_STATE] = -1.0; }   // nothing to finish, until the hand-off says so
   const int img = p.image_index ? p.image_index[inst] : inst;
   if constexpr (FRAMES) {
-    if (!frame_geometry<true, SAMPLE>(p_frame, p_call, img)) {   // uniform: an image index outside the table or a frame row outside the contract - refused
+    // uniform: an image index outside the table or a frame row outside the contract - refused; bit planes: so is a plane offset
+    // outside its contract, loaded only behind an accepted row (frame_bits_offset)
+    if (!frame_geometry<true, SAMPLE>(p_frame, p_call, img) || (SRC == 3 && !frame_bits_offset_ok(p_call, inst))) {
       if (tid == 0) {                    // before anything is read through it (no barrier has been passed: the whole workgroup leaves)
         if (p.aux) {
           double* a = p.aux + (long long)inst * LA3D_AUX;
@@ -243,7 +245,10 @@ __global__ __launch_bounds__(NT, NT / 64) void fit_instances_kernel(const KParam
   } else if (LDSMASK && SRC == 3) {
     // masks arrive as bit planes: the plane IS the bit image - a straight stream into LDS, no decode (38 400 B for 640x480 against
     // the 307 200 B of a u8 plane)
-    nmask = bits_plane_to_lds<NT>(p.mask_bits + (long long)inst * p.bits_plane_stride, bits, p.nwords, HW, p.bits_vec, tid);
+    // (frames call: the plane lies at its own offset - accepted above, loaded again here -, holds the whole words of the instance's
+    // own frame and is 16-byte aligned: always the 16-byte form)
+    if constexpr (FRAMES) nmask = bits_plane_to_lds<NT>(p.mask_bits + frame_bits_offset(p_call, inst), bits, p.nwords, HW, 1, tid);
+    else nmask = bits_plane_to_lds<NT>(p.mask_bits + (long long)inst * p.bits_plane_stride, bits, p.nwords, HW, p.bits_vec, tid);
   } else if (LDSMASK) {
     unsigned short* b16 = reinterpret_cast<unsigned short*>(bits);
     const int ngroups = (HW + 15) >> 4;
@@ -1004,9 +1009,11 @@ int launch_fit(const KParams& p, size_t lds, hipStream_t s, void* workspace = nu
 }
 
 
-// la3d_fit_instances_frames / la3d_fit_instances_frames_depth16: run lengths or polygon parts, the tiled form (full-mask or subsample)
+// la3d_fit_instances_frames / la3d_fit_instances_frames_depth16: run lengths or polygon parts, la3d_fit_instances_frames_bits: bit
+// planes - the tiled form (full-mask or subsample)
 template <bool SAMPLE>
 int launch_fit_frames(const KParams& p, size_t lds, hipStream_t s, void* workspace) {
+  if (p.mask_bits != nullptr) return launch_fit_inst<true, true, SAMPLE, true, 3, true>(p, lds, s, workspace);
   if (p.rle_counts != nullptr) return launch_fit_inst<true, true, SAMPLE, true, 1, true>(p, lds, s, workspace);
   return launch_fit_inst<true, true, SAMPLE, true, 2, true>(p, lds, s, workspace);
 }

@@ -909,6 +909,36 @@ __device__ inline void label_area(int* __restrict__ area, int b, unsigned pat) {
   if (area && n && (threadIdx.x & 63) == 0) atomicAdd(area + b, n);
 }
 
+// the 32 labels of an output word, as loaded (2 / 4 / 8 groups of 16 bytes), against one id (wave-uniform), both sides as int32:
+// the compare of pack_labels_vec_kernel below, for the frames form (the older kernel keeps its own text - and so the instruction
+// stream it had: moved into this function its U16 / I32 loops schedule differently)
+template <int KIND>
+__device__ inline unsigned label_word_pattern(const u32x4* q, int id) {
+  constexpr int NQ = 2 * LabelElem<KIND>::BYTES;
+  unsigned pat = 0;
+  if constexpr (KIND == LB_U8) {
+    const unsigned s = (unsigned)(id & 255) * 0x01010101u;
+    pat = ~(nz16(q[0].x ^ s, q[0].y ^ s, q[0].z ^ s, q[0].w ^ s) | (nz16(q[1].x ^ s, q[1].y ^ s, q[1].z ^ s, q[1].w ^ s) << 16));
+    if ((unsigned)id > 255u) pat = 0;
+  } else if constexpr (KIND == LB_U16) {
+    const unsigned s = (unsigned)(id & 0xffff) * 0x00010001u;
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) {
+      const unsigned x[4] = {q[k].x ^ s, q[k].y ^ s, q[k].z ^ s, q[k].w ^ s};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        pat |= ((x[j] & 0xffffu) == 0 ? 1u : 0u) << (8 * k + 2 * j) | ((x[j] >> 16) == 0 ? 1u : 0u) << (8 * k + 2 * j + 1);
+    }
+    if ((unsigned)id > 65535u) pat = 0;
+  } else {
+#pragma unroll
+    for (int k = 0; k < NQ; ++k)
+      pat |= ((int)q[k].x == id ? 1u : 0u) << (4 * k) | ((int)q[k].y == id ? 1u : 0u) << (4 * k + 1) |
+             ((int)q[k].z == id ? 1u : 0u) << (4 * k + 2) | ((int)q[k].w == id ? 1u : 0u) << (4 * k + 3);
+  }
+  return pat;
+}
+
 // Vector form (chosen on the host: U8 / U16 / I32, W_out == W, H*W % 32 == 0, every label plane 16-byte aligned): a workgroup owns
 // 256 consecutive output words of one image; each lane loads the 32 labels of its word once (2 / 4 / 8 loads of 16 bytes) and
 // stores one word per instance - 256 contiguous bytes per wave.  blockIdx.x = image * chunks + chunk.
@@ -1001,6 +1031,100 @@ __global__ __launch_bounds__(256) void pack_labels_kernel(const void* __restrict
   }
 }
 
+// ---- label maps of images of different sizes (la3d_pack_label_bits_frames) -------------------
+// The two forms above with the geometry of every image read from its la3d_frame row (wave-uniform: scalar loads) and the plane of
+// every (image, id) row at its own offset.  The pitch of a conforming row is a multiple of 32, so a word never straddles two rows:
+// word w of an image holds columns 32 (w % (W/32)) .. + 31 of row w / (W/32), and `have` clears the bits of the columns >=
+// frame_width whatever the padding elements hold.  A row that breaks the contract (frame_row_ok: the check the fit makes) is left
+// before anything is read through it; so is a plane whose offset is negative or not a multiple of 4.  blockIdx.x = image * chunks +
+// chunk, chunks sized for the bounds' plane: a chunk beyond its image's words returns before any load.
+__device__ inline long long plane_offset(const long long* __restrict__ offs, int b) {
+  const long long v = offs[b];
+  return ((long long)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+}
+__device__ inline unsigned image_columns(int w, int W, int fw) {
+  const int rem = fw - (w % (W >> 5)) * 32;
+  return rem >= 32 ? 0xffffffffu : rem <= 0 ? 0u : (1u << rem) - 1u;
+}
+
+// U8 / U16 / I32: each lane loads the 32 labels of its word once - in 16-byte groups where the plane is 16-byte aligned (labels is, and
+// depth_offset % 4 == 0 makes every I32 plane so; a U8 / U16 plane whose offset is not a multiple of 16 / 8 elements takes the same
+// bytes in 4-byte loads) - and stores one word per instance
+template <int KIND>
+__global__ __launch_bounds__(256) void pack_labels_frames_vec_kernel(const void* __restrict__ labels, const la3d_frame* __restrict__ frames,
+                                                                     int max_h, int max_w, int chunks, const int* __restrict__ inst_offsets,
+                                                                     const int* __restrict__ inst_label, int B, unsigned* __restrict__ out,
+                                                                     const long long* __restrict__ out_offsets, int* __restrict__ area) {
+  constexpr int NQ = 2 * LabelElem<KIND>::BYTES;   // 16-byte groups per output word
+  const int p = blockIdx.x / chunks, chunk = blockIdx.x - p * chunks;
+  int i0, i1;
+  label_rows(inst_offsets, p, B, &i0, &i1);
+  if (i0 >= i1) return;   // (uniform) an image without instances is never read
+  const FrameRow r = frame_row_load(frames + p);
+  if (!frame_row_ok(r, max_h, max_w)) return;   // (uniform) a broken row: nothing is read through it, nothing written for it
+  const int nwords = (r.H * r.W) >> 5;   // (<= the bounds' plane: H <= max_h, W <= max_w)
+  if (chunk * 256 >= nwords) return;     // (uniform) a chunk beyond this image's words
+  const int w = chunk * 256 + (int)threadIdx.x;
+  const bool live = w < nwords;
+  const unsigned have = live ? image_columns(w, r.W, r.fw) : 0u;
+  const long long base_bytes = r.off * LabelElem<KIND>::BYTES;
+  const unsigned char* plane = static_cast<const unsigned char*>(labels) + base_bytes;
+  u32x4 q[NQ];
+  if ((base_bytes & 15) == 0) {   // uniform
+    const u32x4* s4 = reinterpret_cast<const u32x4*>(plane) + (long long)w * NQ;
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) q[k] = live ? __builtin_nontemporal_load(s4 + k) : u32x4{0u, 0u, 0u, 0u};
+  } else {
+    const unsigned* s1 = reinterpret_cast<const unsigned*>(plane) + (long long)w * NQ * 4;
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) q[k] = live ? u32x4{s1[4 * k], s1[4 * k + 1], s1[4 * k + 2], s1[4 * k + 3]} : u32x4{0u, 0u, 0u, 0u};
+  }
+  for (int b = i0; b < i1; ++b) {   // uniform trip count: every lane takes part in the reduction
+    const long long oo = plane_offset(out_offsets, b);
+    if (oo < 0 || (oo & 3) != 0) continue;   // (uniform) before an address is formed from it: the fit refuses this instance too
+    const int id = inst_label[b];   // (wave-uniform)
+    const unsigned pat = label_word_pattern<KIND>(q, id) & have;
+    if (live) out[oo + w] = pat;
+    label_area(area, b, pat);
+  }
+}
+
+// RGB8 (3 bytes per pixel: no 16-byte form): one thread per output word, the image columns of its 32 pixels read byte by byte
+__global__ __launch_bounds__(256) void pack_labels_frames_rgb8_kernel(const unsigned char* __restrict__ labels, const la3d_frame* __restrict__ frames,
+                                                                      int max_h, int max_w, int chunks, const int* __restrict__ inst_offsets,
+                                                                      const int* __restrict__ inst_label, int B, unsigned* __restrict__ out,
+                                                                      const long long* __restrict__ out_offsets, int* __restrict__ area) {
+  const int p = blockIdx.x / chunks, chunk = blockIdx.x - p * chunks;
+  int i0, i1;
+  label_rows(inst_offsets, p, B, &i0, &i1);
+  if (i0 >= i1) return;   // (uniform)
+  const FrameRow r = frame_row_load(frames + p);
+  if (!frame_row_ok(r, max_h, max_w)) return;   // (uniform)
+  const int nwords = (r.H * r.W) >> 5;
+  if (chunk * 256 >= nwords) return;   // (uniform)
+  const int w = chunk * 256 + (int)threadIdx.x;
+  const bool live = w < nwords;
+  const unsigned have = live ? image_columns(w, r.W, r.fw) : 0u;
+  const unsigned char* sp = labels + (r.off + (long long)w * 32) * 3;   // (pixel 32 w of the plane: row w / (W/32), column 32 (w % (W/32)))
+  int lab[32];
+#pragma unroll
+  for (int k = 0; k < 32; ++k) {
+    lab[k] = 0;
+    if ((have >> k) & 1u) lab[k] = (int)sp[k * 3] | (int)sp[k * 3 + 1] << 8 | (int)sp[k * 3 + 2] << 16;
+  }
+  for (int b = i0; b < i1; ++b) {   // uniform trip count
+    const long long oo = plane_offset(out_offsets, b);
+    if (oo < 0 || (oo & 3) != 0) continue;   // (uniform)
+    const int id = inst_label[b];
+    unsigned pat = 0;
+#pragma unroll
+    for (int k = 0; k < 32; ++k) pat |= (lab[k] == id ? 1u : 0u) << k;
+    pat &= have;
+    if (live) out[oo + w] = pat;
+    label_area(area, b, pat);
+  }
+}
+
 template <int KIND>
 int pack_labels_launch(const void* labels, long long plane_stride, int P, int H, int W, int W_out, const int* inst_offsets,
                        const int* inst_label, int B, uint32_t* bits, long long bits_plane_stride, int* area, hipStream_t s) {
@@ -1064,6 +1188,58 @@ int la3d_pack_label_bits(const void* labels, int dtype, int64_t plane_stride, in
     case LA3D_LABEL_I32: return pack_labels_launch<LB_I32>(labels, plane_stride, P, H, W, W_out, inst_offsets, inst_label, B, bits, bits_plane_stride, area, s);
     default: return pack_labels_launch<LB_RGB8>(labels, plane_stride, P, H, W, W_out, inst_offsets, inst_label, B, bits, bits_plane_stride, area, s);
   }
+}
+
+int la3d_pack_label_bits_frames(const void* labels, int dtype, const la3d_frame* frames, int32_t P, int H, int W,
+                                const int32_t* inst_offsets, const int32_t* inst_label, int B, uint32_t* bits,
+                                const int64_t* bits_offsets, int32_t* area, void* stream) {
+  const char* bad = nullptr;
+  const bool work = B > 0 && P > 0;
+  const long long words = H > 0 && W > 0 ? (long long)H * ((W + 31) / 32) : 0;   // the bounds' plane: rows of whole words
+  if (dtype != LA3D_LABEL_U8 && dtype != LA3D_LABEL_U16 && dtype != LA3D_LABEL_I32 && dtype != LA3D_LABEL_RGB8)
+    bad = "unknown dtype (LA3D_LABEL_U8, LA3D_LABEL_U16, LA3D_LABEL_I32 or LA3D_LABEL_RGB8)";
+  else if (B < 0 || P < 0 || H <= 0 || W <= 0) bad = "bad argument (B, P >= 0, bounds H, W > 0)";
+  else if (words > (1LL << 23) || (long long)P * ((words + 255) / 256) > 0x7fffffffLL)
+    bad = "bounds or batch too large (H * roundup32(W) <= 2^28, P * ceil(H * roundup32(W) / 8192) < 2^31)";
+  else if (work && (!labels || !frames || !inst_offsets || !inst_label || !bits || !bits_offsets))
+    bad = "NULL labels, frames, inst_offsets, inst_label, bits or bits_offsets";
+  else if (work && (reinterpret_cast<uintptr_t>(labels) & 15)) bad = "labels not a 16-byte aligned pointer";
+  else if (work && (reinterpret_cast<uintptr_t>(bits) & 3)) bad = "bits not a 4-byte aligned pointer";
+  else if (work && ((reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(bits_offsets)) & 7))
+    bad = "frames or bits_offsets not an 8-byte aligned pointer";
+  else if (work && ((reinterpret_cast<uintptr_t>(inst_offsets) | reinterpret_cast<uintptr_t>(inst_label) | reinterpret_cast<uintptr_t>(area)) & 3))
+    bad = "inst_offsets, inst_label or area not a 4-byte aligned pointer";
+  if (bad) {
+    char msg[200];
+    snprintf(msg, sizeof(msg), "la3d_pack_label_bits_frames: %s", bad);
+    set_err(msg);
+    return LA3D_ERR_ARG;
+  }
+  if (!work) return LA3D_SUCCESS;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (area) {   // (as la3d_pack_label_bits: a kernel node of the call's own when captured)
+    hipLaunchKernelGGL(clear_area_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, area, B);
+    const int rc = check_launch("clear_area_kernel");
+    if (rc != LA3D_SUCCESS) return rc;
+  }
+  const int chunks = (int)((words + 255) / 256);
+  const dim3 grid((unsigned)((long long)P * chunks));
+  const long long* offs = reinterpret_cast<const long long*>(bits_offsets);
+  switch (dtype) {
+    case LA3D_LABEL_U8:
+      hipLaunchKernelGGL(pack_labels_frames_vec_kernel<LB_U8>, grid, dim3(256), 0, s, labels, frames, H, W, chunks, inst_offsets, inst_label, B, bits, offs, area);
+      break;
+    case LA3D_LABEL_U16:
+      hipLaunchKernelGGL(pack_labels_frames_vec_kernel<LB_U16>, grid, dim3(256), 0, s, labels, frames, H, W, chunks, inst_offsets, inst_label, B, bits, offs, area);
+      break;
+    case LA3D_LABEL_I32:
+      hipLaunchKernelGGL(pack_labels_frames_vec_kernel<LB_I32>, grid, dim3(256), 0, s, labels, frames, H, W, chunks, inst_offsets, inst_label, B, bits, offs, area);
+      break;
+    default:
+      hipLaunchKernelGGL(pack_labels_frames_rgb8_kernel, grid, dim3(256), 0, s, static_cast<const unsigned char*>(labels), frames, H, W, chunks, inst_offsets,
+                         inst_label, B, bits, offs, area);
+  }
+  return check_launch("pack_labels_frames_kernel");
 }
 
 }  // extern "C"

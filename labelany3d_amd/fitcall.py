@@ -15,8 +15,9 @@ from .batched import (Depth16, InstanceFitter, _as_dev, _bits_stride, _bulk, _en
 
 class MaskSource(NamedTuple):
     """The masks of a call: ``B`` instances on a frame of ``H`` x ``W`` (None, None: a frames call - every instance has its own);
-    ``kw``: the mask keywords of ``_fit_args``; ``bits``: the (pointer, stride, flags) of bit planes; ``keep``: the tensors behind the
-    pointers; ``what``: the word the error texts use for the masks."""
+    ``kw``: the mask keywords of ``_fit_args``; ``bits``: the (pointer, stride, flags) of bit planes - in a frames call (pointer,
+    pointer to the per-instance plane offsets, flags); ``keep``: the tensors behind the pointers; ``what``: the word the error texts
+    use for the masks."""
     B: int
     H: Optional[int]
     W: Optional[int]
@@ -34,9 +35,10 @@ class FramesDepth(NamedTuple):
     d16: Optional[_lib.Depth16Block]
 
 
-def mask_source(dev, masks=None, rles=None, polys=None, bits=None, small=(None, None, None, None)):
+def mask_source(dev, masks=None, rles=None, polys=None, bits=None, frame_bits=None, small=(None, None, None, None)):
     """-> (MaskSource, ground, image_index, sample_idx, area_hint).  ``masks``: (B,H,W) u8 / bool; ``rles``: (counts, offsets, H, W);
-    ``polys``: (xy, ring_offsets, inst_rings, H, W); ``bits``: (``MaskBits``, flags).  Host run-length / polygon arrays go up in ONE
+    ``polys``: (xy, ring_offsets, inst_rings, H, W); ``bits``: (``MaskBits``, flags); ``frame_bits``: (``FrameBits``, flags) - the
+    bit planes of a frames call, one per instance at its own offset.  Host run-length / polygon arrays go up in ONE
     copy together with the call's other small host arrays ``small`` = (ground, image_index, sample_idx, area_hint), which come back
     as device tensors where they went along (tensors and None pass through)."""
     if masks is not None:
@@ -47,6 +49,10 @@ def mask_source(dev, masks=None, rles=None, polys=None, bits=None, small=(None, 
         mb, flags = bits
         B = mb.bits.shape[0]
         return (MaskSource(B, mb.H, mb.W, {}, (_ptr(mb.bits), _bits_stride(mb.bits, B, mb.H, mb.W), flags), [mb.bits], "bit-plane"), *small)
+    if frame_bits is not None:
+        fb, flags = frame_bits
+        return (MaskSource(int(fb.offsets.numel()), None, None, {}, (_ptr(fb.bits), _ptr(fb.offsets), flags), [fb.bits, fb.offsets], "bit-plane"),
+                *small)
     i32, i64, (g, ii, si, ah) = torch.int32, torch.int64, small   # (spelled out: this runs once per image on a ~100 us path)
     if rles is not None:
         c, o, H, W = rles

@@ -844,9 +844,18 @@ def label_instances(labels, ignore=(0,), min_area: int = 1, rgb: bool = False):
     """The instances a label map holds, for callers without a ``segments_info`` (the output of a panoptic / entity segmentation
     network): ``(ids, areas)`` - per image a NumPy int32 array of the ids present, ascending, without those in ``ignore`` (0: the
     unlabeled id of COCO panoptic maps) and those of fewer than ``min_area`` pixels, and an int64 array of their pixel counts.
-    ``labels`` / ``rgb`` as in ``pack_label_bits``, on the host or the device.  Plumbing, not a hot path: one ``torch.unique`` over
+    ``labels`` / ``rgb`` as in ``pack_label_bits``, on the host or the device - or a sequence of maps of DIFFERENT sizes (what
+    ``pack_label_frames`` takes), handled image by image.  Plumbing, not a hot path: one ``torch.unique`` over
     ``image << 32 | label`` keys where the labels lie, and it SYNCHRONISES (the result is read back).  ``draw_sample_idx(np.concatenate(
     areas))`` gives the reference's draws for subsample mode (``sample_idx`` of ``fit_instances_labels``)."""
+    if isinstance(labels, (list, tuple)) and len({tuple(m.shape) for m in labels if hasattr(m, "shape")}) > 1:
+        # maps of different sizes (what pack_label_frames takes): image by image
+        ids, areas = [], []
+        for m in labels:
+            i, a = label_instances(m, ignore=ignore, min_area=min_area, rgb=rgb)
+            ids += i
+            areas += a
+        return ids, areas
     labels, code, P, H, W = _label_planes(labels, rgb)
     t = labels if isinstance(labels, torch.Tensor) else torch.as_tensor(labels.view(np.int16) if labels.dtype == np.uint16 else labels)
     if t.dtype == torch.uint16:
@@ -1101,6 +1110,209 @@ def fit_instances_frames(frames, K, rles=None, polys=None, image_index=None, gro
     # (_fitter: buffers a caller keeps between calls - fit_scenes -, sized for at least this call's B and bounds)
     return fit_call(src, depth, K, dev, frames.H, frames.W, image_index=ii, ground=ground, sample_idx=sample_idx, area_hint=area_hint,
                     filter=filter, image_size=(1, 1) if proj else None, stream=stream, method=method, fitter=_fitter)
+
+
+# ---- label maps and bit planes of images of different sizes (include/la3d.h "images of different sizes in one call") ----------------
+class PackedLabels(NamedTuple):
+    """Label maps of different sizes in one buffer (``pack_label_frames``; C-ABI ``la3d_pack_label_bits_frames``): ``data`` flat -
+    ``torch.uint8`` / ``int16`` (the bit patterns of uint16 labels) / ``int32``, or ``uint8`` with 3 bytes per pixel for RGB maps -
+    in the layout of ``PackedFrames`` counted in ELEMENTS (pixels for RGB): map p starts ``table_host["depth_offset"][p]`` elements
+    in, its rows ``padded_width(W_p)`` elements apart, the columns past ``W_p`` zero; ``table`` / ``table_host`` / ``H`` / ``W`` /
+    ``sizes`` as in ``PackedFrames`` - the table IS the one ``pack_frames`` gives for depth maps of the same sizes; ``code``: the
+    element (``_lib.LABEL_*``)."""
+    data: torch.Tensor
+    table: torch.Tensor
+    table_host: np.ndarray
+    H: int
+    W: int
+    sizes: list
+    code: int
+
+
+class FrameBits(NamedTuple):
+    """Bit planes of instances of images of different sizes (``pack_label_bits_frames``; C-ABI ``la3d_fit_instances_frames_bits``):
+    ``bits`` flat int32 on the GPU; ``offsets`` int64 (B,) on the GPU - the plane of row b starts ``offsets[b]`` words in (a multiple of
+    4) and holds the ``H_p * padded_width(W_p) / 32`` words of its image's frame -; ``image_index`` int32 (B,) and ``area`` int32 (B,)
+    on the GPU as in ``LabelBits``; ``table``: the HOST frame table (``FRAME_DTYPE``) the planes were laid out for - what
+    ``fit_instances_frames_bits`` compares with the table of its depth, without touching the device -; ``H``, ``W``: its bounds."""
+    bits: torch.Tensor
+    offsets: torch.Tensor
+    image_index: torch.Tensor
+    area: torch.Tensor
+    table: np.ndarray
+    H: int
+    W: int
+
+
+_LABEL_STORE = {_lib.LABEL_U8: torch.uint8, _lib.LABEL_U16: torch.int16, _lib.LABEL_I32: torch.int32, _lib.LABEL_RGB8: torch.uint8}
+
+
+def pack_label_frames(label_maps, rgb: bool = False, device=None, pinned=None) -> PackedLabels:
+    """Label maps of DIFFERENT sizes -> ``PackedLabels``: one flat buffer in the layout ``pack_frames`` gives depth maps of the same
+    sizes (``frame_table(sizes)``: pitch ``padded_width(W)``, the padding zero), so ONE table serves ``pack_label_bits_frames`` and
+    the fit.  ``label_maps``: a sequence of (H_p, W_p) arrays / tensors of ONE dtype - uint8, uint16, int16 (read as uint16) or int32 -
+    or, with ``rgb=True``, of (H_p, W_p, 3) uint8 maps (a COCO panoptic PNG as it decodes).  ``pinned``: a pinned staging tensor of
+    the stored dtype and at least the packed size (host maps only; the upload is then asynchronous on the current stream).
+    ``device="cpu"`` gives the layout on the host (no GPU needed)."""
+    dev = torch.device(device) if device is not None and torch.device(device).type == "cpu" else _dev(device)
+    maps = list(label_maps)
+    code, c = None, 3 if rgb else 1
+    for p, m in enumerate(maps):
+        one = _LABEL_TORCH.get(m.dtype) if isinstance(m, torch.Tensor) else _LABEL_NUMPY.get(np.asarray(m).dtype)
+        if one is None:
+            raise ValueError(f"label map {p} must be uint8, uint16, int16 (read as uint16) or int32, not {getattr(m, 'dtype', type(m).__name__)}")
+        if rgb and (one != _lib.LABEL_U8 or len(m.shape) != 3 or m.shape[-1] != 3):
+            raise ValueError(f"label map {p}: rgb=True takes (H, W, 3) uint8 maps, not {tuple(m.shape)} {m.dtype}")
+        if not rgb and len(m.shape) != 2:
+            raise ValueError(f"label map {p} must be (H, W), got {tuple(m.shape)}")
+        if code is not None and one != code:
+            raise ValueError(f"label map {p} has another dtype than label map 0: pack maps of one dtype")
+        code = one
+    code = _lib.LABEL_RGB8 if rgb else (code if code is not None else _lib.LABEL_U8)
+    tdt = _LABEL_STORE[code]
+
+    def words(m):   # the map in the stored dtype (uint16 as its int16 bit pattern)
+        if isinstance(m, torch.Tensor):
+            return m.view(torch.int16) if m.dtype == torch.uint16 else m
+        a = np.asarray(m)
+        return a.view(np.int16) if a.dtype == np.uint16 else a
+
+    maps = [words(m) for m in maps]
+    sizes = [(int(m.shape[0]), int(m.shape[1])) for m in maps]
+    table = frame_table(sizes)
+    rows = [(int(r["depth_offset"]), int(r["H"]), int(r["W"]), int(r["frame_width"])) for r in table]
+    total = sum(h * wp for _, h, wp, _ in rows)
+    n = max(total, 16) * c
+    if any(isinstance(m, torch.Tensor) and m.is_cuda for m in maps):
+        flat = torch.zeros(n, dtype=tdt, device=dev)
+        for m, (o, h, wp, w) in zip(maps, rows):
+            flat[o * c:(o + h * wp) * c].view(h, wp * c)[:, :w * c].copy_(torch.as_tensor(m).to(device=dev).reshape(h, w * c))
+    else:
+        if pinned is not None and pinned.dtype == tdt and pinned.numel() >= n:
+            host_t = pinned[:n]
+        else:
+            pinned, host_t = None, torch.empty(n, dtype=tdt)
+        host = host_t.numpy()
+        host[total * c:] = 0
+        for m, (o, h, wp, w) in zip(maps, rows):
+            dst = host[o * c:(o + h * wp) * c].reshape(h, wp * c)
+            dst[:, :w * c] = (m.numpy() if isinstance(m, torch.Tensor) else np.asarray(m)).reshape(h, w * c)
+            dst[:, w * c:] = 0
+        flat = host_t if dev.type == "cpu" else host_t.to(dev, non_blocking=pinned is not None)
+    tab_words = np.ascontiguousarray(table).view(np.int32).reshape(len(maps), 6) if len(maps) else np.zeros((0, 6), np.int32)
+    tab = torch.as_tensor(tab_words.copy(), device=dev)
+    bounds = (max((h for h, _ in sizes), default=0), max((wp for _, _, wp, _ in rows), default=0))
+    return PackedLabels(flat, tab, table, *bounds, sizes, code)
+
+
+def frame_bits_offsets(table, image_index):
+    """The layout ``pack_label_bits_frames`` gives the planes of host ids: -> (offsets int64 (B,), total words).  Row b gets the
+    ``H * W / 32`` words of the frame row ``table[image_index[b]]`` (W: the pitch, a multiple of 32); the planes follow each other
+    in row order, each start rounded up to a multiple of 4 words (16 bytes)."""
+    ii = np.asarray(image_index, np.int64).reshape(-1)
+    words = (table["H"].astype(np.int64) * table["W"].astype(np.int64) // 32)[ii] if len(ii) else np.zeros(0, np.int64)
+    step = (words + 3) // 4 * 4
+    offsets = np.zeros(len(ii), np.int64)
+    np.cumsum(step[:-1], out=offsets[1:])
+    return offsets, int(step.sum())
+
+
+def pack_label_bits_frames(labels: PackedLabels, ids, stream=None, out=None) -> FrameBits:
+    """``pack_label_bits`` for label maps of different sizes (C-ABI ``la3d_pack_label_bits_frames``): one launch reads every map once
+    and writes, per (image, id) row, the bit plane ``labels[image] == id`` of the image's OWN frame - ``H_p * padded_width(W_p) / 32``
+    words, the bits of the padding columns zero whatever id is asked (id 0 of a zero-padded map marks image pixels only).
+    ``labels``: a resident ``PackedLabels``; ``ids`` as in ``pack_label_bits``.  Host ids: the planes follow each other, each start
+    rounded up to 4 words (``frame_bits_offsets``), and offsets, ids and image indices go up in ONE copy.  Device ids: no
+    synchronisation - the sizes of the rows are then unknown here, so the planes lie a uniform stride apart, the words of the bounds'
+    frame rounded up to 4.  ``out``: a flat int32 device tensor of at least that many words to fill (only the words of each plane are
+    written).  Returns ``FrameBits``; an id that is absent or outside the dtype's range gives an all-zero plane of area 0."""
+    if not isinstance(labels, PackedLabels):
+        raise ValueError("labels must be the PackedLabels of pack_label_frames")
+    P = len(labels.sizes)
+    lab, off, ii, B = _label_rows(ids, P)
+    if not labels.data.is_cuda:
+        raise ValueError("the label maps must live on the GPU (pack_label_frames with a GPU device)")
+    dev = labels.data.device
+    with torch.cuda.device(dev):
+        if ii is not None:
+            offs_h, total = frame_bits_offsets(labels.table_host, ii)
+            lab, off, ii, offs = _upload_many([(lab, torch.int32), (off, torch.int32), (ii, torch.int32), (offs_h, torch.int64)], dev)
+        else:
+            lab, off = _as_dev(lab, torch.int32, dev), _as_dev(off, torch.int32, dev)
+            ii = torch.searchsorted(off[1:].contiguous(), torch.arange(B, dtype=torch.int32, device=dev), right=True).to(torch.int32)
+            stride = (labels.H * labels.W // 32 + 3) // 4 * 4
+            offs, total = torch.arange(B, dtype=torch.int64, device=dev) * stride, B * stride
+        if out is None:
+            o = torch.empty(max(total, 4), dtype=torch.int32, device=dev)
+        else:
+            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int32 and out.dim() == 1 and out.is_contiguous()
+                    and out.numel() >= total and out.data_ptr() % 16 == 0):
+                raise ValueError(f"out must be a flat, 16-byte aligned int32 device tensor of at least {total} words")
+            o = out
+        area = torch.empty(B, dtype=torch.int32, device=dev)
+        check(lib.la3d_pack_label_bits_frames(_ptr(labels.data), labels.code, _ptr(labels.table), P, labels.H, labels.W, _ptr(off), _ptr(lab), B,
+                                              _ptr(o), _ptr(offs), _ptr(area), _stream(stream)), "la3d_pack_label_bits_frames")
+    _record(stream, labels.data, labels.table, lab, off, ii, offs, o, area)
+    return FrameBits(o, offs, ii, area, labels.table_host, labels.H, labels.W)
+
+
+def fit_instances_frames_bits(frames, bits: FrameBits, K, image_index=None, ground=None, sample_idx=None, filter=None, proj: bool = False,
+                              area_hint=None, height_rule: str = "rows", stream=None, method: str = "pca", _fitter=None):
+    """``fit_instances_frames`` with the masks given as bit planes, one per instance, each of its own image's frame (C-ABI
+    ``la3d_fit_instances_frames_bits``): what ``pack_label_bits_frames`` makes of the label maps of a panoptic dataset.  ``frames``: a
+    ``PackedFrames`` or ``PackedFrames16`` laid out by the SAME frame table as the planes (``bits.table``; a mismatch is a ValueError
+    before any device work); ``image_index`` defaults to ``bits.image_index``; ``ground`` / ``sample_idx`` / ``filter`` / ``proj`` /
+    ``area_hint`` as in ``fit_instances_frames``, ``height_rule`` as in ``fit_instances_bits``.  An instance whose image index, frame
+    row or plane offset breaks the contract comes back with status 5 and a NaN record - decided on the device, never an exception.
+    ``method="convex_hull"`` is not offered for frames of different sizes (ValueError).  Returns the dict of ``fit_instances_frames``."""
+    if _lib.method_code(method) != _lib.METHOD_PCA:   # (the reference's error for an unknown method; before any device work)
+        raise ValueError("fit_instances_frames_bits: method='convex_hull' is not supported for frames of different sizes; group by size and use fit_instances_bits")
+    flags = height_rule_code(height_rule)
+    refuse_depth16(frames, "fit_instances_frames_bits")
+    refuse_depth16(getattr(frames, "depth", None), "fit_instances_frames_bits")
+    is16 = isinstance(frames, PackedFrames16)
+    if is16:
+        t = frames.data
+        if not isinstance(t, torch.Tensor) or t.dim() != 1:
+            raise ValueError("PackedFrames16.data must be the flat tensor of pack_frames(dtype=...)")
+        _depth16_check(Depth16(t[None], frames.scale, frames.zero_is_hole))
+    elif not isinstance(frames, PackedFrames):
+        raise ValueError("frames must be the PackedFrames of pack_frames")
+    if not isinstance(bits, FrameBits):
+        raise ValueError("bits must be the FrameBits of pack_label_bits_frames")
+    if (bits.H, bits.W) != (frames.H, frames.W) or not np.array_equal(np.asarray(bits.table), np.asarray(frames.table_host)):
+        raise ValueError("the bit planes were laid out for another frame table than the depth: pack depth and label maps of the same sizes, in the same order")
+    fdepth = frames.data if is16 else frames.depth
+    if not fdepth.is_cuda or not bits.bits.is_cuda:
+        raise ValueError("frames and bit planes must live on the GPU")
+    dev = fdepth.device
+    if bits.bits.device != dev:
+        raise ValueError("the bit planes live on another device")
+    src, ground, ii, sample_idx, area_hint = mask_source(dev, frame_bits=(bits, flags), small=(
+        ground, bits.image_index if image_index is None else image_index, sample_idx, area_hint))
+    depth = FramesDepth(fdepth, frames.table, _d16_block(fdepth, frames.scale, frames.zero_is_hole) if is16 else None)
+    return fit_call(src, depth, K, dev, frames.H, frames.W, image_index=ii, ground=ground, sample_idx=sample_idx, area_hint=area_hint,
+                    filter=filter, image_size=(1, 1) if proj else None, stream=stream, method=method, fitter=_fitter)
+
+
+def fit_instances_frames_labels(frames, label_maps, ids, K, image_index=None, ground=None, sample_idx=None, filter=None, proj: bool = False,
+                                height_rule: str = "rows", stream=None, method: str = "pca", rgb: bool = False):
+    """The depth + mask fit of every listed instance of label maps of DIFFERENT sizes in one call: ``pack_label_frames`` (skipped for a
+    ``PackedLabels``), ``pack_label_bits_frames`` (one pass over the labels), then ``fit_instances_frames_bits`` with the rows'
+    ``image_index`` and their exact areas as ``area_hint``.  ``frames``: the ``PackedFrames`` / ``PackedFrames16`` of the depth maps of
+    the same images in the same order; ``label_maps`` / ``rgb`` as in ``pack_label_frames``; ``ids`` as in ``pack_label_bits``; the
+    other arguments as in ``fit_instances_frames_bits``, per (image, id) row in ``ids`` order.  Returns its dict plus ``"bits"``: the
+    ``FrameBits``.  With resident ``PackedLabels`` and device ids nothing synchronises and the call can be captured into a graph."""
+    if _lib.method_code(method) != _lib.METHOD_PCA:
+        raise ValueError("fit_instances_frames_labels: method='convex_hull' is not supported for frames of different sizes; group by size and use fit_instances_labels")
+    height_rule_code(height_rule)
+    fdepth = getattr(frames, "data", None) if isinstance(frames, PackedFrames16) else getattr(frames, "depth", None)
+    pl = label_maps if isinstance(label_maps, PackedLabels) else pack_label_frames(label_maps, rgb=rgb, device=getattr(fdepth, "device", None))
+    fb = pack_label_bits_frames(pl, ids, stream=stream)
+    out = fit_instances_frames_bits(frames, fb, K, image_index=image_index, ground=ground, sample_idx=sample_idx, filter=filter, proj=proj,
+                                    area_hint=fb.area, height_rule=height_rule, stream=stream, method=method)
+    out["bits"] = fb
+    return out
 
 
 def masked_ratio_median(depth_map, depth_render, mask, render_mask=None, image_index=None, stream=None):
