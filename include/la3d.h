@@ -539,7 +539,35 @@ int la3d_unpack_depth16(const la3d_depth16* src, int P, int H, int W_in, int W, 
  * U8 / U16 / I32 planes are read in 16-byte groups where they are 16-byte aligned (every I32 plane; U8 / U16 planes at offsets that are
  *   multiples of 16 / 8 elements - what back-to-back packing gives) and in 4-byte loads otherwise; RGB8 byte by byte.
  * LA3D_ERR_ARG: an unknown dtype, negative sizes, bounds beyond H * roundup32(W) <= 2^28, misaligned or NULL pointers with work to do.
- *   B == 0 or P == 0: success, nothing is done.  The call is capturable (area is cleared by a kernel of the call). */
+ *   B == 0 or P == 0: success, nothing is done.  The call is capturable (area is cleared by a kernel of the call).
+ *
+ * la3d_pack_mask_bits_frames / la3d_pack_logits_bits_frames: la3d_pack_mask_bits / la3d_pack_logits_bits ("masks as bit planes"
+ * above) for B planes of DIFFERENT sizes in one launch - the (N_p, H_p, W_p) stack of u8 / boolean masks or of logits an
+ * instance-segmentation network gives per image, read where it lies - into the planes la3d_fit_instances_frames_bits fits.
+ *   SOURCE: instance n belongs to image image_index[n] (dev i32 [B]: the array the fit takes).  Its plane starts src_offsets[n]
+ *     ELEMENTS (dev i64 [B]) behind mask / logits and has frames[p].H rows of frames[p].frame_width image columns, the rows
+ *     src_pitch[n] elements apart (dev i32 [B]); src_pitch == NULL: frame_width apart - a dense (H_p, W_p) plane.  No padding to a
+ *     multiple of 32 is asked of the source (only the OUTPUT has the frame's pitch frames[p].W).  The base pointer is aligned to its
+ *     element; any offset >= 0 and any pitch >= frame_width is packed.  frames, P, H, W (bounds): as in the fit - ONE table serves
+ *     this packer and the fit;
+ *   VALUE: u8: bit = byte != 0.  Logits (LA3D_DTYPE_F32 / F16 / BF16): bit = x > threshold, compared in float32 (NaN -> 0, +inf -> 1
+ *     unless threshold is +inf, -inf -> 0): the rules of la3d_pack_logits_bits;
+ *   OUTPUT: exactly what la3d_pack_label_bits_frames writes - the plane of row n at bits + bits_offsets[n] (dev i64 [B]), the
+ *     H_f * W_f / 32 words of its image's frame (W_f: the pitch of the table), every word of them and nothing else, the bits of
+ *     columns >= frame_width zero; area[n] (dev [B] | NULL) = the popcount of the plane, cleared by a kernel of the call: the call is
+ *     capturable and never synchronises.
+ * Checked ON THE DEVICE, before any address is formed from the value:
+ *   - a row whose image_index is outside [0, P), whose frame row breaks the la3d_frame contract (the check of the fit), or whose
+ *     bits_offsets entry is negative or not a multiple of 4 is NOT written and nothing is read for it: exactly the instances the fit
+ *     then refuses (LA3D_BOX_UNSUPPORTED).  Their area stays 0;
+ *   - a row whose src_offsets entry is negative, or whose pitch is smaller than its frame_width, is written as an ALL-ZERO plane with
+ *     area 0 and nothing is read through it: the fit cannot see the source, so such an instance comes back EMPTY (LA3D_BOX_EMPTY),
+ *     never fitted to whatever the memory held before.
+ * What is read of a conforming instance: only elements (v, u) with v < H_f and u < pitch, and in the last row nothing beyond the last
+ *   image column - a dense plane that ends at the end of an allocation is a normal input.  Planes whose first byte and byte pitch are
+ *   multiples of 16 are read in 16-byte groups, every other plane element by element.
+ * LA3D_ERR_ARG before any launch: an unknown dtype, negative B or P, bounds <= 0 or beyond H * roundup32(W) <= 2^28,
+ *   B * ceil(H * roundup32(W) / 8192) >= 2^31, NULL or misaligned pointers with work to do.  B == 0 or P == 0: success, nothing is done. */
 typedef struct la3d_frame {      /* one row per IMAGE, device-resident */
   int64_t depth_offset;          /* elements from the base of the depth buffer to this image's plane, % 4 == 0: floats from args->depth
                                     (la3d_fit_instances_frames), 16-bit words from depth->planes (la3d_fit_instances_frames_depth16) */
@@ -555,6 +583,17 @@ int la3d_fit_instances_frames_bits(const la3d_fit_args* args, const la3d_depth16
 int la3d_pack_label_bits_frames(const void* labels, int dtype, const la3d_frame* frames, int32_t P, int H, int W /* bounds */,
                                 const int32_t* inst_offsets /* dev [P+1] */, const int32_t* inst_label /* dev [B] */, int B,
                                 uint32_t* bits, const int64_t* bits_offsets /* dev [B] */, int32_t* area /* dev [B] or NULL */, void* stream);
+int la3d_pack_mask_bits_frames(const uint8_t* mask, const la3d_frame* frames, int32_t P, int H, int W /* bounds */,
+                               const int32_t* image_index /* dev [B] */, const int64_t* src_offsets /* dev [B], ELEMENTS from mask */,
+                               const int32_t* src_pitch /* dev [B] ELEMENTS between rows, or NULL = frame_width of the row's image */,
+                               int B, uint32_t* bits, const int64_t* bits_offsets /* dev [B] */, int32_t* area /* dev [B] or NULL */,
+                               void* stream);
+int la3d_pack_logits_bits_frames(const void* logits, int dtype /* LA3D_DTYPE_F32 | F16 | BF16 */, float threshold,
+                                 const la3d_frame* frames, int32_t P, int H, int W /* bounds */,
+                                 const int32_t* image_index /* dev [B] */, const int64_t* src_offsets /* dev [B], ELEMENTS from logits */,
+                                 const int32_t* src_pitch /* dev [B] ELEMENTS between rows, or NULL = frame_width of the row's image */,
+                                 int B, uint32_t* bits, const int64_t* bits_offsets /* dev [B] */, int32_t* area /* dev [B] or NULL */,
+                                 void* stream);
 
 /* create_boolean_mask_from_polygon for a batch: polygon parts -> u8 planes mask_out dev [B][H*W] (0/1). */
 int la3d_poly_decode(const int32_t* poly_xy, const int64_t* ring_offsets, const int64_t* inst_rings, int B, int H, int W,

@@ -1243,3 +1243,149 @@ int la3d_pack_label_bits_frames(const void* labels, int dtype, const la3d_frame*
 }
 
 }  // extern "C"
+
+namespace {
+// ---- u8 masks and logits of images of different sizes (la3d_pack_mask_bits_frames / la3d_pack_logits_bits_frames) ------------
+// One plane per INSTANCE, each of its own image's size, anywhere behind one base pointer: what an instance-segmentation network
+// hands over per image, read where it lies.  One lane per output word, blockIdx.x = instance * chunks + chunk, chunks sized for the
+// bounds' plane.  Everything that decides whether and where something is read or written is wave-uniform (scalar loads) and checked
+// BEFORE an address is formed from it, in this order:
+//   image_index outside [0, P), a frame row that breaks the contract (frame_row_ok: the check the fit makes), a bits_offsets entry
+//   that is negative or no multiple of 4: return - nothing read, nothing written, area stays 0 (the fit gives these status 5);
+//   a chunk beyond the instance's words: return before any load;
+//   a negative src_offsets entry or a pitch < frame_width: the plane is written as zeros, nothing is read (status 1 in the fit).
+// What is read of a conforming instance: elements (v, u) with v < H and u < pitch; in the last row none with u >= frame_width.
+//   16-byte form (the plane's first byte and its byte pitch are multiples of 16; a word starts 32 elements = a multiple of 16 bytes
+//   into its row, so every group address is 16-byte aligned): a group is loaded whole only if its first column cg < frame_width.  The
+//   pitch is then a multiple of the group's EPG elements, as cg is, so cg < frame_width <= pitch gives cg + EPG <= pitch: the group lies
+//   inside row v.  In the LAST row a group is loaded whole only if cg + EPG <= frame_width; one that reaches past it takes the
+//   element form, so nothing behind the last image column of the last row is touched (a dense plane may end its allocation).
+//   Element form (everything else): element (v, u) is loaded only where u < frame_width <= pitch.
+// The bits of columns >= frame_width are cleared by image_columns() whatever a whole group brought along.
+template <int KIND>
+__global__ __launch_bounds__(256) void pack_masks_frames_kernel(const void* __restrict__ src, const la3d_frame* __restrict__ frames, int P,
+                                                                int max_h, int max_w, int chunks, const int* __restrict__ image_index,
+                                                                const long long* __restrict__ src_offsets, const int* __restrict__ src_pitch,
+                                                                float thr, unsigned* __restrict__ out,
+                                                                const long long* __restrict__ out_offsets, int* __restrict__ area) {
+  typedef typename PackElem<KIND>::T T;
+  constexpr int ES = (int)sizeof(T);
+  constexpr int EPG = 16 / ES;    // elements per 16-byte group: 16 / 8 / 4
+  constexpr int NQ = 32 / EPG;    // groups per output word: 2 / 4 / 8
+  const int n = blockIdx.x / chunks, chunk = blockIdx.x - n * chunks;
+  const int img = __builtin_amdgcn_readfirstlane(image_index[n]);
+  if ((unsigned)img >= (unsigned)P) return;   // (uniform) before the frame row is addressed
+  const FrameRow r = frame_row_load(frames + img);
+  if (!frame_row_ok(r, max_h, max_w)) return;   // (uniform) a broken row: nothing read, nothing written
+  const long long oo = plane_offset(out_offsets, n);
+  if (oo < 0 || (oo & 3) != 0) return;   // (uniform) before an address is formed from it: the fit refuses this instance too
+  const int nwords = (r.H * r.W) >> 5;   // (<= the bounds' plane: H <= max_h, W <= max_w)
+  if (chunk * 256 >= nwords) return;     // (uniform) a chunk beyond this instance's words
+  const int w = chunk * 256 + (int)threadIdx.x;
+  const bool live = w < nwords;
+  const long long so = plane_offset(src_offsets, n);
+  const int pitch = src_pitch ? __builtin_amdgcn_readfirstlane(src_pitch[n]) : r.fw;
+  if (so < 0 || pitch < r.fw) {   // (uniform) a source that cannot be read: an empty plane, never what the memory held before
+    if (live) out[oo + w] = 0u;
+    return;
+  }
+  unsigned pat = 0;
+  if (live) {
+    const int wpr = r.W >> 5;
+    const int v = w / wpr, c0 = (w - v * wpr) << 5;   // row and first column of this word
+    const T* sp = static_cast<const T*>(src) + so + (long long)v * pitch + c0;
+    const bool vec = ((reinterpret_cast<uintptr_t>(src) + (unsigned long long)so * ES) & 15) == 0 && (((long long)pitch * ES) & 15) == 0;   // uniform
+    const bool last = v == r.H - 1;
+#pragma unroll
+    for (int g = 0; g < NQ; ++g) {
+      const int cg = c0 + g * EPG;
+      unsigned gb = 0;
+      if (vec && cg < r.fw && (!last || cg + EPG <= r.fw)) {
+        gb = pack_group<KIND>(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(sp + g * EPG)), thr);
+      } else {
+#pragma unroll
+        for (int e = 0; e < EPG; ++e)
+          if (cg + e < r.fw && pack_pred<KIND>(sp[g * EPG + e], thr)) gb |= 1u << e;
+      }
+      pat |= gb << (g * EPG);
+    }
+    pat &= image_columns(w, r.W, r.fw);
+    out[oo + w] = pat;
+  }
+  label_area(area, n, pat);   // (every lane of the wave takes part)
+}
+
+template <int KIND>
+int pack_masks_frames_launch(const void* src, const la3d_frame* frames, int P, int H, int W, const int32_t* image_index,
+                             const int64_t* src_offsets, const int32_t* src_pitch, int B, float thr, uint32_t* bits,
+                             const int64_t* bits_offsets, int32_t* area, hipStream_t s, int chunks) {
+  hipLaunchKernelGGL(pack_masks_frames_kernel<KIND>, dim3((unsigned)((long long)B * chunks)), dim3(256), 0, s, src, frames, P, H, W, chunks,
+                     image_index, reinterpret_cast<const long long*>(src_offsets), src_pitch, thr, bits,
+                     reinterpret_cast<const long long*>(bits_offsets), area);
+  return check_launch("pack_masks_frames_kernel");
+}
+
+// the checks and the launch the two entries share; kind: PK_*
+int pack_masks_frames(const char* who, const void* src, int kind, float thr, const la3d_frame* frames, int P, int H, int W,
+                      const int32_t* image_index, const int64_t* src_offsets, const int32_t* src_pitch, int B, uint32_t* bits,
+                      const int64_t* bits_offsets, int32_t* area, void* stream) {
+  const char* bad = nullptr;
+  const bool work = B > 0 && P > 0;
+  const long long words = H > 0 && W > 0 ? (long long)H * ((W + 31) / 32) : 0;   // the bounds' plane: rows of whole words
+  const long long chunks = (words + 255) / 256;
+  if (B < 0 || P < 0 || H <= 0 || W <= 0) bad = "bad argument (B, P >= 0, bounds H, W > 0)";
+  else if (words > (1LL << 23) || (long long)B * chunks > 0x7fffffffLL)
+    bad = "bounds or batch too large (H * roundup32(W) <= 2^28, B * ceil(H * roundup32(W) / 8192) < 2^31)";
+  else if (work && (!src || !frames || !image_index || !src_offsets || !bits || !bits_offsets))
+    bad = "NULL source, frames, image_index, src_offsets, bits or bits_offsets";
+  else if (work && (reinterpret_cast<uintptr_t>(src) & (kind == PK_F32 ? 3 : kind == PK_U8 ? 0 : 1))) bad = "source not aligned to its element size";
+  else if (work && (reinterpret_cast<uintptr_t>(bits) & 3)) bad = "bits not a 4-byte aligned pointer";
+  else if (work && ((reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(src_offsets) | reinterpret_cast<uintptr_t>(bits_offsets)) & 7))
+    bad = "frames, src_offsets or bits_offsets not an 8-byte aligned pointer";
+  else if (work && ((reinterpret_cast<uintptr_t>(image_index) | reinterpret_cast<uintptr_t>(src_pitch) | reinterpret_cast<uintptr_t>(area)) & 3))
+    bad = "image_index, src_pitch or area not a 4-byte aligned pointer";
+  if (bad) {
+    char msg[240];
+    snprintf(msg, sizeof(msg), "%s: %s", who, bad);
+    set_err(msg);
+    return LA3D_ERR_ARG;
+  }
+  if (!work) return LA3D_SUCCESS;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (area) {   // (as la3d_pack_label_bits: a kernel node of the call's own when captured)
+    hipLaunchKernelGGL(clear_area_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, area, B);
+    const int rc = check_launch("clear_area_kernel");
+    if (rc != LA3D_SUCCESS) return rc;
+  }
+  const int c = (int)chunks;
+  switch (kind) {
+    case PK_U8: return pack_masks_frames_launch<PK_U8>(src, frames, P, H, W, image_index, src_offsets, src_pitch, B, thr, bits, bits_offsets, area, s, c);
+    case PK_F32: return pack_masks_frames_launch<PK_F32>(src, frames, P, H, W, image_index, src_offsets, src_pitch, B, thr, bits, bits_offsets, area, s, c);
+    case PK_F16: return pack_masks_frames_launch<PK_F16>(src, frames, P, H, W, image_index, src_offsets, src_pitch, B, thr, bits, bits_offsets, area, s, c);
+    default: return pack_masks_frames_launch<PK_BF16>(src, frames, P, H, W, image_index, src_offsets, src_pitch, B, thr, bits, bits_offsets, area, s, c);
+  }
+}
+}  // namespace
+
+extern "C" {
+
+int la3d_pack_mask_bits_frames(const uint8_t* mask, const la3d_frame* frames, int32_t P, int H, int W, const int32_t* image_index,
+                               const int64_t* src_offsets, const int32_t* src_pitch, int B, uint32_t* bits, const int64_t* bits_offsets,
+                               int32_t* area, void* stream) {
+  return pack_masks_frames("la3d_pack_mask_bits_frames", mask, PK_U8, 0.0f, frames, P, H, W, image_index, src_offsets, src_pitch, B, bits,
+                           bits_offsets, area, stream);
+}
+
+int la3d_pack_logits_bits_frames(const void* logits, int dtype, float threshold, const la3d_frame* frames, int32_t P, int H, int W,
+                                 const int32_t* image_index, const int64_t* src_offsets, const int32_t* src_pitch, int B, uint32_t* bits,
+                                 const int64_t* bits_offsets, int32_t* area, void* stream) {
+  if (dtype != LA3D_DTYPE_F32 && dtype != LA3D_DTYPE_F16 && dtype != LA3D_DTYPE_BF16) {
+    set_err("la3d_pack_logits_bits_frames: unknown dtype (LA3D_DTYPE_F32, LA3D_DTYPE_F16 or LA3D_DTYPE_BF16)");
+    return LA3D_ERR_ARG;
+  }
+  const int kind = dtype == LA3D_DTYPE_F32 ? PK_F32 : dtype == LA3D_DTYPE_F16 ? PK_F16 : PK_BF16;
+  return pack_masks_frames("la3d_pack_logits_bits_frames", logits, kind, threshold, frames, P, H, W, image_index, src_offsets, src_pitch, B,
+                           bits, bits_offsets, area, stream);
+}
+
+}  // extern "C"

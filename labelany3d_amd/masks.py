@@ -24,7 +24,7 @@ from __future__ import annotations
 import ctypes as C
 import itertools
 import threading
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -1259,7 +1259,8 @@ def pack_label_bits_frames(labels: PackedLabels, ids, stream=None, out=None) -> 
 def fit_instances_frames_bits(frames, bits: FrameBits, K, image_index=None, ground=None, sample_idx=None, filter=None, proj: bool = False,
                               area_hint=None, height_rule: str = "rows", stream=None, method: str = "pca", _fitter=None):
     """``fit_instances_frames`` with the masks given as bit planes, one per instance, each of its own image's frame (C-ABI
-    ``la3d_fit_instances_frames_bits``): what ``pack_label_bits_frames`` makes of the label maps of a panoptic dataset.  ``frames``: a
+    ``la3d_fit_instances_frames_bits``): what ``pack_label_bits_frames`` makes of the label maps of a panoptic dataset, or
+    ``pack_mask_bits_frames`` of the per-image mask / logit stacks of an instance-segmentation network.  ``frames``: a
     ``PackedFrames`` or ``PackedFrames16`` laid out by the SAME frame table as the planes (``bits.table``; a mismatch is a ValueError
     before any device work); ``image_index`` defaults to ``bits.image_index``; ``ground`` / ``sample_idx`` / ``filter`` / ``proj`` /
     ``area_hint`` as in ``fit_instances_frames``, ``height_rule`` as in ``fit_instances_bits``.  An instance whose image index, frame
@@ -1309,6 +1310,212 @@ def fit_instances_frames_labels(frames, label_maps, ids, K, image_index=None, gr
     fdepth = getattr(frames, "data", None) if isinstance(frames, PackedFrames16) else getattr(frames, "depth", None)
     pl = label_maps if isinstance(label_maps, PackedLabels) else pack_label_frames(label_maps, rgb=rgb, device=getattr(fdepth, "device", None))
     fb = pack_label_bits_frames(pl, ids, stream=stream)
+    out = fit_instances_frames_bits(frames, fb, K, image_index=image_index, ground=ground, sample_idx=sample_idx, filter=filter, proj=proj,
+                                    area_hint=fb.area, height_rule=height_rule, stream=stream, method=method)
+    out["bits"] = fb
+    return out
+
+
+# ---- network masks and logits of images of different sizes (include/la3d.h: la3d_pack_mask_bits_frames / la3d_pack_logits_bits_frames) --
+MASKS_U8 = -1
+"""``PackedMasks.kind`` of uint8 / boolean masks; logits carry their ``_lib.DTYPE_*`` code."""
+_MASK_TORCH = {torch.bool: MASKS_U8, torch.uint8: MASKS_U8, **_LOGIT_DTYPES}
+_MASK_NUMPY = {np.dtype(np.bool_): MASKS_U8, np.dtype(np.uint8): MASKS_U8, np.dtype(np.float32): _lib.DTYPE_F32, np.dtype(np.float16): _lib.DTYPE_F16}
+_MASK_STORE = {MASKS_U8: torch.uint8, _lib.DTYPE_F32: torch.float32, _lib.DTYPE_F16: torch.float16, _lib.DTYPE_BF16: torch.bfloat16}
+
+
+class PackedMasks(NamedTuple):
+    """Per-image stacks of masks or logits of different sizes behind one base pointer (``pack_mask_frames``; C-ABI
+    ``la3d_pack_mask_bits_frames`` / ``la3d_pack_logits_bits_frames``): ``data`` flat ``torch.uint8`` / ``float32`` / ``float16`` /
+    ``bfloat16`` - the plane of row n starts ``offsets[n]`` ELEMENTS (int64 (B,)) behind ``data``'s first element and has the
+    ``(H_p, W_p)`` of image ``image_index[n]`` (int32 (B,)), its rows ``pitch[n]`` elements apart (int32 (B,); None: ``W_p`` apart -
+    dense planes) -; ``table`` / ``table_host`` / ``H`` / ``W`` / ``sizes`` as in ``PackedFrames`` - the table IS the one
+    ``pack_frames`` gives depth maps of the same sizes; ``kind``: ``MASKS_U8`` or the logits' ``_lib.DTYPE_*`` code;
+    ``bits_offsets`` int64 (B,) on the device of ``data`` / ``bits_words``: the layout ``frame_bits_offsets`` gives the bit planes of
+    these rows (resident, so that ``pack_mask_bits_frames`` uploads nothing; None / 0: computed there); ``sources``: the tensors
+    ``data`` aliases (a zero-copy pack), kept alive with the result."""
+    data: torch.Tensor
+    offsets: torch.Tensor
+    pitch: Optional[torch.Tensor]
+    image_index: torch.Tensor
+    table: torch.Tensor
+    table_host: np.ndarray
+    H: int
+    W: int
+    sizes: list
+    kind: int
+    bits_offsets: Optional[torch.Tensor] = None
+    bits_words: int = 0
+    sources: tuple = ()
+
+
+def _mask_stacks(stacks):
+    """the argument errors of per-image mask stacks that need no device -> (stacks, kind, sizes, counts)"""
+    stacks = list(stacks)
+    kind = None
+    for p, m in enumerate(stacks):
+        dt = m.dtype if isinstance(m, torch.Tensor) else np.asarray(m).dtype
+        one = _MASK_TORCH.get(dt) if isinstance(m, torch.Tensor) else _MASK_NUMPY.get(dt)
+        if one is None:
+            raise ValueError(f"mask stack {p} (image {p}) must be bool, uint8, float32, float16 or bfloat16, not {dt}")
+        if len(m.shape) != 3:
+            raise ValueError(f"mask stack {p} (image {p}) must be (N, H, W), got {tuple(m.shape)}")
+        if kind is not None and one != kind:
+            raise ValueError(f"mask stack {p} (image {p}) has another dtype than mask stack 0: pack stacks of one dtype")
+        kind = one
+        if int(m.shape[1]) <= 0 or int(m.shape[2]) <= 0:
+            raise ValueError(f"mask stack {p} (image {p}) has an empty frame {(int(m.shape[1]), int(m.shape[2]))}")
+    sizes = [(int(m.shape[1]), int(m.shape[2])) for m in stacks]
+    counts = [int(m.shape[0]) for m in stacks]
+    return stacks, (MASKS_U8 if kind is None else kind), sizes, counts
+
+
+def _mask_in_place(m, dev) -> bool:
+    """a device stack the packer can read where it lies: adjacent pixels, rows at least a frame's width apart"""
+    if not (isinstance(m, torch.Tensor) and m.is_cuda and m.device == dev):
+        return False
+    n, h, w = m.shape
+    return (w == 1 or m.stride(2) == 1) and (h == 1 or m.stride(1) >= w) and m.stride(1) < 2 ** 31
+
+
+def pack_mask_frames(stacks, device=None, pinned=None) -> PackedMasks:
+    """The outputs of an instance-segmentation network for images of DIFFERENT sizes -> ``PackedMasks``.  ``stacks``: a sequence over
+    IMAGES of (N_p, H_p, W_p) arrays / tensors (N_p may be 0), all of ONE dtype out of bool / uint8 (masks: non-zero = inside) and
+    float32 / float16 / bfloat16 (logits, thresholded by ``pack_mask_bits_frames``); row n of the result is the n-th plane in image
+    order.  The table is ``frame_table(sizes)`` - the one ``pack_frames`` gives depth maps of the same sizes, so ONE table serves the
+    packer and the fit.
+    Host stacks are laid back to back, dense - no padding of the rows -, into one buffer and uploaded in one copy (``pinned``: a pinned
+    staging tensor of the stored dtype and at least the packed size; the upload is then asynchronous on the current stream).
+    DEVICE stacks whose planes have adjacent pixels (``stride(2) == 1``, ``stride(1) >= W_p``) are NOT copied: ``data`` is a flat view
+    based at the lowest ``data_ptr()`` among them, ``offsets`` the element distances from there and ``pitch`` given where any
+    ``stride(1) != W_p`` - a network's outputs read where they lie, the top-left crop of a padded canvas included; the result keeps
+    the tensors alive (``sources``).  Anything else is made dense first.  ``device="cpu"`` gives the dense layout on the host (no GPU
+    needed).  ValueError, naming the image: mixed dtypes, a stack that is not 3-D, an empty frame."""
+    stacks, kind, sizes, counts = _mask_stacks(stacks)
+    dev = torch.device(device) if device is not None and torch.device(device).type == "cpu" else _dev(device)
+    tdt = _MASK_STORE[kind]
+    es = torch.empty(0, dtype=tdt).element_size()
+    table = frame_table(sizes)
+    P, B = len(stacks), sum(counts)
+    ii = np.repeat(np.arange(P, dtype=np.int32), counts)
+    pitch, sources = None, ()
+    live = [m for m, c in zip(stacks, counts) if c]
+
+    def stored(m):   # the stack in the stored dtype (bool as its bytes)
+        if isinstance(m, torch.Tensor):
+            return m.view(torch.uint8) if m.dtype == torch.bool else m
+        a = np.asarray(m)
+        return a.view(np.uint8) if a.dtype == np.bool_ else a
+
+    if dev.type == "cuda" and live and all(_mask_in_place(m, dev) for m in live):
+        live = [stored(m) for m in live]
+        low = min(live, key=lambda m: m.data_ptr())
+        base = low.data_ptr()
+        data = low.as_strided((low.untyped_storage().nbytes() // es - low.storage_offset(),), (1,))
+        offs, pit = [], []
+        for m, c, (h, w) in zip(stacks, counts, sizes):
+            if c:
+                first = (m.data_ptr() - base) // es
+                offs.append(first + np.arange(c, dtype=np.int64) * (m.stride(0) if c > 1 else 0))
+                pit.append(np.full(c, m.stride(1) if h > 1 else w, np.int32))
+        offsets = np.concatenate(offs)
+        pit = np.concatenate(pit)
+        if (pit != np.asarray(sizes, np.int64).reshape(-1, 2)[ii, 1]).any():
+            pitch = pit
+        sources = tuple(live)
+    else:
+        words = np.asarray([h * w for h, w in sizes], np.int64)[ii] if B else np.zeros(0, np.int64)
+        offsets = np.zeros(B, np.int64)
+        np.cumsum(words[:-1], out=offsets[1:])
+        total = int(words.sum())
+        n = max(total, 16)
+        starts = np.concatenate([[0], np.cumsum([c * h * w for c, (h, w) in zip(counts, sizes)])]).astype(np.int64)
+        if any(isinstance(m, torch.Tensor) and m.is_cuda for m in stacks):
+            data = torch.zeros(n, dtype=tdt, device=dev)
+            for m, o, c, (h, w) in zip(stacks, starts, counts, sizes):
+                if c:
+                    data[o:o + c * h * w].view(c, h, w).copy_(torch.as_tensor(stored(m)).to(device=dev))
+        else:
+            if pinned is not None and pinned.dtype == tdt and pinned.numel() >= n:
+                host_t = pinned[:n]
+            else:
+                pinned, host_t = None, torch.empty(n, dtype=tdt)
+            host_t[total:] = 0
+            for m, o, c, (h, w) in zip(stacks, starts, counts, sizes):
+                if c:
+                    host_t[o:o + c * h * w].view(c, h, w).copy_(torch.as_tensor(stored(m)))
+            data = host_t if dev.type == "cpu" else host_t.to(dev, non_blocking=pinned is not None)
+    tab_words = np.ascontiguousarray(table).view(np.int32).reshape(P, 6) if P else np.zeros((0, 6), np.int32)
+    boffs, bwords = frame_bits_offsets(table, ii)
+    small = [(offsets, torch.int64), (boffs, torch.int64), (ii, torch.int32), (tab_words.copy(), torch.int32), (pitch, torch.int32)]
+    if dev.type == "cpu":
+        offs_t, boffs_t, ii_t, tab, pitch_t = [None if a is None else torch.as_tensor(np.ascontiguousarray(a)) for a, _ in small]
+    else:
+        with torch.cuda.device(dev):
+            offs_t, boffs_t, ii_t, tab, pitch_t = _upload_many(small, dev)
+    bounds = (max((h for h, _ in sizes), default=0), max((padded_width(w) for _, w in sizes), default=0))
+    return PackedMasks(data, offs_t, pitch_t, ii_t, tab, table, *bounds, sizes, kind, boffs_t, bwords, sources)
+
+
+def pack_mask_bits_frames(masks, threshold: float = 0.0, stream=None, out=None) -> FrameBits:
+    """``pack_mask_bits`` / ``pack_logits_bits`` for the stacks of images of different sizes (C-ABI ``la3d_pack_mask_bits_frames`` /
+    ``la3d_pack_logits_bits_frames``): ONE launch reads every plane once, where it lies, and writes per row the bit plane of its
+    image's OWN frame - ``H_p * padded_width(W_p) / 32`` words, the bits of the padding columns zero - laid out by
+    ``frame_bits_offsets(table_host, image_index)``.  ``masks``: a ``PackedMasks``, or a sequence that goes through
+    ``pack_mask_frames``; ``threshold``: logits only (bit = x > threshold in float32; NaN gives 0); ``out``: as in
+    ``pack_label_bits_frames``.  With a resident ``PackedMasks`` nothing is uploaded and nothing synchronises.  Returns ``FrameBits``."""
+    pm = masks if isinstance(masks, PackedMasks) else pack_mask_frames(masks)
+    if pm.kind not in _MASK_STORE or pm.data.dtype != _MASK_STORE[pm.kind]:
+        raise ValueError(f"PackedMasks.kind {pm.kind!r} does not name the dtype of its data ({pm.data.dtype})")
+    if not pm.data.is_cuda:
+        raise ValueError("the masks must live on the GPU (pack_mask_frames with a GPU device)")
+    dev = pm.data.device
+    P, B = len(pm.sizes), int(pm.offsets.numel())
+    with torch.cuda.device(dev):
+        if pm.bits_offsets is None:
+            offs_h, total = frame_bits_offsets(pm.table_host, pm.image_index.cpu().numpy())
+            offs = _as_dev(offs_h, torch.int64, dev)
+        else:
+            offs, total = pm.bits_offsets, int(pm.bits_words)
+        if out is None:
+            o = torch.empty(max(total, 4), dtype=torch.int32, device=dev)
+        else:
+            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int32 and out.dim() == 1 and out.is_contiguous()
+                    and out.numel() >= total and out.data_ptr() % 16 == 0):
+                raise ValueError(f"out must be a flat, 16-byte aligned int32 device tensor of at least {total} words")
+            o = out
+        area = torch.empty(B, dtype=torch.int32, device=dev)
+        tail = (_ptr(pm.table), P, pm.H, pm.W, _ptr(pm.image_index), _ptr(pm.offsets), _ptr(pm.pitch), B, _ptr(o), _ptr(offs), _ptr(area),
+                _stream(stream))
+        if pm.kind == MASKS_U8:
+            check(lib.la3d_pack_mask_bits_frames(_ptr(pm.data), *tail), "la3d_pack_mask_bits_frames")
+        else:
+            check(lib.la3d_pack_logits_bits_frames(_ptr(pm.data), pm.kind, float(threshold), *tail), "la3d_pack_logits_bits_frames")
+    _record(stream, pm.data, pm.table, pm.image_index, pm.offsets, pm.pitch, offs, o, area, *pm.sources)
+    return FrameBits(o, offs, pm.image_index, area, pm.table_host, pm.H, pm.W)
+
+
+def fit_instances_frames_masks(frames, masks, K, threshold: float = 0.0, image_index=None, ground=None, sample_idx=None, filter=None,
+                               proj: bool = False, height_rule: str = "rows", stream=None, method: str = "pca"):
+    """The depth + mask fit of the per-image mask / logit stacks of an instance-segmentation network, images of DIFFERENT sizes, in
+    one call: ``pack_mask_frames`` (skipped for a ``PackedMasks``), ``pack_mask_bits_frames`` (one launch over the planes where they
+    lie), then ``fit_instances_frames_bits`` with the rows' ``image_index`` and their exact areas as ``area_hint``.  ``frames``: the
+    ``PackedFrames`` / ``PackedFrames16`` of the depth maps of the same images in the same order (another ``(H_p, W_p)`` than the
+    masks': ValueError before any device work); ``threshold``: logits only; the other arguments as in ``fit_instances_frames_bits``,
+    per plane in image order.  Returns its dict plus ``"bits"``: the ``FrameBits``.  With a resident ``PackedMasks`` nothing
+    synchronises and the call can be captured into a graph."""
+    if _lib.method_code(method) != _lib.METHOD_PCA:
+        raise ValueError("fit_instances_frames_masks: method='convex_hull' is not supported for frames of different sizes; group by size and use fit_instances_bits")
+    height_rule_code(height_rule)
+    if isinstance(masks, PackedMasks):
+        sizes = masks.sizes
+    else:
+        masks, _, sizes, _ = _mask_stacks(masks)
+    if [tuple(s) for s in sizes] != [tuple(s) for s in getattr(frames, "sizes", ())]:
+        raise ValueError("the masks have another (H, W) per image than the depth: give one stack per depth map, each of its image's size, in the same order")
+    fdepth = getattr(frames, "data", None) if isinstance(frames, PackedFrames16) else getattr(frames, "depth", None)
+    pm = masks if isinstance(masks, PackedMasks) else pack_mask_frames(masks, device=getattr(fdepth, "device", None))
+    fb = pack_mask_bits_frames(pm, threshold=threshold, stream=stream)
     out = fit_instances_frames_bits(frames, fb, K, image_index=image_index, ground=ground, sample_idx=sample_idx, filter=filter, proj=proj,
                                     area_hint=fb.area, height_rule=height_rule, stream=stream, method=method)
     out["bits"] = fb
