@@ -670,6 +670,77 @@ int la3d_fit_points(const double* points, const int64_t* offsets, const double* 
                     const int32_t* sample_idx, int method, int B,
                     double* out, int32_t* status, double* aux, void* stream);
 
+/* ---- instance point clouds ----------------------------------------------------------------------------------------------
+ * The intermediate the fused fit never materialises: the per-instance cloud
+ *     pts[n] = depth_to_points(depth[img(n)][None], K[img(n)])[mask[n]]          # src/util.py:52-75, :480-481
+ * row-major (v ascending, then u ascending: NumPy's order), all B clouds packed into ONE array with an offsets array - exactly what
+ * la3d_fit_points takes - for a PLY per object, another estimator, an aligner, or a look at what a box was fitted from.  Two stages
+ * on the caller's stream; neither synchronises, so the chain can be captured into a HIP graph:
+ *   la3d_instance_point_offsets(args)  counts[n] (i32 [B]) = the true pixels N_n of instance n - a non-zero byte of a u8 plane or a set
+ *       bit of a bit plane, in columns < frame_width only -, offsets (i64 [B+1]) = the exclusive prefix of the rows each instance
+ *       gets: N_n, or - with sample_idx - N_n if N_n <= 500, else 500 (the reference's rule, src/util_3dbox.py:123).  The scan runs on
+ *       the device, deterministic, any B.  Per-band counts stay in `workspace` for the gather.  B == 0: offsets[0] = 0.
+ *   la3d_gather_instance_points(args)  row offsets[n] + r of `points` = the point of the pixel of rank r of instance n (the rank of a
+ *       pixel = the set pixels before it in row-major order, from popcount prefixes - never from atomics); with sample_idx and
+ *       N_n > 500 row offsets[n] + j = the point of rank sample_idx[n][j] (repeated ranks repeat the row; a rank outside [0, N_n) gives a
+ *       NaN row and pixel -1).  pixels (optional) = v * frame_width + u, the flat index in the unpadded image.
+ * Both take the SAME block (the gather reads offsets and workspace as the first stage left them; points, pixels, status, capacity and
+ * out_is_f64 are not read by the first stage, counts not by the second).
+ * VALUE.  (d * Kinv) @ [u, v, 1] followed by the identity R, t multiply - the arithmetic of la3d_unproject_batch, K inverted in the
+ *   kernel by the same elimination - so a row equals the row of la3d_unproject_batch's output bit for bit (float32 output: the cast of
+ *   the float64 value).  NaN, inf, zero and negative depths are kept as they come (a NaN / inf depth poisons its row as there): this is
+ *   the cloud BEFORE estimate_bbox drops anything.  16-bit planes: the value rules of "16-bit depth planes", unchanged - a call gives
+ *   the rows of the float32 call on la3d_unpack_depth16's output, bit for bit.
+ * FORMS.  frames == NULL: B instances of ONE H x W (W = pixels per row in memory; frame_width 0 = W, else the image columns).
+ *   depth float32 planes depth_plane_stride floats apart (0 = one shared plane), or depth16 (its own plane_stride; depth_plane_stride 0);
+ *   plane of instance n = image_index[n] or n, K likewise (k_stride 0 = shared).  mask: u8 planes mask_plane_stride bytes apart
+ *   (0 = H*W; any width, any alignment - 16-byte groups where a band of rows is aligned, a general form behind it), or mask_bits: bit
+ *   planes in the layout of la3d_pack_mask_bits, pitch W, bits_plane_stride words apart (0 = the words of a plane), 4-byte aligned.
+ *   frames != NULL selects the FRAMES form (one pair of entries serves both): the ragged depth buffer + la3d_frame table (P rows) of
+ *   la3d_fit_instances_frames / _frames_depth16 and bit planes at per-instance bits_offsets as in la3d_fit_instances_frames_bits;
+ *   H, W are bounds, image_index is required, depth_plane_stride / frame_width / depth16->plane_stride must be 0, mask_bits 16-byte and
+ *   the depth base 16-byte (16-bit: 8-byte) aligned.  An instance whose image index is outside [0, P), whose frame row breaks the
+ *   la3d_frame contract or whose plane offset is negative or not a multiple of 4 gets count 0 in the first stage and
+ *   LA3D_BOX_UNSUPPORTED (5) with nothing written in the second - decided on the device before any address is formed from the row.
+ * STATUS (i32 [B], written by the gather).  The gather never writes outside rows [offsets[n], offsets[n+1]) of its own instance,
+ *   whatever the masks hold: LA3D_CLOUD_NO_ROOM - the range does not lie within [0, capacity]: nothing of the instance is written;
+ *   LA3D_CLOUD_MISMATCH - the mask count differs from the range length, or a band's count from what the first stage left in the
+ *   workspace (the masks changed between the two calls): the range is filled only as far as it reaches.
+ * workspace: la3d_instance_points_workspace_bytes(B, H, W) bytes, 4-byte aligned; ONE workspace serves one pair of calls at a time.
+ * LA3D_ERR_ARG before any launch: a bad struct_size, both or neither of mask / mask_bits, both or neither of depth / depth16, a bad
+ *   la3d_depth16, frame_width outside [0, W], negative sizes or strides, strides below a plane, NULL K / workspace / outputs with work to
+ *   do, misaligned mask_bits / bits_offsets / frames / depth, frames with u8 masks or without image_index, bits_offsets without
+ *   frames.  LA3D_ERR_UNSUPPORTED: W > 65536 (a row must fit a band's bit image in LDS), H * W >= 2^31, B x bands >= 2^31. */
+#define LA3D_CLOUD_OK 0
+#define LA3D_CLOUD_NO_ROOM 1
+#define LA3D_CLOUD_MISMATCH 2
+typedef struct la3d_cloud_args {
+  int32_t struct_size;                                   /* sizeof(la3d_cloud_args) of the caller */
+  int32_t B, H, W;
+  int32_t frame_width;                                   /* 0 = W */
+  int32_t k_stride;
+  const float* depth; int64_t depth_plane_stride;        /* float32 planes, or NULL with depth16 */
+  const la3d_depth16* depth16;                           /* HOST block, read before the call returns */
+  const int32_t* image_index;                            /* dev [B] | NULL (frames: required) */
+  const uint8_t* mask; int64_t mask_plane_stride;        /* u8 planes | NULL */
+  const uint32_t* mask_bits; int64_t bits_plane_stride;  /* bit planes | NULL */
+  const double* K;
+  const int32_t* sample_idx;                             /* dev [B][500] | NULL */
+  const la3d_frame* frames; int32_t P;                   /* dev [P] | NULL: the frames form */
+  int32_t out_is_f64;                                    /* points: f64 (the reference's dtype) when != 0, else f32 */
+  const int64_t* bits_offsets;                           /* dev [B], frames form */
+  int32_t* counts;                                       /* dev [B]: first stage */
+  int64_t* offsets;                                      /* dev [B+1]: written by the first stage, read by the second */
+  void* points;                                          /* dev [capacity][3] */
+  int32_t* pixels;                                       /* dev [capacity] | NULL */
+  int32_t* status;                                       /* dev [B] */
+  int64_t capacity;                                      /* rows of points / pixels */
+  void* workspace; void* stream;
+} la3d_cloud_args;
+size_t la3d_instance_points_workspace_bytes(int B, int H, int W);   /* host, no device; 0 for B, H or W <= 0 */
+int la3d_instance_point_offsets(const la3d_cloud_args* args);
+int la3d_gather_instance_points(const la3d_cloud_args* args);
+
 /* Host-pointer single calls (round 5): the reference's own calling pattern is one object / one image per call on NumPy arrays.
  * One C call = upload + kernel + download, synchronous, on a private stream of the calling thread; the staging memory (pinned and
  * device-mapped for the cloud, device scratch for the frame) belongs to the library, is per thread and per device, grows on demand

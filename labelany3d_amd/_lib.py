@@ -49,7 +49,26 @@ class Frame(C.Structure):
     _fields_ = [("depth_offset", C.c_int64), ("H", C.c_int32), ("W", C.c_int32), ("frame_width", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CloudArgs(C.Structure):
+    """``la3d_cloud_args`` of include/la3d.h (argument block of la3d_instance_point_offsets / la3d_gather_instance_points, 192 bytes);
+    field order is the header's."""
+    _fields_ = [("struct_size", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("frame_width", C.c_int32), ("k_stride", C.c_int32),
+                ("depth", C.c_void_p), ("depth_plane_stride", C.c_int64), ("depth16", C.POINTER(Depth16Block)),
+                ("image_index", C.c_void_p),
+                ("mask", C.c_void_p), ("mask_plane_stride", C.c_int64), ("mask_bits", C.c_void_p), ("bits_plane_stride", C.c_int64),
+                ("K", C.c_void_p), ("sample_idx", C.c_void_p),
+                ("frames", C.c_void_p), ("P", C.c_int32), ("out_is_f64", C.c_int32), ("bits_offsets", C.c_void_p),
+                ("counts", C.c_void_p), ("offsets", C.c_void_p), ("points", C.c_void_p), ("pixels", C.c_void_p), ("status", C.c_void_p),
+                ("capacity", C.c_int64), ("workspace", C.c_void_p), ("stream", C.c_void_p)]
+
+
+CLOUD_OK, CLOUD_NO_ROOM, CLOUD_MISMATCH = 0, 1, 2   # status of la3d_gather_instance_points (5 = BOX_UNSUPPORTED: a refused frames row)
+
 _SIGS = {
+    "la3d_instance_points_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "la3d_instance_point_offsets": (C.c_int, [C.POINTER(CloudArgs)]),
+    "la3d_gather_instance_points": (C.c_int, [C.POINTER(CloudArgs)]),
     "la3d_fit_instances_ex": (C.c_int, [C.POINTER(FitArgs)]),
     "la3d_fit_instances_frames": (C.c_int, [C.POINTER(FitArgs), C.c_void_p, C.c_int32]),
     "la3d_fit_instances_frames_depth16": (C.c_int, [C.POINTER(FitArgs), C.POINTER(Depth16Block), C.c_void_p, C.c_int32]),
