@@ -709,7 +709,7 @@ int la3d_fit_points(const double* points, const int64_t* offsets, const double* 
  * workspace: la3d_instance_points_workspace_bytes(B, H, W) bytes, 4-byte aligned; ONE workspace serves one pair of calls at a time.
  * LA3D_ERR_ARG before any launch: a bad struct_size, both or neither of mask / mask_bits, both or neither of depth / depth16, a bad
  *   la3d_depth16, frame_width outside [0, W], negative sizes or strides, strides below a plane, NULL K / workspace / outputs with work to
- *   do, misaligned mask_bits / bits_offsets / frames / depth, frames with u8 masks or without image_index, bits_offsets without
+ *   do (points may be NULL with capacity 0: every cloud is empty or has no room, no row is written), misaligned mask_bits / bits_offsets / frames / depth, frames with u8 masks or without image_index, bits_offsets without
  *   frames.  LA3D_ERR_UNSUPPORTED: W > 65536 (a row must fit a band's bit image in LDS), H * W >= 2^31, B x bands >= 2^31. */
 #define LA3D_CLOUD_OK 0
 #define LA3D_CLOUD_NO_ROOM 1

@@ -462,7 +462,8 @@ int cloud_check(const la3d_cloud_args* args, const char* who, bool gather, la3d_
   if (!a.workspace || (reinterpret_cast<uintptr_t>(a.workspace) & 3)) return fail(LA3D_ERR_ARG, who, "workspace NULL or not 4-byte aligned (la3d_instance_points_workspace_bytes)");
   if (!a.offsets) return fail(LA3D_ERR_ARG, who, "offsets is NULL");
   if (!gather && !a.counts) return fail(LA3D_ERR_ARG, who, "counts is NULL");
-  if (gather && (!a.points || !a.status)) return fail(LA3D_ERR_ARG, who, "points / status is NULL");
+  // (capacity 0 - a batch of empty masks sized exactly - has no row to point at: points may be NULL there, no row is ever written)
+  if (gather && ((!a.points && a.capacity > 0) || !a.status)) return fail(LA3D_ERR_ARG, who, "points / status is NULL");
   if (gather && a.capacity < 0) return fail(LA3D_ERR_ARG, who, "negative capacity");
   if (a.mask_bits && (reinterpret_cast<uintptr_t>(a.mask_bits) & 3)) return fail(LA3D_ERR_ARG, who, "mask_bits not 4-byte aligned");
   if (a.frames) {

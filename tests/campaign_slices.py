@@ -12,7 +12,9 @@ failure on one of them is a regression since then.
   HULL_SEEDS          NO campaign record yet (oracle/campaigns/hull.py: the convex-hull yaw of the depth + mask fit): picked by the
                       CPU scan of seeds 70000 ... 70499 alone.  The slice itself has passed on an MI355X; the range as a whole has
                       not run, so a failure on another seed of it need not be a regression.  profiles/hull/fuzz_hull.py writes the
-                      record (profiles/hull/fuzz_hull.txt) - commit it with the first run of the range"""
+                      record (profiles/hull/fuzz_hull.txt) - commit it with the first run of the range
+  CLOUD_SEEDS         profiles/clouds/fuzz_clouds.txt (oracle/campaigns/clouds.py: the instance point clouds; seeds 80000 ... 80499:
+                      the whole range has run, see the record)"""
 
 ENGINE_SEEDS = [
     10018, 10023, 10025, 10032, 10034, 10046, 10050, 10051, 10056, 10058,
@@ -46,4 +48,18 @@ HULL_SEEDS = [
     70218, 70225, 70235, 70237, 70244, 70246, 70262, 70268, 70279, 70285,
     70329, 70350, 70354, 70368, 70380, 70386, 70404, 70405, 70411, 70432,
     70450, 70452, 70455, 70456, 70469, 70470, 70475, 70483, 70487, 70493,
+]
+
+# the campaign of the instance point clouds (oracle/campaigns/clouds.py), picked by a CPU scan of seeds 80000 ... 80499: bands of 1024
+# words (all set, the last word short, fewer than 32 pixels over the whole table), a band count BAND_PIX dictates, scan chunks 1 / 2 / 3
+# (B = 1025, 2049, 2500; 80013: B = 2049 on 33 x 47), both u8 forms within one instance (1000 x 1), empty instances first / last /
+# between and an all-empty case, subsample mode under every run with ranks outside the cloud and instances of exactly 500 / 501 pixels,
+# C-entry frame widths of 1 and more than 64 columns below W, mixed sizes, a shared K with an image_index, every frame of the generator
+# (tests/test_differential_checkers.py::test_cloud_slice_covers asserts all of it)
+CLOUD_SEEDS = [
+    80000, 80001, 80002, 80003, 80004, 80005, 80006, 80007, 80008, 80009,
+    80010, 80011, 80012, 80013, 80014, 80015, 80016, 80017, 80018, 80019,
+    80020, 80021, 80022, 80023, 80024, 80025, 80026, 80027, 80028, 80029,
+    80030, 80032, 80033, 80034, 80035, 80036, 80037, 80038, 80039, 80040,
+    80041, 80042, 80061, 80068, 80136, 80138, 80231, 80340,
 ]

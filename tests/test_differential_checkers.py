@@ -8,6 +8,7 @@ import pytest
 from oracle import la3d_oracle as O
 from oracle.campaigns import annotations as A
 from oracle.campaigns import aux as X
+from oracle.campaigns import clouds as CL
 from oracle.campaigns import engines as E
 from oracle.campaigns import hull as HU
 from oracle.campaigns import points as PT
@@ -517,3 +518,231 @@ def test_hull_checker_flat_and_fallback_rules():
     assert HU.check_run(c, ref, {}, g)
     g = copy.deepcopy(good); g["boxes"][n, 0] += 1e-6 * scale       # (both on the PCA axis, resolved gap: the centre is held too)
     assert HU.check_run(c, ref, {}, g)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the instance point clouds (oracle/campaigns/clouds.py)
+# ---------------------------------------------------------------------------------------------------------------------------------
+CLOUD_REQUIRED = (
+    "uniform: band of 1024 words, all 65536 pixels set", "frames: band of 1024 words, all 65536 pixels set",
+    "uniform: band of 1024 words, the last one short", "frames: rows padded to a pitch of 65536",
+    "uniform: capacity band with fewer than 32 pixels over more than 512 words",
+    "frames: capacity band with fewer than 32 pixels over more than 512 words",
+    "band count from BAND_PIX", "trailing empty bands", "scan chunk 1", "scan chunk 2", "scan chunk 3", "B = 1025", "B = 1",
+    "u8: both forms in one instance", "empty first", "empty last", "empty between", "all empty",
+    "subsample: exactly 500 pixels", "subsample: exactly 501 pixels", "subsample: ranks outside the cloud", "subsample: repeated ranks",
+    "subsample: the last rank", "C entry: more than 64 padding columns", "C entry: frame_width 1",
+    "mixed: four sizes, one without an instance", "K shared, P > 1, image_index", "skew", "no skew", "u8 bytes 0", "u8 bytes 1", "u8 bytes 2")
+
+
+def test_cloud_slice_covers():
+    """The slice of the instance point clouds, from generator and oracle alone - conditions on the INPUTS: a slice that misses one gets
+    other seeds.  Full bands of 1024 words (all set; the last word short; a sparse one whose select searches the whole table), a band
+    count BAND_PIX dictates, scan chunks 1 / 2 / 3 with a ragged last run, both u8 forms within one instance, empty instances in every
+    place, subsample mode under every run, the C entry's padding, mixed sizes, a shared K with an image_index - and the oracle's own
+    rounding: within a tenth of the 1e-13 tolerance of a np.longdouble evaluation with K inverted in closed form."""
+    assert 40 <= len(S.CLOUD_SEEDS) <= 56 and all(80000 <= s < 80500 for s in S.CLOUD_SEEDS) and len(set(S.CLOUD_SEEDS)) == len(S.CLOUD_SEEDS)
+    cases = [CL.make_case(s) for s in S.CLOUD_SEEDS]
+    have = set().union(*[CL.features(c) for c in cases])
+    for name in CLOUD_REQUIRED:
+        assert name in have, name
+    assert "B = 2049" in have or "B = 2500" in have                                 # chunk 3 with a ragged last run
+    assert any(c["B"] == 2049 and c["sizes"][0] == (33, 47) for c in cases)
+    assert {sz for c in cases for sz in c["sizes"]} >= set(CL.TINY) | set(CL.CAPACITY) | {CL.BIG}
+    assert all(c["B"] <= 3 for c in cases if set(c["sizes"]) & (set(CL.CAPACITY) | {CL.BIG}))
+    assert all(max(c["sizes"]) <= (9, 40) or (c["sizes"][0], c["B"]) == ((33, 47), 2049) for c in cases if c["B"] > 300)
+    for r in CL.RUNS:
+        assert sum(CL.applies(c, r) for c in cases) >= 5, r
+        if r:
+            assert f"subsample: {r}" in have, r                                       # (an instance above 500 pixels with sample_idx)
+    assert sum(int((c["counts"] > CL.NSAMPLE).sum()) for c in cases if c["sidx"] is not None) >= 10
+    assert any(c["uniform"] for c in cases) and any(not c["uniform"] for c in cases)
+    worst = 0.0
+    for s, c in zip(S.CLOUD_SEEDS, cases):
+        want = CL.oracle_case(s)
+        for p in range(c["P"]):
+            fin = np.isfinite(c["depth"][p]).reshape(-1)
+            ld = CL.longdouble_cloud(c["depth"][p], c["K"][p])[fin]
+            err = np.abs(want["clouds"]["f32"][p][fin] - ld) / (CL.TOL + CL.TOL * np.abs(ld))
+            worst = max(worst, float(err.max()) if err.size else 0.0)
+    assert worst <= 0.1, worst
+
+
+def test_cloud_campaign_restates_the_band_split():
+    """CL.bands against the library: la3d_instance_points_workspace_bytes is 4 B (bands + 1), sized for the frame's width and for its
+    padded width - for every frame and batch size of the generator and a spread around the thresholds of cloud_bands."""
+    from labelany3d_amd import _lib
+
+    ws = _lib.lib.la3d_instance_points_workspace_bytes
+    frames = CL.TINY + CL.CAPACITY + CL.SMALL + [CL.BIG, (1, 65535), (2, 32768), (2, 32769), (3, 21845), (3, 21846), (5, 65536), (257, 255),
+                                                 (256, 256), (255, 257), (1024, 64), (1025, 64), (4, 7), (5, 7), (2000, 33)]
+    for H, W in frames:
+        for B in CL.BS + CL.LARGE_BS + [4, 127, 128, 129, 1024, 2048, 4096, 8191, 8192, 8193, 100000]:
+            Wp = CL.padded_width(W)
+            want = 4 * B * (max(CL.bands(B, H, W), CL.bands(B, H, Wp)) + 1) if Wp <= CL.BAND_PIX else 0
+            assert ws(B, H, W) == want, (B, H, W)
+    assert CL.bands(1, 3, 65536) == 3 and CL.bands(1, 4, 16384) == 1 and CL.bands(1, 480, 640) == 64 and CL.bands(2500, 9, 40) == 3
+    assert CL.band_words(1, 1, 65536) == [1024] and CL.band_words(1, 2, 65535) == [1024, 1024] and max(CL.band_words(3, 480, 640)) == 80
+    assert [CL.scan_chunk(B) for B in (1, 1024, 1025, 2048, 2049, 2500)] == [1, 1, 2, 2, 3, 3]
+    assert set(CL.u8_forms(2, 1000, 1, 0)) == {"16", "general"} and set(CL.u8_forms(2, 1000, 1, 1)) == {"general"}
+
+
+def test_cloud_campaign_restatements_agree():
+    """The campaign's private copies of the suite's rules: the 16-bit quantisers (tests/depth16_cases.py), the ten standard masks and
+    the cloud rule (tests/instance_points_cases.py) - two independent restatements each."""
+    from tests import depth16_cases as D16
+    from tests import instance_points_cases as IC
+
+    rs = np.random.RandomState(3)
+    d = np.concatenate([CL.special_plane(rs, 40, 70).reshape(-1), np.float32([6.55349, 6.5535, 6.55351, 70000.0, 1e-9, 6e-8, 65504.0, 65520.0, -0.0])])
+    for dtype, scale in [("f16", 1.0)] + [("u16", s) for s in CL.SCALES]:
+        q = CL.quantise(d, dtype, scale)
+        np.testing.assert_array_equal(q, D16.quantise(d, dtype, scale))
+        for hole in (True, False):
+            np.testing.assert_array_equal(CL.upconvert(q, scale, hole), D16.upconvert(q, scale, hole))
+    for H, W in IC.FRAMES:
+        np.testing.assert_array_equal(CL.standard_masks(H, W, 2), IC.standard_masks(H, W, 2))
+    seen = set()
+    for s in S.CLOUD_SEEDS:
+        c = CL.make_case(s)
+        key = (c["sidx"] is not None, c["cfw"] < c["W"]) if c["uniform"] else None
+        if key is None or key in seen or c["B"] > 40 or c["H"] * c["W"] > 70000:
+            continue
+        seen.add(key)
+        want = CL.oracle_case(s)
+        for name, kind in (("f32", "f32"), ("u16h", "u16h"), ("c_u8", "f32")):
+            rule = IC.cloud_rule(np.stack(CL.value_planes(c, kind)), np.stack(c["masks"]), c["K"], c["img"], c["sidx"], want[name]["fw"])
+            for a, b in zip(CL.packed(want[name], np.arange(c["B"])), rule):
+                np.testing.assert_array_equal(a, b, err_msg=f"seed {s} {name}")
+    assert len(seen) == 4
+
+
+def _cloud_output(c, want, r):
+    """The oracle's own output, arranged as a correct run's (the rows the clouds are cut from: the oracle's planes)."""
+    name, kind = CL.variant(c, r)
+    order = CL.run_order(c, r)
+    pts, pix, off, cnt = CL.packed(want[name], order)
+    cap = c["cap"] if r.get("capacity") else None
+    st = np.zeros(c["B"], np.int32)
+    if cap is not None:
+        st = (off[1:] > cap).astype(np.int32)
+        live = np.repeat(st == 0, np.diff(off))
+        T = len(pts)
+        pts = np.concatenate([np.where(live[:, None], pts, CL.SENT), np.full((64, 3), CL.SENT)])
+        pix = np.concatenate([np.where(live, pix, int(CL.SENT)), np.full(64, int(CL.SENT))]).astype(np.int32)
+        assert len(pts) == T + 64
+    if r.get("out") == "f32":
+        pts, pix = pts.astype(np.float32), None
+    return dict(points=pts, pixels=pix, offsets=off, counts=cnt.astype(np.int32), status=st, order=order, rows=want["clouds"][kind], capacity=cap)
+
+
+def test_cloud_checker_passes_the_oracle_in_every_run():
+    seen = set()
+    for s in S.CLOUD_SEEDS[::3]:
+        c, want = CL.make_case(s), CL.oracle_case(s)
+        default = _cloud_output(c, want, {}) if c["uniform"] else None
+        for r in CL.RUNS:
+            if CL.applies(c, r):
+                assert CL.check_run(c, want, r, _cloud_output(c, want, r), default) == [], (s, r)
+                seen.add(repr(r))
+    assert len(seen) == len(CL.RUNS)
+
+
+def _cloud_case():
+    """A uniform case of the slice in subsample mode with a rank outside a cloud, a short capacity that leaves instances on both
+    sides, and a C-entry frame width below W that leaves pixels."""
+    for s in S.CLOUD_SEEDS:
+        c = CL.make_case(s)
+        if not (c["uniform"] and c["sidx"] is not None and c["cap"] is not None and c["cfw"] < c["W"] and 3 <= c["B"] <= 300):
+            continue
+        want = CL.oracle_case(s)
+        off = CL.packed(want["f32"], np.arange(c["B"]))[2]
+        if (want["f32"]["pixels"][0] is not None and any((p == -1).any() for p in want["f32"]["pixels"]) and off[1] <= c["cap"] and
+                len(CL.packed(want["c_u8"], np.arange(c["B"]))[0]) > 2 and c["cfw"] > 1):
+            return c, want
+    raise AssertionError("no such case in the slice")
+
+
+def test_cloud_checker_sensitivity():
+    """Every planted error is reported, and - RULES taken out one at a time - every rule of check_run is the only one that reports
+    some planted error: none of them is redundant."""
+    c, want = _cloud_case()
+    B = c["B"]
+    default = _cloud_output(c, want, {})
+    good = {k: _cloud_output(c, want, r) for k, r in dict(default={}, c_u8=dict(entry="c_u8"), cap=dict(capacity="short"), f32=dict(out="f32"),
+                                                         bits=dict(entry="bits", frame_pad=True)).items()}
+    runs = dict(default={}, c_u8=dict(entry="c_u8"), cap=dict(capacity="short"), f32=dict(out="f32"), bits=dict(entry="bits", frame_pad=True))
+    for k, g in good.items():
+        assert CL.check_run(c, want, runs[k], g, default) == [], k
+    g0 = good["default"]
+    off, pix = g0["offsets"], g0["pixels"]
+    fin = np.flatnonzero(np.isfinite(g0["points"]).all(1) & (np.abs(g0["points"][:, 0]) > 1e-3))
+    i = int(next(i for i in fin if i + 1 in fin and np.searchsorted(off, i, "right") == np.searchsorted(off, i + 1, "right")))   # two finite rows of one instance
+    lost = int(np.flatnonzero(pix == -1)[0])                                          # the row of a rank outside its cloud
+    plants = []                                                                       # (name, run, output, default, the one rule that sees it or None)
+
+    def plant(name, run, f, only=None, dflt=default):
+        g = copy.deepcopy(good[run])
+        d2 = f(g)
+        plants.append((name, run, g, dflt if d2 is None else d2, only))
+
+    def swap(g):
+        g["points"][[i, i + 1]] = g["points"][[i + 1, i]]; g["pixels"][[i, i + 1]] = g["pixels"][[i + 1, i]]
+
+    def drop(g):
+        n = int(np.searchsorted(off, i, "right") - 1)
+        g["points"][i:off[n + 1] - 1] = g["points"][i + 1:off[n + 1]].copy(); g["pixels"][i:off[n + 1] - 1] = g["pixels"][i + 1:off[n + 1]].copy()
+
+    def with_W(g):
+        px = g["pixels"].astype(np.int64)
+        g["pixels"][:] = np.where(px >= 0, px // c["cfw"] * c["W"] + px % c["cfw"], -1)
+
+    def ulp(g):
+        g["points"][i, 0] = np.nextafter(g["points"][i, 0], np.inf)
+
+    def both_off(g):
+        g["points"][i, 0] *= 1 + 1e-12
+        g["rows"] = [r.copy() for r in g["rows"]]
+        n = int(np.searchsorted(off, i, "right") - 1)
+        g["rows"][int(c["img"][n])][pix[i], 0] *= 1 + 1e-12
+
+    gk = good["cap"]
+    dead = np.flatnonzero(np.repeat(gk["status"] == 1, np.diff(gk["offsets"])))
+    assert len(dead) and (gk["status"] == 0).any()
+    T = int(off[-1])
+    plant("two neighbouring rows exchanged", "default", swap)
+    plant("two neighbouring points exchanged, pixels in place", "default", lambda g: g["points"].__setitem__([i, i + 1], g["points"][[i + 1, i]]))
+    plant("a row dropped and the rest shifted", "default", drop)
+    plant("an offset off by one", "default", lambda g: g["offsets"].__setitem__(2, g["offsets"][2] + 1), "offsets")
+    plant("a count off by one", "default", lambda g: g["counts"].__setitem__(1, g["counts"][1] + 1), "counts")
+    plant("a pixel index computed with W where the frame width is smaller", "c_u8", with_W, "pixels")
+    plant("one coordinate off by 1e-12 relative", "default", lambda g: g["points"].__setitem__((i, 0), g["points"][i, 0] * (1 + 1e-12)))
+    plant("one coordinate off by one ulp", "default", ulp, "rows")
+    plant("the cloud and unproject off by 1e-12 alike", "default", both_off, "oracle")
+    plant("a NaN row written as zeros", "default", lambda g: g["points"].__setitem__(lost, 0.0))
+    plant("a non-NaN row for a rank outside the cloud", "default", lambda g: g["points"].__setitem__(lost, g["points"][i]))
+    plant("pixel 0 in place of -1", "default", lambda g: g["pixels"].__setitem__(lost, 0), "pixels")
+    plant("status 0 on an instance beyond the capacity", "cap", lambda g: g["status"].__setitem__(int(np.flatnonzero(g["status"] == 1)[0]), 0), "status")
+    plant("status 1 on an instance within the capacity", "cap", lambda g: g["status"].__setitem__(int(np.flatnonzero(g["status"] == 0)[0]), 1), "status")
+    plant("a sentinel overwritten inside a status-1 range", "cap", lambda g: g["points"].__setitem__((dead[-1], 2), 1.0), "sentinel")
+    plant("a pixel sentinel overwritten inside a status-1 range", "cap", lambda g: g["pixels"].__setitem__(dead[0], 5), "sentinel")
+    plant("a write beyond offsets[-1]", "cap", lambda g: g["points"].__setitem__((T, 0), 0.0), "sentinel")
+    plant("a write at the very end of the buffers", "cap", lambda g: g["pixels"].__setitem__(T + 63, -1), "sentinel")
+    plant("a row too many", "default", lambda g: g.__setitem__("points", np.concatenate([g["points"], np.zeros((1, 3))])), "shape")
+    plant("float32 output with pixels", "f32", lambda g: g.__setitem__("pixels", pix.copy()), "shape")
+    plant("float32 output one float32 step off", "f32", lambda g: g["points"].__setitem__((i, 0), np.nextafter(g["points"][i, 0], np.float32(np.inf))))
+
+    def other_default(g):
+        d2 = copy.deepcopy(default); d2["points"][i, 0] *= 1 + 1e-6
+        return d2
+
+    plant("float32 output that is not the cast of the float64 run", "f32", other_default, "cast")
+    plant("bit planes: rows that are not the default run's", "bits", other_default, "default")
+    for name, run, g, dflt, only in plants:
+        assert CL.check_run(c, want, runs[run], g, dflt), f"planted error not reported: {name}"
+        if only is not None:
+            assert CL.check_run(c, want, runs[run], g, dflt, rules=[k for k in CL.RULES if k != only]) == [], f"{name}: reported without the rule '{only}'"
+    assert {only for *_, only in plants if only} == set(CL.RULES)
+    # every message names its rows / instances and the field
+    msg = CL.check_run(c, want, {}, plants[0][2], default)
+    assert any("instance" in m and ("pixels" in m or "points" in m) for m in msg), msg

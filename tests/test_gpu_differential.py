@@ -8,6 +8,8 @@
   annotations   fit_annotations (GPU-resident and through the host entry) and fit_annotations_all with three filters, 40 images
   hull          the convex-hull yaw of the depth + mask fit (oracle/campaigns/hull.py): every mask source, the pins hull calls ignore
                 (the same bytes as the default run), full-mask and subsample mode, 60 cases
+  clouds        the instance point clouds (oracle/campaigns/clouds.py): u8 and bit planes, float32 output, every 16-bit kind, the
+                frames form, a short capacity and the C entry in place, with and without sample_idx, 48 cases
   aux           unproject, decoders, mask statistics, filters, consumers, depth statistics, matcher, 40 cases
 A case fails with the campaign's own message, which names its seed."""
 import numpy as np
@@ -15,6 +17,7 @@ import pytest
 
 from oracle.campaigns import annotations as A
 from oracle.campaigns import aux as X
+from oracle.campaigns import clouds as CL
 from oracle.campaigns import engines as E
 from oracle.campaigns import hull as HU
 from oracle.campaigns import points as PT
@@ -128,6 +131,33 @@ def test_hull_campaign_slice(gpu, seeds):
                 fails += [f"seed {s} {r}: {m}" for m in (HU.check_pin(default, got) if default is not None else ["no default run to compare with"])]
             fails += [f"seed {s} {r}: {m}" for m in HU.check_run(c, ref, r, got, tally)]
     print("\n".join(HU.tally_lines(tally)))
+    assert not fails, _report(fails)
+
+
+@pytest.mark.parametrize("seeds", _groups(S.CLOUD_SEEDS, 6), ids=lambda v: str(v[0]))
+def test_cloud_campaign_slice(gpu, seeds):
+    """instance_points / instance_points_frames / the C entry: counts, offsets, status, pixels and every row (the unproject row of its
+    pixel) exactly, points within 1e-13 of the oracle, the runs among each other.  A call that raises ends the group's GPU work."""
+    fails = []
+    tally = CL.new_tally()
+    for s in seeds:
+        c = CL.make_case(s)
+        want = CL.oracle_case(s)
+        CL.tally_case(tally, c, want)
+        cache, default = {}, None
+        for r in CL.RUNS:
+            if not CL.applies(c, r):
+                continue
+            try:
+                got = CL.run_gpu(c, r, cache)
+            except Exception as e:   # noqa: BLE001 - whatever made the call fail is looked at before anything else runs on the device
+                print("\n".join(CL.tally_lines(tally)))
+                pytest.fail(_report(fails + [f"seed {s} {r}: call failed, nothing more was run: {e!r}"]))
+            tally["calls"] += 1
+            if not r:
+                default = got
+            fails += [f"seed {s} {r}: {m}" for m in CL.check_run(c, want, r, got, default)]
+    print("\n".join(CL.tally_lines(tally)))
     assert not fails, _report(fails)
 
 
