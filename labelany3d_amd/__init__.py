@@ -25,12 +25,12 @@ from .masks import (annotation_areas, filter_annotations, fit_annotations, fit_a
                     segmentations_to_masks)  # noqa: E402,F401
 from .masks import MaskBits, fit_instances_bits, mask_stats_bits, pack_logits_bits, pack_mask_bits, unpack_mask_bits  # noqa: E402,F401
 
-from .masks import PackedFrames, PackedFrames16, fit_instances_frames, pack_frames  # noqa: E402,F401
+from .frames import PackedFrames, PackedFrames16, fit_instances_frames, pack_frames  # noqa: E402,F401  (after .masks: masks.py ends by importing frames, which imports masks)
 from .masks import Depth16, pack_depth16, unpack_depth16  # noqa: E402,F401
 from .masks import LabelBits, fit_instances_labels, label_instances, pack_label_bits  # noqa: E402,F401
-from .masks import (PackedMasks, pack_mask_frames, pack_mask_bits_frames, fit_instances_frames_masks,  # noqa: E402,F401
-                    FrameBits, PackedLabels, fit_instances_frames_bits, fit_instances_frames_labels, frame_bits_offsets,  # noqa: E402,F401
-                    pack_label_bits_frames, pack_label_frames)
+from .frames import (PackedMasks, pack_mask_frames, pack_mask_bits_frames, fit_instances_frames_masks,  # noqa: E402,F401
+                     FrameBits, PackedLabels, fit_instances_frames_bits, fit_instances_frames_labels, frame_bits_offsets,  # noqa: E402,F401
+                     pack_label_bits_frames, pack_label_frames)
 
 from .clouds import InstancePoints, instance_points, instance_points_frames  # noqa: E402,F401
 

@@ -12,10 +12,10 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
-from .batched import (Depth16, _as_dev, _bits_stride, _d16_block, _depth16_block, _depth16_check, _dev, _fit_inputs, _record, _stream,
-                      padded_width)
-from .fitcall import depth_rows
-from .masks import FrameBits, LabelBits, MaskBits, PackedFrames, PackedFrames16, _mask_bits
+from .batched import Depth16, _as_dev, _bits_stride, _depth16_block, _depth16_check, _dev, _fit_inputs, _record, _stream
+from .fitcall import depth_rows_for_bits
+from .frames import FrameBits, _frames_depth, _on_gpu, _same_table
+from .masks import LabelBits, _mask_bits
 
 
 class InstancePoints(NamedTuple):
@@ -95,8 +95,7 @@ def instance_points(depth, masks, K, image_index=None, sample_idx=None, capacity
     if isinstance(masks, LabelBits):
         image_index = masks.image_index if image_index is None else image_index
         masks = masks.bits
-    is16 = isinstance(depth, Depth16)
-    if is16:
+    if isinstance(depth, Depth16):
         _depth16_check(depth)
     a = _lib.CloudArgs(struct_size=C.sizeof(_lib.CloudArgs))
     if isinstance(masks, tuple):
@@ -105,10 +104,7 @@ def instance_points(depth, masks, K, image_index=None, sample_idx=None, capacity
         if mb.bits.device != dev:
             raise ValueError("the bit planes live on another device")
         B, H, W, fw = int(mb.bits.shape[0]), mb.H, mb.W, mb.frame_width
-        Wd = int((depth.data if is16 else depth).shape[-1])
-        if Wd != W and (Wd != fw or padded_width(fw) != W):
-            raise ValueError(f"depth rows of {Wd} pixels match neither the stored width {W} nor the frame width {fw} of the bit planes")
-        depth, fw_send = depth_rows(depth, W, fw, dev, pad=Wd != W)
+        depth, fw_send = depth_rows_for_bits(depth, W, fw, dev)
         a.mask_bits, a.bits_plane_stride, a.frame_width = mb.bits.data_ptr(), _bits_stride(mb.bits, B, H, W), fw_send
         keep, frame = [mb.bits], "the bit-plane frame"
     else:
@@ -145,32 +141,16 @@ def instance_points_frames(frames, bits: FrameBits, K, image_index=None, sample_
     image index, frame row or plane offset breaks the contract gets count 0, status 5 and no rows - decided on the device, never an
     exception.  Other arguments and the result as ``instance_points``."""
     _cloud_args(out_dtype, capacity)
-    is16 = isinstance(frames, PackedFrames16)
-    if is16:
-        t = frames.data
-        if not isinstance(t, torch.Tensor) or t.dim() != 1:
-            raise ValueError("PackedFrames16.data must be the flat tensor of pack_frames(dtype=...)")
-        _depth16_check(Depth16(t[None], frames.scale, frames.zero_is_hole))
-    elif not isinstance(frames, PackedFrames):
-        raise ValueError("frames must be the PackedFrames / PackedFrames16 of pack_frames")
-    if not isinstance(bits, FrameBits):
-        raise ValueError("bits must be the FrameBits of pack_label_bits_frames / pack_mask_bits_frames")
-    if (bits.H, bits.W) != (frames.H, frames.W) or not np.array_equal(np.asarray(bits.table), np.asarray(frames.table_host)):
-        raise ValueError("the bit planes were laid out for another frame table than the depth: pack depth and masks of the same sizes, in the same order")
-    fdepth = frames.data if is16 else frames.depth
-    if not fdepth.is_cuda or not bits.bits.is_cuda:
-        raise ValueError("frames and bit planes must live on the GPU")
-    dev = fdepth.device
-    if bits.bits.device != dev:
-        raise ValueError("the bit planes live on another device")
+    fdepth, depth = _frames_depth(frames, "instance_points_frames")
+    _same_table(frames, bits)
+    dev = _on_gpu(fdepth, bits.bits)
     B, P = int(bits.offsets.numel()), int(frames.table.shape[0])
     H, W = max(int(frames.H), 1), max(int(frames.W), 1)
     _, k, ii, _, si, _ = _fit_inputs(None, K, bits.image_index if image_index is None else image_index, None, sample_idx, B, H, W, dev, None,
                                      planes=P, expand_K=False, check_host_index=False)
     a = _lib.CloudArgs(struct_size=C.sizeof(_lib.CloudArgs), B=B, H=H, W=W, P=P)
-    if is16:
-        blk = _d16_block(fdepth, frames.scale, frames.zero_is_hole)
-        a.depth16 = C.pointer(blk)
+    if depth.d16 is not None:
+        a.depth16 = C.pointer(depth.d16)
     else:
         a.depth = fdepth.data_ptr()
     a.frames, a.mask_bits, a.bits_offsets = frames.table.data_ptr(), bits.bits.data_ptr(), bits.offsets.data_ptr()

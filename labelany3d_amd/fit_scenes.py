@@ -42,8 +42,8 @@ import torch
 from ._lib import lib, method_code
 from .batched import Depth16, _dev, _upload_many, draw_sample_idx, refuse_depth16
 from .jsonout import SceneRecords, format_scenes
-from .masks import (PackedFrames, PackedFrames16, fit_instances_ex, fit_instances_frames, frame_table, mask_stats_poly, mask_stats_rle, pack_polygons, pack_rle,
-                    pack_rle_frames, pad_depth_rows, padded_width, area_hint_of, split_annotations)
+from .frames import PackedFrames, PackedFrames16, _table_fields, fit_instances_frames, frame_table, pack_rle_frames
+from .masks import fit_instances_ex, mask_stats_poly, mask_stats_rle, pack_polygons, pack_rle, pad_depth_rows, padded_width, area_hint_of, split_annotations
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 OUT_NAME = "3dbbox.json"
@@ -322,15 +322,15 @@ class ScenePipeline:
         with torch.cuda.stream(self.copy_stream):
             pr.h2d0 = torch.cuda.Event(enable_timing=True)
             pr.h2d0.record(self.copy_stream)
-            words = torch.as_tensor(np.ascontiguousarray(table).view(np.int32).reshape(P, 6).copy(), device=self.dev)
+            fields = _table_fields(table, sizes, self.dev)   # (the table goes up first, on the copy stream)
             if self._t16 is None:
                 depth = torch.empty((total,), dtype=torch.float32, device=self.dev)
                 depth.copy_(dpin, non_blocking=True)
-                pr.depth = PackedFrames(depth, words, table, pr.H, pr.W, sizes)
+                pr.depth = PackedFrames(depth, *fields)
             else:   # the 16-bit words go up as they are (as int16 bit patterns) and are fitted where they land
                 depth = torch.empty((total,), dtype=torch.int16, device=self.dev)
                 depth.copy_(dpin.view(torch.int16), non_blocking=True)
-                pr.depth = PackedFrames16(depth.view(tdt), words, table, pr.H, pr.W, sizes, self.depth_scale, self.depth_hole)
+                pr.depth = PackedFrames16(depth.view(tdt), *fields, self.depth_scale, self.depth_hole)
             pr.K = torch.empty((P, 9), dtype=torch.float64, device=self.dev)
             pr.K.copy_(kpin, non_blocking=True)
             pr.groups = {}

@@ -1,5 +1,5 @@
-"""The one place a depth + mask fit call of the convenience wrappers is built (``masks.fit_instances_ex`` / ``fit_instances_bits`` /
-``fit_instances_frames``): a mask source, a depth source, the shared input checks, the outputs, the ``la3d_fit_args`` block, the
+"""The one place a depth + mask fit call of the convenience wrappers is built (``masks.fit_instances_ex`` / ``fit_instances_bits``,
+``frames.fit_instances_frames`` / ``fit_instances_frames_bits``): a mask source, a depth source, the shared input checks, the outputs, the ``la3d_fit_args`` block, the
 enqueue, the stream bookkeeping.  A wrapper does its own argument checks, calls ``fit_call`` and shapes what it returns; a new
 source is one description here plus the checks that are its own."""
 from __future__ import annotations
@@ -10,7 +10,7 @@ import torch
 
 from . import _lib, options
 from .batched import (Depth16, InstanceFitter, _as_dev, _bits_stride, _bulk, _enqueue, _fit_args, _fit_inputs, _pad_rows16, _ptr, _record,
-                      _stream, pad_depth_rows)
+                      _stream, pad_depth_rows, padded_width)
 
 
 class MaskSource(NamedTuple):
@@ -76,6 +76,15 @@ def depth_rows(depth, stored: int, image: int, dev, pad: bool):
                 return _pad_rows16(depth, stored), image
             return pad_depth_rows(depth, dev)   # (the image columns as the DEPTH states them, as this route always sent them)
     return depth, (0 if stored == image else image)
+
+
+def depth_rows_for_bits(depth, stored: int, image: int, dev):
+    """``depth_rows`` for bit planes stored ``stored`` pixels wide with ``image`` image columns: depth rows as wide as the planes
+    are stored go as they are, rows as wide as the image are padded when that gives the stored width, anything else is refused."""
+    Wd = int((depth.data if isinstance(depth, Depth16) else depth).shape[-1])
+    if Wd != stored and (Wd != image or padded_width(image) != stored):
+        raise ValueError(f"depth rows of {Wd} pixels match neither the stored width {stored} nor the frame width {image} of the bit planes")
+    return depth_rows(depth, stored, image, dev, pad=Wd != stored)
 
 
 def fit_call(src: MaskSource, depth, K, dev, H, W, *, image_index, ground, sample_idx, area_hint, filter, image_size, stream, method,

@@ -18,22 +18,25 @@ instances, src/download_coconut.py:275-280) — take ``create_boolean_mask_from_
     boxes, status, aux = fit_instances_poly(depth, polys, K, ...)       # rasterised inside the fit kernel
     masks = poly_decode(polys)                                          # the reference's boolean masks, on the GPU
     keep  = keep_instances(mask_stats_poly(polys), H, from_rle=False)   # height = last row - first row + 1 (:328-335)
+
+These, bit planes (``MaskBits``), label maps (``LabelBits``) and 16-bit depth (``pack_depth16``) are the sources of ONE frame size per
+call; images of different sizes (``pack_frames``, ``fit_instances_frames*``) live in ``frames`` and are re-exported at the end.
 """
 from __future__ import annotations
 
 import ctypes as C
 import itertools
 import threading
-from typing import NamedTuple, Optional
+from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import AUX, BOX_FILTERED, REC, check, lib
-from .batched import (Depth16, InstanceFitter, _as_dev, _bits_stride, _d16_block, _depth16_block, _depth16_check, _dev, _fit_args, _ptr, _record,
+from .batched import (Depth16, InstanceFitter, _as_dev, _bits_stride, _depth16_block, _depth16_check, _dev, _fit_args, _ptr, _record,
                       _stream, _upload_many, height_rule_code, pad_depth_rows, padded_width, refuse_depth16)
-from .fitcall import FramesDepth, depth_rows, fit_call, mask_source
+from .fitcall import depth_rows, depth_rows_for_bits, fit_call, mask_source
 
 
 def rle_from_string(s) -> np.ndarray:
@@ -674,8 +677,7 @@ def fit_instances_bits(depth, bits, K, ground=None, sample_idx=None, image_index
     its rule for polygons); a bit plane does not say where it came from."""
     _lib.method_code(method)   # (the reference's error for an unknown method, before any device work)
     flags = height_rule_code(height_rule)
-    is16 = isinstance(depth, Depth16)
-    if is16:
+    if isinstance(depth, Depth16):
         _depth16_check(depth)
     mb = _mask_bits(bits)
     dev = mb.bits.device if device is None else _dev(device)
@@ -684,10 +686,7 @@ def fit_instances_bits(depth, bits, K, ground=None, sample_idx=None, image_index
     W, fw = mb.W, mb.frame_width
     if frame_width is not None and int(frame_width) != fw:
         raise ValueError(f"frame_width {frame_width} does not match the bit planes' frame width {fw}")
-    Wd = int((depth.data if is16 else depth).shape[-1])
-    if Wd != W and (Wd != fw or padded_width(fw) != W):
-        raise ValueError(f"depth rows of {Wd} pixels match neither the stored width {W} nor the frame width {fw} of the bit planes")
-    depth, fw = depth_rows(depth, W, fw, dev, pad=Wd != W)
+    depth, fw = depth_rows_for_bits(depth, W, fw, dev)
     out = fit_call(mask_source(dev, bits=(mb, flags))[0], depth, K, dev, mb.H, W, image_index=image_index, ground=ground,
                    sample_idx=sample_idx, area_hint=area_hint, filter=filter, image_size=image_size, stream=stream, method=method,
                    frame_width=fw)
@@ -933,595 +932,6 @@ def unpack_depth16(d16: Depth16, stream=None) -> torch.Tensor:
     return out if d16.data.dim() == 3 else out[0]
 
 
-FRAME_DTYPE = np.dtype([("depth_offset", "<i8"), ("H", "<i4"), ("W", "<i4"), ("frame_width", "<i4"), ("reserved", "<i4")])
-"""One row of the frame table of a frames call: ``la3d_frame`` of include/la3d.h (24 bytes)."""
-
-
-class PackedFrames(NamedTuple):
-    """Depth maps of different sizes in one buffer (``pack_frames``; C-ABI ``la3d_fit_instances_frames``): ``depth`` flat float32 -
-    plane p starts ``table_host["depth_offset"][p]`` floats in (a multiple of 4: 16-byte aligned), its rows ``padded_width(W_p)``
-    floats apart, the columns past ``W_p`` zero -; ``table`` int32 (P, 6) on the same device: the ``la3d_frame`` rows as the kernel
-    reads them; ``table_host``: the same rows as a NumPy array of ``FRAME_DTYPE``; ``H``, ``W``: the bounds of the call (largest
-    rows, largest pitch); ``sizes``: the (H, W) of every image, unpadded."""
-    depth: torch.Tensor
-    table: torch.Tensor
-    table_host: np.ndarray
-    H: int
-    W: int
-    sizes: list
-
-
-class PackedFrames16(NamedTuple):
-    """16-bit depth maps of different sizes in one buffer (``pack_frames(dtype=...)``; C-ABI ``la3d_fit_instances_frames_depth16``):
-    ``data`` flat ``torch.float16`` / ``torch.uint16`` - the layout of ``PackedFrames`` counted in 16-bit ELEMENTS: plane p starts
-    ``table_host["depth_offset"][p]`` words in (a multiple of 4: 8-byte aligned), its rows ``padded_width(W_p)`` words apart, the
-    columns past ``W_p`` zero words -; ``table`` / ``table_host`` / ``H`` / ``W`` / ``sizes`` as in ``PackedFrames``; ``scale`` /
-    ``zero_is_hole``: the value rule of uint16 planes (``Depth16``; 1.0 / ignored for float16)."""
-    data: torch.Tensor
-    table: torch.Tensor
-    table_host: np.ndarray
-    H: int
-    W: int
-    sizes: list
-    scale: float = 1.0
-    zero_is_hole: bool = True
-
-
-def frame_table(sizes) -> np.ndarray:
-    """The frame table (``FRAME_DTYPE``) of images of the given unpadded (H, W) sizes packed back to back: pitch =
-    ``padded_width(W)``, planes 16-byte aligned (every pitch is a multiple of 32 floats, so they follow each other directly)."""
-    t = np.zeros(len(sizes), FRAME_DTYPE)
-    off = 0
-    for p, (h, w) in enumerate(sizes):
-        h, w = int(h), int(w)
-        if h <= 0 or w <= 0:
-            raise ValueError(f"depth map {p} has an empty frame {(h, w)}")
-        t[p] = (off, h, padded_width(w), w, 0)
-        off += h * padded_width(w)
-    return t
-
-
-def _words16(m, p: int, dtype: str):
-    """depth map p of a 16-bit ``pack_frames`` as its int16 bit patterns (a view where the map is contiguous): the map must already
-    HAVE the 16-bit dtype - nothing is converted or rounded here"""
-    tdt = _D16_DTYPES[dtype][0]
-    ndt = np.float16 if dtype == "f16" else np.uint16
-    if isinstance(m, torch.Tensor):
-        if m.dtype != tdt:
-            raise ValueError(f"depth map {p}: pack_frames(dtype={dtype!r}) takes maps of {tdt} / numpy {np.dtype(ndt).name}, not {m.dtype}")
-        return m.contiguous().view(torch.int16)
-    a = np.asarray(m)
-    if a.dtype != ndt:
-        raise ValueError(f"depth map {p}: pack_frames(dtype={dtype!r}) takes maps of numpy {np.dtype(ndt).name} / {tdt}, not {a.dtype}")
-    return np.ascontiguousarray(a).view(np.int16)
-
-
-def pack_frames(depth_maps, device=None, pinned=None, dtype=None, scale: float = 0.001, zero_is_hole: bool = True):
-    """Depth maps of DIFFERENT sizes -> ``PackedFrames``: one flat float32 buffer on the device, each plane at its own pitch
-    (``padded_width``) and 16-byte aligned offset, the padding zero, plus the device frame table ``fit_instances_frames`` takes.
-    ``depth_maps``: a sequence of (H_p, W_p) arrays / tensors.  ``pinned``: a pinned float32 staging tensor of at least the packed size
-    (host maps only) - the upload is then asynchronous on the current stream and the caller keeps the buffer untouched until that
-    stream has passed it.  ``device="cpu"`` gives the layout on the host (no GPU needed).
-    ``dtype`` "f16" / "u16": the maps already ARE 16-bit (``np.float16`` / ``np.uint16``, ``torch.float16`` / ``torch.uint16``; any
-    other dtype: ValueError naming the map) and their words are copied as stored - nothing is converted or rounded - into one flat
-    16-bit buffer of the same layout counted in elements: a ``PackedFrames16`` (``scale`` / ``zero_is_hole``: the value rule of uint16
-    planes, see ``Depth16``; ``pinned``: a pinned staging tensor of the 16-bit dtype), fitted where it lies by ``fit_instances_frames``."""
-    dev = torch.device(device) if device is not None and torch.device(device).type == "cpu" else _dev(device)
-    maps = list(depth_maps)
-    if dtype is not None and dtype not in _D16_DTYPES:
-        raise ValueError(f"unknown dtype: {dtype!r}. Use None (float32), 'f16' or 'u16'")
-    tdt = torch.float32 if dtype is None else _D16_DTYPES[dtype][0]
-    if dtype == "u16" and not (np.isfinite(np.float32(scale)) and np.float32(scale) > 0):
-        raise ValueError(f"scale must be finite and > 0 (as float32), not {scale!r}")
-    for p, m in enumerate(maps):
-        if len(m.shape) != 2:
-            raise ValueError(f"depth map {p} must be (H, W), got {tuple(m.shape)}")
-    # the element the copies move: float32 (anything is converted), or the int16 bit pattern of a 16-bit map (nothing is)
-    wdt = torch.float32 if dtype is None else torch.int16
-    if dtype is not None:
-        maps = [_words16(m, p, dtype) for p, m in enumerate(maps)]
-    sizes = [(int(m.shape[0]), int(m.shape[1])) for m in maps]
-    table = frame_table(sizes)   # (offsets in ELEMENTS: multiples of 32, so a float32 plane is 16-byte and a 16-bit plane 8-byte aligned)
-    total = int(sum(int(r["H"]) * int(r["W"]) for r in table))
-    n = max(total, 4)
-    rows = [(int(r["depth_offset"]), int(r["H"]), int(r["W"]), int(r["frame_width"])) for r in table]
-    if any(isinstance(m, torch.Tensor) and m.is_cuda for m in maps):
-        flat = torch.zeros(n, dtype=wdt, device=dev)
-        for m, (o, h, wp, w) in zip(maps, rows):
-            flat[o:o + h * wp].view(h, wp)[:, :w].copy_(torch.as_tensor(m).to(device=dev, dtype=wdt))
-        flat = flat.view(tdt)
-    else:
-        if pinned is not None and pinned.dtype == tdt and pinned.numel() >= n:
-            host_t = pinned[:n]
-        else:
-            pinned, host_t = None, torch.empty(n, dtype=tdt)
-        host = host_t.view(wdt).numpy()
-        for m, (o, h, wp, w) in zip(maps, rows):
-            dst = host[o:o + h * wp].reshape(h, wp)
-            dst[:, :w] = m.numpy() if isinstance(m, torch.Tensor) else np.asarray(m)
-            dst[:, w:] = 0
-        host[total:] = 0
-        flat = host_t if dev.type == "cpu" else host_t.view(wdt).to(dev, non_blocking=pinned is not None).view(tdt)
-    words = np.ascontiguousarray(table).view(np.int32).reshape(len(maps), 6) if len(maps) else np.zeros((0, 6), np.int32)
-    tab = torch.as_tensor(words.copy(), device=dev)
-    bounds = (max((h for h, _ in sizes), default=0), max((wp for _, _, wp, _ in rows), default=0))
-    if dtype is None:
-        return PackedFrames(flat, tab, table, *bounds, sizes)
-    return PackedFrames16(flat, tab, table, *bounds, sizes, float(scale) if dtype == "u16" else 1.0, bool(zero_is_hole))
-
-
-def pack_rle_frames(rles):
-    """Run-length masks of images of different sizes -> ``(counts int32 (T,), offsets int64 (B+1,), sizes int64 (B, 2))``: ``pack_rle``
-    without its one-size rule; ``sizes[n]`` = the (h, w) the annotation states, or -1 where the input does not say."""
-    if isinstance(rles, tuple):
-        counts, offsets = rles[0], rles[1]
-        return counts, offsets, None
-    counts, offsets = _rle_counts([r["counts"] for r in rles])
-    sizes = np.asarray([tuple(r["size"]) for r in rles], np.int64).reshape(-1, 2)
-    return counts, offsets, sizes
-
-
-def fit_instances_frames(frames, K, rles=None, polys=None, image_index=None, ground=None, sample_idx=None, filter=None, proj: bool = False,
-                         area_hint=None, stream=None, method: str = "pca", _fitter=None):
-    """The fit for instances of images of DIFFERENT sizes in one call (C-ABI ``la3d_fit_instances_frames``): ``frames`` is what
-    ``pack_frames`` returns - a ``PackedFrames``, or a ``PackedFrames16`` (16-bit planes fitted where they lie, C-ABI
-    ``la3d_fit_instances_frames_depth16``: the records of the float32 call on the up-converted planes); instance n belongs to image ``image_index[n]`` (required), whose K is ``K[image_index[n]]`` (K: (P,3,3),
-    or (3,3) shared).  Exactly one of ``rles`` - a list of COCO RLE objects, each of its own image's size, or a ``(counts, offsets)``
-    tuple - and ``polys`` - the tuple of ``pack_polygons`` (its H, W are ignored: every instance is clipped to its own frame) - gives
-    the masks.  ``ground`` / ``sample_idx`` / ``filter`` / ``area_hint`` as in ``fit_instances_ex``; ``proj=True`` adds ``boxes2d``,
-    clamped to each instance's own frame.  An instance whose image index or frame row breaks the contract of ``la3d_frame`` comes
-    back with status 5 and a NaN record - decided on the device, never an exception.  ``method="convex_hull"`` is not offered in
-    this form (ValueError).  Returns the dict of ``fit_instances_ex``.  The size-balanced launch order of large batches runs when
-    ``area_hint`` is given."""
-    refuse_depth16(frames, "fit_instances_frames")
-    refuse_depth16(getattr(frames, "depth", None), "fit_instances_frames")
-    if _lib.method_code(method) != _lib.METHOD_PCA:   # (the reference's error for an unknown method; before any device work)
-        raise ValueError("fit_instances_frames: method='convex_hull' is not supported for frames of different sizes; group by size and use fit_instances_ex")
-    is16 = isinstance(frames, PackedFrames16)
-    if is16:
-        t = frames.data   # (dtype, scale: the argument errors of a Depth16, before any device work)
-        if not isinstance(t, torch.Tensor) or t.dim() != 1:
-            raise ValueError("PackedFrames16.data must be the flat tensor of pack_frames(dtype=...)")
-        _depth16_check(Depth16(t[None], frames.scale, frames.zero_is_hole))
-    elif not isinstance(frames, PackedFrames):
-        raise ValueError("frames must be the PackedFrames of pack_frames")
-    if (rles is not None) + (polys is not None) != 1:
-        raise ValueError("give exactly one of rles / polys")
-    if image_index is None:
-        raise ValueError("image_index is required: instance n belongs to frame image_index[n]")
-    fdepth = frames.data if is16 else frames.depth
-    if not fdepth.is_cuda:
-        raise ValueError("frames must live on the GPU (pack_frames with a GPU device)")
-    dev = fdepth.device
-    if rles is not None:
-        counts, offsets, sizes = pack_rle_frames(rles)
-        if sizes is not None and not (isinstance(image_index, torch.Tensor) and image_index.is_cuda):
-            ii_h = np.asarray(image_index.numpy() if isinstance(image_index, torch.Tensor) else image_index).reshape(-1)
-            ok = (ii_h >= 0) & (ii_h < int(frames.table.shape[0]))
-            if len(ii_h) == len(sizes) and ok.any():
-                want = np.asarray(frames.sizes, np.int64).reshape(-1, 2)[ii_h[ok]]
-                if (sizes[ok] != want).any():
-                    raise ValueError("an RLE annotation's size differs from the size of its image")
-        given = dict(rles=(counts, offsets, None, None))
-    else:
-        given = dict(polys=(polys[0], polys[1], polys[2], None, None))   # (their H, W are ignored: every instance has its own frame)
-    src, ground, ii, sample_idx, area_hint = mask_source(dev, small=(ground, image_index, sample_idx, area_hint), **given)
-    depth = FramesDepth(fdepth, frames.table, _d16_block(fdepth, frames.scale, frames.zero_is_hole) if is16 else None)
-    # (_fitter: buffers a caller keeps between calls - fit_scenes -, sized for at least this call's B and bounds)
-    return fit_call(src, depth, K, dev, frames.H, frames.W, image_index=ii, ground=ground, sample_idx=sample_idx, area_hint=area_hint,
-                    filter=filter, image_size=(1, 1) if proj else None, stream=stream, method=method, fitter=_fitter)
-
-
-# ---- label maps and bit planes of images of different sizes (include/la3d.h "images of different sizes in one call") ----------------
-class PackedLabels(NamedTuple):
-    """Label maps of different sizes in one buffer (``pack_label_frames``; C-ABI ``la3d_pack_label_bits_frames``): ``data`` flat -
-    ``torch.uint8`` / ``int16`` (the bit patterns of uint16 labels) / ``int32``, or ``uint8`` with 3 bytes per pixel for RGB maps -
-    in the layout of ``PackedFrames`` counted in ELEMENTS (pixels for RGB): map p starts ``table_host["depth_offset"][p]`` elements
-    in, its rows ``padded_width(W_p)`` elements apart, the columns past ``W_p`` zero; ``table`` / ``table_host`` / ``H`` / ``W`` /
-    ``sizes`` as in ``PackedFrames`` - the table IS the one ``pack_frames`` gives for depth maps of the same sizes; ``code``: the
-    element (``_lib.LABEL_*``)."""
-    data: torch.Tensor
-    table: torch.Tensor
-    table_host: np.ndarray
-    H: int
-    W: int
-    sizes: list
-    code: int
-
-
-class FrameBits(NamedTuple):
-    """Bit planes of instances of images of different sizes (``pack_label_bits_frames``; C-ABI ``la3d_fit_instances_frames_bits``):
-    ``bits`` flat int32 on the GPU; ``offsets`` int64 (B,) on the GPU - the plane of row b starts ``offsets[b]`` words in (a multiple of
-    4) and holds the ``H_p * padded_width(W_p) / 32`` words of its image's frame -; ``image_index`` int32 (B,) and ``area`` int32 (B,)
-    on the GPU as in ``LabelBits``; ``table``: the HOST frame table (``FRAME_DTYPE``) the planes were laid out for - what
-    ``fit_instances_frames_bits`` compares with the table of its depth, without touching the device -; ``H``, ``W``: its bounds."""
-    bits: torch.Tensor
-    offsets: torch.Tensor
-    image_index: torch.Tensor
-    area: torch.Tensor
-    table: np.ndarray
-    H: int
-    W: int
-
-
-_LABEL_STORE = {_lib.LABEL_U8: torch.uint8, _lib.LABEL_U16: torch.int16, _lib.LABEL_I32: torch.int32, _lib.LABEL_RGB8: torch.uint8}
-
-
-def pack_label_frames(label_maps, rgb: bool = False, device=None, pinned=None) -> PackedLabels:
-    """Label maps of DIFFERENT sizes -> ``PackedLabels``: one flat buffer in the layout ``pack_frames`` gives depth maps of the same
-    sizes (``frame_table(sizes)``: pitch ``padded_width(W)``, the padding zero), so ONE table serves ``pack_label_bits_frames`` and
-    the fit.  ``label_maps``: a sequence of (H_p, W_p) arrays / tensors of ONE dtype - uint8, uint16, int16 (read as uint16) or int32 -
-    or, with ``rgb=True``, of (H_p, W_p, 3) uint8 maps (a COCO panoptic PNG as it decodes).  ``pinned``: a pinned staging tensor of
-    the stored dtype and at least the packed size (host maps only; the upload is then asynchronous on the current stream).
-    ``device="cpu"`` gives the layout on the host (no GPU needed)."""
-    dev = torch.device(device) if device is not None and torch.device(device).type == "cpu" else _dev(device)
-    maps = list(label_maps)
-    code, c = None, 3 if rgb else 1
-    for p, m in enumerate(maps):
-        one = _LABEL_TORCH.get(m.dtype) if isinstance(m, torch.Tensor) else _LABEL_NUMPY.get(np.asarray(m).dtype)
-        if one is None:
-            raise ValueError(f"label map {p} must be uint8, uint16, int16 (read as uint16) or int32, not {getattr(m, 'dtype', type(m).__name__)}")
-        if rgb and (one != _lib.LABEL_U8 or len(m.shape) != 3 or m.shape[-1] != 3):
-            raise ValueError(f"label map {p}: rgb=True takes (H, W, 3) uint8 maps, not {tuple(m.shape)} {m.dtype}")
-        if not rgb and len(m.shape) != 2:
-            raise ValueError(f"label map {p} must be (H, W), got {tuple(m.shape)}")
-        if code is not None and one != code:
-            raise ValueError(f"label map {p} has another dtype than label map 0: pack maps of one dtype")
-        code = one
-    code = _lib.LABEL_RGB8 if rgb else (code if code is not None else _lib.LABEL_U8)
-    tdt = _LABEL_STORE[code]
-
-    def words(m):   # the map in the stored dtype (uint16 as its int16 bit pattern)
-        if isinstance(m, torch.Tensor):
-            return m.view(torch.int16) if m.dtype == torch.uint16 else m
-        a = np.asarray(m)
-        return a.view(np.int16) if a.dtype == np.uint16 else a
-
-    maps = [words(m) for m in maps]
-    sizes = [(int(m.shape[0]), int(m.shape[1])) for m in maps]
-    table = frame_table(sizes)
-    rows = [(int(r["depth_offset"]), int(r["H"]), int(r["W"]), int(r["frame_width"])) for r in table]
-    total = sum(h * wp for _, h, wp, _ in rows)
-    n = max(total, 16) * c
-    if any(isinstance(m, torch.Tensor) and m.is_cuda for m in maps):
-        flat = torch.zeros(n, dtype=tdt, device=dev)
-        for m, (o, h, wp, w) in zip(maps, rows):
-            flat[o * c:(o + h * wp) * c].view(h, wp * c)[:, :w * c].copy_(torch.as_tensor(m).to(device=dev).reshape(h, w * c))
-    else:
-        if pinned is not None and pinned.dtype == tdt and pinned.numel() >= n:
-            host_t = pinned[:n]
-        else:
-            pinned, host_t = None, torch.empty(n, dtype=tdt)
-        host = host_t.numpy()
-        host[total * c:] = 0
-        for m, (o, h, wp, w) in zip(maps, rows):
-            dst = host[o * c:(o + h * wp) * c].reshape(h, wp * c)
-            dst[:, :w * c] = (m.numpy() if isinstance(m, torch.Tensor) else np.asarray(m)).reshape(h, w * c)
-            dst[:, w * c:] = 0
-        flat = host_t if dev.type == "cpu" else host_t.to(dev, non_blocking=pinned is not None)
-    tab_words = np.ascontiguousarray(table).view(np.int32).reshape(len(maps), 6) if len(maps) else np.zeros((0, 6), np.int32)
-    tab = torch.as_tensor(tab_words.copy(), device=dev)
-    bounds = (max((h for h, _ in sizes), default=0), max((wp for _, _, wp, _ in rows), default=0))
-    return PackedLabels(flat, tab, table, *bounds, sizes, code)
-
-
-def frame_bits_offsets(table, image_index):
-    """The layout ``pack_label_bits_frames`` gives the planes of host ids: -> (offsets int64 (B,), total words).  Row b gets the
-    ``H * W / 32`` words of the frame row ``table[image_index[b]]`` (W: the pitch, a multiple of 32); the planes follow each other
-    in row order, each start rounded up to a multiple of 4 words (16 bytes)."""
-    ii = np.asarray(image_index, np.int64).reshape(-1)
-    words = (table["H"].astype(np.int64) * table["W"].astype(np.int64) // 32)[ii] if len(ii) else np.zeros(0, np.int64)
-    step = (words + 3) // 4 * 4
-    offsets = np.zeros(len(ii), np.int64)
-    np.cumsum(step[:-1], out=offsets[1:])
-    return offsets, int(step.sum())
-
-
-def pack_label_bits_frames(labels: PackedLabels, ids, stream=None, out=None) -> FrameBits:
-    """``pack_label_bits`` for label maps of different sizes (C-ABI ``la3d_pack_label_bits_frames``): one launch reads every map once
-    and writes, per (image, id) row, the bit plane ``labels[image] == id`` of the image's OWN frame - ``H_p * padded_width(W_p) / 32``
-    words, the bits of the padding columns zero whatever id is asked (id 0 of a zero-padded map marks image pixels only).
-    ``labels``: a resident ``PackedLabels``; ``ids`` as in ``pack_label_bits``.  Host ids: the planes follow each other, each start
-    rounded up to 4 words (``frame_bits_offsets``), and offsets, ids and image indices go up in ONE copy.  Device ids: no
-    synchronisation - the sizes of the rows are then unknown here, so the planes lie a uniform stride apart, the words of the bounds'
-    frame rounded up to 4.  ``out``: a flat int32 device tensor of at least that many words to fill (only the words of each plane are
-    written).  Returns ``FrameBits``; an id that is absent or outside the dtype's range gives an all-zero plane of area 0."""
-    if not isinstance(labels, PackedLabels):
-        raise ValueError("labels must be the PackedLabels of pack_label_frames")
-    P = len(labels.sizes)
-    lab, off, ii, B = _label_rows(ids, P)
-    if not labels.data.is_cuda:
-        raise ValueError("the label maps must live on the GPU (pack_label_frames with a GPU device)")
-    dev = labels.data.device
-    with torch.cuda.device(dev):
-        if ii is not None:
-            offs_h, total = frame_bits_offsets(labels.table_host, ii)
-            lab, off, ii, offs = _upload_many([(lab, torch.int32), (off, torch.int32), (ii, torch.int32), (offs_h, torch.int64)], dev)
-        else:
-            lab, off = _as_dev(lab, torch.int32, dev), _as_dev(off, torch.int32, dev)
-            ii = torch.searchsorted(off[1:].contiguous(), torch.arange(B, dtype=torch.int32, device=dev), right=True).to(torch.int32)
-            stride = (labels.H * labels.W // 32 + 3) // 4 * 4
-            offs, total = torch.arange(B, dtype=torch.int64, device=dev) * stride, B * stride
-        if out is None:
-            o = torch.empty(max(total, 4), dtype=torch.int32, device=dev)
-        else:
-            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int32 and out.dim() == 1 and out.is_contiguous()
-                    and out.numel() >= total and out.data_ptr() % 16 == 0):
-                raise ValueError(f"out must be a flat, 16-byte aligned int32 device tensor of at least {total} words")
-            o = out
-        area = torch.empty(B, dtype=torch.int32, device=dev)
-        check(lib.la3d_pack_label_bits_frames(_ptr(labels.data), labels.code, _ptr(labels.table), P, labels.H, labels.W, _ptr(off), _ptr(lab), B,
-                                              _ptr(o), _ptr(offs), _ptr(area), _stream(stream)), "la3d_pack_label_bits_frames")
-    _record(stream, labels.data, labels.table, lab, off, ii, offs, o, area)
-    return FrameBits(o, offs, ii, area, labels.table_host, labels.H, labels.W)
-
-
-def fit_instances_frames_bits(frames, bits: FrameBits, K, image_index=None, ground=None, sample_idx=None, filter=None, proj: bool = False,
-                              area_hint=None, height_rule: str = "rows", stream=None, method: str = "pca", _fitter=None):
-    """``fit_instances_frames`` with the masks given as bit planes, one per instance, each of its own image's frame (C-ABI
-    ``la3d_fit_instances_frames_bits``): what ``pack_label_bits_frames`` makes of the label maps of a panoptic dataset, or
-    ``pack_mask_bits_frames`` of the per-image mask / logit stacks of an instance-segmentation network.  ``frames``: a
-    ``PackedFrames`` or ``PackedFrames16`` laid out by the SAME frame table as the planes (``bits.table``; a mismatch is a ValueError
-    before any device work); ``image_index`` defaults to ``bits.image_index``; ``ground`` / ``sample_idx`` / ``filter`` / ``proj`` /
-    ``area_hint`` as in ``fit_instances_frames``, ``height_rule`` as in ``fit_instances_bits``.  An instance whose image index, frame
-    row or plane offset breaks the contract comes back with status 5 and a NaN record - decided on the device, never an exception.
-    ``method="convex_hull"`` is not offered for frames of different sizes (ValueError).  Returns the dict of ``fit_instances_frames``."""
-    if _lib.method_code(method) != _lib.METHOD_PCA:   # (the reference's error for an unknown method; before any device work)
-        raise ValueError("fit_instances_frames_bits: method='convex_hull' is not supported for frames of different sizes; group by size and use fit_instances_bits")
-    flags = height_rule_code(height_rule)
-    refuse_depth16(frames, "fit_instances_frames_bits")
-    refuse_depth16(getattr(frames, "depth", None), "fit_instances_frames_bits")
-    is16 = isinstance(frames, PackedFrames16)
-    if is16:
-        t = frames.data
-        if not isinstance(t, torch.Tensor) or t.dim() != 1:
-            raise ValueError("PackedFrames16.data must be the flat tensor of pack_frames(dtype=...)")
-        _depth16_check(Depth16(t[None], frames.scale, frames.zero_is_hole))
-    elif not isinstance(frames, PackedFrames):
-        raise ValueError("frames must be the PackedFrames of pack_frames")
-    if not isinstance(bits, FrameBits):
-        raise ValueError("bits must be the FrameBits of pack_label_bits_frames")
-    if (bits.H, bits.W) != (frames.H, frames.W) or not np.array_equal(np.asarray(bits.table), np.asarray(frames.table_host)):
-        raise ValueError("the bit planes were laid out for another frame table than the depth: pack depth and label maps of the same sizes, in the same order")
-    fdepth = frames.data if is16 else frames.depth
-    if not fdepth.is_cuda or not bits.bits.is_cuda:
-        raise ValueError("frames and bit planes must live on the GPU")
-    dev = fdepth.device
-    if bits.bits.device != dev:
-        raise ValueError("the bit planes live on another device")
-    src, ground, ii, sample_idx, area_hint = mask_source(dev, frame_bits=(bits, flags), small=(
-        ground, bits.image_index if image_index is None else image_index, sample_idx, area_hint))
-    depth = FramesDepth(fdepth, frames.table, _d16_block(fdepth, frames.scale, frames.zero_is_hole) if is16 else None)
-    return fit_call(src, depth, K, dev, frames.H, frames.W, image_index=ii, ground=ground, sample_idx=sample_idx, area_hint=area_hint,
-                    filter=filter, image_size=(1, 1) if proj else None, stream=stream, method=method, fitter=_fitter)
-
-
-def fit_instances_frames_labels(frames, label_maps, ids, K, image_index=None, ground=None, sample_idx=None, filter=None, proj: bool = False,
-                                height_rule: str = "rows", stream=None, method: str = "pca", rgb: bool = False):
-    """The depth + mask fit of every listed instance of label maps of DIFFERENT sizes in one call: ``pack_label_frames`` (skipped for a
-    ``PackedLabels``), ``pack_label_bits_frames`` (one pass over the labels), then ``fit_instances_frames_bits`` with the rows'
-    ``image_index`` and their exact areas as ``area_hint``.  ``frames``: the ``PackedFrames`` / ``PackedFrames16`` of the depth maps of
-    the same images in the same order; ``label_maps`` / ``rgb`` as in ``pack_label_frames``; ``ids`` as in ``pack_label_bits``; the
-    other arguments as in ``fit_instances_frames_bits``, per (image, id) row in ``ids`` order.  Returns its dict plus ``"bits"``: the
-    ``FrameBits``.  With resident ``PackedLabels`` and device ids nothing synchronises and the call can be captured into a graph."""
-    if _lib.method_code(method) != _lib.METHOD_PCA:
-        raise ValueError("fit_instances_frames_labels: method='convex_hull' is not supported for frames of different sizes; group by size and use fit_instances_labels")
-    height_rule_code(height_rule)
-    fdepth = getattr(frames, "data", None) if isinstance(frames, PackedFrames16) else getattr(frames, "depth", None)
-    pl = label_maps if isinstance(label_maps, PackedLabels) else pack_label_frames(label_maps, rgb=rgb, device=getattr(fdepth, "device", None))
-    fb = pack_label_bits_frames(pl, ids, stream=stream)
-    out = fit_instances_frames_bits(frames, fb, K, image_index=image_index, ground=ground, sample_idx=sample_idx, filter=filter, proj=proj,
-                                    area_hint=fb.area, height_rule=height_rule, stream=stream, method=method)
-    out["bits"] = fb
-    return out
-
-
-# ---- network masks and logits of images of different sizes (include/la3d.h: la3d_pack_mask_bits_frames / la3d_pack_logits_bits_frames) --
-MASKS_U8 = -1
-"""``PackedMasks.kind`` of uint8 / boolean masks; logits carry their ``_lib.DTYPE_*`` code."""
-_MASK_TORCH = {torch.bool: MASKS_U8, torch.uint8: MASKS_U8, **_LOGIT_DTYPES}
-_MASK_NUMPY = {np.dtype(np.bool_): MASKS_U8, np.dtype(np.uint8): MASKS_U8, np.dtype(np.float32): _lib.DTYPE_F32, np.dtype(np.float16): _lib.DTYPE_F16}
-_MASK_STORE = {MASKS_U8: torch.uint8, _lib.DTYPE_F32: torch.float32, _lib.DTYPE_F16: torch.float16, _lib.DTYPE_BF16: torch.bfloat16}
-
-
-class PackedMasks(NamedTuple):
-    """Per-image stacks of masks or logits of different sizes behind one base pointer (``pack_mask_frames``; C-ABI
-    ``la3d_pack_mask_bits_frames`` / ``la3d_pack_logits_bits_frames``): ``data`` flat ``torch.uint8`` / ``float32`` / ``float16`` /
-    ``bfloat16`` - the plane of row n starts ``offsets[n]`` ELEMENTS (int64 (B,)) behind ``data``'s first element and has the
-    ``(H_p, W_p)`` of image ``image_index[n]`` (int32 (B,)), its rows ``pitch[n]`` elements apart (int32 (B,); None: ``W_p`` apart -
-    dense planes) -; ``table`` / ``table_host`` / ``H`` / ``W`` / ``sizes`` as in ``PackedFrames`` - the table IS the one
-    ``pack_frames`` gives depth maps of the same sizes; ``kind``: ``MASKS_U8`` or the logits' ``_lib.DTYPE_*`` code;
-    ``bits_offsets`` int64 (B,) on the device of ``data`` / ``bits_words``: the layout ``frame_bits_offsets`` gives the bit planes of
-    these rows (resident, so that ``pack_mask_bits_frames`` uploads nothing; None / 0: computed there); ``sources``: the tensors
-    ``data`` aliases (a zero-copy pack), kept alive with the result."""
-    data: torch.Tensor
-    offsets: torch.Tensor
-    pitch: Optional[torch.Tensor]
-    image_index: torch.Tensor
-    table: torch.Tensor
-    table_host: np.ndarray
-    H: int
-    W: int
-    sizes: list
-    kind: int
-    bits_offsets: Optional[torch.Tensor] = None
-    bits_words: int = 0
-    sources: tuple = ()
-
-
-def _mask_stacks(stacks):
-    """the argument errors of per-image mask stacks that need no device -> (stacks, kind, sizes, counts)"""
-    stacks = list(stacks)
-    kind = None
-    for p, m in enumerate(stacks):
-        dt = m.dtype if isinstance(m, torch.Tensor) else np.asarray(m).dtype
-        one = _MASK_TORCH.get(dt) if isinstance(m, torch.Tensor) else _MASK_NUMPY.get(dt)
-        if one is None:
-            raise ValueError(f"mask stack {p} (image {p}) must be bool, uint8, float32, float16 or bfloat16, not {dt}")
-        if len(m.shape) != 3:
-            raise ValueError(f"mask stack {p} (image {p}) must be (N, H, W), got {tuple(m.shape)}")
-        if kind is not None and one != kind:
-            raise ValueError(f"mask stack {p} (image {p}) has another dtype than mask stack 0: pack stacks of one dtype")
-        kind = one
-        if int(m.shape[1]) <= 0 or int(m.shape[2]) <= 0:
-            raise ValueError(f"mask stack {p} (image {p}) has an empty frame {(int(m.shape[1]), int(m.shape[2]))}")
-    sizes = [(int(m.shape[1]), int(m.shape[2])) for m in stacks]
-    counts = [int(m.shape[0]) for m in stacks]
-    return stacks, (MASKS_U8 if kind is None else kind), sizes, counts
-
-
-def _mask_in_place(m, dev) -> bool:
-    """a device stack the packer can read where it lies: adjacent pixels, rows at least a frame's width apart"""
-    if not (isinstance(m, torch.Tensor) and m.is_cuda and m.device == dev):
-        return False
-    n, h, w = m.shape
-    return (w == 1 or m.stride(2) == 1) and (h == 1 or m.stride(1) >= w) and m.stride(1) < 2 ** 31
-
-
-def pack_mask_frames(stacks, device=None, pinned=None) -> PackedMasks:
-    """The outputs of an instance-segmentation network for images of DIFFERENT sizes -> ``PackedMasks``.  ``stacks``: a sequence over
-    IMAGES of (N_p, H_p, W_p) arrays / tensors (N_p may be 0), all of ONE dtype out of bool / uint8 (masks: non-zero = inside) and
-    float32 / float16 / bfloat16 (logits, thresholded by ``pack_mask_bits_frames``); row n of the result is the n-th plane in image
-    order.  The table is ``frame_table(sizes)`` - the one ``pack_frames`` gives depth maps of the same sizes, so ONE table serves the
-    packer and the fit.
-    Host stacks are laid back to back, dense - no padding of the rows -, into one buffer and uploaded in one copy (``pinned``: a pinned
-    staging tensor of the stored dtype and at least the packed size; the upload is then asynchronous on the current stream).
-    DEVICE stacks whose planes have adjacent pixels (``stride(2) == 1``, ``stride(1) >= W_p``) are NOT copied: ``data`` is a flat view
-    based at the lowest ``data_ptr()`` among them, ``offsets`` the element distances from there and ``pitch`` given where any
-    ``stride(1) != W_p`` - a network's outputs read where they lie, the top-left crop of a padded canvas included; the result keeps
-    the tensors alive (``sources``).  Anything else is made dense first.  ``device="cpu"`` gives the dense layout on the host (no GPU
-    needed).  ValueError, naming the image: mixed dtypes, a stack that is not 3-D, an empty frame."""
-    stacks, kind, sizes, counts = _mask_stacks(stacks)
-    dev = torch.device(device) if device is not None and torch.device(device).type == "cpu" else _dev(device)
-    tdt = _MASK_STORE[kind]
-    es = torch.empty(0, dtype=tdt).element_size()
-    table = frame_table(sizes)
-    P, B = len(stacks), sum(counts)
-    ii = np.repeat(np.arange(P, dtype=np.int32), counts)
-    pitch, sources = None, ()
-    live = [m for m, c in zip(stacks, counts) if c]
-
-    def stored(m):   # the stack in the stored dtype (bool as its bytes)
-        if isinstance(m, torch.Tensor):
-            return m.view(torch.uint8) if m.dtype == torch.bool else m
-        a = np.asarray(m)
-        return a.view(np.uint8) if a.dtype == np.bool_ else a
-
-    if dev.type == "cuda" and live and all(_mask_in_place(m, dev) for m in live):
-        live = [stored(m) for m in live]
-        low = min(live, key=lambda m: m.data_ptr())
-        base = low.data_ptr()
-        data = low.as_strided((low.untyped_storage().nbytes() // es - low.storage_offset(),), (1,))
-        offs, pit = [], []
-        for m, c, (h, w) in zip(stacks, counts, sizes):
-            if c:
-                first = (m.data_ptr() - base) // es
-                offs.append(first + np.arange(c, dtype=np.int64) * (m.stride(0) if c > 1 else 0))
-                pit.append(np.full(c, m.stride(1) if h > 1 else w, np.int32))
-        offsets = np.concatenate(offs)
-        pit = np.concatenate(pit)
-        if (pit != np.asarray(sizes, np.int64).reshape(-1, 2)[ii, 1]).any():
-            pitch = pit
-        sources = tuple(live)
-    else:
-        words = np.asarray([h * w for h, w in sizes], np.int64)[ii] if B else np.zeros(0, np.int64)
-        offsets = np.zeros(B, np.int64)
-        np.cumsum(words[:-1], out=offsets[1:])
-        total = int(words.sum())
-        n = max(total, 16)
-        starts = np.concatenate([[0], np.cumsum([c * h * w for c, (h, w) in zip(counts, sizes)])]).astype(np.int64)
-        if any(isinstance(m, torch.Tensor) and m.is_cuda for m in stacks):
-            data = torch.zeros(n, dtype=tdt, device=dev)
-            for m, o, c, (h, w) in zip(stacks, starts, counts, sizes):
-                if c:
-                    data[o:o + c * h * w].view(c, h, w).copy_(torch.as_tensor(stored(m)).to(device=dev))
-        else:
-            if pinned is not None and pinned.dtype == tdt and pinned.numel() >= n:
-                host_t = pinned[:n]
-            else:
-                pinned, host_t = None, torch.empty(n, dtype=tdt)
-            host_t[total:] = 0
-            for m, o, c, (h, w) in zip(stacks, starts, counts, sizes):
-                if c:
-                    host_t[o:o + c * h * w].view(c, h, w).copy_(torch.as_tensor(stored(m)))
-            data = host_t if dev.type == "cpu" else host_t.to(dev, non_blocking=pinned is not None)
-    tab_words = np.ascontiguousarray(table).view(np.int32).reshape(P, 6) if P else np.zeros((0, 6), np.int32)
-    boffs, bwords = frame_bits_offsets(table, ii)
-    small = [(offsets, torch.int64), (boffs, torch.int64), (ii, torch.int32), (tab_words.copy(), torch.int32), (pitch, torch.int32)]
-    if dev.type == "cpu":
-        offs_t, boffs_t, ii_t, tab, pitch_t = [None if a is None else torch.as_tensor(np.ascontiguousarray(a)) for a, _ in small]
-    else:
-        with torch.cuda.device(dev):
-            offs_t, boffs_t, ii_t, tab, pitch_t = _upload_many(small, dev)
-    bounds = (max((h for h, _ in sizes), default=0), max((padded_width(w) for _, w in sizes), default=0))
-    return PackedMasks(data, offs_t, pitch_t, ii_t, tab, table, *bounds, sizes, kind, boffs_t, bwords, sources)
-
-
-def pack_mask_bits_frames(masks, threshold: float = 0.0, stream=None, out=None) -> FrameBits:
-    """``pack_mask_bits`` / ``pack_logits_bits`` for the stacks of images of different sizes (C-ABI ``la3d_pack_mask_bits_frames`` /
-    ``la3d_pack_logits_bits_frames``): ONE launch reads every plane once, where it lies, and writes per row the bit plane of its
-    image's OWN frame - ``H_p * padded_width(W_p) / 32`` words, the bits of the padding columns zero - laid out by
-    ``frame_bits_offsets(table_host, image_index)``.  ``masks``: a ``PackedMasks``, or a sequence that goes through
-    ``pack_mask_frames``; ``threshold``: logits only (bit = x > threshold in float32; NaN gives 0); ``out``: as in
-    ``pack_label_bits_frames``.  With a resident ``PackedMasks`` nothing is uploaded and nothing synchronises.  Returns ``FrameBits``."""
-    pm = masks if isinstance(masks, PackedMasks) else pack_mask_frames(masks)
-    if pm.kind not in _MASK_STORE or pm.data.dtype != _MASK_STORE[pm.kind]:
-        raise ValueError(f"PackedMasks.kind {pm.kind!r} does not name the dtype of its data ({pm.data.dtype})")
-    if not pm.data.is_cuda:
-        raise ValueError("the masks must live on the GPU (pack_mask_frames with a GPU device)")
-    dev = pm.data.device
-    P, B = len(pm.sizes), int(pm.offsets.numel())
-    with torch.cuda.device(dev):
-        if pm.bits_offsets is None:
-            offs_h, total = frame_bits_offsets(pm.table_host, pm.image_index.cpu().numpy())
-            offs = _as_dev(offs_h, torch.int64, dev)
-        else:
-            offs, total = pm.bits_offsets, int(pm.bits_words)
-        if out is None:
-            o = torch.empty(max(total, 4), dtype=torch.int32, device=dev)
-        else:
-            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int32 and out.dim() == 1 and out.is_contiguous()
-                    and out.numel() >= total and out.data_ptr() % 16 == 0):
-                raise ValueError(f"out must be a flat, 16-byte aligned int32 device tensor of at least {total} words")
-            o = out
-        area = torch.empty(B, dtype=torch.int32, device=dev)
-        tail = (_ptr(pm.table), P, pm.H, pm.W, _ptr(pm.image_index), _ptr(pm.offsets), _ptr(pm.pitch), B, _ptr(o), _ptr(offs), _ptr(area),
-                _stream(stream))
-        if pm.kind == MASKS_U8:
-            check(lib.la3d_pack_mask_bits_frames(_ptr(pm.data), *tail), "la3d_pack_mask_bits_frames")
-        else:
-            check(lib.la3d_pack_logits_bits_frames(_ptr(pm.data), pm.kind, float(threshold), *tail), "la3d_pack_logits_bits_frames")
-    _record(stream, pm.data, pm.table, pm.image_index, pm.offsets, pm.pitch, offs, o, area, *pm.sources)
-    return FrameBits(o, offs, pm.image_index, area, pm.table_host, pm.H, pm.W)
-
-
-def fit_instances_frames_masks(frames, masks, K, threshold: float = 0.0, image_index=None, ground=None, sample_idx=None, filter=None,
-                               proj: bool = False, height_rule: str = "rows", stream=None, method: str = "pca"):
-    """The depth + mask fit of the per-image mask / logit stacks of an instance-segmentation network, images of DIFFERENT sizes, in
-    one call: ``pack_mask_frames`` (skipped for a ``PackedMasks``), ``pack_mask_bits_frames`` (one launch over the planes where they
-    lie), then ``fit_instances_frames_bits`` with the rows' ``image_index`` and their exact areas as ``area_hint``.  ``frames``: the
-    ``PackedFrames`` / ``PackedFrames16`` of the depth maps of the same images in the same order (another ``(H_p, W_p)`` than the
-    masks': ValueError before any device work); ``threshold``: logits only; the other arguments as in ``fit_instances_frames_bits``,
-    per plane in image order.  Returns its dict plus ``"bits"``: the ``FrameBits``.  With a resident ``PackedMasks`` nothing
-    synchronises and the call can be captured into a graph."""
-    if _lib.method_code(method) != _lib.METHOD_PCA:
-        raise ValueError("fit_instances_frames_masks: method='convex_hull' is not supported for frames of different sizes; group by size and use fit_instances_bits")
-    height_rule_code(height_rule)
-    if isinstance(masks, PackedMasks):
-        sizes = masks.sizes
-    else:
-        masks, _, sizes, _ = _mask_stacks(masks)
-    if [tuple(s) for s in sizes] != [tuple(s) for s in getattr(frames, "sizes", ())]:
-        raise ValueError("the masks have another (H, W) per image than the depth: give one stack per depth map, each of its image's size, in the same order")
-    fdepth = getattr(frames, "data", None) if isinstance(frames, PackedFrames16) else getattr(frames, "depth", None)
-    pm = masks if isinstance(masks, PackedMasks) else pack_mask_frames(masks, device=getattr(fdepth, "device", None))
-    fb = pack_mask_bits_frames(pm, threshold=threshold, stream=stream)
-    out = fit_instances_frames_bits(frames, fb, K, image_index=image_index, ground=ground, sample_idx=sample_idx, filter=filter, proj=proj,
-                                    area_hint=fb.area, height_rule=height_rule, stream=stream, method=method)
-    out["bits"] = fb
-    return out
-
-
 def masked_ratio_median(depth_map, depth_render, mask, render_mask=None, image_index=None, stream=None):
     """Per instance ``np.median(depth_map[overlap] / depth_render[overlap])`` with ``overlap = mask & render_mask``
     — the scale estimate of the reference's align_to_depth_match (src/util.py:476-486), exact (radix select on
@@ -1545,3 +955,9 @@ def masked_ratio_median(depth_map, depth_render, mask, render_mask=None, image_i
         check(lib.la3d_masked_ratio_median(_ptr(d), H * W if d.shape[0] > 1 else 0, _ptr(ii), _ptr(r), _ptr(m), _ptr(rm), B, H, W,
                                            _ptr(med), _ptr(cnt), _stream(stream)), "la3d_masked_ratio_median")
     return med, cnt
+
+
+# the mixed-size ("frames") layer: its public names stay importable from here (last on purpose: frames imports from this module)
+from .frames import (FRAME_DTYPE, MASKS_U8, FrameBits, PackedFrames, PackedFrames16, PackedLabels, PackedMasks, fit_instances_frames,  # noqa: E402,F401
+                     fit_instances_frames_bits, fit_instances_frames_labels, fit_instances_frames_masks, frame_bits_offsets, frame_table,
+                     pack_frames, pack_label_bits_frames, pack_label_frames, pack_mask_bits_frames, pack_mask_frames, pack_rle_frames)
