@@ -1,20 +1,20 @@
 """The committed slices of the differential campaigns that tests/test_gpu_differential.py runs on every GPU test run.
 
 The seeds were picked once, by scanning the campaigns' make_case on the CPU for what the slice must cover (tests/test_differential_
-checkers.py::test_slices_cover asserts it), and - HULL_SEEDS excepted, see there - all lie in the seed ranges of the committed round-6 records: a
-failure on one of them is a regression since then.
+checkers.py::test_slices_cover asserts it), and all lie in the seed ranges of the committed campaign records: a failure on one of them
+is a regression since then.
   ENGINE_SEEDS        profiles/r06/fuzz_engines_s10000.txt (seeds 10000 ... 13999; five polygon cases added for the fused filter
                       on polygons, whose thresholds drop most instances of the others)
   ENGINE_TINY_SEEDS   profiles/r06/fuzz_engines_tiny.txt (seeds 20000 ... 21499, make_case(seed, tiny=True))
   POINT_SEEDS         profiles/r06/fuzz_points.txt (0 ... 2999)
   ANNOTATION_SEEDS    profiles/r06/fuzz_annotations.txt (0 ... 3999)
   AUX_SEEDS           profiles/r06/fuzz_aux.txt (0 ... 1999)
-  HULL_SEEDS          NO campaign record yet (oracle/campaigns/hull.py: the convex-hull yaw of the depth + mask fit): picked by the
-                      CPU scan of seeds 70000 ... 70499 alone.  The slice itself has passed on an MI355X; the range as a whole has
-                      not run, so a failure on another seed of it need not be a regression.  profiles/hull/fuzz_hull.py writes the
-                      record (profiles/hull/fuzz_hull.txt) - commit it with the first run of the range
+  HULL_SEEDS          profiles/hull/fuzz_hull.txt (oracle/campaigns/hull.py: the convex-hull yaw of the depth + mask fit; seeds
+                      70000 ... 70499: the whole range has run - 500 cases, 5518 instances, 4277 calls, no failure)
   CLOUD_SEEDS         profiles/clouds/fuzz_clouds.txt (oracle/campaigns/clouds.py: the instance point clouds; seeds 80000 ... 80499:
-                      the whole range has run, see the record)"""
+                      the whole range has run, see the record)
+  FORMAT_SEEDS        profiles/formats/fuzz_formats.txt (oracle/campaigns/formats.py: the mask, logit and label packers and the 16-bit
+                      depth packers; seeds 90000 ... 90499: the whole range has run, see the record)"""
 
 ENGINE_SEEDS = [
     10018, 10023, 10025, 10032, 10034, 10046, 10050, 10051, 10056, 10058,
@@ -62,4 +62,18 @@ CLOUD_SEEDS = [
     80020, 80021, 80022, 80023, 80024, 80025, 80026, 80027, 80028, 80029,
     80030, 80032, 80033, 80034, 80035, 80036, 80037, 80038, 80039, 80040,
     80041, 80042, 80061, 80068, 80136, 80138, 80231, 80340,
+]
+
+# the campaign of the format converters (oracle/campaigns/formats.py), picked by a CPU scan of seeds 90000 ... 90499: every frame of the
+# generator - the second trips of the vector packer (129 / 258 / 516 x 512 for f32 / f16, bf16 / u8) and of the general packer (1031 x 509,
+# 1025 x 500 padded), the hand-made MaskBits of the unpacker's two-word read, 4194560 x 1 for both depth kernels -, every element kind of
+# every packer in a one-size and a mixed case, every threshold, layout, broken input and planted depth value, and a fit leg of more than
+# 200 instances (tests/test_differential_checkers.py::test_format_slice_covers asserts all of it).  No group of six takes
+# a second on an MI355X (profiles/formats/RESULTS.md), so the large frames stay where the seed order puts them
+FORMAT_SEEDS = [
+    90000, 90001, 90002, 90003, 90004, 90006, 90007, 90008, 90009, 90010,
+    90011, 90013, 90015, 90017, 90018, 90019, 90020, 90021, 90022, 90023,
+    90027, 90028, 90030, 90031, 90033, 90034, 90035, 90036, 90037, 90038,
+    90039, 90041, 90046, 90047, 90058, 90061, 90103, 90147, 90206, 90225,
+    90250, 90272, 90317, 90359, 90403,
 ]

@@ -10,6 +10,7 @@ from oracle.campaigns import annotations as A
 from oracle.campaigns import aux as X
 from oracle.campaigns import clouds as CL
 from oracle.campaigns import engines as E
+from oracle.campaigns import formats as FM
 from oracle.campaigns import hull as HU
 from oracle.campaigns import points as PT
 from tests import campaign_slices as S
@@ -746,3 +747,292 @@ def test_cloud_checker_sensitivity():
     # every message names its rows / instances and the field
     msg = CL.check_run(c, want, {}, plants[0][2], default)
     assert any("instance" in m and ("pixels" in m or "points" in m) for m in msg), msg
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the format converters (oracle/campaigns/formats.py)
+# ---------------------------------------------------------------------------------------------------------------------------------
+_FRAMES_RUNS = [r for r in FM.RUNS if r["entry"] == "frames" or r.get("form") == "frames"]
+FORMAT_REQUIRED = (
+    [f"frame {h}x{w}" for h, w in FM.TINY + [FM.BIG] + list(FM.VEC2) + FM.GEN2 + [FM.LONG]] + [f"unpack {a}/{b}" for a, b in FM.UNPACK]
+    + ["second trip: vector packer, f32", "second trip: vector packer, f16", "second trip: vector packer, bf16", "second trip: vector packer, u8",
+       "second trip: general packer, u8", "second trip: general packer, f32", "second trip: general packer, f16", "second trip: general packer, bf16",
+       "second trip: unpacker, quad form", "depth trips 2/2", "masks u8", "masks bool", "u8 bytes 0", "u8 bytes 1", "u8 bytes 2"]
+    + [f"labels {t}" for t in FM.LABEL_TYPES] + [f"logits {t}" for t in FM.LOGIT_TYPES] + [f"threshold {t!r}" for t in FM.THRESHOLDS]
+    + ["device base 1", "device base 5", "device base 16", "plane stride above H*W", "u8 plane stride: multiple of 16 bytes",
+       "u8 plane stride: no multiple of 16 bytes", "u8 canvas pitch: multiple of 16 bytes", "u8 canvas pitch: no multiple of 16 bytes",
+       "lowest data_ptr is not the first image's", "an image with a (0, H, W) stack and no ids", "ids outside the dtype's range", "absent ids",
+       "repeated ids", "negative ids", "fit leg", "fit16 f16", "fit16 u16h", "fit16 u16n"]
+    + [f"second trip at its smallest frame {h}x{w}: vector packer, {e}" for (h, w), e in (((129, 512), "f32"), ((258, 512), "f16"), ((258, 512), "bf16"), ((516, 512), "u8"))]
+    + [f"broken: {b}" for b in FM.BROKEN] + [f"scale {s!r}" for s in FM.D16_SCALES]
+    + [f"depth: {n}" for n in ("tie, even k (power-of-two scale)", "tie, odd k (power-of-two scale)", "below a tie (power-of-two scale)",
+                               "above a tie (power-of-two scale)", "65535 units", "65535.5 units", "above 65535 units", "subnormal", "half a unit")]
+    + [f"run {FM.run_name(r)}: one size" for r in FM.RUNS] + [f"run {FM.run_name(r)}: mixed sizes" for r in _FRAMES_RUNS + [r for r in FM.RUNS if r["entry"] == "depth16"]])
+
+
+def test_format_slice_covers():
+    """The slice of the format converters, from the generator's features alone - conditions on the INPUTS: every frame (the second-trip
+    frames of both packers for every element kind, the hand-made MaskBits, the long depth frame), every element kind of every packer in
+    a one-size and a mixed case, every threshold, each layout, host and device ids, each broken input, both depth kinds (every run
+    unpacks uint16 planes with both hole settings), every planted depth value, a mixed-size and a one-size case of every frames run -
+    and, from the oracle alone, the fit leg (all three 16-bit kinds): more than 200 instances, at least half of its instances have status 0 and an eigen-gap of at least 1e-6."""
+    assert 40 <= len(S.FORMAT_SEEDS) <= 56 and all(90000 <= s < 90500 for s in S.FORMAT_SEEDS) and len(set(S.FORMAT_SEEDS)) == len(S.FORMAT_SEEDS)
+    cases = [FM.make_case(s) for s in S.FORMAT_SEEDS]
+    feats = [FM.features(c) for c in cases]
+    have = set().union(*feats)
+    for name in FORMAT_REQUIRED:
+        assert name in have, name
+    for kind in [f"labels {t}" for t in FM.LABEL_TYPES] + [f"logits {t}" for t in FM.LOGIT_TYPES] + ["masks u8", "masks bool"]:
+        for size in ("one size", "mixed sizes"):
+            assert any(kind in f and size in f and "class tiny" in f for f in feats), (kind, size)
+    assert sum(c["sizes"].count(FM.BIG) for c in cases) >= 1 and all(c["sizes"].count(FM.BIG) <= 1 for c in cases)
+    assert all(max(c["B"].values()) <= 2 for c in cases if c["fclass"] in ("vec2", "gen2"))
+    assert all(c["packer_only"] == (c["fclass"] != "tiny") for c in cases)
+    for c in cases:                                               # the fit leg stays off the packer-only frames and the broken inputs
+        assert not ((c["packer_only"] or c["broken"]) and any(FM.applies(c, r) for r in FM.RUNS if r["entry"] == "fit")), c["seed"]
+    n_all = n_good = 0
+    for s, c in zip(S.FORMAT_SEEDS, cases):
+        if FM.has_fit(c):
+            _, st, _, _, gap = FM.oracle_case(s)["fit"]["f32"]
+            n_all += len(st)
+            n_good += int(((st == 0) & (gap >= 1e-6)).sum())
+    assert n_all > 200 and 2 * n_good >= n_all, (n_good, n_all)
+
+
+def test_format_campaign_restates_the_limits():
+    """The trip counts the campaign's docstring claims for every second-trip frame, from its restated constants (64 chunks of 256 lanes,
+    elements per 16-byte group, grid_for's 16384 workgroups) - and the restated plane layout against frames.frame_bits_offsets."""
+    from labelany3d_amd.frames import frame_bits_offsets, frame_table
+
+    assert (FM.LANES, FM.CHUNKS, FM.GROUP_BYTES, FM.GRID, FM.DEPTH_GROUP) == (256, 64, 16, 16384, 8)
+    for (H, W), elem in FM.VEC2.items():
+        for e in ("f32", "f16", "bf16", "u8"):
+            groups = H * W // (16 // FM.ELEM_BYTES[e])
+            assert FM.vec_form(H, W, W, e) and FM.pack_trips(H, W, W, e) == -(-groups // 16384), (H, W, e)
+        assert H * W // (16 // FM.ELEM_BYTES[elem]) == 16512 and FM.pack_trips(H, W, W, elem) == 2
+        assert FM.pack_trips(16384 * (16 // FM.ELEM_BYTES[elem]) // W, W, W, elem) == 1     # (exactly 16384 groups: one full trip)
+    assert not FM.vec_form(516, 512, 512, "u8", base_bytes=5) and not FM.vec_form(129, 512, 512, "u8", stride_elems=129 * 512 + 3)
+    assert FM.pack_trips(96, 224, 224, "f16") == 1 and FM.pack_trips(480, 640, 640, "u8") == 2 and FM.pack_trips(480, 640, 640, "f32") == 5
+    (H, W), (H2, W2) = FM.GEN2
+    assert not FM.vec_form(H, W, W, "u8") and (H * W + 31) // 32 == 16400 and (H * W) % 32 and FM.pack_trips(H, W, W, "u8") == 2
+    assert not FM.vec_form(H2, W2, 512, "u8") and H2 * 512 // 32 == 16400 and FM.pack_trips(H2, W2, 512, "f32") == 2
+    assert FM.pack_trips(1024, 500, 512, "u8") == 1
+    assert FM.unpack_trips(129, 512) == 2 and FM.unpack_trips(128, 512) == 1 and 129 * 512 // 4 == 16512
+    assert FM.depth_trips(1, *FM.LONG, 1) == (2, 2) and FM.depth_trips(1, 4194304, 1, 1) == (1, 1) and FM.depth_trips(1, 480, 640, 640) == (1, 1)
+    for w_in, fw in FM.UNPACK:                                    # which of the hand-made planes take the quad form's two-word read
+        two = fw % 4 == 0 and any(((v * w_in + u) & 31) > 28 for v in range(40) for u in range(0, fw, 4))
+        assert two == ((w_in, fw) in [(53, 52), (54, 52), (37, 36)]), (w_in, fw)
+    rs = np.random.RandomState(0)
+    for _ in range(20):
+        sizes = [FM.TINY[i] for i in rs.randint(0, len(FM.TINY), 5)] + [FM.BIG]
+        ii = rs.randint(0, len(sizes), 17)
+        a, b = FM.bits_offsets(sizes, ii), frame_bits_offsets(frame_table(sizes), ii)
+        np.testing.assert_array_equal(a[0], b[0])
+        assert a[1] == b[1]
+
+
+def test_format_logit_neighbours():
+    """For every threshold and storage type the generator's "largest <= t" and "smallest > t" are adjacent bit patterns of the type that
+    straddle np.float32(t) - decided in np.longdouble on exactly converted values."""
+    L = np.longdouble
+
+    def value(pat, T):                                            # the stored value, without the campaign's own conversion
+        b, e, m = (32, 8, 23) if T == "f32" else (16, 5, 10) if T == "f16" else (16, 8, 7)
+        pat = int(pat)
+        sign, ex, man = pat >> (b - 1), (pat >> m) & ((1 << e) - 1), pat & ((1 << m) - 1)
+        bias = (1 << (e - 1)) - 1
+        if ex == (1 << e) - 1:
+            return L("nan") if man else (L("-inf") if sign else L("inf"))
+        mag = L(man) * L(2) ** (1 - bias - m) if ex == 0 else (L(1) + L(man) / L(1 << m)) * L(2) ** (ex - bias)
+        return -mag if sign else mag
+
+    for t in FM.THRESHOLDS:
+        t32 = L(np.float32(t))
+        for T in FM.LOGIT_TYPES:
+            le, gt = FM.neighbours(t, T)
+            assert int(FM.key_of(gt, T)) == int(FM.key_of(le, T)) + 1, (t, T)
+            assert value(le, T) <= t32 < value(gt, T), (t, T, hex(int(le)), hex(int(gt)))
+            for pat in (le, gt, *FM.specials(T)):                 # the campaign's conversion is the exact one
+                with np.errstate(invalid="ignore"):               # (a signalling NaN among the specials)
+                    v, w = value(pat, T), L(FM.to_f32(np.asarray([pat]), T)[0])
+                assert (v != v and w != w) or v == w, (T, hex(int(pat)))
+            if T == "f32":
+                assert value(le, T) == t32
+    assert FM.neighbours(0.1, "f16") == (0x2E66, 0x2E67) and FM.neighbours(7e4, "f16") == (0x7BFF, 0x7C00) and FM.neighbours(-0.0, "bf16") == (0, 1)
+    # the planes mean their masks wherever no special value is sprinkled in, and hold the neighbours and the specials
+    rs = np.random.RandomState(1)
+    stack = rs.rand(3, 40, 50) < 0.5
+    for T in FM.LOGIT_TYPES:
+        for t in FM.THRESHOLDS:
+            pat = FM.logit_planes(rs, stack, t, T)
+            agree = (FM.logit_mask(pat, t, T) == stack).mean()
+            assert 0.9 < agree < 1.0, (T, t, agree)
+            assert set(FM.neighbours(t, T)) <= set(pat.reshape(-1).tolist()) and np.isnan(FM.to_f32(pat, T)).any()
+
+
+def _format_output(c, want, r):
+    """The oracle's own answer, laid out as a correct run's (run_gpu's dict)."""
+    e, fam, lay = r["entry"], FM.family(r), c["lay"]
+    if e == "fit":
+        rec, st, nv, _, gap = want["fit"][r["depth"]]
+        aux = np.stack([np.zeros(len(st)), nv.astype(float), want["area"][c["fit_src"]].astype(float), np.where(st == 0, gap, np.nan)], 1)
+        return dict(boxes=rec.copy(), status=st.copy(), aux=aux, sent=None)
+    if e == "depth16":
+        dt, pad = r["dtype"], lay["d16_pad"]
+        words, bufs = [], []
+        for p, (h, w) in enumerate(c["sizes"]):
+            g = np.zeros((h, FM.padded_width(w) if pad else w), np.uint16)
+            g[:, :w] = want["d16"][dt]["words"][p].view(np.uint16)
+            words.append(g)
+        if c["uniform"] and c["fclass"] != "long":
+            n_el = words[0].size
+            ostride = n_el + lay["d16_extra"]
+            obuf = np.full(c["P"] * ostride + 8, FM.SENT16, np.uint16)
+            for p in range(c["P"]):
+                obuf[p * ostride:p * ostride + n_el] = words[p].reshape(-1)
+            bufs.append((obuf, ostride, n_el, c["P"]))
+        values = {h: [v.copy() for v in want["d16"][dt]["values"][h]] if (dt == "u16" or h) else [] for h in (True, False)}
+        return dict(words=words, values=values, bufs=bufs, pad=pad, sent=None)
+    fam = fam or "masks"
+    masks, B, img = want["masks"][fam], c["B"][fam], c["img"][fam]
+    if e == "frames":
+        device = r.get("layout") == "device" or r.get("ids") == "device"
+        order = lay["perm"][fam] if r.get("layout") == "device" else np.arange(B)
+        Hb, Wb = max(h for h, _ in c["sizes"]), max(FM.padded_width(w) for _, w in c["sizes"])
+        if r.get("ids") == "device":
+            stride = (Hb * Wb // 32 + 3) // 4 * 4
+            offs, total = np.arange(B, dtype=np.int64) * stride, B * stride
+        else:
+            offs, total = FM.bits_offsets(c["sizes"], img[order])
+        buf = np.full(max(total, 4) + 8, FM.SENT, np.uint32) if device else np.zeros(max(total, 4), np.uint32)
+        area, ii, offs_out = want["area"][fam][order].copy(), img[order].copy(), offs.copy()
+        broke = c["broken"] if (c["broken"] and fam == "masks" and r.get("layout") == "device") else None
+        for i, n in enumerate(order):
+            ww = FM.plane_words(masks[n], FM.padded_width(masks[n].shape[1]))
+            if broke and broke[1] == i:
+                area[i] = 0
+                if broke[0] in FM.BROKEN[2:]:
+                    if broke[0] == FM.BROKEN[2]:
+                        ii[i] = c["P"] if i % 2 else -1
+                    else:
+                        offs_out[i] = -4 if broke[0] == FM.BROKEN[3] else offs[i] + 2
+                    continue
+                ww = np.zeros_like(ww)
+            buf[offs[i]:offs[i] + len(ww)] = ww
+        return dict(buf=buf, offsets=offs_out, image_index=ii.astype(np.int32), area=area.astype(np.int32), H=Hb, W=Wb, order=np.asarray(order),
+                    sent=FM.SENT if device else None)
+    H, fw = c["sizes"][0]
+    W_st = c["w_in"] if e == "unpack" else (FM.padded_width(fw) if FM.uniform_pad(c, r) else fw)
+    device = r.get("layout") == "device" or r.get("ids") == "device"
+    nw = (H * W_st + 31) // 32
+    buf = np.full((B, nw + (lay["out_pad"] if device else 0)), FM.SENT, np.uint32)
+    for n in range(B):
+        buf[n, :nw] = FM.plane_words(masks[n], W_st)
+    got = dict(buf=buf, H=H, W=W_st, fw=fw, sent=FM.SENT if device else None, unpacked=np.stack(masks), stats={b: want["stats"][fam][b].copy() for b in (10, 3)})
+    if fam == "labels":
+        got.update(area=want["area"][fam].astype(np.int32), image_index=img.copy())
+    return got
+
+
+def test_format_checker_passes_the_oracle_in_every_run():
+    seen = set()
+    for s in S.FORMAT_SEEDS:
+        c, want = FM.make_case(s), FM.oracle_case(s)
+        default = {}
+        for r in FM.RUNS:
+            if FM.applies(c, r):
+                got = _format_output(c, want, r)
+                fam = FM.family(r)
+                if fam is not None and fam not in default:
+                    default[fam] = FM.decoded(c, r, got)
+                assert FM.check_run(c, want, r, got, default.get(fam)) == [], (s, r)
+                seen.add(FM.run_name(r))
+    assert len(seen) == len(FM.RUNS)
+
+
+def test_format_checker_sensitivity():
+    """One planted error per rule: the rule, run alone through rules=, reports it, and without the rule (and the ones named beside it,
+    which see the same words) the checker is silent: none of the rules is redundant, none is vacuous."""
+    run = lambda **kw: next(r for r in FM.RUNS if all(r.get(k) == v for k, v in kw.items()))   # noqa: E731
+    cases = [(FM.make_case(s), FM.oracle_case(s)) for s in S.FORMAT_SEEDS]
+    plants = []
+
+    def plant(name, rule, c, want, r, f, also=(), default=None):
+        good = _format_output(c, want, r)
+        assert FM.check_run(c, want, r, good, default) == [], name
+        bad = copy.deepcopy(good)
+        f(bad)
+        plants.append((name, rule, also, c, want, r, bad, default))
+
+    # a mixed-size masks case without a broken input whose first three planes hold pixels; a width that is no multiple of 32
+    c, want = next((c, w) for c, w in cases if not c["uniform"] and not c["broken"] and c["B"]["masks"] >= 3 and (w["area"]["masks"][:3] > 0).all())
+    r = run(src="masks", entry="frames", layout="device")
+    g = _format_output(c, want, r)
+    order, offs = g["order"], g["offsets"]
+    nw = [h * FM.padded_width(w) // 32 for h, w in (c["sizes"][int(c["img"]["masks"][n])] for n in order)]
+    i = int(np.argmax(nw))
+    for name, at in (("first", offs[i]), ("a middle", offs[i] + nw[i] // 2), ("the last", offs[i] + nw[i] - 1)):
+        plant(f"one bit of {name} word flipped", "words", c, want, r, lambda b, at=at: b["buf"].__setitem__(at, b["buf"][at] ^ np.uint32(1)))
+    j = next(k for k, n in enumerate(order) if c["sizes"][int(c["img"]["masks"][n])][1] % 32)
+    plant("a padding bit set", "padding", c, want, r, lambda b: b["buf"].__setitem__(offs[j] + nw[j] - 1, b["buf"][offs[j] + nw[j] - 1] | np.uint32(1 << 31)), also=("words",))
+    plant("an area off by one", "area", c, want, r, lambda b: b["area"].__setitem__(1, b["area"][1] + 1))
+    plant("a wrong plane offset", "layout", c, want, r, lambda b: b["offsets"].__setitem__(2, b["offsets"][2] + 4))
+    plant("a sentinel touched behind the planes", "sentinel", c, want, r, lambda b: b["buf"].__setitem__(len(b["buf"]) - 1, 0))
+    gap_at = next((int(offs[k] + nw[k]) for k in range(len(order)) if nw[k] % 4), None)
+    if gap_at is not None:
+        plant("a sentinel touched between two planes", "sentinel", c, want, r, lambda b: b["buf"].__setitem__(gap_at, 0))
+    dflt = FM.decoded(c, run(src="masks", entry="frames", layout="host"), _format_output(c, want, run(src="masks", entry="frames", layout="host")))
+    other = copy.deepcopy(dflt)
+    other[int(order[i])][0, 0] ^= True
+    plants.append(("planes that are not the first run's", "agree", (), c, want, r, g, other))
+    # a one-size case: the uniform entries
+    c, want = next((c, w) for c, w in cases if c["uniform"] and c["fclass"] == "tiny" and c["B"]["masks"] >= 2 and c["sizes"][0][0] > 4 and w["area"]["masks"].min() > 0)
+    r = run(src="masks", entry="uniform", layout="device")
+    plant("a sentinel touched behind a plane of out=", "sentinel", c, want, r, lambda b: b["buf"].__setitem__((1, b["buf"].shape[1] - 1), 7))
+    plant("one pixel of the unpacked mask wrong", "roundtrip", c, want, r, lambda b: b["unpacked"].__setitem__((0, 1, 0), ~b["unpacked"][0, 1, 0]))
+    plant("a boundary statistic off by one", "stats", c, want, r, lambda b: b["stats"][3].__setitem__((0, 3), b["stats"][3][0, 3] + 1))
+    plant("a stored width that is not the padded one", "layout", c, want, r, lambda b: b.__setitem__("W", b["W"] + 32))
+    # logits: the stored value next to the threshold, on the wrong side
+    for c, want in cases:
+        le = FM.neighbours(c["threshold"], c["logit_type"])[0]
+        hit = [(p, np.argwhere(st == le)) for p, st in enumerate(c["logits"])]
+        hit = [(p, a[0]) for p, a in hit if len(a)]
+        if c["uniform"] and c["fclass"] == "tiny" and hit:
+            p, (k, v, u) = hit[0]
+            n = int(np.flatnonzero(c["img"]["logits"] == p)[k])
+            r = run(src="logits", entry="uniform", layout="host", frame_pad=True)
+            Wp = FM.padded_width(c["sizes"][0][1])
+            assert not want["masks"]["logits"][n][v, u]           # (the largest value <= the threshold does not pass x > threshold)
+            plant("the logit just below the threshold packed as set", "words", c, want, r,
+                  lambda b, n=n, at=(v * Wp + u): b["buf"].__setitem__((n, at // 32), b["buf"][n, at // 32] | np.uint32(1 << (at % 32))))
+            break
+    else:
+        raise AssertionError("no one-size case of the slice stores the value just below its threshold")
+    # 16-bit depth: one wrong word; an exact tie rounded away from even
+    c, want = next((c, w) for c, w in cases if "tie, even k (power-of-two scale)" in c["planted"])
+    r = run(entry="depth16", dtype="u16")
+    q = [c["depth"][p].astype(np.float64) / c["scale"] for p in range(c["P"])]
+    p, (v, u) = next((p, a[0]) for p, a in ((p, np.argwhere((x % 2 == 0.5) & (x < 65535))) for p, x in enumerate(q)) if len(a))
+    assert want["d16"]["u16"]["words"][p][v, u] == int(q[p][v, u] - 0.5)
+    plant("an exact tie rounded away from even", "depth16", c, want, r, lambda b: b["words"][p].__setitem__((v, u), b["words"][p][v, u] + 1))
+    plant("one 16-bit word wrong", "depth16", c, want, run(entry="depth16", dtype="f16"), lambda b: b["words"][0].__setitem__((0, 0), b["words"][0][0, 0] ^ 1))
+    plant("an unpacked hole that is 0.0", "depth16", c, want, r, lambda b: b["values"][True][p].__setitem__((v, u), np.float32(0) if np.isnan(b["values"][True][p][v, u]) else np.float32("nan")))
+    # the fit leg
+    c, want, n = next((c, w, int(np.flatnonzero((w["fit"]["f32"][1] == 0) & (w["fit"]["f32"][4] > 1e-3))[0])) for c, w in cases
+                      if FM.has_fit(c) and ((w["fit"]["f32"][1] == 0) & (w["fit"]["f32"][4] > 1e-3)).any() and (w["fit"]["f32"][1] != 0).any())
+    r = run(entry="fit", form="frames", depth="f32")
+    m = int(np.flatnonzero(want["fit"]["f32"][1] != 0)[0])
+
+    def swap(b):
+        b["status"][[n, m]] = b["status"][[m, n]]
+
+    plant("two status values exchanged", "fit", c, want, r, swap)
+    plant("a record off by 1e-6", "fit", c, want, r, lambda b: b["boxes"].__setitem__((n, 0), b["boxes"][n, 0] + 1e-6 * max(1.0, np.abs(b["boxes"][n, :6]).max())))
+    plant("a zero eigen-gap reported for a decided record", "fit", c, want, r, lambda b: b["aux"].__setitem__((n, 3), 0.0))
+    plant("a NaN eigen-gap reported for a decided record", "fit", c, want, r, lambda b: b["aux"].__setitem__((n, 3), np.nan))
+    plant("n_valid off by one", "fit", c, want, r, lambda b: b["aux"].__setitem__((n, 1), b["aux"][n, 1] + 1))
+    for name, rule, also, c, want, r, bad, default in plants:
+        assert FM.check_run(c, want, r, bad, default, rules=[rule]), f"planted error not reported by '{rule}' alone: {name}"
+        rest = [k for k in FM.RULES if k != rule and k not in also]
+        assert FM.check_run(c, want, r, bad, default, rules=rest) == [], f"{name}: reported without the rule '{rule}'"
+    assert {rule for _, rule, *_ in plants} == set(FM.RULES)

@@ -10,6 +10,10 @@
                 (the same bytes as the default run), full-mask and subsample mode, 60 cases
   clouds        the instance point clouds (oracle/campaigns/clouds.py): u8 and bit planes, float32 output, every 16-bit kind, the
                 frames form, a short capacity and the C entry in place, with and without sample_idx, 48 cases
+  formats       the format converters in front of the fit (oracle/campaigns/formats.py): the mask, logit and label packers of one
+                frame size and of mixed sizes, host and device layouts, out= buffers, the unpacker, the bit-plane statistics, both
+                16-bit depth packers and the fit on the planes they wrote, 45 cases; the fit leg of the whole slice once more on its own, held to the share of
+                records that must be compared
   aux           unproject, decoders, mask statistics, filters, consumers, depth statistics, matcher, 40 cases
 A case fails with the campaign's own message, which names its seed."""
 import numpy as np
@@ -19,6 +23,7 @@ from oracle.campaigns import annotations as A
 from oracle.campaigns import aux as X
 from oracle.campaigns import clouds as CL
 from oracle.campaigns import engines as E
+from oracle.campaigns import formats as FM
 from oracle.campaigns import hull as HU
 from oracle.campaigns import points as PT
 from tests import campaign_slices as S
@@ -159,6 +164,57 @@ def test_cloud_campaign_slice(gpu, seeds):
             fails += [f"seed {s} {r}: {m}" for m in CL.check_run(c, want, r, got, default)]
     print("\n".join(CL.tally_lines(tally)))
     assert not fails, _report(fails)
+
+
+@pytest.mark.parametrize("seeds", _groups(S.FORMAT_SEEDS, 6), ids=lambda v: str(v[0]))
+def test_format_campaign_slice(gpu, seeds):
+    """The packers, the unpacker, the statistics and the 16-bit depth packers: every word, padding bit, area, offset and sentinel
+    exactly, the runs among each other, and the fit on the packed planes by the engines campaign's rule.  A call that raises ends the
+    group's GPU work."""
+    fails = []
+    tally = FM.new_tally()
+    for s in seeds:
+        c = FM.make_case(s)
+        want = FM.oracle_case(s)
+        FM.tally_case(tally, c, want)
+        cache, default = {}, {}
+        for r in FM.RUNS:
+            if not FM.applies(c, r):
+                continue
+            try:
+                got = FM.run_gpu(c, r, cache)
+            except Exception as e:   # noqa: BLE001 - whatever made the call fail is looked at before anything else runs on the device
+                print("\n".join(FM.tally_lines(tally)))
+                pytest.fail(_report(fails + [f"seed {s} {r}: call failed, nothing more was run: {e!r}"]))
+            FM.tally_call(tally, r)
+            fam = FM.family(r)
+            if fam is not None and fam not in default:
+                default[fam] = FM.decoded(c, r, got)
+            fails += [f"seed {s} {r}: {m}" for m in FM.check_run(c, want, r, got, default.get(fam), tally=tally)]
+    print("\n".join(FM.tally_lines(tally)))
+    assert not fails, _report(fails)
+
+
+def test_format_slice_fit_leg_compares_a_third(gpu):
+    """The fit leg of the WHOLE slice (a group may hold no fit at all): no failure, and at least a third of the fitted instances
+    compared record by record - the ratio of tests/test_gpu_frames.py::test_randomised_sweep.  A reported eigen-gap below 1e-9 takes a
+    record out of the comparison only where the oracle's own gap is small too (FM.check_run), so a library that reported no gap
+    would fail here, not pass unchecked."""
+    fails = []
+    tally = FM.new_tally()
+    for s in S.FORMAT_SEEDS:
+        c = FM.make_case(s)
+        for r in FM.RUNS:
+            if r["entry"] == "fit" and FM.applies(c, r):
+                try:
+                    got = FM.run_gpu(c, r)
+                except Exception as e:   # noqa: BLE001
+                    pytest.fail(_report(fails + [f"seed {s} {r}: call failed, nothing more was run: {e!r}"]))
+                FM.tally_call(tally, r)
+                fails += [f"seed {s} {r}: {m}" for m in FM.check_run(c, FM.oracle_case(s), r, got, rules=("fit",), tally=tally)]
+    print("\n".join(FM.tally_lines(tally)))
+    assert not fails, _report(fails)
+    assert tally["fitted"] > 0 and 3 * tally["compared"] >= tally["fitted"], (tally["compared"], tally["fitted"])
 
 
 def test_engine_slice_reaches_the_documented_refusal(gpu):
