@@ -604,6 +604,47 @@ int la3d_poly_decode(const int32_t* poly_xy, const int64_t* ring_offsets, const 
 int la3d_mask_stats_poly(const int32_t* poly_xy, const int64_t* ring_offsets, const int64_t* inst_rings, int B, int H, int W,
                          int boundary, int32_t* stats, void* stream);
 
+/* ---- annotations as bit planes -----------------------------------------------------------------------------------------
+ * la3d_rle_decode / la3d_poly_decode with the bit image kept as the output: COCO run lengths and polygon parts -> the planes of
+ * "masks as bit planes" (38 400 B per 640x480 instance instead of the 307 200 B of a u8 plane), for every consumer of planes that
+ * is not the fit itself (the fit decodes annotations inside its own kernel): la3d_gather_instance_points, la3d_mask_stats_bits,
+ * la3d_unpack_mask_bits, and la3d_fit_instances_bits / la3d_fit_instances_frames_bits for planes that stay resident.  One workgroup
+ * per instance decodes into LDS and streams the words out; the call never synchronises and is capturable (one kernel, no clear).
+ *
+ * la3d_pack_rle_bits / la3d_pack_poly_bits (one frame size): the annotation arrays as la3d_rle_decode / la3d_poly_decode take them
+ *   (counts + offsets [B+1]: column-major runs over (H, W), zeros first; poly_xy + ring_offsets + inst_rings [B+1]).
+ *   Output: B planes in exactly the format of la3d_pack_mask_bits - la3d_mask_bits_words(H, W_out) words each, bits_plane_stride
+ *   words apart, rows padded from W to W_out with zero bits; every word of every plane is written and nothing else.  W_out is W (any
+ *   width: the decoders' general routes) or a multiple of 32 >= W (the next one is what the tiled forms of the fit want).  A
+ *   16-byte aligned base with bits_plane_stride % 4 == 0 is written in 16-byte groups, anything else word by word.
+ *   area: dev [B] or NULL - the popcount of each plane as written (what area_hint wants), stored by the plane's own workgroup.
+ *   LA3D_ERR_ARG: negative B, H, W <= 0, W_out < W, a W_out != W that is no multiple of 32, bits_plane_stride <
+ *   la3d_mask_bits_words(H, W_out), NULL or misaligned (4 bytes) pointers with work to do.  H*W_out > 1048576 (the bit image lives
+ *   in LDS): LA3D_ERR_UNSUPPORTED.  B == 0: success, nothing is launched.
+ * la3d_pack_rle_bits_frames / la3d_pack_poly_bits_frames (images of different sizes): instance n belongs to image image_index[n]
+ *   (dev i32 [B]); its runs are column-major over its own (H_f, frame_width), its polygon sides are clipped to its own frame_width x
+ *   H_f - the rules of la3d_fit_instances_frames.  frames, P, H, W (bounds): as in the fit - ONE table serves packer and fit.
+ *   Output: the contract of la3d_pack_mask_bits_frames - the plane of row n at bits + bits_offsets[n] (dev i64 [B]), the H_f * W_f / 32
+ *   words of its image's frame, every word of them and nothing else, the bits of columns >= frame_width zero; bits 16-byte aligned
+ *   (LA3D_ERR_ARG otherwise).  Checked ON THE DEVICE, each before an address is formed from the value, in this order:
+ *   image_index[n] in [0, P); the frame row (the check of the fit); bits_offsets[n] >= 0 and a multiple of 4.  A refused row writes
+ *   no plane word and gets area 0: exactly the instances the fit then answers with LA3D_BOX_UNSUPPORTED.
+ *   LA3D_ERR_ARG: negative B or P, bounds <= 0, NULL or misaligned pointers with work to do; bounds beyond H * roundup32(W) <=
+ *   1048576: LA3D_ERR_UNSUPPORTED.  B == 0: success, nothing is launched.
+ * HOSTILE RUN LISTS.  Whatever a run list holds, only the words of the instance's own plane are written (the decode goes to LDS, the
+ *   copy covers exactly the plane): a negative count is a run of length 0, runs past H * frame_width are cut, an offsets pair that
+ *   goes backwards gives an empty plane.  What offsets / ring_offsets / inst_rings ADDRESS must lie inside the caller's arrays. */
+int la3d_pack_rle_bits(const int32_t* counts, const int64_t* offsets, int B, int H, int W, int W_out, uint32_t* bits,
+                       int64_t bits_plane_stride, int32_t* area /* dev [B] or NULL */, void* stream);
+int la3d_pack_poly_bits(const int32_t* poly_xy, const int64_t* ring_offsets, const int64_t* inst_rings, int B, int H, int W, int W_out,
+                        uint32_t* bits, int64_t bits_plane_stride, int32_t* area /* dev [B] or NULL */, void* stream);
+int la3d_pack_rle_bits_frames(const int32_t* counts, const int64_t* offsets, const la3d_frame* frames, int32_t P, int H, int W /* bounds */,
+                              const int32_t* image_index /* dev [B] */, int B, uint32_t* bits, const int64_t* bits_offsets /* dev [B] */,
+                              int32_t* area /* dev [B] or NULL */, void* stream);
+int la3d_pack_poly_bits_frames(const int32_t* poly_xy, const int64_t* ring_offsets, const int64_t* inst_rings, const la3d_frame* frames,
+                               int32_t P, int H, int W /* bounds */, const int32_t* image_index /* dev [B] */, int B, uint32_t* bits,
+                               const int64_t* bits_offsets /* dev [B] */, int32_t* area /* dev [B] or NULL */, void* stream);
+
 /* HOST helper: COCO compressed RLE string (pycocotools rleFrString) -> run lengths.  Returns the number of
  * counts written, or -1 (malformed string / cap too small). */
 int la3d_rle_from_string_host(const char* s, int64_t len, int32_t* counts, int cap);

@@ -15,7 +15,7 @@ from ._lib import check, lib
 from .batched import Depth16, _as_dev, _bits_stride, _depth16_block, _depth16_check, _dev, _fit_inputs, _record, _stream
 from .fitcall import depth_rows_for_bits
 from .frames import FrameBits, _frames_depth, _on_gpu, _same_table
-from .masks import LabelBits, _mask_bits
+from .masks import LabelBits, _PackedBits, _mask_bits
 
 
 class InstancePoints(NamedTuple):
@@ -90,7 +90,10 @@ def instance_points(depth, masks, K, image_index=None, sample_idx=None, capacity
     pixels gets the 500 rows of the given ranks (``draw_sample_idx(counts)``), every other its whole cloud.
     ``capacity=None`` reads ``offsets[-1]`` back once - the one synchronisation - and allocates exactly; ``capacity=int`` never
     synchronises (an instance that does not fit gets status 1 and is not written), so the call can be captured into a graph.
-    ``pixels=True`` adds the flat pixel index of every row.  Returns ``InstancePoints``."""
+    ``pixels=True`` adds the flat pixel index of every row.  Returns ``InstancePoints``.
+    The ``MaskBits`` that ``pack_rle_bits`` / ``pack_poly_bits`` return is trusted: the packer has just checked and filled the tensor, so
+    its layout is not checked a second time here (at one or sixteen instances the call is bound by what this wrapper costs); every
+    other ``MaskBits`` - hand-made, from another packer, a ``_replace`` - is checked as ever."""
     _cloud_args(out_dtype, capacity)
     if isinstance(masks, LabelBits):
         image_index = masks.image_index if image_index is None else image_index
@@ -99,13 +102,18 @@ def instance_points(depth, masks, K, image_index=None, sample_idx=None, capacity
         _depth16_check(depth)
     a = _lib.CloudArgs(struct_size=C.sizeof(_lib.CloudArgs))
     if isinstance(masks, tuple):
-        mb = _mask_bits(masks)
+        # (planes straight from pack_rle_bits / pack_poly_bits: that packer has checked the tensor and left its stride)
+        stride = getattr(masks, "_stride", None) if isinstance(masks, _PackedBits) else None
+        mb = masks if stride is not None else _mask_bits(masks)
         dev = mb.bits.device if device is None else _dev(device)
         if mb.bits.device != dev:
             raise ValueError("the bit planes live on another device")
         B, H, W, fw = int(mb.bits.shape[0]), mb.H, mb.W, mb.frame_width
-        depth, fw_send = depth_rows_for_bits(depth, W, fw, dev)
-        a.mask_bits, a.bits_plane_stride, a.frame_width = mb.bits.data_ptr(), _bits_stride(mb.bits, B, H, W), fw_send
+        if stride is not None and type(depth) is torch.Tensor and depth.dtype == torch.float32 and depth.shape[-1] == W:
+            fw_send = 0 if fw == W else fw   # (depth rows as wide as the planes are stored: what depth_rows_for_bits answers)
+        else:
+            depth, fw_send = depth_rows_for_bits(depth, W, fw, dev)
+        a.mask_bits, a.bits_plane_stride, a.frame_width = mb.bits.data_ptr(), stride if stride is not None else _bits_stride(mb.bits, B, H, W), fw_send
         keep, frame = [mb.bits], "the bit-plane frame"
     else:
         if device is None and isinstance(masks, torch.Tensor) and masks.is_cuda:

@@ -198,6 +198,131 @@ __global__ __launch_bounds__(NT_DEC) void poly_decode_kernel(const int* __restri
   bits_to_plane<NT_DEC>(bits, H * W, out + (long long)blockIdx.x * H * W, tid);
 }
 
+// ---- annotations -> bit planes (la3d_pack_rle_bits / la3d_pack_poly_bits and their frames forms) -----------------------------
+// The two decode kernels above with the LDS bit image KEPT as the output: one workgroup of NT_DEC threads per instance decodes into
+// LDS (rle_to_bits / poly_to_bits with frame_w / clipW: the bits of the padding columns are zero) and streams the words to the
+// instance's plane - an eighth of the bytes of the u8 plane.  The workgroup owns its instance: the area is reduced inside it and
+// stored by one lane (no atomic, no clear kernel).
+struct BitsOut {              // where the planes of a call go (kernel argument)
+  unsigned* bits;
+  long long stride;           // uniform form: words between planes
+  const long long* offsets;   // frames form: words from bits to the plane of each instance
+  int* area;                  // [B] or NULL
+  const la3d_frame* frames;   // frames form: the table, P rows
+  const int* image_index;
+  int P;
+  int H, W;                   // uniform form: the frame as stored (W = W_out); frames form: the bounds
+  int frame_w;                // uniform form: the image columns where the rows are padded (0: none)
+  int lds_words;              // words of the bit image the launch reserved (uniform form: the plane's)
+  int vec;                    // uniform form: every plane 16-byte aligned
+};
+struct PlaneGeo { int H, W, fw, nwords, vec; unsigned* out; };
+
+// The geometry and the plane of instance b.  Frames form: every value that decides an address comes through a scalar load and is
+// checked BEFORE an address is formed from it - the image index, then the frame row (frame_row_ok: the check the fit makes), then
+// the plane's offset (>= 0, a multiple of 4: the rule of the fit).  false: the instance is refused - nothing is written for it.
+template <bool FRAMES>
+__device__ inline bool plane_geometry(const BitsOut& c, int b, PlaneGeo* g) {
+  if constexpr (FRAMES) {
+    const int img = __builtin_amdgcn_readfirstlane(c.image_index[b]);
+    if ((unsigned)img >= (unsigned)c.P) return false;
+    const FrameRow r = frame_row_load(c.frames + img);
+    if (!frame_row_ok(r, c.H, c.W)) return false;
+    const long long oo = poly_uniform(c.offsets[b]);
+    if (oo < 0 || (oo & 3) != 0) return false;
+    g->H = r.H; g->W = r.W; g->fw = r.fw;
+    g->nwords = (r.H * r.W) >> 5;   // (<= lds_words: H <= bound, W <= bound, W % 32 == 0)
+    g->vec = 1;                     // (bits is 16-byte aligned - checked on the host - and the offset a multiple of 4)
+    g->out = c.bits + oo;
+  } else {
+    g->H = c.H; g->W = c.W; g->fw = c.frame_w; g->nwords = c.lds_words; g->vec = c.vec;
+    g->out = c.bits + (long long)b * c.stride;
+  }
+  return true;
+}
+
+// bit image in LDS -> the plane's nwords words, exactly those: 16-byte non-temporal stores (vec: the plane's base is 16-byte
+// aligned) and up to three words of tail, or word by word.  Then area[b] = the popcount of the words as written.  red: LDS, NTH / 64 ints.
+template <int NTH>
+__device__ inline void lds_to_bits_plane(const unsigned* bits, const PlaneGeo& g, int* red, int* __restrict__ area, int b, int tid) {
+  int n = 0;
+  if (g.vec) {   // uniform
+    const int ng = g.nwords >> 2;
+    const u32x4* s4 = reinterpret_cast<const u32x4*>(bits);
+    u32x4* o4 = reinterpret_cast<u32x4*>(g.out);
+#pragma unroll 4
+    for (int q = tid; q < ng; q += NTH) {
+      const u32x4 w = s4[q];
+      __builtin_nontemporal_store(w, o4 + q);
+      n += (__popc(w.x) + __popc(w.y)) + (__popc(w.z) + __popc(w.w));
+    }
+    const int r = ng * 4 + tid;   // the up to three words behind the last whole group
+    if (tid < 4 && r < g.nwords) {
+      const unsigned w = bits[r];
+      g.out[r] = w;
+      n += __popc(w);
+    }
+  } else {
+    for (int i = tid; i < g.nwords; i += NTH) {
+      const unsigned w = bits[i];
+      g.out[i] = w;
+      n += __popc(w);
+    }
+  }
+  if (!area) return;   // uniform
+  n = wave_sum_i(n);
+  if ((tid & 63) == 0) red[tid >> 6] = n;
+  __syncthreads();
+  if (tid == 0) {
+    int s = 0;
+#pragma unroll
+    for (int w = 0; w < NTH / 64; ++w) s += red[w];
+    area[b] = s;
+  }
+}
+
+// Dynamic LDS: the bit image (lds_words), 16 words of wave totals, the block totals of the column scan (scan_words) - the layout
+// of rle_decode_kernel, sized by the call's bounds.
+template <bool FRAMES>
+__global__ __launch_bounds__(NT_DEC) void pack_rle_bits_kernel(const int* __restrict__ counts, const long long* __restrict__ offsets,
+                                                               int scan_words, const BitsOut c) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ int red[NT_DEC / 64];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  PlaneGeo g;
+  if (!plane_geometry<FRAMES>(c, b, &g)) {   // (uniform) refused: no plane word, area 0
+    if (tid == 0 && c.area) c.area[b] = 0;
+    return;
+  }
+  unsigned* bits = reinterpret_cast<unsigned*>(smem);
+  unsigned* wtot = bits + c.lds_words;
+  const long long o0 = offsets[b];
+  (void)rle_to_bits<NT_DEC>(counts + o0, (int)(offsets[b + 1] - o0), bits, g.nwords, g.H, g.W, wtot, tid, wtot + 16, scan_words, g.fw);
+  __syncthreads();
+  lds_to_bits_plane<NT_DEC>(bits, g, red, c.area, b, tid);
+}
+
+// Dynamic LDS: bit image (16-aligned), side stage, flags - the layout of poly_decode_kernel, sized by the call's bounds.
+template <bool FRAMES>
+__global__ __launch_bounds__(NT_DEC) void pack_poly_bits_kernel(const int* __restrict__ xy, const long long* __restrict__ ring_off,
+                                                                const long long* __restrict__ inst_rings, const BitsOut c) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ int red[NT_DEC / 64];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  PlaneGeo g;
+  if (!plane_geometry<FRAMES>(c, b, &g)) {   // (uniform) refused: no plane word, area 0
+    if (tid == 0 && c.area) c.area[b] = 0;
+    return;
+  }
+  unsigned* bits = reinterpret_cast<unsigned*>(smem);
+  const size_t bit_bytes = ((size_t)c.lds_words * 4 + 15) & ~(size_t)15;
+  PolySide* stage = reinterpret_cast<PolySide*>(smem + bit_bytes);
+  unsigned* flags = reinterpret_cast<unsigned*>(smem + bit_bytes + POLY_STAGE_BYTES);
+  (void)poly_to_bits<NT_DEC>(xy, ring_off, inst_rings[b], inst_rings[b + 1], stage, flags, bits, g.nwords, g.H, g.W, tid, g.fw);
+  __syncthreads();
+  lds_to_bits_plane<NT_DEC>(bits, g, red, c.area, b, tid);
+}
+
 // The reference's filter quantities (mask_stats) for polygon annotations without materialising a plane: rasterise into
 // LDS, count there.  Dynamic LDS: bit image, side stage, flags (64 B), per-row counts (H ints), 20 ints.
 __global__ __launch_bounds__(256) void mask_stats_poly_kernel(const int* __restrict__ xy, const long long* __restrict__ ring_off,
@@ -875,6 +1000,158 @@ int la3d_mask_stats_bits(const uint32_t* bits, int64_t bits_plane_stride, int B,
   hipLaunchKernelGGL(mask_stats_bits_kernel, dim3(B), dim3(256), (((size_t)nwords * 4 + 15) & ~(size_t)15) + 16, static_cast<hipStream_t>(stream),
                      bits, (long long)bits_plane_stride, vec, H, W, frame_width > 0 ? frame_width : W, nwords, boundary, stats);
   return check_launch("mask_stats_bits_kernel");
+}
+
+}  // extern "C"
+
+// ---- annotations -> bit planes: the checks and launches of the four entries ---------------------------------------------------
+namespace {
+constexpr size_t ANN_LDS_MAX = 160 * 1024 - 256;
+
+// uniform form: LA3D_ERR_ARG / LA3D_ERR_UNSUPPORTED, 1 = nothing to do (B == 0), LA3D_SUCCESS = launch
+int ann_bits_check(const char* who, bool null_src, int B, int H, int W, int W_out, const uint32_t* bits, long long bits_plane_stride,
+                   const int32_t* area) {
+  char msg[240];
+  const char* bad = nullptr;
+  if (B < 0 || H <= 0 || W <= 0 || W_out < W) bad = "bad argument (B >= 0, H, W > 0, W_out >= W)";
+  else if (W_out != W && W_out % 32 != 0) bad = "W_out must be W or a multiple of 32 (padded rows are whole words)";
+  else if (B > 0 && (null_src || !bits)) bad = "NULL annotation arrays or bits";
+  else if (B > 0 && ((reinterpret_cast<uintptr_t>(bits) | reinterpret_cast<uintptr_t>(area)) & 3)) bad = "bits or area not a 4-byte aligned pointer";
+  if (!bad && (long long)H * W_out > (1LL << 20)) {   // (before the stride rule: its word count is then known to fit an int)
+    snprintf(msg, sizeof(msg), "%s: the bit image must fit LDS (H*W_out <= 1048576)", who);
+    set_err(msg);
+    return LA3D_ERR_UNSUPPORTED;
+  }
+  if (!bad && B > 0 && bits_plane_stride < (long long)la3d_mask_bits_words(H, W_out)) bad = "bits_plane_stride is smaller than la3d_mask_bits_words(H, W_out)";
+  if (bad) {
+    snprintf(msg, sizeof(msg), "%s: %s", who, bad);
+    set_err(msg);
+    return LA3D_ERR_ARG;
+  }
+  return B == 0 ? 1 : LA3D_SUCCESS;
+}
+
+// frames form; *words_out: the words of the bounds' plane (rows of whole words)
+int ann_bits_frames_check(const char* who, bool null_src, const la3d_frame* frames, int P, int H, int W, const int32_t* image_index, int B,
+                          const uint32_t* bits, const int64_t* bits_offsets, const int32_t* area, long long* words_out) {
+  char msg[240];
+  const char* bad = nullptr;
+  if (B < 0 || P < 0 || H <= 0 || W <= 0) bad = "bad argument (B, P >= 0, bounds H, W > 0)";
+  else if (B > 0 && (null_src || (P > 0 && !frames) || !image_index || !bits || !bits_offsets))
+    bad = "NULL annotation arrays, frames, image_index, bits or bits_offsets";
+  else if (B > 0 && (reinterpret_cast<uintptr_t>(bits) & 15)) bad = "bits not a 16-byte aligned pointer";
+  else if (B > 0 && ((reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(bits_offsets)) & 7))
+    bad = "frames or bits_offsets not an 8-byte aligned pointer";
+  else if (B > 0 && ((reinterpret_cast<uintptr_t>(image_index) | reinterpret_cast<uintptr_t>(area)) & 3))
+    bad = "image_index or area not a 4-byte aligned pointer";
+  if (bad) {
+    snprintf(msg, sizeof(msg), "%s: %s", who, bad);
+    set_err(msg);
+    return LA3D_ERR_ARG;
+  }
+  const long long words = (long long)H * ((W + 31) / 32);
+  if (words > (1LL << 15)) {
+    snprintf(msg, sizeof(msg), "%s: the bit image of the bounds must fit LDS (H * roundup32(W) <= 1048576)", who);
+    set_err(msg);
+    return LA3D_ERR_UNSUPPORTED;
+  }
+  *words_out = words;
+  return B == 0 ? 1 : LA3D_SUCCESS;
+}
+
+inline size_t rle_bits_lds(int lds_words, int scan_words) { return (size_t)lds_words * 4 + 64 + (size_t)scan_words * 4; }
+inline size_t poly_bits_lds(int lds_words) { return (((size_t)lds_words * 4 + 15) & ~(size_t)15) + POLY_STAGE_BYTES + 64; }
+
+int ann_lds_refuse(const char* who) {
+  char msg[200];
+  snprintf(msg, sizeof(msg), "%s: frame too large for LDS", who);
+  set_err(msg);
+  return LA3D_ERR_UNSUPPORTED;
+}
+
+BitsOut bits_out_uniform(int H, int W, int W_out, uint32_t* bits, long long stride, int32_t* area) {
+  BitsOut c = {};
+  c.bits = bits; c.stride = stride; c.area = area;
+  c.H = H; c.W = W_out; c.frame_w = W_out > W ? W : 0;
+  c.lds_words = (int)la3d_mask_bits_words(H, W_out);
+  c.vec = ((reinterpret_cast<uintptr_t>(bits) & 15) == 0 && stride % 4 == 0) ? 1 : 0;
+  return c;
+}
+
+BitsOut bits_out_frames(const la3d_frame* frames, int P, int H, int W, const int32_t* image_index, uint32_t* bits, const int64_t* bits_offsets,
+                        int32_t* area, long long words) {
+  BitsOut c = {};
+  c.bits = bits; c.offsets = reinterpret_cast<const long long*>(bits_offsets); c.area = area;
+  c.frames = frames; c.image_index = image_index; c.P = P;
+  c.H = H; c.W = W; c.lds_words = (int)words; c.vec = 1;
+  return c;
+}
+}  // namespace
+
+extern "C" {
+
+int la3d_pack_rle_bits(const int32_t* counts, const int64_t* offsets, int B, int H, int W, int W_out, uint32_t* bits,
+                       int64_t bits_plane_stride, int32_t* area, void* stream) {
+  const int rc = ann_bits_check("la3d_pack_rle_bits", !counts || !offsets, B, H, W, W_out, bits, bits_plane_stride, area);
+  if (rc != LA3D_SUCCESS) return rc < 0 ? rc : LA3D_SUCCESS;
+  const BitsOut c = bits_out_uniform(H, W, W_out, bits, bits_plane_stride, area);
+  // (the block totals of the column scan, as in la3d_rle_decode: word-aligned rows only)
+  const int ntx = W_out / 32;
+  const int scan_words = (W_out % 32 == 0) ? ((NT_DEC / ntx > 2 ? NT_DEC / ntx : 2) * ntx) : 0;
+  const size_t lds = rle_bits_lds(c.lds_words, scan_words);
+  if (lds > ANN_LDS_MAX) return ann_lds_refuse("la3d_pack_rle_bits");
+  allow_big_lds(reinterpret_cast<const void*>(pack_rle_bits_kernel<false>));
+  hipLaunchKernelGGL(pack_rle_bits_kernel<false>, dim3(B), dim3(NT_DEC), lds, static_cast<hipStream_t>(stream), counts,
+                     reinterpret_cast<const long long*>(offsets), scan_words, c);
+  return check_launch("pack_rle_bits_kernel");
+}
+
+int la3d_pack_poly_bits(const int32_t* poly_xy, const int64_t* ring_offsets, const int64_t* inst_rings, int B, int H, int W, int W_out,
+                        uint32_t* bits, int64_t bits_plane_stride, int32_t* area, void* stream) {
+  const int rc = ann_bits_check("la3d_pack_poly_bits", !poly_xy || !ring_offsets || !inst_rings, B, H, W, W_out, bits, bits_plane_stride, area);
+  if (rc != LA3D_SUCCESS) return rc < 0 ? rc : LA3D_SUCCESS;
+  const BitsOut c = bits_out_uniform(H, W, W_out, bits, bits_plane_stride, area);
+  const size_t lds = poly_bits_lds(c.lds_words);
+  if (lds > ANN_LDS_MAX) return ann_lds_refuse("la3d_pack_poly_bits");
+  allow_big_lds(reinterpret_cast<const void*>(pack_poly_bits_kernel<false>));
+  hipLaunchKernelGGL(pack_poly_bits_kernel<false>, dim3(B), dim3(NT_DEC), lds, static_cast<hipStream_t>(stream), poly_xy,
+                     reinterpret_cast<const long long*>(ring_offsets), reinterpret_cast<const long long*>(inst_rings), c);
+  return check_launch("pack_poly_bits_kernel");
+}
+
+int la3d_pack_rle_bits_frames(const int32_t* counts, const int64_t* offsets, const la3d_frame* frames, int32_t P, int H, int W,
+                              const int32_t* image_index, int B, uint32_t* bits, const int64_t* bits_offsets, int32_t* area,
+                              void* stream) {
+  long long words = 0;
+  const int rc = ann_bits_frames_check("la3d_pack_rle_bits_frames", !counts || !offsets, frames, P, H, W, image_index, B, bits, bits_offsets,
+                                       area, &words);
+  if (rc != LA3D_SUCCESS) return rc < 0 ? rc : LA3D_SUCCESS;
+  const BitsOut c = bits_out_frames(frames, P, H, W, image_index, bits, bits_offsets, area, words);
+  // every frame of the call has at most (W + 31) / 32 words per row: room for two block rows of the widest, NT_DEC items otherwise
+  const int ntx = (W + 31) / 32;
+  const int scan_words = 2 * ntx > NT_DEC ? 2 * ntx : NT_DEC;
+  const size_t lds = rle_bits_lds(c.lds_words, scan_words);
+  if (lds > ANN_LDS_MAX) return ann_lds_refuse("la3d_pack_rle_bits_frames");
+  allow_big_lds(reinterpret_cast<const void*>(pack_rle_bits_kernel<true>));
+  hipLaunchKernelGGL(pack_rle_bits_kernel<true>, dim3(B), dim3(NT_DEC), lds, static_cast<hipStream_t>(stream), counts,
+                     reinterpret_cast<const long long*>(offsets), scan_words, c);
+  return check_launch("pack_rle_bits_frames_kernel");
+}
+
+int la3d_pack_poly_bits_frames(const int32_t* poly_xy, const int64_t* ring_offsets, const int64_t* inst_rings, const la3d_frame* frames,
+                               int32_t P, int H, int W, const int32_t* image_index, int B, uint32_t* bits, const int64_t* bits_offsets,
+                               int32_t* area, void* stream) {
+  long long words = 0;
+  const int rc = ann_bits_frames_check("la3d_pack_poly_bits_frames", !poly_xy || !ring_offsets || !inst_rings, frames, P, H, W, image_index, B,
+                                       bits, bits_offsets, area, &words);
+  if (rc != LA3D_SUCCESS) return rc < 0 ? rc : LA3D_SUCCESS;
+  const BitsOut c = bits_out_frames(frames, P, H, W, image_index, bits, bits_offsets, area, words);
+  const size_t lds = poly_bits_lds(c.lds_words);
+  if (lds > ANN_LDS_MAX) return ann_lds_refuse("la3d_pack_poly_bits_frames");
+  allow_big_lds(reinterpret_cast<const void*>(pack_poly_bits_kernel<true>));
+  hipLaunchKernelGGL(pack_poly_bits_kernel<true>, dim3(B), dim3(NT_DEC), lds, static_cast<hipStream_t>(stream), poly_xy,
+                     reinterpret_cast<const long long*>(ring_offsets), reinterpret_cast<const long long*>(inst_rings), c);
+  return check_launch("pack_poly_bits_frames_kernel");
 }
 
 }  // extern "C"

@@ -42,8 +42,11 @@ import torch
 from ._lib import lib, method_code
 from .batched import Depth16, _dev, _upload_many, draw_sample_idx, refuse_depth16
 from .jsonout import SceneRecords, format_scenes
-from .frames import PackedFrames, PackedFrames16, _table_fields, fit_instances_frames, frame_table, pack_rle_frames
-from .masks import fit_instances_ex, mask_stats_poly, mask_stats_rle, pack_polygons, pack_rle, pad_depth_rows, padded_width, area_hint_of, split_annotations
+from .frames import (PackedFrames, PackedFrames16, _table_fields, fit_instances_frames, frame_table, pack_poly_bits_frames, pack_rle_bits_frames,
+                     pack_rle_frames)
+from .masks import (area_hint_of, fit_instances_ex, mask_stats_poly, mask_stats_rle, pack_poly_bits, pack_polygons, pack_rle, pack_rle_bits,
+                    pad_depth_rows, padded_width, split_annotations)
+from .ply import write_ply
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 OUT_NAME = "3dbbox.json"
@@ -197,7 +200,7 @@ def _pinned_rows(key, rows, cols, dtype):
 
 
 class _Prepared:
-    __slots__ = ("scenes", "H", "W", "depth", "K", "groups", "ready", "h2d0", "parity", "t_pack", "t_load", "nbytes", "grounds")
+    __slots__ = ("scenes", "H", "W", "depth", "K", "groups", "ready", "h2d0", "parity", "t_pack", "t_load", "nbytes", "grounds", "clouds", "ply")
 
 
 def _group_annotations(scenes: List[dict]) -> dict:
@@ -222,7 +225,7 @@ class ScenePipeline:
     def __init__(self, device=None, batch_images: int = 256, subsample: bool = False, boundary_threshold: int = 10,
                  scale_threshold: int = 100, loader_threads: int = 16, write: bool = True, out_name: str = OUT_NAME, rng=None,
                  timings: Optional[dict] = None, method: str = "pca", mixed_frames: bool = False, depth_dtype: Optional[str] = None,
-                 depth_scale: float = 0.001, depth_zero_is_hole: bool = True):
+                 depth_scale: float = 0.001, depth_zero_is_hole: bool = True, export_points: bool = False, points_dir: str = "points"):
         """``method``: "pca" | "convex_hull" - the reference's ``bbox_method`` (save_3d_with_ground_alignment_bbox); see
         ``fit_instances`` for what the hull method covers in full-mask mode.  ``mixed_frames``: batches hold images of DIFFERENT
         sizes in arrival order, ``batch_images`` each, and every batch is one frames call per annotation kind
@@ -231,7 +234,15 @@ class ScenePipeline:
         ``np.float16`` / ``np.uint16`` (anything else: ValueError naming the scene) and stays 16-bit all the way - pinned staging,
         upload, device buffer, fit (``PackedFrames16`` in mixed mode, a padded ``Depth16`` otherwise): half the bytes over the host
         link, the records of the float32 pipeline on the up-converted planes.  ``depth_scale`` / ``depth_zero_is_hole``: the value
-        rule of uint16 planes (``Depth16``)."""
+        rule of uint16 planes (``Depth16``).  ``export_points``: also write one point cloud per record of the scene's ``3dbbox.json`` -
+        ``<scene dir>/<points_dir>/<obj_id>_<category name, spaces as underscores>.ply`` (``ply.write_ply``; the reference's
+        ``reconstruction/<id>_<category>.glb`` names), the FULL mask's cloud in the camera frame as float32, rows in NumPy's order,
+        rows with a non-finite coordinate dropped - also under ``subsample`` and with ground vectors.  Per batch and annotation kind
+        the masks are packed into bit planes once (``pack_rle_bits`` / ``pack_poly_bits``, their frames forms in ``mixed_frames``
+        mode) and gathered by ``instance_points[_frames]``.  The export is not free: the clouds of EVERY annotation of the batch are
+        gathered and downloaded (dropped and failed ones included; only the records' are written), and the download synchronises the
+        fitting thread, so the overlap of a batch's fit with the finishing of the previous one is lost while the flag is on.  Off (the
+        default): nothing the pipeline does or writes changes."""
         method_code(method)   # (the reference's error for an unknown method, before any device work)
         if depth_dtype is not None and depth_dtype not in DEPTH_DTYPES:
             raise ValueError(f"unknown depth_dtype: {depth_dtype!r}. Use None (float32), 'f16' or 'u16'")
@@ -250,6 +261,7 @@ class ScenePipeline:
         self.subsample = bool(subsample)
         self.flt = {"boundary_threshold": int(boundary_threshold), "scale_threshold": int(scale_threshold)}
         self.write, self.out_name, self.rng = write, out_name, rng
+        self.export_points, self.points_dir = bool(export_points), str(points_dir)
         self.pool = ThreadPoolExecutor(max_workers=max(1, loader_threads))
         self.copy_stream = torch.cuda.Stream(device=self.dev)
         self.t = timings if timings is not None else {}
@@ -493,7 +505,29 @@ class ScenePipeline:
             hb.copy_(boxes, non_blocking=True); hs.copy_(status, non_blocking=True)
             out[kind] = (hb, hs, g)
         e1.record(cur)
+        pr.clouds = self._clouds(pr, K) if self.export_points else None
         return out, e0, e1
+
+    def _clouds(self, pr: _Prepared, K):
+        """``export_points``: per annotation kind the clouds of the batch's instances on the host -> {kind: (points float32 (T,3),
+        offsets int64 (B+1,))}.  The bit planes are packed once per kind; the gather reads its total back and ``.cpu()`` waits for the
+        download: this thread is synchronised per kind, and every annotation's points move, whether a record comes of it or not."""
+        from .clouds import instance_points, instance_points_frames
+
+        H, W = pr.H, pr.W
+        out = {}
+        for kind, (up, g) in pr.groups.items():
+            ii = up[-2]
+            if self.mixed_frames:
+                fb = (pack_rle_bits_frames(pr.depth, (up[0], up[1]), ii) if kind == "rle"
+                      else pack_poly_bits_frames(pr.depth, (up[0], up[1], up[2], H, W), ii))
+                ip = instance_points_frames(pr.depth, fb, K, out_dtype=torch.float32)
+            else:
+                mb = (pack_rle_bits((up[0], up[1], H, W), device=self.dev) if kind == "rle"
+                      else pack_poly_bits((up[0], up[1], up[2], H, W), device=self.dev))
+                ip = instance_points(pr.depth, mb, K, image_index=ii, out_dtype=torch.float32)   # (on the device of the planes)
+            out[kind] = (ip.points.cpu().numpy(), ip.offsets.cpu().numpy())
+        return out
 
     def _second_phase(self, pr, results, K):
         H = pr.H
@@ -552,6 +586,7 @@ class ScenePipeline:
         kept rows in (image, annotation) order, the object id = index among the image's kept instances, category names through the
         unique ids.  No Python object per record (round 4: 0.112 s of a 0.223 s run went into building them)."""
         S = len(pr.scenes)
+        pr.ply = {}   # export_points: scene index -> [(file name, points)]
         recs, img, ann, st, cat = [], [], [], [], []
         for kind, (hb, hs, g) in out.items():
             recs.append(hb.numpy()); st.append(hs.numpy())
@@ -583,6 +618,16 @@ class ScenePipeline:
                 name_ids[n] = index.setdefault(nm, len(index))
             names = list(index)
         texts = format_scenes(R, rows, obj, name_ids, scene_off, names)
+        if pr.clouds is not None:   # export_points: one cloud per record - (scene, file name, finite rows of the full mask's cloud)
+            kinds = list(out)
+            base = np.cumsum([0] + [len(out[k][2]["seg"]) for k in kinds])
+            which = np.searchsorted(base, rows, side="right") - 1      # the kind of every record's row, and its row in that group
+            for n, r in enumerate(rows):
+                pts, off = pr.clouds[kinds[which[n]]]
+                k = int(r - base[which[n]])
+                cloud = pts[off[k]:off[k + 1]]
+                pr.ply.setdefault(int(img[r]), []).append((f"{int(obj[n])}_{names[name_ids[n]].replace(' ', '_')}.ply",
+                                                           cloud[np.isfinite(cloud).all(axis=1)]))
         counts = np.diff(scene_off)
         return [(sc, SceneRecords(texts[i], int(counts[i]))) for i, sc in enumerate(pr.scenes)]
 
@@ -590,6 +635,11 @@ class ScenePipeline:
         if self.write and "dir" in sc:
             with open(os.path.join(sc["dir"], self.out_name), "wb") as f:
                 f.write(recs.text)
+
+    def _write_ply(self, sc, name, points):
+        d = os.path.join(sc["dir"], self.points_dir)
+        os.makedirs(d, exist_ok=True)
+        write_ply(os.path.join(d, name), points)
 
     def _batches(self, scenes: Iterable[dict]) -> Iterator[List[dict]]:
         if self.mixed_frames:   # arrival order, whatever the sizes
@@ -647,10 +697,12 @@ class ScenePipeline:
                 self.t["images"] += len(ppr.scenes); self.t["batches"] += 1
                 self.t["instances"] += sum(len(g["seg"]) for _, _, g in out.values())
                 t0 = time.perf_counter()
-                for sc, recs in self._finish(ppr, out):
+                for p, (sc, recs) in enumerate(self._finish(ppr, out)):
                     self.t["boxes"] += len(recs)
                     if self.write and "dir" in sc:
                         writers.append(self.pool.submit(self._write, sc, recs))
+                        for name, points in ppr.ply.get(p, ()):   # (a scene's clouds go out with its json, before the scene is yielded)
+                            writers.append(self.pool.submit(self._write_ply, sc, name, points))
                     yield sc, recs
                 self.t["write_s"] += time.perf_counter() - t0
             inflight = nxt
@@ -763,6 +815,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="dtype of every depth_map.npy: f16 / u16 planes are uploaded and fitted as stored, never converted to float32")
     ap.add_argument("--depth-scale", type=float, default=0.001, help="u16 depth: metres per unit (default: millimetres)")
     ap.add_argument("--depth-keep-zero", action="store_true", help="u16 depth: a stored 0 is the valid depth 0.0 (default: a hole)")
+    ap.add_argument("--export-points", action="store_true", help="also write <scene>/<--points-dir>/<obj_id>_<category>.ply per record of "
+                    "3dbbox.json: the full mask's cloud in the camera frame (binary little-endian float32 x, y, z)")
+    ap.add_argument("--points-dir", default="points", help="--export-points: the folder inside every scene directory (default: points)")
     ap.add_argument("--bbox-method", choices=("pca", "convex_hull"), default="pca",
                     help="yaw estimator (the reference's bbox_method): principal axis, or the minimum-area rectangle over the hull edges")
     return ap
@@ -780,7 +835,8 @@ def main(argv=None) -> int:
     timings: dict = {}
     pipe = ScenePipeline(device=torch.device("cuda", args.gpu_idx), batch_images=args.batch_images, subsample=args.subsample, timings=timings,
                          method=args.bbox_method, mixed_frames=args.mixed_frames, depth_dtype=None if args.depth_dtype == "f32" else args.depth_dtype,
-                         depth_scale=args.depth_scale, depth_zero_is_hole=not args.depth_keep_zero)
+                         depth_scale=args.depth_scale, depth_zero_is_hole=not args.depth_keep_zero, export_points=args.export_points,
+                         points_dir=args.points_dir)
     t0 = time.perf_counter()
     n_scenes = n_boxes = 0
     for sc, recs in pipe.run(scenes_from_disk(args.scenes, ann, args.start_index, args.end_index, args.skip_done,

@@ -571,6 +571,95 @@ def pack_mask_bits_frames(masks, threshold: float = 0.0, stream=None, out=None) 
     return FrameBits(o, offs, pm.image_index, area, pm.table_host, pm.H, pm.W)
 
 
+# ---- annotations of images of different sizes as bit planes (include/la3d.h "annotations as bit planes") ---------------------------
+def _annotation_rows(who, frames, B: int, image_index, sizes=None):
+    """The argument errors of ``pack_rle_bits_frames`` / ``pack_poly_bits_frames``, before any device work -> (host image indices or
+    None for a device ``image_index``, the host plane offsets or None, the words of all planes)."""
+    if not isinstance(frames, (PackedFrames, PackedFrames16)):
+        raise ValueError(f"{who}: frames must be the PackedFrames / PackedFrames16 of pack_frames")
+    if image_index is None:
+        raise ValueError(f"{who}: image_index is required: instance n belongs to frame image_index[n]")
+    P = len(frames.sizes)
+    stride = (frames.H * frames.W // 32 + 3) // 4 * 4   # the words of the bounds' frame, rounded up to 16 bytes
+    if isinstance(image_index, torch.Tensor) and image_index.is_cuda:
+        if image_index.dim() != 1 or image_index.numel() != B:
+            raise ValueError(f"{who}: image_index must hold one image per annotation ({B}), got {tuple(image_index.shape)}")
+        return None, None, B * stride
+    ii = np.asarray(image_index.numpy() if isinstance(image_index, torch.Tensor) else image_index).reshape(-1)
+    if len(ii) != B:
+        raise ValueError(f"{who}: image_index must hold one image per annotation ({B}), got {len(ii)}")
+    if B and not np.issubdtype(ii.dtype, np.integer):
+        raise ValueError(f"{who}: image_index must be integers")
+    ii = ii.astype(np.int64)
+    if B and (int(ii.min()) < 0 or int(ii.max()) >= P):
+        raise ValueError(f"{who}: image_index must lie in [0, {P})")
+    if sizes is not None and B and (sizes != np.asarray(frames.sizes, np.int64).reshape(-1, 2)[ii]).any():
+        raise ValueError("an RLE annotation's size differs from the size of its image")
+    offs, total = frame_bits_offsets(frames.table_host, ii)
+    return ii, offs, total
+
+
+def _pack_annotation_bits_frames(entry, name, frames, arrays, B, image_index, ii_h, offs_h, total, stream, out) -> FrameBits:
+    """The device step the two annotation packers share: the small arrays up in one copy, the planes' buffers, the call."""
+    if not (isinstance(frames.table, torch.Tensor) and frames.table.is_cuda):
+        raise ValueError("the frame table must live on the GPU (pack_frames with a GPU device)")
+    dev = frames.table.device
+    P = len(frames.sizes)
+    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev):
+        raise ValueError("out must be a flat int32 tensor on the device of the frame table")
+    with torch.cuda.device(dev):
+        if out is not None:
+            _bits_buffers(out, total, 0, dev)   # (its argument errors, before anything is uploaded)
+        resident = all(isinstance(a, torch.Tensor) and a.is_cuda for a, _ in arrays)   # annotation arrays that are on a GPU already
+        if resident:
+            ann = [_as_dev(a, dt, dev) for a, dt in arrays]
+            ii, offs = (None, None) if ii_h is None else _upload_many([(ii_h, torch.int32), (offs_h, torch.int64)], dev)
+        elif ii_h is not None:
+            *ann, ii, offs = _upload_many(arrays + [(ii_h, torch.int32), (offs_h, torch.int64)], dev)
+        else:
+            ann = _upload_many(arrays, dev)
+        if ii_h is None:
+            ii = _as_dev(image_index, torch.int32, dev)
+            offs = torch.arange(B, dtype=torch.int64, device=dev) * (total // B if B else 0)
+        o, area = _bits_buffers(out, total, B, dev)
+        check(entry(*[_ptr(a) for a in ann], _ptr(frames.table), P, frames.H, frames.W, _ptr(ii), B, _ptr(o), _ptr(offs), _ptr(area),
+                    _stream(stream)), name)
+    _record(stream, frames.table, *ann, ii, offs, o, area)
+    return FrameBits(o, offs, ii, area, frames.table_host, frames.H, frames.W)
+
+
+def pack_rle_bits_frames(frames, rles, image_index, stream=None, out=None) -> FrameBits:
+    """COCO run lengths of images of DIFFERENT sizes -> ``FrameBits`` (C-ABI ``la3d_pack_rle_bits_frames``): one launch decodes every
+    annotation into the bit plane of its image's OWN frame - ``H_p * padded_width(W_p) / 32`` words, the bits of the padding columns
+    zero -, what ``instance_points_frames`` and ``fit_instances_frames_bits`` take.  ``frames``: a ``PackedFrames`` /
+    ``PackedFrames16`` (only its table, bounds and sizes are used); ``rles``: a list of COCO RLE objects, each of its own image's size
+    (another stated size: ValueError), or a ``(counts, offsets)`` tuple; instance n belongs to image ``image_index[n]``.  Host
+    ``image_index``: the planes are laid out by ``frame_bits_offsets`` and the small arrays go up in ONE copy.  Device
+    ``image_index``: no synchronisation - the planes lie a uniform stride apart, the words of the bounds' frame rounded up to 4, and the
+    stated sizes are NOT compared with the images' (which image a row belongs to is unknown here without reading the index back): the
+    runs are then decoded over the image's own frame, whatever the annotation states.
+    ``out``: as in ``pack_label_bits_frames``.  An instance whose image index or frame row breaks the contract gets no plane and
+    area 0 - decided on the device."""
+    counts, offsets, sizes = pack_rle_frames(rles)
+    B = len(offsets) - 1
+    ii_h, offs_h, total = _annotation_rows("pack_rle_bits_frames", frames, B, image_index, sizes)
+    return _pack_annotation_bits_frames(lib.la3d_pack_rle_bits_frames, "la3d_pack_rle_bits_frames", frames,
+                                        [(counts, torch.int32), (offsets, torch.int64)], B, image_index, ii_h, offs_h, total, stream, out)
+
+
+def pack_poly_bits_frames(frames, polys, image_index, stream=None, out=None) -> FrameBits:
+    """Polygon parts of images of DIFFERENT sizes -> ``FrameBits`` (C-ABI ``la3d_pack_poly_bits_frames``): ``polys`` is the tuple of
+    ``pack_polygons`` (its H, W are ignored: every instance is clipped to its own frame).  Other arguments and the result as
+    ``pack_rle_bits_frames``."""
+    if not (isinstance(polys, tuple) and len(polys) == 5):
+        raise ValueError("polys must be the (xy, ring_offsets, inst_rings, H, W) tuple of pack_polygons")
+    B = len(polys[2]) - 1
+    ii_h, offs_h, total = _annotation_rows("pack_poly_bits_frames", frames, B, image_index)
+    return _pack_annotation_bits_frames(lib.la3d_pack_poly_bits_frames, "la3d_pack_poly_bits_frames", frames,
+                                        [(polys[0], torch.int32), (polys[1], torch.int64), (polys[2], torch.int64)], B, image_index, ii_h,
+                                        offs_h, total, stream, out)
+
+
 def fit_instances_frames_masks(frames, masks, K, threshold: float = 0.0, image_index=None, ground=None, sample_idx=None, filter=None,
                                proj: bool = False, height_rule: str = "rows", stream=None, method: str = "pca"):
     """The depth + mask fit of the per-image mask / logit stacks of an instance-segmentation network, images of DIFFERENT sizes, in

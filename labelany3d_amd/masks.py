@@ -24,6 +24,7 @@ call; images of different sizes (``pack_frames``, ``fit_instances_frames*``) liv
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import itertools
 import threading
@@ -640,6 +641,81 @@ def pack_logits_bits(logits, threshold: float = 0.0, frame_pad: bool = True, dev
     return MaskBits(o, H, W_out, W)
 
 
+def _annotation_bits_plan(who, B, H, W, frame_pad, device, out, area):
+    """The argument errors of ``pack_rle_bits`` / ``pack_poly_bits`` that need no device -> (W_out, the plane stride of ``out`` or None,
+    the device to ask for).  ``out`` is checked ONCE, here: at small batches the packers are bound by what this wrapper costs."""
+    if B and (H <= 0 or W <= 0):
+        raise ValueError(f"{who}: the annotations state an empty frame {(H, W)}")
+    W_out = padded_width(W) if frame_pad else W
+    stride = None if out is None else _bits_stride(out, B, H, W_out)
+    if area is not None and not (isinstance(area, torch.Tensor) and area.is_cuda and area.dtype == torch.int32 and area.dim() == 1
+                                 and area.numel() == B and area.is_contiguous()):
+        raise ValueError(f"{who}: area must be a contiguous int32 ({B},) tensor on the GPU")
+    where = out.device if out is not None else area.device if area is not None else None
+    if where is not None:
+        d = where if device is None else torch.device(device)   # ("cuda" without an index names whichever GPU the tensors are on)
+        if (area is not None and area.device != where) or d.type != where.type or (d.index is not None and d.index != where.index):
+            raise ValueError(f"{who}: out / area live on another device")
+    return W_out, stride, where if where is not None else device
+
+
+class _PackedBits(MaskBits):
+    """The ``MaskBits`` a packer of annotations returns: it has just checked and filled the planes, so ``_stride`` - their plane
+    stride in words - rides along and a consumer (``instance_points``) need not check the tensor again.  A tuple like any
+    ``MaskBits``; ``_replace`` gives one without the attribute, which is checked as usual."""
+
+
+def _pack_annotation_bits(entry, name, arrays, B, H, W, frame_pad, device, stream, out, area) -> MaskBits:
+    """What ``pack_rle_bits`` / ``pack_poly_bits`` share: the checks, the planes, the annotation arrays (resident tensors as they are,
+    host arrays in one copy), the call.  At small batches the call costs what this wrapper costs: nothing is checked twice, and the
+    device context is entered only when another device is current."""
+    W_out, stride, device = _annotation_bits_plan(name[5:], B, H, W, frame_pad, device, out, area)
+    dev = device if isinstance(device, torch.device) else _dev(device)
+    if out is None:
+        stride = (H * W_out + 31) // 32
+        out = torch.empty((B, stride), dtype=torch.int32, device=dev)
+    if B:
+        # (the device context costs ~1.5 us of the ~12 us this call costs at small batches: entered only when another device is current)
+        with contextlib.nullcontext() if torch.cuda.current_device() == dev.index else torch.cuda.device(dev):
+            ann = []
+            for a, dt in arrays:   # (resident arrays of the right dtype are taken as they are)
+                if not (isinstance(a, torch.Tensor) and a.dtype == dt and a.device == dev and a.is_contiguous()):
+                    ann = None
+                    break
+                ann.append(a)
+            if ann is None:
+                ann = ([_as_dev(a, dt, dev) for a, dt in arrays] if any(isinstance(a, torch.Tensor) for a, _ in arrays)
+                       else _upload_many(arrays, dev))
+            # (plain integers: the entries' pointer arguments are c_void_p)
+            check(entry(*[a.data_ptr() for a in ann], B, H, W, W_out, out.data_ptr(), stride, None if area is None else area.data_ptr(),
+                        _stream(stream)), name)
+        _record(stream, *ann, out, area)
+    mb = _PackedBits(out, H, W_out, W)
+    mb._stride = stride
+    return mb
+
+
+def pack_rle_bits(rles, frame_pad: bool = True, device=None, stream=None, out=None, area=None) -> MaskBits:
+    """COCO run lengths (a list of RLE objects or the tuple of ``pack_rle``) -> ``MaskBits`` on the GPU (C-ABI ``la3d_pack_rle_bits``):
+    ``rle_decode`` with the bit image kept - an eighth of the bytes of the boolean planes, what ``instance_points``,
+    ``mask_stats_bits``, ``unpack_mask_bits`` and ``fit_instances_bits`` take.  ``frame_pad`` / ``out`` as in ``pack_mask_bits``;
+    ``area``: an int32 (B,) device tensor that receives the popcount of every plane (what ``area_hint`` takes).  A negative count is
+    a run of length 0, runs past the frame are cut."""
+    counts, offsets, H, W = pack_rle(rles)
+    return _pack_annotation_bits(lib.la3d_pack_rle_bits, "la3d_pack_rle_bits", [(counts, torch.int32), (offsets, torch.int64)],
+                                 len(offsets) - 1, H, W, frame_pad, device, stream, out, area)
+
+
+def pack_poly_bits(polys, frame_pad: bool = True, device=None, stream=None, out=None, area=None) -> MaskBits:
+    """Polygon parts (the tuple of ``pack_polygons``) -> ``MaskBits`` on the GPU (C-ABI ``la3d_pack_poly_bits``): ``poly_decode``
+    with the bit image kept.  Other arguments as ``pack_rle_bits``."""
+    if not (isinstance(polys, tuple) and len(polys) == 5):
+        raise ValueError("polys must be the (xy, ring_offsets, inst_rings, H, W) tuple of pack_polygons")
+    return _pack_annotation_bits(lib.la3d_pack_poly_bits, "la3d_pack_poly_bits",
+                                 [(polys[0], torch.int32), (polys[1], torch.int64), (polys[2], torch.int64)], len(polys[2]) - 1,
+                                 int(polys[3]), int(polys[4]), frame_pad, device, stream, out, area)
+
+
 def unpack_mask_bits(bits, stream=None) -> torch.Tensor:
     """``MaskBits`` -> (B,H,frame_width) bool masks on the GPU (C-ABI ``la3d_unpack_mask_bits``)."""
     mb = _mask_bits(bits)
@@ -960,4 +1036,5 @@ def masked_ratio_median(depth_map, depth_render, mask, render_mask=None, image_i
 # the mixed-size ("frames") layer: its public names stay importable from here (last on purpose: frames imports from this module)
 from .frames import (FRAME_DTYPE, MASKS_U8, FrameBits, PackedFrames, PackedFrames16, PackedLabels, PackedMasks, fit_instances_frames,  # noqa: E402,F401
                      fit_instances_frames_bits, fit_instances_frames_labels, fit_instances_frames_masks, frame_bits_offsets, frame_table,
-                     pack_frames, pack_label_bits_frames, pack_label_frames, pack_mask_bits_frames, pack_mask_frames, pack_rle_frames)
+                     pack_frames, pack_label_bits_frames, pack_label_frames, pack_mask_bits_frames, pack_mask_frames, pack_poly_bits_frames,
+                     pack_rle_bits_frames, pack_rle_frames)
