@@ -1,7 +1,7 @@
 """The randomised differential campaign over the format converters in front of the fit: the mask, logit and label packers
 (pack_bits_vec_kernel / pack_bits_kernel, pack_labels_vec_kernel / pack_labels_kernel, pack_labels_frames_vec_kernel /
 pack_labels_frames_rgb8_kernel, pack_masks_frames_kernel, unpack_mask_bits_kernel, mask_stats_bits_kernel: labelany3d_amd/csrc/
-la3d_masks.hip) and the 16-bit depth packers (pack_depth16_kernel / unpack_depth16_kernel: la3d_depth16.hip) - case generator, oracle,
+la3d_bits.hip) and the 16-bit depth packers (pack_depth16_kernel / unpack_depth16_kernel: la3d_depth16.hip) - case generator, oracle,
 GPU runs and the checker.  profiles/formats/fuzz_formats.py drives it at scale; tests/test_gpu_differential.py runs a committed slice of
 its seeds (tests/campaign_slices.py::FORMAT_SEEDS).
 
@@ -60,7 +60,7 @@ import numpy as np
 from .clouds import SCALES, quantise, upconvert
 
 LANES = 256            # lanes of a workgroup of every packer
-CHUNKS = 64            # plane_chunks: workgroups per plane (la3d_masks.hip)
+CHUNKS = 64            # plane_chunks: workgroups per plane (la3d_bits.hip)
 GROUP_BYTES = 16       # pack_bits_vec_kernel: bytes a lane loads
 GRID = 16384           # grid_for: workgroups of the depth packers (la3d_depth16.hip)
 DEPTH_GROUP = 8        # pack_depth16_kernel: output pixels of a lane

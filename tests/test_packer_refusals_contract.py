@@ -1,0 +1,50 @@
+"""CPU-only contract of the argument checks of the bit-plane entries (labelany3d_amd/csrc/la3d_bits.hip: one check routine for all of
+them): every refusal keeps its return code, its message byte for byte, and its rank among the other refusals of its entry.  The
+expectations (tests/golden/packer_refusals.json) were recorded with tests/packer_refusal_cases.py from the library of the commit
+BEFORE the checks were folded into one routine; they are data, never regenerated from the tree under test."""
+import json
+import os
+
+from . import packer_refusal_cases as RC
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "packer_refusals.json")
+PACKERS = ("la3d_pack_mask_bits", "la3d_pack_logits_bits", "la3d_unpack_mask_bits", "la3d_mask_stats_bits", "la3d_pack_rle_bits",
+           "la3d_pack_poly_bits", "la3d_pack_rle_bits_frames", "la3d_pack_poly_bits_frames", "la3d_pack_label_bits",
+           "la3d_pack_label_bits_frames", "la3d_pack_mask_bits_frames", "la3d_pack_logits_bits_frames")
+ERR_ARG, ERR_UNSUPPORTED = -1, -2          # (LA3D_ERR_HIP = -3 would mean that a case reached a launch)
+
+
+def _want():
+    return json.load(open(GOLDEN))["cases"]
+
+
+def test_every_refusal_is_the_recorded_one():
+    from labelany3d_amd import _lib
+
+    got, want = RC.run(_lib.lib), _want()
+    assert [g[:2] for g in got] == [w[:2] for w in want]                     # the same cases, in the same order
+    wrong = [(g, w) for g, w in zip(got, want) if g != w]
+    assert not wrong, wrong[:5]
+
+
+def test_the_fixture_covers_every_entry_and_every_kind_of_refusal():
+    want = _want()
+    by = {}
+    for entry, case, rc, msg in want:
+        by.setdefault(entry, []).append((case, rc, msg))
+        assert rc in (0, ERR_ARG, ERR_UNSUPPORTED), (entry, case, rc)          # refused or nothing to do: no case reached a launch
+        assert (rc == 0) == (msg == "") and (rc == 0 or msg.startswith(entry + ": ")), (entry, case, msg)
+    assert set(PACKERS) <= set(by) and len(by) == len(PACKERS) + 2              # (+ la3d_rle_decode / la3d_poly_decode: the same unit)
+    for entry in PACKERS:
+        cases = {c: (rc, msg) for c, rc, msg in by[entry]}
+        assert cases["B=-1"][0] == cases["H=0"][0] == cases["W=0"][0] == ERR_ARG, entry
+        assert cases["B=0"][0] == 0, entry
+        assert any(c.endswith("=NULL") and rc == ERR_ARG for c, (rc, _) in cases.items()), entry
+        assert any(c.endswith("misaligned") and rc == ERR_ARG for c, (rc, _) in cases.items()), entry
+    # the pairs whose precedence the older contract tests pin
+    for entry in ("la3d_pack_mask_bits", "la3d_pack_label_bits", "la3d_pack_label_bits_frames", "la3d_pack_mask_bits_frames"):
+        rc, msg = {c: (rc, msg) for c, rc, msg in by[entry]}["too large before B=0"]
+        assert rc == ERR_ARG and "too large" in msg, entry
+    for entry in ("la3d_pack_rle_bits", "la3d_pack_poly_bits"):
+        rc, msg = {c: (rc, msg) for c, rc, msg in by[entry]}["LDS bound before short stride"]
+        assert rc == ERR_UNSUPPORTED and "must fit LDS" in msg, entry
