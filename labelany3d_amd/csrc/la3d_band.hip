@@ -140,15 +140,7 @@ __device__ inline void band_moments_to_axis(Shared* sh, const FitParams& p, int 
   if (sh->redo) return;   // uniform
   // rejected instance: band 0 writes the outputs, every band returns (a band that took the instance over after a watchdog
   // timeout writes them itself: band_takeover)
-  if (tid == 0 && h == 0 && sh->st != LA3D_BOX_OK && sh->st < BAND_ST_TAKEOVER) {
-    if (p.aux) {
-      double* a = p.aux + (long long)inst * LA3D_AUX;
-      a[0] = atan2(sh->syaw, sh->cyaw); a[1] = (double)sh->n_valid; a[2] = (double)sh->nm; a[3] = sh->gap;
-    }
-    p.status[inst] = sh->st;
-    write_nan_box(p.out + (long long)inst * LA3D_REC);
-    if (p.proj) { for (int j = 0; j < 8; ++j) p.proj[(long long)inst * 8 + j] = NAN; }
-  }
+  if (tid == 0 && h == 0 && sh->st != LA3D_BOX_OK && sh->st < BAND_ST_TAKEOVER) write_no_box_axis(sh, p, inst);
 }
 
 // Watchdog fallback of the band engine (round 5; ADVICE / VERDICT round 4: a timeout used to drop a fittable box as

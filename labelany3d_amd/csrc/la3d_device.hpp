@@ -677,6 +677,29 @@ struct alignas(16) Shared {
 // include/la3d.h states the tile list of a hull call in bytes (752 behind the bit image); oracle/campaigns/hull.py restates it
 static_assert(sizeof(Shared) == 752, "include/la3d.h (convex-hull yaw, rule 2) and oracle/campaigns/hull.py state this size");
 #endif
+// An instance that gets no box: aux, status, the all-NaN record and - where the call asks for them - the all-NaN 2-D boxes.  ONE
+// thread writes them.  write_no_box: the instance was refused or dropped before any axis existed - aux = (NaN, n_valid, nm, NaN),
+// where the callers that have counted nothing pass n_valid = 0 and the mask's area, or NaN, for nm.
+__device__ inline void write_no_box(const FitParams& p, int inst, int status, double n_valid, double nm) {
+  if (p.aux) {
+    double* a = p.aux + (long long)inst * LA3D_AUX;
+    a[0] = NAN; a[1] = n_valid; a[2] = nm; a[3] = NAN;
+  }
+  p.status[inst] = status;
+  write_nan_box(p.out + (long long)inst * LA3D_REC);
+  if (p.proj) { for (int j = 0; j < 8; ++j) p.proj[(long long)inst * 8 + j] = NAN; }
+}
+// write_no_box_axis: the axis stage rejected the instance (sh->st) - aux = what the stage left in Shared
+__device__ inline void write_no_box_axis(const Shared* sh, const FitParams& p, int inst) {
+  if (p.aux) {
+    double* a = p.aux + (long long)inst * LA3D_AUX;
+    a[0] = atan2(sh->syaw, sh->cyaw); a[1] = (double)sh->n_valid; a[2] = (double)sh->nm; a[3] = sh->gap;
+  }
+  p.status[inst] = sh->st;
+  write_nan_box(p.out + (long long)inst * LA3D_REC);
+  if (p.proj) { for (int j = 0; j < 8; ++j) p.proj[(long long)inst * 8 + j] = NAN; }
+}
+
 #ifdef LA3D_TIMELINE
 #define LA3D_SUBSTAMP(sh, k) do { if (threadIdx.x == 0 && (sh)->tl) (sh)->tl[k] = (double)wall_clock64(); } while (0)
 #else

@@ -26,7 +26,7 @@ int instance_fit(FitParams p, const CallFacts& f, hipStream_t s, void* workspace
 // uint16 x scale elements; la3d_fit_instances_depth16)
 int instance_fit_f16(FitParams16 p, const CallFacts& f, hipStream_t s, void* workspace, const char* who);
 int instance_fit_u16(FitParams16 p, const CallFacts& f, hipStream_t s, void* workspace, const char* who);
-// the launches behind the fit kernel of a hull call, which read no depth (la3d_instance.hip, shared by its 16-bit forms)
+// the launches behind the fit kernel of a hull call, which read no depth (la3d_hull_finish.hip: one unit, shared by the three instance units)
 int hull_finish_launch(const FitParams& p, bool sample, hipStream_t s);
 int hull_refuse_launch(const FitParams& p, hipStream_t s);
 // band engine (la3d_band.hip): two / four / eight workgroups per instance that meet through the workspace

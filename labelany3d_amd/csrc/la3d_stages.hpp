@@ -76,15 +76,7 @@ __device__ inline void stage_moments_to_axis(Shared* sh, const FitParams& p, int
   LA3D_SUBSTAMP(sh, 10);
   __syncthreads();
   if (sh->redo) return;  // uniform
-  if (tid == 0 && sh->st != LA3D_BOX_OK) {  // rejected instance: the workgroup returns right after this call
-    if (p.aux) {
-      double* a = p.aux + (long long)inst * LA3D_AUX;
-      a[0] = atan2(sh->syaw, sh->cyaw); a[1] = (double)sh->n_valid; a[2] = (double)sh->nm; a[3] = sh->gap;
-    }
-    p.status[inst] = sh->st;
-    write_nan_box(p.out + (long long)inst * LA3D_REC);
-    if (p.proj) { for (int j = 0; j < 8; ++j) p.proj[(long long)inst * 8 + j] = NAN; }
-  }
+  if (tid == 0 && sh->st != LA3D_BOX_OK) write_no_box_axis(sh, p, inst);  // rejected instance: the workgroup returns right after this call
 }
 
 // status and aux record of an accepted instance: written at the very end by lane 0 of wave 1, next to wave 0 writing the
