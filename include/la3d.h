@@ -692,6 +692,66 @@ int la3d_align_select_batch(const float* relative, const float* metric, const ui
                             float max_valid_depth, float* relative_out, float* metric_out, int64_t* counts, void* workspace,
                             void* stream);
 
+/* ---- depth alignment: RANSAC scale fit ---------------------------------------------------------------------------
+ * The estimator between la3d_align_select_batch and the prediction scatter, for P frames in ONE call and without any host
+ * synchronisation: scikit-learn's RANSACRegressor(LinearRegression(fit_intercept=False), min_samples=...) as align_depth calls it
+ * (reference src/batch_scripts/depth.py:66-78) - the model y = a x with a median-based threshold.  Per frame, on the compacted float32
+ * samples x = relative_sel[p][0 .. counts[p]), y = metric_sel[p][...]:
+ *   m     = ceil(min_samples * n) in float64 for 0 < min_samples < 1, min_samples for an integer >= 1; m < 1 or m > n fails the fit
+ *   thr   = median(|y - median(y)|), both medians as np.median of float32 data (an even count averages the middle values in float32)
+ *   trial t with its subset of m sample indices: a_t = float32(sum xy / sum xx), sums in float64 (sum xx == 0: a_t = 0);
+ *           pred = float32(x * a_t) for every sample (one rounded product), inliers |y - pred| <= thr in float32, k_t their number,
+ *           score_t = R^2 over the inliers in float64 (fewer than two inliers: NaN; zero total variance: 1 if the residuals are 0, else 0)
+ *   rule    scikit-learn's loop: k_best = 1, score_best = -inf; trial t is skipped if k_t < k_best or (k_t == k_best and score_t <
+ *           score_best; a NaN compares false); otherwise it becomes the best and max_trials = min(max_trials, dynamic) with
+ *           scikit-learn's _dynamic_max_trials(k_best, n, m, stop_probability) in float64; n_trials = trials looked at
+ *   coef  = float32(sum xy / sum xx) over the inliers of the best trial, sums in float64
+ *   status  0 fitted; 1 no sample (counts[p] == 0); 2 the fit failed - a non-finite sample, m outside [1, n] (or beyond m_cap), a subset
+ *           index outside [0, n), counts[p] outside [0, n], no accepted trial: where the reference returns the metric depth.  coef is
+ *           NaN, n_inliers 0 and best_trial -1 for a status other than 0.
+ * Subsets: `subsets` dev i32 [P][max_trials][m_cap] - frame p, trial t uses the first m of its row (for a seeded scikit-learn draw made
+ * on the host) -, or NULL: the kernels draw them from `seed`, counter-based and keyed by (seed, frame, trial): m DISTINCT indices per
+ * trial (a keyed bijection of [0, n)).  The device draw is NOT NumPy's stream; la3d_align_ransac_subsets writes the subsets a seed
+ * gives (rows padded with -1 behind m), and a fit fed those equals the seeded fit bit for bit.
+ * A call is six launches on `stream`, allocates nothing and reads nothing back; every sum is merged in a fixed order, so a call is
+ * reproducible run to run and a frame's result does not depend on the other frames of the batch.
+ * workspace: la3d_align_ransac_workspace_bytes(P, n, max_trials) bytes, 16-byte aligned.
+ * LA3D_ERR_ARG before any launch: a bad struct_size, negative P or n, max_trials < 1, min_samples <= 0 or a non-integer >= 1,
+ *   stop_probability outside [0, 1], subsets with m_cap < 1, NULL or misaligned pointers with work to do.  LA3D_ERR_UNSUPPORTED:
+ *   n > LA3D_ALIGN_RANSAC_MAX_N, max_trials > LA3D_ALIGN_RANSAC_MAX_TRIALS, P > 65535.
+ * la3d_align_apply_batch: out[p] = full(fill); out[p][sel] = float32(relative[p] * coef[p]) with sel = mask when given, else
+ * ~isinf(relative) - the expression of la3d_align_apply with a zero intercept, coef and status read from the device; a frame whose
+ * status is not 0 gets metric[p] copied. */
+#define LA3D_ALIGN_RANSAC_MAX_N (1 << 24)
+#define LA3D_ALIGN_RANSAC_MAX_TRIALS 1024
+typedef struct la3d_align_ransac_args {
+  int32_t struct_size;        /* sizeof(la3d_align_ransac_args) of the caller */
+  int32_t P;                  /* frames */
+  int64_t n;                  /* samples a row holds (frames are n apart) */
+  const float* relative_sel;  /* dev f32 [P][n] */
+  const float* metric_sel;    /* dev f32 [P][n] */
+  const int64_t* counts;      /* dev i64 [P] */
+  double min_samples;
+  double stop_probability;    /* 0.99 in scikit-learn */
+  int32_t max_trials;         /* 100 in scikit-learn */
+  int32_t m_cap;              /* columns of a subsets row */
+  const int32_t* subsets;     /* dev i32 [P][max_trials][m_cap] | NULL: drawn on the device from seed */
+  uint64_t seed;
+  float* coef;                /* dev f32 [P] */
+  int32_t* n_inliers;         /* dev i32 [P] */
+  int32_t* n_trials;          /* dev i32 [P] */
+  int32_t* best_trial;        /* dev i32 [P] */
+  int32_t* status;            /* dev i32 [P] */
+  void* workspace;
+  void* stream;
+} la3d_align_ransac_args;
+size_t la3d_align_ransac_workspace_bytes(int P, int64_t n, int max_trials);
+int la3d_align_ransac_batch(const la3d_align_ransac_args* args);
+int la3d_align_ransac_subsets(const int64_t* counts, int P, double min_samples, int max_trials, uint64_t seed, int32_t* subsets,
+                              int m_cap, void* stream);
+int la3d_align_apply_batch(const float* relative, const float* metric, const uint8_t* mask, int P, int64_t n, const float* coef,
+                           const int32_t* status, float fill, float* out, void* stream);
+
 /* ---- sparse unprojection at match points -------------------------------------------------------
  * Reference src/matching/matcher.py:70-91: depth dev f32 [H][W] looked up at (int(v), int(u)) of each match
  * uv dev f64 [N][2]; matches whose depth is -1 (or that fall outside the frame) get valid = 0 and NaNs;

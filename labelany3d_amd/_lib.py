@@ -63,7 +63,20 @@ class CloudArgs(C.Structure):
                 ("capacity", C.c_int64), ("workspace", C.c_void_p), ("stream", C.c_void_p)]
 
 
-CLOUD_OK, CLOUD_NO_ROOM, CLOUD_MISMATCH = 0, 1, 2   # status of la3d_gather_instance_points (5 = BOX_UNSUPPORTED: a refused frames row)
+class AlignRansacArgs(C.Structure):
+    """``la3d_align_ransac_args`` of include/la3d.h (argument block of la3d_align_ransac_batch, 136 bytes); field order is the header's."""
+    _fields_ = [("struct_size", C.c_int32), ("P", C.c_int32), ("n", C.c_int64),
+                ("relative_sel", C.c_void_p), ("metric_sel", C.c_void_p), ("counts", C.c_void_p),
+                ("min_samples", C.c_double), ("stop_probability", C.c_double),
+                ("max_trials", C.c_int32), ("m_cap", C.c_int32), ("subsets", C.c_void_p), ("seed", C.c_uint64),
+                ("coef", C.c_void_p), ("n_inliers", C.c_void_p), ("n_trials", C.c_void_p), ("best_trial", C.c_void_p),
+                ("status", C.c_void_p), ("workspace", C.c_void_p), ("stream", C.c_void_p)]
+
+
+ALIGN_OK, ALIGN_EMPTY, ALIGN_FAILED = 0, 1, 2       # status of la3d_align_ransac_batch
+ALIGN_RANSAC_MAX_N, ALIGN_RANSAC_MAX_TRIALS = 1 << 24, 1024
+
+CLOUD_OK, CLOUD_NO_ROOM, CLOUD_MISMATCH = 0, 1, 2  # status of la3d_gather_instance_points (5 = BOX_UNSUPPORTED: a refused frames row)
 
 _SIGS = {
     "la3d_instance_points_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
@@ -143,6 +156,11 @@ _SIGS = {
     "la3d_align_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "la3d_align_select_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "la3d_align_ransac_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
+    "la3d_align_ransac_batch": (C.c_int, [C.POINTER(AlignRansacArgs)]),
+    "la3d_align_ransac_subsets": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p]),
+    "la3d_align_apply_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_float,
+                                         C.c_void_p, C.c_void_p]),
     "la3d_unproject_matches": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double,
                                          C.c_double, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
