@@ -645,6 +645,48 @@ int la3d_pack_poly_bits_frames(const int32_t* poly_xy, const int64_t* ring_offse
                                int32_t P, int H, int W /* bounds */, const int32_t* image_index /* dev [B] */, int B, uint32_t* bits,
                                const int64_t* bits_offsets /* dev [B] */, int32_t* area /* dev [B] or NULL */, void* stream);
 
+/* ---- crop-space masks as bit planes ------------------------------------------------------------------------------------
+ * restore_mask_from_crop for a batch (reference src/util.py:171-214; the box stage calls it per object, src/batch_scripts/
+ * whole.py:72-105): the S x S mask of a crop - or the alpha channel of its RGBA image, thresholded - resized by nearest index to
+ * side x side pixels and pasted, clipped, into a full frame; written as the planes of "masks as bit planes", never as a u8 plane.
+ *
+ * SOURCE.  Byte (y, x) of crop n lies at crops + n*crop_stride + y*row_pitch + x*pixel_step (all in BYTES): a dense u8 / bool mask is
+ *   (S*S, S, 1); the alpha of dense RGBA crops is crops = base + 3 with (4*S*S, 4*S, 4).  bit = byte > threshold (0 for masks, 127
+ *   for alpha: whole.py:83).
+ * place dev i32 [B][4], 4-byte aligned: x1, y1, side, 0 (the fourth is not read).  The HOST computes them, in float64 as the
+ *   reference does: side = int(S / scale_factor) (truncated), x1 = int(round(offset_x)), y1 = int(round(offset_y)) with Python's
+ *   round (half to even).
+ * VALUE.  Bit (v, u) of plane n is 0 unless x1 <= u < x1 + side, y1 <= v < y1 + side, u < W and v < H; there it is
+ *   crop[sy][sx] > threshold with sx = min(floor((u - x1) * ifx), S - 1), sy likewise, ifx = 1.0 / ((double)side / (double)S) - one
+ *   float64 multiply, then floor: the index rule of OpenCV's INTER_NEAREST resize (resizeNN, inv_scale = dsize / ssize).
+ * TWO CASES DIFFER FROM THE REFERENCE, both give an all-zero plane and area 0 (LA3D_BOX_EMPTY in the fit), never an error of the call:
+ *   side <= 0 (cv2.resize raises there), and a placement wholly outside the frame (the reference's slice assignment raises a
+ *   broadcast ValueError in most such cases and pastes nothing in the rest).
+ * ADDRESSING.  place is read on the device and checked before an address is formed from it: side must lie in (0, 2^20] - a larger
+ *   side is treated like side <= 0: an all-zero plane -, x1 and y1 may be any int32 (the differences are taken in 64 bits).  A row with
+ *   an empty plane reads nothing from crops, and whatever place holds only bytes (y, x) with 0 <= y, x < S of the row's OWN crop are
+ *   addressed.
+ * la3d_pack_crop_bits (one frame size): the output contract of la3d_pack_rle_bits - B planes of la3d_mask_bits_words(H, W_out) words,
+ *   bits_plane_stride words apart, rows padded from W to W_out (W, or a multiple of 32 >= W) with zero bits; every word of every plane
+ *   is written and nothing else.  la3d_pack_crop_bits_frames (images of different sizes): the contract of la3d_pack_rle_bits_frames -
+ *   the plane of row n at bits + bits_offsets[n], the words of its image's frame, bits 16-byte aligned; checked on the device in the
+ *   same order (image_index[n], the frame row, bits_offsets[n]); a refused row writes no word and gets area 0.
+ *   area: dev [B] or NULL - the popcount of each plane as written; cleared by a kernel of the call on `stream` and accumulated with
+ *   one integer atomic per wave.  One packing kernel (plus that clear), no synchronisation: the call is capturable.
+ * LA3D_ERR_ARG / LA3D_ERR_UNSUPPORTED: as for la3d_pack_rle_bits / la3d_pack_rle_bits_frames (H*W_out, or the bounds' H *
+ *   roundup32(W), beyond 1048576: LA3D_ERR_UNSUPPORTED - what the consumers of planes take); and LA3D_ERR_ARG for S <= 0,
+ *   pixel_step < 1, row_pitch < S*pixel_step, threshold outside [0, 255], crop_stride smaller than a crop ((S-1)*row_pitch +
+ *   (S-1)*pixel_step + 1 bytes), a misaligned place - these are checked first, for B == 0 too.  B == 0 otherwise: success, nothing is
+ *   launched. */
+int la3d_pack_crop_bits(const uint8_t* crops, int64_t crop_stride /* bytes between crops */, int32_t row_pitch /* bytes */,
+                        int32_t pixel_step /* bytes between pixels */, int S, int threshold /* bit = byte > threshold */,
+                        const int32_t* place /* dev [B][4]: x1, y1, side, 0 */, int B, int H, int W, int W_out, uint32_t* bits,
+                        int64_t bits_plane_stride, int32_t* area /* dev [B] or NULL */, void* stream);
+int la3d_pack_crop_bits_frames(const uint8_t* crops, int64_t crop_stride, int32_t row_pitch, int32_t pixel_step, int S, int threshold,
+                               const int32_t* place /* dev [B][4] */, const la3d_frame* frames, int32_t P, int H, int W /* bounds */,
+                               const int32_t* image_index /* dev [B] */, int B, uint32_t* bits, const int64_t* bits_offsets /* dev [B] */,
+                               int32_t* area /* dev [B] or NULL */, void* stream);
+
 /* HOST helper: COCO compressed RLE string (pycocotools rleFrString) -> run lengths.  Returns the number of
  * counts written, or -1 (malformed string / cap too small). */
 int la3d_rle_from_string_host(const char* s, int64_t len, int32_t* counts, int cap);

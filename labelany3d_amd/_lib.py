@@ -101,6 +101,10 @@ _SIGS = {
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "la3d_pack_poly_bits_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_int, C.c_void_p,
                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "la3d_pack_crop_bits": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "la3d_pack_crop_bits_frames": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int32,
+                                             C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "la3d_fit_workspace_bytes": (C.c_size_t, [C.POINTER(FitArgs)]),
     "la3d_fit_instances_bits": (C.c_int, [C.POINTER(FitArgs), C.c_void_p, C.c_int64, C.c_int32]),
     "la3d_fit_instances_depth16": (C.c_int, [C.POINTER(FitArgs), C.POINTER(Depth16Block), C.c_void_p, C.c_int64, C.c_int32]),

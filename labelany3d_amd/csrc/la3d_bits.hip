@@ -1,5 +1,5 @@
 // la3d_bits.hip - masks as bit planes (include/la3d.h "masks as bit planes" and everything behind it): the packers of u8 masks,
-// logits, label maps, COCO run lengths and polygons - each in its uniform and its frames form -, the unpacker and the filter
+// logits, label maps, COCO run lengths, polygons and crop-space masks - each in its uniform and its frames form -, the unpacker and the filter
 // statistics of a bit plane.  This unit also owns the family "annotation into an LDS bit image": NT_DEC, bits_to_plane and with them
 // la3d_rle_decode / la3d_poly_decode, whose kernels the annotation packers repeat with the LDS image kept as the output.
 // Stated once for every entry: where the planes go (BitsOut), the host check (pack_check), the frames prologue of a workgroup
@@ -669,6 +669,95 @@ __global__ __launch_bounds__(256) void pack_masks_frames_kernel(const void* __re
   label_area(area, n, pat);   // (every lane of the wave takes part)
 }
 
+// ---- crop-space masks -> bit planes (la3d_pack_crop_bits / la3d_pack_crop_bits_frames) ------------------------------------------
+// restore_mask_from_crop for a batch (reference src/util.py:171-214, called at src/batch_scripts/whole.py:94): the S x S crop of
+// instance n, resized by nearest index to side x side pixels and pasted at (x1, y1), clipped to the frame - written as the plane's
+// words, never as a u8 plane.  One lane per output word, blockIdx.x = instance, blockIdx.y = chunk of 256 words (sized for the bounds'
+// plane in the frames form: a chunk beyond its plane returns before any load).  A word is 32 independent source lookups; where the
+// stored rows are whole words (W % 32 == 0) a word lies in one frame row and so in one source row, and a word whose row or columns
+// miss the placement is stored as zero without a load.
+// What decides whether and where something is read: the row of `place` - wave-uniform, through scalar loads, checked BEFORE an address
+// is formed from it.
+//   side outside (0, CROP_SIDE_MAX], or a placement that misses the frame (x1 >= frame_width, x1 + side <= 0, y1 >= H, y1 + side <= 0,
+//   in 64 bits: x1, y1 are any int32): nothing is read, the plane is zero.
+//   Otherwise the 32 lookups of a word that meets the placement are issued TOGETHER, each at a distance d CLAMPED into [0, side - 1]
+//   (a bit whose own pixel misses the placement looks up the nearest one that does not, and is masked out afterwards): the loads do
+//   not wait for one another.  0 <= d < 2^20 is exact in float64 and ifx > 0, so 0 <= min(floor(d * ifx), S - 1) <= S - 1: only bytes
+//   (y, x) in [0, S)^2 of the instance's OWN crop are ever addressed, whatever place holds.
+constexpr int CROP_SIDE_MAX = 1 << 20;
+struct CropSrc {
+  const unsigned char* crops;   // byte (y, x) of crop n at crops + n * stride + y * pitch + x * step
+  long long stride;
+  int pitch, step, S, thr;      // bit = byte > thr
+  const int* place;             // dev [B][4]: x1, y1, side, 0
+};
+
+// OpenCV's resizeNN index rule (inv_scale = dsize / ssize, ifx = 1 / inv_scale): min(floor(d * ifx), S - 1).  The product is ONE
+// float64 multiply, rounded on its own (__dmul_rn: never contracted with anything around it), then floor.  d is clamped into
+// [0, side - 1] first: `in` tells whether it was inside.
+__device__ inline int crop_index(long long d, int side, double ifx, int S, bool* in) {
+  *in = d >= 0 && d < side;
+  const int dc = d < 0 ? 0 : d < side ? (int)d : side - 1;
+  const int i = (int)floor(__dmul_rn((double)dc, ifx));
+  return i < S - 1 ? i : S - 1;
+}
+
+template <bool FRAMES>
+__global__ __launch_bounds__(256) void pack_crop_bits_kernel(const CropSrc s, const BitsOut c) {
+  const int n = blockIdx.x, chunk = blockIdx.y;
+  PlaneGeo g;
+  if (!plane_geometry<FRAMES>(c, n, &g)) return;   // (uniform) refused: no plane word, the area stays 0
+  if (chunk * 256 >= g.nwords) return;             // (uniform) before any load
+  const int w = chunk * 256 + (int)threadIdx.x;
+  const bool live = w < g.nwords;
+  const int fw = g.fw > 0 ? g.fw : g.W;            // the image columns
+  const int* pl = s.place + (long long)n * 4;
+  const int x1 = __builtin_amdgcn_readfirstlane(pl[0]), y1 = __builtin_amdgcn_readfirstlane(pl[1]);
+  const int side = __builtin_amdgcn_readfirstlane(pl[2]);
+  const bool shows = side > 0 && side <= CROP_SIDE_MAX && x1 < fw && (long long)x1 + side > 0 && y1 < g.H && (long long)y1 + side > 0;   // uniform
+  unsigned pat = 0;
+  if (live && shows) {
+    const double ifx = 1.0 / ((double)side / (double)s.S);
+    const unsigned char* crop = s.crops + (long long)n * s.stride;
+    bool in;
+    if ((g.W & 31) == 0) {   // uniform: a word lies in one row
+      const int wpr = g.W >> 5;
+      const int v = w / wpr, c0 = (w - v * wpr) << 5;
+      const long long dx0 = (long long)c0 - x1;
+      const int sy = crop_index((long long)v - y1, side, ifx, s.S, &in);   // (v < H: w < nwords)
+      if (in && dx0 + 31 >= 0 && dx0 < side) {
+        const unsigned char* row = crop + (long long)sy * s.pitch;
+        unsigned have = 0;
+#pragma unroll
+        for (int k = 0; k < 32; ++k) {
+          const int sx = crop_index(dx0 + k, side, ifx, s.S, &in);
+          have |= (in && c0 + k < fw ? 1u : 0u) << k;
+          pat |= ((int)row[(long long)sx * s.step] > s.thr ? 1u : 0u) << k;
+        }
+        pat &= have;
+      }
+    } else {                 // W_out == W, no multiple of 32: a word may straddle rows - bit by bit
+      const long long total = (long long)g.H * g.W, i0 = (long long)w * 32;
+      const long long last = i0 + 31 < total ? i0 + 31 : total - 1;
+      int v = (int)(i0 / g.W), u = (int)(i0 - (long long)v * g.W);
+      if (last / g.W >= y1 && v < (long long)y1 + side) {   // one of the word's rows meets the placement
+        unsigned have = 0;
+#pragma unroll 8
+        for (int k = 0; k < 32; ++k) {
+          bool iny;
+          const int sy = crop_index((long long)v - y1, side, ifx, s.S, &iny), sx = crop_index((long long)u - x1, side, ifx, s.S, &in);
+          have |= (in && iny && u < fw && i0 + k < total ? 1u : 0u) << k;
+          pat |= ((int)crop[(long long)sy * s.pitch + (long long)sx * s.step] > s.thr ? 1u : 0u) << k;
+          if (++u == g.W) { u = 0; ++v; }
+        }
+        pat &= have;
+      }
+    }
+  }
+  if (live) g.out[w] = pat;
+  label_area(c.area, n, pat);   // (every lane of the wave takes part)
+}
+
 }  // namespace
 
 // ==========================================================================================
@@ -905,6 +994,27 @@ int pack_masks_frames(const char* who, const void* src, int kind, float thr, con
     return check_launch("pack_masks_frames_kernel");
   });
 }
+
+// ---- crop-space masks: the rules of the source (either form, in front of the packers' check) and the launch behind it ----
+int crop_source(const char* who, const uint8_t* crops, int64_t crop_stride, int32_t row_pitch, int32_t pixel_step, int S, int threshold,
+                const int32_t* place, int B, CropSrc* s) {
+  if (S <= 0 || pixel_step < 1 || (long long)row_pitch < (long long)S * pixel_step || threshold < 0 || threshold > 255)
+    return pack_refuse(who, "bad source (S > 0, pixel_step >= 1, row_pitch >= S * pixel_step, 0 <= threshold <= 255)");
+  // (the bytes of one crop: its last row ends S * pixel_step - (pixel_step - 1) bytes in)
+  if (crop_stride < (long long)(S - 1) * row_pitch + (long long)(S - 1) * pixel_step + 1 || (B > 0 && crop_stride > INT64_MAX / B))
+    return pack_refuse(who, "crop_stride is smaller than a crop (or B * crop_stride overflows)");
+  if (B > 0 && (reinterpret_cast<uintptr_t>(place) & 3)) return pack_refuse(who, "place not a 4-byte aligned pointer");
+  *s = CropSrc{crops, (long long)crop_stride, row_pitch, pixel_step, S, threshold, place};
+  return LA3D_SUCCESS;
+}
+template <bool FRAMES>
+int pack_crop_launch(const CropSrc& src, int B, const BitsOut& c, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int cleared = clear_area(c.area, B, s);
+  if (cleared != LA3D_SUCCESS) return cleared;
+  hipLaunchKernelGGL(pack_crop_bits_kernel<FRAMES>, dim3((unsigned)B, (unsigned)((c.lds_words + 255) / 256)), dim3(256), 0, s, src, c);
+  return check_launch("pack_crop_bits_kernel");
+}
 }  // namespace
 
 extern "C" {
@@ -1035,6 +1145,32 @@ int la3d_pack_poly_bits_frames(const int32_t* poly_xy, const int64_t* ring_offse
   const int rc = ann_frames_check("la3d_pack_poly_bits_frames", poly_xy, ring_offsets, inst_rings, B, c);
   if (rc != PACK_LAUNCH) return pack_done(rc);
   return pack_poly_launch<true>("la3d_pack_poly_bits_frames", "pack_poly_bits_frames_kernel", poly_xy, ring_offsets, inst_rings, B, c, stream);
+}
+
+int la3d_pack_crop_bits(const uint8_t* crops, int64_t crop_stride, int32_t row_pitch, int32_t pixel_step, int S, int threshold,
+                        const int32_t* place, int B, int H, int W, int W_out, uint32_t* bits, int64_t bits_plane_stride, int32_t* area,
+                        void* stream) {
+  const char* who = "la3d_pack_crop_bits";
+  CropSrc src;
+  const int bad = crop_source(who, crops, crop_stride, row_pitch, pixel_step, S, threshold, place, B, &src);
+  if (bad != LA3D_SUCCESS) return bad;
+  const BitsOut c = bits_out_uniform(H, W, W_out, bits, bits_plane_stride, area);
+  const int rc = ann_check(who, crops, place, place, B, W, c);
+  if (rc != PACK_LAUNCH) return pack_done(rc);
+  return pack_crop_launch<false>(src, B, c, stream);
+}
+
+int la3d_pack_crop_bits_frames(const uint8_t* crops, int64_t crop_stride, int32_t row_pitch, int32_t pixel_step, int S, int threshold,
+                               const int32_t* place, const la3d_frame* frames, int32_t P, int H, int W, const int32_t* image_index, int B,
+                               uint32_t* bits, const int64_t* bits_offsets, int32_t* area, void* stream) {
+  const char* who = "la3d_pack_crop_bits_frames";
+  CropSrc src;
+  const int bad = crop_source(who, crops, crop_stride, row_pitch, pixel_step, S, threshold, place, B, &src);
+  if (bad != LA3D_SUCCESS) return bad;
+  const BitsOut c = bits_out_frames(frames, P, H, W, image_index, bits, bits_offsets, area);
+  const int rc = ann_frames_check(who, crops, place, place, B, c);
+  if (rc != PACK_LAUNCH) return pack_done(rc);
+  return pack_crop_launch<true>(src, B, c, stream);
 }
 
 int la3d_pack_label_bits(const void* labels, int dtype, int64_t plane_stride, int P, int H, int W, int W_out,

@@ -13,7 +13,7 @@ from . import _lib
 from ._lib import check, lib
 from .batched import Depth16, _as_dev, _d16_block, _depth16_check, _dev, _ptr, _record, _stream, _upload_many, height_rule_code, padded_width, refuse_depth16
 from .fitcall import FramesDepth, fit_call, mask_source
-from .masks import _D16_DTYPES, _LABEL_NUMPY, _LABEL_TORCH, _LOGIT_DTYPES, _label_rows, _rle_counts
+from .masks import _D16_DTYPES, _LABEL_NUMPY, _LABEL_TORCH, _LOGIT_DTYPES, _crop_place, _crop_source, _crop_threshold, _label_rows, _rle_counts
 
 FRAME_DTYPE = np.dtype([("depth_offset", "<i8"), ("H", "<i4"), ("W", "<i4"), ("frame_width", "<i4"), ("reserved", "<i4")])
 """One row of the frame table of a frames call: ``la3d_frame`` of include/la3d.h (24 bytes)."""
@@ -658,6 +658,40 @@ def pack_poly_bits_frames(frames, polys, image_index, stream=None, out=None) -> 
     return _pack_annotation_bits_frames(lib.la3d_pack_poly_bits_frames, "la3d_pack_poly_bits_frames", frames,
                                         [(polys[0], torch.int32), (polys[1], torch.int64), (polys[2], torch.int64)], B, image_index, ii_h,
                                         offs_h, total, stream, out)
+
+
+def pack_crop_bits_frames(frames, crops, params, image_index, threshold=None, stream=None, out=None) -> FrameBits:
+    """Crop-space masks of images of DIFFERENT sizes -> ``FrameBits`` (C-ABI ``la3d_pack_crop_bits_frames``): ``pack_crop_bits`` with
+    every crop restored into the bit plane of its image's OWN frame - ``H_p * padded_width(W_p) / 32`` words, the bits of the padding
+    columns zero.  ``crops`` / ``params`` / ``threshold`` as in ``pack_crop_bits``; ``frames`` / ``image_index`` / ``out`` and the
+    result as in ``pack_rle_bits_frames`` (host ``image_index``: planes laid out by ``frame_bits_offsets``; device ``image_index``: no
+    synchronisation, a uniform stride).  An instance whose image index or frame row breaks the contract gets no plane and area 0 -
+    decided on the device."""
+    who = "pack_crop_bits_frames"
+    B = int(crops.shape[0]) if hasattr(crops, "shape") else len(crops)
+    ii_h, offs_h, total = _annotation_rows(who, frames, B, image_index)
+    if not (isinstance(frames.table, torch.Tensor) and frames.table.is_cuda):
+        raise ValueError("the frame table must live on the GPU (pack_frames with a GPU device)")
+    dev = frames.table.device
+    P = len(frames.sizes)
+    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev):
+        raise ValueError("out must be a flat int32 tensor on the device of the frame table")
+    with torch.cuda.device(dev):
+        if out is not None:
+            _bits_buffers(out, total, 0, dev)   # (its argument errors, before anything is uploaded)
+        v, sb, sr, sp, S, B, default = _crop_source(who, crops, dev)
+        thr = _crop_threshold(who, threshold, default)
+        place = _crop_place(who, params, S, B, dev)
+        if ii_h is not None:
+            ii, offs = _upload_many([(ii_h, torch.int32), (offs_h, torch.int64)], dev)
+        else:
+            ii = _as_dev(image_index, torch.int32, dev)
+            offs = torch.arange(B, dtype=torch.int64, device=dev) * (total // B if B else 0)
+        o, area = _bits_buffers(out, total, B, dev)
+        check(lib.la3d_pack_crop_bits_frames(v.data_ptr(), sb, sr, sp, S, thr, _ptr(place), _ptr(frames.table), P, frames.H, frames.W, _ptr(ii), B,
+                                             _ptr(o), _ptr(offs), _ptr(area), _stream(stream)), "la3d_pack_crop_bits_frames")
+    _record(stream, frames.table, v, place, ii, offs, o, area)
+    return FrameBits(o, offs, ii, area, frames.table_host, frames.H, frames.W)
 
 
 def fit_instances_frames_masks(frames, masks, K, threshold: float = 0.0, image_index=None, ground=None, sample_idx=None, filter=None,

@@ -716,6 +716,120 @@ def pack_poly_bits(polys, frame_pad: bool = True, device=None, stream=None, out=
                                  int(polys[3]), int(polys[4]), frame_pad, device, stream, out, area)
 
 
+# ---- crop-space masks as bit planes (include/la3d.h "crop-space masks as bit planes") -----------------------------------------------
+def crop_placement(params, S: int) -> np.ndarray:
+    """The paste of ``restore_mask_from_crop`` (reference src/util.py:187, :196-197) for a batch of crops of side ``S``: ``params``
+    (B, 3) or a list of ``(offset_x, offset_y, scale_factor)`` -> int32 (B, 4) rows ``x1, y1, side, 0`` - what ``la3d_pack_crop_bits``
+    reads as ``place``.  Host arithmetic on Python floats, exactly the reference's: ``side = int(S / scale_factor)`` (truncated),
+    ``x1 = int(round(offset_x))`` with Python's ``round`` (half to even); a scale of 0 and values that are no numbers raise what they
+    raise there.  Values that do not fit an int32 are clamped (such a placement lies outside every frame, such a side is refused on
+    the device: an empty plane)."""
+    rows = params.tolist() if hasattr(params, "tolist") else list(params)
+    out = np.zeros((len(rows), 4), np.int32)
+    lim = 2 ** 31 - 1
+    for n, row in enumerate(rows):
+        if len(row) != 3:
+            raise ValueError(f"crop_placement: row {n} must be (offset_x, offset_y, scale_factor)")
+        ox, oy, s = (float(v) for v in row)
+        out[n, :3] = [max(-lim, min(lim, i)) for i in (int(round(ox)), int(round(oy)), int(int(S) / s))]
+    return out
+
+
+def _crop_source(who, crops, dev):
+    """``crops`` of a crop packer -> (tensor that owns the bytes, the view whose first byte is crop 0's pixel (0, 0), crop stride, row
+    pitch, pixel step - bytes -, S, B, the default threshold).  (B, S, S) bool / uint8: a mask, threshold 0; (B, S, S, 4) uint8: RGBA,
+    the alpha channel is read in place through the strides, threshold 127 (reference src/batch_scripts/whole.py:83).  A device tensor
+    is read where it lies when a crop's rows and pixels lie at non-negative strides that do not overlap; host arrays go up as the
+    S x S bytes that are read."""
+    shape = tuple(crops.shape) if hasattr(crops, "shape") else None
+    if shape is None:
+        crops = np.asarray(crops)
+        shape = crops.shape
+    rgba = len(shape) == 4
+    if not ((len(shape) == 3 or (rgba and shape[3] == 4)) and shape[1] == shape[2] and shape[1] > 0):
+        raise ValueError(f"{who}: crops must be (B, S, S) bool / uint8 masks or (B, S, S, 4) uint8 RGBA crops, got {shape}")
+    B, S = int(shape[0]), int(shape[1])
+    if isinstance(crops, torch.Tensor):
+        if crops.dtype not in ((torch.uint8,) if rgba else (torch.uint8, torch.bool)):
+            raise ValueError(f"{who}: crops must be uint8{'' if rgba else ' or bool'}, not {crops.dtype}")
+        t = crops.view(torch.uint8) if crops.dtype == torch.bool else crops
+        v = t[..., 3] if rgba else t
+        if v.device != dev:
+            v = v.to(dev)
+        sb, sr, sp = v.stride()
+        if not (sp >= 1 and sr >= S * sp and (B <= 1 or sb >= (S - 1) * sr + (S - 1) * sp + 1)):
+            v = v.contiguous()
+            sb, sr, sp = v.stride()
+    else:
+        a = np.asarray(crops)
+        if a.dtype not in ((np.uint8,) if rgba else (np.uint8, np.bool_)):
+            raise ValueError(f"{who}: crops must be uint8{'' if rgba else ' or bool'}, not {a.dtype}")
+        a = np.ascontiguousarray(a[..., 3] if rgba else a).view(np.uint8)
+        v = torch.as_tensor(a, device=dev)
+        sb, sr, sp = S * S, S, 1
+    if B <= 1:
+        sb = max(int(sb), (S - 1) * int(sr) + (S - 1) * int(sp) + 1)
+    return v, int(sb), int(sr), int(sp), S, B, (127 if rgba else 0)
+
+
+def _crop_threshold(who, threshold, default: int) -> int:
+    thr = default if threshold is None else int(threshold)
+    if not 0 <= thr <= 255:
+        raise ValueError(f"{who}: threshold must lie in [0, 255] (bit = byte > threshold)")
+    return thr
+
+
+def _crop_place(who, params, S: int, B: int, dev) -> torch.Tensor:
+    """``params`` of a crop packer -> the int32 (B, 4) ``place`` rows on the device: host parameters through ``crop_placement``; an
+    int32 (B, 4) device tensor is taken as the rows themselves (``crop_placement`` uploaded once: nothing is copied, the call is
+    capturable)."""
+    if isinstance(params, torch.Tensor) and params.is_cuda:
+        if not (params.dtype == torch.int32 and tuple(params.shape) == (B, 4) and params.is_contiguous() and params.device == dev):
+            raise ValueError(f"{who}: device params must be the contiguous int32 ({B}, 4) rows of crop_placement, on the crops' device")
+        return params
+    place = crop_placement(params, S)
+    if len(place) != B:
+        raise ValueError(f"{who}: params must hold one (offset_x, offset_y, scale_factor) per crop ({B}), got {len(place)}")
+    return torch.as_tensor(place, device=dev)
+
+
+def pack_crop_bits(crops, params, image_size, threshold=None, frame_pad: bool = True, device=None, stream=None, out=None,
+                   area=None) -> MaskBits:
+    """Crop-space masks -> ``MaskBits`` of the full frame on the GPU (C-ABI ``la3d_pack_crop_bits``): ``restore_mask_from_crop``
+    (reference src/util.py:171-214) for a batch, written as bit planes - the nearest-index resize to ``int(S / scale_factor)`` pixels
+    and the clipped paste at ``round(offset)`` happen inside one kernel, so a 640x480 instance costs its 65 536 B crop (nothing when
+    the crop is resident) instead of a host resize, a 307 200 B upload and a pack.  ``crops``: (B, S, S) bool / uint8 masks (bit =
+    byte > ``threshold``, default 0) or (B, S, S, 4) uint8 RGBA crops, whose alpha is read in place (default threshold 127, as at
+    src/batch_scripts/whole.py:83), on the host or the device; ``params``: (B, 3) ``(offset_x, offset_y, scale_factor)`` as
+    ``crop_object`` returns them (``crop_placement`` turns them into the paste on the host, in the reference's float arithmetic), or
+    the int32 (B, 4) rows of ``crop_placement`` already on the device (nothing is uploaded then: with resident crops the call copies
+    nothing and can be captured into a graph);
+    ``image_size`` = (width, height).  ``frame_pad`` / ``out`` / ``area`` as in ``pack_rle_bits``.  Unlike the reference, a scale
+    that leaves no pixel (side <= 0) and a crop that lies wholly outside the frame give an empty plane (area 0), not an exception."""
+    who = "pack_crop_bits"
+    if device is None and isinstance(crops, torch.Tensor) and crops.is_cuda:
+        device = crops.device
+    W, H = int(image_size[0]), int(image_size[1])
+    B0 = int(crops.shape[0]) if hasattr(crops, "shape") else len(crops)
+    W_out, stride, device = _annotation_bits_plan(who, B0, H, W, frame_pad, device, out, area)
+    if H <= 0 or W <= 0:
+        raise ValueError(f"{who}: image_size states an empty frame {(W, H)}")
+    dev = device if isinstance(device, torch.device) else _dev(device)
+    with torch.cuda.device(dev):
+        v, sb, sr, sp, S, B, default = _crop_source(who, crops, dev)
+        thr = _crop_threshold(who, threshold, default)
+        place = _crop_place(who, params, S, B, dev)
+        if out is None:
+            stride = (H * W_out + 31) // 32
+            out = torch.empty((B, stride), dtype=torch.int32, device=dev)
+        check(lib.la3d_pack_crop_bits(v.data_ptr(), sb, sr, sp, S, thr, place.data_ptr(), B, H, W, W_out, out.data_ptr(), stride,
+                                      None if area is None else area.data_ptr(), _stream(stream)), "la3d_pack_crop_bits")
+    _record(stream, v, place, out, area)
+    mb = _PackedBits(out, H, W_out, W)
+    mb._stride = stride
+    return mb
+
+
 def unpack_mask_bits(bits, stream=None) -> torch.Tensor:
     """``MaskBits`` -> (B,H,frame_width) bool masks on the GPU (C-ABI ``la3d_unpack_mask_bits``)."""
     mb = _mask_bits(bits)
@@ -1036,5 +1150,5 @@ def masked_ratio_median(depth_map, depth_render, mask, render_mask=None, image_i
 # the mixed-size ("frames") layer: its public names stay importable from here (last on purpose: frames imports from this module)
 from .frames import (FRAME_DTYPE, MASKS_U8, FrameBits, PackedFrames, PackedFrames16, PackedLabels, PackedMasks, fit_instances_frames,  # noqa: E402,F401
                      fit_instances_frames_bits, fit_instances_frames_labels, fit_instances_frames_masks, frame_bits_offsets, frame_table,
-                     pack_frames, pack_label_bits_frames, pack_label_frames, pack_mask_bits_frames, pack_mask_frames, pack_poly_bits_frames,
+                     pack_crop_bits_frames, pack_frames, pack_label_bits_frames, pack_label_frames, pack_mask_bits_frames, pack_mask_frames, pack_poly_bits_frames,
                      pack_rle_bits_frames, pack_rle_frames)

@@ -48,6 +48,22 @@ def depth_to_points(depth, K=None, R=None, t=None):
     return out
 
 
+def restore_mask_from_crop(resized_mask, offset_x, offset_y, scale_factor, original_mask_shape):
+    """The reference's ``restore_mask_from_crop`` (src/util.py:171-214) on the MI355X: the (S, S) mask of a crop (boolean or 0 / 1;
+    non-zero = True) resized by nearest index to ``int(S / scale_factor)`` pixels and pasted, clipped, at ``round(offset)`` into a
+    mask of ``original_mask_shape`` = (H, W); returns a NumPy bool (H, W) array.  One ``pack_crop_bits`` and one
+    ``unpack_mask_bits``; a caller that goes on to the fit keeps the ``MaskBits`` of ``pack_crop_bits`` instead.  Unlike the
+    reference, a scale that leaves no pixel and a crop wholly outside the frame give an empty mask, not an exception."""
+    from .masks import pack_crop_bits, unpack_mask_bits
+
+    m = np.asarray(resized_mask)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError(f"restore_mask_from_crop: resized_mask must be a square (S, S) mask, got {m.shape}")
+    H, W = int(original_mask_shape[0]), int(original_mask_shape[1])
+    bits = pack_crop_bits((m != 0)[None], [(offset_x, offset_y, scale_factor)], (W, H), frame_pad=False)
+    return unpack_mask_bits(bits)[0].cpu().numpy()
+
+
 def project_to_2d(point_3d, camera_matrix):
     """Pinhole projection of one camera-frame point: ``(K @ p)[:2] / (K @ p)[2]`` (reference src/util.py:225-227)."""
     h = np.dot(camera_matrix, point_3d)
