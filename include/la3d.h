@@ -751,6 +751,17 @@ int la3d_align_select_batch(const float* relative, const float* metric, const ui
  *   status  0 fitted; 1 no sample (counts[p] == 0); 2 the fit failed - a non-finite sample, m outside [1, n] (or beyond m_cap), a subset
  *           index outside [0, n), counts[p] outside [0, n], no accepted trial: where the reference returns the metric depth.  coef is
  *           NaN, n_inliers 0 and best_trial -1 for a status other than 0.
+ * Where this parts from scikit-learn.  (1) A ZERO THRESHOLD - one sample, constant y, more than half of the y equal: the inlier test is
+ *   then the exact float32 equality y == float32(x * a_t) and hangs on the last bit of the slope, where float32(sum xy / sum xx) and
+ *   LAPACK's float32 gelsd solution differ.  The library may fit such a frame (status 0, as few as one inlier) for which scikit-learn
+ *   raises "no consensus set" and the reference returns the metric depth, or both fit with different coefficients (up to 1.7 x apart
+ *   on constant y).  A caller who wants the reference's answer there treats thr == 0 as a failed fit.  (2) Magnitudes outside
+ *   float32's range for sum y^2 (|y| of the order 1e19): scikit-learn scores float32 targets in float32, its scores overflow and
+ *   its choice among trials of equal k is no longer by R^2; the scores here are float64.  (3) The residual squared in the score is
+ *   the float32 residual of the inlier test or the float64 difference y - pred: left open, the two differ by 2^-24 relative at most
+ *   (the kernels square the float32 one).  Everywhere else n_trials, the inlier set and coef (to 1.5e-6 relative) are scikit-learn's
+ *   on the same subsets (tests/test_align_ransac_restatement.py); the kernels are held to the NumPy restatement in every class
+ *   (oracle/campaigns/align_ransac.py).
  * Subsets: `subsets` dev i32 [P][max_trials][m_cap] - frame p, trial t uses the first m of its row (for a seeded scikit-learn draw made
  * on the host) -, or NULL: the kernels draw them from `seed`, counter-based and keyed by (seed, frame, trial): m DISTINCT indices per
  * trial (a keyed bijection of [0, n)).  The device draw is NOT NumPy's stream; la3d_align_ransac_subsets writes the subsets a seed

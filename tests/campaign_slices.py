@@ -14,7 +14,10 @@ is a regression since then.
   CLOUD_SEEDS         profiles/clouds/fuzz_clouds.txt (oracle/campaigns/clouds.py: the instance point clouds; seeds 80000 ... 80499:
                       the whole range has run, see the record)
   FORMAT_SEEDS        profiles/formats/fuzz_formats.txt (oracle/campaigns/formats.py: the mask, logit and label packers and the 16-bit
-                      depth packers; seeds 90000 ... 90499: the whole range has run, see the record)"""
+                      depth packers; seeds 90000 ... 90499: the whole range has run, see the record)
+  ALIGN_RANSAC_SEEDS  profiles/align_ransac/fuzz_align_ransac.txt (oracle/campaigns/align_ransac.py: the batched RANSAC scale fit, its
+                      device draw and the chain select -> fit -> apply; seeds 100000 ... 100499: the whole range has run, see the
+                      record)"""
 
 ENGINE_SEEDS = [
     10018, 10023, 10025, 10032, 10034, 10046, 10050, 10051, 10056, 10058,
@@ -76,4 +79,19 @@ FORMAT_SEEDS = [
     90027, 90028, 90030, 90031, 90033, 90034, 90035, 90036, 90037, 90038,
     90039, 90041, 90046, 90047, 90058, 90061, 90103, 90147, 90206, 90225,
     90250, 90272, 90317, 90359, 90403,
+]
+
+# the campaign of the batched RANSAC scale fit (oracle/campaigns/align_ransac.py), picked by a CPU scan of seeds 100000 ... 100499: every
+# family and status, every listed n (1 ... 20000: frames of 1, 2, 3, 4 and 5 segments), every max_trials, stop_probability and
+# min_samples kind, m_cap tight / wide (-1 and in-range garbage behind m) / shorter than one frame's m, even counts whose upper middle
+# value differs from the lower one in each of the two medians, thr == 0 frames that fit and that fail, trials with k < 2, with all
+# inlier y equal and with sum xx == 0, trial limits of 0 and infinity, early stops and full runs, the draw-only sizes 16384 / 65536 /
+# 65537, depth frames of every size with and without mask and of every status; 100063 holds a frame undecided by its trial limit,
+# 100283 one by a score tie and one by a slope, 100494 an undecided depth frame (tests/test_differential_checkers.py::test_align_ransac_slice_covers asserts all of it)
+ALIGN_RANSAC_SEEDS = [
+    100011, 100037, 100043, 100049, 100063, 100080, 100099, 100101, 100106, 100114,
+    100124, 100134, 100156, 100170, 100172, 100178, 100186, 100190, 100208, 100209,
+    100222, 100231, 100272, 100275, 100283, 100286, 100291, 100294, 100303, 100319,
+    100321, 100324, 100330, 100331, 100352, 100361, 100375, 100380, 100390, 100403,
+    100413, 100419, 100433, 100444, 100465, 100478, 100494, 100495,
 ]

@@ -14,11 +14,14 @@
                 frame size and of mixed sizes, host and device layouts, out= buffers, the unpacker, the bit-plane statistics, both
                 16-bit depth packers and the fit on the planes they wrote, 45 cases; the fit leg of the whole slice once more on its own, held to the share of
                 records that must be compared
+  align_ransac  the batched RANSAC scale fit (oracle/campaigns/align_ransac.py): explicit subsets batched, every frame alone, the same
+                call twice, unaligned buffers, the device draw and the fit on it, select -> fit -> apply on depth frames, 48 cases
   aux           unproject, decoders, mask statistics, filters, consumers, depth statistics, matcher, 40 cases
 A case fails with the campaign's own message, which names its seed."""
 import numpy as np
 import pytest
 
+from oracle.campaigns import align_ransac as AR
 from oracle.campaigns import annotations as A
 from oracle.campaigns import aux as X
 from oracle.campaigns import clouds as CL
@@ -215,6 +218,35 @@ def test_format_slice_fit_leg_compares_a_third(gpu):
     print("\n".join(FM.tally_lines(tally)))
     assert not fails, _report(fails)
     assert tally["fitted"] > 0 and 3 * tally["compared"] >= tally["fitted"], (tally["compared"], tally["fitted"])
+
+
+@pytest.mark.parametrize("seeds", _groups(S.ALIGN_RANSAC_SEEDS, 6), ids=lambda v: str(v[0]))
+def test_align_ransac_campaign_slice(gpu, seeds):
+    """ransac_scale_batch / ransac_subsets / align_depth_batch against the NumPy restatement (tests/align_ransac_cases.py): status,
+    n_trials, n_inliers and best_trial exactly and coef to the adjacent float32 on every decided frame, one of the oracle's own walks
+    on an undecided one (classes from the oracle alone), the runs among each other bit for bit, every drawn row, every pixel of the
+    aligned maps.  A call that raises ends the group's GPU work."""
+    fails = []
+    tally = AR.new_tally()
+    for s in seeds:
+        c = AR.make_case(s)
+        want = AR.oracle_case(s)
+        AR.tally_case(tally, c, want)
+        cache, default = {}, None
+        for r in AR.RUNS:
+            if not AR.applies(c, r):
+                continue
+            try:
+                got = AR.run_gpu(c, r, cache)
+            except Exception as e:   # noqa: BLE001 - whatever made the call fail is looked at before anything else runs on the device
+                print("\n".join(AR.tally_lines(tally)))
+                pytest.fail(_report(fails + [f"seed {s} {r}: call failed, nothing more was run: {e!r}"]))
+            tally["calls"] += 1
+            if not r:
+                default = got
+            fails += [f"seed {s} {r}: {m}" for m in AR.check_run(c, want, r, got, default, tally)]
+    print("\n".join(AR.tally_lines(tally)))
+    assert not fails, _report(fails)
 
 
 def test_engine_slice_reaches_the_documented_refusal(gpu):
