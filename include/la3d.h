@@ -645,6 +645,66 @@ int la3d_pack_poly_bits_frames(const int32_t* poly_xy, const int64_t* ring_offse
                                int32_t P, int H, int W /* bounds */, const int32_t* image_index /* dev [B] */, int B, uint32_t* bits,
                                const int64_t* bits_offsets /* dev [B] */, int32_t* area /* dev [B] or NULL */, void* stream);
 
+/* ---- bit planes as run lengths ------------------------------------------------------------------------------------------
+ * The way back out of a plane: binary_mask_to_rle for a batch (reference src/download_coconut.py:167-175) - the planes of "masks as
+ * bit planes", whatever packer made them, become COCO run lengths on the device: a few hundred bytes per instance, the fastest source
+ * of the fit (la3d_fit_instances_rle), what the sharded entries ship and what the annotation JSON stores.  All B run lists are packed
+ * into ONE counts array with an offsets array - exactly what la3d_fit_instances_rle, la3d_rle_decode, la3d_mask_stats_rle and
+ * la3d_pack_rle_bits take.  Two stages on the caller's stream; neither synchronises, so the chain can be captured into a HIP graph:
+ *   la3d_rle_encode_offsets(args)  runs[n] (i32 [B]) = the number of counts of instance n's run list; offsets (i64 [B+1]) = the
+ *       exclusive prefix of runs, scanned on the device, deterministic, any B.  Per column the number of transitions and the row of
+ *       the last one stay in `workspace` for the second stage.  B == 0: offsets[0] = 0, nothing else is launched.
+ *   la3d_rle_encode(args)          counts[offsets[n] .. offsets[n+1]) (i32) = the run list of instance n.  The place of a count is the
+ *       rank of the transition that ends it, from prefixes over the columns - never from atomics.
+ * Both take the SAME block (the second stage reads offsets and workspace as the first left them; counts, status and capacity are not
+ * read by the first stage, runs not by the second).
+ * VALUE.  The runs of the (H, frame_width) image in COLUMN-major order (flat index u * H + v), alternating zeros and ones, zeros
+ *   first: a leading 0 when pixel (0, 0) is set; an all-zero plane gives [H * frame_width], an all-one plane [0, H * frame_width];
+ *   runs = transitions + 1 + bit(0, 0).  The list is the reference's, count for count.
+ * WHAT IS READ OF A PLANE.  Only bits (v, u) with v < H and u < frame_width: the pad bits of rows stored W > frame_width wide and
+ *   the bits of the last word past H * W are never read as mask, whatever they hold.
+ * FORMS.  frames == NULL: B planes of ONE H x W in the layout of la3d_pack_mask_bits (W = pixels per row in memory; frame_width
+ *   0 = W, else the image columns), bits_plane_stride words apart (0 = the words of a plane), 4-byte aligned; a 16-byte aligned base
+ *   with a stride that is a multiple of 4 is streamed in 16-byte groups, anything else word by word.  frames != NULL selects the
+ *   FRAMES form (one pair of entries serves both): the plane of row n at mask_bits + bits_offsets[n] (dev i64 [B]), its geometry
+ *   frames[image_index[n]] - the table and the planes of la3d_fit_instances_frames_bits; H, W are bounds, image_index is required,
+ *   frame_width and bits_plane_stride must be 0, mask_bits 16-byte aligned.  Checked ON THE DEVICE, each before an address is formed
+ *   from the value, in the order of the packers: image_index[n] in [0, P); the frame row (the check of the fit); bits_offsets[n] >= 0
+ *   and a multiple of 4.  A refused row gets runs 0, nothing is read or written for it, and status 5 (LA3D_BOX_UNSUPPORTED).
+ * STATUS (i32 [B], written by the second stage).  The second stage never writes outside counts[offsets[n] .. offsets[n+1]) of its
+ *   own instance, whatever the planes hold: LA3D_RLE_NO_ROOM - the range does not lie within [0, capacity]: nothing of the instance is
+ *   written; LA3D_RLE_MISMATCH - the plane's run count differs from the range length, or a column from what the first stage left in
+ *   the workspace (the planes changed between the two calls): the range is filled only as far as it reaches, with values that mean
+ *   nothing.
+ * workspace: la3d_rle_encode_workspace_bytes(B, H, W) bytes (host, no device; 0 for B, H or W <= 0), 8-byte aligned; ONE workspace
+ *   serves one pair of calls at a time.
+ * LA3D_ERR_ARG before any launch: a bad struct_size, negative sizes, strides or capacity, frame_width outside [0, W], an empty frame
+ *   with B > 0, bits_plane_stride below the words of a plane, bits_offsets without frames, frames without image_index, NULL or
+ *   misaligned pointers with work to do (offsets always; counts may be NULL with capacity 0).  H * W (frames: H * roundup32(W))
+ *   > 1048576: LA3D_ERR_UNSUPPORTED - the bit image lives in LDS, as for every consumer of planes. */
+#define LA3D_RLE_OK 0
+#define LA3D_RLE_NO_ROOM 1
+#define LA3D_RLE_MISMATCH 2
+typedef struct la3d_rle_encode_args {
+  int32_t struct_size;                                   /* sizeof(la3d_rle_encode_args) of the caller */
+  int32_t B, H, W;
+  int32_t frame_width;                                   /* 0 = W */
+  int32_t P;                                             /* rows of frames */
+  const uint32_t* mask_bits; int64_t bits_plane_stride;  /* bit planes; words between planes, 0 = the words of a plane */
+  const la3d_frame* frames;                              /* dev [P] | NULL: the frames form */
+  const int32_t* image_index;                            /* dev [B], frames form */
+  const int64_t* bits_offsets;                           /* dev [B], frames form */
+  int32_t* runs;                                         /* dev [B]: first stage */
+  int64_t* offsets;                                      /* dev [B+1]: written by the first stage, read by the second */
+  int32_t* counts;                                       /* dev [capacity]: second stage */
+  int32_t* status;                                       /* dev [B]: second stage */
+  int64_t capacity;                                      /* counts the array holds */
+  void* workspace; void* stream;
+} la3d_rle_encode_args;
+size_t la3d_rle_encode_workspace_bytes(int B, int H, int W);
+int la3d_rle_encode_offsets(const la3d_rle_encode_args* args);
+int la3d_rle_encode(const la3d_rle_encode_args* args);
+
 /* ---- crop-space masks as bit planes ------------------------------------------------------------------------------------
  * restore_mask_from_crop for a batch (reference src/util.py:171-214; the box stage calls it per object, src/batch_scripts/
  * whole.py:72-105): the S x S mask of a crop - or the alpha channel of its RGBA image, thresholded - resized by nearest index to
@@ -690,6 +750,9 @@ int la3d_pack_crop_bits_frames(const uint8_t* crops, int64_t crop_stride, int32_
 /* HOST helper: COCO compressed RLE string (pycocotools rleFrString) -> run lengths.  Returns the number of
  * counts written, or -1 (malformed string / cap too small). */
 int la3d_rle_from_string_host(const char* s, int64_t len, int32_t* counts, int cap);
+/* HOST helper, the inverse: run lengths -> COCO compressed RLE string (pycocotools rleToString), byte for byte, without a
+ * terminating NUL.  Returns the bytes written (at most 7 per count), or -1 (bad argument / cap too small: out then holds a prefix). */
+int64_t la3d_rle_to_string_host(const int32_t* counts, int64_t n, char* out, int64_t cap);
 
 /* ---- box consumers: the step immediately downstream of the path ----------------------------
  * Reference src/tools/combine_results.py: the 8 corners of each record are projected with the image's K

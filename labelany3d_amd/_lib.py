@@ -78,7 +78,25 @@ ALIGN_RANSAC_MAX_N, ALIGN_RANSAC_MAX_TRIALS = 1 << 24, 1024
 
 CLOUD_OK, CLOUD_NO_ROOM, CLOUD_MISMATCH = 0, 1, 2  # status of la3d_gather_instance_points (5 = BOX_UNSUPPORTED: a refused frames row)
 
+
+class RleEncodeArgs(C.Structure):
+    """``la3d_rle_encode_args`` of include/la3d.h (argument block of la3d_rle_encode_offsets / la3d_rle_encode, 120 bytes); field order
+    is the header's."""
+    _fields_ = [("struct_size", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("frame_width", C.c_int32), ("P", C.c_int32),
+                ("mask_bits", C.c_void_p), ("bits_plane_stride", C.c_int64),
+                ("frames", C.c_void_p), ("image_index", C.c_void_p), ("bits_offsets", C.c_void_p),
+                ("runs", C.c_void_p), ("offsets", C.c_void_p), ("counts", C.c_void_p), ("status", C.c_void_p),
+                ("capacity", C.c_int64), ("workspace", C.c_void_p), ("stream", C.c_void_p)]
+
+
+RLE_OK, RLE_NO_ROOM, RLE_MISMATCH = 0, 1, 2        # status of la3d_rle_encode (5 = BOX_UNSUPPORTED: a refused frames row)
+
 _SIGS = {
+    "la3d_rle_encode_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "la3d_rle_encode_offsets": (C.c_int, [C.POINTER(RleEncodeArgs)]),
+    "la3d_rle_encode": (C.c_int, [C.POINTER(RleEncodeArgs)]),
+    "la3d_rle_to_string_host": (C.c_int64, [C.c_void_p, C.c_int64, C.c_char_p, C.c_int64]),
     "la3d_instance_points_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "la3d_instance_point_offsets": (C.c_int, [C.POINTER(CloudArgs)]),
     "la3d_gather_instance_points": (C.c_int, [C.POINTER(CloudArgs)]),

@@ -492,6 +492,27 @@ int la3d_rle_from_string_host(const char* s, int64_t len, int32_t* counts, int c
   return m;
 }
 
+int64_t la3d_rle_to_string_host(const int32_t* counts, int64_t n, char* out, int64_t cap) {
+  // pycocotools rleToString (maskApi.c): the inverse of the above - counts beyond the third as the difference to the count two
+  // places earlier, 5 bits per character from the low end, bit 5 = more follow; the groups end once the rest is all sign
+  if (n < 0 || cap < 0 || (!counts && n > 0) || (!out && cap > 0)) return -1;
+  int64_t p = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    long x = counts[i];
+    if (i > 2) x -= counts[i - 2];
+    int more = 1;
+    while (more) {
+      char c = (char)(x & 0x1f);
+      x >>= 5;
+      more = (c & 0x10) ? x != -1 : x != 0;
+      if (more) c |= 0x20;
+      if (p >= cap) return -1;
+      out[p++] = (char)(c + 48);
+    }
+  }
+  return p;
+}
+
 int la3d_mask_stats_poly(const int32_t* poly_xy, const int64_t* ring_offsets, const int64_t* inst_rings, int B, int H, int W,
                          int boundary, int32_t* stats, void* stream) {
   if (((!poly_xy || !ring_offsets || !inst_rings || !stats) && B > 0) || B < 0 || H <= 0 || W <= 0 || boundary < 0 ||

@@ -4,6 +4,7 @@ routine, one table), the bit planes of their instances and the ``fit_instances_f
 The sources of one frame size live in ``masks``, which re-exports the public names of this module; the call itself in ``fitcall``."""
 from __future__ import annotations
 
+import ctypes as C
 from typing import NamedTuple, Optional
 
 import numpy as np
@@ -13,7 +14,7 @@ from . import _lib
 from ._lib import check, lib
 from .batched import Depth16, _as_dev, _d16_block, _depth16_check, _dev, _ptr, _record, _stream, _upload_many, height_rule_code, padded_width, refuse_depth16
 from .fitcall import FramesDepth, fit_call, mask_source
-from .masks import _D16_DTYPES, _LABEL_NUMPY, _LABEL_TORCH, _LOGIT_DTYPES, _crop_place, _crop_source, _crop_threshold, _label_rows, _rle_counts
+from .masks import _D16_DTYPES, _LABEL_NUMPY, _LABEL_TORCH, _LOGIT_DTYPES, _crop_place, _crop_source, _crop_threshold, _label_rows, _rle_capacity, _rle_counts, _rle_encode_run
 
 FRAME_DTYPE = np.dtype([("depth_offset", "<i8"), ("H", "<i4"), ("W", "<i4"), ("frame_width", "<i4"), ("reserved", "<i4")])
 """One row of the frame table of a frames call: ``la3d_frame`` of include/la3d.h (24 bytes)."""
@@ -692,6 +693,41 @@ def pack_crop_bits_frames(frames, crops, params, image_index, threshold=None, st
                                              _ptr(o), _ptr(offs), _ptr(area), _stream(stream)), "la3d_pack_crop_bits_frames")
     _record(stream, frames.table, v, place, ii, offs, o, area)
     return FrameBits(o, offs, ii, area, frames.table_host, frames.H, frames.W)
+
+
+def rle_encode_bits_frames(frames, bits: FrameBits, capacity=None, stream=None, return_status: bool = False):
+    """``rle_encode_bits`` for the planes of images of DIFFERENT sizes (the frames form of C-ABI ``la3d_rle_encode_offsets`` +
+    ``la3d_rle_encode``): ``frames`` - a ``PackedFrames`` / ``PackedFrames16`` / ``PackedLabels`` / ``PackedMasks`` whose frame table
+    the planes were laid out for (another table: ValueError before any device work) -, ``bits`` the ``FrameBits`` of a frames packer.
+    The runs of instance n are column-major over its OWN image, ``(H_p, W_p)`` unpadded.  Returns ``((counts, offsets), sizes)`` -
+    ``(counts int32, offsets int64 (B+1,))`` on the GPU is what ``fit_instances_frames(rles=...)`` and ``pack_rle_bits_frames`` take;
+    ``sizes`` int32 (B, 2) on the GPU holds the (h, w) of every instance (-1, -1 for a row whose image index lies outside the table;
+    ``rle_objects((counts, offsets), sizes=sizes)`` writes the JSON objects) - and, with ``return_status=True``, ``status`` int32 (B,)
+    as a third item: 0, 1 = no room in ``capacity``, 2 = the planes changed between the stages, 5 = a row whose image index, frame row
+    or plane offset breaks the contract (it gets no runs - decided on the device, never an exception).  ``capacity`` as in
+    ``rle_encode_bits``: None synchronises once for the exact size, an int never does."""
+    who = "rle_encode_bits_frames"
+    _rle_capacity(who, capacity)
+    if not isinstance(frames, (PackedFrames, PackedFrames16, PackedLabels, PackedMasks)):
+        raise ValueError(f"{who}: frames must be a PackedFrames / PackedFrames16 / PackedLabels / PackedMasks")
+    _same_table(frames, bits)
+    dev = _on_gpu(frames.table, bits.bits)
+    B, P = int(bits.offsets.numel()), int(frames.table.shape[0])
+    if B and not P:
+        raise ValueError(f"{who}: instances without a frame table")
+    ii = _as_dev(bits.image_index, torch.int32, dev)
+    a = _lib.RleEncodeArgs(struct_size=C.sizeof(_lib.RleEncodeArgs), B=B, H=max(int(frames.H), 1), W=max(int(frames.W), 1), P=P,
+                           mask_bits=bits.bits.data_ptr(), frames=frames.table.data_ptr() if P else None, image_index=ii.data_ptr() if P else None,
+                           bits_offsets=bits.offsets.data_ptr() if P else None)
+    counts, offsets, status = _rle_encode_run(a, B, dev, capacity, stream, [frames.table, bits.bits, bits.offsets, ii])
+    with torch.cuda.device(dev):
+        if P:
+            ok = (ii >= 0) & (ii < P)
+            hw = frames.table[ii.clamp(0, P - 1).long()][:, [2, 4]]   # (the la3d_frame words: H, frame_width)
+            sizes = torch.where(ok[:, None], hw, torch.full_like(hw, -1))
+        else:
+            sizes = torch.zeros((0, 2), dtype=torch.int32, device=dev)
+    return ((counts, offsets), sizes, status) if return_status else ((counts, offsets), sizes)
 
 
 def fit_instances_frames_masks(frames, masks, K, threshold: float = 0.0, image_index=None, ground=None, sample_idx=None, filter=None,
