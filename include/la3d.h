@@ -747,6 +747,41 @@ int la3d_pack_crop_bits_frames(const uint8_t* crops, int64_t crop_stride, int32_
                                const int32_t* image_index /* dev [B] */, int B, uint32_t* bits, const int64_t* bits_offsets /* dev [B] */,
                                int32_t* area /* dev [B] or NULL */, void* stream);
 
+/* ---- morphology on bit planes ------------------------------------------------------------------------------------------
+ * The mask step between the annotations and the crops (reference src/batch_scripts/get_crops_enhanced.py:68-99): each instance mask
+ * is resized x4 with nearest neighbour, opened with scipy.ndimage.binary_opening(mask, np.ones((7, 7))), dropped when fewer than 6400
+ * pixels survive, and the cv2.boundingRect of what is left gives the (offset_x, offset_y, scale_factor) that "crop-space masks as bit
+ * planes" takes.  la3d_open_bits does the upscale, the opening, the area and the rectangle for a batch of planes in one pass; at
+ * upscale 1 it strips speckle and hairlines from network masks before a fit.
+ * VALUE, per plane.  M = the H x frame_width mask; U = its nearest-neighbour upscale by s = upscale, U[v, u] = M[v / s, u / s] (integer
+ *   division); out = binary_opening(U, ones((k, k))) as SciPy defines it: an erosion, then a dilation, both with border_value = 0 and
+ *   origin 0 - pixels outside the image count as unset.  k is odd, 1 .. 31; k = 1 is the identity.  upscale is 1, 2 or 4: for these
+ *   factors 1 / s is exact in binary floating point, so EVERY nearest rule - OpenCV's floor(x * (1 / s)) included - gives u / s; that
+ *   is why 3 is not offered.  (The opening is pinned to SciPy bit for bit, tests/golden/g19_opening.npz; the nearest rule and the
+ *   rectangle convention are restated, parity unpinned until OpenCV is at hand.)
+ * INPUT.  B planes of "masks as bit planes", stored W pixels wide (rows need not start on a word when W % 32 != 0), bits_plane_stride
+ *   words apart.  Columns at and beyond frame_width are zero by the format's contract and are masked here anyway; the bits of the
+ *   last word past H * W are never read as mask.
+ * OUTPUT.  out_bits (NULL: statistics only): planes of s * H rows stored W_out >= s * frame_width pixels wide, out_plane_stride words
+ *   apart, same format.  Only the la3d_mask_bits_words(s * H, W_out) words of each plane are written; the pad columns and the tail
+ *   bits of the last word are zero.  A 16-byte aligned base with W_out % 128 == 0 and a stride that is a multiple of 4 is written in
+ *   16-byte stores, W_out % 32 == 0 word by word, anything else through a general form that gathers each word from the rows crossing it.
+ * STATISTICS.  stats[b] (NULL: none) = {area, x, y, w, h} of the output plane in output pixels: x, y, w, h as cv2.boundingRect gives
+ *   them for a binary image - the tight box of the set pixels -, 0, 0, 0, 0 for an empty plane.  k = 1, upscale = 1, out_bits = NULL
+ *   is a pure area-and-rectangle pass over planes.
+ * workspace: la3d_open_bits_workspace_bytes(B, H, upscale) bytes (host, no device; 0 for B, H <= 0), 4-byte aligned; needed with
+ *   stats (one record per band of output rows, reduced per instance by a second kernel: two stages, no atomics).  The call takes no
+ *   host synchronisation and can be captured into a HIP graph.
+ * Refused before any launch - LA3D_ERR_ARG: B < 0, H, W <= 0; k even or outside 1 .. 31; upscale not 1, 2 or 4; frame_width outside
+ *   (0, W]; out_bits and stats both NULL; W_out < s * frame_width (with out_bits; without it W_out is not read); with B > 0: bits NULL, workspace NULL with stats, a pointer that
+ *   is not 4-byte aligned, a stride shorter than its plane, or word ranges [bits, bits + B * bits_plane_stride) and [out_bits,
+ *   out_bits + B * out_plane_stride) that overlap (neighbouring bands read each other's halo: the call cannot work in place).
+ *   LA3D_ERR_UNSUPPORTED: s * frame_width > 8192 (a band of rows lives in LDS) or s * H * W_out > 2^28.  B == 0 returns 0, no launch. */
+size_t la3d_open_bits_workspace_bytes(int B, int H, int upscale);
+int la3d_open_bits(const uint32_t* bits, int64_t bits_plane_stride, int B, int H, int W, int frame_width, int k, int upscale,
+                   uint32_t* out_bits /* NULL: statistics only */, int64_t out_plane_stride, int W_out,
+                   int32_t* stats /* dev [B][5] or NULL */, void* workspace, void* stream);
+
 /* HOST helper: COCO compressed RLE string (pycocotools rleFrString) -> run lengths.  Returns the number of
  * counts written, or -1 (malformed string / cap too small). */
 int la3d_rle_from_string_host(const char* s, int64_t len, int32_t* counts, int cap);

@@ -93,6 +93,9 @@ class RleEncodeArgs(C.Structure):
 RLE_OK, RLE_NO_ROOM, RLE_MISMATCH = 0, 1, 2        # status of la3d_rle_encode (5 = BOX_UNSUPPORTED: a refused frames row)
 
 _SIGS = {
+    "la3d_open_bits_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "la3d_open_bits": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "la3d_rle_encode_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "la3d_rle_encode_offsets": (C.c_int, [C.POINTER(RleEncodeArgs)]),
     "la3d_rle_encode": (C.c_int, [C.POINTER(RleEncodeArgs)]),

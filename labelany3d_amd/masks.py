@@ -966,6 +966,109 @@ def rle_objects(runs, compress: bool = False, sizes=None) -> list:
     return out
 
 
+# ---- morphology on bit planes (include/la3d.h "morphology on bit planes") -------------------------------------------------------------
+def _open_args(who: str, bits, k, upscale) -> MaskBits:
+    if not isinstance(bits, MaskBits):
+        raise ValueError(f"{who}: bits must be a MaskBits (pack_mask_bits, pack_rle_bits, pack_poly_bits, pack_crop_bits, ...)")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 31 or int(k) % 2 == 0:
+        raise ValueError(f"{who}: k must be an odd int in 1 .. 31, not {k!r}")
+    if isinstance(upscale, bool) or not isinstance(upscale, (int, np.integer)) or int(upscale) not in (1, 2, 4):
+        raise ValueError(f"{who}: upscale must be 1, 2 or 4 (factors whose nearest-neighbour rule is u // s under every convention), not {upscale!r}")
+    mb = _mask_bits(bits)
+    if mb.H <= 0:
+        raise ValueError(f"{who}: the planes state an empty frame {(mb.H, mb.W)}")
+    return mb
+
+
+def _open_run(who: str, mb: MaskBits, k: int, s: int, W_out: int, out, want_stats: bool, stream):
+    """One ``la3d_open_bits`` call on checked arguments -> (out, stats); ``out`` None: statistics only."""
+    B, dev = int(mb.bits.shape[0]), mb.bits.device
+    out_stride = 0 if out is None else _bits_stride(out, B, s * mb.H, W_out)
+    with torch.cuda.device(dev):
+        stats = ws = None
+        if want_stats:
+            stats = torch.empty((B, 5), dtype=torch.int32, device=dev)
+            ws = torch.empty(max(int(lib.la3d_open_bits_workspace_bytes(B, mb.H, s)) // 4, 1), dtype=torch.int32, device=dev)
+        if B:   # (an empty batch has no planes to point at)
+            check(lib.la3d_open_bits(_ptr(mb.bits), _bits_stride(mb.bits, B, mb.H, mb.W), B, mb.H, mb.W, mb.frame_width, k, s,
+                                     _ptr(out), out_stride, W_out, _ptr(stats), _ptr(ws), _stream(stream)), "la3d_open_bits")
+    _record(stream, mb.bits, out, stats, ws)
+    return out, stats
+
+
+def open_bits(bits: MaskBits, k: int = 7, upscale: int = 1, frame_pad: bool = True, stream=None, out=None, return_stats: bool = False):
+    """Binary opening of bit planes on the GPU (C-ABI ``la3d_open_bits``): ``scipy.ndimage.binary_opening(U, np.ones((k, k)))`` of the
+    nearest-neighbour upscale ``U[v, u] = M[v // s, u // s]`` of every plane, ``s = upscale`` - the crop stage's mask step (reference
+    src/batch_scripts/get_crops_enhanced.py:68-88: x4, k = 7); at ``upscale=1`` it strips speckle and hairlines from network masks
+    before a fit.  ``k``: odd, 1 .. 31 (1 = identity); ``upscale``: 1, 2 or 4.  Returns ``MaskBits`` of ``s*H`` rows and ``s*frame_width``
+    image columns, stored ``padded_width(s*frame_width)`` wide with ``frame_pad`` (else unpadded) - or ``(MaskBits, stats)`` with
+    ``return_stats``: ``stats`` int32 (B, 5) on the device, ``area, x, y, w, h`` of each opened plane (``cv2.boundingRect``'s
+    convention; zeros for an empty plane).  ``out``: an int32 (B, >= words) device tensor to fill; it must not overlap the input (the
+    call cannot work in place).  No host synchronisation; capturable."""
+    who = "open_bits"
+    mb = _open_args(who, bits, k, upscale)
+    k, s = int(k), int(upscale)
+    B, dev = int(mb.bits.shape[0]), mb.bits.device
+    fw = s * mb.frame_width
+    W_out = padded_width(fw) if frame_pad else fw
+    if out is not None and isinstance(out, torch.Tensor) and out.device != dev:
+        raise ValueError(f"{who}: out lives on another device")
+    o = _bits_out(out, B, s * mb.H, W_out, dev)
+    o, stats = _open_run(who, mb, k, s, W_out, o, bool(return_stats), stream)
+    res = MaskBits(o, s * mb.H, W_out, fw)
+    return (res, stats) if return_stats else res
+
+
+def bits_rects(bits: MaskBits, stream=None) -> torch.Tensor:
+    """``MaskBits`` -> int32 (B, 5) on the device: ``area, x, y, w, h`` of every plane - the statistics-only call of ``la3d_open_bits``
+    with ``k = 1, upscale = 1`` (nothing but the planes is read, no plane is written)."""
+    mb = _open_args("bits_rects", bits, 1, 1)
+    return _open_run("bits_rects", mb, 1, 1, mb.frame_width, None, True, stream)[1]
+
+
+def crop_params(stats, crop_size: int = 512, upscale: int = 4, ratio: float = 0.7) -> np.ndarray:
+    """The crop parameters of the reference's crop stage from the rectangles of opened planes: ``stats`` (B, 5) ``area, x, y, w, h``
+    (``open_bits(..., return_stats=True)``, ``bits_rects``; a (B, 4) array is taken as ``x, y, w, h``) -> float64 (B, 3) rows
+    ``(offset_x, offset_y, scale_factor)``, what ``crop_placement`` / ``pack_crop_bits`` take.  Host arithmetic on Python numbers,
+    exactly the reference's (``crop_object``, src/util.py:142-157, then src/batch_scripts/get_crops_enhanced.py:98):
+    ``side = int(max(w, h) / ratio)``, ``ox = x + (w - side) / 2``, ``oy = y + (h - side) / 2``, ``sf = crop_size / side``; the row is
+    ``[ox / upscale, oy / upscale, sf * upscale]`` - the rectangle is measured on the upscaled image, the parameters speak of the
+    original one.  Rows with ``w == 0`` (an empty plane) are NaN."""
+    a = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats)
+    if a.ndim != 2 or a.shape[1] not in (4, 5):
+        raise ValueError(f"crop_params: stats must be (B, 5) area, x, y, w, h or (B, 4) x, y, w, h, got {a.shape}")
+    if not (crop_size > 0 and upscale > 0 and ratio > 0):
+        raise ValueError("crop_params: crop_size, upscale and ratio must be positive")
+    out = np.full((a.shape[0], 3), np.nan, np.float64)
+    for n, row in enumerate(a[:, -4:].tolist()):
+        x, y, w, h = (int(v) for v in row)
+        if w <= 0 or h <= 0:
+            continue
+        side = int(max(w, h) / ratio)
+        ox, oy, sf = x + (w - side) / 2, y + (h - side) / 2, crop_size / side
+        out[n] = [ox / upscale, oy / upscale, sf * upscale]
+    return out
+
+
+def select_crops(bits: MaskBits, min_area: int = 6400, k: int = 7, upscale: int = 4, crop_size: int = 512, stream=None):
+    """The instance selection of the reference's crop stage (src/batch_scripts/get_crops_enhanced.py:68-99) for a batch of planes:
+    ``open_bits(bits, k, upscale)``, then ``keep = area >= min_area`` and ``crop_params`` of the rectangles -> ``(keep, params, stats,
+    opened)``: ``keep`` bool (B,) and ``params`` float64 (B, 3) NumPy arrays (NaN rows for empty planes), ``stats`` int32 (B, 5) on the
+    device, ``opened`` the ``MaskBits`` of the opened, upscaled planes.  The defaults are the reference's gate (x4, 7 x 7, 6400
+    surviving pixels, 512-pixel crops); one device-to-host copy (the statistics).  The reference walks the instances LAST TO FIRST and
+    appends the boxes it keeps to ``bboxes.json`` in that order: rows here stay in the caller's order, and the order of
+    ``bboxes.json`` is the caller's business."""
+    if isinstance(min_area, bool) or not isinstance(min_area, (int, np.integer)) or int(min_area) < 0:
+        raise ValueError(f"select_crops: min_area must be an int >= 0, not {min_area!r}")
+    if isinstance(crop_size, bool) or not isinstance(crop_size, (int, np.integer)) or int(crop_size) <= 0:
+        raise ValueError(f"select_crops: crop_size must be an int > 0, not {crop_size!r}")
+    opened, stats = open_bits(bits, k=k, upscale=upscale, frame_pad=True, stream=stream, return_stats=True)
+    if stream is not None and stream != torch.cuda.current_stream():
+        stream.synchronize()
+    host = stats.cpu().numpy()
+    return host[:, 0] >= int(min_area), crop_params(host, crop_size=int(crop_size), upscale=int(upscale)), stats, opened
+
+
 def fit_instances_bits(depth, bits, K, ground=None, sample_idx=None, image_index=None, stream=None, device=None, filter=None,
                        image_size=None, area_hint=None, frame_width=None, method: str = "pca", height_rule: str = "rows"):
     """fit_instances with the masks given as bit planes (``pack_mask_bits`` / ``pack_logits_bits``; C-ABI
