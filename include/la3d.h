@@ -781,6 +781,41 @@ size_t la3d_open_bits_workspace_bytes(int B, int H, int upscale);
 int la3d_open_bits(const uint32_t* bits, int64_t bits_plane_stride, int B, int H, int W, int frame_width, int k, int upscale,
                    uint32_t* out_bits /* NULL: statistics only */, int64_t out_plane_stride, int W_out,
                    int32_t* stats /* dev [B][5] or NULL */, void* workspace, void* stream);
+/* la3d_open_bits_frames: the same VALUE and STATISTICS for the planes of images of DIFFERENT sizes in one call ("images of different
+ * sizes in one call": the la3d_frame table, P rows, and its bounds H, W - the largest rows and the largest pitch).  One k and one
+ * upscale per call; the structuring element is a square.
+ * INPUT.  Row n belongs to image image_index[n]; its plane lies at bits + bits_offsets[n] and holds the H_f * W_f / 32 words of that
+ *   image's frame row (H_f rows, pitch W_f - a multiple of 32 -, frame_width fw_f image columns).  Columns at and beyond fw_f count as
+ *   zero whatever the plane holds, and so does everything outside rows [0, H_f).  bits_words: the words of the buffer at bits.
+ * OUTPUT.  out_bits (NULL: statistics only): the plane of row n at out_bits + out_offsets[n], in the layout the frame table of an
+ *   image of size (s * H_f, s * fw_f) has: s * H_f rows, pitch roundup32(s * fw_f), frame_width s * fw_f.  A conforming row writes
+ *   exactly the s * H_f * roundup32(s * fw_f) / 32 words of its plane - the bits of the padding columns zero - and nothing else.  The
+ *   planes must not overlap each other; out_words: the words of the buffer at out_bits.
+ * CHECKED ON THE DEVICE, per row, every value wave-uniform and before an address is formed from it, in this order: image_index[n]
+ *   inside [0, P); the frame row against the la3d_frame contract and the bounds (the check of the fit); bits_offsets[n] >= 0 and a
+ *   multiple of 4; out_offsets[n] likewise (with out_bits); then that the planes end inside their buffers: bits_offsets[n] + words
+ *   <= bits_words and out_offsets[n] + words <= out_words.  A refused row reads nothing, writes no plane word and gets the statistics
+ *   row -1, 0, 0, 0, 0: area -1 tells it from an empty plane (0, 0, 0, 0, 0), and area >= min_area stays false for it.
+ * workspace: la3d_open_bits_frames_workspace_bytes(B, H, upscale) bytes with H the bound (host, no device; 0 for B, H <= 0), 4-byte
+ *   aligned, needed with stats.  Nothing depends on what it held before: only band records this call wrote are read.  Two kernels
+ *   (the bands of the bounds for every row - a row with fewer bands leaves the rest idle -, then one wave per row for the
+ *   statistics), no atomics, no host synchronisation: the call can be captured into a HIP graph.
+ * PARITY.  The opening is pinned to SciPy bit for bit (tests/golden/g19_opening.npz); the nearest rule and the rectangle convention
+ *   are restated, parity unpinned, as for la3d_open_bits.
+ * Refused before any launch, for B == 0 too - LA3D_ERR_ARG: B, P < 0, bounds H, W <= 0; k even or outside 1 .. 31; upscale not 1, 2
+ *   or 4; out_bits and stats both NULL; bits_words < 0, out_words < 0 with out_bits; bits or out_bits not 16-byte aligned;
+ *   bits_offsets, out_offsets or frames not 8-byte aligned; stats, workspace or image_index not 4-byte aligned; the word ranges
+ *   [bits, bits + bits_words) and [out_bits, out_bits + out_words) overlapping (the call cannot work in place); and with B > 0: bits,
+ *   bits_offsets, image_index or - with P > 0 - frames NULL, out_offsets NULL with out_bits, workspace NULL with stats.
+ *   LA3D_ERR_UNSUPPORTED: upscale * W > 8192, upscale * H * roundup32(upscale * W) > 2^28, B * bands > 2^31 - 1.
+ *   B == 0 returns 0 with nothing launched.  P == 0 with B > 0: every row is refused - no plane kernel runs, the statistics rows (if
+ *   asked for) are -1, 0, 0, 0, 0. */
+size_t la3d_open_bits_frames_workspace_bytes(int B, int H /* bound */, int upscale);
+int la3d_open_bits_frames(const uint32_t* bits, int64_t bits_words, const int64_t* bits_offsets /* dev [B] */,
+                          const la3d_frame* frames, int32_t P, int H, int W /* bounds of the table */,
+                          const int32_t* image_index /* dev [B] */, int B, int k, int upscale,
+                          uint32_t* out_bits /* NULL: statistics only */, int64_t out_words, const int64_t* out_offsets /* dev [B] */,
+                          int32_t* stats /* dev [B][5] or NULL */, void* workspace, void* stream);
 
 /* HOST helper: COCO compressed RLE string (pycocotools rleFrString) -> run lengths.  Returns the number of
  * counts written, or -1 (malformed string / cap too small). */

@@ -96,6 +96,9 @@ _SIGS = {
     "la3d_open_bits_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "la3d_open_bits": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int,
                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "la3d_open_bits_frames_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "la3d_open_bits_frames": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "la3d_rle_encode_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "la3d_rle_encode_offsets": (C.c_int, [C.POINTER(RleEncodeArgs)]),
     "la3d_rle_encode": (C.c_int, [C.POINTER(RleEncodeArgs)]),

@@ -979,6 +979,9 @@ __global__ __launch_bounds__(NT_DEC) void rle_encode_emit_kernel(const BitsOut c
 //   the OR of k rows of B (vertical dilation) is the output word, formed in registers, counted for the statistics and stored.
 // Rows and columns outside the image are zero (SciPy's border_value = 0): an erosion window that leaves the image holds its own
 // centre, which is zero, so nothing beyond the zero rows of A and the masked last word is needed.
+// FRAMES (la3d_open_bits_frames, images of different sizes): the same passes on a geometry formed per instance from its la3d_frame row
+// (open_instance, all of it wave-uniform: SGPRs); ONE band plan per call, from the bounds - the grid has the bounds' bands for every
+// instance and LDS is requested for the bounds, an instance uses its own words per row of it.
 constexpr int OPEN_NT = 256;
 struct OpenArgs {
   const unsigned* bits; long long stride;   // input planes, words apart
@@ -990,6 +993,10 @@ struct OpenArgs {
   int nwords_out;                           // words of an output plane
   int R, nA, nbands, vec;                   // band rows; rows of A; bands per plane; 16-byte stores allowed
   int* partial;                             // [B][nbands][8] or NULL
+  // frames form (H, W: the bounds of the table; the fields above that speak of a plane are then formed per instance, open_instance)
+  const long long* offsets; const long long* out_offsets;   // [B] words from bits / out to the plane of each instance
+  const la3d_frame* frames; const int* image_index; int P;
+  long long bits_words, out_words;          // words of the two buffers: a plane that does not end inside its buffer is refused
 };
 
 __device__ inline unsigned spread_bits(unsigned x, int s) {   // the low 32 / s bits of x, each repeated s times
@@ -1048,16 +1055,57 @@ struct OpenItem {
   }
 };
 
-__global__ __launch_bounds__(OPEN_NT) void open_bits_kernel(const OpenArgs a) {
+// The plane geometry of instance b.  Uniform form: the argument block's own, planes a stride apart.  Frames form: formed here from the
+// la3d_frame row of image_index[b] - every value wave-uniform, through scalar loads, checked before an address is formed from it, in
+// the order of frames_prologue (image index, frame row, input offset), then the output offset (the same rule), then that either plane
+// ends inside its buffer.  The output plane is the one frame_table lays out for an image of (s * H, s * fw): pitch roundup32(s * fw),
+// so its rows are whole words.  false: refused - nothing is read, nothing is written.
+template <bool FRAMES>
+__device__ inline bool open_instance(const OpenArgs& a, int b, OpenArgs* g, const unsigned** plane, unsigned** op) {
+  if constexpr (FRAMES) {
+    FramesWork f;
+    if (!frames_prologue<true, false>(a.frames, a.P, a.image_index, a.H, a.W, const_cast<unsigned*>(a.bits), a.offsets, b, 0, &f)) return false;
+    long long oo = 0;
+    if (a.out && !frames_plane_at(a.out_offsets, b, &oo)) return false;
+    const int fw_out = a.s * f.r.fw, W_out = (fw_out + 31) & ~31, H_out = a.s * f.r.H;
+    const int words_out = H_out * (W_out >> 5);          // (<= 2^23: the entry bounds s * H * roundup32(s * W) by 2^28)
+    if (f.off > a.bits_words - f.nwords) return false;
+    if (a.out && oo > a.out_words - words_out) return false;
+    g->H = f.r.H; g->W = f.r.W; g->fw = f.r.fw; g->nwords_in = f.nwords;
+    g->H_out = H_out; g->W_out = W_out; g->nw = W_out >> 5; g->nwords_out = words_out;
+    g->vec = (W_out & 127) == 0;                         // (out is 16-byte aligned - checked on the host - and the offset a multiple of 4)
+    *plane = a.bits + f.off;                             // (formed only now: after the last check)
+    *op = a.out ? a.out + oo : nullptr;
+  } else {
+    *plane = a.bits + (long long)b * a.stride;
+    *op = a.out ? a.out + (long long)b * a.out_stride : nullptr;
+  }
+  return true;
+}
+
+template <bool FRAMES>
+__global__ __launch_bounds__(OPEN_NT) void open_bits_kernel(const OpenArgs call) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ int red[5 * (OPEN_NT / 64)];
+  const int tid = threadIdx.x, b = blockIdx.x / call.nbands, band = blockIdx.x - b * call.nbands;
+  // frames form: the grid has the bands of the bounds; a workgroup of a refused instance, or whose band lies below its instance's last
+  // row, ends here (uniform: before any barrier)
+  OpenArgs own;
+  const unsigned* plane;
+  unsigned* op;
+  if constexpr (FRAMES) {
+    own = call;
+    if (!open_instance<true>(call, b, &own, &plane, &op)) return;
+    if (band * call.R >= own.H_out) return;
+  } else {
+    open_instance<false>(call, b, nullptr, &plane, &op);
+  }
+  const OpenArgs& a = FRAMES ? own : call;
   unsigned* A = reinterpret_cast<unsigned*>(smem);
   unsigned* Bv = A + (size_t)a.nA * a.nw;
-  const int tid = threadIdx.x, b = blockIdx.x / a.nbands, band = blockIdx.x - b * a.nbands;
   const int r = a.k >> 1, s = a.s, nw = a.nw, k = a.k;
   const int r0 = band * a.R;
   const int rows = min(a.R, a.H_out - r0);            // output rows of this band (>= 1)
-  const unsigned* plane = a.bits + (long long)b * a.stride;
   // floor((r0 - 2r) / s): the first source row of A (negative above the image)
   const int t0 = r0 - 2 * r;
   const int ls = s >> 1;                               // log2 s for s = 1, 2, 4: x >> ls is floor(x / s), negative x included
@@ -1120,8 +1168,7 @@ __global__ __launch_bounds__(OPEN_NT) void open_bits_kernel(const OpenArgs a) {
     ymin = min(ymin, r0 + v); ymax = max(ymax, r0 + v);
     xmin = min(xmin, wc * 32 + __ffs((int)x) - 1); xmax = max(xmax, wc * 32 + 31 - __clz((int)x));
   };
-  unsigned* op = a.out ? a.out + (long long)b * a.out_stride : nullptr;
-  const bool aligned = (a.W_out & 31) == 0;
+  const bool aligned = (a.W_out & 31) == 0;           // (frames form: always)
   if (op && aligned && a.vec) {                        // rows of whole words, 16-byte stores: four words per thread
     const int wq = a.W_out >> 7;                       // (vec: W_out % 128 == 0)
     u32x4* o4 = reinterpret_cast<u32x4*>(op + (long long)r0 * (a.W_out >> 5));
@@ -1145,7 +1192,7 @@ __global__ __launch_bounds__(OPEN_NT) void open_bits_kernel(const OpenArgs a) {
     // plane is gathered from the rows that cross it
     if (a.partial)
       for (OpenItem i(tid, nw); i.it < rows * nw; i.next(nw)) count(i.row, i.col, word(i.row, i.col));
-    if (op) {
+    if (!FRAMES && op) {
       const long long bit0 = (long long)r0 * a.W_out;                       // a multiple of 32
       const int w0 = (int)(bit0 >> 5);
       const int w1 = (int)min((long long)a.nwords_out, (bit0 + (long long)a.R * a.W_out) >> 5);
@@ -1185,9 +1232,7 @@ __global__ __launch_bounds__(OPEN_NT) void open_bits_kernel(const OpenArgs a) {
 
 // the band records of one instance -> stats[b] = area, x, y, w, h (cv2.boundingRect of a binary image; 0, 0, 0, 0 when empty): one
 // wave per instance, every band record has one writer and one reader - no atomics
-__global__ __launch_bounds__(64) void open_bits_stats_kernel(const int* __restrict__ partial, int nbands, int* __restrict__ stats) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  const int* p = partial + (long long)b * nbands * 8;
+__device__ inline void open_stats_reduce(const int* __restrict__ p, int nbands, int lane, int* __restrict__ o) {
   int area = 0, ymin = 0x7fffffff, ymax = -1, xmin = 0x7fffffff, xmax = -1;
   for (int i = lane; i < nbands; i += 64) {
     area += p[i * 8]; ymin = min(ymin, p[i * 8 + 1]); ymax = max(ymax, p[i * 8 + 2]);
@@ -1195,10 +1240,27 @@ __global__ __launch_bounds__(64) void open_bits_stats_kernel(const int* __restri
   }
   area = wave_sum_i(area); ymin = wave_min_i(ymin); ymax = wave_max_i(ymax); xmin = wave_min_i(xmin); xmax = wave_max_i(xmax);
   if (lane == 0) {
-    int* o = stats + (long long)b * 5;
     const bool any = area > 0;
     o[0] = area; o[1] = any ? xmin : 0; o[2] = any ? ymin : 0; o[3] = any ? xmax - xmin + 1 : 0; o[4] = any ? ymax - ymin + 1 : 0;
   }
+}
+__global__ __launch_bounds__(64) void open_bits_stats_kernel(const int* __restrict__ partial, int nbands, int* __restrict__ stats) {
+  const int b = blockIdx.x;
+  open_stats_reduce(partial + (long long)b * nbands * 8, nbands, threadIdx.x, stats + (long long)b * 5);
+}
+// frames form: the decision of open_bits_kernel<true> made again, then only the records the instance's own bands wrote in this call
+// (the grid's further bands wrote none); a refused row gets -1, 0, 0, 0, 0
+__global__ __launch_bounds__(64) void open_bits_frames_stats_kernel(const OpenArgs call, int* __restrict__ stats) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  int* o = stats + (long long)b * 5;
+  OpenArgs own = call;
+  const unsigned* plane;
+  unsigned* op;
+  if (!open_instance<true>(call, b, &own, &plane, &op)) {
+    if (lane < 5) o[lane] = lane ? 0 : -1;
+    return;
+  }
+  open_stats_reduce(call.partial + (long long)b * call.nbands * 8, (own.H_out + call.R - 1) / call.R, lane, o);
 }
 
 }  // namespace
@@ -1834,12 +1896,62 @@ int la3d_open_bits(const uint32_t* bits, int64_t bits_plane_stride, int B, int H
   a.vec = (out_bits && W_out % 128 == 0 && (reinterpret_cast<uintptr_t>(out_bits) & 15) == 0 && out_plane_stride % 4 == 0) ? 1 : 0;
   a.partial = stats ? static_cast<int*>(workspace) : nullptr;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  allow_big_lds(reinterpret_cast<const void*>(open_bits_kernel));
-  hipLaunchKernelGGL(open_bits_kernel, dim3((unsigned)((long long)B * p.nbands)), dim3(OPEN_NT), p.lds, st, a);
+  allow_big_lds(reinterpret_cast<const void*>(open_bits_kernel<false>));
+  hipLaunchKernelGGL(open_bits_kernel<false>, dim3((unsigned)((long long)B * p.nbands)), dim3(OPEN_NT), p.lds, st, a);
   const int rc = check_launch("open_bits_kernel");
   if (rc != LA3D_SUCCESS || !stats) return rc;
   hipLaunchKernelGGL(open_bits_stats_kernel, dim3((unsigned)B), dim3(64), 0, st, a.partial, p.nbands, stats);
   return check_launch("open_bits_stats_kernel");
+}
+
+size_t la3d_open_bits_frames_workspace_bytes(int B, int H, int upscale) { return la3d_open_bits_workspace_bytes(B, H, upscale); }
+
+int la3d_open_bits_frames(const uint32_t* bits, int64_t bits_words, const int64_t* bits_offsets, const la3d_frame* frames, int32_t P, int H,
+                          int W, const int32_t* image_index, int B, int k, int upscale, uint32_t* out_bits, int64_t out_words,
+                          const int64_t* out_offsets, int32_t* stats, void* workspace, void* stream) {
+  const char* who = "la3d_open_bits_frames";
+  const int s = upscale;
+  auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+  if (B < 0 || P < 0 || H <= 0 || W <= 0) return pack_refuse(who, SIZES_FRAMES);
+  if (k < 1 || k > 31 || !(k & 1)) return pack_refuse(who, "k must be odd and lie in 1 .. 31");
+  if (s != 1 && s != 2 && s != 4) return pack_refuse(who, "upscale must be 1, 2 or 4");
+  if (!out_bits && !stats) return pack_refuse(who, "nothing to do: out_bits and stats are both NULL");
+  if (bits_words < 0 || (out_bits && out_words < 0)) return pack_refuse(who, "bits_words and out_words must not be negative");
+  if (B > 0) {
+    if (!bits || !bits_offsets || (!frames && P > 0) || !image_index) return pack_refuse(who, "NULL bits, bits_offsets, frames or image_index");
+    if (out_bits && !out_offsets) return pack_refuse(who, "out_offsets must not be NULL with out_bits");
+    if (stats && !workspace) return pack_refuse(who, "workspace must not be NULL with stats");
+  }
+  if ((at(bits) | at(out_bits)) & 15) return pack_refuse(who, "bits or out_bits not a 16-byte aligned pointer");
+  if ((at(bits_offsets) | at(out_offsets) | at(frames)) & 7) return pack_refuse(who, "bits_offsets, out_offsets or frames not an 8-byte aligned pointer");
+  if ((at(stats) | at(workspace) | at(image_index)) & 3) return pack_refuse(who, "stats, workspace or image_index not a 4-byte aligned pointer");
+  if (bits && out_bits) {   // neighbouring bands read each other's halo: the call cannot work in place
+    const uintptr_t i0 = at(bits), i1 = i0 + (uintptr_t)bits_words * 4, o0 = at(out_bits), o1 = o0 + (uintptr_t)out_words * 4;
+    if (i0 < o1 && o0 < i1) return pack_refuse(who, "the input buffer and the output buffer overlap");
+  }
+  if ((long long)s * W > 8192) return pack_refuse(who, "upscale * W must not exceed 8192 (a band of rows lives in LDS)", LA3D_ERR_UNSUPPORTED);
+  const long long W_out = ((long long)s * W + 31) / 32 * 32;
+  if ((long long)s * H > (1LL << 28) || (long long)s * H * W_out > (1LL << 28))
+    return pack_refuse(who, "upscale * H * roundup32(upscale * W) must not exceed 2^28", LA3D_ERR_UNSUPPORTED);
+  const OpenPlan p = open_plan(s * H, (int)(W_out / 32), k, s);   // one plan per call, from the bounds
+  if ((long long)B * p.nbands > 0x7fffffffLL) return pack_refuse(who, "too many bands for one launch (B * bands > 2^31 - 1)", LA3D_ERR_UNSUPPORTED);
+  if (B == 0) return LA3D_SUCCESS;
+  OpenArgs a = {};
+  a.bits = bits; a.H = H; a.W = W; a.k = k; a.s = s; a.out = out_bits;
+  a.R = p.R; a.nA = p.nA; a.nbands = p.nbands;
+  a.partial = stats ? static_cast<int*>(workspace) : nullptr;
+  a.offsets = reinterpret_cast<const long long*>(bits_offsets); a.out_offsets = reinterpret_cast<const long long*>(out_offsets);
+  a.frames = frames; a.image_index = image_index; a.P = P; a.bits_words = bits_words; a.out_words = out_bits ? out_words : 0;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (P > 0) {   // (no image: every row is refused, which the statistics kernel alone says)
+    allow_big_lds(reinterpret_cast<const void*>(open_bits_kernel<true>));
+    hipLaunchKernelGGL(open_bits_kernel<true>, dim3((unsigned)((long long)B * p.nbands)), dim3(OPEN_NT), p.lds, st, a);
+    const int rc = check_launch("open_bits_kernel");
+    if (rc != LA3D_SUCCESS) return rc;
+  }
+  if (!stats) return LA3D_SUCCESS;
+  hipLaunchKernelGGL(open_bits_frames_stats_kernel, dim3((unsigned)B), dim3(64), 0, st, a, stats);
+  return check_launch("open_bits_frames_stats_kernel");
 }
 
 }  // extern "C"

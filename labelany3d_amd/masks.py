@@ -967,13 +967,24 @@ def rle_objects(runs, compress: bool = False, sizes=None) -> list:
 
 
 # ---- morphology on bit planes (include/la3d.h "morphology on bit planes") -------------------------------------------------------------
-def _open_args(who: str, bits, k, upscale) -> MaskBits:
-    if not isinstance(bits, MaskBits):
-        raise ValueError(f"{who}: bits must be a MaskBits (pack_mask_bits, pack_rle_bits, pack_poly_bits, pack_crop_bits, ...)")
+def _open_scalars(who: str, k, upscale) -> None:   # the k and upscale of an opening, of either form
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 31 or int(k) % 2 == 0:
         raise ValueError(f"{who}: k must be an odd int in 1 .. 31, not {k!r}")
     if isinstance(upscale, bool) or not isinstance(upscale, (int, np.integer)) or int(upscale) not in (1, 2, 4):
         raise ValueError(f"{who}: upscale must be 1, 2 or 4 (factors whose nearest-neighbour rule is u // s under every convention), not {upscale!r}")
+
+
+def _gate_scalars(who: str, min_area, crop_size) -> None:   # the gate of select_crops, of either form
+    if isinstance(min_area, bool) or not isinstance(min_area, (int, np.integer)) or int(min_area) < 0:
+        raise ValueError(f"{who}: min_area must be an int >= 0, not {min_area!r}")
+    if isinstance(crop_size, bool) or not isinstance(crop_size, (int, np.integer)) or int(crop_size) <= 0:
+        raise ValueError(f"{who}: crop_size must be an int > 0, not {crop_size!r}")
+
+
+def _open_args(who: str, bits, k, upscale) -> MaskBits:
+    if not isinstance(bits, MaskBits):
+        raise ValueError(f"{who}: bits must be a MaskBits (pack_mask_bits, pack_rle_bits, pack_poly_bits, pack_crop_bits, ...)")
+    _open_scalars(who, k, upscale)
     mb = _mask_bits(bits)
     if mb.H <= 0:
         raise ValueError(f"{who}: the planes state an empty frame {(mb.H, mb.W)}")
@@ -1058,10 +1069,7 @@ def select_crops(bits: MaskBits, min_area: int = 6400, k: int = 7, upscale: int 
     surviving pixels, 512-pixel crops); one device-to-host copy (the statistics).  The reference walks the instances LAST TO FIRST and
     appends the boxes it keeps to ``bboxes.json`` in that order: rows here stay in the caller's order, and the order of
     ``bboxes.json`` is the caller's business."""
-    if isinstance(min_area, bool) or not isinstance(min_area, (int, np.integer)) or int(min_area) < 0:
-        raise ValueError(f"select_crops: min_area must be an int >= 0, not {min_area!r}")
-    if isinstance(crop_size, bool) or not isinstance(crop_size, (int, np.integer)) or int(crop_size) <= 0:
-        raise ValueError(f"select_crops: crop_size must be an int > 0, not {crop_size!r}")
+    _gate_scalars("select_crops", min_area, crop_size)
     opened, stats = open_bits(bits, k=k, upscale=upscale, frame_pad=True, stream=stream, return_stats=True)
     if stream is not None and stream != torch.cuda.current_stream():
         stream.synchronize()
