@@ -817,6 +817,109 @@ int la3d_open_bits_frames(const uint32_t* bits, int64_t bits_words, const int64_
                           uint32_t* out_bits /* NULL: statistics only */, int64_t out_words, const int64_t* out_offsets /* dev [B] */,
                           int32_t* stats /* dev [B][5] or NULL */, void* workspace, void* stream);
 
+/* ---- mask overlap on bit planes ----------------------------------------------------------------------------------------
+ * What relates two planes of one image: for every GROUP g (an image) and every pair of a row i of A_g and a row j of B_g
+ *     inter[offsets[g] + i * nb_g + j] = popcount(A_i & B_j)   over the words [0, nwords) of the planes,
+ * with the planes' own areas popcount(A_i), popcount(B_j) from the same loads, and on request
+ *     iou = (double)inter / (double)den,  den = area_a + area_b - inter (LA3D_OVERLAP_IOU) | min(area_a, area_b) (LA3D_OVERLAP_IOM) |
+ *           area_a (LA3D_OVERLAP_IOA);  den == 0 gives 0.0.
+ * The planes are those of "masks as bit planes", whatever packer made them.  FRAME CONTRACT: the padding bits of a plane are zero
+ * (every packer writes them so) - ALL words [0, nwords) are counted.  The rows of a group are contiguous in A and in B; B == NULL is
+ * the SELF form (B is A): only the tiles on and above the diagonal are computed and mirrored, the full square matrix is written.
+ *
+ * la3d_mask_overlap_plan - HOST, no device.  From the rows per group of A and of B (counts_b NULL: self) and the words per group
+ *   (group_words NULL: nwords for every group) it writes offsets[G + 1] (offsets[g + 1] - offsets[g] = na_g * nb_g, row-major (i, j))
+ *   and the TILE TABLE: one la3d_overlap_tile per workgroup - up to 8 x 8 planes of one group and the words [w0, w1) of them.  Every
+ *   (group, i, j, word) of the call lies in exactly one tile (self form: every i <= j, the mirror tile standing for the rest).  A call
+ *   with few tiles gets the word range of each tile split into chunks (whole multiples of 1024 words), so that one image still fills
+ *   the chip; the chunks of a tile follow each other in the table.  A group whose other side is empty keeps tiles with nj (ni) = 0:
+ *   they carry its areas.  The caller uploads the rows it got (8-byte aligned) and hands them to la3d_mask_overlap unchanged - the
+ *   kernels trust the table.  tiles NULL: count only.  Returns the number of tiles; -1 (LA3D_ERR_ARG) when capacity is smaller or an
+ *   argument is bad (G < 0, a negative count or word count, offsets NULL); LA3D_ERR_UNSUPPORTED beyond the limits below.
+ * la3d_mask_overlap_workspace_bytes(ntiles) - HOST: 320 bytes per tile (its 64 pair counts and 16 areas); 0 for ntiles <= 0.
+ * la3d_mask_overlap - two kernels on the caller's stream: one workgroup per tile leaves its partial counts in the workspace, then
+ *   one per tile sums the chunks and writes inter, area_a, area_b (i32) and - iou != NULL - iou (f64).  No atomics, nothing is
+ *   pre-cleared by the caller, every element of [0, offsets[G]) is written exactly once and nothing else is; no host synchronisation:
+ *   with its table and workspace the call can be captured into a HIP graph.  Planes are addressed in one of two ways:
+ *   UNIFORM (frames NULL): plane of row r at a_bits + r * a_stride, nwords words, 4-byte aligned; a 16-byte aligned base with a
+ *     stride that is a multiple of 4 (both sides) is read in 16-byte groups, anything else word by word - never a misaligned vector
+ *     load -, with the same results.
+ *   FRAMES (frames != NULL): plane of row r at a_bits + a_offsets[r] (dev i64), group g IS image g of the table (G == P) and its
+ *     planes hold the H_g * W_g / 32 words of frames[g]; a_bits / b_bits 16-byte aligned.  CHECKED ON THE DEVICE, per row, before an
+ *     address is formed: the frame row of its group (the check of the fit, against the bounds H, W) and that its words are the
+ *     plan's; a_image_index[r] == g; a_offsets[r] >= 0 and a multiple of 4; a_offsets[r] + words <= a_words.  A refused row reads
+ *     nothing; every pair of it gets inter -1 and iou NaN, its area is -1.  Never through the call status.
+ *   LA3D_ERR_ARG before any launch: a bad struct_size or kind, G or a row count < 0, NULL or misaligned pointers with work to do,
+ *     a stride below nwords, frames with G != P or bounds <= 0.  LA3D_ERR_UNSUPPORTED: nwords (frames: H * W / 32 of the bounds) above
+ *     2^23 - H * W_stored <= 2^28, so a count fits int32 -, npairs above 2^31 - 1.  ntiles == 0: success, nothing is launched.
+ * la3d_mask_nms - greedy mask NMS on a SELF overlap, one workgroup per group: the rows of group g are visited in the order
+ *   order[row_offsets[g] .. row_offsets[g + 1]) (global row indices; an entry outside its group's rows is skipped).  A kept row t
+ *   suppresses a later row u iff labels is NULL or labels[t] == labels[u], den(t, u) > 0 and
+ *       (double)inter[t, u] > thr * (double)den(t, u)            - a multiply, never a division: host and device agree bit for bit -
+ *   den by kind (LA3D_OVERLAP_IOU or LA3D_OVERLAP_IOM).  keep (u8 [B]) is written for every row: 1 kept, 0 otherwise.  A row with
+ *   area -1 is never kept and suppresses nothing; so is a row the order does not name.  At most 46340 rows per group (its matrix
+ *   has at most 2^31 - 1 pairs); no synchronisation, capturable. */
+#define LA3D_OVERLAP_NONE 0
+#define LA3D_OVERLAP_IOU 1
+#define LA3D_OVERLAP_IOM 2
+#define LA3D_OVERLAP_IOA 3
+#define LA3D_OVERLAP_MIRROR 1   /* la3d_overlap_tile::flags - self form, above the diagonal: the tile is also written transposed */
+#define LA3D_OVERLAP_AREA_A 2   /*   the tile writes area_a of its rows of A */
+#define LA3D_OVERLAP_AREA_B 4   /*   the tile writes area_b of its rows of B */
+typedef struct la3d_overlap_tile {   /* 64 bytes */
+  int32_t g;                         /* group */
+  int32_t i0, j0;                    /* first row of A / of B, within the group */
+  int32_t ni, nj;                    /* rows of A / of B: 0 .. 8 */
+  int32_t row_a, row_b;              /* the same first rows, counted over the whole call */
+  int32_t w0, w1;                    /* words [w0, w1) of the planes */
+  int32_t nw;                        /* words of a plane of the group */
+  int32_t chunk, nchunks;            /* this tile is chunk `chunk` of `nchunks` consecutive rows of the table */
+  int32_t nb;                        /* nb_g: the row length of the group's matrix */
+  int32_t flags;                     /* LA3D_OVERLAP_MIRROR | LA3D_OVERLAP_AREA_A | LA3D_OVERLAP_AREA_B */
+  int64_t out0;                      /* offsets[g] */
+} la3d_overlap_tile;
+typedef struct la3d_mask_overlap_args {
+  int32_t struct_size;                                   /* sizeof(la3d_mask_overlap_args) of the caller */
+  int32_t G;                                             /* groups */
+  int32_t kind;                                          /* LA3D_OVERLAP_*: the denominator of iou (read with iou != NULL) */
+  int32_t P, H, W;                                       /* frames form: rows of the table, its bounds */
+  int64_t rows_a, rows_b;                                /* rows of A, of B (self form: rows_b is not read) */
+  const uint32_t* a_bits; const uint32_t* b_bits;        /* b_bits NULL: the self form - every b_* field is then A's */
+  int64_t a_stride, b_stride; int64_t nwords;            /* uniform form */
+  const la3d_frame* frames;                              /* dev [P] | NULL: the frames form */
+  const int64_t* a_offsets; const int64_t* b_offsets;    /* dev [rows], frames form */
+  const int32_t* a_image_index; const int32_t* b_image_index;   /* dev [rows], frames form */
+  int64_t a_words, b_words;                              /* words of the buffers at a_bits / b_bits, frames form */
+  const la3d_overlap_tile* tiles; int64_t ntiles;        /* dev: the table of la3d_mask_overlap_plan */
+  int64_t npairs;                                        /* offsets[G] of the plan */
+  int32_t* inter;                                        /* dev [npairs] */
+  int32_t* area_a; int32_t* area_b;                      /* dev [rows_a], [rows_b]; self form: area_b may be NULL or area_a */
+  double* iou;                                           /* dev [npairs] | NULL */
+  void* workspace; void* stream;
+} la3d_mask_overlap_args;
+typedef struct la3d_mask_nms_args {
+  int32_t struct_size;                                   /* sizeof(la3d_mask_nms_args) of the caller */
+  int32_t G;                                             /* groups */
+  int32_t kind;                                          /* LA3D_OVERLAP_IOU | LA3D_OVERLAP_IOM */
+  int32_t reserved;
+  int64_t B;                                             /* rows */
+  const int32_t* inter; const int32_t* area;             /* dev: a self overlap and its areas */
+  const int64_t* offsets;                                /* dev [G + 1]: the plan's offsets */
+  const int32_t* row_offsets;                            /* dev [G + 1]: the first row of each group, row_offsets[G] = B */
+  const int32_t* order;                                  /* dev [B] */
+  const int32_t* labels;                                 /* dev [B] | NULL */
+  double thr;
+  uint8_t* keep;                                         /* dev [B] */
+  void* stream;
+} la3d_mask_nms_args;
+int64_t la3d_mask_overlap_plan(int32_t G, const int32_t* counts_a, const int32_t* counts_b /* NULL: self */,
+                               const int64_t* group_words /* NULL: nwords for all */, int64_t nwords,
+                               la3d_overlap_tile* tiles /* host [capacity] | NULL: count only */, int64_t capacity,
+                               int64_t* offsets /* host [G + 1] */);
+size_t la3d_mask_overlap_workspace_bytes(int64_t ntiles);
+int la3d_mask_overlap(const la3d_mask_overlap_args* args);
+int la3d_mask_nms(const la3d_mask_nms_args* args);
+
 /* HOST helper: COCO compressed RLE string (pycocotools rleFrString) -> run lengths.  Returns the number of
  * counts written, or -1 (malformed string / cap too small). */
 int la3d_rle_from_string_host(const char* s, int64_t len, int32_t* counts, int cap);

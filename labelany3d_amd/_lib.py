@@ -92,7 +92,42 @@ class RleEncodeArgs(C.Structure):
 
 RLE_OK, RLE_NO_ROOM, RLE_MISMATCH = 0, 1, 2        # status of la3d_rle_encode (5 = BOX_UNSUPPORTED: a refused frames row)
 
+
+class OverlapTile(C.Structure):
+    """``la3d_overlap_tile`` of include/la3d.h: one row of the tile table of la3d_mask_overlap_plan (64 bytes)."""
+    _fields_ = [("g", C.c_int32), ("i0", C.c_int32), ("j0", C.c_int32), ("ni", C.c_int32), ("nj", C.c_int32),
+                ("row_a", C.c_int32), ("row_b", C.c_int32), ("w0", C.c_int32), ("w1", C.c_int32), ("nw", C.c_int32),
+                ("chunk", C.c_int32), ("nchunks", C.c_int32), ("nb", C.c_int32), ("flags", C.c_int32), ("out0", C.c_int64)]
+
+
+class MaskOverlapArgs(C.Structure):
+    """``la3d_mask_overlap_args`` of include/la3d.h (argument block of la3d_mask_overlap, 208 bytes); field order is the header's."""
+    _fields_ = [("struct_size", C.c_int32), ("G", C.c_int32), ("kind", C.c_int32), ("P", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("rows_a", C.c_int64), ("rows_b", C.c_int64),
+                ("a_bits", C.c_void_p), ("b_bits", C.c_void_p), ("a_stride", C.c_int64), ("b_stride", C.c_int64), ("nwords", C.c_int64),
+                ("frames", C.c_void_p), ("a_offsets", C.c_void_p), ("b_offsets", C.c_void_p),
+                ("a_image_index", C.c_void_p), ("b_image_index", C.c_void_p), ("a_words", C.c_int64), ("b_words", C.c_int64),
+                ("tiles", C.c_void_p), ("ntiles", C.c_int64), ("npairs", C.c_int64),
+                ("inter", C.c_void_p), ("area_a", C.c_void_p), ("area_b", C.c_void_p), ("iou", C.c_void_p),
+                ("workspace", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class MaskNmsArgs(C.Structure):
+    """``la3d_mask_nms_args`` of include/la3d.h (argument block of la3d_mask_nms, 96 bytes); field order is the header's."""
+    _fields_ = [("struct_size", C.c_int32), ("G", C.c_int32), ("kind", C.c_int32), ("reserved", C.c_int32), ("B", C.c_int64),
+                ("inter", C.c_void_p), ("area", C.c_void_p), ("offsets", C.c_void_p), ("row_offsets", C.c_void_p),
+                ("order", C.c_void_p), ("labels", C.c_void_p), ("thr", C.c_double), ("keep", C.c_void_p), ("stream", C.c_void_p)]
+
+
+OVERLAP_NONE, OVERLAP_IOU, OVERLAP_IOM, OVERLAP_IOA = 0, 1, 2, 3      # la3d_mask_overlap_args.kind
+OVERLAP_MIRROR, OVERLAP_AREA_A, OVERLAP_AREA_B = 1, 2, 4              # la3d_overlap_tile.flags
+OVERLAP_TILE, OVERLAP_STEP = 8, 1024                                   # planes per side of a tile; words a chunk is a multiple of
+
 _SIGS = {
+    "la3d_mask_overlap_plan": (C.c_int64, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "la3d_mask_overlap_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "la3d_mask_overlap": (C.c_int, [C.POINTER(MaskOverlapArgs)]),
+    "la3d_mask_nms": (C.c_int, [C.POINTER(MaskNmsArgs)]),
     "la3d_open_bits_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "la3d_open_bits": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int,
                                  C.c_void_p, C.c_void_p, C.c_void_p]),
