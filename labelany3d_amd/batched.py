@@ -60,6 +60,20 @@ def _as_dev(x, dtype, device, cache: bool = False) -> torch.Tensor:
     return torch.as_tensor(np.ascontiguousarray(a), device=device).to(dtype).contiguous()
 
 
+def _plane_source(x, dev, dtypes):
+    """(B,H,W) input of a packer -> (tensor, plane stride in elements): a device tensor whose planes are dense (rows W apart, pixels
+    adjacent) is read where it lies, whatever its plane stride and base alignment; everything else is made contiguous first."""
+    if isinstance(x, torch.Tensor) and x.is_cuda and x.device == dev and x.dim() == 3 and x.dtype in dtypes:
+        B, H, W = x.shape
+        if (W == 1 or x.stride(2) == 1) and (H == 1 or x.stride(1) == W) and (B <= 1 or x.stride(0) >= H * W):
+            t = x.view(torch.uint8) if x.dtype == torch.bool else x
+            return t, (int(x.stride(0)) if B > 1 else H * W)
+    t = _as_dev(x, dtypes[0] if not (isinstance(x, torch.Tensor) and x.dtype in dtypes) else x.dtype, dev)
+    if t.dim() != 3:
+        raise ValueError("expected (B,H,W)")
+    return t, int(t.shape[1] * t.shape[2])
+
+
 def _upload_many(arrays, device, pinned: Optional[torch.Tensor] = None):
     """Several small host arrays -> device tensors with ONE host-to-device copy (each separate upload costs ~17 us of launch
     overhead on this stack; the per-image wrappers have six to eight of them).  ``arrays``: list of (ndarray | None, torch dtype);

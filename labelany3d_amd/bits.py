@@ -1,0 +1,554 @@
+"""Masks as bit planes of ONE frame size per call (include/la3d.h "masks as bit planes" and what followed it): ``MaskBits``, the packers
+(u8 masks, logits, run lengths, polygons), the restore of crop-space masks, the unpacker and the plane statistics, the way back out -
+the run-length encoder (``RleRuns``) -, morphology and the crop gate, and the fit that takes the planes (``fit_instances_bits``).
+Label maps build on this module (``labels``); the mixed-size forms live in ``frames``.  ``masks`` re-exports the public names."""
+from __future__ import annotations
+
+import contextlib
+import ctypes as C
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, lib
+from .batched import (Depth16, _as_dev, _bits_stride, _depth16_check, _dev, _plane_source, _ptr, _record, _stream, _upload_many, height_rule_code,
+                      padded_width)
+from .fitcall import depth_rows_for_bits, fit_call, mask_source
+from .masks import pack_rle
+
+
+class MaskBits(NamedTuple):
+    """Masks as bit planes (include/la3d.h "masks as bit planes"): ``bits`` int32 (B, words) on the GPU - row b holds the
+    ``ceil(H*W/32)`` little-endian words of plane b, pixel (v, u) = bit ``(v*W + u) & 31`` of word ``(v*W + u) >> 5``, i.e.
+    ``np.packbits(mask.reshape(B, -1), axis=1, bitorder="little")`` viewed as uint32 -; ``H``, ``W``: the frame as STORED (rows
+    padded to ``W``); ``frame_width``: the image columns (== W when the rows are not padded)."""
+    bits: torch.Tensor
+    H: int
+    W: int
+    frame_width: int
+
+
+def _mask_bits(bits) -> MaskBits:
+    if not (isinstance(bits, tuple) and len(bits) == 4):
+        raise ValueError("bits must be the (bits, H, W, frame_width) tuple of pack_mask_bits / pack_logits_bits")
+    mb = MaskBits(bits[0], int(bits[1]), int(bits[2]), int(bits[3]))
+    if not 0 < mb.frame_width <= mb.W:
+        raise ValueError("frame_width must lie in (0, W]")
+    _bits_stride(mb.bits, mb.bits.shape[0] if isinstance(mb.bits, torch.Tensor) and mb.bits.dim() == 2 else 0, mb.H, mb.W)
+    return mb
+
+
+def _bits_out(out, B, H, W_out, dev):
+    nwords = (H * W_out + 31) // 32
+    if out is None:
+        return torch.empty((B, nwords), dtype=torch.int32, device=dev)
+    _bits_stride(out, B, H, W_out)
+    return out
+
+
+def pack_mask_bits(masks, frame_pad: bool = True, device=None, stream=None, out=None) -> MaskBits:
+    """(B,H,W) bool / uint8 masks (non-zero = True) -> ``MaskBits`` on the GPU (C-ABI ``la3d_pack_mask_bits``).  ``frame_pad``: rows
+    of a width that is not a multiple of 32 are padded with zero bits to ``padded_width(W)`` - exactly as ``pad_depth_rows`` pads
+    the depth -, which is what the tiled forms of the fit want (``frame_width`` of the result keeps W).  A device tensor with
+    dense planes is read in place (any plane stride, any base alignment).  ``out``: an int32 (B, >= words) device tensor to fill
+    (only the words of each plane are written).  Worth it when the masks are fitted more than once or stay resident: a single
+    fit of a u8 plane that already exists reads fewer bytes through ``fit_instances``."""
+    if device is None and isinstance(masks, torch.Tensor) and masks.is_cuda:
+        device = masks.device
+    dev = _dev(device)
+    m, ps = _plane_source(masks, dev, (torch.uint8, torch.bool))
+    B, H, W = m.shape
+    W_out = padded_width(W) if frame_pad else W
+    o = _bits_out(out, B, H, W_out, dev)
+    with torch.cuda.device(dev):
+        check(lib.la3d_pack_mask_bits(_ptr(m), ps, B, H, W, W_out, _ptr(o), _bits_stride(o, B, H, W_out), _stream(stream)),
+              "la3d_pack_mask_bits")
+    _record(stream, m, o)
+    return MaskBits(o, H, W_out, W)
+
+
+_LOGIT_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
+
+
+def pack_logits_bits(logits, threshold: float = 0.0, frame_pad: bool = True, device=None, stream=None, out=None) -> MaskBits:
+    """(B,H,W) float32 / float16 / bfloat16 logits of a segmentation network -> ``MaskBits`` of ``logits > threshold`` (compared in
+    float32; NaN -> 0), without a boolean plane in between (C-ABI ``la3d_pack_logits_bits``).  Other arguments as
+    ``pack_mask_bits``."""
+    if device is None and isinstance(logits, torch.Tensor) and logits.is_cuda:
+        device = logits.device
+    dev = _dev(device)
+    x, ps = _plane_source(logits, dev, (torch.float32, torch.float16, torch.bfloat16))
+    B, H, W = x.shape
+    W_out = padded_width(W) if frame_pad else W
+    o = _bits_out(out, B, H, W_out, dev)
+    with torch.cuda.device(dev):
+        check(lib.la3d_pack_logits_bits(_ptr(x), _LOGIT_DTYPES[x.dtype], ps, float(threshold), B, H, W, W_out, _ptr(o),
+                                        _bits_stride(o, B, H, W_out), _stream(stream)), "la3d_pack_logits_bits")
+    _record(stream, x, o)
+    return MaskBits(o, H, W_out, W)
+
+
+def _annotation_bits_plan(who, B, H, W, frame_pad, device, out, area):
+    """The argument errors of ``pack_rle_bits`` / ``pack_poly_bits`` that need no device -> (W_out, the plane stride of ``out`` or None,
+    the device to ask for).  ``out`` is checked ONCE, here: at small batches the packers are bound by what this wrapper costs."""
+    if B and (H <= 0 or W <= 0):
+        raise ValueError(f"{who}: the annotations state an empty frame {(H, W)}")
+    W_out = padded_width(W) if frame_pad else W
+    stride = None if out is None else _bits_stride(out, B, H, W_out)
+    if area is not None and not (isinstance(area, torch.Tensor) and area.is_cuda and area.dtype == torch.int32 and area.dim() == 1
+                                 and area.numel() == B and area.is_contiguous()):
+        raise ValueError(f"{who}: area must be a contiguous int32 ({B},) tensor on the GPU")
+    where = out.device if out is not None else area.device if area is not None else None
+    if where is not None:
+        d = where if device is None else torch.device(device)   # ("cuda" without an index names whichever GPU the tensors are on)
+        if (area is not None and area.device != where) or d.type != where.type or (d.index is not None and d.index != where.index):
+            raise ValueError(f"{who}: out / area live on another device")
+    return W_out, stride, where if where is not None else device
+
+
+class _PackedBits(MaskBits):
+    """The ``MaskBits`` a packer of annotations returns: it has just checked and filled the planes, so ``_stride`` - their plane
+    stride in words - rides along and a consumer (``instance_points``) need not check the tensor again.  A tuple like any
+    ``MaskBits``; ``_replace`` gives one without the attribute, which is checked as usual."""
+
+
+def _pack_annotation_bits(entry, name, arrays, B, H, W, frame_pad, device, stream, out, area) -> MaskBits:
+    """What ``pack_rle_bits`` / ``pack_poly_bits`` share: the checks, the planes, the annotation arrays (resident tensors as they are,
+    host arrays in one copy), the call.  At small batches the call costs what this wrapper costs: nothing is checked twice, and the
+    device context is entered only when another device is current."""
+    W_out, stride, device = _annotation_bits_plan(name[5:], B, H, W, frame_pad, device, out, area)
+    dev = device if isinstance(device, torch.device) else _dev(device)
+    if out is None:
+        stride = (H * W_out + 31) // 32
+        out = torch.empty((B, stride), dtype=torch.int32, device=dev)
+    if B:
+        # (the device context costs ~1.5 us of the ~12 us this call costs at small batches: entered only when another device is current)
+        with contextlib.nullcontext() if torch.cuda.current_device() == dev.index else torch.cuda.device(dev):
+            ann = []
+            for a, dt in arrays:   # (resident arrays of the right dtype are taken as they are)
+                if not (isinstance(a, torch.Tensor) and a.dtype == dt and a.device == dev and a.is_contiguous()):
+                    ann = None
+                    break
+                ann.append(a)
+            if ann is None:
+                ann = ([_as_dev(a, dt, dev) for a, dt in arrays] if any(isinstance(a, torch.Tensor) for a, _ in arrays)
+                       else _upload_many(arrays, dev))
+            # (plain integers: the entries' pointer arguments are c_void_p)
+            check(entry(*[a.data_ptr() for a in ann], B, H, W, W_out, out.data_ptr(), stride, None if area is None else area.data_ptr(),
+                        _stream(stream)), name)
+        _record(stream, *ann, out, area)
+    mb = _PackedBits(out, H, W_out, W)
+    mb._stride = stride
+    return mb
+
+
+def pack_rle_bits(rles, frame_pad: bool = True, device=None, stream=None, out=None, area=None) -> MaskBits:
+    """COCO run lengths (a list of RLE objects or the tuple of ``pack_rle``) -> ``MaskBits`` on the GPU (C-ABI ``la3d_pack_rle_bits``):
+    ``rle_decode`` with the bit image kept - an eighth of the bytes of the boolean planes, what ``instance_points``,
+    ``mask_stats_bits``, ``unpack_mask_bits`` and ``fit_instances_bits`` take.  ``frame_pad`` / ``out`` as in ``pack_mask_bits``;
+    ``area``: an int32 (B,) device tensor that receives the popcount of every plane (what ``area_hint`` takes).  A negative count is
+    a run of length 0, runs past the frame are cut."""
+    counts, offsets, H, W = pack_rle(rles)
+    return _pack_annotation_bits(lib.la3d_pack_rle_bits, "la3d_pack_rle_bits", [(counts, torch.int32), (offsets, torch.int64)],
+                                 len(offsets) - 1, H, W, frame_pad, device, stream, out, area)
+
+
+def pack_poly_bits(polys, frame_pad: bool = True, device=None, stream=None, out=None, area=None) -> MaskBits:
+    """Polygon parts (the tuple of ``pack_polygons``) -> ``MaskBits`` on the GPU (C-ABI ``la3d_pack_poly_bits``): ``poly_decode``
+    with the bit image kept.  Other arguments as ``pack_rle_bits``."""
+    if not (isinstance(polys, tuple) and len(polys) == 5):
+        raise ValueError("polys must be the (xy, ring_offsets, inst_rings, H, W) tuple of pack_polygons")
+    return _pack_annotation_bits(lib.la3d_pack_poly_bits, "la3d_pack_poly_bits",
+                                 [(polys[0], torch.int32), (polys[1], torch.int64), (polys[2], torch.int64)], len(polys[2]) - 1,
+                                 int(polys[3]), int(polys[4]), frame_pad, device, stream, out, area)
+
+
+# ---- crop-space masks as bit planes (include/la3d.h "crop-space masks as bit planes") -----------------------------------------------
+def crop_placement(params, S: int) -> np.ndarray:
+    """The paste of ``restore_mask_from_crop`` (reference src/util.py:187, :196-197) for a batch of crops of side ``S``: ``params``
+    (B, 3) or a list of ``(offset_x, offset_y, scale_factor)`` -> int32 (B, 4) rows ``x1, y1, side, 0`` - what ``la3d_pack_crop_bits``
+    reads as ``place``.  Host arithmetic on Python floats, exactly the reference's: ``side = int(S / scale_factor)`` (truncated),
+    ``x1 = int(round(offset_x))`` with Python's ``round`` (half to even); a scale of 0 and values that are no numbers raise what they
+    raise there.  Values that do not fit an int32 are clamped (such a placement lies outside every frame, such a side is refused on
+    the device: an empty plane)."""
+    rows = params.tolist() if hasattr(params, "tolist") else list(params)
+    out = np.zeros((len(rows), 4), np.int32)
+    lim = 2 ** 31 - 1
+    for n, row in enumerate(rows):
+        if len(row) != 3:
+            raise ValueError(f"crop_placement: row {n} must be (offset_x, offset_y, scale_factor)")
+        ox, oy, s = (float(v) for v in row)
+        out[n, :3] = [max(-lim, min(lim, i)) for i in (int(round(ox)), int(round(oy)), int(int(S) / s))]
+    return out
+
+
+def _crop_source(who, crops, dev):
+    """``crops`` of a crop packer -> (tensor that owns the bytes, the view whose first byte is crop 0's pixel (0, 0), crop stride, row
+    pitch, pixel step - bytes -, S, B, the default threshold).  (B, S, S) bool / uint8: a mask, threshold 0; (B, S, S, 4) uint8: RGBA,
+    the alpha channel is read in place through the strides, threshold 127 (reference src/batch_scripts/whole.py:83).  A device tensor
+    is read where it lies when a crop's rows and pixels lie at non-negative strides that do not overlap; host arrays go up as the
+    S x S bytes that are read."""
+    shape = tuple(crops.shape) if hasattr(crops, "shape") else None
+    if shape is None:
+        crops = np.asarray(crops)
+        shape = crops.shape
+    rgba = len(shape) == 4
+    if not ((len(shape) == 3 or (rgba and shape[3] == 4)) and shape[1] == shape[2] and shape[1] > 0):
+        raise ValueError(f"{who}: crops must be (B, S, S) bool / uint8 masks or (B, S, S, 4) uint8 RGBA crops, got {shape}")
+    B, S = int(shape[0]), int(shape[1])
+    if isinstance(crops, torch.Tensor):
+        if crops.dtype not in ((torch.uint8,) if rgba else (torch.uint8, torch.bool)):
+            raise ValueError(f"{who}: crops must be uint8{'' if rgba else ' or bool'}, not {crops.dtype}")
+        t = crops.view(torch.uint8) if crops.dtype == torch.bool else crops
+        v = t[..., 3] if rgba else t
+        if v.device != dev:
+            v = v.to(dev)
+        sb, sr, sp = v.stride()
+        if not (sp >= 1 and sr >= S * sp and (B <= 1 or sb >= (S - 1) * sr + (S - 1) * sp + 1)):
+            v = v.contiguous()
+            sb, sr, sp = v.stride()
+    else:
+        a = np.asarray(crops)
+        if a.dtype not in ((np.uint8,) if rgba else (np.uint8, np.bool_)):
+            raise ValueError(f"{who}: crops must be uint8{'' if rgba else ' or bool'}, not {a.dtype}")
+        a = np.ascontiguousarray(a[..., 3] if rgba else a).view(np.uint8)
+        v = torch.as_tensor(a, device=dev)
+        sb, sr, sp = S * S, S, 1
+    if B <= 1:
+        sb = max(int(sb), (S - 1) * int(sr) + (S - 1) * int(sp) + 1)
+    return v, int(sb), int(sr), int(sp), S, B, (127 if rgba else 0)
+
+
+def _crop_threshold(who, threshold, default: int) -> int:
+    thr = default if threshold is None else int(threshold)
+    if not 0 <= thr <= 255:
+        raise ValueError(f"{who}: threshold must lie in [0, 255] (bit = byte > threshold)")
+    return thr
+
+
+def _crop_place(who, params, S: int, B: int, dev) -> torch.Tensor:
+    """``params`` of a crop packer -> the int32 (B, 4) ``place`` rows on the device: host parameters through ``crop_placement``; an
+    int32 (B, 4) device tensor is taken as the rows themselves (``crop_placement`` uploaded once: nothing is copied, the call is
+    capturable)."""
+    if isinstance(params, torch.Tensor) and params.is_cuda:
+        if not (params.dtype == torch.int32 and tuple(params.shape) == (B, 4) and params.is_contiguous() and params.device == dev):
+            raise ValueError(f"{who}: device params must be the contiguous int32 ({B}, 4) rows of crop_placement, on the crops' device")
+        return params
+    place = crop_placement(params, S)
+    if len(place) != B:
+        raise ValueError(f"{who}: params must hold one (offset_x, offset_y, scale_factor) per crop ({B}), got {len(place)}")
+    return torch.as_tensor(place, device=dev)
+
+
+def pack_crop_bits(crops, params, image_size, threshold=None, frame_pad: bool = True, device=None, stream=None, out=None,
+                   area=None) -> MaskBits:
+    """Crop-space masks -> ``MaskBits`` of the full frame on the GPU (C-ABI ``la3d_pack_crop_bits``): ``restore_mask_from_crop``
+    (reference src/util.py:171-214) for a batch, written as bit planes - the nearest-index resize to ``int(S / scale_factor)`` pixels
+    and the clipped paste at ``round(offset)`` happen inside one kernel, so a 640x480 instance costs its 65 536 B crop (nothing when
+    the crop is resident) instead of a host resize, a 307 200 B upload and a pack.  ``crops``: (B, S, S) bool / uint8 masks (bit =
+    byte > ``threshold``, default 0) or (B, S, S, 4) uint8 RGBA crops, whose alpha is read in place (default threshold 127, as at
+    src/batch_scripts/whole.py:83), on the host or the device; ``params``: (B, 3) ``(offset_x, offset_y, scale_factor)`` as
+    ``crop_object`` returns them (``crop_placement`` turns them into the paste on the host, in the reference's float arithmetic), or
+    the int32 (B, 4) rows of ``crop_placement`` already on the device (nothing is uploaded then: with resident crops the call copies
+    nothing and can be captured into a graph);
+    ``image_size`` = (width, height).  ``frame_pad`` / ``out`` / ``area`` as in ``pack_rle_bits``.  Unlike the reference, a scale
+    that leaves no pixel (side <= 0) and a crop that lies wholly outside the frame give an empty plane (area 0), not an exception."""
+    who = "pack_crop_bits"
+    if device is None and isinstance(crops, torch.Tensor) and crops.is_cuda:
+        device = crops.device
+    W, H = int(image_size[0]), int(image_size[1])
+    B0 = int(crops.shape[0]) if hasattr(crops, "shape") else len(crops)
+    W_out, stride, device = _annotation_bits_plan(who, B0, H, W, frame_pad, device, out, area)
+    if H <= 0 or W <= 0:
+        raise ValueError(f"{who}: image_size states an empty frame {(W, H)}")
+    dev = device if isinstance(device, torch.device) else _dev(device)
+    with torch.cuda.device(dev):
+        v, sb, sr, sp, S, B, default = _crop_source(who, crops, dev)
+        thr = _crop_threshold(who, threshold, default)
+        place = _crop_place(who, params, S, B, dev)
+        if out is None:
+            stride = (H * W_out + 31) // 32
+            out = torch.empty((B, stride), dtype=torch.int32, device=dev)
+        check(lib.la3d_pack_crop_bits(v.data_ptr(), sb, sr, sp, S, thr, place.data_ptr(), B, H, W, W_out, out.data_ptr(), stride,
+                                      None if area is None else area.data_ptr(), _stream(stream)), "la3d_pack_crop_bits")
+    _record(stream, v, place, out, area)
+    mb = _PackedBits(out, H, W_out, W)
+    mb._stride = stride
+    return mb
+
+
+def unpack_mask_bits(bits, stream=None) -> torch.Tensor:
+    """``MaskBits`` -> (B,H,frame_width) bool masks on the GPU (C-ABI ``la3d_unpack_mask_bits``)."""
+    mb = _mask_bits(bits)
+    B = mb.bits.shape[0]
+    out = torch.empty((B, mb.H, mb.frame_width), dtype=torch.uint8, device=mb.bits.device)
+    with torch.cuda.device(mb.bits.device):
+        check(lib.la3d_unpack_mask_bits(_ptr(mb.bits), _bits_stride(mb.bits, B, mb.H, mb.W), B, mb.H, mb.W, mb.frame_width, _ptr(out),
+                                        _stream(stream)), "la3d_unpack_mask_bits")
+    _record(stream, mb.bits, out)
+    return out.view(torch.bool)
+
+
+def mask_stats_bits(bits, boundary_threshold: int = 10, stream=None) -> torch.Tensor:
+    """``mask_stats`` of ``MaskBits``: (B,4) int32 - area, rows holding a pixel, last - first + 1 rows, boundary-strip pixels (the
+    right strip ends at ``frame_width``)."""
+    mb = _mask_bits(bits)
+    B = mb.bits.shape[0]
+    out = torch.empty((B, 4), dtype=torch.int32, device=mb.bits.device)
+    with torch.cuda.device(mb.bits.device):
+        check(lib.la3d_mask_stats_bits(_ptr(mb.bits), _bits_stride(mb.bits, B, mb.H, mb.W), B, mb.H, mb.W, mb.frame_width,
+                                       int(boundary_threshold), _ptr(out), _stream(stream)), "la3d_mask_stats_bits")
+    _record(stream, mb.bits, out)
+    return out
+
+
+# ---- bit planes as run lengths (include/la3d.h "bit planes as run lengths") ----------------------------------------------------------
+class RleRuns(NamedTuple):
+    """What ``rle_encode_bits`` / ``rle_encode`` return: the COCO run lengths of B masks of one frame size, on the GPU - ``counts``
+    int32 (capacity,): the run list of instance n is ``counts[offsets[n]:offsets[n+1]]``, column-major over (H, W), zeros first;
+    ``offsets`` int64 (B+1,); ``H``, ``W``: the IMAGE (W = its columns, never a padded pitch).  It is the 4-tuple ``pack_rle`` passes
+    through: ``fit_instances_rle``, ``fit_instances_ex(rles=...)``, ``pack_rle_bits``, ``rle_decode`` and ``mask_stats_rle`` take it as
+    it is."""
+    counts: torch.Tensor
+    offsets: torch.Tensor
+    H: int
+    W: int
+
+
+def rle_to_string(counts) -> str:
+    """Run lengths -> COCO compressed RLE string (pycocotools rleToString), via the library's host helper: the inverse of
+    ``rle_from_string``."""
+    c = np.ascontiguousarray(counts.cpu().numpy() if isinstance(counts, torch.Tensor) else counts, dtype=np.int32).reshape(-1)
+    cap = 7 * len(c) + 1   # (a count or a difference of two has at most 33 bits and a sign: seven 5-bit groups)
+    buf = C.create_string_buffer(cap)
+    n = lib.la3d_rle_to_string_host(c.ctypes.data, len(c), buf, cap)
+    if n < 0:
+        raise ValueError("la3d_rle_to_string_host refused the counts")
+    return buf.raw[:n].decode("ascii")
+
+
+def _rle_capacity(who: str, capacity) -> None:
+    if capacity is not None and (not isinstance(capacity, (int, np.integer)) or isinstance(capacity, bool) or int(capacity) < 0):
+        raise ValueError(f"{who}: capacity must be None or an int >= 0, not {capacity!r}")
+
+
+def _rle_encode_run(a: _lib.RleEncodeArgs, B: int, dev, capacity, stream, keep):
+    """Both stages of one call.  ``a``: the block with every input set -> (counts, offsets, status)."""
+    with torch.cuda.device(dev):
+        a.stream = _stream(stream)
+        runs = torch.empty(max(B, 1), dtype=torch.int32, device=dev)
+        offsets = torch.empty(B + 1, dtype=torch.int64, device=dev)
+        ws = torch.empty(max(int(lib.la3d_rle_encode_workspace_bytes(B, a.H, a.W)) // 8, 1), dtype=torch.int64, device=dev)
+        a.runs, a.offsets, a.workspace = runs.data_ptr(), offsets.data_ptr(), ws.data_ptr()
+        check(lib.la3d_rle_encode_offsets(C.byref(a)), "la3d_rle_encode_offsets")
+        if capacity is None:
+            if stream is not None and stream != torch.cuda.current_stream():
+                stream.synchronize()
+            cap = int(offsets[-1].item())   # the ONE synchronisation of the call: the exact size
+        else:
+            cap = int(capacity)
+        counts = torch.empty(cap, dtype=torch.int32, device=dev) if cap else torch.zeros(1, dtype=torch.int32, device=dev)   # (the consumers take no NULL)
+        status = torch.empty(max(B, 1), dtype=torch.int32, device=dev)[:B]
+        a.counts, a.status, a.capacity = counts.data_ptr(), status.data_ptr(), cap
+        check(lib.la3d_rle_encode(C.byref(a)), "la3d_rle_encode")
+    _record(stream, runs, offsets, ws, counts, status, *keep)
+    return counts, offsets, status
+
+
+def rle_encode_bits(bits: MaskBits, capacity=None, stream=None, return_status: bool = False):
+    """``MaskBits`` -> ``RleRuns`` on the GPU (C-ABI ``la3d_rle_encode_offsets`` + ``la3d_rle_encode``): ``binary_mask_to_rle``
+    (reference src/download_coconut.py:167-175) for a batch - the planes of any packer (``pack_mask_bits``, ``pack_logits_bits``,
+    ``pack_label_bits(...).bits``, ``pack_poly_bits``, ``pack_crop_bits``) become COCO run lengths without leaving the device: the
+    fastest source of the fit, a few hundred bytes per instance, what ``fit_annotations_sharded`` ships and the annotation JSON stores
+    (``rle_objects``).  The runs cover the image (``bits.H`` x ``bits.frame_width``): pad columns are never mask.
+    ``capacity=None`` reads ``offsets[-1]`` back once - the call's ONLY host synchronisation - and allocates ``counts`` exactly;
+    ``capacity=int`` never synchronises (the chain can be captured into a graph): an instance whose run list does not fit gets status 1
+    and is not written, so ask for ``return_status=True`` then - ``(RleRuns, status int32 (B,))``: 0 ok, 1 no room, 2 the planes
+    changed between the two stages."""
+    if not isinstance(bits, MaskBits):
+        raise ValueError("rle_encode_bits: bits must be a MaskBits (pack_mask_bits, pack_logits_bits, pack_label_bits(...).bits, ...)")
+    _rle_capacity("rle_encode_bits", capacity)
+    mb = _mask_bits(bits)
+    B, dev = int(mb.bits.shape[0]), mb.bits.device
+    a = _lib.RleEncodeArgs(struct_size=C.sizeof(_lib.RleEncodeArgs), B=B, H=mb.H, W=mb.W, frame_width=0 if mb.frame_width == mb.W else mb.frame_width,
+                           mask_bits=mb.bits.data_ptr(), bits_plane_stride=_bits_stride(mb.bits, B, mb.H, mb.W))
+    counts, offsets, status = _rle_encode_run(a, B, dev, capacity, stream, [mb.bits])
+    runs = RleRuns(counts, offsets, mb.H, mb.frame_width)
+    return (runs, status) if return_status else runs
+
+
+def rle_encode(masks, device=None, stream=None) -> RleRuns:
+    """(B,H,W) bool / uint8 masks, on the host or the device -> ``RleRuns`` on the GPU: ``pack_mask_bits``, then ``rle_encode_bits``
+    (one host synchronisation, for the exact size)."""
+    return rle_encode_bits(pack_mask_bits(masks, frame_pad=True, device=device, stream=stream), stream=stream)
+
+
+def rle_objects(runs, compress: bool = False, sizes=None) -> list:
+    """Run lengths on the device -> the list of COCO RLE objects of the annotation JSON, ``{"size": [h, w], "counts": list}`` - or, with
+    ``compress=True``, ``counts`` as the compressed ``str`` of ``rle_to_string``.  ``runs``: an ``RleRuns``; or the ``(counts, offsets)``
+    of ``rle_encode_bits_frames`` with its ``sizes`` (B, 2).  ONE device-to-host copy (offsets, sizes and counts in one buffer)."""
+    if isinstance(runs, tuple) and len(runs) == 4:
+        counts, offsets, H, W = runs
+    elif isinstance(runs, tuple) and len(runs) == 2 and sizes is not None:
+        counts, offsets, H, W = runs[0], runs[1], None, None
+    else:
+        raise ValueError("rle_objects takes an RleRuns, or (counts, offsets) with sizes=")
+    if isinstance(counts, torch.Tensor) and counts.is_cuda:
+        B = int(offsets.numel()) - 1
+        parts = [offsets.to(counts.device).to(torch.int64).reshape(-1), counts.to(torch.int64).reshape(-1)]
+        if sizes is not None:
+            parts.insert(1, torch.as_tensor(sizes).to(counts.device).to(torch.int64).reshape(-1))
+        host = torch.cat(parts).cpu().numpy()
+        offs = host[:B + 1]
+        sz = host[B + 1:3 * B + 1].reshape(B, 2) if sizes is not None else None
+        cnt = host[(3 * B + 1) if sizes is not None else (B + 1):]
+    else:
+        offs, cnt = np.asarray(offsets, np.int64).reshape(-1), np.asarray(counts, np.int64).reshape(-1)
+        sz = None if sizes is None else np.asarray(sizes.cpu() if isinstance(sizes, torch.Tensor) else sizes, np.int64).reshape(-1, 2)
+    out = []
+    for n in range(len(offs) - 1):
+        c = cnt[offs[n]:offs[n + 1]]
+        out.append({"size": [int(H), int(W)] if sz is None else [int(sz[n, 0]), int(sz[n, 1])],
+                    "counts": rle_to_string(c) if compress else c.tolist()})
+    return out
+
+
+# ---- morphology on bit planes (include/la3d.h "morphology on bit planes") -------------------------------------------------------------
+def _open_scalars(who: str, k, upscale) -> None:   # the k and upscale of an opening, of either form
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 31 or int(k) % 2 == 0:
+        raise ValueError(f"{who}: k must be an odd int in 1 .. 31, not {k!r}")
+    if isinstance(upscale, bool) or not isinstance(upscale, (int, np.integer)) or int(upscale) not in (1, 2, 4):
+        raise ValueError(f"{who}: upscale must be 1, 2 or 4 (factors whose nearest-neighbour rule is u // s under every convention), not {upscale!r}")
+
+
+def _gate_scalars(who: str, min_area, crop_size) -> None:   # the gate of select_crops, of either form
+    if isinstance(min_area, bool) or not isinstance(min_area, (int, np.integer)) or int(min_area) < 0:
+        raise ValueError(f"{who}: min_area must be an int >= 0, not {min_area!r}")
+    if isinstance(crop_size, bool) or not isinstance(crop_size, (int, np.integer)) or int(crop_size) <= 0:
+        raise ValueError(f"{who}: crop_size must be an int > 0, not {crop_size!r}")
+
+
+def _open_args(who: str, bits, k, upscale) -> MaskBits:
+    if not isinstance(bits, MaskBits):
+        raise ValueError(f"{who}: bits must be a MaskBits (pack_mask_bits, pack_rle_bits, pack_poly_bits, pack_crop_bits, ...)")
+    _open_scalars(who, k, upscale)
+    mb = _mask_bits(bits)
+    if mb.H <= 0:
+        raise ValueError(f"{who}: the planes state an empty frame {(mb.H, mb.W)}")
+    return mb
+
+
+def _open_run(who: str, mb: MaskBits, k: int, s: int, W_out: int, out, want_stats: bool, stream):
+    """One ``la3d_open_bits`` call on checked arguments -> (out, stats); ``out`` None: statistics only."""
+    B, dev = int(mb.bits.shape[0]), mb.bits.device
+    out_stride = 0 if out is None else _bits_stride(out, B, s * mb.H, W_out)
+    with torch.cuda.device(dev):
+        stats = ws = None
+        if want_stats:
+            stats = torch.empty((B, 5), dtype=torch.int32, device=dev)
+            ws = torch.empty(max(int(lib.la3d_open_bits_workspace_bytes(B, mb.H, s)) // 4, 1), dtype=torch.int32, device=dev)
+        if B:   # (an empty batch has no planes to point at)
+            check(lib.la3d_open_bits(_ptr(mb.bits), _bits_stride(mb.bits, B, mb.H, mb.W), B, mb.H, mb.W, mb.frame_width, k, s,
+                                     _ptr(out), out_stride, W_out, _ptr(stats), _ptr(ws), _stream(stream)), "la3d_open_bits")
+    _record(stream, mb.bits, out, stats, ws)
+    return out, stats
+
+
+def open_bits(bits: MaskBits, k: int = 7, upscale: int = 1, frame_pad: bool = True, stream=None, out=None, return_stats: bool = False):
+    """Binary opening of bit planes on the GPU (C-ABI ``la3d_open_bits``): ``scipy.ndimage.binary_opening(U, np.ones((k, k)))`` of the
+    nearest-neighbour upscale ``U[v, u] = M[v // s, u // s]`` of every plane, ``s = upscale`` - the crop stage's mask step (reference
+    src/batch_scripts/get_crops_enhanced.py:68-88: x4, k = 7); at ``upscale=1`` it strips speckle and hairlines from network masks
+    before a fit.  ``k``: odd, 1 .. 31 (1 = identity); ``upscale``: 1, 2 or 4.  Returns ``MaskBits`` of ``s*H`` rows and ``s*frame_width``
+    image columns, stored ``padded_width(s*frame_width)`` wide with ``frame_pad`` (else unpadded) - or ``(MaskBits, stats)`` with
+    ``return_stats``: ``stats`` int32 (B, 5) on the device, ``area, x, y, w, h`` of each opened plane (``cv2.boundingRect``'s
+    convention; zeros for an empty plane).  ``out``: an int32 (B, >= words) device tensor to fill; it must not overlap the input (the
+    call cannot work in place).  No host synchronisation; capturable."""
+    who = "open_bits"
+    mb = _open_args(who, bits, k, upscale)
+    k, s = int(k), int(upscale)
+    B, dev = int(mb.bits.shape[0]), mb.bits.device
+    fw = s * mb.frame_width
+    W_out = padded_width(fw) if frame_pad else fw
+    if out is not None and isinstance(out, torch.Tensor) and out.device != dev:
+        raise ValueError(f"{who}: out lives on another device")
+    o = _bits_out(out, B, s * mb.H, W_out, dev)
+    o, stats = _open_run(who, mb, k, s, W_out, o, bool(return_stats), stream)
+    res = MaskBits(o, s * mb.H, W_out, fw)
+    return (res, stats) if return_stats else res
+
+
+def bits_rects(bits: MaskBits, stream=None) -> torch.Tensor:
+    """``MaskBits`` -> int32 (B, 5) on the device: ``area, x, y, w, h`` of every plane - the statistics-only call of ``la3d_open_bits``
+    with ``k = 1, upscale = 1`` (nothing but the planes is read, no plane is written)."""
+    mb = _open_args("bits_rects", bits, 1, 1)
+    return _open_run("bits_rects", mb, 1, 1, mb.frame_width, None, True, stream)[1]
+
+
+def crop_params(stats, crop_size: int = 512, upscale: int = 4, ratio: float = 0.7) -> np.ndarray:
+    """The crop parameters of the reference's crop stage from the rectangles of opened planes: ``stats`` (B, 5) ``area, x, y, w, h``
+    (``open_bits(..., return_stats=True)``, ``bits_rects``; a (B, 4) array is taken as ``x, y, w, h``) -> float64 (B, 3) rows
+    ``(offset_x, offset_y, scale_factor)``, what ``crop_placement`` / ``pack_crop_bits`` take.  Host arithmetic on Python numbers,
+    exactly the reference's (``crop_object``, src/util.py:142-157, then src/batch_scripts/get_crops_enhanced.py:98):
+    ``side = int(max(w, h) / ratio)``, ``ox = x + (w - side) / 2``, ``oy = y + (h - side) / 2``, ``sf = crop_size / side``; the row is
+    ``[ox / upscale, oy / upscale, sf * upscale]`` - the rectangle is measured on the upscaled image, the parameters speak of the
+    original one.  Rows with ``w == 0`` (an empty plane) are NaN."""
+    a = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats)
+    if a.ndim != 2 or a.shape[1] not in (4, 5):
+        raise ValueError(f"crop_params: stats must be (B, 5) area, x, y, w, h or (B, 4) x, y, w, h, got {a.shape}")
+    if not (crop_size > 0 and upscale > 0 and ratio > 0):
+        raise ValueError("crop_params: crop_size, upscale and ratio must be positive")
+    out = np.full((a.shape[0], 3), np.nan, np.float64)
+    for n, row in enumerate(a[:, -4:].tolist()):
+        x, y, w, h = (int(v) for v in row)
+        if w <= 0 or h <= 0:
+            continue
+        side = int(max(w, h) / ratio)
+        ox, oy, sf = x + (w - side) / 2, y + (h - side) / 2, crop_size / side
+        out[n] = [ox / upscale, oy / upscale, sf * upscale]
+    return out
+
+
+def select_crops(bits: MaskBits, min_area: int = 6400, k: int = 7, upscale: int = 4, crop_size: int = 512, stream=None):
+    """The instance selection of the reference's crop stage (src/batch_scripts/get_crops_enhanced.py:68-99) for a batch of planes:
+    ``open_bits(bits, k, upscale)``, then ``keep = area >= min_area`` and ``crop_params`` of the rectangles -> ``(keep, params, stats,
+    opened)``: ``keep`` bool (B,) and ``params`` float64 (B, 3) NumPy arrays (NaN rows for empty planes), ``stats`` int32 (B, 5) on the
+    device, ``opened`` the ``MaskBits`` of the opened, upscaled planes.  The defaults are the reference's gate (x4, 7 x 7, 6400
+    surviving pixels, 512-pixel crops); one device-to-host copy (the statistics).  The reference walks the instances LAST TO FIRST and
+    appends the boxes it keeps to ``bboxes.json`` in that order: rows here stay in the caller's order, and the order of
+    ``bboxes.json`` is the caller's business."""
+    _gate_scalars("select_crops", min_area, crop_size)
+    opened, stats = open_bits(bits, k=k, upscale=upscale, frame_pad=True, stream=stream, return_stats=True)
+    if stream is not None and stream != torch.cuda.current_stream():
+        stream.synchronize()
+    host = stats.cpu().numpy()
+    return host[:, 0] >= int(min_area), crop_params(host, crop_size=int(crop_size), upscale=int(upscale)), stats, opened
+
+
+def fit_instances_bits(depth, bits, K, ground=None, sample_idx=None, image_index=None, stream=None, device=None, filter=None,
+                       image_size=None, area_hint=None, frame_width=None, method: str = "pca", height_rule: str = "rows"):
+    """fit_instances with the masks given as bit planes (``pack_mask_bits`` / ``pack_logits_bits``; C-ABI
+    ``la3d_fit_instances_bits``): the planes are copied straight into the fit kernel's LDS bit image - an eighth of the bytes of a u8
+    plane, no decode.  Arguments and returns as ``fit_instances_rle`` (``filter`` adds the (B,4) statistics), plus ``image_size`` /
+    ``area_hint`` as in ``fit_instances_ex`` (``image_size`` appends ``boxes2d`` (B,8) to the returned tuple).  ``depth``: planes as
+    wide as the bit planes are stored (``bits.W``), or ``bits.frame_width`` wide - then the rows are padded here
+    (``pad_depth_rows``).  ``frame_width``: None, or the image width, checked against the planes'.  ``height_rule``: the height the
+    fused filter uses - "rows" (rows holding a pixel, the reference's rule for run-length annotations) or "span" (last - first + 1,
+    its rule for polygons); a bit plane does not say where it came from."""
+    _lib.method_code(method)   # (the reference's error for an unknown method, before any device work)
+    flags = height_rule_code(height_rule)
+    if isinstance(depth, Depth16):
+        _depth16_check(depth)
+    mb = _mask_bits(bits)
+    dev = mb.bits.device if device is None else _dev(device)
+    if mb.bits.device != dev:
+        raise ValueError("the bit planes live on another device")
+    W, fw = mb.W, mb.frame_width
+    if frame_width is not None and int(frame_width) != fw:
+        raise ValueError(f"frame_width {frame_width} does not match the bit planes' frame width {fw}")
+    depth, fw = depth_rows_for_bits(depth, W, fw, dev)
+    out = fit_call(mask_source(dev, bits=(mb, flags))[0], depth, K, dev, mb.H, W, image_index=image_index, ground=ground,
+                   sample_idx=sample_idx, area_hint=area_hint, filter=filter, image_size=image_size, stream=stream, method=method,
+                   frame_width=fw)
+    return tuple(out.values())

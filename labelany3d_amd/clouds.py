@@ -15,7 +15,8 @@ from ._lib import check, lib
 from .batched import Depth16, _as_dev, _bits_stride, _depth16_block, _depth16_check, _dev, _fit_inputs, _record, _stream
 from .fitcall import depth_rows_for_bits
 from .frames import FrameBits, _frames_depth, _on_gpu, _same_table
-from .masks import LabelBits, _PackedBits, _mask_bits
+from .bits import _PackedBits, _mask_bits
+from .labels import LabelBits
 
 
 class InstancePoints(NamedTuple):

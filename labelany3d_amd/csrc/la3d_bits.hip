@@ -1,9 +1,11 @@
-// la3d_bits.hip - masks as bit planes (include/la3d.h "masks as bit planes" and everything behind it): the packers of u8 masks,
-// logits, label maps, COCO run lengths, polygons and crop-space masks - each in its uniform and its frames form -, the unpacker, the filter
-// statistics of a bit plane and the way back out of one: the run-length encoder (la3d_rle_encode_offsets / la3d_rle_encode).  This unit also owns the family "annotation into an LDS bit image": NT_DEC, bits_to_plane and with them
-// la3d_rle_decode / la3d_poly_decode, whose kernels the annotation packers repeat with the LDS image kept as the output.
-// Stated once for every entry: where the planes go (BitsOut), the host check (pack_check), the frames prologue of a workgroup
-// (frames_plane).  la3d_masks.hip keeps depth_to_points, row padding and the statistics of u8 planes, run lengths and polygons.
+// la3d_bits.hip - masks as bit planes (include/la3d.h "masks as bit planes"): the packers of u8 masks, logits, label maps, COCO run
+// lengths, polygons and crop-space masks - each in its uniform and its frames form -, the unpacker and the filter statistics of a bit
+// plane.  This unit also owns the family "annotation into an LDS bit image": bits_to_plane and with it la3d_rle_decode /
+// la3d_poly_decode, whose kernels the annotation packers repeat with the LDS image kept as the output.
+// Shared with the other bit-plane units and stated once, in la3d_bitplanes.hpp: where the planes go (BitsOut), the host check
+// (pack_check), the frames prologue of a workgroup (frames_prologue).  The way back out of a plane, the run-length encoder, is
+// la3d_rle_encode.hip; morphology is la3d_open.hip.  la3d_masks.hip keeps depth_to_points, row padding and the statistics of u8 planes,
+// run lengths and polygons.
 #include <cstdint>
 #include <cstddef>
 #include <cstring>
@@ -12,12 +14,11 @@
 
 #include "la3d_device.hpp"
 #include "la3d_poly.hpp"
+#include "la3d_bitplanes.hpp"
 
 using namespace la3d;
 
 namespace {
-constexpr int NT_DEC = 512;   // decode kernels: 8 waves per workgroup (four workgroups per CU by LDS: 32 waves keep the stores coming)
-
 // bit image in LDS -> u8 plane (0/1), coalesced 16-byte non-temporal stores where the plane allows; NTH threads.  Four bits
 // become four bytes with one multiply: bit i of the nibble lands at 8 i through the partial product shifted by 7 i (the 16 partial
 // products hit 16 different bit positions: no carries).
@@ -73,89 +74,6 @@ __global__ __launch_bounds__(NT_DEC) void poly_decode_kernel(const int* __restri
 // LDS (rle_to_bits / poly_to_bits with frame_w / clipW: the bits of the padding columns are zero) and streams the words to the
 // instance's plane - an eighth of the bytes of the u8 plane.  The workgroup owns its instance: the area is reduced inside it and
 // stored by one lane (no atomic, no clear kernel).
-struct BitsOut {              // where the planes of a call go (kernel argument)
-  unsigned* bits;
-  long long stride;           // uniform form: words between planes
-  const long long* offsets;   // frames form: words from bits to the plane of each instance
-  int* area;                  // [B] or NULL
-  const la3d_frame* frames;   // frames form: the table, P rows
-  const int* image_index;
-  int P;
-  int H, W;                   // uniform form: the frame as stored (W = W_out); frames form: the bounds
-  int frame_w;                // uniform form: the image columns where the rows are padded (0: none)
-  int lds_words;              // words of the bit image the launch reserved (uniform form: the plane's)
-  int vec;                    // uniform form: every plane 16-byte aligned
-};
-struct PlaneGeo { int H, W, fw, nwords, vec; unsigned* out; };
-
-// ---- the prologue of a frames packer's workgroup, stated once ------------------------------------------------------------------
-// Every value that decides whether and where something is read or written is wave-uniform, comes through a scalar load and is checked
-// BEFORE an address is formed from it.  The order of the steps is the safety property:
-//   1  BY_INSTANCE: image_index[n] inside [0, P) - before the frame row is addressed (else n IS the image: the grid's own)
-//   2  the frame row keeps the contract (frame_row_ok: the check the fit makes) - before anything is read or written through it
-//   3  BY_INSTANCE: the plane's offset >= 0 and a multiple of 4 (frames_plane_at: the rule of the fit)
-//   4  nwords = H * W / 32   (<= the bounds' plane: H <= max_h, W <= max_w, W % 32 == 0)
-//   5  CHUNKED (one lane per word, 256 words per chunk): a chunk beyond the plane's words - before any load; then the lane's word w,
-//      live = w < nwords, have = the bits of word w that are image columns (0 where not live)
-// false: refused - nothing is read, nothing is written.
-// (The text below is shaped by the instruction streams of its four users, which are those they had with a prologue each: the row is
-// checked as a local and stored afterwards - checked in place, the annotation packers lose `0 < fw <= W` and clip again -, and the
-// plane is given both as a pointer and as words from bits, because pack_*_bits_kernel forms bits + off here and the others off + w.)
-struct FramesWork { FrameRow r; unsigned* out; long long off; int nwords, w; bool live; unsigned have; };   // out = bits + off: the plane
-
-// the bits of word w of a plane W wide that are columns < fw (a row is a whole number of words)
-__device__ inline unsigned image_columns(int w, int W, int fw) {
-  const int rem = fw - (w % (W >> 5)) * 32;
-  return rem >= 32 ? 0xffffffffu : rem <= 0 ? 0u : (1u << rem) - 1u;
-}
-__device__ inline bool frames_plane_at(const long long* __restrict__ offsets, int b, long long* off) {
-  const long long oo = poly_uniform(offsets[b]);
-  if (oo < 0 || (oo & 3) != 0) return false;
-  *off = oo;
-  return true;
-}
-template <bool BY_INSTANCE, bool CHUNKED>
-__device__ inline bool frames_prologue(const la3d_frame* frames, int P, const int* image_index, int max_h, int max_w, unsigned* bits,
-                                       const long long* offsets, int n, int chunk, FramesWork* f) {
-  int img = n;
-  if constexpr (BY_INSTANCE) {
-    img = __builtin_amdgcn_readfirstlane(image_index[n]);
-    if ((unsigned)img >= (unsigned)P) return false;
-  }
-  const FrameRow r = frame_row_load(frames + img);
-  if (!frame_row_ok(r, max_h, max_w)) return false;
-  if constexpr (BY_INSTANCE) {
-    if (!frames_plane_at(offsets, n, &f->off)) return false;
-    f->out = bits + f->off;
-  }
-  f->r = r;
-  f->nwords = (r.H * r.W) >> 5;
-  if constexpr (CHUNKED) {
-    if (chunk * 256 >= f->nwords) return false;
-    f->w = chunk * 256 + (int)threadIdx.x;
-    f->live = f->w < f->nwords;
-    f->have = f->live ? image_columns(f->w, r.W, r.fw) : 0u;
-  }
-  return true;
-}
-
-// The geometry and the plane of instance b.  false (frames form): the instance is refused - nothing is written for it.
-template <bool FRAMES>
-__device__ inline bool plane_geometry(const BitsOut& c, int b, PlaneGeo* g) {
-  if constexpr (FRAMES) {
-    FramesWork f;
-    if (!frames_prologue<true, false>(c.frames, c.P, c.image_index, c.H, c.W, c.bits, c.offsets, b, 0, &f)) return false;
-    g->H = f.r.H; g->W = f.r.W; g->fw = f.r.fw;
-    g->nwords = f.nwords;           // (<= lds_words)
-    g->vec = 1;                     // (bits is 16-byte aligned - checked on the host - and the offset a multiple of 4)
-    g->out = f.out;
-  } else {
-    g->H = c.H; g->W = c.W; g->fw = c.frame_w; g->nwords = c.lds_words; g->vec = c.vec;
-    g->out = c.bits + (long long)b * c.stride;
-  }
-  return true;
-}
-
 // bit image in LDS -> the plane's nwords words, exactly those: 16-byte non-temporal stores (vec: the plane's base is 16-byte
 // aligned) and up to three words of tail, or word by word.  Then area[b] = the popcount of the words as written.  red: LDS, NTH / 64 ints.
 template <int NTH>
@@ -759,587 +677,19 @@ __global__ __launch_bounds__(256) void pack_crop_bits_kernel(const CropSrc s, co
   label_area(c.area, n, pat);   // (every lane of the wave takes part)
 }
 
-// ---- bit planes -> COCO run lengths (la3d_rle_encode_offsets / la3d_rle_encode) --------------------------------------------------
-// binary_mask_to_rle for a batch (reference src/download_coconut.py:167-175): the runs of the (H, frame_width) image in COLUMN-major
-// order (flat = u * H + v), zeros first.  A transition is a flat index i > 0 whose pixel differs from pixel i - 1; with T transitions
-// at p_1 < ... < p_T, p_0 = 0 and p_{T+1} = H * frame_width the run list is [p_1 - p_0, ..., p_{T+1} - p_T], led by a 0 when pixel
-// (0, 0) is set: T + 1 + bit(0, 0) counts.
-// One workgroup per instance streams the plane into LDS (bits_plane_to_lds: the consumers' copy) and gives every image column a thread
-// that walks it top to bottom - the 64 lanes of a wave read the same one or two LDS words of a row (a broadcast), each its own bit.
-// Only bits (v, u) with v < H and u < frame_width are looked at: pad columns and the spare bits of the last word are never mask.
-//   stage 1  per column: T[u], its transitions, and L[u], the row of its last one (-1: none) -> workspace; runs[n] = sum T + 1 + bit(0, 0)
-//   stage 2  T and L come back from the workspace; a scan over the columns (a sum for the rank, a maximum for the position of the
-//            transition before the column: shuffles inside a wave, the wave totals through LDS, a carry from chunk to chunk of NT_DEC
-//            columns) tells every thread the index of its first count and the position that count starts from, so the second walk
-//            stores each count where it belongs: no atomics, no ordering between threads.  Every store is guarded by the instance's
-//            own range, so a plane that changed after stage 1 (or a foreign workspace) can only spoil values inside that range.
-struct RleOut {
-  int* runs;                  // [B], stage 1
-  long long* offsets;         // [B + 1]: written by stage 1, read by stage 2
-  int* counts;                // [capacity], stage 2
-  int* status;                // [B], stage 2
-  long long capacity;
-  int2* ws;                   // [B][ws_cols]: (T, L) of every column
-  int ws_cols;
-};
-constexpr size_t RLE_SCAN_BYTES = 2 * (NT_DEC / 64) * sizeof(int);   // behind the bit image (16-aligned): the wave totals of the scan
-
-// bit (v, u) of an LDS bit image whose rows lie W bits apart, for v = 0 .. H - 1: on(v) is called wherever it differs from the pixel
-// before it in column-major order - (v - 1, u), or (H - 1, u - 1) for v = 0; pixel (0, 0) has none
-template <typename F>
-__device__ inline void column_transitions(const unsigned* bits, int H, int W, int u, F&& on) {
-  const int before = u > 0 ? (H - 1) * W + u - 1 : 0;
-  unsigned prev = (bits[before >> 5] >> (before & 31)) & 1u;
-  if ((W & 31) == 0) {   // uniform: rows of whole words - one word index per row, one shift for the column
-    // eight rows per step: eight independent LDS reads, their bits gathered into m, the transitions among them as the set bits of
-    // x = m ^ (m shifted by one row) - most steps of a real mask have none, and the loop over them is skipped
-    const unsigned* p = bits + (u >> 5);
-    const int wpr = W >> 5, sh = u & 31;
-    int v = 0;
-    for (; v + 8 <= H; v += 8) {
-      unsigned m = 0;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) m |= ((p[(v + k) * wpr] >> sh) & 1u) << k;
-      unsigned x = (m ^ ((m << 1) | prev)) & 0xffu;
-      prev = m >> 7;
-      while (x) {
-        on(v + __ffs((int)x) - 1);
-        x &= x - 1u;
-      }
-    }
-    for (; v < H; ++v) {
-      const unsigned b = (p[v * wpr] >> sh) & 1u;
-      if (b != prev) on(v);
-      prev = b;
-    }
-  } else {
-    int i = u;
-    for (int v = 0; v < H; ++v, i += W) {
-      const unsigned b = (bits[i >> 5] >> (i & 31)) & 1u;
-      if (b != prev) on(v);
-      prev = b;
-    }
-  }
-}
-
-// Over the NTH threads of the workgroup: the exclusive prefix of a sum (t) and of a maximum (p >= 0), and both totals.  Every thread
-// calls it; sc: LDS, 2 * NTH / 64 ints, free again when it returns.
-template <int NTH>
-__device__ inline void block_scan_sum_max(int t, int p, int* sc, int tid, int* ex_t, int* ex_p, int* tot_t, int* tot_p) {
-  const int lane = tid & 63, wave = tid >> 6;
-  int it = t, ip = p;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int a = __shfl_up(it, d), b = __shfl_up(ip, d);
-    if (lane >= d) { it += a; ip = max(ip, b); }
-  }
-  const int before_p = __shfl_up(ip, 1);
-  if (lane == 63) { sc[wave] = it; sc[NTH / 64 + wave] = ip; }
-  __syncthreads();
-  int bt = 0, bp = 0, st = 0, sp = 0;
-#pragma unroll
-  for (int w = 0; w < NTH / 64; ++w) {
-    const int a = sc[w], b = sc[NTH / 64 + w];
-    if (w < wave) { bt += a; bp = max(bp, b); }
-    st += a; sp = max(sp, b);
-  }
-  __syncthreads();
-  *ex_t = bt + it - t;
-  *ex_p = lane > 0 ? max(bp, before_p) : bp;
-  *tot_t = st; *tot_p = sp;
-}
-
-template <bool FRAMES>
-__global__ __launch_bounds__(NT_DEC) void rle_encode_count_kernel(const BitsOut c, const RleOut e) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x, n = blockIdx.x;
-  PlaneGeo g;
-  if (!plane_geometry<FRAMES>(c, n, &g)) {   // (uniform) refused: nothing is read, no run
-    if (tid == 0) e.runs[n] = 0;
-    return;
-  }
-  unsigned* bits = reinterpret_cast<unsigned*>(smem);
-  int* sc = reinterpret_cast<int*>(smem + (((size_t)c.lds_words * 4 + 15) & ~(size_t)15));
-  (void)bits_plane_to_lds<NT_DEC>(g.out, bits, g.nwords, g.H * g.W, g.vec, tid);
-  __syncthreads();
-  const int fw = g.fw > 0 ? g.fw : g.W;   // the image columns
-  int2* ws = e.ws + (long long)n * e.ws_cols;
-  int total = 0;
-  for (int u = tid; u < fw; u += NT_DEC) {
-    int T = 0, L = -1;
-    column_transitions(bits, g.H, g.W, u, [&](int v) { ++T; L = v; });
-    ws[u] = make_int2(T, L);
-    total += T;
-  }
-  total = wave_sum_i(total);
-  if ((tid & 63) == 0) sc[tid >> 6] = total;
-  __syncthreads();
-  if (tid == 0) {
-    int s = 1 + (int)(bits[0] & 1u);
-#pragma unroll
-    for (int w = 0; w < NT_DEC / 64; ++w) s += sc[w];
-    e.runs[n] = s;
-  }
-}
-
-// One workgroup: offsets = the exclusive prefix of runs.  Thread t owns a run of consecutive instances, the runs are scanned in LDS:
-// deterministic, any B (the scan of la3d_instance_point_offsets).  B == 0: offsets[0] = 0.
-constexpr int RLE_ST = 1024;
-__global__ __launch_bounds__(RLE_ST) void rle_encode_scan_kernel(const int* __restrict__ runs, long long* __restrict__ offsets, int B) {
-  __shared__ long long part[RLE_ST];
-  const int tid = threadIdx.x;
-  const int chunk = (B + RLE_ST - 1) / RLE_ST;
-  const int n0 = (int)min((long long)B, (long long)tid * chunk), n1 = (int)min((long long)B, (long long)n0 + chunk);
-  long long sum = 0;
-  for (int n = n0; n < n1; ++n) sum += runs[n];
-  part[tid] = sum;
-  __syncthreads();
-  for (int d = 1; d < RLE_ST; d <<= 1) {
-    const long long t = tid >= d ? part[tid - d] : 0;
-    __syncthreads();
-    part[tid] += t;
-    __syncthreads();
-  }
-  long long run = part[tid] - sum;
-  if (tid == 0) offsets[0] = 0;
-  for (int n = n0; n < n1; ++n) {
-    run += runs[n];
-    offsets[n + 1] = run;
-  }
-}
-
-template <bool FRAMES>
-__global__ __launch_bounds__(NT_DEC) void rle_encode_emit_kernel(const BitsOut c, const RleOut e) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x, n = blockIdx.x;
-  PlaneGeo g;
-  if (!plane_geometry<FRAMES>(c, n, &g)) {   // (uniform) refused: nothing is read or written
-    if (tid == 0) e.status[n] = LA3D_BOX_UNSUPPORTED;
-    return;
-  }
-  const long long off0 = poly_uniform(e.offsets[n]), off1 = poly_uniform(e.offsets[n + 1]);
-  if (off0 < 0 || off1 < off0 || off1 > e.capacity) {   // (uniform) no room: nothing of the instance is written
-    if (tid == 0) e.status[n] = LA3D_RLE_NO_ROOM;
-    return;
-  }
-  const long long len = off1 - off0;   // every store below goes to out[i] with 0 <= i < len
-  unsigned* bits = reinterpret_cast<unsigned*>(smem);
-  int* sc = reinterpret_cast<int*>(smem + (((size_t)c.lds_words * 4 + 15) & ~(size_t)15));
-  (void)bits_plane_to_lds<NT_DEC>(g.out, bits, g.nwords, g.H * g.W, g.vec, tid);
-  __syncthreads();
-  const int H = g.H, fw = g.fw > 0 ? g.fw : g.W;
-  const int lead = (int)(bits[0] & 1u);
-  const int2* ws = e.ws + (long long)n * e.ws_cols;
-  int* out = e.counts + off0;
-  int carry_t = 0, carry_p = 0, bad = 0;
-  for (int u0 = 0; u0 < fw; u0 += NT_DEC) {   // uniform trip count: every thread takes part in the scan
-    const int u = u0 + tid;
-    int wT = 0, wL = -1;
-    if (u < fw) {
-      const int2 w = ws[u];
-      wT = w.x; wL = w.y;
-    }
-    if (wT < 0 || wT > H || wL < -1 || wL >= H || (wT == 0) != (wL < 0)) {   // not what stage 1 writes: nothing is derived from it
-      bad = 1; wT = 0; wL = -1;
-    }
-    int ex_t, ex_p, tot_t, tot_p;
-    block_scan_sum_max<NT_DEC>(wT, wL >= 0 ? u * H + wL : 0, sc, tid, &ex_t, &ex_p, &tot_t, &tot_p);
-    if (u < fw) {
-      int rank = lead + carry_t + ex_t;   // the count this column's first transition ends
-      int prev = max(carry_p, ex_p);      // where that count starts: the transition before the column, or 0
-      int T = 0, L = -1;
-      column_transitions(bits, H, g.W, u, [&](int v) {
-        const int p = u * H + v;
-        if ((long long)rank < len) out[rank] = p - prev;
-        prev = p; ++rank; ++T; L = v;
-      });
-      bad |= (T != wT || L != wL) ? 1 : 0;
-    }
-    carry_t += tot_t; carry_p = max(carry_p, tot_p);
-  }
-  bad = __syncthreads_or(bad);
-  if (tid == 0) {
-    const long long last = (long long)lead + carry_t;   // the count that ends at H * frame_width
-    if (lead && len > 0) out[0] = 0;
-    if (last < len) out[last] = H * fw - carry_p;
-    e.status[n] = (bad || last + 1 != len) ? LA3D_RLE_MISMATCH : LA3D_RLE_OK;
-  }
-}
-
-// ---- morphology on bit planes ---------------------------------------------------------------
-// include/la3d.h "morphology on bit planes": binary opening by a k x k square of the nearest x s upscale of a plane, with the area and
-// the bounding rectangle of the result.  One workgroup per (band of R output rows, instance); R is a multiple of 32, so a band begins
-// on a word of the output whatever W_out is and no two workgroups write one word.  In LDS every row is word-ALIGNED (nw words, lanes
-// over the word column: consecutive banks, no conflicts whatever the row stride):
-//   A  the source rows the band needs, realigned (funnel shift by (v*W) & 31) and spread to s bits per bit - ONE row per source row:
-//      the s upscaled rows that repeat it are indexed, never stored
-//   B  upscaled rows [r0 - r, r0 + R + r): the AND of the k rows around each (vertical erosion); then, in place, the horizontal
-//      opening of each row (erosion and dilation along x are one function of a word and its two neighbours, since 2r <= 30 bits);
-//      a row is owned by ONE wave, which reads all of it before it writes, so the pass needs no second buffer
-//   the OR of k rows of B (vertical dilation) is the output word, formed in registers, counted for the statistics and stored.
-// Rows and columns outside the image are zero (SciPy's border_value = 0): an erosion window that leaves the image holds its own
-// centre, which is zero, so nothing beyond the zero rows of A and the masked last word is needed.
-// FRAMES (la3d_open_bits_frames, images of different sizes): the same passes on a geometry formed per instance from its la3d_frame row
-// (open_instance, all of it wave-uniform: SGPRs); ONE band plan per call, from the bounds - the grid has the bounds' bands for every
-// instance and LDS is requested for the bounds, an instance uses its own words per row of it.
-constexpr int OPEN_NT = 256;
-struct OpenArgs {
-  const unsigned* bits; long long stride;   // input planes, words apart
-  int H, W, fw;                             // source rows, stored width, image columns
-  long long nwords_in;                      // words of an input plane (nothing beyond is read)
-  int k, s;
-  unsigned* out; long long out_stride;      // NULL: statistics only
-  int H_out, W_out, nw;                     // output rows, stored width; words of an aligned upscaled row = ceil(s*fw / 32)
-  int nwords_out;                           // words of an output plane
-  int R, nA, nbands, vec;                   // band rows; rows of A; bands per plane; 16-byte stores allowed
-  int* partial;                             // [B][nbands][8] or NULL
-  // frames form (H, W: the bounds of the table; the fields above that speak of a plane are then formed per instance, open_instance)
-  const long long* offsets; const long long* out_offsets;   // [B] words from bits / out to the plane of each instance
-  const la3d_frame* frames; const int* image_index; int P;
-  long long bits_words, out_words;          // words of the two buffers: a plane that does not end inside its buffer is refused
-};
-
-__device__ inline unsigned spread_bits(unsigned x, int s) {   // the low 32 / s bits of x, each repeated s times
-  if (s == 4) {
-    x = (x | (x << 12)) & 0x000F000Fu; x = (x | (x << 6)) & 0x03030303u; x = (x | (x << 3)) & 0x11111111u;
-    return x * 15u;
-  }
-  if (s == 2) {
-    x = (x | (x << 8)) & 0x00FF00FFu; x = (x | (x << 4)) & 0x0F0F0F0Fu; x = (x | (x << 2)) & 0x33333333u; x = (x | (x << 1)) & 0x55555555u;
-    return x * 3u;
-  }
-  return x;
-}
-
-// word wc of the aligned, upscaled form of source row v (0 <= v < H, wc < nw): columns at and beyond fw are zero whatever the plane holds
-__device__ inline unsigned open_source_word(const OpenArgs& a, const unsigned* __restrict__ plane, int v, int wc) {
-  const int nb = 32 >> (a.s >> 1), c0 = wc * nb;       // 32 / s for s = 1, 2, 4
-  const long long i = (long long)v * a.W + c0;
-  const long long w = i >> 5;
-  const unsigned sh = (unsigned)(i & 31);
-  unsigned x = plane[w] >> sh;
-  if (sh && w + 1 < a.nwords_in) x |= plane[w + 1] << (32 - sh);
-  const int valid = min(nb, a.fw - c0);
-  if (valid < 32) x &= (1u << valid) - 1u;
-  return spread_bits(x, a.s);
-}
-
-__device__ inline unsigned long long and_window(unsigned long long x, int k) {   // bit i = AND of bits i .. i + k - 1
-  int w = 1;
-  for (; 2 * w <= k; w *= 2) x &= x >> w;
-  if (w < k) x &= x >> (k - w);
-  return x;
-}
-__device__ inline unsigned long long or_window(unsigned long long x, int k) {    // bit i = OR of bits i - k + 1 .. i
-  int w = 1;
-  for (; 2 * w <= k; w *= 2) x |= x << w;
-  if (w < k) x |= x << (k - w);
-  return x;
-}
-// horizontal opening of the word `c` between its neighbours `l` (lower columns) and `r`: with e[i] = AND x[i .. i + k - 1] the erosion is
-// e[c - r] and its dilation OR e[c - k + 1 .. c]; both windows stay inside the three words because k - 1 <= 30
-__device__ inline unsigned open_row_word(unsigned l, unsigned c, unsigned r, int k) {
-  const unsigned long long lo = and_window(((unsigned long long)c << 32) | l, k);   // valid for bits 0 .. 33
-  const unsigned long long hi = and_window(((unsigned long long)r << 32) | c, k);   // columns 32 .. 65
-  const unsigned long long e = (lo & 0xffffffffull) | (hi << 32);
-  return (unsigned)(or_window(e, k) >> 32);
-}
-
-// item `it` of a (rows x n) grid as (row, column), stepped by the workgroup's size without a division per item
-struct OpenItem {
-  int it, row, col, drow, dcol;
-  __device__ OpenItem(int tid, int n) : it(tid), row(tid / n), col(tid - (tid / n) * n), drow(OPEN_NT / n), dcol(OPEN_NT - (OPEN_NT / n) * n) {}
-  __device__ void next(int n) {
-    it += OPEN_NT; row += drow; col += dcol;
-    if (col >= n) { col -= n; ++row; }
-  }
-};
-
-// The plane geometry of instance b.  Uniform form: the argument block's own, planes a stride apart.  Frames form: formed here from the
-// la3d_frame row of image_index[b] - every value wave-uniform, through scalar loads, checked before an address is formed from it, in
-// the order of frames_prologue (image index, frame row, input offset), then the output offset (the same rule), then that either plane
-// ends inside its buffer.  The output plane is the one frame_table lays out for an image of (s * H, s * fw): pitch roundup32(s * fw),
-// so its rows are whole words.  false: refused - nothing is read, nothing is written.
-template <bool FRAMES>
-__device__ inline bool open_instance(const OpenArgs& a, int b, OpenArgs* g, const unsigned** plane, unsigned** op) {
-  if constexpr (FRAMES) {
-    FramesWork f;
-    if (!frames_prologue<true, false>(a.frames, a.P, a.image_index, a.H, a.W, const_cast<unsigned*>(a.bits), a.offsets, b, 0, &f)) return false;
-    long long oo = 0;
-    if (a.out && !frames_plane_at(a.out_offsets, b, &oo)) return false;
-    const int fw_out = a.s * f.r.fw, W_out = (fw_out + 31) & ~31, H_out = a.s * f.r.H;
-    const int words_out = H_out * (W_out >> 5);          // (<= 2^23: the entry bounds s * H * roundup32(s * W) by 2^28)
-    if (f.off > a.bits_words - f.nwords) return false;
-    if (a.out && oo > a.out_words - words_out) return false;
-    g->H = f.r.H; g->W = f.r.W; g->fw = f.r.fw; g->nwords_in = f.nwords;
-    g->H_out = H_out; g->W_out = W_out; g->nw = W_out >> 5; g->nwords_out = words_out;
-    g->vec = (W_out & 127) == 0;                         // (out is 16-byte aligned - checked on the host - and the offset a multiple of 4)
-    *plane = a.bits + f.off;                             // (formed only now: after the last check)
-    *op = a.out ? a.out + oo : nullptr;
-  } else {
-    *plane = a.bits + (long long)b * a.stride;
-    *op = a.out ? a.out + (long long)b * a.out_stride : nullptr;
-  }
-  return true;
-}
-
-template <bool FRAMES>
-__global__ __launch_bounds__(OPEN_NT) void open_bits_kernel(const OpenArgs call) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ int red[5 * (OPEN_NT / 64)];
-  const int tid = threadIdx.x, b = blockIdx.x / call.nbands, band = blockIdx.x - b * call.nbands;
-  // frames form: the grid has the bands of the bounds; a workgroup of a refused instance, or whose band lies below its instance's last
-  // row, ends here (uniform: before any barrier)
-  OpenArgs own;
-  const unsigned* plane;
-  unsigned* op;
-  if constexpr (FRAMES) {
-    own = call;
-    if (!open_instance<true>(call, b, &own, &plane, &op)) return;
-    if (band * call.R >= own.H_out) return;
-  } else {
-    open_instance<false>(call, b, nullptr, &plane, &op);
-  }
-  const OpenArgs& a = FRAMES ? own : call;
-  unsigned* A = reinterpret_cast<unsigned*>(smem);
-  unsigned* Bv = A + (size_t)a.nA * a.nw;
-  const int r = a.k >> 1, s = a.s, nw = a.nw, k = a.k;
-  const int r0 = band * a.R;
-  const int rows = min(a.R, a.H_out - r0);            // output rows of this band (>= 1)
-  // floor((r0 - 2r) / s): the first source row of A (negative above the image)
-  const int t0 = r0 - 2 * r;
-  const int ls = s >> 1;                               // log2 s for s = 1, 2, 4: x >> ls is floor(x / s), negative x included
-  const int vA0 = t0 >> ls;
-  for (OpenItem i(tid, nw); i.it < a.nA * nw; i.next(nw)) {
-    const int v = vA0 + i.row;
-    A[i.it] = (v >= 0 && v < a.H) ? open_source_word(a, plane, v, i.col) : 0u;
-  }
-  __syncthreads();
-  // vertical erosion: B row j is upscaled row V = r0 - r + j, the AND of upscaled rows V - r .. V + r = source rows floor((V - r) / s) ..
-  // floor((V + r) / s); V - r >= r0 - 2r, so both lie in A
-  const int nB = rows + 2 * r;
-  for (OpenItem i(tid, nw); i.it < nB * nw; i.next(nw)) {
-    const int lo = t0 + i.row, hi = lo + 2 * r;       // upscaled rows V - r, V + r
-    const int a0 = (lo >> ls) - vA0, a1 = (hi >> ls) - vA0;
-    const unsigned* col = A + i.col;
-    unsigned x = ~0u;
-#pragma unroll 4
-    for (int q = a0; q <= a1; ++q) x &= col[q * nw];
-    Bv[i.it] = x;
-  }
-  __syncthreads();
-  // horizontal opening, in place: wave w owns rows w, w + 4, ..; it reads the whole row (nw <= 256 = four words per lane) before it
-  // writes any of it
-  if (k > 1) {
-    const int lane = tid & 63, wave = tid >> 6;
-    for (int j = wave; j < nB; j += OPEN_NT / 64) {
-      unsigned* row = Bv + j * nw;
-      unsigned res[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int wc = q * 64 + lane;
-        res[q] = 0u;
-        if (wc < nw) res[q] = open_row_word(wc > 0 ? row[wc - 1] : 0u, row[wc], wc + 1 < nw ? row[wc + 1] : 0u, k);
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int wc = q * 64 + lane;
-        if (wc < nw) row[wc] = res[q];
-      }
-    }
-  }
-  __syncthreads();
-  // vertical dilation: the word (v, wc) of the opened band, v relative to r0; counted for the statistics as it is formed
-  const int tail = s * a.fw - (nw - 1) * 32;          // image bits of the last word column (1 .. 32)
-  const unsigned tail_mask = tail < 32 ? (1u << tail) - 1u : ~0u;
-  int area = 0, ymin = 0x7fffffff, ymax = -1, xmin = 0x7fffffff, xmax = -1;
-  auto word = [&](int v, int wc) -> unsigned {
-    if (wc >= nw) return 0u;
-    const unsigned* col = Bv + v * nw + wc;
-    unsigned x = 0u;
-#pragma unroll 8
-    for (int q = 0; q < k; ++q) x |= col[q * nw];                // B rows of upscaled rows r0 + v - r .. r0 + v + r
-    if (wc == nw - 1) x &= tail_mask;
-    return x;
-  };
-  auto count = [&](int v, int wc, unsigned x) {
-    if (!x) return;
-    area += __popc(x);
-    ymin = min(ymin, r0 + v); ymax = max(ymax, r0 + v);
-    xmin = min(xmin, wc * 32 + __ffs((int)x) - 1); xmax = max(xmax, wc * 32 + 31 - __clz((int)x));
-  };
-  const bool aligned = (a.W_out & 31) == 0;           // (frames form: always)
-  if (op && aligned && a.vec) {                        // rows of whole words, 16-byte stores: four words per thread
-    const int wq = a.W_out >> 7;                       // (vec: W_out % 128 == 0)
-    u32x4* o4 = reinterpret_cast<u32x4*>(op + (long long)r0 * (a.W_out >> 5));
-    for (OpenItem i(tid, wq); i.it < rows * wq; i.next(wq)) {
-      const int v = i.row, q = i.col, it = i.it;
-      u32x4 x;
-      x.x = word(v, 4 * q); x.y = word(v, 4 * q + 1); x.z = word(v, 4 * q + 2); x.w = word(v, 4 * q + 3);
-      count(v, 4 * q, x.x); count(v, 4 * q + 1, x.y); count(v, 4 * q + 2, x.z); count(v, 4 * q + 3, x.w);
-      o4[it] = x;
-    }
-  } else if (op && aligned) {                          // rows of whole words, word stores
-    const int ww = a.W_out >> 5;
-    unsigned* o = op + (long long)r0 * ww;
-    for (OpenItem i(tid, ww); i.it < rows * ww; i.next(ww)) {
-      const unsigned x = word(i.row, i.col);
-      count(i.row, i.col, x);
-      o[i.it] = x;
-    }
-  } else {
-    // statistics over the aligned words; then (W_out % 32 != 0) the general form of the store: every word of the band's range of the
-    // plane is gathered from the rows that cross it
-    if (a.partial)
-      for (OpenItem i(tid, nw); i.it < rows * nw; i.next(nw)) count(i.row, i.col, word(i.row, i.col));
-    if (!FRAMES && op) {
-      const long long bit0 = (long long)r0 * a.W_out;                       // a multiple of 32
-      const int w0 = (int)(bit0 >> 5);
-      const int w1 = (int)min((long long)a.nwords_out, (bit0 + (long long)a.R * a.W_out) >> 5);
-      for (int j = w0 + tid; j < w1; j += OPEN_NT) {
-        unsigned x = 0u;
-        int g = (j - w0) * 32, filled = 0;                                  // bit of the band at which the next piece begins
-        while (filled < 32) {
-          const int v = g / a.W_out, col = g - v * a.W_out;
-          if (v >= rows) break;                                             // past the plane's last row: the tail bits stay zero
-          const int n = min(32 - filled, a.W_out - col);
-          const int wc = col >> 5, sh = col & 31;
-          unsigned p = word(v, wc) >> sh;
-          if (sh && sh + n > 32) p |= word(v, wc + 1) << (32 - sh);
-          if (n < 32) p &= (1u << n) - 1u;
-          x |= p << filled;
-          filled += n; g += n;
-        }
-        op[j] = x;
-      }
-    }
-  }
-  if (a.partial) {
-    area = wave_sum_i(area); ymin = wave_min_i(ymin); ymax = wave_max_i(ymax); xmin = wave_min_i(xmin); xmax = wave_max_i(xmax);
-    const int wave = tid >> 6;
-    if ((tid & 63) == 0) { red[wave] = area; red[4 + wave] = ymin; red[8 + wave] = ymax; red[12 + wave] = xmin; red[16 + wave] = xmax; }
-    __syncthreads();
-    if (tid == 0) {
-      int* p = a.partial + ((long long)b * a.nbands + band) * 8;
-      p[0] = red[0] + red[1] + red[2] + red[3];
-      p[1] = min(min(red[4], red[5]), min(red[6], red[7]));
-      p[2] = max(max(red[8], red[9]), max(red[10], red[11]));
-      p[3] = min(min(red[12], red[13]), min(red[14], red[15]));
-      p[4] = max(max(red[16], red[17]), max(red[18], red[19]));
-    }
-  }
-}
-
-// the band records of one instance -> stats[b] = area, x, y, w, h (cv2.boundingRect of a binary image; 0, 0, 0, 0 when empty): one
-// wave per instance, every band record has one writer and one reader - no atomics
-__device__ inline void open_stats_reduce(const int* __restrict__ p, int nbands, int lane, int* __restrict__ o) {
-  int area = 0, ymin = 0x7fffffff, ymax = -1, xmin = 0x7fffffff, xmax = -1;
-  for (int i = lane; i < nbands; i += 64) {
-    area += p[i * 8]; ymin = min(ymin, p[i * 8 + 1]); ymax = max(ymax, p[i * 8 + 2]);
-    xmin = min(xmin, p[i * 8 + 3]); xmax = max(xmax, p[i * 8 + 4]);
-  }
-  area = wave_sum_i(area); ymin = wave_min_i(ymin); ymax = wave_max_i(ymax); xmin = wave_min_i(xmin); xmax = wave_max_i(xmax);
-  if (lane == 0) {
-    const bool any = area > 0;
-    o[0] = area; o[1] = any ? xmin : 0; o[2] = any ? ymin : 0; o[3] = any ? xmax - xmin + 1 : 0; o[4] = any ? ymax - ymin + 1 : 0;
-  }
-}
-__global__ __launch_bounds__(64) void open_bits_stats_kernel(const int* __restrict__ partial, int nbands, int* __restrict__ stats) {
-  const int b = blockIdx.x;
-  open_stats_reduce(partial + (long long)b * nbands * 8, nbands, threadIdx.x, stats + (long long)b * 5);
-}
-// frames form: the decision of open_bits_kernel<true> made again, then only the records the instance's own bands wrote in this call
-// (the grid's further bands wrote none); a refused row gets -1, 0, 0, 0, 0
-__global__ __launch_bounds__(64) void open_bits_frames_stats_kernel(const OpenArgs call, int* __restrict__ stats) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  int* o = stats + (long long)b * 5;
-  OpenArgs own = call;
-  const unsigned* plane;
-  unsigned* op;
-  if (!open_instance<true>(call, b, &own, &plane, &op)) {
-    if (lane < 5) o[lane] = lane ? 0 : -1;
-    return;
-  }
-  open_stats_reduce(call.partial + (long long)b * call.nbands * 8, (own.H_out + call.R - 1) / call.R, lane, o);
-}
-
 }  // namespace
 
 // ==========================================================================================
 // host side: the destination, the ONE argument check and the launch helpers of the packer entries
 // ==========================================================================================
 namespace {
-constexpr size_t ANN_LDS_MAX = 160 * 1024 - 256;
-
 // workgroups per plane: enough to cover `items` once, at most 64 (grid-stride inside the plane beyond that)
 inline int plane_chunks(long long items) {
   const long long c = (items + 255) / 256;
   return (int)(c < 1 ? 1 : (c > 64 ? 64 : c));
 }
-// the elements of a stored plane / the words of the bounds' plane of a frames call (rows of whole words); 0 for sizes the check refuses
-inline long long plane_items(int H, int W_out) { return H > 0 && W_out > 0 ? (long long)H * W_out : 0; }
-inline long long bounds_words(int H, int W) { return H > 0 && W > 0 ? (long long)H * (((long long)W + 31) / 32) : 0; }
-
-// How an entry describes its destination - to pack_check, and to the kernels that take a BitsOut.
-BitsOut bits_out_uniform(int H, int W, int W_out, uint32_t* bits, long long stride, int32_t* area) {
-  BitsOut c = {};
-  c.bits = bits; c.stride = stride; c.area = area;
-  c.H = H; c.W = W_out; c.frame_w = W_out > W ? W : 0;
-  c.lds_words = (int)la3d_mask_bits_words(H, W_out);
-  c.vec = ((reinterpret_cast<uintptr_t>(bits) & 15) == 0 && stride % 4 == 0) ? 1 : 0;
-  return c;
-}
-BitsOut bits_out_frames(const la3d_frame* frames, int P, int H, int W, const int32_t* image_index, uint32_t* bits, const int64_t* bits_offsets,
-                        int32_t* area) {
-  BitsOut c = {};
-  c.bits = bits; c.offsets = reinterpret_cast<const long long*>(bits_offsets); c.area = area;
-  c.frames = frames; c.image_index = image_index; c.P = P;
-  c.H = H; c.W = W; c.lds_words = (int)bounds_words(H, W); c.vec = 1;
-  return c;
-}
-
-int pack_refuse(const char* who, const char* what, int code = LA3D_ERR_ARG) {
-  char msg[256];
-  snprintf(msg, sizeof(msg), "%s: %s", who, what);
-  set_err(msg);
-  return code;
-}
-
-// The argument check of every packer entry.  The rules and their rank are the same for all of them and stated here, once; an entry
-// brings its sizes, its pointers and ITS wording of each rule (the text of a refusal is part of the C ABI: two entries that phrase one
-// rule differently keep their phrasing).  A rule whose wording is NULL does not exist for that entry.
-//   1  sizes         B, P < 0, H, W <= 0, W_out < W                                    (P = 1: an entry without images)
-//   2  shape         the entry's own bound on the frame and the grid: `shape_bad`
-//   3  null_ptr      a pointer of the list that is not optional is NULL                 \ only where there is work to do
-//   4  misaligned    (address & mask) != 0, pointer by pointer in the order of the list /
-//   5  lds           the bit image does not fit LDS: `lds_bad` - LA3D_ERR_UNSUPPORTED, every other rule LA3D_ERR_ARG
-//   6  src_stride    uniform form: the source's plane stride < H*W                      \ only where there is work to do
-//   7  bits_stride   uniform form: out.stride < la3d_mask_bits_words(H, W_out)          /   (the frames form has neither)
-// Returns the refusal's code (la3d_last_error() is set), PACK_NOTHING (the call is valid and has no work: success) or PACK_LAUNCH.
-enum { PACK_LAUNCH = 0, PACK_NOTHING = 1 };
-struct PackWords { const char *sizes, *shape, *null_ptr, *lds, *src_stride, *bits_stride; };
-struct PackPtr { const void* p; unsigned mask; const char* misaligned; bool optional = false; };
-
-int pack_check(const char* who, const PackWords& say, int B, int P, int W, bool work, bool shape_bad, bool lds_bad,
-               std::initializer_list<PackPtr> ptrs, long long src_stride, const BitsOut& out) {
-  if (B < 0 || P < 0 || out.H <= 0 || W <= 0 || out.W < W) return pack_refuse(who, say.sizes);
-  if (say.shape && shape_bad) return pack_refuse(who, say.shape);
-  if (work) {
-    for (const PackPtr& q : ptrs)
-      if (!q.p && !q.optional) return pack_refuse(who, say.null_ptr);
-    for (const PackPtr& q : ptrs)
-      if (reinterpret_cast<uintptr_t>(q.p) & q.mask) return pack_refuse(who, q.misaligned);
-  }
-  if (say.lds && lds_bad) return pack_refuse(who, say.lds, LA3D_ERR_UNSUPPORTED);
-  if (work && say.src_stride && src_stride < (long long)out.H * W) return pack_refuse(who, say.src_stride);
-  if (work && say.bits_stride && out.stride < (long long)la3d_mask_bits_words(out.H, out.W)) return pack_refuse(who, say.bits_stride);
-  return work ? PACK_LAUNCH : PACK_NOTHING;
-}
-inline int pack_done(int rc) { return rc < 0 ? rc : LA3D_SUCCESS; }   // what an entry returns when pack_check said anything but PACK_LAUNCH
 
 const char* const SIZES_UNIFORM = "bad argument (B >= 0, H, W > 0, W_out >= W)";
-const char* const SIZES_FRAMES = "bad argument (B, P >= 0, bounds H, W > 0)";
-const char* const BITS_STRIDE = "bits_plane_stride is smaller than la3d_mask_bits_words(H, W_out)";
 const char* const BITS_4 = "bits not a 4-byte aligned pointer";
 const char* const LABEL_DTYPE = "unknown dtype (LA3D_LABEL_U8, LA3D_LABEL_U16, LA3D_LABEL_I32 or LA3D_LABEL_RGB8)";
 const char* const LABEL_PTRS_4 = "inst_offsets, inst_label or area not a 4-byte aligned pointer";
@@ -1520,54 +870,6 @@ int pack_crop_launch(const CropSrc& src, int B, const BitsOut& c, void* stream) 
   hipLaunchKernelGGL(pack_crop_bits_kernel<FRAMES>, dim3((unsigned)B, (unsigned)((c.lds_words + 255) / 256)), dim3(256), 0, s, src, c);
   return check_launch("pack_crop_bits_kernel");
 }
-
-// ---- bit planes -> run lengths: the check of both stages, made before any launch.  The rules of the block itself come first; the
-// planes then go through pack_check as the SOURCE of the call (a BitsOut that is only read), in either form.  RLE_NOTHING: B == 0.
-enum { RLE_LAUNCH = 0, RLE_NOTHING = 1 };
-int rle_encode_check(const la3d_rle_encode_args* args, const char* who, bool emit, la3d_rle_encode_args& a, BitsOut& c, RleOut& e) {
-  static_assert(sizeof(la3d_rle_encode_args) == 120, "la3d_rle_encode_args is part of the ABI");
-  if (!args || args->struct_size < (int32_t)sizeof(la3d_rle_encode_args)) return pack_refuse(who, "bad struct_size");
-  memcpy(&a, args, sizeof(a));   // (a longer block from a newer caller is fine)
-  if (a.B < 0 || a.H < 0 || a.W < 0 || a.P < 0) return pack_refuse(who, "negative sizes (B, H, W, P)");
-  if (a.frame_width < 0 || a.frame_width > a.W) return pack_refuse(who, "frame_width outside [0, W]");
-  if (a.bits_plane_stride < 0) return pack_refuse(who, "negative bits_plane_stride");
-  if (emit && a.capacity < 0) return pack_refuse(who, "negative capacity");
-  if (a.bits_offsets && !a.frames) return pack_refuse(who, "bits_offsets without frames");
-  if (a.frames && !a.image_index) return pack_refuse(who, "frames without image_index: instance n belongs to frame row image_index[n]");
-  if (a.frames && (a.frame_width != 0 || a.bits_plane_stride != 0))
-    return pack_refuse(who, "frame_width and bits_plane_stride must be 0 in a frames call (the frame table and bits_offsets say both)");
-  if (!a.offsets || (reinterpret_cast<uintptr_t>(a.offsets) & 7)) return pack_refuse(who, "offsets NULL or not an 8-byte aligned pointer");
-  memset(&e, 0, sizeof(e));
-  e.runs = a.runs; e.offsets = reinterpret_cast<long long*>(a.offsets); e.counts = a.counts; e.status = a.status; e.capacity = a.capacity;
-  e.ws = static_cast<int2*>(a.workspace); e.ws_cols = a.W;
-  if (a.B == 0) return RLE_NOTHING;
-  static const char* const p8 = "frames, bits_offsets or workspace not an 8-byte aligned pointer";
-  static const char* const p4 = "image_index, runs, counts or status not a 4-byte aligned pointer";
-  static const char* const nul = "NULL mask_bits, bits_offsets, runs, counts, status or workspace";
-  uint32_t* planes = const_cast<uint32_t*>(a.mask_bits);   // (read only: the kernels of this pair load through BitsOut::bits)
-  const bool no_counts = a.capacity == 0;                   // (no count can be written: counts may be NULL)
-  int rc;
-  if (a.frames) {
-    static const PackWords say = {"empty bounds (H, W > 0 with B > 0)", nullptr, nul, "the bit image of the bounds must fit LDS (H * roundup32(W) <= 1048576)",
-                                  nullptr, nullptr};
-    c = bits_out_frames(a.frames, a.P, a.H, a.W, a.image_index, planes, a.bits_offsets, nullptr);
-    rc = pack_check(who, say, a.B, a.P, a.W, true, false, bounds_words(a.H, a.W) > (1LL << 15),
-                    {{planes, 15, "mask_bits of a frames call not a 16-byte aligned pointer"}, {a.frames, 7, p8}, {a.bits_offsets, 7, p8},
-                     {a.workspace, 7, p8}, {a.image_index, 3, p4}, {a.runs, 3, p4, emit}, {a.counts, 3, p4, !emit || no_counts},
-                     {a.status, 3, p4, !emit}}, 0, c);
-  } else {
-    static const PackWords say = {"empty frame (H, W > 0 with B > 0)", nullptr, nul, "the bit image must fit LDS (H*W <= 1048576)", nullptr,
-                                  "bits_plane_stride is smaller than la3d_mask_bits_words(H, W)"};
-    const int fw = a.frame_width ? a.frame_width : a.W;
-    const long long stride = a.bits_plane_stride ? (long long)a.bits_plane_stride : (long long)la3d_mask_bits_words(a.H, a.W);
-    c = bits_out_uniform(a.H, fw, a.W, planes, stride, nullptr);
-    rc = pack_check(who, say, a.B, 1, fw, true, false, plane_items(a.H, a.W) > (1LL << 20),
-                    {{planes, 3, "mask_bits not a 4-byte aligned pointer"}, {a.workspace, 7, p8}, {a.runs, 3, p4, emit},
-                     {a.counts, 3, p4, !emit || no_counts}, {a.status, 3, p4, !emit}}, 0, c);
-  }
-  return rc == PACK_LAUNCH ? RLE_LAUNCH : rc;   // (work is always true here: PACK_NOTHING does not come back)
-}
-inline size_t rle_encode_lds(const BitsOut& c) { return (((size_t)c.lds_words * 4 + 15) & ~(size_t)15) + RLE_SCAN_BYTES; }
 }  // namespace
 
 extern "C" {
@@ -1783,175 +1085,6 @@ int la3d_pack_logits_bits_frames(const void* logits, int dtype, float threshold,
   const int kind = dtype == LA3D_DTYPE_F32 ? PK_F32 : dtype == LA3D_DTYPE_F16 ? PK_F16 : PK_BF16;
   return pack_masks_frames("la3d_pack_logits_bits_frames", logits, kind, threshold, frames, P, H, W, image_index, src_offsets, src_pitch, B,
                            bits, bits_offsets, area, stream);
-}
-
-size_t la3d_rle_encode_workspace_bytes(int B, int H, int W) {
-  if (B <= 0 || H <= 0 || W <= 0) return 0;
-  return (size_t)B * (size_t)W * sizeof(int2);   // (T, L) of every column of every instance
-}
-
-int la3d_rle_encode_offsets(const la3d_rle_encode_args* args) {
-  const char* who = "la3d_rle_encode_offsets";
-  la3d_rle_encode_args a;
-  BitsOut c;
-  RleOut e;
-  const int rc = rle_encode_check(args, who, false, a, c, e);
-  if (rc < 0) return rc;
-  hipStream_t s = static_cast<hipStream_t>(a.stream);
-  if (rc == RLE_LAUNCH) {
-    if (a.frames) {
-      allow_big_lds(reinterpret_cast<const void*>(rle_encode_count_kernel<true>));
-      hipLaunchKernelGGL(rle_encode_count_kernel<true>, dim3((unsigned)a.B), dim3(NT_DEC), rle_encode_lds(c), s, c, e);
-    } else {
-      allow_big_lds(reinterpret_cast<const void*>(rle_encode_count_kernel<false>));
-      hipLaunchKernelGGL(rle_encode_count_kernel<false>, dim3((unsigned)a.B), dim3(NT_DEC), rle_encode_lds(c), s, c, e);
-    }
-    const int rc2 = check_launch("rle_encode_count_kernel");
-    if (rc2 != LA3D_SUCCESS) return rc2;
-  }
-  hipLaunchKernelGGL(rle_encode_scan_kernel, dim3(1), dim3(RLE_ST), 0, s, e.runs, e.offsets, a.B);   // (B == 0: offsets[0] = 0)
-  return check_launch("rle_encode_scan_kernel");
-}
-
-int la3d_rle_encode(const la3d_rle_encode_args* args) {
-  const char* who = "la3d_rle_encode";
-  la3d_rle_encode_args a;
-  BitsOut c;
-  RleOut e;
-  const int rc = rle_encode_check(args, who, true, a, c, e);
-  if (rc != RLE_LAUNCH) return pack_done(rc);
-  hipStream_t s = static_cast<hipStream_t>(a.stream);
-  if (a.frames) {
-    allow_big_lds(reinterpret_cast<const void*>(rle_encode_emit_kernel<true>));
-    hipLaunchKernelGGL(rle_encode_emit_kernel<true>, dim3((unsigned)a.B), dim3(NT_DEC), rle_encode_lds(c), s, c, e);
-  } else {
-    allow_big_lds(reinterpret_cast<const void*>(rle_encode_emit_kernel<false>));
-    hipLaunchKernelGGL(rle_encode_emit_kernel<false>, dim3((unsigned)a.B), dim3(NT_DEC), rle_encode_lds(c), s, c, e);
-  }
-  return check_launch("rle_encode_emit_kernel");
-}
-
-// ---- morphology on bit planes ----
-namespace {
-// the band of one launch: 64 output rows where the two LDS images of such a band stay within 48 KiB (three workgroups per CU), else 32
-// - the least a band can have (its first row has to begin on a word of the output)
-struct OpenPlan { int R, nA, nbands; size_t lds; };
-OpenPlan open_plan(int H_out, int nw, int k, int s) {
-  const int r = k / 2;
-  auto at = [&](int R) {
-    OpenPlan p;
-    p.R = R;
-    p.nA = (R + 4 * r - 1 + s - 1) / s + 1;          // floor((t0 + R + 4r - 1) / s) - floor(t0 / s) + 1 at most
-    p.nbands = (H_out + R - 1) / R;
-    p.lds = (size_t)(p.nA + R + 2 * r) * nw * sizeof(unsigned);
-    return p;
-  };
-  const OpenPlan p64 = at(64);
-  return (H_out > 32 && p64.lds <= 48 * 1024) ? p64 : at(32);
-}
-}  // namespace
-
-size_t la3d_open_bits_workspace_bytes(int B, int H, int upscale) {
-  if (B <= 0 || H <= 0 || upscale <= 0) return 0;
-  return (size_t)B * (((size_t)H * (size_t)upscale + 31) / 32) * 8 * sizeof(int);   // one record per band of 32 rows: no plan has more
-}
-
-int la3d_open_bits(const uint32_t* bits, int64_t bits_plane_stride, int B, int H, int W, int frame_width, int k, int upscale,
-                   uint32_t* out_bits, int64_t out_plane_stride, int W_out, int32_t* stats, void* workspace, void* stream) {
-  const char* who = "la3d_open_bits";
-  const int s = upscale;
-  if (B < 0 || H <= 0 || W <= 0) return pack_refuse(who, "bad argument (B >= 0, H, W > 0)");
-  if (k < 1 || k > 31 || !(k & 1)) return pack_refuse(who, "k must be odd and lie in 1 .. 31");
-  if (s != 1 && s != 2 && s != 4) return pack_refuse(who, "upscale must be 1, 2 or 4");
-  if (frame_width <= 0 || frame_width > W) return pack_refuse(who, "frame_width must lie in (0, W]");
-  if (!out_bits && !stats) return pack_refuse(who, "nothing to do: out_bits and stats are both NULL");
-  if (out_bits && (long long)W_out < (long long)s * frame_width) return pack_refuse(who, "W_out is smaller than upscale * frame_width");
-  if (B == 0) return LA3D_SUCCESS;
-  if (!bits || (stats && !workspace)) return pack_refuse(who, "bits (and workspace, with stats) must not be NULL");
-  if ((reinterpret_cast<uintptr_t>(bits) | reinterpret_cast<uintptr_t>(out_bits) | reinterpret_cast<uintptr_t>(stats) |
-       reinterpret_cast<uintptr_t>(workspace)) & 3)
-    return pack_refuse(who, "bits, out_bits, stats or workspace not a 4-byte aligned pointer");
-  if (!out_bits) W_out = s * frame_width;             // statistics only: the plane that is never stored
-  if ((long long)s * frame_width > 8192) return pack_refuse(who, "upscale * frame_width must not exceed 8192 (a band of rows lives in LDS)", LA3D_ERR_UNSUPPORTED);
-  if ((long long)s * H > (1LL << 28) || (long long)s * H * W_out > (1LL << 28))
-    return pack_refuse(who, "upscale * H * W_out must not exceed 2^28", LA3D_ERR_UNSUPPORTED);
-  const int H_out = s * H;
-  const long long words_in = (long long)la3d_mask_bits_words(H, W), words_out = ((long long)H_out * W_out + 31) / 32;
-  if (bits_plane_stride < words_in) return pack_refuse(who, BITS_STRIDE);
-  if (out_bits) {
-    if (out_plane_stride < words_out) return pack_refuse(who, "out_plane_stride is smaller than la3d_mask_bits_words(upscale * H, W_out)");
-    // neighbouring bands read each other's halo: the call cannot work in place
-    const uintptr_t i0 = reinterpret_cast<uintptr_t>(bits), i1 = i0 + (uintptr_t)B * (uintptr_t)bits_plane_stride * 4;
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out_bits), o1 = o0 + (uintptr_t)B * (uintptr_t)out_plane_stride * 4;
-    if (i0 < o1 && o0 < i1) return pack_refuse(who, "the input planes and the output planes overlap");
-  }
-  const int nw = (s * frame_width + 31) / 32;
-  const OpenPlan p = open_plan(H_out, nw, k, s);
-  if ((long long)B * p.nbands > 0x7fffffffLL) return pack_refuse(who, "too many bands for one launch (B * bands > 2^31 - 1)", LA3D_ERR_UNSUPPORTED);
-  OpenArgs a = {};
-  a.bits = bits; a.stride = bits_plane_stride; a.H = H; a.W = W; a.fw = frame_width; a.nwords_in = words_in;
-  a.k = k; a.s = s; a.out = out_bits; a.out_stride = out_plane_stride;
-  a.H_out = H_out; a.W_out = W_out; a.nw = nw; a.nwords_out = (int)words_out;
-  a.R = p.R; a.nA = p.nA; a.nbands = p.nbands;
-  a.vec = (out_bits && W_out % 128 == 0 && (reinterpret_cast<uintptr_t>(out_bits) & 15) == 0 && out_plane_stride % 4 == 0) ? 1 : 0;
-  a.partial = stats ? static_cast<int*>(workspace) : nullptr;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  allow_big_lds(reinterpret_cast<const void*>(open_bits_kernel<false>));
-  hipLaunchKernelGGL(open_bits_kernel<false>, dim3((unsigned)((long long)B * p.nbands)), dim3(OPEN_NT), p.lds, st, a);
-  const int rc = check_launch("open_bits_kernel");
-  if (rc != LA3D_SUCCESS || !stats) return rc;
-  hipLaunchKernelGGL(open_bits_stats_kernel, dim3((unsigned)B), dim3(64), 0, st, a.partial, p.nbands, stats);
-  return check_launch("open_bits_stats_kernel");
-}
-
-size_t la3d_open_bits_frames_workspace_bytes(int B, int H, int upscale) { return la3d_open_bits_workspace_bytes(B, H, upscale); }
-
-int la3d_open_bits_frames(const uint32_t* bits, int64_t bits_words, const int64_t* bits_offsets, const la3d_frame* frames, int32_t P, int H,
-                          int W, const int32_t* image_index, int B, int k, int upscale, uint32_t* out_bits, int64_t out_words,
-                          const int64_t* out_offsets, int32_t* stats, void* workspace, void* stream) {
-  const char* who = "la3d_open_bits_frames";
-  const int s = upscale;
-  auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
-  if (B < 0 || P < 0 || H <= 0 || W <= 0) return pack_refuse(who, SIZES_FRAMES);
-  if (k < 1 || k > 31 || !(k & 1)) return pack_refuse(who, "k must be odd and lie in 1 .. 31");
-  if (s != 1 && s != 2 && s != 4) return pack_refuse(who, "upscale must be 1, 2 or 4");
-  if (!out_bits && !stats) return pack_refuse(who, "nothing to do: out_bits and stats are both NULL");
-  if (bits_words < 0 || (out_bits && out_words < 0)) return pack_refuse(who, "bits_words and out_words must not be negative");
-  if (B > 0) {
-    if (!bits || !bits_offsets || (!frames && P > 0) || !image_index) return pack_refuse(who, "NULL bits, bits_offsets, frames or image_index");
-    if (out_bits && !out_offsets) return pack_refuse(who, "out_offsets must not be NULL with out_bits");
-    if (stats && !workspace) return pack_refuse(who, "workspace must not be NULL with stats");
-  }
-  if ((at(bits) | at(out_bits)) & 15) return pack_refuse(who, "bits or out_bits not a 16-byte aligned pointer");
-  if ((at(bits_offsets) | at(out_offsets) | at(frames)) & 7) return pack_refuse(who, "bits_offsets, out_offsets or frames not an 8-byte aligned pointer");
-  if ((at(stats) | at(workspace) | at(image_index)) & 3) return pack_refuse(who, "stats, workspace or image_index not a 4-byte aligned pointer");
-  if (bits && out_bits) {   // neighbouring bands read each other's halo: the call cannot work in place
-    const uintptr_t i0 = at(bits), i1 = i0 + (uintptr_t)bits_words * 4, o0 = at(out_bits), o1 = o0 + (uintptr_t)out_words * 4;
-    if (i0 < o1 && o0 < i1) return pack_refuse(who, "the input buffer and the output buffer overlap");
-  }
-  if ((long long)s * W > 8192) return pack_refuse(who, "upscale * W must not exceed 8192 (a band of rows lives in LDS)", LA3D_ERR_UNSUPPORTED);
-  const long long W_out = ((long long)s * W + 31) / 32 * 32;
-  if ((long long)s * H > (1LL << 28) || (long long)s * H * W_out > (1LL << 28))
-    return pack_refuse(who, "upscale * H * roundup32(upscale * W) must not exceed 2^28", LA3D_ERR_UNSUPPORTED);
-  const OpenPlan p = open_plan(s * H, (int)(W_out / 32), k, s);   // one plan per call, from the bounds
-  if ((long long)B * p.nbands > 0x7fffffffLL) return pack_refuse(who, "too many bands for one launch (B * bands > 2^31 - 1)", LA3D_ERR_UNSUPPORTED);
-  if (B == 0) return LA3D_SUCCESS;
-  OpenArgs a = {};
-  a.bits = bits; a.H = H; a.W = W; a.k = k; a.s = s; a.out = out_bits;
-  a.R = p.R; a.nA = p.nA; a.nbands = p.nbands;
-  a.partial = stats ? static_cast<int*>(workspace) : nullptr;
-  a.offsets = reinterpret_cast<const long long*>(bits_offsets); a.out_offsets = reinterpret_cast<const long long*>(out_offsets);
-  a.frames = frames; a.image_index = image_index; a.P = P; a.bits_words = bits_words; a.out_words = out_bits ? out_words : 0;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (P > 0) {   // (no image: every row is refused, which the statistics kernel alone says)
-    allow_big_lds(reinterpret_cast<const void*>(open_bits_kernel<true>));
-    hipLaunchKernelGGL(open_bits_kernel<true>, dim3((unsigned)((long long)B * p.nbands)), dim3(OPEN_NT), p.lds, st, a);
-    const int rc = check_launch("open_bits_kernel");
-    if (rc != LA3D_SUCCESS) return rc;
-  }
-  if (!stats) return LA3D_SUCCESS;
-  hipLaunchKernelGGL(open_bits_frames_stats_kernel, dim3((unsigned)B), dim3(64), 0, st, a, stats);
-  return check_launch("open_bits_frames_stats_kernel");
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // la3d_masks.hip - whole-frame depth_to_points (src/util.py:52-75), row padding, pixel counts, the host-side run-length string reader,
 // and the filter statistics of u8 planes, COCO run lengths and polygon parts (src/util.py:291-415) as kernels of their own.
-// Everything that reads or writes a BIT plane - and the family "annotation into an LDS bit image" (la3d_rle_decode / la3d_poly_decode
-// and the annotation packers, which share NT_DEC and bits_to_plane) - lives in la3d_bits.hip.
+// What reads or writes a BIT plane lives in units of its own: the packers, the unpacker, the plane statistics - and the family
+// "annotation into an LDS bit image" (la3d_rle_decode / la3d_poly_decode and the annotation packers, which share bits_to_plane) - in
+// la3d_bits.hip, the run-length encoder in la3d_rle_encode.hip, the opening in la3d_open.hip; la3d_bitplanes.hpp is what they share.
 #include <atomic>
 #include <chrono>
 #include <cstdint>

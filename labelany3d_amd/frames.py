@@ -1,7 +1,8 @@
 """Images of DIFFERENT sizes in one call (include/la3d.h "images of different sizes in one call"): the frame table, the packers that
 lay depth maps, label maps and mask stacks out by it (``pack_frames`` / ``pack_label_frames`` / ``pack_mask_frames``: one staging
 routine, one table), the bit planes of their instances and the ``fit_instances_frames*`` fits (one check of the ``frames`` argument).
-The sources of one frame size live in ``masks``, which re-exports the public names of this module; the call itself in ``fitcall``."""
+The sources of one frame size live in ``masks``, ``bits``, ``labels`` and ``depth16``; ``masks`` re-exports the public names of this
+module; the call itself in ``fitcall``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -14,8 +15,10 @@ from . import _lib
 from ._lib import check, lib
 from .batched import Depth16, _as_dev, _d16_block, _depth16_check, _dev, _ptr, _record, _stream, _upload_many, height_rule_code, padded_width, refuse_depth16
 from .fitcall import FramesDepth, fit_call, mask_source
-from .masks import (_D16_DTYPES, _LABEL_NUMPY, _LABEL_TORCH, _LOGIT_DTYPES, _crop_place, _crop_source, _crop_threshold, _gate_scalars, _label_rows,
-                    _open_scalars, _rle_capacity, _rle_counts, _rle_encode_run, crop_params)
+from .bits import _LOGIT_DTYPES, _crop_place, _crop_source, _crop_threshold, _gate_scalars, _open_scalars, _rle_capacity, _rle_encode_run, crop_params
+from .depth16 import _D16_DTYPES
+from .labels import _LABEL_NUMPY, _LABEL_TORCH, _label_rows
+from .masks import _rle_counts
 
 FRAME_DTYPE = np.dtype([("depth_offset", "<i8"), ("H", "<i4"), ("W", "<i4"), ("frame_width", "<i4"), ("reserved", "<i4")])
 """One row of the frame table of a frames call: ``la3d_frame`` of include/la3d.h (24 bytes)."""

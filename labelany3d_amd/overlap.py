@@ -13,7 +13,7 @@ from . import _lib
 from ._lib import check, lib
 from .batched import _bits_stride, _record, _stream, _upload_many
 from .frames import FrameBits, _on_gpu, _same_table
-from .masks import MaskBits
+from .bits import MaskBits
 
 TILE_DTYPE = np.dtype([(n, "<i8" if n == "out0" else "<i4") for n, _ in _lib.OverlapTile._fields_])
 """One row of the tile table of ``la3d_mask_overlap_plan``: ``la3d_overlap_tile`` of include/la3d.h (64 bytes)."""

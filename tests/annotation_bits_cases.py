@@ -7,7 +7,7 @@ import numpy as np
 from oracle import la3d_oracle as O
 from oracle import poly_oracle as P
 
-NT_DEC = 512   # threads of a decode workgroup = runs per decode step (labelany3d_amd/csrc/la3d_bits.hip)
+NT_DEC = 512   # threads of a decode workgroup = runs per decode step (labelany3d_amd/csrc/la3d_bitplanes.hpp)
 # (H, W, frame_pad): 8x32 one word per row; 7x64 14 words (three 16-byte groups + a tail of two); 75x64 150 words (tail of two);
 # odd widths padded (word-aligned rows, frame_w / clipW) and unpadded (the decoders' general routes, a ragged last word)
 UNIFORM = ((8, 32, True), (7, 64, True), (75, 64, True), (5, 13, True), (5, 13, False), (33, 47, True), (33, 47, False))

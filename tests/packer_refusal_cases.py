@@ -1,10 +1,14 @@
-"""The refusal cases of the 13 bit-plane entries of the C ABI (include/la3d.h "masks as bit planes" and later; kernels and checks:
-labelany3d_amd/csrc/la3d_bits.hip), shared by tests/test_packer_refusals_contract.py and by whoever records
-tests/golden/packer_refusals.json.
+"""The refusal cases of the bit-plane entries of the C ABI (include/la3d.h "masks as bit planes" and later; kernels and checks:
+labelany3d_amd/csrc/la3d_bits.hip - decoders, packers, unpacker, statistics -, la3d_rle_encode.hip - the run-length encoder -,
+la3d_open.hip - the opening; what they share: la3d_bitplanes.hpp), shared by tests/test_packer_refusals_contract.py and by whoever
+records tests/golden/packer_refusals.json.
 
 Every case starts from a valid call - host pointers into one small aligned buffer, never dereferenced, a NULL stream - and breaks one
 argument (or one of the pairs whose precedence is part of the contract).  The valid call itself is never made, and every case is
 either refused or has nothing to do: no case reaches a launch, so the cases run on a machine without a GPU.
+
+The encoder's pair takes an argument block (la3d_rle_encode_args): its cases change fields of a valid block, and "args" = None passes
+no block at all.  Its first stage writes offsets[0] on the stream even for B = 0 - that call reaches a launch and has no case here.
 
 ``run(lib)`` -> [[entry, case, return code, la3d_last_error() or "" for a success], ...] in a fixed order."""
 import ctypes as C
@@ -13,6 +17,9 @@ F32, F16, BF16 = 0, 1, 2            # LA3D_DTYPE_*
 U8, U16, I32, RGB8 = 0, 1, 2, 3     # LA3D_LABEL_*
 H, W = 8, 32                         # the valid frame: 8 words a plane
 BIG = dict(H=1 << 10, W=1 << 11)     # 2^21 pixels: more than a bit image in LDS holds, fine for the pixel packers
+BLOCK_ENTRIES = ("la3d_rle_encode_offsets", "la3d_rle_encode")   # one argument: a la3d_rle_encode_args block
+ENC_FIELDS = ["struct_size", "B", "H", "W", "frame_width", "P", "mask_bits", "bits_plane_stride", "frames", "image_index", "bits_offsets",
+              "runs", "offsets", "counts", "status", "capacity", "workspace"]
 
 
 def specs(p):
@@ -54,6 +61,146 @@ def specs(p):
                 ptrs(["frames", "image_index", "src_offsets", "bits", "bits_offsets"],
                      dict(bits=4, frames=8, src_offsets=8, bits_offsets=8, image_index=4, src_pitch=4, area=4)) + nothing_p)
     dec = sizes("BHW", False) + [("frame too large", dict(H=1 << 10, W=1 << 11))] + nothing
+
+    # ---- crop-space masks: the rules of the source come before the packers' own ----
+    crop_v = dict(crops=p, crop_stride=16, row_pitch=4, pixel_step=1, S=4, threshold=127, place=p)
+    crop_args = ["crops", "crop_stride", "row_pitch", "pixel_step", "S", "threshold", "place"]
+    crop_src = [("S=0", dict(S=0)), ("S=-1", dict(S=-1)), ("pixel_step=0", dict(pixel_step=0)), ("row_pitch<S*pixel_step", dict(row_pitch=3)),
+                ("row_pitch<S*pixel_step, step 2", dict(pixel_step=2, row_pitch=7, crop_stride=64)),
+                ("threshold=-1", dict(threshold=-1)), ("threshold=256", dict(threshold=256)),
+                ("short crop_stride", dict(crop_stride=15)), ("crop_stride=0", dict(crop_stride=0)),
+                ("B*crop_stride overflows", dict(crop_stride=1 << 62, B=4)), ("place misaligned", dict(place=p + 2)),
+                ("place misaligned, B=0", dict(place=p + 2, B=0)),
+                ("source before crop_stride", dict(S=0, crop_stride=0)), ("crop_stride before place", dict(crop_stride=15, place=p + 2)),
+                ("source before sizes", dict(threshold=256, H=0)), ("source before B=-1", dict(S=0, B=-1)),
+                ("crop_stride before sizes", dict(crop_stride=15, W=0)), ("place before sizes", dict(place=p + 2, H=0)),
+                ("place before NULL", dict(place=p + 2, bits=None)), ("source before B=0", dict(pixel_step=0, B=0))]
+    crop_lds = [("source before LDS bound", dict(BIG, S=0))]
+    crop_lds_u = [("source before LDS bound", dict(BIG, S=0, W_out=BIG["W"], bits_plane_stride=1 << 16))]
+    # ---- bit planes -> run lengths: a block; the stage decides which of runs / counts / status may be NULL ----
+    enc_v = dict(struct_size=120, B=1, H=H, W=W, frame_width=0, P=0, mask_bits=p, bits_plane_stride=0, frames=None, image_index=None,
+                 bits_offsets=None, runs=p, offsets=p, counts=p, status=p, capacity=64, workspace=p)
+    enc_f = dict(P=1, frames=p, image_index=p, bits_offsets=p)
+
+    def enc_cases(emit):
+        c = [("args=NULL", dict(args=None)), ("struct_size=0", dict(struct_size=0)), ("struct_size=8", dict(struct_size=8)),
+             ("struct_size=119", dict(struct_size=119)), ("a longer block is read", dict(struct_size=128, B=-1)),
+             ("struct_size before sizes", dict(struct_size=0, B=-1))]
+        c += [(f"{n}=-1", {n: -1}) for n in "BHWP"]
+        c += [("frame_width=-1", dict(frame_width=-1)), ("frame_width>W", dict(frame_width=W + 1)), ("sizes before frame_width", dict(H=-1, frame_width=-1)),
+              ("bits_plane_stride=-1", dict(bits_plane_stride=-1)), ("frame_width before stride", dict(frame_width=W + 1, bits_plane_stride=-1)),
+              ("bits_offsets without frames", dict(bits_offsets=p)), ("frames without image_index", dict(frames=p, bits_offsets=p)),
+              ("bits_offsets before image_index", dict(bits_offsets=p, image_index=p)),
+              ("frame_width in a frames call", dict(enc_f, frame_width=16)), ("stride in a frames call", dict(enc_f, bits_plane_stride=8)),
+              ("offsets=NULL", dict(offsets=None)), ("offsets misaligned", dict(offsets=p + 4)), ("offsets=NULL, frames", dict(enc_f, offsets=None)),
+              ("frames rules before offsets", dict(enc_f, frame_width=16, offsets=None)),
+              ("offsets before B=0", dict(B=0, offsets=None)),
+              ("B=0, every pointer NULL", dict(B=0, mask_bits=None, runs=None, offsets=None, counts=None, status=None, workspace=None)),
+              ("offsets before sizes", dict(offsets=None, H=0)),
+              ("H=0", dict(H=0)), ("W=0", dict(W=0)), ("H=0, frames", dict(enc_f, H=0)), ("W=0, frames", dict(enc_f, W=0)),
+              ("mask_bits=NULL", dict(mask_bits=None)), ("workspace=NULL", dict(workspace=None)),
+              ("mask_bits=NULL, frames", dict(enc_f, mask_bits=None)), ("bits_offsets=NULL, frames", dict(enc_f, bits_offsets=None)),
+              ("workspace=NULL, frames", dict(enc_f, workspace=None)),
+              ("mask_bits misaligned", dict(mask_bits=p + 2)), ("workspace misaligned", dict(workspace=p + 4)),
+              ("mask_bits misaligned, frames", dict(enc_f, mask_bits=p + 8)), ("frames misaligned", dict(enc_f, frames=p + 4)),
+              ("bits_offsets misaligned, frames", dict(enc_f, bits_offsets=p + 4)), ("workspace misaligned, frames", dict(enc_f, workspace=p + 4)),
+              ("image_index misaligned, frames", dict(enc_f, image_index=p + 2)),
+              ("NULL before misaligned", dict(workspace=None, mask_bits=p + 2)),
+              ("short bits stride", dict(bits_plane_stride=7)), ("short bits stride, padded rows", dict(W=64, frame_width=40, bits_plane_stride=15)),
+              ("LDS bound", dict(BIG)), ("LDS bound, frames", dict(enc_f, **BIG)), ("LDS bound, frames, padded", dict(enc_f, H=1 << 10, W=(1 << 10) + 1)),
+              ("LDS bound before short stride", dict(BIG, bits_plane_stride=7)), ("NULL before LDS bound", dict(BIG, mask_bits=None)),
+              ("misaligned before LDS bound", dict(BIG, workspace=p + 4)), ("misaligned before LDS bound, frames", dict(enc_f, image_index=p + 2, **BIG)),
+              ("sizes before NULL", dict(H=0, mask_bits=None))]
+        if emit:
+            c += [("capacity=-1", dict(capacity=-1)), ("stride before capacity", dict(bits_plane_stride=-1, capacity=-1)),
+                  ("capacity before bits_offsets", dict(capacity=-1, bits_offsets=p)),
+                  ("counts=NULL", dict(counts=None)), ("status=NULL", dict(status=None)), ("counts=NULL, frames", dict(enc_f, counts=None)),
+                  ("status=NULL, frames", dict(enc_f, status=None)),
+                  ("counts misaligned", dict(counts=p + 2)), ("status misaligned", dict(status=p + 2)), ("runs misaligned", dict(runs=p + 2)),
+                  ("runs may be NULL", dict(runs=None, status=p + 2)), ("runs may be NULL, frames", dict(enc_f, runs=None, status=p + 2)),
+                  ("capacity=0 lets counts be NULL", dict(capacity=0, counts=None, status=p + 2)),
+                  ("capacity=0 lets counts be NULL, frames", dict(enc_f, capacity=0, counts=None, status=p + 2)),
+                  ("capacity=0, status=NULL", dict(capacity=0, counts=None, status=None)),
+                  ("capacity=0, counts misaligned", dict(capacity=0, counts=p + 2)),
+                  ("B=0", dict(B=0)), ("B=0, only offsets", dict(B=0, mask_bits=None, runs=None, counts=None, status=None, workspace=None)),
+                  ("B=0, empty frame", dict(B=0, H=0, W=0)), ("B=0, frames", dict(enc_f, B=0, P=0))]
+        else:
+            c += [("runs=NULL", dict(runs=None)), ("runs=NULL, frames", dict(enc_f, runs=None)), ("runs misaligned", dict(runs=p + 2)),
+                  ("counts misaligned", dict(counts=p + 2)), ("status misaligned", dict(status=p + 2)),
+                  ("counts and status may be NULL", dict(counts=None, status=None, runs=p + 2)),
+                  ("counts and status may be NULL, frames", dict(enc_f, counts=None, status=None, runs=p + 2)),
+                  ("capacity is not read", dict(capacity=-1, runs=None))]
+        return c
+
+    # ---- morphology: hand-written checks, every line in turn, then every adjacent pair (the first of the two answers) ----
+    q = p + 256                          # the output planes: 32 bytes a plane, clear of the input
+    wide = dict(W=8224, frame_width=8193, W_out=8224, bits_plane_stride=1 << 20, out_plane_stride=1 << 20)      # upscale * frame_width > 8192
+    tall = dict(H=1 << 16, W=8192, frame_width=8192, W_out=8192, bits_plane_stride=1 << 30, out_plane_stride=1 << 30)   # upscale * H * W_out > 2^28
+    bands = dict(B=0x7fffffff, H=65, bits_plane_stride=65, out_bits=None)                                       # two bands a plane under any plan
+    open_v = dict(bits=p, bits_plane_stride=8, B=1, H=H, W=W, frame_width=W, k=3, upscale=1, out_bits=q, out_plane_stride=8, W_out=W,
+                  stats=p, workspace=p)
+    open_cases = (sizes("BHW", False) +
+                  [(f"k={v}", dict(k=v)) for v in (0, 2, 33, -1)] + [(f"upscale={v}", dict(upscale=v)) for v in (0, 3, 8, -1)] +
+                  [("frame_width=0", dict(frame_width=0)), ("frame_width>W", dict(frame_width=W + 1)),
+                   ("nothing to do", dict(out_bits=None, stats=None)), ("W_out<upscale*frame_width", dict(W_out=W - 1)),
+                   ("W_out<upscale*frame_width, upscale 2", dict(upscale=2, W_out=63, out_plane_stride=32)),
+                   ("B=0", dict(B=0)), ("B=0, pointers NULL", dict(B=0, bits=None, out_bits=None, workspace=None)),
+                   ("bits=NULL", dict(bits=None)), ("workspace=NULL with stats", dict(workspace=None)),
+                   ("bits misaligned", dict(bits=p + 2)), ("out_bits misaligned", dict(out_bits=q + 2)), ("stats misaligned", dict(stats=p + 2)),
+                   ("workspace misaligned", dict(workspace=p + 2)),
+                   ("too wide for LDS", dict(wide)), ("too wide for LDS, upscale 2", dict(wide, W=4128, frame_width=4097, upscale=2)),
+                   ("too many pixels", dict(tall)), ("too many rows", dict(H=(1 << 26) + 1, upscale=4, W=1, frame_width=1, W_out=4, bits_plane_stride=1 << 30, out_plane_stride=1 << 30)),
+                   ("short bits stride", dict(bits_plane_stride=7)), ("short out stride", dict(out_plane_stride=7)),
+                   ("short out stride, upscale 4", dict(upscale=4, W_out=128, out_plane_stride=127)),
+                   ("in place", dict(out_bits=p)), ("output inside the input", dict(out_bits=p + 28)), ("input inside the output", dict(bits=q + 28)),
+                   ("too many bands", dict(bands)),
+                   # adjacent pairs, in the order of the entry
+                   ("sizes before k", dict(H=0, k=2)), ("k before upscale", dict(k=2, upscale=3)), ("upscale before frame_width", dict(upscale=3, frame_width=0)),
+                   ("frame_width before nothing to do", dict(frame_width=0, out_bits=None, stats=None)),
+                   ("W_out before B=0", dict(W_out=W - 1, B=0)), ("B=0 before NULL", dict(B=0, bits=None)),
+                   ("NULL before misaligned", dict(bits=None, stats=p + 2)), ("misaligned before too wide", dict(wide, bits=p + 2)),
+                   ("too wide before too many pixels", dict(wide, H=1 << 16)), ("too many pixels before short bits stride", dict(tall, bits_plane_stride=7)),
+                   ("bits stride before out stride", dict(bits_plane_stride=7, out_plane_stride=7)), ("out stride before overlap", dict(out_plane_stride=7, out_bits=p)),
+                   ("overlap before too many bands", dict(bands, out_bits=q, out_plane_stride=65)),
+                   # B = 0 against the rules it ranks behind and in front of
+                   ("k before B=0", dict(k=2, B=0)), ("upscale before B=0", dict(upscale=3, B=0)), ("frame_width before B=0", dict(frame_width=W + 1, B=0)),
+                   ("nothing to do before B=0", dict(out_bits=None, stats=None, B=0)), ("B=0 before misaligned", dict(B=0, bits=p + 2)),
+                   ("B=0 before too wide", dict(wide, B=0)), ("B=0 before short stride", dict(B=0, bits_plane_stride=7)), ("B=0 before overlap", dict(B=0, out_bits=p))])
+    fwide = dict(W=8224)
+    fbands = dict(B=0x7fffffff, H=65)
+    openf_v = dict(bits=p, bits_words=8, bits_offsets=p, frames=p, P=1, H=H, W=W, image_index=p, B=1, k=3, upscale=1, out_bits=q, out_words=8,
+                   out_offsets=p, stats=p, workspace=p)
+    openf_cases = (sizes("BPHW", False) +
+                   [(f"k={v}", dict(k=v)) for v in (0, 2, 33, -1)] + [(f"upscale={v}", dict(upscale=v)) for v in (0, 3, 8, -1)] +
+                   [("nothing to do", dict(out_bits=None, stats=None)), ("bits_words=-1", dict(bits_words=-1)), ("out_words=-1", dict(out_words=-1)),
+                    ("out_words=-1 without out_bits", dict(out_words=-1, out_bits=None, bits=None))] +
+                   ptrs(["bits", "bits_offsets", "frames", "image_index"], {}) +
+                   [("out_offsets=NULL with out_bits", dict(out_offsets=None)), ("workspace=NULL with stats", dict(workspace=None)),
+                    ("bits misaligned", dict(bits=p + 8)), ("out_bits misaligned", dict(out_bits=q + 8)),
+                    ("bits_offsets misaligned", dict(bits_offsets=p + 4)), ("out_offsets misaligned", dict(out_offsets=p + 4)), ("frames misaligned", dict(frames=p + 4)),
+                    ("stats misaligned", dict(stats=p + 2)), ("workspace misaligned", dict(workspace=p + 2)), ("image_index misaligned", dict(image_index=p + 2)),
+                    ("in place", dict(out_bits=p)), ("output inside the input", dict(out_bits=p + 16)), ("input inside the output", dict(bits=q + 16)),
+                    ("a long input buffer holds the output", dict(bits_words=4096)),
+                    ("too wide for LDS", dict(fwide)), ("too wide for LDS, upscale 4", dict(W=2080, upscale=4)),
+                    ("too many pixels", dict(H=(1 << 15) + 1, W=8192)), ("too many rows", dict(H=(1 << 26) + 1, upscale=4, W=32)),
+                    ("too many bands", dict(fbands)),
+                    ("B=0", dict(B=0)), ("B=0, P=0", dict(B=0, P=0)),
+                    ("B=0, pointers NULL", dict(B=0, bits=None, bits_offsets=None, frames=None, image_index=None, out_offsets=None, workspace=None)),
+                    ("B=0, statistics only", dict(B=0, out_bits=None, out_offsets=None)), ("B=0, planes only", dict(B=0, stats=None, workspace=None)),
+                    ("P=0 lets frames be NULL", dict(P=0, frames=None, bits=p + 8)),
+                    # adjacent pairs, in the order of the entry
+                    ("sizes before k", dict(H=0, k=2)), ("k before upscale", dict(k=2, upscale=3)), ("upscale before nothing to do", dict(upscale=3, out_bits=None, stats=None)),
+                    ("nothing to do before words", dict(out_bits=None, stats=None, bits_words=-1)), ("words before NULL", dict(bits_words=-1, bits=None)),
+                    ("NULL before out_offsets", dict(bits=None, out_offsets=None)), ("out_offsets before workspace", dict(out_offsets=None, workspace=None)),
+                    ("workspace before 16-byte rule", dict(workspace=None, bits=p + 8)), ("16-byte rule before 8-byte rule", dict(bits=p + 8, frames=p + 4)),
+                    ("8-byte rule before 4-byte rule", dict(frames=p + 4, stats=p + 2)), ("4-byte rule before overlap", dict(stats=p + 2, out_bits=p)),
+                    ("overlap before too wide", dict(fwide, out_bits=p)), ("too wide before too many pixels", dict(fwide, H=1 << 16)),
+                    ("too many pixels before too many bands", dict(fbands, H=(1 << 15) + 1, W=8192)),
+                    # B = 0: the last rule of all
+                    ("k before B=0", dict(k=2, B=0)), ("nothing to do before B=0", dict(out_bits=None, stats=None, B=0)), ("words before B=0", dict(bits_words=-1, B=0)),
+                    ("B=0 lets pointers be NULL", dict(B=0, bits=None, workspace=None)), ("misaligned before B=0", dict(B=0, image_index=p + 2)),
+                    ("overlap before B=0", dict(B=0, out_bits=p)), ("too wide before B=0", dict(fwide, B=0)), ("too many pixels before B=0", dict(H=(1 << 15) + 1, W=8192, B=0)),
+                    ("side by side, B=0", dict(B=0, out_bits=p + 32))])
     return {
         # (the decode pair lives in the same unit: its one-line checks are pinned along)
         "la3d_rle_decode": (["counts", "offsets", "B", "H", "W", "mask_out"], dict(counts=p, offsets=p, B=1, H=H, W=W, mask_out=p),
@@ -110,6 +257,19 @@ def specs(p):
                                         ptrs(["labels", "frames", "inst_offsets", "inst_label", "bits", "bits_offsets"],
                                              dict(labels=16, bits=4, frames=8, bits_offsets=8, inst_offsets=4, inst_label=4, area=4)) +
                                         [("labels before bits", dict(labels=p + 8, bits=p + 2))] + nothing_p),
+        "la3d_pack_crop_bits": (crop_args + ["B", "H", "W", "W_out", "bits", "bits_plane_stride", "area"], dict(uni, area=p, **crop_v),
+                                crop_src + crop_lds_u + sizes("BHW", True) + ann +
+                                ptrs(["crops", "place", "bits"], dict(bits=4, area=4)) + nothing),
+        "la3d_pack_crop_bits_frames": (crop_args + ["frames", "P", "H", "W", "image_index", "B", "bits", "bits_offsets", "area"],
+                                       dict(frm, image_index=p, **crop_v),
+                                       crop_src + crop_lds + sizes("BPHW", False) + ann_f +
+                                       ptrs(["crops", "place", "frames", "image_index", "bits", "bits_offsets"], ann_fp) + nothing),
+        "la3d_rle_encode_offsets": (ENC_FIELDS, enc_v, enc_cases(False)),
+        "la3d_rle_encode": (ENC_FIELDS, enc_v, enc_cases(True)),
+        "la3d_open_bits": (["bits", "bits_plane_stride", "B", "H", "W", "frame_width", "k", "upscale", "out_bits", "out_plane_stride", "W_out", "stats", "workspace"],
+                           open_v, open_cases),
+        "la3d_open_bits_frames": (["bits", "bits_words", "bits_offsets", "frames", "P", "H", "W", "image_index", "B", "k", "upscale", "out_bits", "out_words",
+                                   "out_offsets", "stats", "workspace"], openf_v, openf_cases),
         "la3d_pack_mask_bits_frames": (["mask"] + mf_args, dict(mf, mask=p), mf_cases + ptrs(["mask"], {}) + [("any byte address holds a u8 mask", dict(mask=p + 1, B=0))]),
         "la3d_pack_logits_bits_frames": (["logits", "dtype", "threshold"] + mf_args, dict(mf, logits=p, dtype=F16, threshold=0.0),
                                          lg_dtype + mf_cases + ptrs(["logits"], dict(logits=2)) +
@@ -126,7 +286,14 @@ def run(lib):
         fn = getattr(lib, entry)
         for name, change in cases:
             a = dict(valid, **change)
-            assert set(change) <= set(order), (entry, name)
-            rc = fn(*[a[k] for k in order], None)
+            if entry in BLOCK_ENTRIES:
+                from labelany3d_amd._lib import RleEncodeArgs
+
+                assert set(change) <= set(order) | {"args"}, (entry, name)
+                block = RleEncodeArgs(**{k: a[k] for k in order})      # (the stream stays NULL)
+                rc = fn(None if "args" in change else C.byref(block))
+            else:
+                assert set(change) <= set(order), (entry, name)
+                rc = fn(*[a[k] for k in order], None)
             out.append([entry, name, rc, lib.la3d_last_error().decode() if rc != 0 else ""])
     return out
