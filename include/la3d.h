@@ -817,6 +817,56 @@ int la3d_open_bits_frames(const uint32_t* bits, int64_t bits_words, const int64_
                           uint32_t* out_bits /* NULL: statistics only */, int64_t out_words, const int64_t* out_offsets /* dev [B] */,
                           int32_t* stats /* dev [B][5] or NULL */, void* workspace, void* stream);
 
+/* ---- connected components on bit planes --------------------------------------------------------------------------------
+ * What tells a mask as it arrives from a mask worth fitting: an occluded COCO instance arrives as several polygon parts, a network
+ * mask with islands far from the object, and the depth + mask fit takes every set pixel.  la3d_open_bits removes by SHAPE (it also
+ * eats thin true structure and leaves any island wider than k alone); this entry removes by COMPONENT - keep the largest part, or drop
+ * the parts under an area - for a batch of planes in one launch, without the unpack / device-to-host copy / scipy.ndimage.label /
+ * np.bincount / pack round trip per instance.
+ * VALUE, per plane (exact integers).  M = the H x frame_width image of a plane of "masks as bit planes"; columns at and beyond
+ *   frame_width and bits past H * W count as zero whatever they hold.  labels, n = scipy.ndimage.label(M, structure): connectivity 8
+ *   is structure = ones((3, 3)), connectivity 4 the cross (SciPy's default).  Components are numbered 1 .. n in raster order of their
+ *   first pixel - that order is part of the contract.  Candidates: the components with area >= min_area.  largest = 0 keeps every
+ *   candidate, largest = 1 only the candidate of greatest area, ties going to the lowest label.  The output plane is the union of
+ *   the kept components, in the input's geometry (H rows, pitch W, frame_width): all la3d_mask_bits_words(H, W) words of it are
+ *   written, pad columns and tail bits zero.
+ * STATISTICS.  stats[b] (i32 [8]) = n_components, n_kept, area_in, area_out, x, y, w, h - the rectangle of the OUTPUT plane as
+ *   cv2.boundingRect gives it for a binary image (the convention la3d_open_bits restates), 0, 0, 0, 0 for an empty output.
+ * TABLE.  components[b][j] (i32 [5]) = area, x, y, w, h of the component with label j + 1, for j < min(n, max_components); the rows
+ *   beyond are zero.  n_components of stats tells a truncated table from a complete one.
+ * CAPACITY.  A RUN is a maximal horizontal span of set pixels within one image row; the call works on runs, never on a label per
+ *   pixel, and max_runs is the caller's bound on the runs of one plane.  A plane with more runs is never labelled wrongly or partly:
+ *   its stats row is -1, runs, 0, 0, 0, 0, 0, 0 with runs the count it needs (call again with that), its output plane is written as
+ *   all zeros, its table rows are zero.  The other planes of the batch are not affected.
+ * workspace: la3d_components_workspace_bytes(B, H, max_runs) = B * (16 * max_runs + 8 * H) bytes (host, no device; 0 for B, H or
+ *   max_runs <= 0), 4-byte aligned: per run its start, its end and two words of the union-find, per row the index of its first run.
+ *   Nothing depends on what it held before.  One kernel, one workgroup per plane, no host synchronisation, no allocation: the call
+ *   can be captured into a HIP graph.  Deterministic: labels are ranks from prefix sums, the only atomics are integer min / max / add.
+ * Refused before any launch, in this order - LA3D_ERR_ARG: a NULL block or a bad struct_size; B < 0, H, W <= 0; frame_width outside
+ *   [0, W]; connectivity not 4 or 8; largest not 0 or 1; min_area < 0; max_runs < 1; max_components < 0; components without
+ *   max_components > 0; out_bits, stats and components all NULL.  LA3D_ERR_UNSUPPORTED: H * W > 1048576 (what the consumers of planes
+ *   take); max_runs > 524288 (a plane of 1048576 pixels has no more runs).  B == 0 then returns 0 with no launch.  With B > 0,
+ *   LA3D_ERR_ARG: mask_bits or workspace NULL; a pointer that is not 4-byte aligned; a stride shorter than a plane; word ranges
+ *   [mask_bits, mask_bits + B * bits_plane_stride) and [out_bits, out_bits + B * out_plane_stride) that overlap (the output is
+ *   gathered from the runs of the input: the call cannot work in place). */
+typedef struct la3d_components_args {
+  int32_t struct_size;                                   /* sizeof(la3d_components_args) of the caller */
+  int32_t B, H, W;
+  int32_t frame_width;                                   /* 0 = W */
+  int32_t connectivity;                                  /* 4 | 8 */
+  int32_t min_area;                                      /* >= 0: components below it are dropped */
+  int32_t largest;                                       /* 0: every candidate | 1: the largest candidate */
+  int32_t max_runs;                                      /* runs one plane may have: 1 .. 524288 */
+  int32_t max_components;                                /* rows of the table per plane */
+  const uint32_t* mask_bits; int64_t bits_plane_stride;  /* bit planes; words between planes, 0 = the words of a plane */
+  uint32_t* out_bits; int64_t out_plane_stride;          /* NULL: statistics only; words between planes, 0 = the words of a plane */
+  int32_t* stats;                                        /* dev [B][8] or NULL */
+  int32_t* components;                                   /* dev [B][max_components][5] or NULL */
+  void* workspace; void* stream;
+} la3d_components_args;
+size_t la3d_components_workspace_bytes(int B, int H, int max_runs);
+int la3d_components_bits(const la3d_components_args* args);
+
 /* ---- mask overlap on bit planes ----------------------------------------------------------------------------------------
  * What relates two planes of one image: for every GROUP g (an image) and every pair of a row i of A_g and a row j of B_g
  *     inter[offsets[g] + i * nb_g + j] = popcount(A_i & B_j)   over the words [0, nwords) of the planes,

@@ -93,6 +93,18 @@ class RleEncodeArgs(C.Structure):
 RLE_OK, RLE_NO_ROOM, RLE_MISMATCH = 0, 1, 2        # status of la3d_rle_encode (5 = BOX_UNSUPPORTED: a refused frames row)
 
 
+class ComponentsArgs(C.Structure):
+    """``la3d_components_args`` of include/la3d.h (argument block of la3d_components_bits, 104 bytes); field order is the header's."""
+    _fields_ = [("struct_size", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("frame_width", C.c_int32), ("connectivity", C.c_int32), ("min_area", C.c_int32), ("largest", C.c_int32),
+                ("max_runs", C.c_int32), ("max_components", C.c_int32),
+                ("mask_bits", C.c_void_p), ("bits_plane_stride", C.c_int64), ("out_bits", C.c_void_p), ("out_plane_stride", C.c_int64),
+                ("stats", C.c_void_p), ("components", C.c_void_p), ("workspace", C.c_void_p), ("stream", C.c_void_p)]
+
+
+COMPONENTS_MAX_RUNS = 524288                       # la3d_components_bits: the largest max_runs (a plane of 2^20 pixels has no more)
+
+
 class OverlapTile(C.Structure):
     """``la3d_overlap_tile`` of include/la3d.h: one row of the tile table of la3d_mask_overlap_plan (64 bytes)."""
     _fields_ = [("g", C.c_int32), ("i0", C.c_int32), ("j0", C.c_int32), ("ni", C.c_int32), ("nj", C.c_int32),
@@ -128,6 +140,8 @@ _SIGS = {
     "la3d_mask_overlap_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "la3d_mask_overlap": (C.c_int, [C.POINTER(MaskOverlapArgs)]),
     "la3d_mask_nms": (C.c_int, [C.POINTER(MaskNmsArgs)]),
+    "la3d_components_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "la3d_components_bits": (C.c_int, [C.POINTER(ComponentsArgs)]),
     "la3d_open_bits_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "la3d_open_bits": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int,
                                  C.c_void_p, C.c_void_p, C.c_void_p]),
