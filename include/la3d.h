@@ -866,6 +866,51 @@ typedef struct la3d_components_args {
 } la3d_components_args;
 size_t la3d_components_workspace_bytes(int B, int H, int max_runs);
 int la3d_components_bits(const la3d_components_args* args);
+/* la3d_components_bits_frames: the same VALUE, STATISTICS, TABLE and CAPACITY rule for the planes of images of DIFFERENT sizes in one
+ * call ("images of different sizes in one call": the la3d_frame table, P rows, and its bounds H, W - the largest rows and the largest
+ * pitch).  One connectivity, min_area, largest, max_runs and max_components per call.
+ * INPUT.  Row n belongs to image image_index[n]; its plane lies at bits + bits_offsets[n] and holds the H_f * W_f / 32 words of that
+ *   image's frame row (H_f rows, pitch W_f - a multiple of 32 -, frame_width fw_f image columns).  Columns at and beyond fw_f count as
+ *   zero whatever the plane holds.  bits_words: the words of the buffer at bits.
+ * OUTPUT.  out_bits (NULL: statistics only): the plane of row n at out_bits + out_offsets[n], in the INPUT's geometry (H_f rows, pitch
+ *   W_f, frame_width fw_f) - out_offsets may be the very pointer given as bits_offsets: the same layout serves a second buffer.  A
+ *   conforming row writes exactly the H_f * W_f / 32 words of its plane - the bits of the padding columns zero - and nothing else.
+ *   The planes must not overlap each other; out_words: the words of the buffer at out_bits.
+ * CONFORMING ROWS get what la3d_components_bits gives for the same plane with H = H_f, W = W_f, frame_width = fw_f: SciPy's
+ *   labelling, labels in raster order of the first pixel, the same statistics and table rows; a row over capacity keeps
+ *   -1, runs, 0, 0, 0, 0, 0, 0, an all-zero output plane and zero table rows.
+ * CHECKED ON THE DEVICE, per row, every value wave-uniform and before an address is formed from it, in this order: image_index[n]
+ *   inside [0, P); the frame row against the la3d_frame contract and the bounds (the check of the fit); bits_offsets[n] >= 0 and a
+ *   multiple of 4; out_offsets[n] likewise (with out_bits); then that the planes end inside their buffers: bits_offsets[n] + words
+ *   <= bits_words and out_offsets[n] + words <= out_words.  A refused row reads no plane word, writes no plane word and gets the
+ *   statistics row -2, 0, 0, 0, 0, 0, 0, 0 and zero table rows (both addressed by n alone): -2 tells it from a row over capacity
+ *   (-1, runs, ...) and from an empty plane (0, 0, ...).  The other rows of the call are not affected by either.
+ * workspace: la3d_components_workspace_bytes(B, H, max_runs) bytes with H the bound - the sizing call of la3d_components_bits serves
+ *   both forms -, 4-byte aligned: one segment per row, sized by the bound.  Nothing depends on what it held before.  The dynamic LDS
+ *   is 4 * max_runs bytes up to 32768 runs, as in the uniform form.  One kernel, one workgroup per row, no host synchronisation, no
+ *   allocation, no atomics beyond integer min / max / add: the call can be captured into a HIP graph.
+ * Refused before any launch, for B == 0 too, in this order - LA3D_ERR_ARG: a NULL block or a bad struct_size; B, P < 0, bounds H, W
+ *   <= 0; connectivity not 4 or 8; largest not 0 or 1; min_area < 0; max_runs < 1; max_components < 0; components without
+ *   max_components > 0; out_bits, stats and components all NULL; nonzero reserved; bits_words < 0, out_words < 0 with out_bits; bits or
+ *   out_bits not 16-byte aligned; bits_offsets, out_offsets or frames not 8-byte aligned; stats, components, workspace or image_index
+ *   not 4-byte aligned; the word ranges [bits, bits + bits_words) and [out_bits, out_bits + out_words) overlapping (the output is
+ *   gathered from the runs of the input: the call cannot work in place); and with B > 0: bits, bits_offsets, image_index, workspace or
+ *   - with P > 0 - frames NULL, out_offsets NULL with out_bits.  LA3D_ERR_UNSUPPORTED: bounds with H * roundup32(W) > 1048576;
+ *   max_runs > 524288.  B == 0 then returns 0 with nothing launched.  P == 0 with B > 0: every row is refused on the device (-2 rows). */
+typedef struct la3d_components_frames_args {
+  int32_t struct_size;                                   /* sizeof(la3d_components_frames_args) of the caller */
+  int32_t B, P;
+  int32_t H, W;                                          /* bounds of the table */
+  int32_t connectivity, min_area, largest, max_runs, max_components;   /* as in la3d_components_args */
+  int32_t reserved[2];                                   /* 0 */
+  const uint32_t* bits; int64_t bits_words; const int64_t* bits_offsets;      /* the buffer, its words, dev [B] */
+  const la3d_frame* frames; const int32_t* image_index;                        /* dev [P], dev [B] */
+  uint32_t* out_bits; int64_t out_words; const int64_t* out_offsets;          /* NULL: statistics only; dev [B] */
+  int32_t* stats;                                        /* dev [B][8] or NULL */
+  int32_t* components;                                   /* dev [B][max_components][5] or NULL */
+  void* workspace; void* stream;
+} la3d_components_frames_args;
+int la3d_components_bits_frames(const la3d_components_frames_args* args);
 
 /* ---- mask overlap on bit planes ----------------------------------------------------------------------------------------
  * What relates two planes of one image: for every GROUP g (an image) and every pair of a row i of A_g and a row j of B_g

@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 # (la3d_bits.hip: the packers of bit planes, the unpacker, the plane statistics and the annotation decoders)
 # (la3d_rle_encode.hip: bit planes -> COCO run lengths, kernels and C entries in one unit)
 # (la3d_open.hip: binary opening on bit planes, uniform and frames form, kernels and C entries in one unit)
-# (la3d_components.hip: connected components on bit planes - largest part, island removal -, kernel and C entry in one unit)
+# (la3d_components.hip: connected components on bit planes - largest part, island removal -, uniform and frames form, kernel and C entries in one unit)
 # (la3d_bitplanes.hpp: what those three share - BitsOut, the frames prologue, pack_check - and the refusal helper la3d_overlap.hip takes too)
 # (la3d_align.hip: the batched RANSAC scale fit of the depth alignment, kernels and C entries in one unit)
 # (la3d_overlap.hip: pairwise mask overlap on bit planes and the mask NMS that reads it, kernels and C entries in one unit)

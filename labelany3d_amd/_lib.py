@@ -102,7 +102,19 @@ class ComponentsArgs(C.Structure):
                 ("stats", C.c_void_p), ("components", C.c_void_p), ("workspace", C.c_void_p), ("stream", C.c_void_p)]
 
 
-COMPONENTS_MAX_RUNS = 524288                       # la3d_components_bits: the largest max_runs (a plane of 2^20 pixels has no more)
+class ComponentsFramesArgs(C.Structure):
+    """``la3d_components_frames_args`` of include/la3d.h (argument block of la3d_components_bits_frames, 144 bytes); field order is
+    the header's."""
+    _fields_ = [("struct_size", C.c_int32), ("B", C.c_int32), ("P", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("connectivity", C.c_int32), ("min_area", C.c_int32), ("largest", C.c_int32), ("max_runs", C.c_int32),
+                ("max_components", C.c_int32), ("reserved", C.c_int32 * 2),
+                ("bits", C.c_void_p), ("bits_words", C.c_int64), ("bits_offsets", C.c_void_p),
+                ("frames", C.c_void_p), ("image_index", C.c_void_p),
+                ("out_bits", C.c_void_p), ("out_words", C.c_int64), ("out_offsets", C.c_void_p),
+                ("stats", C.c_void_p), ("components", C.c_void_p), ("workspace", C.c_void_p), ("stream", C.c_void_p)]
+
+
+COMPONENTS_MAX_RUNS = 524288                      # la3d_components_bits: the largest max_runs (a plane of 2^20 pixels has no more)
 
 
 class OverlapTile(C.Structure):
@@ -142,6 +154,7 @@ _SIGS = {
     "la3d_mask_nms": (C.c_int, [C.POINTER(MaskNmsArgs)]),
     "la3d_components_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "la3d_components_bits": (C.c_int, [C.POINTER(ComponentsArgs)]),
+    "la3d_components_bits_frames": (C.c_int, [C.POINTER(ComponentsFramesArgs)]),
     "la3d_open_bits_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "la3d_open_bits": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int,
                                  C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1,5 +1,6 @@
 // la3d_bitplanes.hpp - what the units that read or write bit planes share (la3d_bits.hip: decoders, packers, unpacker, statistics;
-// la3d_rle_encode.hip: the run-length encoder; la3d_open.hip: the opening; la3d_overlap.hip: the refusal helpers only).
+// la3d_rle_encode.hip: the run-length encoder; la3d_open.hip: the opening; la3d_components.hip: connected components, whose frames
+// form takes the prologue; la3d_overlap.hip: the refusal helpers only).
 // Device side: where the planes of a call lie (BitsOut), the geometry of one of them (plane_geometry) and the prologue of a frames
 // workgroup (frames_prologue).  Host side: how an entry describes its planes (bits_out_uniform / bits_out_frames), how it refuses
 // (pack_refuse) and the ONE argument check of the packer entries (pack_check), with the wording more than one unit uses.

@@ -1,5 +1,6 @@
 // la3d_components.hip - connected components on bit planes (include/la3d.h "connected components on bit planes"):
-// la3d_components_bits, kernels and C entry in one unit.  From la3d_bitplanes.hpp come pack_refuse and at().
+// la3d_components_bits and its frames form, la3d_components_bits_frames: kernels and C entries in one unit.  From la3d_bitplanes.hpp
+// come the frames prologue of a workgroup, pack_refuse, at() and the wording shared with the packers.
 #include <cstdint>
 #include <cstddef>
 
@@ -33,6 +34,10 @@ namespace {
 // dependent loads: the waves hide one another's) of 106 VGPRs - 4 waves per SIMD -, so a CU holds ONE workgroup whatever max_runs is;
 // its LDS (4 * max_runs bytes: 64 KiB at the default 16384, 128 KiB at 32768, none beyond) never is what limits it.  Measured
 // (profiles/components/RESULTS.md): two workgroups of 8 waves and 57 VGPRs per CU were slower at every batch size.
+// FRAMES (la3d_components_bits_frames, images of different sizes): the same passes on a geometry formed per workgroup from the la3d_frame
+// row of its plane (comp_plane, all of it wave-uniform: SGPRs).  H, W of the call are then the bounds of the table: they size the
+// segment of the workspace (rs has the bound's rows), a plane uses its own rows of it.  A row the device refuses gets -2 in its
+// statistics, zero table rows, and neither reads nor writes a plane word.
 constexpr int COMP_NT = 1024;
 constexpr int COMP_NW = COMP_NT / 64;
 constexpr int COMP_LDS_RUNS = 32768;      // parent in LDS up to here
@@ -41,15 +46,49 @@ constexpr int COMP_MAX_RUNS = 524288;     // a plane of 2^20 pixels has no more
 struct CompArgs {
   const unsigned* bits; long long stride;
   unsigned* out; long long out_stride;
-  int H, W, fw, nw;                        // rows, pitch, image columns, aligned words per image row
+  int H, W, fw, nw;                        // rows, pitch, image columns, aligned words per image row (frames form: H, W are the bounds)
   int nwords;                              // words of a plane
   int conn8, min_area, largest, max_runs, maxc;
   int* stats; int* comps;
   int* ws; long long ws_stride;            // ints per plane: 4 * max_runs + 2 * H
 };
+// frames form, beside a CompArgs whose fields that speak of ONE plane (stride, out_stride, fw, nw, nwords) are unused: those are formed
+// per workgroup (comp_plane).  A kernel argument of its own: the uniform instantiation never reads it, and its CompArgs is the block
+// it always had.
+struct CompFrames {
+  const long long* offsets; const long long* out_offsets;   // [B] words from bits / out to the plane of each row
+  const la3d_frame* frames; const int* image_index; int P;
+  long long bits_words, out_words;         // words of the two buffers: a plane that does not end inside its buffer is refused
+};
+// what a workgroup works on: the geometry of its plane, where it is read and where the result goes (NULL: statistics only)
+struct CompPlane { int H, W, fw, nw, nwords; const unsigned* plane; unsigned* op; };
+
+// The plane of workgroup b.  Uniform form: the argument block's own geometry, planes a stride apart.  Frames form: formed here from the
+// la3d_frame row of image_index[b] - every value wave-uniform, through scalar loads, checked before an address is formed from it, in
+// the order of frames_prologue (image index, frame row, input offset), then the output offset (the same rule), then that either plane
+// ends inside its buffer.  The output has the input's geometry.  false: refused - nothing is read, nothing is written through it.
+template <bool FRAMES>
+__device__ inline bool comp_plane(const CompArgs& a, const CompFrames& fr, int b, CompPlane* g) {
+  if constexpr (FRAMES) {
+    FramesWork f;
+    if (!frames_prologue<true, false>(fr.frames, fr.P, fr.image_index, a.H, a.W, const_cast<unsigned*>(a.bits), fr.offsets, b, 0, &f)) return false;
+    long long oo = 0;
+    if (a.out && !frames_plane_at(fr.out_offsets, b, &oo)) return false;
+    if (f.off > fr.bits_words - f.nwords) return false;
+    if (a.out && oo > fr.out_words - f.nwords) return false;
+    g->H = f.r.H; g->W = f.r.W; g->fw = f.r.fw; g->nw = (f.r.fw + 31) >> 5; g->nwords = f.nwords;
+    g->plane = a.bits + f.off;               // (formed only now: after the last check)
+    g->op = a.out ? a.out + oo : nullptr;
+  } else {
+    g->H = a.H; g->W = a.W; g->fw = a.fw; g->nw = a.nw; g->nwords = a.nwords;
+    g->plane = a.bits + (long long)b * a.stride;
+    g->op = a.out ? a.out + (long long)b * a.out_stride : nullptr;
+  }
+  return true;
+}
 
 // word wc of image row v, aligned to the row's first column; columns at and beyond fw are zero whatever the plane holds
-__device__ inline unsigned comp_row_word(const CompArgs& a, const unsigned* __restrict__ plane, int v, int wc) {
+__device__ inline unsigned comp_row_word(const CompPlane& a, const unsigned* __restrict__ plane, int v, int wc) {
   const long long i = (long long)v * a.W + wc * 32;
   const int w = (int)(i >> 5);
   const unsigned sh = (unsigned)(i & 31);
@@ -63,7 +102,7 @@ __device__ inline unsigned comp_row_word(const CompArgs& a, const unsigned* __re
 // item `it` = (row v, word wc): its word, carry = the pixel left of the word, next = the pixel right of it (both 0 outside the row's
 // image columns).  Neighbouring lanes take neighbouring items: the loads of a wave fall into a few lines.
 struct CompItem { int v, wc; unsigned x, carry, next; };
-__device__ inline CompItem comp_item(const CompArgs& a, const unsigned* __restrict__ plane, int it) {
+__device__ inline CompItem comp_item(const CompPlane& a, const unsigned* __restrict__ plane, int it) {
   CompItem i;
   i.v = it / a.nw; i.wc = it - i.v * a.nw;
   i.x = comp_row_word(a, plane, i.v, i.wc);
@@ -129,37 +168,44 @@ __device__ inline void comp_unite(int* parent, int a, int b) {
   }
 }
 
-template <bool COMP_LDS>
-__global__ __launch_bounds__(COMP_NT) void components_kernel(const CompArgs a) {
+template <bool COMP_LDS, bool FRAMES>
+__global__ __launch_bounds__(COMP_NT) void components_kernel(const CompArgs a, const CompFrames fr) {
   extern __shared__ __attribute__((aligned(16))) int comp_smem[];
   __shared__ int red[COMP_NW + 1];
   const int tid = threadIdx.x, b = blockIdx.x;
-  const unsigned* plane = a.bits + (long long)b * a.stride;
-  unsigned* op = a.out ? a.out + (long long)b * a.out_stride : nullptr;
+  CompPlane g;
+  const bool conforming = comp_plane<FRAMES>(a, fr, b, &g);
   int* stats = a.stats ? a.stats + (long long)b * 8 : nullptr;
   int* table = a.comps ? a.comps + (long long)b * a.maxc * 5 : nullptr;
+  if (!conforming) {                       // (uniform, before any barrier) refused: the rows addressed by b alone say so
+    if (stats && tid < 8) stats[tid] = tid == 0 ? -2 : 0;
+    if (table) for (int j = tid; j < a.maxc * 5; j += COMP_NT) table[j] = 0;
+    return;
+  }
+  const unsigned* plane = g.plane;
+  unsigned* op = g.op;
   int* seg = a.ws + (long long)b * a.ws_stride;
   int* px = seg;                           // v * fw + x0 of run i
   int* xe = seg + a.max_runs;              // x1 of run i
   int* parent = COMP_LDS ? comp_smem : seg + 2 * (long long)a.max_runs;
   int* area = seg + (COMP_LDS ? 2 : 3) * (long long)a.max_runs;   // area of a root; after the choice its tag
   int* rs = seg + 4 * (long long)a.max_runs;                       // [H + 1]
-  const int fw = a.fw;
+  const int fw = g.fw;
 
   // 1  count
   // wave w owns the items [w0, w1), a contiguous range, and takes them 64 at a time, lane by lane
-  const int items = a.H * a.nw, lane = tid & 63;
+  const int items = g.H * g.nw, lane = tid & 63;
   const int ipw = ((items + COMP_NW - 1) / COMP_NW + 63) & ~63;
   const int w0 = min(items, (tid >> 6) * ipw), w1 = min(items, w0 + ipw);
   int mine = 0;
   for (int it = w0 + lane; it < w1; it += 64) {
-    const CompItem i = comp_item(a, plane, it);
+    const CompItem i = comp_item(g, plane, it);
     mine += __popc(i.x & ~((i.x << 1) | i.carry));
   }
   int runs;
   const int base = comp_scan(mine, red, &runs);   // (of lane 0: the runs before the wave's first item)
   if (runs > a.max_runs) {                 // (uniform) refused: nothing was indexed by a run
-    if (op) for (int j = tid; j < a.nwords; j += COMP_NT) op[j] = 0u;
+    if (op) for (int j = tid; j < g.nwords; j += COMP_NT) op[j] = 0u;
     if (stats && tid < 8) stats[tid] = tid == 0 ? -1 : tid == 1 ? runs : 0;
     if (table) for (int j = tid; j < a.maxc * 5; j += COMP_NT) table[j] = 0;
     return;
@@ -172,7 +218,7 @@ __global__ __launch_bounds__(COMP_NT) void components_kernel(const CompArgs a) {
       unsigned starts = 0u, ends = 0u;
       CompItem i = {};
       if (it < w1) {
-        i = comp_item(a, plane, it);
+        i = comp_item(g, plane, it);
         starts = i.x & ~((i.x << 1) | i.carry); ends = i.x & ~((i.x >> 1) | (i.next << 31));
       }
       const int cnt = __popc(starts), incl = comp_wave_scan(cnt);
@@ -192,7 +238,7 @@ __global__ __launch_bounds__(COMP_NT) void components_kernel(const CompArgs a) {
         xe[ei++] = i.wc * 32 + q;
       }
     }
-    if (tid == 0) rs[a.H] = runs;
+    if (tid == 0) rs[g.H] = runs;
   }
   __syncthreads();
   // 3  join
@@ -274,13 +320,13 @@ __global__ __launch_bounds__(COMP_NT) void components_kernel(const CompArgs a) {
     }
   }
   if (op) {
-    for (int j = tid; j < a.nwords; j += COMP_NT) {
+    for (int j = tid; j < g.nwords; j += COMP_NT) {
       unsigned x = 0u;
-      int g = j * 32, filled = 0;                          // g: the pixel index at which the next piece begins (< 2^20 + 32)
+      int gi = j * 32, filled = 0;                          // gi: the pixel index at which the next piece begins (< 2^20 + 32)
       while (filled < 32) {
-        const int v = g / a.W, col = g - v * a.W;
-        if (v >= a.H) break;                               // past the plane's last row: the tail bits stay zero
-        const int nb = min(32 - filled, a.W - col);         // bits of row v in this word: columns [col, col + nb)
+        const int v = gi / g.W, col = gi - v * g.W;
+        if (v >= g.H) break;                               // past the plane's last row: the tail bits stay zero
+        const int nb = min(32 - filled, g.W - col);         // bits of row v in this word: columns [col, col + nb)
         if (col < fw) {
           const int e = rs[v + 1], above = v * fw;
           int l = rs[v], r = e;                            // the first run of row v that ends at or beyond col
@@ -297,7 +343,7 @@ __global__ __launch_bounds__(COMP_NT) void components_kernel(const CompArgs a) {
             x |= span << filled;
           }
         }
-        filled += nb; g += nb;
+        filled += nb; gi += nb;
       }
       op[j] = x;
     }
@@ -368,10 +414,62 @@ int la3d_components_bits(const la3d_components_args* args) {
   a.ws = static_cast<int*>(g.workspace); a.ws_stride = 4 * (long long)g.max_runs + 2 * (long long)g.H;
   hipStream_t st = static_cast<hipStream_t>(g.stream);
   if (g.max_runs <= COMP_LDS_RUNS) {
-    allow_big_lds(reinterpret_cast<const void*>(components_kernel<true>));
-    hipLaunchKernelGGL(components_kernel<true>, dim3((unsigned)g.B), dim3(COMP_NT), (size_t)g.max_runs * sizeof(int), st, a);
+    allow_big_lds(reinterpret_cast<const void*>(components_kernel<true, false>));
+    hipLaunchKernelGGL((components_kernel<true, false>), dim3((unsigned)g.B), dim3(COMP_NT), (size_t)g.max_runs * sizeof(int), st, a, CompFrames{});
   } else {
-    hipLaunchKernelGGL(components_kernel<false>, dim3((unsigned)g.B), dim3(COMP_NT), 0, st, a);
+    hipLaunchKernelGGL((components_kernel<false, false>), dim3((unsigned)g.B), dim3(COMP_NT), 0, st, a, CompFrames{});
+  }
+  return check_launch("components_kernel");
+}
+
+int la3d_components_bits_frames(const la3d_components_frames_args* args) {
+  const char* who = "la3d_components_bits_frames";
+  if (!args || args->struct_size != (int32_t)sizeof(la3d_components_frames_args)) return pack_refuse(who, "NULL block or bad struct_size");
+  const la3d_components_frames_args& g = *args;
+  if (g.B < 0 || g.P < 0 || g.H <= 0 || g.W <= 0) return pack_refuse(who, SIZES_FRAMES);
+  if (g.connectivity != 4 && g.connectivity != 8) return pack_refuse(who, "connectivity must be 4 or 8");
+  if (g.largest != 0 && g.largest != 1) return pack_refuse(who, "largest must be 0 or 1");
+  if (g.min_area < 0) return pack_refuse(who, "min_area must not be negative");
+  if (g.max_runs < 1) return pack_refuse(who, "max_runs must be at least 1");
+  if (g.max_components < 0) return pack_refuse(who, "max_components must not be negative");
+  if (g.components && g.max_components == 0) return pack_refuse(who, "components needs max_components > 0");
+  if (!g.out_bits && !g.stats && !g.components) return pack_refuse(who, "nothing to do: out_bits, stats and components are all NULL");
+  if (g.reserved[0] != 0 || g.reserved[1] != 0) return pack_refuse(who, "reserved must be 0");
+  if (g.bits_words < 0 || (g.out_bits && g.out_words < 0)) return pack_refuse(who, "bits_words and out_words must not be negative");
+  if ((at(g.bits) | at(g.out_bits)) & 15) return pack_refuse(who, "bits or out_bits not a 16-byte aligned pointer");
+  if ((at(g.bits_offsets) | at(g.out_offsets) | at(g.frames)) & 7) return pack_refuse(who, "bits_offsets, out_offsets or frames not an 8-byte aligned pointer");
+  if ((at(g.stats) | at(g.components) | at(g.workspace) | at(g.image_index)) & 3)
+    return pack_refuse(who, "stats, components, workspace or image_index not a 4-byte aligned pointer");
+  if (g.bits && g.out_bits) {   // a word of the output is gathered from runs listed before: the call does not work in place
+    const uintptr_t i0 = at(g.bits), i1 = i0 + (uintptr_t)g.bits_words * 4, o0 = at(g.out_bits), o1 = o0 + (uintptr_t)g.out_words * 4;
+    if (i0 < o1 && o0 < i1) return pack_refuse(who, "the input buffer and the output buffer overlap");
+  }
+  if (g.B > 0) {
+    if (!g.bits || !g.bits_offsets || !g.image_index || !g.workspace || (!g.frames && g.P > 0))
+      return pack_refuse(who, "NULL bits, bits_offsets, image_index, workspace or frames");
+    if (g.out_bits && !g.out_offsets) return pack_refuse(who, "out_offsets must not be NULL with out_bits");
+  }
+  if (bounds_words(g.H, g.W) * 32 > 1048576)
+    return pack_refuse(who, "the bounds' H * roundup32(W) must not exceed 1048576", LA3D_ERR_UNSUPPORTED);
+  if (g.max_runs > COMP_MAX_RUNS) return pack_refuse(who, "max_runs must not exceed 524288 (a plane of 1048576 pixels has no more)", LA3D_ERR_UNSUPPORTED);
+  if (g.B == 0) return LA3D_SUCCESS;
+  CompArgs a = {};
+  a.bits = g.bits; a.out = g.out_bits;
+  a.H = g.H; a.W = g.W;                      // the bounds: every other word of a plane's geometry is formed per workgroup
+  a.conn8 = g.connectivity == 8; a.min_area = g.min_area; a.largest = g.largest; a.max_runs = g.max_runs;
+  a.maxc = g.components ? g.max_components : 0;
+  a.stats = g.stats; a.comps = g.components;
+  a.ws = static_cast<int*>(g.workspace); a.ws_stride = 4 * (long long)g.max_runs + 2 * (long long)g.H;
+  CompFrames fr = {};
+  fr.offsets = reinterpret_cast<const long long*>(g.bits_offsets); fr.out_offsets = reinterpret_cast<const long long*>(g.out_offsets);
+  fr.frames = g.frames; fr.image_index = g.image_index; fr.P = g.P;   // (P == 0: every row is refused before a frame row is addressed)
+  fr.bits_words = g.bits_words; fr.out_words = g.out_bits ? g.out_words : 0;
+  hipStream_t st = static_cast<hipStream_t>(g.stream);
+  if (g.max_runs <= COMP_LDS_RUNS) {
+    allow_big_lds(reinterpret_cast<const void*>(components_kernel<true, true>));
+    hipLaunchKernelGGL((components_kernel<true, true>), dim3((unsigned)g.B), dim3(COMP_NT), (size_t)g.max_runs * sizeof(int), st, a, fr);
+  } else {
+    hipLaunchKernelGGL((components_kernel<false, true>), dim3((unsigned)g.B), dim3(COMP_NT), 0, st, a, fr);
   }
   return check_launch("components_kernel");
 }
