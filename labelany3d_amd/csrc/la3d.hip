@@ -165,8 +165,7 @@ static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 // The workspace of ONE call: la3d_workspace_bytes(B,H,W) for a PCA call; a convex-hull call adds its hand-off area behind that,
 // 256-aligned - per instance the larger of the two modes' slots (hull_stride_bytes), so the size does not depend on sample_idx
 size_t la3d_fit_workspace_bytes(const la3d_fit_args* args) {
-  constexpr int32_t V1_SIZE = (int32_t)offsetof(la3d_fit_args, area_hint);
-  if (!args || args->struct_size < V1_SIZE || args->B <= 0) return 0;
+  if (!fit_args_size_ok(args) || args->B <= 0) return 0;
   const size_t base = la3d_workspace_bytes(args->B, args->H, args->W);
   const bool has_method = (size_t)args->struct_size >= offsetof(la3d_fit_args, method) + sizeof(int32_t);
   if (!has_method || args->method != LA3D_METHOD_CONVEX_HULL) return base;
@@ -180,7 +179,7 @@ struct FramesSource { const la3d_frame* rows; int32_t P; };                     
 struct Depth16Source { const la3d_depth16* d; };                                      // la3d_fit_instances_depth16's own argument (checked there)
 
 // Every fit entry ends here with its arguments in one block.  filter_on: the fused instance filter runs (the *_filtered entries
-// always; la3d_fit_instances_ex when filter_boundary >= 0 and filter_max_edge > 0).  who: the entry named in la3d_last_error().
+// always; the entries that take a block when block_filter_on says so).  who: the entry named in la3d_last_error().
 // bs: the bit planes of la3d_fit_instances_bits (an internal parameter: the public block is frozen), null for every other entry.
 // fr: the frame table of la3d_fit_instances_frames (H, W of the block are then bounds), null for every other entry.
 // ds: the 16-bit depth planes of la3d_fit_instances_depth16 (a.depth is then null), null for every other entry but
@@ -200,20 +199,13 @@ static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who,
   const bool rle = a.rle_counts != nullptr || a.poly_xy != nullptr || bs != nullptr;   // "no u8 plane": the mask is decoded into the LDS bit image
   if ((!a.depth && !ds) || (!a.mask && !rle) || (a.rle_counts && !a.rle_offsets) || (a.poly_xy && (!a.ring_offsets || !a.inst_rings)) ||
       !a.K || !a.out || !a.status || B < 0 || H <= 0 || W <= 0 ||
-      a.depth_plane_stride < 0 || (a.k_stride != 0 && a.k_stride < 9) || (long long)H * W > (1LL << 28)) {
-    snprintf(g_err, sizeof(g_err), "%s: bad argument", who);
-    return LA3D_ERR_ARG;
-  }
-  if (a.method != LA3D_METHOD_PCA && a.method != LA3D_METHOD_CONVEX_HULL) {
-    snprintf(g_err, sizeof(g_err), "%s: unknown method (LA3D_METHOD_PCA or LA3D_METHOD_CONVEX_HULL)", who);
-    return LA3D_ERR_ARG;
-  }
+      a.depth_plane_stride < 0 || (a.k_stride != 0 && a.k_stride < 9) || (long long)H * W > (1LL << 28))
+    return refuse(who, "bad argument");
+  if (a.method != LA3D_METHOD_PCA && a.method != LA3D_METHOD_CONVEX_HULL) return refuse(who, "unknown method (LA3D_METHOD_PCA or LA3D_METHOD_CONVEX_HULL)");
   if (B == 0) return LA3D_SUCCESS;
-  if (!a.workspace || (reinterpret_cast<uintptr_t>(a.workspace) & 7)) {
-    if (a.method == LA3D_METHOD_CONVEX_HULL) snprintf(g_err, sizeof(g_err), "%s: a convex-hull call needs a workspace of la3d_fit_workspace_bytes() bytes (8-aligned)", who);
-    else snprintf(g_err, sizeof(g_err), "%s: workspace of la3d_workspace_bytes() bytes (8-aligned) required", who);
-    return LA3D_ERR_ARG;
-  }
+  if (!a.workspace || (reinterpret_cast<uintptr_t>(a.workspace) & 7))
+    return refuse(who, a.method == LA3D_METHOD_CONVEX_HULL ? "a convex-hull call needs a workspace of la3d_fit_workspace_bytes() bytes (8-aligned)"
+                                                           : "workspace of la3d_workspace_bytes() bytes (8-aligned) required");
   FitParams p;   // (every other field keeps its default: see FitParams)
   p.geo = static_cast<double*>(a.workspace);
   p.depth = a.depth; p.depth_plane_stride = ds ? ds->d->plane_stride : a.depth_plane_stride; p.image_index = a.image_index;
@@ -246,18 +238,13 @@ static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who,
   if (fr) { p.frames = fr->rows; p.frames_P = fr->P; p.frames_max_h = a.H; p.frames_max_w = a.W; }
   if (a.frame_width != 0 && a.frame_width != W) {
     // rows padded on the right (la3d_fit_args::frame_width): run-length / polygon masks, word-aligned rows
-    if (a.frame_width < 0 || a.frame_width > W || a.mask != nullptr || W % 32 != 0) {
-      snprintf(g_err, sizeof(g_err), bs ? "%s: frame_width must be 0 or in (0, W], with W %% 32 == 0"
-                                        : "%s: frame_width must be 0 or in (0, W], with run-length / polygon masks and W %% 32 == 0", who);
-      return LA3D_ERR_ARG;
-    }
+    if (a.frame_width < 0 || a.frame_width > W || a.mask != nullptr || W % 32 != 0)
+      return refuse(who, bs ? "frame_width must be 0 or in (0, W], with W % 32 == 0"
+                            : "frame_width must be 0 or in (0, W], with run-length / polygon masks and W % 32 == 0");
     p.frame_w = a.frame_width;
   }
   if (filter_on) {
-    if (!rle || a.filter_boundary < 0) {
-      snprintf(g_err, sizeof(g_err), "%s: the fused filter needs run-length or polygon masks and boundary >= 0", who);
-      return LA3D_ERR_ARG;
-    }
+    if (!rle || a.filter_boundary < 0) return refuse(who, "the fused filter needs run-length or polygon masks and boundary >= 0");
     p.filter_boundary = a.filter_boundary; p.filter_min_area = a.filter_min_area; p.filter_max_edge = a.filter_max_edge;
     p.filter_stats = a.stats;
   }
@@ -265,11 +252,8 @@ static int fit_dispatch(const la3d_fit_args& a, bool filter_on, const char* who,
   CallFacts f;
   f.ldsmask = bit_bytes <= MAX_MASK_LDS;
   p.mask_lds_bytes = f.ldsmask ? bit_bytes : 0;
-  if (rle && !f.ldsmask) {
-    snprintf(g_err, sizeof(g_err), bs ? "%s: bit-plane masks need the bit image in LDS (H*W <= 1048576)"
-                                      : "%s: run-length / polygon masks need the bit image in LDS (H*W <= 1048576)", who);
-    return LA3D_ERR_UNSUPPORTED;
-  }
+  if (rle && !f.ldsmask) return refuse(who, bs ? "bit-plane masks need the bit image in LDS (H*W <= 1048576)"
+                          : "run-length / polygon masks need the bit image in LDS (H*W <= 1048576)", LA3D_ERR_UNSUPPORTED);
   // 16-byte vector path: every plane base 16-aligned (the u8 mask only when it is read at all)
   // (16-bit planes: a lane's quad is 8 bytes - base 8-aligned, stride a multiple of four elements)
   f.vec = (p.HW % 16 == 0) && (rle || (reinterpret_cast<uintptr_t>(a.mask) & 15) == 0) &&
@@ -350,10 +334,7 @@ int la3d_fit_instances_rle(const float* depth, int64_t depth_plane_stride, const
                            const int32_t* rle_counts, const int64_t* rle_offsets, const double* K, int32_t k_stride,
                            const double* ground, const int32_t* sample_idx, int B, int H, int W, double* out,
                            int32_t* status, double* aux, void* workspace, void* stream) {
-  if (!rle_counts && B > 0) {
-    set_err("la3d_fit_instances_rle: bad argument");
-    return LA3D_ERR_ARG;
-  }
+  if (!rle_counts && B > 0) return refuse("la3d_fit_instances_rle", "bad argument");
   la3d_fit_args a = legacy_args(depth, depth_plane_stride, image_index, K, k_stride, ground, sample_idx, B, H, W, out, status, aux,
                                 workspace, stream);
   a.rle_counts = rle_counts; a.rle_offsets = rle_offsets;
@@ -364,10 +345,7 @@ int la3d_fit_instances_poly(const float* depth, int64_t depth_plane_stride, cons
                             const int32_t* poly_xy, const int64_t* ring_offsets, const int64_t* inst_rings, const double* K,
                             int32_t k_stride, const double* ground, const int32_t* sample_idx, int B, int H, int W, double* out,
                             int32_t* status, double* aux, void* workspace, void* stream) {
-  if ((!poly_xy || !ring_offsets || !inst_rings) && B > 0) {
-    set_err("la3d_fit_instances_poly: bad argument");
-    return LA3D_ERR_ARG;
-  }
+  if ((!poly_xy || !ring_offsets || !inst_rings) && B > 0) return refuse("la3d_fit_instances_poly", "bad argument");
   la3d_fit_args a = legacy_args(depth, depth_plane_stride, image_index, K, k_stride, ground, sample_idx, B, H, W, out, status, aux,
                                 workspace, stream);
   legacy_poly(a, poly_xy, ring_offsets, inst_rings);
@@ -380,10 +358,7 @@ int la3d_fit_instances_rle_filtered(const float* depth, int64_t depth_plane_stri
                                     const double* ground, const int32_t* sample_idx, int B, int H, int W, int boundary,
                                     int min_area, int max_edge, double* out, int32_t* status, double* aux, int32_t* stats,
                                     void* workspace, void* stream) {
-  if (!rle_counts && B > 0) {
-    set_err("la3d_fit_instances_rle_filtered: bad argument");
-    return LA3D_ERR_ARG;
-  }
+  if (!rle_counts && B > 0) return refuse("la3d_fit_instances_rle_filtered", "bad argument");
   la3d_fit_args a = legacy_args(depth, depth_plane_stride, image_index, K, k_stride, ground, sample_idx, B, H, W, out, status, aux,
                                 workspace, stream);
   a.rle_counts = rle_counts; a.rle_offsets = rle_offsets;
@@ -396,10 +371,7 @@ int la3d_fit_instances_poly_filtered(const float* depth, int64_t depth_plane_str
                                      const double* K, int32_t k_stride, const double* ground, const int32_t* sample_idx, int B,
                                      int H, int W, int boundary, int min_area, int max_edge, double* out, int32_t* status,
                                      double* aux, int32_t* stats, void* workspace, void* stream) {
-  if ((!poly_xy || !ring_offsets || !inst_rings) && B > 0) {
-    set_err("la3d_fit_instances_poly_filtered: bad argument");
-    return LA3D_ERR_ARG;
-  }
+  if ((!poly_xy || !ring_offsets || !inst_rings) && B > 0) return refuse("la3d_fit_instances_poly_filtered", "bad argument");
   la3d_fit_args a = legacy_args(depth, depth_plane_stride, image_index, K, k_stride, ground, sample_idx, B, H, W, out, status, aux,
                                 workspace, stream);
   legacy_poly(a, poly_xy, ring_offsets, inst_rings);
@@ -409,41 +381,27 @@ int la3d_fit_instances_poly_filtered(const float* depth, int64_t depth_plane_str
 
 // what la3d_fit_instances_ex and la3d_fit_instances_bits check alike
 static int check_block_options(const la3d_fit_args& a, const char* who) {
-  if (a.proj && !(a.image_width > 0 && a.image_height > 0)) {
-    snprintf(g_err, sizeof(g_err), "%s: proj needs image_width / image_height > 0", who);
-    return LA3D_ERR_ARG;
-  }
+  if (a.proj && !(a.image_width > 0 && a.image_height > 0)) return refuse(who, "proj needs image_width / image_height > 0");
   if (a.opt_engine < 0 || a.opt_engine > LA3D_ENGINE_ROWS2 || a.opt_launch_order < 0 || a.opt_launch_order > LA3D_ORDER_ON ||
-      a.opt_build < 0 || a.opt_build > LA3D_BUILD_NOCULL) {
-    snprintf(g_err, sizeof(g_err), "%s: bad opt_engine / opt_launch_order / opt_build", who);
-    return LA3D_ERR_ARG;
-  }
+      a.opt_build < 0 || a.opt_build > LA3D_BUILD_NOCULL)
+    return refuse(who, "bad opt_engine / opt_launch_order / opt_build");
   return LA3D_SUCCESS;
 }
 
+// Whether a block entry runs the fused filter: filter_boundary >= 0 AND filter_max_edge > 0.  A zero-initialised block (the natural
+// C idiom, and what "missing fields are zero" gives) means NO filter - max_edge == 0 would reject every instance (edge < 0 never holds)
+static bool block_filter_on(const la3d_fit_args& a) { return a.filter_boundary >= 0 && a.filter_max_edge > 0; }
+
 int la3d_fit_instances_ex(const la3d_fit_args* args) {
-  constexpr int32_t V1_SIZE = (int32_t)offsetof(la3d_fit_args, area_hint);   // the block as first published: every field up to `stream`
-  if (!args || args->struct_size < V1_SIZE) {   // (a longer block from a newer caller is fine, fields it lacks are taken as zero)
-    set_err("la3d_fit_instances_ex: bad struct_size");
-    return LA3D_ERR_ARG;
-  }
-  la3d_fit_args a;
-  memset(&a, 0, sizeof(a));
-  memcpy(&a, args, (size_t)args->struct_size < sizeof(a) ? (size_t)args->struct_size : sizeof(a));
+  const char* who = "la3d_fit_instances_ex";
+  if (!fit_args_size_ok(args)) return refuse(who, "bad struct_size");
+  const la3d_fit_args a = fit_args_copy(args);
   const int kinds = (a.mask ? 1 : 0) + (a.rle_counts ? 1 : 0) + (a.poly_xy ? 1 : 0);
-  if (kinds != 1 && a.B > 0) {
-    set_err("la3d_fit_instances_ex: give exactly one of mask / rle_counts / poly_xy");
-    return LA3D_ERR_ARG;
-  }
-  if (a.poly_xy && (!a.ring_offsets || !a.inst_rings)) {
-    set_err("la3d_fit_instances_ex: polygon masks need ring_offsets and inst_rings");
-    return LA3D_ERR_ARG;
-  }
-  const int rc = check_block_options(a, "la3d_fit_instances_ex");
+  if (kinds != 1 && a.B > 0) return refuse(who, "give exactly one of mask / rle_counts / poly_xy");
+  if (a.poly_xy && (!a.ring_offsets || !a.inst_rings)) return refuse(who, "polygon masks need ring_offsets and inst_rings");
+  const int rc = check_block_options(a, who);
   if (rc != LA3D_SUCCESS) return rc;
-  // the fused filter is on when filter_boundary >= 0 AND filter_max_edge > 0: a zero-initialised block (the natural C idiom, and
-  // what "missing fields are zero" gives) means NO filter - max_edge == 0 would reject every instance (edge < 0 never holds)
-  return fit_dispatch(a, a.filter_boundary >= 0 && a.filter_max_edge > 0, "la3d_fit_instances_ex");
+  return fit_dispatch(a, block_filter_on(a), who);
 }
 
 size_t la3d_mask_bits_words(int H, int W) {
@@ -452,76 +410,38 @@ size_t la3d_mask_bits_words(int H, int W) {
 }
 
 int la3d_fit_instances_bits(const la3d_fit_args* args, const uint32_t* mask_bits, int64_t bits_plane_stride, int32_t flags) {
-  constexpr int32_t V1_SIZE = (int32_t)offsetof(la3d_fit_args, area_hint);
-  if (!args || args->struct_size < V1_SIZE) {
-    set_err("la3d_fit_instances_bits: bad struct_size");
-    return LA3D_ERR_ARG;
-  }
-  la3d_fit_args a;
-  memset(&a, 0, sizeof(a));
-  memcpy(&a, args, (size_t)args->struct_size < sizeof(a) ? (size_t)args->struct_size : sizeof(a));
-  if (a.mask || a.rle_counts || a.poly_xy) {
-    set_err("la3d_fit_instances_bits: the masks are the bit planes - mask, rle_counts and poly_xy must be NULL");
-    return LA3D_ERR_ARG;
-  }
-  if (flags & ~(int32_t)LA3D_BITS_HEIGHT_SPAN) {
-    set_err("la3d_fit_instances_bits: unknown flags (LA3D_BITS_HEIGHT_ROWS or LA3D_BITS_HEIGHT_SPAN)");
-    return LA3D_ERR_ARG;
-  }
-  if (a.B > 0 && (!mask_bits || (reinterpret_cast<uintptr_t>(mask_bits) & 3))) {
-    set_err("la3d_fit_instances_bits: mask_bits must be a 4-byte aligned device pointer");
-    return LA3D_ERR_ARG;
-  }
-  if (a.B > 0 && a.H > 0 && a.W > 0 && bits_plane_stride < (int64_t)la3d_mask_bits_words(a.H, a.W)) {
-    set_err("la3d_fit_instances_bits: bits_plane_stride is smaller than la3d_mask_bits_words(H, W)");
-    return LA3D_ERR_ARG;
-  }
-  const int rc = check_block_options(a, "la3d_fit_instances_bits");
+  const char* who = "la3d_fit_instances_bits";
+  if (!fit_args_size_ok(args)) return refuse(who, "bad struct_size");
+  const la3d_fit_args a = fit_args_copy(args);
+  if (a.mask || a.rle_counts || a.poly_xy) return refuse(who, "the masks are the bit planes - mask, rle_counts and poly_xy must be NULL");
+  if (flags & ~(int32_t)LA3D_BITS_HEIGHT_SPAN) return refuse(who, "unknown flags (LA3D_BITS_HEIGHT_ROWS or LA3D_BITS_HEIGHT_SPAN)");
+  if (a.B > 0 && (!mask_bits || (reinterpret_cast<uintptr_t>(mask_bits) & 3))) return refuse(who, "mask_bits must be a 4-byte aligned device pointer");
+  if (a.B > 0 && a.H > 0 && a.W > 0 && bits_plane_stride < (int64_t)la3d_mask_bits_words(a.H, a.W))
+    return refuse(who, "bits_plane_stride is smaller than la3d_mask_bits_words(H, W)");
+  const int rc = check_block_options(a, who);
   if (rc != LA3D_SUCCESS) return rc;
   const BitsSource bs{mask_bits, bits_plane_stride, flags};
-  return fit_dispatch(a, a.filter_boundary >= 0 && a.filter_max_edge > 0, "la3d_fit_instances_bits", &bs);
+  return fit_dispatch(a, block_filter_on(a), who, &bs);
 }
 
 // what la3d_fit_instances_depth16 and la3d_fit_instances_frames_depth16 check alike, in two steps (the entry copies its block between
 // them): the two blocks and the planes pointer, then the value rule of the la3d_depth16 block
 static int depth16_block_head(const la3d_fit_args* args, const la3d_depth16* depth, const char* who) {
-  constexpr int32_t V1_SIZE = (int32_t)offsetof(la3d_fit_args, area_hint);
   static_assert(sizeof(la3d_depth16) == 32, "la3d_depth16 is part of the ABI");
-  if (!args || args->struct_size < V1_SIZE) {
-    snprintf(g_err, sizeof(g_err), "%s: bad struct_size", who);
-    return LA3D_ERR_ARG;
-  }
-  if (!depth) {
-    snprintf(g_err, sizeof(g_err), "%s: depth (the la3d_depth16 block) is NULL", who);
-    return LA3D_ERR_ARG;
-  }
-  if (depth->struct_size < (int32_t)sizeof(la3d_depth16)) {
-    snprintf(g_err, sizeof(g_err), "%s: bad struct_size of la3d_depth16", who);
-    return LA3D_ERR_ARG;
-  }
-  if (depth->dtype != LA3D_DTYPE_F16 && depth->dtype != LA3D_DTYPE_U16) {
-    snprintf(g_err, sizeof(g_err), "%s: unknown dtype (LA3D_DTYPE_F16 or LA3D_DTYPE_U16)", who);
-    return LA3D_ERR_ARG;
-  }
-  if (!depth->planes || (reinterpret_cast<uintptr_t>(depth->planes) & 1)) {
-    snprintf(g_err, sizeof(g_err), "%s: planes must be a 2-byte aligned device pointer", who);
-    return LA3D_ERR_ARG;
-  }
+  if (!fit_args_size_ok(args)) return refuse(who, "bad struct_size");
+  if (!depth) return refuse(who, "depth (the la3d_depth16 block) is NULL");
+  if (depth->struct_size < (int32_t)sizeof(la3d_depth16)) return refuse(who, "bad struct_size of la3d_depth16");
+  if (depth->dtype != LA3D_DTYPE_F16 && depth->dtype != LA3D_DTYPE_U16) return refuse(who, "unknown dtype (LA3D_DTYPE_F16 or LA3D_DTYPE_U16)");
+  if (!depth->planes || (reinterpret_cast<uintptr_t>(depth->planes) & 1)) return refuse(who, "planes must be a 2-byte aligned device pointer");
   return LA3D_SUCCESS;
 }
 static int depth16_block_values(const la3d_depth16* depth, const char* who) {
   if (depth->dtype == LA3D_DTYPE_U16) {
-    if (!(depth->scale > 0.0f && depth->scale <= 3.4028234663852886e38f)) {   // (false for NaN)
-      snprintf(g_err, sizeof(g_err), "%s: the scale of LA3D_DTYPE_U16 planes must be finite and > 0", who);
-      return LA3D_ERR_ARG;
-    }
-    if (depth->flags & ~(int32_t)LA3D_DEPTH_ZERO_IS_HOLE) {
-      snprintf(g_err, sizeof(g_err), "%s: unknown flags (LA3D_DEPTH_ZERO_IS_HOLE or 0)", who);
-      return LA3D_ERR_ARG;
-    }
+    if (!(depth->scale > 0.0f && depth->scale <= 3.4028234663852886e38f))   // (false for NaN)
+      return refuse(who, "the scale of LA3D_DTYPE_U16 planes must be finite and > 0");
+    if (depth->flags & ~(int32_t)LA3D_DEPTH_ZERO_IS_HOLE) return refuse(who, "unknown flags (LA3D_DEPTH_ZERO_IS_HOLE or 0)");
   } else if (depth->flags != 0) {
-    snprintf(g_err, sizeof(g_err), "%s: flags must be 0 for LA3D_DTYPE_F16 planes", who);
-    return LA3D_ERR_ARG;
+    return refuse(who, "flags must be 0 for LA3D_DTYPE_F16 planes");
   }
   return LA3D_SUCCESS;
 }
@@ -531,105 +451,59 @@ int la3d_fit_instances_depth16(const la3d_fit_args* args, const la3d_depth16* de
   const char* who = "la3d_fit_instances_depth16";
   int rc = depth16_block_head(args, depth, who);
   if (rc != LA3D_SUCCESS) return rc;
-  la3d_fit_args a;
-  memset(&a, 0, sizeof(a));
-  memcpy(&a, args, (size_t)args->struct_size < sizeof(a) ? (size_t)args->struct_size : sizeof(a));
-  if (a.depth || a.depth_plane_stride != 0) {
-    set_err("la3d_fit_instances_depth16: the depth planes come in the la3d_depth16 block - args->depth must be NULL and depth_plane_stride 0");
-    return LA3D_ERR_ARG;
-  }
+  const la3d_fit_args a = fit_args_copy(args);
+  if (a.depth || a.depth_plane_stride != 0)
+    return refuse(who, "the depth planes come in the la3d_depth16 block - args->depth must be NULL and depth_plane_stride 0");
   rc = depth16_block_values(depth, who);
   if (rc != LA3D_SUCCESS) return rc;
-  if (depth->plane_stride < 0 || (depth->plane_stride != 0 && a.H > 0 && a.W > 0 && depth->plane_stride < (int64_t)a.H * a.W)) {
-    set_err("la3d_fit_instances_depth16: plane_stride must be 0 (one shared plane) or >= H*W elements");
-    return LA3D_ERR_ARG;
-  }
+  if (depth->plane_stride < 0 || (depth->plane_stride != 0 && a.H > 0 && a.W > 0 && depth->plane_stride < (int64_t)a.H * a.W))
+    return refuse(who, "plane_stride must be 0 (one shared plane) or >= H*W elements");
   const int kinds = (a.mask ? 1 : 0) + (a.rle_counts ? 1 : 0) + (a.poly_xy ? 1 : 0) + (mask_bits ? 1 : 0);
-  if (kinds != 1) {
-    set_err("la3d_fit_instances_depth16: give exactly one mask source: mask / rle_counts / poly_xy in the block, or mask_bits");
-    return LA3D_ERR_ARG;
-  }
-  if (a.poly_xy && (!a.ring_offsets || !a.inst_rings)) {
-    set_err("la3d_fit_instances_depth16: polygon masks need ring_offsets and inst_rings");
-    return LA3D_ERR_ARG;
-  }
+  if (kinds != 1) return refuse(who, "give exactly one mask source: mask / rle_counts / poly_xy in the block, or mask_bits");
+  if (a.poly_xy && (!a.ring_offsets || !a.inst_rings)) return refuse(who, "polygon masks need ring_offsets and inst_rings");
+  // (the rules of la3d_fit_instances_bits, but for a source that is optional here: they hold for B = 0 too, and say bits_flags)
   if (mask_bits) {
-    if (bits_flags & ~(int32_t)LA3D_BITS_HEIGHT_SPAN) {
-      set_err("la3d_fit_instances_depth16: unknown bits_flags (LA3D_BITS_HEIGHT_ROWS or LA3D_BITS_HEIGHT_SPAN)");
-      return LA3D_ERR_ARG;
-    }
-    if (reinterpret_cast<uintptr_t>(mask_bits) & 3) {
-      set_err("la3d_fit_instances_depth16: mask_bits must be a 4-byte aligned device pointer");
-      return LA3D_ERR_ARG;
-    }
-    if (a.B > 0 && a.H > 0 && a.W > 0 && bits_plane_stride < (int64_t)la3d_mask_bits_words(a.H, a.W)) {
-      set_err("la3d_fit_instances_depth16: bits_plane_stride is smaller than la3d_mask_bits_words(H, W)");
-      return LA3D_ERR_ARG;
-    }
+    if (bits_flags & ~(int32_t)LA3D_BITS_HEIGHT_SPAN) return refuse(who, "unknown bits_flags (LA3D_BITS_HEIGHT_ROWS or LA3D_BITS_HEIGHT_SPAN)");
+    if (reinterpret_cast<uintptr_t>(mask_bits) & 3) return refuse(who, "mask_bits must be a 4-byte aligned device pointer");
+    if (a.B > 0 && a.H > 0 && a.W > 0 && bits_plane_stride < (int64_t)la3d_mask_bits_words(a.H, a.W))
+      return refuse(who, "bits_plane_stride is smaller than la3d_mask_bits_words(H, W)");
   }
   rc = check_block_options(a, who);
   if (rc != LA3D_SUCCESS) return rc;
   const BitsSource bs{mask_bits, bits_plane_stride, bits_flags};
   const Depth16Source ds{depth};
-  return fit_dispatch(a, a.filter_boundary >= 0 && a.filter_max_edge > 0, who, mask_bits ? &bs : nullptr, nullptr, &ds);
+  return fit_dispatch(a, block_filter_on(a), who, mask_bits ? &bs : nullptr, nullptr, &ds);
 }
 
 // what la3d_fit_instances_frames and la3d_fit_instances_frames_depth16 check alike on the copied block and the frame table
 // (bits: la3d_fit_instances_frames_bits, whose masks are its own arguments - it has refused mask / rle_counts / poly_xy itself)
-static int check_frames_call(la3d_fit_args& a, const la3d_frame* frames, int32_t P, const char* who, bool bits = false) {
+static int check_frames_call(const la3d_fit_args& a, const la3d_frame* frames, int32_t P, const char* who, bool bits = false) {
   static_assert(sizeof(la3d_frame) == 24, "la3d_frame is part of the ABI");
-  if (a.mask) {
-    snprintf(g_err, sizeof(g_err), "%s: u8 mask planes are not supported - run lengths or polygon parts", who);
-    return LA3D_ERR_UNSUPPORTED;
-  }
-  if (a.method == LA3D_METHOD_CONVEX_HULL) {
-    snprintf(g_err, sizeof(g_err), "%s: method = LA3D_METHOD_CONVEX_HULL is not supported in this form", who);
-    return LA3D_ERR_UNSUPPORTED;
-  }
+  if (a.mask) return refuse(who, "u8 mask planes are not supported - run lengths or polygon parts", LA3D_ERR_UNSUPPORTED);
+  if (a.method == LA3D_METHOD_CONVEX_HULL) return refuse(who, "method = LA3D_METHOD_CONVEX_HULL is not supported in this form", LA3D_ERR_UNSUPPORTED);
   const int kinds = (a.rle_counts ? 1 : 0) + (a.poly_xy ? 1 : 0);
-  if (!bits && kinds != 1 && a.B > 0) {
-    snprintf(g_err, sizeof(g_err), "%s: give exactly one of rle_counts / poly_xy", who);
-    return LA3D_ERR_ARG;
-  }
-  if (a.poly_xy && (!a.ring_offsets || !a.inst_rings)) {
-    snprintf(g_err, sizeof(g_err), "%s: polygon masks need ring_offsets and inst_rings", who);
-    return LA3D_ERR_ARG;
-  }
-  if (P < 0 || (a.B > 0 && (!frames || P == 0 || (reinterpret_cast<uintptr_t>(frames) & 7)))) {
-    snprintf(g_err, sizeof(g_err), "%s: frames must be an 8-byte aligned device pointer to P >= 1 rows", who);
-    return LA3D_ERR_ARG;
-  }
-  if (a.B > 0 && !a.image_index) {
-    snprintf(g_err, sizeof(g_err), "%s: image_index is required (instance n belongs to frame row image_index[n])", who);
-    return LA3D_ERR_ARG;
-  }
-  if (a.depth_plane_stride != 0 || a.frame_width != 0) {
-    snprintf(g_err, sizeof(g_err), "%s: depth_plane_stride and frame_width must be 0 (the frame table holds them per image)", who);
-    return LA3D_ERR_ARG;
-  }
+  if (!bits && kinds != 1 && a.B > 0) return refuse(who, "give exactly one of rle_counts / poly_xy");
+  if (a.poly_xy && (!a.ring_offsets || !a.inst_rings)) return refuse(who, "polygon masks need ring_offsets and inst_rings");
+  if (P < 0 || (a.B > 0 && (!frames || P == 0 || (reinterpret_cast<uintptr_t>(frames) & 7))))
+    return refuse(who, "frames must be an 8-byte aligned device pointer to P >= 1 rows");
+  if (a.B > 0 && !a.image_index) return refuse(who, "image_index is required (instance n belongs to frame row image_index[n])");
+  if (a.depth_plane_stride != 0 || a.frame_width != 0)
+    return refuse(who, "depth_plane_stride and frame_width must be 0 (the frame table holds them per image)");
   return LA3D_SUCCESS;
 }
 
 int la3d_fit_instances_frames(const la3d_fit_args* args, const la3d_frame* frames, int32_t P) {
-  constexpr int32_t V1_SIZE = (int32_t)offsetof(la3d_fit_args, area_hint);
-  if (!args || args->struct_size < V1_SIZE) {
-    set_err("la3d_fit_instances_frames: bad struct_size");
-    return LA3D_ERR_ARG;
-  }
-  la3d_fit_args a;
-  memset(&a, 0, sizeof(a));
-  memcpy(&a, args, (size_t)args->struct_size < sizeof(a) ? (size_t)args->struct_size : sizeof(a));
-  int rc = check_frames_call(a, frames, P, "la3d_fit_instances_frames");
+  const char* who = "la3d_fit_instances_frames";
+  if (!fit_args_size_ok(args)) return refuse(who, "bad struct_size");
+  la3d_fit_args a = fit_args_copy(args);
+  int rc = check_frames_call(a, frames, P, who);
   if (rc != LA3D_SUCCESS) return rc;
-  if (reinterpret_cast<uintptr_t>(a.depth) & 15) {
-    set_err("la3d_fit_instances_frames: depth must be 16-byte aligned");
-    return LA3D_ERR_ARG;
-  }
+  if (reinterpret_cast<uintptr_t>(a.depth) & 15) return refuse(who, "depth must be 16-byte aligned");
   a.image_width = a.image_height = 1.0;   // (ignored: proj clamps to the instance's own frame)
-  rc = check_block_options(a, "la3d_fit_instances_frames");
+  rc = check_block_options(a, who);
   if (rc != LA3D_SUCCESS) return rc;
   const FramesSource fs{frames, P};
-  return fit_dispatch(a, a.filter_boundary >= 0 && a.filter_max_edge > 0, "la3d_fit_instances_frames", nullptr, &fs);
+  return fit_dispatch(a, block_filter_on(a), who, nullptr, &fs);
 }
 
 // the frames call on 16-bit planes: the checks of both parents, then fit_dispatch with both sources (it launches the FRAMES
@@ -638,31 +512,20 @@ int la3d_fit_instances_frames_depth16(const la3d_fit_args* args, const la3d_dept
   const char* who = "la3d_fit_instances_frames_depth16";
   int rc = depth16_block_head(args, depth, who);
   if (rc != LA3D_SUCCESS) return rc;
-  la3d_fit_args a;
-  memset(&a, 0, sizeof(a));
-  memcpy(&a, args, (size_t)args->struct_size < sizeof(a) ? (size_t)args->struct_size : sizeof(a));
-  if (a.depth) {
-    snprintf(g_err, sizeof(g_err), "%s: the depth planes come in the la3d_depth16 block - args->depth must be NULL", who);
-    return LA3D_ERR_ARG;
-  }
+  la3d_fit_args a = fit_args_copy(args);
+  if (a.depth) return refuse(who, "the depth planes come in the la3d_depth16 block - args->depth must be NULL");
   rc = depth16_block_values(depth, who);
   if (rc != LA3D_SUCCESS) return rc;
-  if (depth->plane_stride != 0) {
-    snprintf(g_err, sizeof(g_err), "%s: plane_stride of the la3d_depth16 block must be 0 (the frame table says where every plane lies)", who);
-    return LA3D_ERR_ARG;
-  }
+  if (depth->plane_stride != 0) return refuse(who, "plane_stride of the la3d_depth16 block must be 0 (the frame table says where every plane lies)");
   rc = check_frames_call(a, frames, P, who);
   if (rc != LA3D_SUCCESS) return rc;
-  if (reinterpret_cast<uintptr_t>(depth->planes) & 7) {
-    snprintf(g_err, sizeof(g_err), "%s: planes (the base of the ragged buffer) must be 8-byte aligned", who);
-    return LA3D_ERR_ARG;
-  }
+  if (reinterpret_cast<uintptr_t>(depth->planes) & 7) return refuse(who, "planes (the base of the ragged buffer) must be 8-byte aligned");
   a.image_width = a.image_height = 1.0;   // (ignored: proj clamps to the instance's own frame)
   rc = check_block_options(a, who);
   if (rc != LA3D_SUCCESS) return rc;
   const FramesSource fs{frames, P};
   const Depth16Source ds{depth};
-  return fit_dispatch(a, a.filter_boundary >= 0 && a.filter_max_edge > 0, who, nullptr, &fs, &ds);
+  return fit_dispatch(a, block_filter_on(a), who, nullptr, &fs, &ds);
 }
 
 // the frames call on bit planes, one plane per instance at its own offset: the checks of la3d_fit_instances_frames (with depth16: of
@@ -670,59 +533,37 @@ int la3d_fit_instances_frames_depth16(const la3d_fit_args* args, const la3d_dept
 int la3d_fit_instances_frames_bits(const la3d_fit_args* args, const la3d_depth16* depth16, const la3d_frame* frames, int32_t P,
                                    const uint32_t* mask_bits, const int64_t* bits_offsets, int32_t bits_flags) {
   const char* who = "la3d_fit_instances_frames_bits";
-  constexpr int32_t V1_SIZE = (int32_t)offsetof(la3d_fit_args, area_hint);
   int rc = LA3D_SUCCESS;
   if (depth16) {
     rc = depth16_block_head(args, depth16, who);
     if (rc != LA3D_SUCCESS) return rc;
-  } else if (!args || args->struct_size < V1_SIZE) {
-    snprintf(g_err, sizeof(g_err), "%s: bad struct_size", who);
-    return LA3D_ERR_ARG;
+  } else if (!fit_args_size_ok(args)) {
+    return refuse(who, "bad struct_size");
   }
-  la3d_fit_args a;
-  memset(&a, 0, sizeof(a));
-  memcpy(&a, args, (size_t)args->struct_size < sizeof(a) ? (size_t)args->struct_size : sizeof(a));
+  la3d_fit_args a = fit_args_copy(args);
   if (depth16) {
-    if (a.depth) {
-      snprintf(g_err, sizeof(g_err), "%s: the depth planes come in the la3d_depth16 block - args->depth must be NULL", who);
-      return LA3D_ERR_ARG;
-    }
+    if (a.depth) return refuse(who, "the depth planes come in the la3d_depth16 block - args->depth must be NULL");
     rc = depth16_block_values(depth16, who);
     if (rc != LA3D_SUCCESS) return rc;
-    if (depth16->plane_stride != 0) {
-      snprintf(g_err, sizeof(g_err), "%s: plane_stride of the la3d_depth16 block must be 0 (the frame table says where every plane lies)", who);
-      return LA3D_ERR_ARG;
-    }
+    if (depth16->plane_stride != 0) return refuse(who, "plane_stride of the la3d_depth16 block must be 0 (the frame table says where every plane lies)");
   }
-  if (a.mask || a.rle_counts || a.poly_xy) {
-    snprintf(g_err, sizeof(g_err), "%s: the masks are the bit planes - mask, rle_counts and poly_xy must be NULL", who);
-    return LA3D_ERR_ARG;
-  }
-  if (bits_flags & ~(int32_t)LA3D_BITS_HEIGHT_SPAN) {
-    snprintf(g_err, sizeof(g_err), "%s: unknown bits_flags (LA3D_BITS_HEIGHT_ROWS or LA3D_BITS_HEIGHT_SPAN)", who);
-    return LA3D_ERR_ARG;
-  }
+  if (a.mask || a.rle_counts || a.poly_xy) return refuse(who, "the masks are the bit planes - mask, rle_counts and poly_xy must be NULL");
+  if (bits_flags & ~(int32_t)LA3D_BITS_HEIGHT_SPAN) return refuse(who, "unknown bits_flags (LA3D_BITS_HEIGHT_ROWS or LA3D_BITS_HEIGHT_SPAN)");
   rc = check_frames_call(a, frames, P, who, true);
   if (rc != LA3D_SUCCESS) return rc;
-  if (a.B > 0 && (!mask_bits || (reinterpret_cast<uintptr_t>(mask_bits) & 15))) {
-    snprintf(g_err, sizeof(g_err), "%s: mask_bits must be a 16-byte aligned device pointer", who);
-    return LA3D_ERR_ARG;
-  }
-  if (a.B > 0 && (!bits_offsets || (reinterpret_cast<uintptr_t>(bits_offsets) & 7))) {
-    snprintf(g_err, sizeof(g_err), "%s: bits_offsets must be an 8-byte aligned device pointer to B plane offsets", who);
-    return LA3D_ERR_ARG;
-  }
-  if (depth16 ? (reinterpret_cast<uintptr_t>(depth16->planes) & 7) != 0 : (reinterpret_cast<uintptr_t>(a.depth) & 15) != 0) {
-    snprintf(g_err, sizeof(g_err), depth16 ? "%s: planes (the base of the ragged buffer) must be 8-byte aligned" : "%s: depth must be 16-byte aligned", who);
-    return LA3D_ERR_ARG;
-  }
+  // (one plane per instance at its own offset, read in 16-byte groups: no stride to check, and a stricter alignment than the uniform form's)
+  if (a.B > 0 && (!mask_bits || (reinterpret_cast<uintptr_t>(mask_bits) & 15))) return refuse(who, "mask_bits must be a 16-byte aligned device pointer");
+  if (a.B > 0 && (!bits_offsets || (reinterpret_cast<uintptr_t>(bits_offsets) & 7)))
+    return refuse(who, "bits_offsets must be an 8-byte aligned device pointer to B plane offsets");
+  if (depth16 ? (reinterpret_cast<uintptr_t>(depth16->planes) & 7) != 0 : (reinterpret_cast<uintptr_t>(a.depth) & 15) != 0)
+    return refuse(who, depth16 ? "planes (the base of the ragged buffer) must be 8-byte aligned" : "depth must be 16-byte aligned");
   a.image_width = a.image_height = 1.0;   // (ignored: proj clamps to the instance's own frame)
   rc = check_block_options(a, who);
   if (rc != LA3D_SUCCESS) return rc;
   const BitsSource bs{mask_bits, 0, bits_flags, bits_offsets};
   const FramesSource fs{frames, P};
   const Depth16Source ds{depth16};
-  return fit_dispatch(a, a.filter_boundary >= 0 && a.filter_max_edge > 0, who, &bs, &fs, depth16 ? &ds : nullptr);
+  return fit_dispatch(a, block_filter_on(a), who, &bs, &fs, depth16 ? &ds : nullptr);
 }
 
 }  // extern "C"

@@ -574,27 +574,27 @@ __global__ __launch_bounds__(256) void align_apply_batch_kernel(const float* __r
 
 const char* ar_check(const la3d_align_ransac_args* a, int* rc) {
   *rc = LA3D_ERR_ARG;
-  if (!a) return "la3d_align_ransac_batch: NULL argument block";
-  if (a->struct_size != (int32_t)sizeof(la3d_align_ransac_args)) return "la3d_align_ransac_batch: struct_size is not sizeof(la3d_align_ransac_args)";
-  if (a->P < 0 || a->n < 0) return "la3d_align_ransac_batch: negative P or n";
-  if (a->max_trials < 1) return "la3d_align_ransac_batch: max_trials must be at least 1";
+  if (!a) return "NULL argument block";
+  if (a->struct_size != (int32_t)sizeof(la3d_align_ransac_args)) return "struct_size is not sizeof(la3d_align_ransac_args)";
+  if (a->P < 0 || a->n < 0) return "negative P or n";
+  if (a->max_trials < 1) return "max_trials must be at least 1";
   if (!(a->min_samples > 0.0) || (a->min_samples >= 1.0 && (a->min_samples != (double)(long long)a->min_samples || a->min_samples > 2147483647.0)))
-    return "la3d_align_ransac_batch: min_samples must be a fraction in (0, 1) or an integer >= 1";
-  if (!(a->stop_probability >= 0.0 && a->stop_probability <= 1.0)) return "la3d_align_ransac_batch: stop_probability outside [0, 1]";
-  if (a->subsets && a->m_cap < 1) return "la3d_align_ransac_batch: subsets given with m_cap < 1";
+    return "min_samples must be a fraction in (0, 1) or an integer >= 1";
+  if (!(a->stop_probability >= 0.0 && a->stop_probability <= 1.0)) return "stop_probability outside [0, 1]";
+  if (a->subsets && a->m_cap < 1) return "subsets given with m_cap < 1";
   if ((reinterpret_cast<uintptr_t>(a->relative_sel) | reinterpret_cast<uintptr_t>(a->metric_sel) | reinterpret_cast<uintptr_t>(a->subsets) |
        reinterpret_cast<uintptr_t>(a->coef) | reinterpret_cast<uintptr_t>(a->n_inliers) | reinterpret_cast<uintptr_t>(a->n_trials) |
        reinterpret_cast<uintptr_t>(a->best_trial) | reinterpret_cast<uintptr_t>(a->status)) & 3u)
-    return "la3d_align_ransac_batch: a pointer is not 4-byte aligned";
+    return "a pointer is not 4-byte aligned";
   if ((reinterpret_cast<uintptr_t>(a->counts) & 7u) || (reinterpret_cast<uintptr_t>(a->workspace) & 15u))
-    return "la3d_align_ransac_batch: counts must be 8-byte, the workspace 16-byte aligned";
+    return "counts must be 8-byte, the workspace 16-byte aligned";
   if (a->P > 0 && (!a->counts || !a->coef || !a->n_inliers || !a->n_trials || !a->best_trial || !a->status || !a->workspace ||
                    (a->n > 0 && (!a->relative_sel || !a->metric_sel))))
-    return "la3d_align_ransac_batch: NULL pointer with work to do";
+    return "NULL pointer with work to do";
   *rc = LA3D_ERR_UNSUPPORTED;
-  if (a->n > LA3D_ALIGN_RANSAC_MAX_N) return "la3d_align_ransac_batch: more than LA3D_ALIGN_RANSAC_MAX_N samples per frame";
-  if (a->max_trials > LA3D_ALIGN_RANSAC_MAX_TRIALS) return "la3d_align_ransac_batch: more than LA3D_ALIGN_RANSAC_MAX_TRIALS trials";
-  if (a->P > 65535) return "la3d_align_ransac_batch: more than 65535 frames";
+  if (a->n > LA3D_ALIGN_RANSAC_MAX_N) return "more than LA3D_ALIGN_RANSAC_MAX_N samples per frame";
+  if (a->max_trials > LA3D_ALIGN_RANSAC_MAX_TRIALS) return "more than LA3D_ALIGN_RANSAC_MAX_TRIALS trials";
+  if (a->P > 65535) return "more than 65535 frames";
   *rc = LA3D_SUCCESS;
   return nullptr;
 }
@@ -610,10 +610,7 @@ size_t la3d_align_ransac_workspace_bytes(int P, int64_t n, int max_trials) {
 
 int la3d_align_ransac_batch(const la3d_align_ransac_args* a) {
   int rc;
-  if (const char* msg = ar_check(a, &rc)) {
-    set_err(msg);
-    return rc;
-  }
+  if (const char* what = ar_check(a, &rc)) return refuse("la3d_align_ransac_batch", what, rc);
   if (a->P == 0) return LA3D_SUCCESS;
   const int P = a->P, T = a->max_trials;
   const ArLayout L = ar_layout(P, a->n, T);
@@ -651,14 +648,10 @@ int la3d_align_ransac_subsets(const int64_t* counts, int P, double min_samples, 
                               int m_cap, void* stream) {
   if (P < 0 || max_trials < 1 || m_cap < 1 || !(min_samples > 0.0) ||
       (min_samples >= 1.0 && (min_samples != (double)(long long)min_samples || min_samples > 2147483647.0)) ||
-      (P > 0 && (!counts || !subsets)) || (reinterpret_cast<uintptr_t>(counts) & 7u) || (reinterpret_cast<uintptr_t>(subsets) & 3u)) {
-    set_err("la3d_align_ransac_subsets: bad argument");
-    return LA3D_ERR_ARG;
-  }
-  if (max_trials > LA3D_ALIGN_RANSAC_MAX_TRIALS || P > 65535) {
-    set_err("la3d_align_ransac_subsets: more than LA3D_ALIGN_RANSAC_MAX_TRIALS trials or 65535 frames");
-    return LA3D_ERR_UNSUPPORTED;
-  }
+      (P > 0 && (!counts || !subsets)) || (reinterpret_cast<uintptr_t>(counts) & 7u) || (reinterpret_cast<uintptr_t>(subsets) & 3u))
+    return refuse("la3d_align_ransac_subsets", "bad argument");
+  if (max_trials > LA3D_ALIGN_RANSAC_MAX_TRIALS || P > 65535)
+    return refuse("la3d_align_ransac_subsets", "more than LA3D_ALIGN_RANSAC_MAX_TRIALS trials or 65535 frames", LA3D_ERR_UNSUPPORTED);
   if (P == 0) return LA3D_SUCCESS;
   hipLaunchKernelGGL(align_export_subsets_kernel, dim3(max_trials, P), dim3(AR_NT), 0, static_cast<hipStream_t>(stream),
                      reinterpret_cast<const long long*>(counts), min_samples, max_trials, m_cap, (unsigned long long)seed, subsets);
@@ -669,15 +662,10 @@ int la3d_align_apply_batch(const float* relative, const float* metric, const uin
                            const int32_t* status, float fill, float* out, void* stream) {
   if (P < 0 || P > 65535 || n < 0 || (P > 0 && n > 0 && (!relative || !metric || !coef || !status || !out)) ||
       ((reinterpret_cast<uintptr_t>(relative) | reinterpret_cast<uintptr_t>(metric) | reinterpret_cast<uintptr_t>(coef) |
-        reinterpret_cast<uintptr_t>(status) | reinterpret_cast<uintptr_t>(out)) & 3u)) {
-    set_err("la3d_align_apply_batch: bad argument (P <= 65535, 4-byte aligned pointers)");
-    return LA3D_ERR_ARG;
-  }
+        reinterpret_cast<uintptr_t>(status) | reinterpret_cast<uintptr_t>(out)) & 3u))
+    return refuse("la3d_align_apply_batch", "bad argument (P <= 65535, 4-byte aligned pointers)");
   if (P == 0 || n == 0) return LA3D_SUCCESS;
-  if ((n + 255) / 256 > 0x7fffffffLL) {
-    set_err("la3d_align_apply_batch: frame too large");
-    return LA3D_ERR_UNSUPPORTED;
-  }
+  if ((n + 255) / 256 > 0x7fffffffLL) return refuse("la3d_align_apply_batch", "frame too large", LA3D_ERR_UNSUPPORTED);
   hipLaunchKernelGGL(align_apply_batch_kernel, dim3((unsigned)((n + 255) / 256), P), dim3(256), 0, static_cast<hipStream_t>(stream),
                      relative, metric, mask, (long long)n, coef, status, 0.0f, fill, out);
   return check_launch("la3d_align_apply_batch");

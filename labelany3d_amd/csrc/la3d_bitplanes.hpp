@@ -1,9 +1,9 @@
 // la3d_bitplanes.hpp - what the units that read or write bit planes share (la3d_bits.hip: decoders, packers, unpacker, statistics;
 // la3d_rle_encode.hip: the run-length encoder; la3d_open.hip: the opening; la3d_components.hip: connected components, whose frames
-// form takes the prologue; la3d_overlap.hip: the refusal helpers only).
+// form takes the prologue; la3d_overlap.hip: at() only).
 // Device side: where the planes of a call lie (BitsOut), the geometry of one of them (plane_geometry) and the prologue of a frames
-// workgroup (frames_prologue).  Host side: how an entry describes its planes (bits_out_uniform / bits_out_frames), how it refuses
-// (pack_refuse) and the ONE argument check of the packer entries (pack_check), with the wording more than one unit uses.
+// workgroup (frames_prologue).  Host side: how an entry describes its planes (bits_out_uniform / bits_out_frames) and the ONE
+// argument check of the packer entries (pack_check), with the wording more than one unit uses.  (Refusals: refuse, la3d_device.hpp.)
 // A BitsOut describes the planes of ONE call, in the uniform form (stride) or the frames form (offsets, frames, image_index):
 //   as a DESTINATION (every packer) the kernels store the words of instance b's plane through `bits` and, where the entry has one,
 //     its popcount to area[b];
@@ -128,12 +128,6 @@ BitsOut bits_out_frames(const la3d_frame* frames, int P, int H, int W, const int
   return c;
 }
 
-int pack_refuse(const char* who, const char* what, int code = LA3D_ERR_ARG) {
-  char msg[256];
-  snprintf(msg, sizeof(msg), "%s: %s", who, what);
-  set_err(msg);
-  return code;
-}
 inline uintptr_t at(const void* q) { return reinterpret_cast<uintptr_t>(q); }   // for the alignment and overlap rules an entry writes out
 
 // The argument check of every packer entry.  The rules and their rank are the same for all of them and stated here, once; an entry
@@ -153,17 +147,17 @@ struct PackPtr { const void* p; unsigned mask; const char* misaligned; bool opti
 
 int pack_check(const char* who, const PackWords& say, int B, int P, int W, bool work, bool shape_bad, bool lds_bad,
                std::initializer_list<PackPtr> ptrs, long long src_stride, const BitsOut& out) {
-  if (B < 0 || P < 0 || out.H <= 0 || W <= 0 || out.W < W) return pack_refuse(who, say.sizes);
-  if (say.shape && shape_bad) return pack_refuse(who, say.shape);
+  if (B < 0 || P < 0 || out.H <= 0 || W <= 0 || out.W < W) return refuse(who, say.sizes);
+  if (say.shape && shape_bad) return refuse(who, say.shape);
   if (work) {
     for (const PackPtr& q : ptrs)
-      if (!q.p && !q.optional) return pack_refuse(who, say.null_ptr);
+      if (!q.p && !q.optional) return refuse(who, say.null_ptr);
     for (const PackPtr& q : ptrs)
-      if (reinterpret_cast<uintptr_t>(q.p) & q.mask) return pack_refuse(who, q.misaligned);
+      if (reinterpret_cast<uintptr_t>(q.p) & q.mask) return refuse(who, q.misaligned);
   }
-  if (say.lds && lds_bad) return pack_refuse(who, say.lds, LA3D_ERR_UNSUPPORTED);
-  if (work && say.src_stride && src_stride < (long long)out.H * W) return pack_refuse(who, say.src_stride);
-  if (work && say.bits_stride && out.stride < (long long)la3d_mask_bits_words(out.H, out.W)) return pack_refuse(who, say.bits_stride);
+  if (say.lds && lds_bad) return refuse(who, say.lds, LA3D_ERR_UNSUPPORTED);
+  if (work && say.src_stride && src_stride < (long long)out.H * W) return refuse(who, say.src_stride);
+  if (work && say.bits_stride && out.stride < (long long)la3d_mask_bits_words(out.H, out.W)) return refuse(who, say.bits_stride);
   return work ? PACK_LAUNCH : PACK_NOTHING;
 }
 inline int pack_done(int rc) { return rc < 0 ? rc : LA3D_SUCCESS; }   // what an entry returns when pack_check said anything but PACK_LAUNCH

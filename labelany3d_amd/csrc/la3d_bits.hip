@@ -773,7 +773,7 @@ template <bool FRAMES>
 int pack_rle_launch(const char* who, const char* kernel, const int32_t* counts, const int64_t* offsets, int B, int scan_words, const BitsOut& c,
                     void* stream) {
   const size_t lds = rle_bits_lds(c.lds_words, scan_words);
-  if (lds > ANN_LDS_MAX) return pack_refuse(who, "frame too large for LDS", LA3D_ERR_UNSUPPORTED);
+  if (lds > ANN_LDS_MAX) return refuse(who, "frame too large for LDS", LA3D_ERR_UNSUPPORTED);
   allow_big_lds(reinterpret_cast<const void*>(pack_rle_bits_kernel<FRAMES>));
   hipLaunchKernelGGL(pack_rle_bits_kernel<FRAMES>, dim3(B), dim3(NT_DEC), lds, static_cast<hipStream_t>(stream), counts,
                      reinterpret_cast<const long long*>(offsets), scan_words, c);
@@ -783,7 +783,7 @@ template <bool FRAMES>
 int pack_poly_launch(const char* who, const char* kernel, const int32_t* poly_xy, const int64_t* ring_offsets, const int64_t* inst_rings, int B,
                      const BitsOut& c, void* stream) {
   const size_t lds = poly_bits_lds(c.lds_words);
-  if (lds > ANN_LDS_MAX) return pack_refuse(who, "frame too large for LDS", LA3D_ERR_UNSUPPORTED);
+  if (lds > ANN_LDS_MAX) return refuse(who, "frame too large for LDS", LA3D_ERR_UNSUPPORTED);
   allow_big_lds(reinterpret_cast<const void*>(pack_poly_bits_kernel<FRAMES>));
   hipLaunchKernelGGL(pack_poly_bits_kernel<FRAMES>, dim3(B), dim3(NT_DEC), lds, static_cast<hipStream_t>(stream), poly_xy,
                      reinterpret_cast<const long long*>(ring_offsets), reinterpret_cast<const long long*>(inst_rings), c);
@@ -854,11 +854,11 @@ int pack_masks_frames(const char* who, const void* src, int kind, float thr, con
 int crop_source(const char* who, const uint8_t* crops, int64_t crop_stride, int32_t row_pitch, int32_t pixel_step, int S, int threshold,
                 const int32_t* place, int B, CropSrc* s) {
   if (S <= 0 || pixel_step < 1 || (long long)row_pitch < (long long)S * pixel_step || threshold < 0 || threshold > 255)
-    return pack_refuse(who, "bad source (S > 0, pixel_step >= 1, row_pitch >= S * pixel_step, 0 <= threshold <= 255)");
+    return refuse(who, "bad source (S > 0, pixel_step >= 1, row_pitch >= S * pixel_step, 0 <= threshold <= 255)");
   // (the bytes of one crop: its last row ends S * pixel_step - (pixel_step - 1) bytes in)
   if (crop_stride < (long long)(S - 1) * row_pitch + (long long)(S - 1) * pixel_step + 1 || (B > 0 && crop_stride > INT64_MAX / B))
-    return pack_refuse(who, "crop_stride is smaller than a crop (or B * crop_stride overflows)");
-  if (B > 0 && (reinterpret_cast<uintptr_t>(place) & 3)) return pack_refuse(who, "place not a 4-byte aligned pointer");
+    return refuse(who, "crop_stride is smaller than a crop (or B * crop_stride overflows)");
+  if (B > 0 && (reinterpret_cast<uintptr_t>(place) & 3)) return refuse(who, "place not a 4-byte aligned pointer");
   *s = CropSrc{crops, (long long)crop_stride, row_pitch, pixel_step, S, threshold, place};
   return LA3D_SUCCESS;
 }
@@ -875,19 +875,14 @@ int pack_crop_launch(const CropSrc& src, int B, const BitsOut& c, void* stream) 
 extern "C" {
 
 int la3d_rle_decode(const int32_t* counts, const int64_t* offsets, int B, int H, int W, uint8_t* mask_out, void* stream) {
-  if ((!counts && B > 0) || !offsets || !mask_out || B < 0 || H <= 0 || W <= 0 || (long long)H * W > (1LL << 20)) {
-    set_err("la3d_rle_decode: bad argument (H*W <= 1048576)");
-    return LA3D_ERR_ARG;
-  }
+  if ((!counts && B > 0) || !offsets || !mask_out || B < 0 || H <= 0 || W <= 0 || (long long)H * W > (1LL << 20))
+    return refuse("la3d_rle_decode", "bad argument (H*W <= 1048576)");
   if (B == 0) return LA3D_SUCCESS;
   const int nwords = (H * W + 31) / 32;
   // behind the bit image: 16 words of wave totals, then the block totals of the column scan (word-aligned rows)
   const int scan_words = (W % 32 == 0) ? ((NT_DEC / (W / 32) > 2 ? NT_DEC / (W / 32) : 2) * (W / 32)) : 0;
   const size_t lds = (size_t)nwords * 4 + 64 + (size_t)scan_words * 4;
-  if (lds > 160 * 1024 - 256) {
-    set_err("la3d_rle_decode: frame too large for LDS");
-    return LA3D_ERR_UNSUPPORTED;
-  }
+  if (lds > 160 * 1024 - 256) return refuse("la3d_rle_decode", "frame too large for LDS", LA3D_ERR_UNSUPPORTED);
   allow_big_lds(reinterpret_cast<const void*>(rle_decode_kernel));
   hipLaunchKernelGGL(rle_decode_kernel, dim3(B), dim3(NT_DEC), lds, static_cast<hipStream_t>(stream), counts,
                      reinterpret_cast<const long long*>(offsets), H, W, nwords, scan_words, mask_out);
@@ -897,10 +892,8 @@ int la3d_rle_decode(const int32_t* counts, const int64_t* offsets, int B, int H,
 int la3d_poly_decode(const int32_t* poly_xy, const int64_t* ring_offsets, const int64_t* inst_rings, int B, int H, int W,
                      uint8_t* mask_out, void* stream) {
   if (((!poly_xy || !ring_offsets || !inst_rings || !mask_out) && B > 0) || B < 0 || H <= 0 || W <= 0 ||
-      (long long)H * W > (1LL << 20)) {
-    set_err("la3d_poly_decode: bad argument (H*W <= 1048576)");
-    return LA3D_ERR_ARG;
-  }
+      (long long)H * W > (1LL << 20))
+    return refuse("la3d_poly_decode", "bad argument (H*W <= 1048576)");
   if (B == 0) return LA3D_SUCCESS;
   const int nwords = (H * W + 31) / 32;
   const size_t lds = (((size_t)nwords * 4 + 15) & ~(size_t)15) + POLY_STAGE_BYTES + 64;
@@ -921,19 +914,17 @@ int la3d_pack_logits_bits(const void* logits, int dtype, int64_t plane_stride, f
                           uint32_t* bits, int64_t bits_plane_stride, void* stream) {
   const char* who = "la3d_pack_logits_bits";
   if (dtype != LA3D_DTYPE_F32 && dtype != LA3D_DTYPE_F16 && dtype != LA3D_DTYPE_BF16)
-    return pack_refuse(who, "unknown dtype (LA3D_DTYPE_F32, LA3D_DTYPE_F16 or LA3D_DTYPE_BF16)");
+    return refuse(who, "unknown dtype (LA3D_DTYPE_F32, LA3D_DTYPE_F16 or LA3D_DTYPE_BF16)");
   const int kind = dtype == LA3D_DTYPE_F32 ? PK_F32 : dtype == LA3D_DTYPE_F16 ? PK_F16 : PK_BF16;
   // (this entry alone ranks the source's alignment in front of the size rules)
-  if (B > 0 && (reinterpret_cast<uintptr_t>(logits) & pack_elem_mask(kind))) return pack_refuse(who, "logits not aligned to their element size");
+  if (B > 0 && (reinterpret_cast<uintptr_t>(logits) & pack_elem_mask(kind))) return refuse(who, "logits not aligned to their element size");
   return pack_bits(who, "pack_logits_bits_kernel", logits, kind, plane_stride, threshold, B, H, W, W_out, bits, bits_plane_stride, stream);
 }
 
 int la3d_unpack_mask_bits(const uint32_t* bits, int64_t bits_plane_stride, int B, int H, int W_in, int W, uint8_t* mask, void* stream) {
   if (B < 0 || H <= 0 || W <= 0 || W_in < W || (long long)H * W_in > (1LL << 28) || (long long)B * 64 > 0x7fffffffLL ||
-      (B > 0 && (!bits || !mask || (reinterpret_cast<uintptr_t>(bits) & 3) || bits_plane_stride < (int64_t)la3d_mask_bits_words(H, W_in)))) {
-    set_err("la3d_unpack_mask_bits: bad argument (W <= W_in, bits 4-byte aligned, bits_plane_stride >= la3d_mask_bits_words(H, W_in))");
-    return LA3D_ERR_ARG;
-  }
+      (B > 0 && (!bits || !mask || (reinterpret_cast<uintptr_t>(bits) & 3) || bits_plane_stride < (int64_t)la3d_mask_bits_words(H, W_in))))
+    return refuse("la3d_unpack_mask_bits", "bad argument (W <= W_in, bits 4-byte aligned, bits_plane_stride >= la3d_mask_bits_words(H, W_in))");
   if (B == 0) return LA3D_SUCCESS;
   const int quads = (W % 4 == 0 && (reinterpret_cast<uintptr_t>(mask) & 3) == 0) ? 1 : 0;
   const int chunks = plane_chunks(quads ? (long long)H * W / 4 : (long long)H * W);
@@ -945,14 +936,9 @@ int la3d_unpack_mask_bits(const uint32_t* bits, int64_t bits_plane_stride, int B
 int la3d_mask_stats_bits(const uint32_t* bits, int64_t bits_plane_stride, int B, int H, int W, int frame_width, int boundary,
                          int32_t* stats, void* stream) {
   if (B < 0 || H <= 0 || W <= 0 || boundary < 0 || frame_width < 0 || frame_width > W ||
-      (B > 0 && (!bits || !stats || (reinterpret_cast<uintptr_t>(bits) & 3) || bits_plane_stride < (int64_t)la3d_mask_bits_words(H, W)))) {
-    set_err("la3d_mask_stats_bits: bad argument (0 <= frame_width <= W, bits 4-byte aligned, bits_plane_stride >= la3d_mask_bits_words(H, W))");
-    return LA3D_ERR_ARG;
-  }
-  if ((long long)H * W > (1LL << 20)) {
-    set_err("la3d_mask_stats_bits: the bit image must fit LDS (H*W <= 1048576)");
-    return LA3D_ERR_UNSUPPORTED;
-  }
+      (B > 0 && (!bits || !stats || (reinterpret_cast<uintptr_t>(bits) & 3) || bits_plane_stride < (int64_t)la3d_mask_bits_words(H, W))))
+    return refuse("la3d_mask_stats_bits", "bad argument (0 <= frame_width <= W, bits 4-byte aligned, bits_plane_stride >= la3d_mask_bits_words(H, W))");
+  if ((long long)H * W > (1LL << 20)) return refuse("la3d_mask_stats_bits", "the bit image must fit LDS (H*W <= 1048576)", LA3D_ERR_UNSUPPORTED);
   if (B == 0) return LA3D_SUCCESS;
   const int nwords = (int)la3d_mask_bits_words(H, W);
   const int vec = ((reinterpret_cast<uintptr_t>(bits) & 15) == 0 && bits_plane_stride % 4 == 0) ? 1 : 0;
@@ -1035,7 +1021,7 @@ int la3d_pack_label_bits(const void* labels, int dtype, int64_t plane_stride, in
   static const PackWords say = {"bad argument (B, P >= 0, H, W > 0, W_out >= W)",
                                 "frame or batch too large (H*W_out <= 2^28, P * ceil(H*W_out / 8192) < 2^31)",
                                 "NULL labels, inst_offsets, inst_label or bits", nullptr, "label plane stride smaller than H*W", BITS_STRIDE};
-  if (dtype != LA3D_LABEL_U8 && dtype != LA3D_LABEL_U16 && dtype != LA3D_LABEL_I32 && dtype != LA3D_LABEL_RGB8) return pack_refuse(who, LABEL_DTYPE);
+  if (dtype != LA3D_LABEL_U8 && dtype != LA3D_LABEL_U16 && dtype != LA3D_LABEL_I32 && dtype != LA3D_LABEL_RGB8) return refuse(who, LABEL_DTYPE);
   const long long plane = plane_items(H, W_out);
   const int rc = pack_check(who, say, B, P, W, B > 0 && P > 0, plane > (1LL << 28) || (long long)P * ((plane + 8191) / 8192) > 0x7fffffffLL, false,
                             {{bits, 3, BITS_4}, {labels, dtype == LA3D_LABEL_I32 ? 3u : dtype == LA3D_LABEL_U16 ? 1u : 0u, "labels not aligned to their element size"},
@@ -1057,7 +1043,7 @@ int la3d_pack_label_bits_frames(const void* labels, int dtype, const la3d_frame*
   static const char* const p8 = "frames or bits_offsets not an 8-byte aligned pointer";
   static const PackWords say = {SIZES_FRAMES, "bounds or batch too large (H * roundup32(W) <= 2^28, P * ceil(H * roundup32(W) / 8192) < 2^31)",
                                 "NULL labels, frames, inst_offsets, inst_label, bits or bits_offsets", nullptr, nullptr, nullptr};
-  if (dtype != LA3D_LABEL_U8 && dtype != LA3D_LABEL_U16 && dtype != LA3D_LABEL_I32 && dtype != LA3D_LABEL_RGB8) return pack_refuse(who, LABEL_DTYPE);
+  if (dtype != LA3D_LABEL_U8 && dtype != LA3D_LABEL_U16 && dtype != LA3D_LABEL_I32 && dtype != LA3D_LABEL_RGB8) return refuse(who, LABEL_DTYPE);
   const BitsOut c = bits_out_frames(frames, P, H, W, nullptr, bits, bits_offsets, area);   // (the image of a row: inst_offsets)
   const long long words = bounds_words(H, W), chunks = (words + 255) / 256;
   const int rc = pack_check(who, say, B, P, W, B > 0 && P > 0, words > (1LL << 23) || (long long)P * chunks > 0x7fffffffLL, false,
@@ -1081,7 +1067,7 @@ int la3d_pack_logits_bits_frames(const void* logits, int dtype, float threshold,
                                  const int32_t* image_index, const int64_t* src_offsets, const int32_t* src_pitch, int B, uint32_t* bits,
                                  const int64_t* bits_offsets, int32_t* area, void* stream) {
   if (dtype != LA3D_DTYPE_F32 && dtype != LA3D_DTYPE_F16 && dtype != LA3D_DTYPE_BF16)
-    return pack_refuse("la3d_pack_logits_bits_frames", "unknown dtype (LA3D_DTYPE_F32, LA3D_DTYPE_F16 or LA3D_DTYPE_BF16)");
+    return refuse("la3d_pack_logits_bits_frames", "unknown dtype (LA3D_DTYPE_F32, LA3D_DTYPE_F16 or LA3D_DTYPE_BF16)");
   const int kind = dtype == LA3D_DTYPE_F32 ? PK_F32 : dtype == LA3D_DTYPE_F16 ? PK_F16 : PK_BF16;
   return pack_masks_frames("la3d_pack_logits_bits_frames", logits, kind, threshold, frames, P, H, W, image_index, src_offsets, src_pitch, B,
                            bits, bits_offsets, area, stream);

@@ -419,73 +419,68 @@ int cloud_bands(int B, int H, int W) {
   return nb;
 }
 
-int fail(int code, const char* who, const char* what) {
-  snprintf(g_err, sizeof(g_err), "%s: %s", who, what);
-  return code;
-}
-
 // the checks of both entries, made before any launch; on success `p` is the kernel argument and `a` the caller's block with the
 // fields it lacks zeroed
 int cloud_check(const la3d_cloud_args* args, const char* who, bool gather, la3d_cloud_args& a, CloudParams& p) {
   static_assert(sizeof(la3d_cloud_args) == 192, "la3d_cloud_args is part of the ABI");
-  if (!args || args->struct_size < (int32_t)sizeof(la3d_cloud_args)) return fail(LA3D_ERR_ARG, who, "bad struct_size");
+  if (!args || args->struct_size < (int32_t)sizeof(la3d_cloud_args)) return refuse(who, "bad struct_size");
   memcpy(&a, args, sizeof(a));   // (a longer block from a newer caller is fine)
-  if (a.B < 0 || a.H < 0 || a.W < 0 || a.P < 0 || (a.B > 0 && (a.H == 0 || a.W == 0))) return fail(LA3D_ERR_ARG, who, "negative or empty sizes (B, H, W, P)");
-  if (a.frame_width < 0 || a.frame_width > a.W) return fail(LA3D_ERR_ARG, who, "frame_width outside [0, W]");
+  if (a.B < 0 || a.H < 0 || a.W < 0 || a.P < 0 || (a.B > 0 && (a.H == 0 || a.W == 0))) return refuse(who, "negative or empty sizes (B, H, W, P)");
+  if (a.frame_width < 0 || a.frame_width > a.W) return refuse(who, "frame_width outside [0, W]");
   if (a.B == 0) {
-    if (!gather && !a.offsets) return fail(LA3D_ERR_ARG, who, "offsets is NULL");
+    if (!gather && !a.offsets) return refuse(who, "offsets is NULL");
     memset(&p, 0, sizeof(p));
     p.offsets = reinterpret_cast<long long*>(a.offsets);
     return LA3D_SUCCESS;
   }
-  if ((a.mask ? 1 : 0) + (a.mask_bits ? 1 : 0) != 1) return fail(LA3D_ERR_ARG, who, "give exactly one of mask / mask_bits");
-  if ((a.depth ? 1 : 0) + (a.depth16 ? 1 : 0) != 1) return fail(LA3D_ERR_ARG, who, "give exactly one of depth / depth16");
+  if ((a.mask ? 1 : 0) + (a.mask_bits ? 1 : 0) != 1) return refuse(who, "give exactly one of mask / mask_bits");
+  if ((a.depth ? 1 : 0) + (a.depth16 ? 1 : 0) != 1) return refuse(who, "give exactly one of depth / depth16");
   float d16_scale = 1.0f;
   int d16_hole = 0;
   const void* dplanes = a.depth;
   long long dstride = a.depth_plane_stride;
   if (a.depth16) {
     const la3d_depth16* d = a.depth16;
-    if (d->struct_size < (int32_t)sizeof(la3d_depth16)) return fail(LA3D_ERR_ARG, who, "bad struct_size of la3d_depth16");
-    if (d->dtype != LA3D_DTYPE_F16 && d->dtype != LA3D_DTYPE_U16) return fail(LA3D_ERR_ARG, who, "la3d_depth16: unknown dtype (LA3D_DTYPE_F16 or LA3D_DTYPE_U16)");
+    if (d->struct_size < (int32_t)sizeof(la3d_depth16)) return refuse(who, "bad struct_size of la3d_depth16");
+    if (d->dtype != LA3D_DTYPE_F16 && d->dtype != LA3D_DTYPE_U16) return refuse(who, "la3d_depth16: unknown dtype (LA3D_DTYPE_F16 or LA3D_DTYPE_U16)");
     if (d->dtype == LA3D_DTYPE_U16 ? (!(d->scale > 0.0f && d->scale <= 3.4028234663852886e38f) || (d->flags & ~LA3D_DEPTH_ZERO_IS_HOLE)) : d->flags != 0)
-      return fail(LA3D_ERR_ARG, who, "la3d_depth16: U16 needs a finite scale > 0 and flags LA3D_DEPTH_ZERO_IS_HOLE or 0; F16 needs flags 0");
-    if (!d->planes || (reinterpret_cast<uintptr_t>(d->planes) & 1)) return fail(LA3D_ERR_ARG, who, "la3d_depth16: planes NULL or not 2-byte aligned");
-    if (a.depth_plane_stride != 0) return fail(LA3D_ERR_ARG, who, "depth_plane_stride must be 0 with depth16 (the block carries the stride)");
+      return refuse(who, "la3d_depth16: U16 needs a finite scale > 0 and flags LA3D_DEPTH_ZERO_IS_HOLE or 0; F16 needs flags 0");
+    if (!d->planes || (reinterpret_cast<uintptr_t>(d->planes) & 1)) return refuse(who, "la3d_depth16: planes NULL or not 2-byte aligned");
+    if (a.depth_plane_stride != 0) return refuse(who, "depth_plane_stride must be 0 with depth16 (the block carries the stride)");
     if (d->dtype == LA3D_DTYPE_U16) { d16_scale = d->scale; d16_hole = (d->flags & LA3D_DEPTH_ZERO_IS_HOLE) ? 1 : 0; }
     dplanes = d->planes;
     dstride = d->plane_stride;
-  } else if (reinterpret_cast<uintptr_t>(a.depth) & 3) return fail(LA3D_ERR_ARG, who, "depth not 4-byte aligned");
-  if (dstride < 0 || a.mask_plane_stride < 0 || a.bits_plane_stride < 0) return fail(LA3D_ERR_ARG, who, "negative plane stride");
-  if (a.k_stride != 0 && a.k_stride < 9) return fail(LA3D_ERR_ARG, who, "k_stride must be 0 (shared) or >= 9");
-  if (!a.K) return fail(LA3D_ERR_ARG, who, "K is NULL");
-  if (!a.workspace || (reinterpret_cast<uintptr_t>(a.workspace) & 3)) return fail(LA3D_ERR_ARG, who, "workspace NULL or not 4-byte aligned (la3d_instance_points_workspace_bytes)");
-  if (!a.offsets) return fail(LA3D_ERR_ARG, who, "offsets is NULL");
-  if (!gather && !a.counts) return fail(LA3D_ERR_ARG, who, "counts is NULL");
+  } else if (reinterpret_cast<uintptr_t>(a.depth) & 3) return refuse(who, "depth not 4-byte aligned");
+  if (dstride < 0 || a.mask_plane_stride < 0 || a.bits_plane_stride < 0) return refuse(who, "negative plane stride");
+  if (a.k_stride != 0 && a.k_stride < 9) return refuse(who, "k_stride must be 0 (shared) or >= 9");
+  if (!a.K) return refuse(who, "K is NULL");
+  if (!a.workspace || (reinterpret_cast<uintptr_t>(a.workspace) & 3)) return refuse(who, "workspace NULL or not 4-byte aligned (la3d_instance_points_workspace_bytes)");
+  if (!a.offsets) return refuse(who, "offsets is NULL");
+  if (!gather && !a.counts) return refuse(who, "counts is NULL");
   // (capacity 0 - a batch of empty masks sized exactly - has no row to point at: points may be NULL there, no row is ever written)
-  if (gather && ((!a.points && a.capacity > 0) || !a.status)) return fail(LA3D_ERR_ARG, who, "points / status is NULL");
-  if (gather && a.capacity < 0) return fail(LA3D_ERR_ARG, who, "negative capacity");
-  if (a.mask_bits && (reinterpret_cast<uintptr_t>(a.mask_bits) & 3)) return fail(LA3D_ERR_ARG, who, "mask_bits not 4-byte aligned");
+  if (gather && ((!a.points && a.capacity > 0) || !a.status)) return refuse(who, "points / status is NULL");
+  if (gather && a.capacity < 0) return refuse(who, "negative capacity");
+  if (a.mask_bits && (reinterpret_cast<uintptr_t>(a.mask_bits) & 3)) return refuse(who, "mask_bits not 4-byte aligned");
   if (a.frames) {
-    if (a.mask) return fail(LA3D_ERR_ARG, who, "a frames call takes bit planes (mask_bits + bits_offsets), not u8 masks");
-    if (reinterpret_cast<uintptr_t>(a.frames) & 7) return fail(LA3D_ERR_ARG, who, "frames not 8-byte aligned");
-    if (!a.bits_offsets || (reinterpret_cast<uintptr_t>(a.bits_offsets) & 7)) return fail(LA3D_ERR_ARG, who, "bits_offsets NULL or not 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(a.mask_bits) & 15) return fail(LA3D_ERR_ARG, who, "mask_bits of a frames call not 16-byte aligned");
-    if (!a.image_index) return fail(LA3D_ERR_ARG, who, "image_index is required: instance n belongs to frame row image_index[n]");
-    if (dstride != 0 || a.frame_width != 0) return fail(LA3D_ERR_ARG, who, "depth plane stride and frame_width must be 0 in a frames call (the frame table says both)");
-    if (reinterpret_cast<uintptr_t>(dplanes) & (a.depth16 ? 7 : 15)) return fail(LA3D_ERR_ARG, who, "the depth buffer of a frames call must be 16-byte (16-bit planes: 8-byte) aligned");
+    if (a.mask) return refuse(who, "a frames call takes bit planes (mask_bits + bits_offsets), not u8 masks");
+    if (reinterpret_cast<uintptr_t>(a.frames) & 7) return refuse(who, "frames not 8-byte aligned");
+    if (!a.bits_offsets || (reinterpret_cast<uintptr_t>(a.bits_offsets) & 7)) return refuse(who, "bits_offsets NULL or not 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(a.mask_bits) & 15) return refuse(who, "mask_bits of a frames call not 16-byte aligned");
+    if (!a.image_index) return refuse(who, "image_index is required: instance n belongs to frame row image_index[n]");
+    if (dstride != 0 || a.frame_width != 0) return refuse(who, "depth plane stride and frame_width must be 0 in a frames call (the frame table says both)");
+    if (reinterpret_cast<uintptr_t>(dplanes) & (a.depth16 ? 7 : 15)) return refuse(who, "the depth buffer of a frames call must be 16-byte (16-bit planes: 8-byte) aligned");
   } else {
-    if (a.bits_offsets) return fail(LA3D_ERR_ARG, who, "bits_offsets without frames");
+    if (a.bits_offsets) return refuse(who, "bits_offsets without frames");
     const long long HW = (long long)a.H * a.W;
-    if (a.mask && a.mask_plane_stride != 0 && a.mask_plane_stride < HW) return fail(LA3D_ERR_ARG, who, "mask_plane_stride below H*W");
-    if (a.mask_bits && a.bits_plane_stride != 0 && a.bits_plane_stride < (HW + 31) / 32) return fail(LA3D_ERR_ARG, who, "bits_plane_stride below the words of a plane");
-    if (dstride != 0 && dstride < HW) return fail(LA3D_ERR_ARG, who, "depth plane stride below H*W");
+    if (a.mask && a.mask_plane_stride != 0 && a.mask_plane_stride < HW) return refuse(who, "mask_plane_stride below H*W");
+    if (a.mask_bits && a.bits_plane_stride != 0 && a.bits_plane_stride < (HW + 31) / 32) return refuse(who, "bits_plane_stride below the words of a plane");
+    if (dstride != 0 && dstride < HW) return refuse(who, "depth plane stride below H*W");
   }
   const int Wb = a.frames ? ((a.W + 31) & ~31) : a.W;   // (frames: W bounds the pitch)
-  if (Wb > BAND_PIX) return fail(LA3D_ERR_UNSUPPORTED, who, "W > 65536: one row does not fit a band's bit image in LDS");
-  if ((long long)a.H * Wb > 0x7fffffffLL) return fail(LA3D_ERR_UNSUPPORTED, who, "H * W >= 2^31: pixel indices are int32");
+  if (Wb > BAND_PIX) return refuse(who, "W > 65536: one row does not fit a band's bit image in LDS", LA3D_ERR_UNSUPPORTED);
+  if ((long long)a.H * Wb > 0x7fffffffLL) return refuse(who, "H * W >= 2^31: pixel indices are int32", LA3D_ERR_UNSUPPORTED);
   const int nb = cloud_bands(a.B, a.H, Wb);
-  if ((long long)a.B * nb > 0x7fffffffLL) return fail(LA3D_ERR_UNSUPPORTED, who, "B x bands >= 2^31: beyond one grid");
+  if ((long long)a.B * nb > 0x7fffffffLL) return refuse(who, "B x bands >= 2^31: beyond one grid", LA3D_ERR_UNSUPPORTED);
   memset(&p, 0, sizeof(p));
   p.B = a.B; p.H = a.H; p.W = a.frames ? Wb : a.W; p.fw = a.frame_width ? a.frame_width : a.W; p.nb = nb; p.P = a.P;
   p.k_stride = a.k_stride; p.d16_hole = d16_hole; p.d16_scale = d16_scale;

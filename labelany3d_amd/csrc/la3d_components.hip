@@ -1,6 +1,6 @@
 // la3d_components.hip - connected components on bit planes (include/la3d.h "connected components on bit planes"):
 // la3d_components_bits and its frames form, la3d_components_bits_frames: kernels and C entries in one unit.  From la3d_bitplanes.hpp
-// come the frames prologue of a workgroup, pack_refuse, at() and the wording shared with the packers.
+// come the frames prologue of a workgroup, at() and the wording shared with the packers.
 #include <cstdint>
 #include <cstddef>
 
@@ -377,33 +377,33 @@ size_t la3d_components_workspace_bytes(int B, int H, int max_runs) {
 
 int la3d_components_bits(const la3d_components_args* args) {
   const char* who = "la3d_components_bits";
-  if (!args || args->struct_size != (int32_t)sizeof(la3d_components_args)) return pack_refuse(who, "NULL block or bad struct_size");
+  if (!args || args->struct_size != (int32_t)sizeof(la3d_components_args)) return refuse(who, "NULL block or bad struct_size");
   const la3d_components_args& g = *args;
-  if (g.B < 0 || g.H <= 0 || g.W <= 0) return pack_refuse(who, "bad argument (B >= 0, H, W > 0)");
-  if (g.frame_width < 0 || g.frame_width > g.W) return pack_refuse(who, "frame_width must lie in [0, W] (0 = W)");
-  if (g.connectivity != 4 && g.connectivity != 8) return pack_refuse(who, "connectivity must be 4 or 8");
-  if (g.largest != 0 && g.largest != 1) return pack_refuse(who, "largest must be 0 or 1");
-  if (g.min_area < 0) return pack_refuse(who, "min_area must not be negative");
-  if (g.max_runs < 1) return pack_refuse(who, "max_runs must be at least 1");
-  if (g.max_components < 0) return pack_refuse(who, "max_components must not be negative");
-  if (g.components && g.max_components == 0) return pack_refuse(who, "components needs max_components > 0");
-  if (!g.out_bits && !g.stats && !g.components) return pack_refuse(who, "nothing to do: out_bits, stats and components are all NULL");
-  if ((long long)g.H * g.W > 1048576) return pack_refuse(who, "H * W must not exceed 1048576", LA3D_ERR_UNSUPPORTED);
-  if (g.max_runs > COMP_MAX_RUNS) return pack_refuse(who, "max_runs must not exceed 524288 (a plane of 1048576 pixels has no more)", LA3D_ERR_UNSUPPORTED);
+  if (g.B < 0 || g.H <= 0 || g.W <= 0) return refuse(who, "bad argument (B >= 0, H, W > 0)");
+  if (g.frame_width < 0 || g.frame_width > g.W) return refuse(who, "frame_width must lie in [0, W] (0 = W)");
+  if (g.connectivity != 4 && g.connectivity != 8) return refuse(who, "connectivity must be 4 or 8");
+  if (g.largest != 0 && g.largest != 1) return refuse(who, "largest must be 0 or 1");
+  if (g.min_area < 0) return refuse(who, "min_area must not be negative");
+  if (g.max_runs < 1) return refuse(who, "max_runs must be at least 1");
+  if (g.max_components < 0) return refuse(who, "max_components must not be negative");
+  if (g.components && g.max_components == 0) return refuse(who, "components needs max_components > 0");
+  if (!g.out_bits && !g.stats && !g.components) return refuse(who, "nothing to do: out_bits, stats and components are all NULL");
+  if ((long long)g.H * g.W > 1048576) return refuse(who, "H * W must not exceed 1048576", LA3D_ERR_UNSUPPORTED);
+  if (g.max_runs > COMP_MAX_RUNS) return refuse(who, "max_runs must not exceed 524288 (a plane of 1048576 pixels has no more)", LA3D_ERR_UNSUPPORTED);
   if (g.B == 0) return LA3D_SUCCESS;
-  if (!g.mask_bits || !g.workspace) return pack_refuse(who, "mask_bits and workspace must not be NULL");
+  if (!g.mask_bits || !g.workspace) return refuse(who, "mask_bits and workspace must not be NULL");
   if ((at(g.mask_bits) | at(g.out_bits) | at(g.stats) | at(g.components) | at(g.workspace)) & 3)
-    return pack_refuse(who, "mask_bits, out_bits, stats, components or workspace not a 4-byte aligned pointer");
+    return refuse(who, "mask_bits, out_bits, stats, components or workspace not a 4-byte aligned pointer");
   const long long words = (long long)la3d_mask_bits_words(g.H, g.W);
   const long long stride = g.bits_plane_stride ? g.bits_plane_stride : words;
   const long long out_stride = g.out_plane_stride ? g.out_plane_stride : words;
-  if (stride < words) return pack_refuse(who, "bits_plane_stride is smaller than la3d_mask_bits_words(H, W)");
+  if (stride < words) return refuse(who, "bits_plane_stride is smaller than la3d_mask_bits_words(H, W)");
   if (g.out_bits) {
-    if (out_stride < words) return pack_refuse(who, "out_plane_stride is smaller than la3d_mask_bits_words(H, W)");
+    if (out_stride < words) return refuse(who, "out_plane_stride is smaller than la3d_mask_bits_words(H, W)");
     // a word of the output is gathered from runs listed before: the call does not work in place
     const uintptr_t i0 = at(g.mask_bits), i1 = i0 + (uintptr_t)g.B * (uintptr_t)stride * 4;
     const uintptr_t o0 = at(g.out_bits), o1 = o0 + (uintptr_t)g.B * (uintptr_t)out_stride * 4;
-    if (i0 < o1 && o0 < i1) return pack_refuse(who, "the input planes and the output planes overlap");
+    if (i0 < o1 && o0 < i1) return refuse(who, "the input planes and the output planes overlap");
   }
   CompArgs a = {};
   a.bits = g.mask_bits; a.stride = stride; a.out = g.out_bits; a.out_stride = out_stride;
@@ -424,34 +424,34 @@ int la3d_components_bits(const la3d_components_args* args) {
 
 int la3d_components_bits_frames(const la3d_components_frames_args* args) {
   const char* who = "la3d_components_bits_frames";
-  if (!args || args->struct_size != (int32_t)sizeof(la3d_components_frames_args)) return pack_refuse(who, "NULL block or bad struct_size");
+  if (!args || args->struct_size != (int32_t)sizeof(la3d_components_frames_args)) return refuse(who, "NULL block or bad struct_size");
   const la3d_components_frames_args& g = *args;
-  if (g.B < 0 || g.P < 0 || g.H <= 0 || g.W <= 0) return pack_refuse(who, SIZES_FRAMES);
-  if (g.connectivity != 4 && g.connectivity != 8) return pack_refuse(who, "connectivity must be 4 or 8");
-  if (g.largest != 0 && g.largest != 1) return pack_refuse(who, "largest must be 0 or 1");
-  if (g.min_area < 0) return pack_refuse(who, "min_area must not be negative");
-  if (g.max_runs < 1) return pack_refuse(who, "max_runs must be at least 1");
-  if (g.max_components < 0) return pack_refuse(who, "max_components must not be negative");
-  if (g.components && g.max_components == 0) return pack_refuse(who, "components needs max_components > 0");
-  if (!g.out_bits && !g.stats && !g.components) return pack_refuse(who, "nothing to do: out_bits, stats and components are all NULL");
-  if (g.reserved[0] != 0 || g.reserved[1] != 0) return pack_refuse(who, "reserved must be 0");
-  if (g.bits_words < 0 || (g.out_bits && g.out_words < 0)) return pack_refuse(who, "bits_words and out_words must not be negative");
-  if ((at(g.bits) | at(g.out_bits)) & 15) return pack_refuse(who, "bits or out_bits not a 16-byte aligned pointer");
-  if ((at(g.bits_offsets) | at(g.out_offsets) | at(g.frames)) & 7) return pack_refuse(who, "bits_offsets, out_offsets or frames not an 8-byte aligned pointer");
+  if (g.B < 0 || g.P < 0 || g.H <= 0 || g.W <= 0) return refuse(who, SIZES_FRAMES);
+  if (g.connectivity != 4 && g.connectivity != 8) return refuse(who, "connectivity must be 4 or 8");
+  if (g.largest != 0 && g.largest != 1) return refuse(who, "largest must be 0 or 1");
+  if (g.min_area < 0) return refuse(who, "min_area must not be negative");
+  if (g.max_runs < 1) return refuse(who, "max_runs must be at least 1");
+  if (g.max_components < 0) return refuse(who, "max_components must not be negative");
+  if (g.components && g.max_components == 0) return refuse(who, "components needs max_components > 0");
+  if (!g.out_bits && !g.stats && !g.components) return refuse(who, "nothing to do: out_bits, stats and components are all NULL");
+  if (g.reserved[0] != 0 || g.reserved[1] != 0) return refuse(who, "reserved must be 0");
+  if (g.bits_words < 0 || (g.out_bits && g.out_words < 0)) return refuse(who, "bits_words and out_words must not be negative");
+  if ((at(g.bits) | at(g.out_bits)) & 15) return refuse(who, "bits or out_bits not a 16-byte aligned pointer");
+  if ((at(g.bits_offsets) | at(g.out_offsets) | at(g.frames)) & 7) return refuse(who, "bits_offsets, out_offsets or frames not an 8-byte aligned pointer");
   if ((at(g.stats) | at(g.components) | at(g.workspace) | at(g.image_index)) & 3)
-    return pack_refuse(who, "stats, components, workspace or image_index not a 4-byte aligned pointer");
+    return refuse(who, "stats, components, workspace or image_index not a 4-byte aligned pointer");
   if (g.bits && g.out_bits) {   // a word of the output is gathered from runs listed before: the call does not work in place
     const uintptr_t i0 = at(g.bits), i1 = i0 + (uintptr_t)g.bits_words * 4, o0 = at(g.out_bits), o1 = o0 + (uintptr_t)g.out_words * 4;
-    if (i0 < o1 && o0 < i1) return pack_refuse(who, "the input buffer and the output buffer overlap");
+    if (i0 < o1 && o0 < i1) return refuse(who, "the input buffer and the output buffer overlap");
   }
   if (g.B > 0) {
     if (!g.bits || !g.bits_offsets || !g.image_index || !g.workspace || (!g.frames && g.P > 0))
-      return pack_refuse(who, "NULL bits, bits_offsets, image_index, workspace or frames");
-    if (g.out_bits && !g.out_offsets) return pack_refuse(who, "out_offsets must not be NULL with out_bits");
+      return refuse(who, "NULL bits, bits_offsets, image_index, workspace or frames");
+    if (g.out_bits && !g.out_offsets) return refuse(who, "out_offsets must not be NULL with out_bits");
   }
   if (bounds_words(g.H, g.W) * 32 > 1048576)
-    return pack_refuse(who, "the bounds' H * roundup32(W) must not exceed 1048576", LA3D_ERR_UNSUPPORTED);
-  if (g.max_runs > COMP_MAX_RUNS) return pack_refuse(who, "max_runs must not exceed 524288 (a plane of 1048576 pixels has no more)", LA3D_ERR_UNSUPPORTED);
+    return refuse(who, "the bounds' H * roundup32(W) must not exceed 1048576", LA3D_ERR_UNSUPPORTED);
+  if (g.max_runs > COMP_MAX_RUNS) return refuse(who, "max_runs must not exceed 524288 (a plane of 1048576 pixels has no more)", LA3D_ERR_UNSUPPORTED);
   if (g.B == 0) return LA3D_SUCCESS;
   CompArgs a = {};
   a.bits = g.bits; a.out = g.out_bits;

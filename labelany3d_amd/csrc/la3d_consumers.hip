@@ -599,19 +599,15 @@ extern "C" {
 int la3d_masked_ratio_median(const float* num, int64_t num_plane_stride, const int32_t* image_index, const float* den,
                              const uint8_t* mask_a, const uint8_t* mask_b, int B, int H, int W, float* median,
                              int32_t* count, void* stream) {
-  if (!num || !den || !mask_a || !median || !count || B < 0 || H <= 0 || W <= 0 || num_plane_stride < 0) {
-    set_err("la3d_masked_ratio_median: bad argument (null pointer, negative size or stride)");
-    return LA3D_ERR_ARG;
-  }
+  if (!num || !den || !mask_a || !median || !count || B < 0 || H <= 0 || W <= 0 || num_plane_stride < 0)
+    return refuse("la3d_masked_ratio_median", "bad argument (null pointer, negative size or stride)");
   if (B == 0) return LA3D_SUCCESS;
   // ONE size limit, from the LDS the kernel needs: bit image + chunk list + key buffer in one CU's 160 KiB (about 819 k pixels)
   const long long HWl = (long long)H * W;
   const long long nwl = (HWl + 31) / 32;
   const long long ldsl = ((nwl + 3) & ~3LL) * 4 + (long long)(RM_CAP + 1024 + 256 + 16) * 4 + ((HWl + 63) / 64) * 2 + 16;
-  if (ldsl > 160 * 1024) {
-    set_err("la3d_masked_ratio_median: frame too large for the LDS bit image (H*W up to about 819200)");
-    return LA3D_ERR_UNSUPPORTED;
-  }
+  if (ldsl > 160 * 1024)
+    return refuse("la3d_masked_ratio_median", "frame too large for the LDS bit image (H*W up to about 819200)", LA3D_ERR_UNSUPPORTED);
   const int HW = (int)HWl, nwords = (int)nwl;
   const size_t lds = (size_t)ldsl;
   allow_big_lds(reinterpret_cast<const void*>(ratio_median_kernel));
@@ -629,10 +625,8 @@ int la3d_align_select_batch(const float* relative, const float* metric, const ui
                             float max_valid_depth, float* relative_out, float* metric_out, int64_t* counts, void* workspace,
                             void* stream) {
   if (P < 0 || P > 65535 || n < 0 || (P > 0 && (!counts || !workspace)) ||
-      (P > 0 && n > 0 && (!relative || !metric || !relative_out || !metric_out))) {
-    set_err("la3d_align_select_batch: bad argument (P <= 65535)");
-    return LA3D_ERR_ARG;
-  }
+      (P > 0 && n > 0 && (!relative || !metric || !relative_out || !metric_out)))
+    return refuse("la3d_align_select_batch", "bad argument (P <= 65535)");
   if (P == 0) return LA3D_SUCCESS;
   hipStream_t s = static_cast<hipStream_t>(stream);
   long long* tile_counts = static_cast<long long*>(workspace);   // [P][nb + 1]
@@ -649,19 +643,14 @@ int la3d_align_select_batch(const float* relative, const float* metric, const ui
 
 int la3d_align_select(const float* relative, const float* metric, const uint8_t* mask, int64_t n, float max_valid_depth,
                       float* relative_out, float* metric_out, int64_t* count, void* workspace, void* stream) {
-  if (n < 0 || !count || !workspace || (n > 0 && (!relative || !metric || !relative_out || !metric_out))) {
-    set_err("la3d_align_select: bad argument");
-    return LA3D_ERR_ARG;
-  }
+  if (n < 0 || !count || !workspace || (n > 0 && (!relative || !metric || !relative_out || !metric_out)))
+    return refuse("la3d_align_select", "bad argument");
   return la3d_align_select_batch(relative, metric, mask, 1, n, max_valid_depth, relative_out, metric_out, count, workspace, stream);
 }
 
 int la3d_align_apply(const float* relative, const uint8_t* mask, int64_t n, float coef, float intercept, float fill,
                      float* out, void* stream) {
-  if (n < 0 || (n > 0 && (!relative || !out))) {
-    set_err("la3d_align_apply: bad argument");
-    return LA3D_ERR_ARG;
-  }
+  if (n < 0 || (n > 0 && (!relative || !out))) return refuse("la3d_align_apply", "bad argument");
   if (n == 0) return LA3D_SUCCESS;
   hipLaunchKernelGGL(align_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      relative, mask, (long long)n, coef, intercept, fill, out);
@@ -671,10 +660,8 @@ int la3d_align_apply(const float* relative, const uint8_t* mask, int64_t n, floa
 int la3d_unproject_matches(const float* depth, int H, int W, const double* uv, int N, double fx, double fy, double cx,
                            double cy, int use_flip, double flip, const double* R9, const double* T3, double* out,
                            int32_t* valid, void* stream) {
-  if (!depth || (!uv && N > 0) || !out || !valid || N < 0 || H <= 0 || W <= 0 || (R9 == nullptr) != (T3 == nullptr)) {
-    set_err("la3d_unproject_matches: bad argument");
-    return LA3D_ERR_ARG;
-  }
+  if (!depth || (!uv && N > 0) || !out || !valid || N < 0 || H <= 0 || W <= 0 || (R9 == nullptr) != (T3 == nullptr))
+    return refuse("la3d_unproject_matches", "bad argument");
   if (N == 0) return LA3D_SUCCESS;
   MatchParams p;
   p.fx = fx; p.fy = fy; p.cx = cx; p.cy = cy; p.flip = flip; p.use_flip = use_flip; p.H = H; p.W = W; p.N = N;
@@ -688,10 +675,7 @@ int la3d_unproject_matches(const float* depth, int H, int W, const double* uv, i
 
 int la3d_project_boxes(const double* records, const double* K, int32_t k_stride, const int32_t* image_index, int B,
                        double width, double height, double* out, void* stream) {
-  if ((!records && B > 0) || !K || !out || B < 0 || (k_stride != 0 && k_stride < 9)) {
-    set_err("la3d_project_boxes: bad argument");
-    return LA3D_ERR_ARG;
-  }
+  if ((!records && B > 0) || !K || !out || B < 0 || (k_stride != 0 && k_stride < 9)) return refuse("la3d_project_boxes", "bad argument");
   if (B == 0) return LA3D_SUCCESS;
   hipLaunchKernelGGL(project_boxes_kernel, dim3((B + 127) / 128), dim3(128), 0, static_cast<hipStream_t>(stream), records, K,
                      k_stride, image_index, B, width, height, out);
@@ -699,10 +683,7 @@ int la3d_project_boxes(const double* records, const double* K, int32_t k_stride,
 }
 
 int la3d_iou_matrix(const double* boxes_a, int na, const double* boxes_b, int nb, double* out, void* stream) {
-  if (na < 0 || nb < 0 || ((!boxes_a || !boxes_b || !out) && na > 0 && nb > 0)) {
-    set_err("la3d_iou_matrix: bad argument");
-    return LA3D_ERR_ARG;
-  }
+  if (na < 0 || nb < 0 || ((!boxes_a || !boxes_b || !out) && na > 0 && nb > 0)) return refuse("la3d_iou_matrix", "bad argument");
   if (na == 0 || nb == 0) return LA3D_SUCCESS;
   const long long n = (long long)na * nb;
   hipLaunchKernelGGL(iou_matrix_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),

@@ -74,20 +74,13 @@ extern "C" {
 
 int la3d_pack_depth16(const float* depth, int64_t plane_stride, int P, int H, int W, int W_out, int dtype, float scale, void* out,
                       int64_t out_plane_stride, void* stream) {
-  if (dtype != LA3D_DTYPE_F16 && dtype != LA3D_DTYPE_U16) {
-    set_err("la3d_pack_depth16: unknown dtype (LA3D_DTYPE_F16 or LA3D_DTYPE_U16)");
-    return LA3D_ERR_ARG;
-  }
-  if (dtype == LA3D_DTYPE_U16 && !(scale > 0.0f && scale <= 3.4028234663852886e38f)) {
-    set_err("la3d_pack_depth16: scale must be finite and > 0");
-    return LA3D_ERR_ARG;
-  }
+  if (dtype != LA3D_DTYPE_F16 && dtype != LA3D_DTYPE_U16) return refuse("la3d_pack_depth16", "unknown dtype (LA3D_DTYPE_F16 or LA3D_DTYPE_U16)");
+  if (dtype == LA3D_DTYPE_U16 && !(scale > 0.0f && scale <= 3.4028234663852886e38f))
+    return refuse("la3d_pack_depth16", "scale must be finite and > 0");
   if (P < 0 || H <= 0 || W <= 0 || W_out < W || (long long)H * W_out > (1LL << 28) || plane_stride < 0 ||
       (P > 0 && (!depth || !out || (reinterpret_cast<uintptr_t>(depth) & 3) || (reinterpret_cast<uintptr_t>(out) & 1))) ||
-      (P > 1 && (plane_stride < (long long)H * W || out_plane_stride < (long long)H * W_out))) {
-    set_err("la3d_pack_depth16: bad argument (W_out >= W, plane strides >= the planes, depth 4-byte and out 2-byte aligned)");
-    return LA3D_ERR_ARG;
-  }
+      (P > 1 && (plane_stride < (long long)H * W || out_plane_stride < (long long)H * W_out)))
+    return refuse("la3d_pack_depth16", "bad argument (W_out >= W, plane strides >= the planes, depth 4-byte and out 2-byte aligned)");
   if (P == 0) return LA3D_SUCCESS;
   const int vec = (W_out % 8 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (P == 1 || out_plane_stride % 8 == 0)) ? 1 : 0;
   const int blocks = grid_for((long long)P * H * ((W_out + 7) / 8));
@@ -103,25 +96,16 @@ int la3d_pack_depth16(const float* depth, int64_t plane_stride, int P, int H, in
 }
 
 int la3d_unpack_depth16(const la3d_depth16* src, int P, int H, int W_in, int W, float* out, void* stream) {
-  if (!src || src->struct_size < (int32_t)sizeof(la3d_depth16)) {
-    set_err("la3d_unpack_depth16: bad struct_size");
-    return LA3D_ERR_ARG;
-  }
-  if (src->dtype != LA3D_DTYPE_F16 && src->dtype != LA3D_DTYPE_U16) {
-    set_err("la3d_unpack_depth16: unknown dtype (LA3D_DTYPE_F16 or LA3D_DTYPE_U16)");
-    return LA3D_ERR_ARG;
-  }
+  if (!src || src->struct_size < (int32_t)sizeof(la3d_depth16)) return refuse("la3d_unpack_depth16", "bad struct_size");
+  if (src->dtype != LA3D_DTYPE_F16 && src->dtype != LA3D_DTYPE_U16)
+    return refuse("la3d_unpack_depth16", "unknown dtype (LA3D_DTYPE_F16 or LA3D_DTYPE_U16)");
   if (src->dtype == LA3D_DTYPE_U16 ? (!(src->scale > 0.0f && src->scale <= 3.4028234663852886e38f) || (src->flags & ~LA3D_DEPTH_ZERO_IS_HOLE))
-                                   : src->flags != 0) {
-    set_err("la3d_unpack_depth16: U16 needs a finite scale > 0 and flags LA3D_DEPTH_ZERO_IS_HOLE or 0; F16 needs flags 0");
-    return LA3D_ERR_ARG;
-  }
+                                   : src->flags != 0)
+    return refuse("la3d_unpack_depth16", "U16 needs a finite scale > 0 and flags LA3D_DEPTH_ZERO_IS_HOLE or 0; F16 needs flags 0");
   if (P < 0 || H <= 0 || W <= 0 || W_in < W || (long long)H * W_in > (1LL << 28) || src->plane_stride < 0 ||
       (P > 0 && (!src->planes || !out || (reinterpret_cast<uintptr_t>(src->planes) & 1))) ||
-      (P > 1 && src->plane_stride != 0 && src->plane_stride < (long long)H * W_in)) {
-    set_err("la3d_unpack_depth16: bad argument (W <= W_in, plane_stride 0 or >= H*W_in, planes 2-byte aligned)");
-    return LA3D_ERR_ARG;
-  }
+      (P > 1 && src->plane_stride != 0 && src->plane_stride < (long long)H * W_in))
+    return refuse("la3d_unpack_depth16", "bad argument (W <= W_in, plane_stride 0 or >= H*W_in, planes 2-byte aligned)");
   if (P == 0) return LA3D_SUCCESS;
   const int blocks = grid_for((long long)P * H * W);
   hipStream_t s = static_cast<hipStream_t>(stream);

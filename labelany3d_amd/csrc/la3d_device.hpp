@@ -10,6 +10,7 @@
 #include <utility>
 #include <vector>
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -27,7 +28,22 @@ constexpr double PI_2 = 1.57079632679489661923;
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));  // native vector: usable with nontemporal builtins
 
 extern thread_local char g_err[256];
-inline void set_err(const char* msg) { snprintf(g_err, sizeof(g_err), "%s", msg); }
+// how every C entry refuses a call: la3d_last_error() = "who: what", and the code to return
+inline int refuse(const char* who, const char* what, int code = LA3D_ERR_ARG) {
+  snprintf(g_err, sizeof(g_err), "%s: %s", who, what);
+  return code;
+}
+
+// la3d_fit_args as first published: every field up to `stream`.  No entry takes a shorter block (each refuses it under its own name);
+// a longer one from a newer caller is fine, and the fields a block lacks are taken as zero.
+constexpr int32_t FIT_ARGS_V1_SIZE = (int32_t)offsetof(la3d_fit_args, area_hint);
+inline bool fit_args_size_ok(const la3d_fit_args* args) { return args && args->struct_size >= FIT_ARGS_V1_SIZE; }
+inline la3d_fit_args fit_args_copy(const la3d_fit_args* args) {   // (args has passed fit_args_size_ok)
+  la3d_fit_args a;
+  memset(&a, 0, sizeof(a));
+  memcpy(&a, args, (size_t)args->struct_size < sizeof(a) ? (size_t)args->struct_size : sizeof(a));
+  return a;
+}
 
 // Process defaults of the scheduling decisions, read from the environment ONCE (config(), la3d.hip) and immutable afterwards:
 // the hot path of the C-ABI never calls getenv.  Measurement scripts set the variables before the first call; a caller that

@@ -582,10 +582,7 @@ namespace la3d {
 int LA3D_INSTANCE_FIT(KParams p, const CallFacts& f, hipStream_t s, void* workspace, const char* who) {
   const int H = p.H, W = p.W, B = p.B;
   const bool vec = f.vec, ldsmask = f.ldsmask;
-  if (f.sample && !ldsmask) {
-    snprintf(g_err, sizeof(g_err), "%s: reference-subsample mode needs the bit image in LDS (H*W <= 1048576)", who);
-    return LA3D_ERR_UNSUPPORTED;
-  }
+  if (f.sample && !ldsmask) return refuse(who, "reference-subsample mode needs the bit image in LDS (H*W <= 1048576)", LA3D_ERR_UNSUPPORTED);
   // LDS per workgroup: bit image + Shared (f.lds), and behind them ONE area that the tile list, the rank prefix of the subsample mode
   // (one word per 32-word block of the bit image) and the polygon side stage share
   const size_t blocks = f.sample ? (size_t)rank_prefix_bytes(p.nwords) : 0;
@@ -598,10 +595,7 @@ int LA3D_INSTANCE_FIT(KParams p, const CallFacts& f, hipStream_t s, void* worksp
   p.tiles_per_wave = (p.ntx * p.nty + NWAVE - 1) / NWAVE;
   const bool tiled_frame = ldsmask && vec && W % 32 == 0 && p.ntx <= 255 && p.nty <= 255;
   if (f.sample) {
-    if (lds_with(0) > 160 * 1024 - 256) {
-      snprintf(g_err, sizeof(g_err), "%s: reference-subsample mode: frame too large for LDS", who);
-      return LA3D_ERR_UNSUPPORTED;
-    }
+    if (lds_with(0) > 160 * 1024 - 256) return refuse(who, "reference-subsample mode: frame too large for LDS", LA3D_ERR_UNSUPPORTED);
     if (f.method == LA3D_METHOD_CONVEX_HULL) {   // every instance goes the sampled way: no tile list
       p.geo = static_cast<double*>(f.hull_area);
       return vec ? launch_hull<true, true>(p, lds_with(0), s) : launch_hull<false, true>(p, lds_with(0), s);
@@ -616,11 +610,9 @@ int LA3D_INSTANCE_FIT(KParams p, const CallFacts& f, hipStream_t s, void* worksp
         return launch_fit<true, true, true, true>(p, lds_with((size_t)cap * 2), s);
       }
     }
-    if (f.frames) {
-      snprintf(g_err, sizeof(g_err), "%s: reference-subsample mode: bounds outside the tiled form: H <= 2040, W <= 8160, and bit image + rank "
-               "prefix + 64 tile-list entries within one workgroup's LDS (160 KiB)", who);
-      return LA3D_ERR_UNSUPPORTED;
-    }
+    if (f.frames)
+      return refuse(who, "reference-subsample mode: bounds outside the tiled form: H <= 2040, W <= 8160, and bit image + rank "
+                         "prefix + 64 tile-list entries within one workgroup's LDS (160 KiB)", LA3D_ERR_UNSUPPORTED);
     return vec ? launch_fit<true, true, true>(p, lds_with(0), s) : launch_fit<false, true, true>(p, lds_with(0), s);
   }
   if (tiled_frame) {
@@ -648,11 +640,9 @@ int LA3D_INSTANCE_FIT(KParams p, const CallFacts& f, hipStream_t s, void* worksp
       return launch_fit<true, true, false, true>(p, lds, s, workspace);
     }
   }
-  if (f.frames) {
-    snprintf(g_err, sizeof(g_err), "%s: bounds outside the tiled form: H <= 2040, W <= 8160, and bit image + 64 tile-list entries within one "
-             "workgroup's LDS (160 KiB)", who);
-    return LA3D_ERR_UNSUPPORTED;
-  }
+  if (f.frames)
+    return refuse(who, "bounds outside the tiled form: H <= 2040, W <= 8160, and bit image + 64 tile-list entries within one "
+                       "workgroup's LDS (160 KiB)", LA3D_ERR_UNSUPPORTED);
   if (f.method == LA3D_METHOD_CONVEX_HULL) {
     // full-mask hull on a frame outside the tiled vector path: no per-column structure to take the hull from - every instance is
     // refused (LA3D_BOX_UNSUPPORTED); reference-subsample mode (sample_idx) covers such frames

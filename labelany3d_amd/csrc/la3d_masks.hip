@@ -397,10 +397,7 @@ extern "C" {
 
 int la3d_unproject(const float* depth, const double* K9, const double* Rt12, int H, int W, void* out,
                    int out_is_f64, void* stream) {
-  if (!depth || !K9 || !out || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL / 4) {
-    set_err("la3d_unproject: bad argument");
-    return LA3D_ERR_ARG;
-  }
+  if (!depth || !K9 || !out || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL / 4) return refuse("la3d_unproject", "bad argument");
   UnprojParams p;
   inv3_host(K9, p.Kinv);
   p.has_rt = Rt12 != nullptr;
@@ -418,10 +415,8 @@ int la3d_unproject(const float* depth, const double* K9, const double* Rt12, int
 int la3d_unproject_batch(const float* depth, const double* K, int32_t k_stride, const double* Rt12, int P, int H, int W, void* out,
                          int out_is_f64, void* stream) {
   if (!depth || !K || !out || P < 0 || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL / 4 || (k_stride != 0 && k_stride < 9) ||
-      P > 65535) {
-    set_err("la3d_unproject_batch: bad argument (P <= 65535)");
-    return LA3D_ERR_ARG;
-  }
+      P > 65535)
+    return refuse("la3d_unproject_batch", "bad argument (P <= 65535)");
   if (P == 0) return LA3D_SUCCESS;
   UnprojParams p;
   for (int i = 0; i < 9; ++i) p.Kinv[i] = 0.0;
@@ -445,10 +440,8 @@ int la3d_unproject_batch(const float* depth, const double* K, int32_t k_stride, 
 }
 
 int la3d_pad_rows(const float* src, int64_t rows, int W, int Wp, float* dst, void* stream) {
-  if (rows < 0 || W <= 0 || Wp < W || Wp % 4 != 0 || (rows > 0 && (!src || !dst)) || (reinterpret_cast<uintptr_t>(dst) & 15)) {
-    set_err("la3d_pad_rows: bad argument (Wp >= W, Wp % 4 == 0, dst 16-byte aligned)");
-    return LA3D_ERR_ARG;
-  }
+  if (rows < 0 || W <= 0 || Wp < W || Wp % 4 != 0 || (rows > 0 && (!src || !dst)) || (reinterpret_cast<uintptr_t>(dst) & 15))
+    return refuse("la3d_pad_rows", "bad argument (Wp >= W, Wp % 4 == 0, dst 16-byte aligned)");
   if (rows == 0) return LA3D_SUCCESS;
   const long long total = (long long)rows * (Wp / 4);
   const long long want = (total + 255) / 256;
@@ -458,10 +451,7 @@ int la3d_pad_rows(const float* src, int64_t rows, int W, int Wp, float* dst, voi
 }
 
 int la3d_mask_counts(const uint8_t* mask, int B, int H, int W, int32_t* counts, void* stream) {
-  if (!mask || !counts || B < 0 || H <= 0 || W <= 0) {
-    set_err("la3d_mask_counts: bad argument");
-    return LA3D_ERR_ARG;
-  }
+  if (!mask || !counts || B < 0 || H <= 0 || W <= 0) return refuse("la3d_mask_counts", "bad argument");
   if (B == 0) return LA3D_SUCCESS;
   const int HW = H * W;
   const int vec = (HW % 16 == 0) && ((reinterpret_cast<uintptr_t>(mask) & 15) == 0);
@@ -517,17 +507,12 @@ int64_t la3d_rle_to_string_host(const int32_t* counts, int64_t n, char* out, int
 int la3d_mask_stats_poly(const int32_t* poly_xy, const int64_t* ring_offsets, const int64_t* inst_rings, int B, int H, int W,
                          int boundary, int32_t* stats, void* stream) {
   if (((!poly_xy || !ring_offsets || !inst_rings || !stats) && B > 0) || B < 0 || H <= 0 || W <= 0 || boundary < 0 ||
-      (long long)H * W > (1LL << 20)) {
-    set_err("la3d_mask_stats_poly: bad argument (H*W <= 1048576)");
-    return LA3D_ERR_ARG;
-  }
+      (long long)H * W > (1LL << 20))
+    return refuse("la3d_mask_stats_poly", "bad argument (H*W <= 1048576)");
   if (B == 0) return LA3D_SUCCESS;
   const int nwords = (H * W + 31) / 32;
   const size_t lds = (((size_t)nwords * 4 + 15) & ~(size_t)15) + POLY_STAGE_BYTES + 64 + (size_t)H * 4 + 128;
-  if (lds > 160 * 1024 - 256) {
-    set_err("la3d_mask_stats_poly: frame too large for LDS");
-    return LA3D_ERR_UNSUPPORTED;
-  }
+  if (lds > 160 * 1024 - 256) return refuse("la3d_mask_stats_poly", "frame too large for LDS", LA3D_ERR_UNSUPPORTED);
   allow_big_lds(reinterpret_cast<const void*>(mask_stats_poly_kernel));
   hipLaunchKernelGGL(mask_stats_poly_kernel, dim3(B), dim3(256), lds, static_cast<hipStream_t>(stream), poly_xy,
                      reinterpret_cast<const long long*>(ring_offsets), reinterpret_cast<const long long*>(inst_rings), H, W, nwords,
@@ -541,10 +526,7 @@ static void stats_lds_attr() {  // rows beyond 16 K need more than the default 6
 }
 
 int la3d_mask_stats(const uint8_t* mask, int B, int H, int W, int boundary, int32_t* stats, void* stream) {
-  if (!mask || !stats || B < 0 || H <= 0 || W <= 0 || boundary < 0) {
-    set_err("la3d_mask_stats: bad argument");
-    return LA3D_ERR_ARG;
-  }
+  if (!mask || !stats || B < 0 || H <= 0 || W <= 0 || boundary < 0) return refuse("la3d_mask_stats", "bad argument");
   if (B == 0) return LA3D_SUCCESS;
   if (W % 16 == 0 && (reinterpret_cast<uintptr_t>(mask) & 15) == 0 && H <= 32768) {
     stats_lds_attr();
@@ -559,10 +541,8 @@ int la3d_mask_stats(const uint8_t* mask, int B, int H, int W, int boundary, int3
 int la3d_mask_stats_rle(const int32_t* counts, const int64_t* offsets, int B, int H, int W, int boundary, int32_t* stats,
                         void* stream) {
   if ((!counts && B > 0) || !offsets || !stats || B < 0 || H <= 0 || W <= 0 || boundary < 0 || H > 32768 ||
-      (long long)H * W > (1LL << 30)) {
-    set_err("la3d_mask_stats_rle: bad argument (H <= 32768, H*W <= 2^30)");
-    return LA3D_ERR_ARG;
-  }
+      (long long)H * W > (1LL << 30))
+    return refuse("la3d_mask_stats_rle", "bad argument (H <= 32768, H*W <= 2^30)");
   if (B == 0) return LA3D_SUCCESS;
   stats_lds_attr();
   hipLaunchKernelGGL(mask_stats_rle_kernel, dim3(B), dim3(256), (size_t)(H + 1) * 4, static_cast<hipStream_t>(stream), counts,

@@ -1,6 +1,6 @@
 // la3d_open.hip - morphology on bit planes (include/la3d.h "morphology on bit planes"): la3d_open_bits and its frames form,
 // la3d_open_bits_frames.  The checks of the two entries are written out here - their rank is theirs, not pack_check's; from
-// la3d_bitplanes.hpp come the frames prologue of a workgroup, pack_refuse and the wording shared with the packers.
+// la3d_bitplanes.hpp come the frames prologue of a workgroup and the wording shared with the packers.
 #include <cstdint>
 #include <cstddef>
 
@@ -333,34 +333,34 @@ int la3d_open_bits(const uint32_t* bits, int64_t bits_plane_stride, int B, int H
                    uint32_t* out_bits, int64_t out_plane_stride, int W_out, int32_t* stats, void* workspace, void* stream) {
   const char* who = "la3d_open_bits";
   const int s = upscale;
-  if (B < 0 || H <= 0 || W <= 0) return pack_refuse(who, "bad argument (B >= 0, H, W > 0)");
-  if (k < 1 || k > 31 || !(k & 1)) return pack_refuse(who, "k must be odd and lie in 1 .. 31");
-  if (s != 1 && s != 2 && s != 4) return pack_refuse(who, "upscale must be 1, 2 or 4");
-  if (frame_width <= 0 || frame_width > W) return pack_refuse(who, "frame_width must lie in (0, W]");
-  if (!out_bits && !stats) return pack_refuse(who, "nothing to do: out_bits and stats are both NULL");
-  if (out_bits && (long long)W_out < (long long)s * frame_width) return pack_refuse(who, "W_out is smaller than upscale * frame_width");
+  if (B < 0 || H <= 0 || W <= 0) return refuse(who, "bad argument (B >= 0, H, W > 0)");
+  if (k < 1 || k > 31 || !(k & 1)) return refuse(who, "k must be odd and lie in 1 .. 31");
+  if (s != 1 && s != 2 && s != 4) return refuse(who, "upscale must be 1, 2 or 4");
+  if (frame_width <= 0 || frame_width > W) return refuse(who, "frame_width must lie in (0, W]");
+  if (!out_bits && !stats) return refuse(who, "nothing to do: out_bits and stats are both NULL");
+  if (out_bits && (long long)W_out < (long long)s * frame_width) return refuse(who, "W_out is smaller than upscale * frame_width");
   if (B == 0) return LA3D_SUCCESS;
-  if (!bits || (stats && !workspace)) return pack_refuse(who, "bits (and workspace, with stats) must not be NULL");
+  if (!bits || (stats && !workspace)) return refuse(who, "bits (and workspace, with stats) must not be NULL");
   if ((reinterpret_cast<uintptr_t>(bits) | reinterpret_cast<uintptr_t>(out_bits) | reinterpret_cast<uintptr_t>(stats) |
        reinterpret_cast<uintptr_t>(workspace)) & 3)
-    return pack_refuse(who, "bits, out_bits, stats or workspace not a 4-byte aligned pointer");
+    return refuse(who, "bits, out_bits, stats or workspace not a 4-byte aligned pointer");
   if (!out_bits) W_out = s * frame_width;             // statistics only: the plane that is never stored
-  if ((long long)s * frame_width > 8192) return pack_refuse(who, "upscale * frame_width must not exceed 8192 (a band of rows lives in LDS)", LA3D_ERR_UNSUPPORTED);
+  if ((long long)s * frame_width > 8192) return refuse(who, "upscale * frame_width must not exceed 8192 (a band of rows lives in LDS)", LA3D_ERR_UNSUPPORTED);
   if ((long long)s * H > (1LL << 28) || (long long)s * H * W_out > (1LL << 28))
-    return pack_refuse(who, "upscale * H * W_out must not exceed 2^28", LA3D_ERR_UNSUPPORTED);
+    return refuse(who, "upscale * H * W_out must not exceed 2^28", LA3D_ERR_UNSUPPORTED);
   const int H_out = s * H;
   const long long words_in = (long long)la3d_mask_bits_words(H, W), words_out = ((long long)H_out * W_out + 31) / 32;
-  if (bits_plane_stride < words_in) return pack_refuse(who, BITS_STRIDE);
+  if (bits_plane_stride < words_in) return refuse(who, BITS_STRIDE);
   if (out_bits) {
-    if (out_plane_stride < words_out) return pack_refuse(who, "out_plane_stride is smaller than la3d_mask_bits_words(upscale * H, W_out)");
+    if (out_plane_stride < words_out) return refuse(who, "out_plane_stride is smaller than la3d_mask_bits_words(upscale * H, W_out)");
     // neighbouring bands read each other's halo: the call cannot work in place
     const uintptr_t i0 = reinterpret_cast<uintptr_t>(bits), i1 = i0 + (uintptr_t)B * (uintptr_t)bits_plane_stride * 4;
     const uintptr_t o0 = reinterpret_cast<uintptr_t>(out_bits), o1 = o0 + (uintptr_t)B * (uintptr_t)out_plane_stride * 4;
-    if (i0 < o1 && o0 < i1) return pack_refuse(who, "the input planes and the output planes overlap");
+    if (i0 < o1 && o0 < i1) return refuse(who, "the input planes and the output planes overlap");
   }
   const int nw = (s * frame_width + 31) / 32;
   const OpenPlan p = open_plan(H_out, nw, k, s);
-  if ((long long)B * p.nbands > 0x7fffffffLL) return pack_refuse(who, "too many bands for one launch (B * bands > 2^31 - 1)", LA3D_ERR_UNSUPPORTED);
+  if ((long long)B * p.nbands > 0x7fffffffLL) return refuse(who, "too many bands for one launch (B * bands > 2^31 - 1)", LA3D_ERR_UNSUPPORTED);
   OpenArgs a = {};
   a.bits = bits; a.stride = bits_plane_stride; a.H = H; a.W = W; a.fw = frame_width; a.nwords_in = words_in;
   a.k = k; a.s = s; a.out = out_bits; a.out_stride = out_plane_stride;
@@ -384,29 +384,29 @@ int la3d_open_bits_frames(const uint32_t* bits, int64_t bits_words, const int64_
                           const int64_t* out_offsets, int32_t* stats, void* workspace, void* stream) {
   const char* who = "la3d_open_bits_frames";
   const int s = upscale;
-  if (B < 0 || P < 0 || H <= 0 || W <= 0) return pack_refuse(who, SIZES_FRAMES);
-  if (k < 1 || k > 31 || !(k & 1)) return pack_refuse(who, "k must be odd and lie in 1 .. 31");
-  if (s != 1 && s != 2 && s != 4) return pack_refuse(who, "upscale must be 1, 2 or 4");
-  if (!out_bits && !stats) return pack_refuse(who, "nothing to do: out_bits and stats are both NULL");
-  if (bits_words < 0 || (out_bits && out_words < 0)) return pack_refuse(who, "bits_words and out_words must not be negative");
+  if (B < 0 || P < 0 || H <= 0 || W <= 0) return refuse(who, SIZES_FRAMES);
+  if (k < 1 || k > 31 || !(k & 1)) return refuse(who, "k must be odd and lie in 1 .. 31");
+  if (s != 1 && s != 2 && s != 4) return refuse(who, "upscale must be 1, 2 or 4");
+  if (!out_bits && !stats) return refuse(who, "nothing to do: out_bits and stats are both NULL");
+  if (bits_words < 0 || (out_bits && out_words < 0)) return refuse(who, "bits_words and out_words must not be negative");
   if (B > 0) {
-    if (!bits || !bits_offsets || (!frames && P > 0) || !image_index) return pack_refuse(who, "NULL bits, bits_offsets, frames or image_index");
-    if (out_bits && !out_offsets) return pack_refuse(who, "out_offsets must not be NULL with out_bits");
-    if (stats && !workspace) return pack_refuse(who, "workspace must not be NULL with stats");
+    if (!bits || !bits_offsets || (!frames && P > 0) || !image_index) return refuse(who, "NULL bits, bits_offsets, frames or image_index");
+    if (out_bits && !out_offsets) return refuse(who, "out_offsets must not be NULL with out_bits");
+    if (stats && !workspace) return refuse(who, "workspace must not be NULL with stats");
   }
-  if ((at(bits) | at(out_bits)) & 15) return pack_refuse(who, "bits or out_bits not a 16-byte aligned pointer");
-  if ((at(bits_offsets) | at(out_offsets) | at(frames)) & 7) return pack_refuse(who, "bits_offsets, out_offsets or frames not an 8-byte aligned pointer");
-  if ((at(stats) | at(workspace) | at(image_index)) & 3) return pack_refuse(who, "stats, workspace or image_index not a 4-byte aligned pointer");
+  if ((at(bits) | at(out_bits)) & 15) return refuse(who, "bits or out_bits not a 16-byte aligned pointer");
+  if ((at(bits_offsets) | at(out_offsets) | at(frames)) & 7) return refuse(who, "bits_offsets, out_offsets or frames not an 8-byte aligned pointer");
+  if ((at(stats) | at(workspace) | at(image_index)) & 3) return refuse(who, "stats, workspace or image_index not a 4-byte aligned pointer");
   if (bits && out_bits) {   // neighbouring bands read each other's halo: the call cannot work in place
     const uintptr_t i0 = at(bits), i1 = i0 + (uintptr_t)bits_words * 4, o0 = at(out_bits), o1 = o0 + (uintptr_t)out_words * 4;
-    if (i0 < o1 && o0 < i1) return pack_refuse(who, "the input buffer and the output buffer overlap");
+    if (i0 < o1 && o0 < i1) return refuse(who, "the input buffer and the output buffer overlap");
   }
-  if ((long long)s * W > 8192) return pack_refuse(who, "upscale * W must not exceed 8192 (a band of rows lives in LDS)", LA3D_ERR_UNSUPPORTED);
+  if ((long long)s * W > 8192) return refuse(who, "upscale * W must not exceed 8192 (a band of rows lives in LDS)", LA3D_ERR_UNSUPPORTED);
   const long long W_out = ((long long)s * W + 31) / 32 * 32;
   if ((long long)s * H > (1LL << 28) || (long long)s * H * W_out > (1LL << 28))
-    return pack_refuse(who, "upscale * H * roundup32(upscale * W) must not exceed 2^28", LA3D_ERR_UNSUPPORTED);
+    return refuse(who, "upscale * H * roundup32(upscale * W) must not exceed 2^28", LA3D_ERR_UNSUPPORTED);
   const OpenPlan p = open_plan(s * H, (int)(W_out / 32), k, s);   // one plan per call, from the bounds
-  if ((long long)B * p.nbands > 0x7fffffffLL) return pack_refuse(who, "too many bands for one launch (B * bands > 2^31 - 1)", LA3D_ERR_UNSUPPORTED);
+  if ((long long)B * p.nbands > 0x7fffffffLL) return refuse(who, "too many bands for one launch (B * bands > 2^31 - 1)", LA3D_ERR_UNSUPPORTED);
   if (B == 0) return LA3D_SUCCESS;
   OpenArgs a = {};
   a.bits = bits; a.H = H; a.W = W; a.k = k; a.s = s; a.out = out_bits;

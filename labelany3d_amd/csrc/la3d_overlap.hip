@@ -17,7 +17,7 @@
 #include <cstddef>
 #include <cstring>
 
-#include "la3d_bitplanes.hpp"   // (pack_refuse, at)
+#include "la3d_bitplanes.hpp"   // (at)
 
 using namespace la3d;
 
@@ -293,15 +293,15 @@ extern "C" {
 int64_t la3d_mask_overlap_plan(int32_t G, const int32_t* counts_a, const int32_t* counts_b, const int64_t* group_words, int64_t nwords,
                                la3d_overlap_tile* tiles, int64_t capacity, int64_t* offsets) {
   const char* who = "la3d_mask_overlap_plan";
-  if (G < 0 || !offsets || (G > 0 && !counts_a) || capacity < 0 || (!group_words && nwords < 0)) return pack_refuse(who, "G < 0, a NULL counts_a or offsets, a negative capacity or nwords");
+  if (G < 0 || !offsets || (G > 0 && !counts_a) || capacity < 0 || (!group_words && nwords < 0)) return refuse(who, "G < 0, a NULL counts_a or offsets, a negative capacity or nwords");
   const bool self = counts_b == nullptr;
   long long pairs = 0, rows_a = 0, rows_b = 0, base_tiles = 0;
   for (int g = 0; g < G; ++g) {
     const long long na = counts_a[g], nb = self ? na : counts_b[g], nw = group_words ? group_words[g] : nwords;
-    if (na < 0 || nb < 0 || nw < 0) return pack_refuse(who, "a negative row count or word count");
-    if (nw > MAX_WORDS) return pack_refuse(who, "a plane of more than 2^23 words (H * W_stored > 2^28): a count would not fit int32", LA3D_ERR_UNSUPPORTED);
+    if (na < 0 || nb < 0 || nw < 0) return refuse(who, "a negative row count or word count");
+    if (nw > MAX_WORDS) return refuse(who, "a plane of more than 2^23 words (H * W_stored > 2^28): a count would not fit int32", LA3D_ERR_UNSUPPORTED);
     pairs += na * nb; rows_a += na; rows_b += nb;
-    if (pairs > MAX_PAIRS || rows_a > MAX_PAIRS || rows_b > MAX_PAIRS) return pack_refuse(who, "more than 2^31 - 1 pairs or rows in one call", LA3D_ERR_UNSUPPORTED);
+    if (pairs > MAX_PAIRS || rows_a > MAX_PAIRS || rows_b > MAX_PAIRS) return refuse(who, "more than 2^31 - 1 pairs or rows in one call", LA3D_ERR_UNSUPPORTED);
     const long long ta = tiles_of(na), tb = tiles_of(nb);
     base_tiles += self ? ta * (ta + 1) / 2 : (na == 0 ? tb : nb == 0 ? ta : ta * tb);
   }
@@ -319,7 +319,7 @@ int64_t la3d_mask_overlap_plan(int32_t G, const int32_t* counts_a, const int32_t
       for (long long tj = self ? ti : 0; tj < (tb ? tb : 1); ++tj)
         for (long long c = 0; c < nch; ++c, ++n) {
           if (!tiles) continue;
-          if (n >= capacity) return pack_refuse(who, "the tile table is smaller than the call needs");
+          if (n >= capacity) return refuse(who, "the tile table is smaller than the call needs");
           la3d_overlap_tile& t = tiles[n];
           t.g = g; t.i0 = (int)(ti * TILE); t.j0 = (int)(tj * TILE);
           t.ni = (int)(na - t.i0 < TILE ? na - t.i0 : TILE); t.nj = (int)(nb - t.j0 < TILE ? nb - t.j0 : TILE);
@@ -330,7 +330,7 @@ int64_t la3d_mask_overlap_plan(int32_t G, const int32_t* counts_a, const int32_t
                          : (tj == 0 ? LA3D_OVERLAP_AREA_A : 0) | (ti == 0 ? LA3D_OVERLAP_AREA_B : 0);
           t.out0 = out0;
         }
-    if (n > MAX_PAIRS) return pack_refuse(who, "more than 2^31 - 1 tiles in one call", LA3D_ERR_UNSUPPORTED);
+    if (n > MAX_PAIRS) return refuse(who, "more than 2^31 - 1 tiles in one call", LA3D_ERR_UNSUPPORTED);
     out0 += na * nb; ra += na; rb += nb;
     offsets[g + 1] = out0;
   }
@@ -341,29 +341,29 @@ size_t la3d_mask_overlap_workspace_bytes(int64_t ntiles) { return ntiles > 0 ? (
 
 int la3d_mask_overlap(const la3d_mask_overlap_args* args) {
   const char* who = "la3d_mask_overlap";
-  if (!args || args->struct_size != (int32_t)sizeof(la3d_mask_overlap_args)) return pack_refuse(who, "NULL block or a struct_size that is not sizeof(la3d_mask_overlap_args)");
+  if (!args || args->struct_size != (int32_t)sizeof(la3d_mask_overlap_args)) return refuse(who, "NULL block or a struct_size that is not sizeof(la3d_mask_overlap_args)");
   const la3d_mask_overlap_args& a = *args;
   const bool self = a.b_bits == nullptr, frames = a.frames != nullptr;
-  if (a.G < 0 || a.rows_a < 0 || (!self && a.rows_b < 0) || a.ntiles < 0 || a.npairs < 0) return pack_refuse(who, "negative G, rows, ntiles or npairs");
-  if (a.iou && (a.kind < LA3D_OVERLAP_IOU || a.kind > LA3D_OVERLAP_IOA)) return pack_refuse(who, "kind must be LA3D_OVERLAP_IOU, _IOM or _IOA with iou");
+  if (a.G < 0 || a.rows_a < 0 || (!self && a.rows_b < 0) || a.ntiles < 0 || a.npairs < 0) return refuse(who, "negative G, rows, ntiles or npairs");
+  if (a.iou && (a.kind < LA3D_OVERLAP_IOU || a.kind > LA3D_OVERLAP_IOA)) return refuse(who, "kind must be LA3D_OVERLAP_IOU, _IOM or _IOA with iou");
   if (frames) {
-    if (a.P != a.G || a.H <= 0 || a.W <= 0) return pack_refuse(who, "frames form: G must be P (group g is image g) and the bounds H, W > 0");
-    if (a.a_words < 0 || (!self && a.b_words < 0)) return pack_refuse(who, "a_words and b_words must not be negative");
-    if ((((long long)a.H * ((a.W + 31) / 32 * 32)) >> 5) > MAX_WORDS) return pack_refuse(who, "bounds beyond H * roundup32(W) <= 2^28: a count would not fit int32", LA3D_ERR_UNSUPPORTED);
+    if (a.P != a.G || a.H <= 0 || a.W <= 0) return refuse(who, "frames form: G must be P (group g is image g) and the bounds H, W > 0");
+    if (a.a_words < 0 || (!self && a.b_words < 0)) return refuse(who, "a_words and b_words must not be negative");
+    if ((((long long)a.H * ((a.W + 31) / 32 * 32)) >> 5) > MAX_WORDS) return refuse(who, "bounds beyond H * roundup32(W) <= 2^28: a count would not fit int32", LA3D_ERR_UNSUPPORTED);
   } else {
-    if (a.nwords < 0) return pack_refuse(who, "nwords must not be negative");
-    if (a.nwords > MAX_WORDS) return pack_refuse(who, "a plane of more than 2^23 words (H * W_stored > 2^28): a count would not fit int32", LA3D_ERR_UNSUPPORTED);
+    if (a.nwords < 0) return refuse(who, "nwords must not be negative");
+    if (a.nwords > MAX_WORDS) return refuse(who, "a plane of more than 2^23 words (H * W_stored > 2^28): a count would not fit int32", LA3D_ERR_UNSUPPORTED);
   }
   if (a.npairs > MAX_PAIRS || a.ntiles > MAX_PAIRS || a.rows_a > MAX_PAIRS || (!self && a.rows_b > MAX_PAIRS))
-    return pack_refuse(who, "more than 2^31 - 1 pairs, rows or tiles in one call", LA3D_ERR_UNSUPPORTED);
+    return refuse(who, "more than 2^31 - 1 pairs, rows or tiles in one call", LA3D_ERR_UNSUPPORTED);
   if (a.ntiles == 0) return LA3D_SUCCESS;
   // (a side without rows, or a call without pairs, has nothing to point at: a b_bits that is NULL with rows_b == 0 reads as the self
   // form, whose tiles then have no row of B either)
   if (!a.tiles || !a.workspace || (a.rows_a > 0 && (!a.a_bits || !a.area_a)) || (!self && a.rows_b > 0 && !a.area_b) || (a.npairs > 0 && !a.inter))
-    return pack_refuse(who, "NULL a_bits, tiles, inter, area_a, area_b or workspace");
+    return refuse(who, "NULL a_bits, tiles, inter, area_a, area_b or workspace");
   if ((at(a.a_bits) | at(a.b_bits) | at(a.inter) | at(a.area_a) | at(a.area_b) | at(a.workspace)) & 3)
-    return pack_refuse(who, "a_bits, b_bits, inter, area_a, area_b or workspace not a 4-byte aligned pointer");
-  if ((at(a.tiles) | at(a.iou)) & 7) return pack_refuse(who, "tiles or iou not an 8-byte aligned pointer");
+    return refuse(who, "a_bits, b_bits, inter, area_a, area_b or workspace not a 4-byte aligned pointer");
+  if ((at(a.tiles) | at(a.iou)) & 7) return refuse(who, "tiles or iou not an 8-byte aligned pointer");
   OverlapParams p = {};
   p.a = a.a_bits; p.b = self ? a.a_bits : a.b_bits;
   p.tiles = a.tiles; p.partial = static_cast<int*>(a.workspace);
@@ -371,10 +371,10 @@ int la3d_mask_overlap(const la3d_mask_overlap_args* args) {
   hipStream_t st = static_cast<hipStream_t>(a.stream);
   const dim3 grid((unsigned)a.ntiles);
   if (frames) {
-    if (!a.a_offsets || !a.a_image_index || (!self && (!a.b_offsets || !a.b_image_index))) return pack_refuse(who, "frames form: NULL offsets or image_index");
-    if ((at(a.a_bits) | at(a.b_bits)) & 15) return pack_refuse(who, "frames form: a_bits or b_bits not a 16-byte aligned pointer");
-    if ((at(a.a_offsets) | at(a.b_offsets) | at(a.frames)) & 7) return pack_refuse(who, "a_offsets, b_offsets or frames not an 8-byte aligned pointer");
-    if ((at(a.a_image_index) | at(a.b_image_index)) & 3) return pack_refuse(who, "a_image_index or b_image_index not a 4-byte aligned pointer");
+    if (!a.a_offsets || !a.a_image_index || (!self && (!a.b_offsets || !a.b_image_index))) return refuse(who, "frames form: NULL offsets or image_index");
+    if ((at(a.a_bits) | at(a.b_bits)) & 15) return refuse(who, "frames form: a_bits or b_bits not a 16-byte aligned pointer");
+    if ((at(a.a_offsets) | at(a.b_offsets) | at(a.frames)) & 7) return refuse(who, "a_offsets, b_offsets or frames not an 8-byte aligned pointer");
+    if ((at(a.a_image_index) | at(a.b_image_index)) & 3) return refuse(who, "a_image_index or b_image_index not a 4-byte aligned pointer");
     p.a_off = reinterpret_cast<const long long*>(a.a_offsets); p.a_img = a.a_image_index; p.a_words = a.a_words;
     p.b_off = self ? p.a_off : reinterpret_cast<const long long*>(a.b_offsets);
     p.b_img = self ? p.a_img : a.b_image_index; p.b_words = self ? a.a_words : a.b_words;
@@ -385,7 +385,7 @@ int la3d_mask_overlap(const la3d_mask_overlap_args* args) {
     hipLaunchKernelGGL(mask_overlap_finish_kernel<true>, grid, dim3(128), 0, st, p);
     return check_launch("mask_overlap_finish_kernel");
   }
-  if (a.a_stride < a.nwords || (!self && a.b_stride < a.nwords)) return pack_refuse(who, "a_stride or b_stride below nwords");
+  if (a.a_stride < a.nwords || (!self && a.b_stride < a.nwords)) return refuse(who, "a_stride or b_stride below nwords");
   p.a_stride = a.a_stride; p.b_stride = self ? a.a_stride : a.b_stride;
   const bool vec = ((at(p.a) | at(p.b)) & 15) == 0 && (p.a_stride & 3) == 0 && (p.b_stride & 3) == 0;
   if (vec) hipLaunchKernelGGL((mask_overlap_kernel<false, true>), grid, dim3(OT), 0, st, p);
@@ -398,16 +398,16 @@ int la3d_mask_overlap(const la3d_mask_overlap_args* args) {
 
 int la3d_mask_nms(const la3d_mask_nms_args* args) {
   const char* who = "la3d_mask_nms";
-  if (!args || args->struct_size != (int32_t)sizeof(la3d_mask_nms_args)) return pack_refuse(who, "NULL block or a struct_size that is not sizeof(la3d_mask_nms_args)");
+  if (!args || args->struct_size != (int32_t)sizeof(la3d_mask_nms_args)) return refuse(who, "NULL block or a struct_size that is not sizeof(la3d_mask_nms_args)");
   const la3d_mask_nms_args& a = *args;
-  if (a.G < 0 || a.B < 0) return pack_refuse(who, "negative G or B");
-  if (a.kind != LA3D_OVERLAP_IOU && a.kind != LA3D_OVERLAP_IOM) return pack_refuse(who, "kind must be LA3D_OVERLAP_IOU or LA3D_OVERLAP_IOM");
-  if (!(a.thr == a.thr)) return pack_refuse(who, "thr must not be NaN");
-  if (a.B > MAX_PAIRS) return pack_refuse(who, "more than 2^31 - 1 rows in one call", LA3D_ERR_UNSUPPORTED);
+  if (a.G < 0 || a.B < 0) return refuse(who, "negative G or B");
+  if (a.kind != LA3D_OVERLAP_IOU && a.kind != LA3D_OVERLAP_IOM) return refuse(who, "kind must be LA3D_OVERLAP_IOU or LA3D_OVERLAP_IOM");
+  if (!(a.thr == a.thr)) return refuse(who, "thr must not be NaN");
+  if (a.B > MAX_PAIRS) return refuse(who, "more than 2^31 - 1 rows in one call", LA3D_ERR_UNSUPPORTED);
   if (a.G == 0 || a.B == 0) return LA3D_SUCCESS;
-  if (!a.inter || !a.area || !a.offsets || !a.row_offsets || !a.order || !a.keep) return pack_refuse(who, "NULL inter, area, offsets, row_offsets, order or keep");
-  if ((at(a.inter) | at(a.area) | at(a.row_offsets) | at(a.order) | at(a.labels)) & 3) return pack_refuse(who, "inter, area, row_offsets, order or labels not a 4-byte aligned pointer");
-  if (at(a.offsets) & 7) return pack_refuse(who, "offsets not an 8-byte aligned pointer");
+  if (!a.inter || !a.area || !a.offsets || !a.row_offsets || !a.order || !a.keep) return refuse(who, "NULL inter, area, offsets, row_offsets, order or keep");
+  if ((at(a.inter) | at(a.area) | at(a.row_offsets) | at(a.order) | at(a.labels)) & 3) return refuse(who, "inter, area, row_offsets, order or labels not a 4-byte aligned pointer");
+  if (at(a.offsets) & 7) return refuse(who, "offsets not an 8-byte aligned pointer");
   NmsParams p = {a.inter, a.area, reinterpret_cast<const long long*>(a.offsets), a.row_offsets, a.order, a.labels, a.thr, a.kind, a.keep};
   hipLaunchKernelGGL(mask_nms_kernel, dim3((unsigned)a.G), dim3(NMS_T), 0, static_cast<hipStream_t>(a.stream), p);
   return check_launch("mask_nms_kernel");

@@ -377,17 +377,11 @@ extern "C" {
 
 int la3d_fit_points(const double* points, const int64_t* offsets, const double* ground, const int32_t* sample_idx,
                     int method, int B, double* out, int32_t* status, double* aux, void* stream) {
-  if (B < 0 || (B > 0 && (!offsets || !out || !status || !points))) {
-    set_err("la3d_fit_points: bad argument");
-    return LA3D_ERR_ARG;
-  }
+  if (B < 0 || (B > 0 && (!offsets || !out || !status || !points))) return refuse("la3d_fit_points", "bad argument");
   const bool small = (method & LA3D_HINT_SMALL_CLOUDS) != 0;
   const bool hull512 = (method & LA3D_HINT_HULL_512) != 0 || sample_idx != nullptr;   // (sampled clouds hold 500 rows)
   method &= ~(LA3D_HINT_SMALL_CLOUDS | LA3D_HINT_HULL_512);
-  if (method != LA3D_METHOD_PCA && method != LA3D_METHOD_CONVEX_HULL) {
-    set_err("la3d_fit_points: unknown method");
-    return LA3D_ERR_ARG;
-  }
+  if (method != LA3D_METHOD_PCA && method != LA3D_METHOD_CONVEX_HULL) return refuse("la3d_fit_points", "unknown method");
   if (B == 0) return LA3D_SUCCESS;
   PtsParams p;
   p.points = points; p.offsets = reinterpret_cast<const long long*>(offsets); p.ground = ground;
@@ -434,7 +428,7 @@ void host_ctx_release(HostCtx& c) {
 int host_ctx(HostCtx** out, size_t pin_need, size_t dev_need, const char* who) {
   HostCtx& c = t_host;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { snprintf(g_err, sizeof(g_err), "%s: no device", who); (void)hipGetLastError(); return LA3D_ERR_HIP; }
+  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return refuse(who, "no device", LA3D_ERR_HIP); }
   if (c.device != dev) {
     if (c.device >= 0) {   // the thread moved to another GPU: the old context's memory belongs to the old device
       int cur = dev;
@@ -444,7 +438,7 @@ int host_ctx(HostCtx** out, size_t pin_need, size_t dev_need, const char* who) {
     }
     c.device = dev;
     if (hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking) != hipSuccess) {
-      snprintf(g_err, sizeof(g_err), "%s: hipStreamCreate failed", who); (void)hipGetLastError(); c = HostCtx(); return LA3D_ERR_HIP;
+      (void)hipGetLastError(); c = HostCtx(); return refuse(who, "hipStreamCreate failed", LA3D_ERR_HIP);
     }
   }
   auto grow = [](size_t need) { size_t n = 64 * 1024; while (n < need) n *= 2; return n; };
@@ -479,14 +473,8 @@ int host_ctx(HostCtx** out, size_t pin_need, size_t dev_need, const char* who) {
 
 int la3d_estimate_bbox_host(const double* points, int64_t n, const double* ground4, int method, double* out39, double* aux4,
                             int32_t* status) {
-  if (n < 0 || (n > 0 && !points) || !out39 || !status || n > (int64_t)1 << 31) {
-    set_err("la3d_estimate_bbox_host: bad argument");
-    return LA3D_ERR_ARG;
-  }
-  if (method != LA3D_METHOD_PCA && method != LA3D_METHOD_CONVEX_HULL) {
-    set_err("la3d_estimate_bbox_host: unknown method");
-    return LA3D_ERR_ARG;
-  }
+  if (n < 0 || (n > 0 && !points) || !out39 || !status || n > (int64_t)1 << 31) return refuse("la3d_estimate_bbox_host", "bad argument");
+  if (method != LA3D_METHOD_PCA && method != LA3D_METHOD_CONVEX_HULL) return refuse("la3d_estimate_bbox_host", "unknown method");
   HostCtx* c = nullptr;
   const int rc = host_ctx(&c, HOSTFIT_HDR + (size_t)n * 24 + 16, 0, "la3d_estimate_bbox_host");
   if (rc != LA3D_SUCCESS) return rc;
@@ -534,10 +522,7 @@ int la3d_estimate_bbox_host(const double* points, int64_t n, const double* groun
 }
 
 int la3d_unproject_host(const float* depth, const double* K9, const double* Rt12, int H, int W, void* out, int out_is_f64) {
-  if (!depth || !K9 || !out || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL / 4) {
-    set_err("la3d_unproject_host: bad argument");
-    return LA3D_ERR_ARG;
-  }
+  if (!depth || !K9 || !out || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL / 4) return refuse("la3d_unproject_host", "bad argument");
   const size_t in_bytes = (size_t)H * W * 4, out_bytes = (size_t)H * W * 3 * (out_is_f64 ? 8 : 4);
   const size_t out_off = (in_bytes + 255) & ~(size_t)255;
   HostCtx* c = nullptr;
@@ -569,29 +554,21 @@ inline size_t up64(size_t v) { return (v + 63) & ~(size_t)63; }
 }  // namespace
 
 int la3d_fit_annotations_host(const la3d_fit_args* args) {
-  constexpr int32_t V1_SIZE = (int32_t)offsetof(la3d_fit_args, area_hint);
-  if (!args || args->struct_size < V1_SIZE) {
-    set_err("la3d_fit_annotations_host: bad struct_size");
-    return LA3D_ERR_ARG;
-  }
-  la3d_fit_args a;
-  memset(&a, 0, sizeof(a));
-  memcpy(&a, args, (size_t)args->struct_size < sizeof(a) ? (size_t)args->struct_size : sizeof(a));
+  const char* who = "la3d_fit_annotations_host";
+  if (!fit_args_size_ok(args)) return refuse(who, "bad struct_size");
+  const la3d_fit_args a = fit_args_copy(args);
   const bool rle = a.rle_counts != nullptr, poly = a.poly_xy != nullptr;
   if (a.B < 0 || a.H <= 0 || a.W <= 0 || a.mask || rle == poly || (rle && !a.rle_offsets) || (poly && (!a.ring_offsets || !a.inst_rings)) ||
-      !a.depth || !a.K || !a.out || !a.status || a.sample_idx || a.proj || (a.k_stride != 0 && a.k_stride < 9)) {
-    set_err("la3d_fit_annotations_host: bad argument (run lengths or polygon parts, host arrays; depth on the device; no u8 planes, "
-            "sample_idx or proj)");
-    return LA3D_ERR_ARG;
-  }
+      !a.depth || !a.K || !a.out || !a.status || a.sample_idx || a.proj || (a.k_stride != 0 && a.k_stride < 9))
+    return refuse(who, "bad argument (run lengths or polygon parts, host arrays; depth on the device; no u8 planes, sample_idx or proj)");
   const int B = a.B;
   if (B == 0) return LA3D_SUCCESS;
   int64_t P = 1;
-  if (a.image_index) for (int i = 0; i < B; ++i) { if (a.image_index[i] < 0) { set_err("la3d_fit_annotations_host: negative image_index"); return LA3D_ERR_ARG; } if (a.image_index[i] + 1 > P) P = a.image_index[i] + 1; }
+  if (a.image_index) for (int i = 0; i < B; ++i) { if (a.image_index[i] < 0) return refuse(who, "negative image_index"); if (a.image_index[i] + 1 > P) P = a.image_index[i] + 1; }
   else if (a.depth_plane_stride != 0 || a.k_stride != 0) P = B;
   const int64_t R = poly ? a.inst_rings[B] : 0;
   const int64_t T = rle ? a.rle_offsets[B] : a.ring_offsets[R];
-  if (T < 0 || R < 0) { set_err("la3d_fit_annotations_host: bad offsets"); return LA3D_ERR_ARG; }
+  if (T < 0 || R < 0) return refuse(who, "bad offsets");
   // block layout: [0] flag | inputs (uploaded) | outputs (written by the kernels through the mapping)
   size_t off = 64;
   const size_t o_idx = off;    off += up64(a.image_index ? (size_t)B * 4 : 0);
@@ -609,7 +586,7 @@ int la3d_fit_annotations_host(const la3d_fit_args* args) {
   const size_t ws_bytes = la3d_fit_workspace_bytes(&a);   // (a convex-hull call needs its hand-off area too)
   const size_t d_ws = (in_end + 255) & ~(size_t)255;
   HostCtx* c = nullptr;
-  const int rc = host_ctx(&c, off, d_ws + ws_bytes + 256, "la3d_fit_annotations_host");
+  const int rc = host_ctx(&c, off, d_ws + ws_bytes + 256, who);
   if (rc != LA3D_SUCCESS) return rc;
   unsigned char* h = c->pin;
   if (a.image_index) memcpy(h + o_idx, a.image_index, (size_t)B * 4);

@@ -220,17 +220,17 @@ __global__ __launch_bounds__(NT_DEC) void rle_encode_emit_kernel(const BitsOut c
 enum { RLE_LAUNCH = 0, RLE_NOTHING = 1 };
 int rle_encode_check(const la3d_rle_encode_args* args, const char* who, bool emit, la3d_rle_encode_args& a, BitsOut& c, RleOut& e) {
   static_assert(sizeof(la3d_rle_encode_args) == 120, "la3d_rle_encode_args is part of the ABI");
-  if (!args || args->struct_size < (int32_t)sizeof(la3d_rle_encode_args)) return pack_refuse(who, "bad struct_size");
+  if (!args || args->struct_size < (int32_t)sizeof(la3d_rle_encode_args)) return refuse(who, "bad struct_size");
   memcpy(&a, args, sizeof(a));   // (a longer block from a newer caller is fine)
-  if (a.B < 0 || a.H < 0 || a.W < 0 || a.P < 0) return pack_refuse(who, "negative sizes (B, H, W, P)");
-  if (a.frame_width < 0 || a.frame_width > a.W) return pack_refuse(who, "frame_width outside [0, W]");
-  if (a.bits_plane_stride < 0) return pack_refuse(who, "negative bits_plane_stride");
-  if (emit && a.capacity < 0) return pack_refuse(who, "negative capacity");
-  if (a.bits_offsets && !a.frames) return pack_refuse(who, "bits_offsets without frames");
-  if (a.frames && !a.image_index) return pack_refuse(who, "frames without image_index: instance n belongs to frame row image_index[n]");
+  if (a.B < 0 || a.H < 0 || a.W < 0 || a.P < 0) return refuse(who, "negative sizes (B, H, W, P)");
+  if (a.frame_width < 0 || a.frame_width > a.W) return refuse(who, "frame_width outside [0, W]");
+  if (a.bits_plane_stride < 0) return refuse(who, "negative bits_plane_stride");
+  if (emit && a.capacity < 0) return refuse(who, "negative capacity");
+  if (a.bits_offsets && !a.frames) return refuse(who, "bits_offsets without frames");
+  if (a.frames && !a.image_index) return refuse(who, "frames without image_index: instance n belongs to frame row image_index[n]");
   if (a.frames && (a.frame_width != 0 || a.bits_plane_stride != 0))
-    return pack_refuse(who, "frame_width and bits_plane_stride must be 0 in a frames call (the frame table and bits_offsets say both)");
-  if (!a.offsets || (reinterpret_cast<uintptr_t>(a.offsets) & 7)) return pack_refuse(who, "offsets NULL or not an 8-byte aligned pointer");
+    return refuse(who, "frame_width and bits_plane_stride must be 0 in a frames call (the frame table and bits_offsets say both)");
+  if (!a.offsets || (reinterpret_cast<uintptr_t>(a.offsets) & 7)) return refuse(who, "offsets NULL or not an 8-byte aligned pointer");
   memset(&e, 0, sizeof(e));
   e.runs = a.runs; e.offsets = reinterpret_cast<long long*>(a.offsets); e.counts = a.counts; e.status = a.status; e.capacity = a.capacity;
   e.ws = static_cast<int2*>(a.workspace); e.ws_cols = a.W;

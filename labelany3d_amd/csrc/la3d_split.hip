@@ -691,10 +691,8 @@ int split_fit(const FitParams& pin, void* workspace, hipStream_t s) {
   if (nsub > 4) nsub = 4;
   while ((B + nsub - 1) / nsub * L.nband > MAX_SEG && nsub < MAX_SUB) ++nsub;
   if (nsub > MAX_SUB) nsub = MAX_SUB;
-  if ((B + nsub - 1) / nsub * L.nband > MAX_SEG) {
-    set_err("la3d split engine: batch too large for one call (split the batch)");
-    return LA3D_ERR_UNSUPPORTED;
-  }
+  if ((B + nsub - 1) / nsub * L.nband > MAX_SEG)
+    return refuse("la3d split engine", "batch too large for one call (split the batch)", LA3D_ERR_UNSUPPORTED);
   const bool single = nsub == 1;
   hipStream_t scan_s = s;
   if (!single) {
