@@ -1015,6 +1015,78 @@ size_t la3d_mask_overlap_workspace_bytes(int64_t ntiles);
 int la3d_mask_overlap(const la3d_mask_overlap_args* args);
 int la3d_mask_nms(const la3d_mask_nms_args* args);
 
+/* ---- assignment on the device (reference stage 8: hungarian_matching, src/tools/combine_results.py:126-144) ----------------
+ * la3d_assign - for every GROUP g (an image) the rectangular linear sum assignment of the na_g x nb_g matrix at cost + offsets[g],
+ *   row-major (row i of A, row j of B): the layout of la3d_mask_overlap's inter / iou and of la3d_iou_matrix_groups.  na_g, nb_g are
+ *   the differences of row_offsets_a / row_offsets_b (as in la3d_mask_nms).  cost_dtype LA3D_ASSIGN_F64, or LA3D_ASSIGN_I32 (the
+ *   `inter` of a mask overlap; converted to double, which is exact).  maximize 1: the matrix is negated first.
+ *   The arithmetic is SciPy's (scipy.optimize.linear_sum_assignment, 1.15: shortest augmenting paths on float64, additions and
+ *   subtractions only), step for step, TIES INCLUDED - most pairs of an image score 0, so ties decide real matrices: na > nb solves
+ *   the transpose; rows in ascending order; of the remaining columns with the least path cost an unassigned one at the highest
+ *   position of SciPy's `remaining` list wins, else the one at the lowest position.  The result is SciPy's (rows, cols) exactly.
+ *   One wave per group, no barriers, no atomics, no workspace, no allocation, no host synchronisation: the call can be captured.
+ *   Column j lives in lane j % 64 (path cost, dual, row, predecessor, position: registers), the duals of the rows in LDS; a group
+ *   of at most LA3D_ASSIGN_STAGE_MAX elements is staged into LDS in the solver's orientation, a larger one is read where it lies -
+ *   the same results either way.
+ *   col_of_row i32 [rows_a]: the column within its group, -1 if none; row_of_col i32 [rows_b] likewise; status i32 [G]:
+ *     0 LA3D_ASSIGN_OK          assigned (an empty side: all -1)
+ *     1 LA3D_ASSIGN_INVALID     an entry is NaN, or -inf after the sign of maximize  (SciPy: "matrix contains invalid numeric
+ *                               entries"; +inf is legal)
+ *     2 LA3D_ASSIGN_INFEASIBLE  (SciPy: "cost matrix is infeasible")
+ *     3 LA3D_ASSIGN_TOO_LARGE   max(na, nb) > LA3D_ASSIGN_MAX_N
+ *     4 LA3D_ASSIGN_BROKEN      the tables are broken: a negative count, a row range outside [0, rows_a] / [0, rows_b], or a matrix
+ *                               outside [0, ncost) - checked wave-uniformly before any address is formed from these values; such a
+ *                               group gets ONLY its status written
+ *   With status 1 - 3 every row and column of the group gets -1.  Every output element of a well-formed group is written exactly once.
+ *   LA3D_ERR_ARG before any launch, in this order: a NULL block or a bad struct_size; G, rows_a, rows_b or ncost < 0; a bad
+ *   cost_dtype, or maximize not 0 or 1; (G == 0: success, nothing launched;) NULL offsets, row_offsets_a, row_offsets_b, status, or
+ *   cost / col_of_row / row_of_col with ncost / rows_a / rows_b > 0; cost (8 bytes for F64, 4 for I32), offsets (8) or the i32
+ *   pointers (4) misaligned.
+ * la3d_iou_matrix_groups - la3d_iou_matrix for G groups in one launch: out[offsets[g] + i * nb_g + j] = iou2D(A row
+ *   row_offsets_a[g] + i, B row row_offsets_b[g] + j), the same device expression: every group's values are bit-identical to a
+ *   la3d_iou_matrix call on it.  One thread per element of [0, npairs) finds its group in offsets (npairs = offsets[G], known to the
+ *   host); an element whose tables are broken (it lies in no group's matrix, or its rows outside [0, rows_a) / [0, rows_b)) gets NaN
+ *   and reads no box.  LA3D_ERR_ARG: NULL block, bad struct_size, G / rows / npairs < 0, NULL or misaligned pointers with npairs > 0. */
+#define LA3D_ASSIGN_F64 0
+#define LA3D_ASSIGN_I32 1
+#define LA3D_ASSIGN_MAX_N 256        /* rows and columns of a group: four columns per lane */
+#define LA3D_ASSIGN_STAGE_MAX 2048   /* elements of a group's matrix that are staged in LDS (16 KiB of doubles: eight waves per CU) */
+#define LA3D_ASSIGN_OK 0
+#define LA3D_ASSIGN_INVALID 1
+#define LA3D_ASSIGN_INFEASIBLE 2
+#define LA3D_ASSIGN_TOO_LARGE 3
+#define LA3D_ASSIGN_BROKEN 4
+typedef struct la3d_assign_args {
+  int32_t struct_size;                                   /* sizeof(la3d_assign_args) of the caller */
+  int32_t G;                                             /* groups */
+  const void* cost;                                      /* dev: the flat cost buffer */
+  int32_t cost_dtype;                                    /* LA3D_ASSIGN_F64 | LA3D_ASSIGN_I32 */
+  int32_t reserved0;
+  int64_t ncost;                                         /* elements of cost */
+  const int64_t* offsets;                                /* dev [G + 1] */
+  const int32_t* row_offsets_a; const int32_t* row_offsets_b;   /* dev [G + 1] */
+  int64_t rows_a, rows_b;                                /* total rows of A, of B */
+  int32_t maximize;                                      /* 0 | 1 */
+  int32_t reserved1;
+  int32_t* col_of_row;                                   /* dev [rows_a] */
+  int32_t* row_of_col;                                   /* dev [rows_b] */
+  int32_t* status;                                       /* dev [G] */
+  void* stream;
+} la3d_assign_args;
+typedef struct la3d_iou_groups_args {
+  int32_t struct_size;                                   /* sizeof(la3d_iou_groups_args) of the caller */
+  int32_t G;                                             /* groups */
+  const double* boxes_a; const double* boxes_b;          /* dev f64 [rows_a][4], [rows_b][4], xyxy */
+  int64_t rows_a, rows_b;
+  const int32_t* row_offsets_a; const int32_t* row_offsets_b;   /* dev [G + 1] */
+  const int64_t* offsets;                                /* dev [G + 1] */
+  int64_t npairs;                                        /* offsets[G] */
+  double* out;                                           /* dev f64 [npairs] */
+  void* stream;
+} la3d_iou_groups_args;
+int la3d_assign(const la3d_assign_args* args);
+int la3d_iou_matrix_groups(const la3d_iou_groups_args* args);
+
 /* HOST helper: COCO compressed RLE string (pycocotools rleFrString) -> run lengths.  Returns the number of
  * counts written, or -1 (malformed string / cap too small). */
 int la3d_rle_from_string_host(const char* s, int64_t len, int32_t* counts, int cap);

@@ -143,6 +143,24 @@ class MaskNmsArgs(C.Structure):
                 ("order", C.c_void_p), ("labels", C.c_void_p), ("thr", C.c_double), ("keep", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class AssignArgs(C.Structure):
+    """``la3d_assign_args`` of include/la3d.h (argument block of la3d_assign, 112 bytes); field order is the header's."""
+    _fields_ = [("struct_size", C.c_int32), ("G", C.c_int32), ("cost", C.c_void_p), ("cost_dtype", C.c_int32), ("reserved0", C.c_int32),
+                ("ncost", C.c_int64), ("offsets", C.c_void_p), ("row_offsets_a", C.c_void_p), ("row_offsets_b", C.c_void_p),
+                ("rows_a", C.c_int64), ("rows_b", C.c_int64), ("maximize", C.c_int32), ("reserved1", C.c_int32),
+                ("col_of_row", C.c_void_p), ("row_of_col", C.c_void_p), ("status", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class IouGroupsArgs(C.Structure):
+    """``la3d_iou_groups_args`` of include/la3d.h (argument block of la3d_iou_matrix_groups, 88 bytes); field order is the header's."""
+    _fields_ = [("struct_size", C.c_int32), ("G", C.c_int32), ("boxes_a", C.c_void_p), ("boxes_b", C.c_void_p),
+                ("rows_a", C.c_int64), ("rows_b", C.c_int64), ("row_offsets_a", C.c_void_p), ("row_offsets_b", C.c_void_p),
+                ("offsets", C.c_void_p), ("npairs", C.c_int64), ("out", C.c_void_p), ("stream", C.c_void_p)]
+
+
+ASSIGN_F64, ASSIGN_I32 = 0, 1                                          # la3d_assign_args.cost_dtype
+ASSIGN_MAX_N, ASSIGN_STAGE_MAX = 256, 2048                             # rows / columns of a group; elements staged in LDS
+ASSIGN_OK, ASSIGN_INVALID, ASSIGN_INFEASIBLE, ASSIGN_TOO_LARGE, ASSIGN_BROKEN = 0, 1, 2, 3, 4   # status of a group
 OVERLAP_NONE, OVERLAP_IOU, OVERLAP_IOM, OVERLAP_IOA = 0, 1, 2, 3      # la3d_mask_overlap_args.kind
 OVERLAP_MIRROR, OVERLAP_AREA_A, OVERLAP_AREA_B = 1, 2, 4              # la3d_overlap_tile.flags
 OVERLAP_TILE, OVERLAP_STEP = 8, 1024                                   # planes per side of a tile; words a chunk is a multiple of
@@ -152,6 +170,8 @@ _SIGS = {
     "la3d_mask_overlap_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "la3d_mask_overlap": (C.c_int, [C.POINTER(MaskOverlapArgs)]),
     "la3d_mask_nms": (C.c_int, [C.POINTER(MaskNmsArgs)]),
+    "la3d_assign": (C.c_int, [C.POINTER(AssignArgs)]),
+    "la3d_iou_matrix_groups": (C.c_int, [C.POINTER(IouGroupsArgs)]),
     "la3d_components_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "la3d_components_bits": (C.c_int, [C.POINTER(ComponentsArgs)]),
     "la3d_components_bits_frames": (C.c_int, [C.POINTER(ComponentsFramesArgs)]),

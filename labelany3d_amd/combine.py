@@ -3,7 +3,8 @@
 JSON.  Same arguments, files, printed messages, ids, key order and skip rules; the arithmetic runs on the MI355X in batched form:
 the 8 corners of EVERY annotation of the split are projected in one ``la3d_project_boxes`` launch (the reference: eight ``np.dot``
 per box, :105-108, :233-239), and each scene's IoU matrix comes from ``la3d_iou_matrix`` (the reference: a Python double loop,
-:111-136); the assignment is SciPy's ``linear_sum_assignment`` as in the reference (:138).
+:111-136); the assignment is SciPy's ``linear_sum_assignment`` as in the reference (:138) - or, with ``matching="device"``, one
+``match_boxes`` call for all scenes (SciPy's arithmetic on the device, the same pairs).
 
 The category table (COCO names with Omni3D-style ids, :17-99) is data: ``labelany3d_amd/data/omni3d_coco_categories.json``.
 """
@@ -29,8 +30,13 @@ def _load(path):
         return json.load(f)
 
 
-def combine_coco_results(results_dir, split, output_path, bbox_filename="3dbbox.json"):
-    """See the module docstring; reference src/tools/combine_results.py:146-310."""
+def combine_coco_results(results_dir, split, output_path, bbox_filename="3dbbox.json", matching="host"):
+    """See the module docstring; reference src/tools/combine_results.py:146-310.  ``matching``: "host" - one IoU matrix per scene
+    copied back and assigned with SciPy, as the reference does - or "device": every scene of the split matched by ONE ``match_boxes``
+    call (grouped IoU + the batched assignment, SciPy's arithmetic step for step) and one copy back.  A scene with more boxes on a
+    side than the device solver takes (``assign.MAX_N``) is matched on the host."""
+    if matching not in ("host", "device"):
+        raise ValueError(f"combine_coco_results: matching must be 'host' or 'device', not {matching!r}")
     from scipy.optimize import linear_sum_assignment
 
     categories = coco_categories()
@@ -99,6 +105,7 @@ def combine_coco_results(results_dir, split, output_path, bbox_filename="3dbbox.
 
     # ---- pass 3: records, then the per-scene matching ---------------------------------------------------------------------------
     annotations = []
+    pending = []                     # matching="device": (records, bbox2d) of every scene that is matched
     r = 0
     for img_id, K, H, W, kept, bbox2d in scenes:
         local = []
@@ -116,15 +123,34 @@ def combine_coco_results(results_dir, split, output_path, bbox_filename="3dbbox.
             })
             annotation_id += 1
         if bbox2d is not None and len(local) > 0 and len(bbox2d) > 0:
-            trunc = np.array([a["bbox2D_trunc"] for a in local], dtype=np.float64)
-            iou = iou2d_matrix(trunc, np.array(bbox2d, dtype=np.float64)).cpu().numpy()
-            rows, cols = linear_sum_assignment(-iou)
-            for i, j in zip(rows, cols):
-                local[i]["bbox2D_tight"] = bbox2d[j]
+            if matching == "device":
+                pending.append((local, bbox2d))
+            else:
+                trunc = np.array([a["bbox2D_trunc"] for a in local], dtype=np.float64)
+                iou = iou2d_matrix(trunc, np.array(bbox2d, dtype=np.float64)).cpu().numpy()
+                rows, cols = linear_sum_assignment(-iou)
+                for i, j in zip(rows, cols):
+                    local[i]["bbox2D_tight"] = bbox2d[j]
         else:
             for a in local:
                 a["bbox2D_tight"] = a["bbox2D_trunc"]
         annotations.extend(local)
+    if pending:   # matching="device": all scenes in one call, one copy back
+        from .assign import match_boxes
+
+        c0, c1 = [len(recs) for recs, _ in pending], [len(b) for _, b in pending]
+        trunc = np.array([a["bbox2D_trunc"] for recs, _ in pending for a in recs], dtype=np.float64).reshape(-1, 4)
+        tight = np.array([b for _, bb in pending for b in bb], dtype=np.float64).reshape(-1, 4)
+        matched = match_boxes(trunc, tight, c0, c1)
+        status = matched.host()[2]
+        for g, (local, bbox2d) in enumerate(pending):
+            if status[g] == 0:
+                rows, cols = matched.pairs(g)
+            else:         # beyond the device solver's size (or an entry SciPy refuses: it then raises here as it does on the host path)
+                t = np.array([a["bbox2D_trunc"] for a in local], dtype=np.float64)
+                rows, cols = linear_sum_assignment(-iou2d_matrix(t, np.array(bbox2d, dtype=np.float64)).cpu().numpy())
+            for i, j in zip(rows, cols):
+                local[int(i)]["bbox2D_tight"] = bbox2d[int(j)]
 
     output = {
         "info": {"id": dataset_id, "source": "COCO", "name": f"COCO {'Validation' if val else 'Train'}", "split": split.capitalize(),

@@ -1,7 +1,8 @@
 """Box consumers on the device: what the reference does with the fitted boxes right after the
 path (src/tools/combine_results.py) — project the 8 corners with K, take the 2-D box and its clamp to the frame,
-and build the IoU matrix the Hungarian matching consumes.  The assignment itself stays scipy
-(`linear_sum_assignment`, as in the reference :138): it is a tiny sequential problem per image."""
+and build the IoU matrix the Hungarian matching consumes.  ``hungarian_matching`` here assigns with SciPy
+(`linear_sum_assignment`, as in the reference :138), one image per call; ``assign.match_boxes`` does the same for every image of a
+call on the device, with SciPy's arithmetic."""
 from __future__ import annotations
 
 import numpy as np

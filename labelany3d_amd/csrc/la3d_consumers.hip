@@ -42,15 +42,39 @@ __global__ __launch_bounds__(128) void project_boxes_kernel(const double* __rest
 
 // IoU of every pair of xyxy boxes (iou2D, reference src/tools/combine_results.py:111-124): the negated matrix is
 // the Hungarian cost matrix of :131-135.
+__device__ __forceinline__ double iou2d(const double* __restrict__ p, const double* __restrict__ q) {
+  const double x1 = fmax(p[0], q[0]), y1 = fmax(p[1], q[1]), x2 = fmin(p[2], q[2]), y2 = fmin(p[3], q[3]);
+  const double inter = fmax(0.0, x2 - x1) * fmax(0.0, y2 - y1);
+  return inter / ((p[2] - p[0]) * (p[3] - p[1]) + (q[2] - q[0]) * (q[3] - q[1]) - inter + 1e-6);
+}
 __global__ __launch_bounds__(256) void iou_matrix_kernel(const double* __restrict__ a, int na, const double* __restrict__ b,
                                                          int nb, double* __restrict__ out) {
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   if (t >= (long long)na * nb) return;
-  const double* p = a + (t / nb) * 4;
-  const double* q = b + (t % nb) * 4;
-  const double x1 = fmax(p[0], q[0]), y1 = fmax(p[1], q[1]), x2 = fmin(p[2], q[2]), y2 = fmin(p[3], q[3]);
-  const double inter = fmax(0.0, x2 - x1) * fmax(0.0, y2 - y1);
-  out[t] = inter / ((p[2] - p[0]) * (p[3] - p[1]) + (q[2] - q[0]) * (q[3] - q[1]) - inter + 1e-6);
+  out[t] = iou2d(a + (t / nb) * 4, b + (t % nb) * 4);
+}
+
+// The same for G groups in one launch (la3d_iou_matrix_groups): element t of [0, npairs) finds its group in offsets - the last g with
+// offsets[g] <= t - and its pair in the group's row-major matrix.  Every table value is checked before a box is addressed with it: an
+// element that lies in no group's matrix, or whose rows lie outside the boxes, gets NaN.
+struct IouGroupsParams {
+  const double* a; const double* b; long long rows_a, rows_b;
+  const int* row_a; const int* row_b; const long long* offsets; long long npairs; double* out; int G;
+};
+__global__ __launch_bounds__(256) void iou_matrix_groups_kernel(const IouGroupsParams p) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= p.npairs) return;
+  int lo = 0, hi = p.G - 1;          // (G >= 1)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (p.offsets[mid] <= t) lo = mid; else hi = mid - 1;
+  }
+  const long long k = t - p.offsets[lo];
+  const long long a0 = p.row_a[lo], na = (long long)p.row_a[lo + 1] - a0, b0 = p.row_b[lo], nb = (long long)p.row_b[lo + 1] - b0;
+  double r = NAN;
+  if (k >= 0 && na > 0 && nb > 0 && k < na * nb && a0 >= 0 && a0 + na <= p.rows_a && b0 >= 0 && b0 + nb <= p.rows_b)
+    r = iou2d(p.a + (a0 + k / nb) * 4, p.b + (b0 + k % nb) * 4);
+  p.out[t] = r;
 }
 
 // Masked depth-ratio median — reference src/util.py:476-486 (align_to_depth_match): overlap = mask_a & mask_b,
@@ -689,6 +713,23 @@ int la3d_iou_matrix(const double* boxes_a, int na, const double* boxes_b, int nb
   hipLaunchKernelGGL(iou_matrix_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      boxes_a, na, boxes_b, nb, out);
   return check_launch("iou_matrix_kernel");
+}
+
+int la3d_iou_matrix_groups(const la3d_iou_groups_args* args) {
+  const char* who = "la3d_iou_matrix_groups";
+  if (!args || args->struct_size != (int32_t)sizeof(la3d_iou_groups_args)) return refuse(who, "NULL block or a struct_size that is not sizeof(la3d_iou_groups_args)");
+  const la3d_iou_groups_args& a = *args;
+  if (a.G < 0 || a.rows_a < 0 || a.rows_b < 0 || a.npairs < 0) return refuse(who, "negative G, rows_a, rows_b or npairs");
+  if (a.G == 0 || a.npairs == 0) return LA3D_SUCCESS;
+  if (a.npairs > 0x7fffffffLL * 256) return refuse(who, "more than 2^39 pairs in one call", LA3D_ERR_UNSUPPORTED);
+  if (!a.boxes_a || !a.boxes_b || !a.row_offsets_a || !a.row_offsets_b || !a.offsets || !a.out) return refuse(who, "NULL boxes_a, boxes_b, row_offsets_a, row_offsets_b, offsets or out");
+  const auto at = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+  if ((at(a.boxes_a) | at(a.boxes_b) | at(a.offsets) | at(a.out)) & 7) return refuse(who, "boxes_a, boxes_b, offsets or out not an 8-byte aligned pointer");
+  if ((at(a.row_offsets_a) | at(a.row_offsets_b)) & 3) return refuse(who, "row_offsets_a or row_offsets_b not a 4-byte aligned pointer");
+  const IouGroupsParams p = {a.boxes_a, a.boxes_b, a.rows_a, a.rows_b, a.row_offsets_a, a.row_offsets_b,
+                             reinterpret_cast<const long long*>(a.offsets), a.npairs, a.out, a.G};
+  hipLaunchKernelGGL(iou_matrix_groups_kernel, dim3((unsigned)((a.npairs + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(a.stream), p);
+  return check_launch("iou_matrix_groups_kernel");
 }
 
 }  // extern "C"

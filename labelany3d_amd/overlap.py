@@ -229,8 +229,9 @@ def mask_overlap(a, b=None, counts_a=None, counts_b=None, frames=None, iou=None,
 
 
 def mask_iou(a, b=None, counts_a=None, counts_b=None, frames=None, stream=None, plan=None) -> MaskOverlap:
-    """``mask_overlap(..., iou="iou")``: the mask-level IoU matrix of every image - ``matrix(g, "iou")`` is what
-    ``scipy.optimize.linear_sum_assignment`` takes (negated), the way ``hungarian_matching`` takes the box-level one."""
+    """``mask_overlap(..., iou="iou")``: the mask-level IoU matrix of every image - what ``assign.assign_overlap`` matches on the
+    device (``matrix(g, "iou")``, negated, is what ``scipy.optimize.linear_sum_assignment`` takes, the way ``hungarian_matching``
+    takes the box-level one: the same answer)."""
     return mask_overlap(a, b, counts_a=counts_a, counts_b=counts_b, frames=frames, iou="iou", stream=stream, plan=plan)
 
 
