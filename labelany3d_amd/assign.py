@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
-from .batched import _as_dev, _dev, _record, _stream, _upload_many
+from ._device import _as_dev, _dev, _record, _stream, _upload_many
 from .overlap import MaskOverlap, _counts, mask_overlap
 
 MAX_N = _lib.ASSIGN_MAX_N

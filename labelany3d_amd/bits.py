@@ -1,22 +1,20 @@
 """Masks as bit planes of ONE frame size per call (include/la3d.h "masks as bit planes" and what followed it): ``MaskBits``, the packers
-(u8 masks, logits, run lengths, polygons), the restore of crop-space masks, the unpacker and the plane statistics, the way back out -
-the run-length encoder (``RleRuns``) -, morphology and the crop gate, and the fit that takes the planes (``fit_instances_bits``).
-Label maps build on this module (``labels``); the mixed-size forms live in ``frames``.  ``masks`` re-exports the public names."""
+(u8 masks, logits, run lengths, polygons), the restore of crop-space masks, the unpacker and the plane statistics, and the fit that takes
+the planes (``fit_instances_bits``).  ``labels`` builds on this module; mixed-size packers: ``frames``; plane operations: ``morph``, ``rle_encode``."""
 from __future__ import annotations
 
 import contextlib
-import ctypes as C
 from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._device import _as_dev, _dev, _plane_source, _ptr, _record, _stream, _upload_many
 from ._lib import check, lib
-from .batched import (Depth16, _as_dev, _bits_stride, _depth16_check, _dev, _plane_source, _ptr, _record, _stream, _upload_many, height_rule_code,
-                      padded_width)
+from .batched import Depth16, _bits_stride, _depth16_check, height_rule_code, padded_width
 from .fitcall import depth_rows_for_bits, fit_call, mask_source
-from .masks import pack_rle
+from .segm import pack_rle
 
 
 class MaskBits(NamedTuple):
@@ -302,228 +300,6 @@ def mask_stats_bits(bits, boundary_threshold: int = 10, stream=None) -> torch.Te
                                        int(boundary_threshold), _ptr(out), _stream(stream)), "la3d_mask_stats_bits")
     _record(stream, mb.bits, out)
     return out
-
-
-# ---- bit planes as run lengths (include/la3d.h "bit planes as run lengths") ----------------------------------------------------------
-class RleRuns(NamedTuple):
-    """What ``rle_encode_bits`` / ``rle_encode`` return: the COCO run lengths of B masks of one frame size, on the GPU - ``counts``
-    int32 (capacity,): the run list of instance n is ``counts[offsets[n]:offsets[n+1]]``, column-major over (H, W), zeros first;
-    ``offsets`` int64 (B+1,); ``H``, ``W``: the IMAGE (W = its columns, never a padded pitch).  It is the 4-tuple ``pack_rle`` passes
-    through: ``fit_instances_rle``, ``fit_instances_ex(rles=...)``, ``pack_rle_bits``, ``rle_decode`` and ``mask_stats_rle`` take it as
-    it is."""
-    counts: torch.Tensor
-    offsets: torch.Tensor
-    H: int
-    W: int
-
-
-def rle_to_string(counts) -> str:
-    """Run lengths -> COCO compressed RLE string (pycocotools rleToString), via the library's host helper: the inverse of
-    ``rle_from_string``."""
-    c = np.ascontiguousarray(counts.cpu().numpy() if isinstance(counts, torch.Tensor) else counts, dtype=np.int32).reshape(-1)
-    cap = 7 * len(c) + 1   # (a count or a difference of two has at most 33 bits and a sign: seven 5-bit groups)
-    buf = C.create_string_buffer(cap)
-    n = lib.la3d_rle_to_string_host(c.ctypes.data, len(c), buf, cap)
-    if n < 0:
-        raise ValueError("la3d_rle_to_string_host refused the counts")
-    return buf.raw[:n].decode("ascii")
-
-
-def _rle_capacity(who: str, capacity) -> None:
-    if capacity is not None and (not isinstance(capacity, (int, np.integer)) or isinstance(capacity, bool) or int(capacity) < 0):
-        raise ValueError(f"{who}: capacity must be None or an int >= 0, not {capacity!r}")
-
-
-def _rle_encode_run(a: _lib.RleEncodeArgs, B: int, dev, capacity, stream, keep):
-    """Both stages of one call.  ``a``: the block with every input set -> (counts, offsets, status)."""
-    with torch.cuda.device(dev):
-        a.stream = _stream(stream)
-        runs = torch.empty(max(B, 1), dtype=torch.int32, device=dev)
-        offsets = torch.empty(B + 1, dtype=torch.int64, device=dev)
-        ws = torch.empty(max(int(lib.la3d_rle_encode_workspace_bytes(B, a.H, a.W)) // 8, 1), dtype=torch.int64, device=dev)
-        a.runs, a.offsets, a.workspace = runs.data_ptr(), offsets.data_ptr(), ws.data_ptr()
-        check(lib.la3d_rle_encode_offsets(C.byref(a)), "la3d_rle_encode_offsets")
-        if capacity is None:
-            if stream is not None and stream != torch.cuda.current_stream():
-                stream.synchronize()
-            cap = int(offsets[-1].item())   # the ONE synchronisation of the call: the exact size
-        else:
-            cap = int(capacity)
-        counts = torch.empty(cap, dtype=torch.int32, device=dev) if cap else torch.zeros(1, dtype=torch.int32, device=dev)   # (the consumers take no NULL)
-        status = torch.empty(max(B, 1), dtype=torch.int32, device=dev)[:B]
-        a.counts, a.status, a.capacity = counts.data_ptr(), status.data_ptr(), cap
-        check(lib.la3d_rle_encode(C.byref(a)), "la3d_rle_encode")
-    _record(stream, runs, offsets, ws, counts, status, *keep)
-    return counts, offsets, status
-
-
-def rle_encode_bits(bits: MaskBits, capacity=None, stream=None, return_status: bool = False):
-    """``MaskBits`` -> ``RleRuns`` on the GPU (C-ABI ``la3d_rle_encode_offsets`` + ``la3d_rle_encode``): ``binary_mask_to_rle``
-    (reference src/download_coconut.py:167-175) for a batch - the planes of any packer (``pack_mask_bits``, ``pack_logits_bits``,
-    ``pack_label_bits(...).bits``, ``pack_poly_bits``, ``pack_crop_bits``) become COCO run lengths without leaving the device: the
-    fastest source of the fit, a few hundred bytes per instance, what ``fit_annotations_sharded`` ships and the annotation JSON stores
-    (``rle_objects``).  The runs cover the image (``bits.H`` x ``bits.frame_width``): pad columns are never mask.
-    ``capacity=None`` reads ``offsets[-1]`` back once - the call's ONLY host synchronisation - and allocates ``counts`` exactly;
-    ``capacity=int`` never synchronises (the chain can be captured into a graph): an instance whose run list does not fit gets status 1
-    and is not written, so ask for ``return_status=True`` then - ``(RleRuns, status int32 (B,))``: 0 ok, 1 no room, 2 the planes
-    changed between the two stages."""
-    if not isinstance(bits, MaskBits):
-        raise ValueError("rle_encode_bits: bits must be a MaskBits (pack_mask_bits, pack_logits_bits, pack_label_bits(...).bits, ...)")
-    _rle_capacity("rle_encode_bits", capacity)
-    mb = _mask_bits(bits)
-    B, dev = int(mb.bits.shape[0]), mb.bits.device
-    a = _lib.RleEncodeArgs(struct_size=C.sizeof(_lib.RleEncodeArgs), B=B, H=mb.H, W=mb.W, frame_width=0 if mb.frame_width == mb.W else mb.frame_width,
-                           mask_bits=mb.bits.data_ptr(), bits_plane_stride=_bits_stride(mb.bits, B, mb.H, mb.W))
-    counts, offsets, status = _rle_encode_run(a, B, dev, capacity, stream, [mb.bits])
-    runs = RleRuns(counts, offsets, mb.H, mb.frame_width)
-    return (runs, status) if return_status else runs
-
-
-def rle_encode(masks, device=None, stream=None) -> RleRuns:
-    """(B,H,W) bool / uint8 masks, on the host or the device -> ``RleRuns`` on the GPU: ``pack_mask_bits``, then ``rle_encode_bits``
-    (one host synchronisation, for the exact size)."""
-    return rle_encode_bits(pack_mask_bits(masks, frame_pad=True, device=device, stream=stream), stream=stream)
-
-
-def rle_objects(runs, compress: bool = False, sizes=None) -> list:
-    """Run lengths on the device -> the list of COCO RLE objects of the annotation JSON, ``{"size": [h, w], "counts": list}`` - or, with
-    ``compress=True``, ``counts`` as the compressed ``str`` of ``rle_to_string``.  ``runs``: an ``RleRuns``; or the ``(counts, offsets)``
-    of ``rle_encode_bits_frames`` with its ``sizes`` (B, 2).  ONE device-to-host copy (offsets, sizes and counts in one buffer)."""
-    if isinstance(runs, tuple) and len(runs) == 4:
-        counts, offsets, H, W = runs
-    elif isinstance(runs, tuple) and len(runs) == 2 and sizes is not None:
-        counts, offsets, H, W = runs[0], runs[1], None, None
-    else:
-        raise ValueError("rle_objects takes an RleRuns, or (counts, offsets) with sizes=")
-    if isinstance(counts, torch.Tensor) and counts.is_cuda:
-        B = int(offsets.numel()) - 1
-        parts = [offsets.to(counts.device).to(torch.int64).reshape(-1), counts.to(torch.int64).reshape(-1)]
-        if sizes is not None:
-            parts.insert(1, torch.as_tensor(sizes).to(counts.device).to(torch.int64).reshape(-1))
-        host = torch.cat(parts).cpu().numpy()
-        offs = host[:B + 1]
-        sz = host[B + 1:3 * B + 1].reshape(B, 2) if sizes is not None else None
-        cnt = host[(3 * B + 1) if sizes is not None else (B + 1):]
-    else:
-        offs, cnt = np.asarray(offsets, np.int64).reshape(-1), np.asarray(counts, np.int64).reshape(-1)
-        sz = None if sizes is None else np.asarray(sizes.cpu() if isinstance(sizes, torch.Tensor) else sizes, np.int64).reshape(-1, 2)
-    out = []
-    for n in range(len(offs) - 1):
-        c = cnt[offs[n]:offs[n + 1]]
-        out.append({"size": [int(H), int(W)] if sz is None else [int(sz[n, 0]), int(sz[n, 1])],
-                    "counts": rle_to_string(c) if compress else c.tolist()})
-    return out
-
-
-# ---- morphology on bit planes (include/la3d.h "morphology on bit planes") -------------------------------------------------------------
-def _open_scalars(who: str, k, upscale) -> None:   # the k and upscale of an opening, of either form
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 31 or int(k) % 2 == 0:
-        raise ValueError(f"{who}: k must be an odd int in 1 .. 31, not {k!r}")
-    if isinstance(upscale, bool) or not isinstance(upscale, (int, np.integer)) or int(upscale) not in (1, 2, 4):
-        raise ValueError(f"{who}: upscale must be 1, 2 or 4 (factors whose nearest-neighbour rule is u // s under every convention), not {upscale!r}")
-
-
-def _gate_scalars(who: str, min_area, crop_size) -> None:   # the gate of select_crops, of either form
-    if isinstance(min_area, bool) or not isinstance(min_area, (int, np.integer)) or int(min_area) < 0:
-        raise ValueError(f"{who}: min_area must be an int >= 0, not {min_area!r}")
-    if isinstance(crop_size, bool) or not isinstance(crop_size, (int, np.integer)) or int(crop_size) <= 0:
-        raise ValueError(f"{who}: crop_size must be an int > 0, not {crop_size!r}")
-
-
-def _open_args(who: str, bits, k, upscale) -> MaskBits:
-    if not isinstance(bits, MaskBits):
-        raise ValueError(f"{who}: bits must be a MaskBits (pack_mask_bits, pack_rle_bits, pack_poly_bits, pack_crop_bits, ...)")
-    _open_scalars(who, k, upscale)
-    mb = _mask_bits(bits)
-    if mb.H <= 0:
-        raise ValueError(f"{who}: the planes state an empty frame {(mb.H, mb.W)}")
-    return mb
-
-
-def _open_run(who: str, mb: MaskBits, k: int, s: int, W_out: int, out, want_stats: bool, stream):
-    """One ``la3d_open_bits`` call on checked arguments -> (out, stats); ``out`` None: statistics only."""
-    B, dev = int(mb.bits.shape[0]), mb.bits.device
-    out_stride = 0 if out is None else _bits_stride(out, B, s * mb.H, W_out)
-    with torch.cuda.device(dev):
-        stats = ws = None
-        if want_stats:
-            stats = torch.empty((B, 5), dtype=torch.int32, device=dev)
-            ws = torch.empty(max(int(lib.la3d_open_bits_workspace_bytes(B, mb.H, s)) // 4, 1), dtype=torch.int32, device=dev)
-        if B:   # (an empty batch has no planes to point at)
-            check(lib.la3d_open_bits(_ptr(mb.bits), _bits_stride(mb.bits, B, mb.H, mb.W), B, mb.H, mb.W, mb.frame_width, k, s,
-                                     _ptr(out), out_stride, W_out, _ptr(stats), _ptr(ws), _stream(stream)), "la3d_open_bits")
-    _record(stream, mb.bits, out, stats, ws)
-    return out, stats
-
-
-def open_bits(bits: MaskBits, k: int = 7, upscale: int = 1, frame_pad: bool = True, stream=None, out=None, return_stats: bool = False):
-    """Binary opening of bit planes on the GPU (C-ABI ``la3d_open_bits``): ``scipy.ndimage.binary_opening(U, np.ones((k, k)))`` of the
-    nearest-neighbour upscale ``U[v, u] = M[v // s, u // s]`` of every plane, ``s = upscale`` - the crop stage's mask step (reference
-    src/batch_scripts/get_crops_enhanced.py:68-88: x4, k = 7); at ``upscale=1`` it strips speckle and hairlines from network masks
-    before a fit.  ``k``: odd, 1 .. 31 (1 = identity); ``upscale``: 1, 2 or 4.  Returns ``MaskBits`` of ``s*H`` rows and ``s*frame_width``
-    image columns, stored ``padded_width(s*frame_width)`` wide with ``frame_pad`` (else unpadded) - or ``(MaskBits, stats)`` with
-    ``return_stats``: ``stats`` int32 (B, 5) on the device, ``area, x, y, w, h`` of each opened plane (``cv2.boundingRect``'s
-    convention; zeros for an empty plane).  ``out``: an int32 (B, >= words) device tensor to fill; it must not overlap the input (the
-    call cannot work in place).  No host synchronisation; capturable."""
-    who = "open_bits"
-    mb = _open_args(who, bits, k, upscale)
-    k, s = int(k), int(upscale)
-    B, dev = int(mb.bits.shape[0]), mb.bits.device
-    fw = s * mb.frame_width
-    W_out = padded_width(fw) if frame_pad else fw
-    if out is not None and isinstance(out, torch.Tensor) and out.device != dev:
-        raise ValueError(f"{who}: out lives on another device")
-    o = _bits_out(out, B, s * mb.H, W_out, dev)
-    o, stats = _open_run(who, mb, k, s, W_out, o, bool(return_stats), stream)
-    res = MaskBits(o, s * mb.H, W_out, fw)
-    return (res, stats) if return_stats else res
-
-
-def bits_rects(bits: MaskBits, stream=None) -> torch.Tensor:
-    """``MaskBits`` -> int32 (B, 5) on the device: ``area, x, y, w, h`` of every plane - the statistics-only call of ``la3d_open_bits``
-    with ``k = 1, upscale = 1`` (nothing but the planes is read, no plane is written)."""
-    mb = _open_args("bits_rects", bits, 1, 1)
-    return _open_run("bits_rects", mb, 1, 1, mb.frame_width, None, True, stream)[1]
-
-
-def crop_params(stats, crop_size: int = 512, upscale: int = 4, ratio: float = 0.7) -> np.ndarray:
-    """The crop parameters of the reference's crop stage from the rectangles of opened planes: ``stats`` (B, 5) ``area, x, y, w, h``
-    (``open_bits(..., return_stats=True)``, ``bits_rects``; a (B, 4) array is taken as ``x, y, w, h``) -> float64 (B, 3) rows
-    ``(offset_x, offset_y, scale_factor)``, what ``crop_placement`` / ``pack_crop_bits`` take.  Host arithmetic on Python numbers,
-    exactly the reference's (``crop_object``, src/util.py:142-157, then src/batch_scripts/get_crops_enhanced.py:98):
-    ``side = int(max(w, h) / ratio)``, ``ox = x + (w - side) / 2``, ``oy = y + (h - side) / 2``, ``sf = crop_size / side``; the row is
-    ``[ox / upscale, oy / upscale, sf * upscale]`` - the rectangle is measured on the upscaled image, the parameters speak of the
-    original one.  Rows with ``w == 0`` (an empty plane) are NaN."""
-    a = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats)
-    if a.ndim != 2 or a.shape[1] not in (4, 5):
-        raise ValueError(f"crop_params: stats must be (B, 5) area, x, y, w, h or (B, 4) x, y, w, h, got {a.shape}")
-    if not (crop_size > 0 and upscale > 0 and ratio > 0):
-        raise ValueError("crop_params: crop_size, upscale and ratio must be positive")
-    out = np.full((a.shape[0], 3), np.nan, np.float64)
-    for n, row in enumerate(a[:, -4:].tolist()):
-        x, y, w, h = (int(v) for v in row)
-        if w <= 0 or h <= 0:
-            continue
-        side = int(max(w, h) / ratio)
-        ox, oy, sf = x + (w - side) / 2, y + (h - side) / 2, crop_size / side
-        out[n] = [ox / upscale, oy / upscale, sf * upscale]
-    return out
-
-
-def select_crops(bits: MaskBits, min_area: int = 6400, k: int = 7, upscale: int = 4, crop_size: int = 512, stream=None):
-    """The instance selection of the reference's crop stage (src/batch_scripts/get_crops_enhanced.py:68-99) for a batch of planes:
-    ``open_bits(bits, k, upscale)``, then ``keep = area >= min_area`` and ``crop_params`` of the rectangles -> ``(keep, params, stats,
-    opened)``: ``keep`` bool (B,) and ``params`` float64 (B, 3) NumPy arrays (NaN rows for empty planes), ``stats`` int32 (B, 5) on the
-    device, ``opened`` the ``MaskBits`` of the opened, upscaled planes.  The defaults are the reference's gate (x4, 7 x 7, 6400
-    surviving pixels, 512-pixel crops); one device-to-host copy (the statistics).  The reference walks the instances LAST TO FIRST and
-    appends the boxes it keeps to ``bboxes.json`` in that order: rows here stay in the caller's order, and the order of
-    ``bboxes.json`` is the caller's business."""
-    _gate_scalars("select_crops", min_area, crop_size)
-    opened, stats = open_bits(bits, k=k, upscale=upscale, frame_pad=True, stream=stream, return_stats=True)
-    if stream is not None and stream != torch.cuda.current_stream():
-        stream.synchronize()
-    host = stats.cpu().numpy()
-    return host[:, 0] >= int(min_area), crop_params(host, crop_size=int(crop_size), upscale=int(upscale)), stats, opened
 
 
 def fit_instances_bits(depth, bits, K, ground=None, sample_idx=None, image_index=None, stream=None, device=None, filter=None,

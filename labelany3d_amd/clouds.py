@@ -12,7 +12,8 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
-from .batched import Depth16, _as_dev, _bits_stride, _depth16_block, _depth16_check, _dev, _fit_inputs, _record, _stream
+from ._device import _as_dev, _dev, _record, _stream
+from .batched import Depth16, _bits_stride, _depth16_block, _depth16_check, _fit_inputs
 from .fitcall import depth_rows_for_bits
 from .frames import FrameBits, _frames_depth, _on_gpu, _same_table
 from .bits import _PackedBits, _mask_bits

@@ -136,7 +136,7 @@ def combine_coco_results(results_dir, split, output_path, bbox_filename="3dbbox.
                 a["bbox2D_tight"] = a["bbox2D_trunc"]
         annotations.extend(local)
     if pending:   # matching="device": all scenes in one call, one copy back
-        from .assign import match_boxes
+        from .assign import match_boxes   # (lazy on purpose: the host matching needs none of the device layers behind ``assign``)
 
         c0, c1 = [len(recs) for recs, _ in pending], [len(b) for _, b in pending]
         trunc = np.array([a["bbox2D_trunc"] for recs, _ in pending for a in recs], dtype=np.float64).reshape(-1, 4)

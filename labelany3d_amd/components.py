@@ -12,17 +12,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._device import _as_dev, _int_arg, _record, _stream
 from ._lib import check, lib
-from .batched import _bits_stride, _record, _stream
+from .batched import _bits_stride
 from .bits import MaskBits, _bits_out, _mask_bits
-from .frames import _TABLED, FrameBits, _as_dev, _on_gpu, _same_table
-
-
-def _int_arg(who: str, name: str, v, lo: int, hi=None) -> int:
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < lo or (hi is not None and int(v) > hi):
-        rng = f">= {lo}" if hi is None else f"in {lo} .. {hi}"
-        raise ValueError(f"{who}: {name} must be an int {rng}, not {v!r}")
-    return int(v)
+from .frames import FrameBits, _flat_out, _on_gpu, _tabled
 
 
 def _components_scalars(who: str, min_area, largest, connectivity, max_components, max_runs) -> None:
@@ -124,9 +118,7 @@ def drop_islands_bits(bits: MaskBits, min_area: int, connectivity: int = 8, max_
 
 # ---- the planes of images of different sizes (include/la3d.h "connected components on bit planes", la3d_components_bits_frames) ------
 def _components_frames_check(who: str, frames, bits, min_area, largest, connectivity, max_components, max_runs) -> None:
-    if not isinstance(frames, _TABLED):
-        raise ValueError(f"{who}: frames must be a PackedFrames / PackedFrames16 / PackedLabels / PackedMasks / FrameGrid")
-    _same_table(frames, bits)
+    _tabled(who, frames, bits)
     _components_scalars(who, min_area, largest, connectivity, max_components, max_runs)
     H, W = int(frames.H), int(frames.W)
     if H * ((W + 31) // 32 * 32) > 1048576:
@@ -176,14 +168,7 @@ def components_bits_frames(frames, bits: FrameBits, min_area: int = 0, largest: 
     who = "components_bits_frames"
     _components_frames_check(who, frames, bits, min_area, largest, connectivity, max_components, max_runs)
     total = int(bits.bits.numel())
-    if out is not None:
-        if isinstance(out, torch.Tensor) and out.dtype == torch.int32 and out.dim() == 1:
-            a0, b0 = out.data_ptr(), bits.bits.data_ptr()
-            if a0 < b0 + 4 * total and b0 < a0 + 4 * out.numel():
-                raise ValueError(f"{who}: out overlaps the input planes (the call cannot work in place)")
-        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int32 and out.dim() == 1 and out.is_contiguous()
-                and out.numel() >= total and out.data_ptr() % 16 == 0):
-            raise ValueError(f"{who}: out must be a flat, 16-byte aligned int32 device tensor of at least {total} words")
+    _flat_out(who, out, total, bits.bits)
     dev = _on_gpu(frames.table, bits.bits)
     if out is not None and out.device != dev:
         raise ValueError(f"{who}: out lives on another device")

@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
-from .batched import _as_dev, _dev, _ptr, _stream
+from ._device import _as_dev, _dev, _ptr, _stream
 
 
 def project_boxes(boxes, K, image_size, image_index=None, stream=None) -> torch.Tensor:

@@ -9,7 +9,8 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
-from .batched import Depth16, _depth16_block, _depth16_check, _dev, _plane_source, _ptr, _record, _stream, padded_width
+from ._device import _dev, _plane_source, _ptr, _record, _stream
+from .batched import Depth16, _depth16_block, _depth16_check, padded_width
 
 _D16_DTYPES = {"f16": (torch.float16, _lib.DTYPE_F16), "u16": (torch.uint16, _lib.DTYPE_U16)}
 

@@ -15,15 +15,14 @@ alignment helpers, on the MI355X.
 """
 from __future__ import annotations
 
-import numpy as np
-import torch
-
 import ctypes as C
 from typing import NamedTuple
 
+import numpy as np
+import torch
+
+from ._device import _as_dev, _dev, _ptr, _record, _stream
 from ._lib import AlignRansacArgs, check, lib
-from .batched import _as_dev, _dev, _ptr, _record, _stream
-from .masks import masked_ratio_median
 
 
 def align_select(relative_depth, metric_depth, mask=None, max_valid_depth: float = 400.0, device=None, stream=None):
@@ -208,6 +207,31 @@ def align_depth_batch(relative_depth, metric_depth, mask=None, min_samples=0.2, 
                                          _stream(stream)), "la3d_align_apply_batch")
     _record(stream, rel, met, m, out)
     return out, res
+
+
+def masked_ratio_median(depth_map, depth_render, mask, render_mask=None, image_index=None, stream=None):
+    """Per instance ``np.median(depth_map[overlap] / depth_render[overlap])`` with ``overlap = mask & render_mask``
+    — the scale estimate of the reference's align_to_depth_match (src/util.py:476-486), exact (radix select on
+    the float32 ratios).  depth_map (P,H,W) or (H,W); depth_render, mask, render_mask (B,H,W).
+    Returns (median float32 (B,), count int32 (B,)) on the GPU; an empty overlap gives count 0 and NaN (the
+    reference returns the identity transform there, :476-478)."""
+    dev = mask.device if isinstance(mask, torch.Tensor) and mask.is_cuda else _dev()
+    m = _as_dev(mask, torch.uint8, dev)
+    B, H, W = m.shape
+    rm = None if render_mask is None else _as_dev(render_mask, torch.uint8, dev)
+    d = _as_dev(depth_map, torch.float32, dev)
+    if d.dim() == 2:
+        d = d[None]
+    r = _as_dev(depth_render, torch.float32, dev)
+    ii = None if image_index is None else _as_dev(image_index, torch.int32, dev)
+    if ii is None and d.shape[0] not in (1, B):
+        raise ValueError("without image_index, depth_map must have 1 or B planes")
+    med = torch.empty(B, dtype=torch.float32, device=dev)
+    cnt = torch.empty(B, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.la3d_masked_ratio_median(_ptr(d), H * W if d.shape[0] > 1 else 0, _ptr(ii), _ptr(r), _ptr(m), _ptr(rm), B, H, W,
+                                           _ptr(med), _ptr(cnt), _stream(stream)), "la3d_masked_ratio_median")
+    return med, cnt
 
 
 def _as_batch(x):

@@ -39,14 +39,17 @@ from typing import Dict, Iterable, Iterator, List, Optional
 import numpy as np
 import torch
 
+from ._device import _dev, _upload_many
 from ._lib import lib, method_code
-from .batched import Depth16, _dev, _upload_many, draw_sample_idx, refuse_depth16
-from .jsonout import SceneRecords, format_scenes
+from .batched import Depth16, InstanceFitter, draw_sample_idx, pad_depth_rows, padded_width, refuse_depth16
+from .bits import pack_poly_bits, pack_rle_bits
+from .clouds import instance_points, instance_points_frames
 from .frames import (PackedFrames, PackedFrames16, _table_fields, fit_instances_frames, frame_table, pack_poly_bits_frames, pack_rle_bits_frames,
                      pack_rle_frames)
-from .masks import (area_hint_of, fit_instances_ex, mask_stats_poly, mask_stats_rle, pack_poly_bits, pack_polygons, pack_rle, pack_rle_bits,
-                    pad_depth_rows, padded_width, split_annotations)
+from .jsonout import SceneRecords, format_scenes
+from .masks import area_hint_of, fit_instances_ex, mask_stats_poly, mask_stats_rle, split_annotations
 from .ply import write_ply
+from .segm import pack_polygons, pack_rle
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 OUT_NAME = "3dbbox.json"
@@ -448,7 +451,6 @@ class ScenePipeline:
     def _fitter(self, kind, parity, B, H, W):
         """output buffers + workspace of a fit call, kept per (kind, ring slot, frame size) and sized by capacity (the number of
         annotations changes with every batch; a fresh InstanceFitter per call cost ~1 ms of allocations)"""
-        from .batched import InstanceFitter
         key = (kind, parity, H, W, self.method)
         f = self._fitters.pop(key, None)
         if f is None or f.B < B:
@@ -512,8 +514,6 @@ class ScenePipeline:
         """``export_points``: per annotation kind the clouds of the batch's instances on the host -> {kind: (points float32 (T,3),
         offsets int64 (B+1,))}.  The bit planes are packed once per kind; the gather reads its total back and ``.cpu()`` waits for the
         download: this thread is synchronised per kind, and every annotation's points move, whether a record comes of it or not."""
-        from .clouds import instance_points, instance_points_frames
-
         H, W = pr.H, pr.W
         out = {}
         for kind, (up, g) in pr.groups.items():

@@ -9,8 +9,8 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib, options
-from .batched import (Depth16, InstanceFitter, _as_dev, _bits_stride, _bulk, _enqueue, _fit_args, _fit_inputs, _pad_rows16, _ptr, _record,
-                      _stream, pad_depth_rows, padded_width)
+from ._device import _as_dev, _bulk, _ptr, _record, _stream
+from .batched import Depth16, InstanceFitter, _bits_stride, _enqueue, _fit_args, _fit_inputs, _pad_rows16, pad_depth_rows, padded_width
 
 
 class MaskSource(NamedTuple):
@@ -136,5 +136,5 @@ def fit_call(src: MaskSource, depth, K, dev, H, W, *, image_index, ground, sampl
                       opts=options.codes(), frame_width=frame_width, method=meth, **src.kw)
         _enqueue(a, src.bits, table)
     if stream is not None:
-        _record(stream, d, table and depth.table, k, ii, g, si, ah, *src.keep, f.workspace, *out.values())
+        _record(stream, d.data if isinstance(d, Depth16) else d, table and depth.table, k, ii, g, si, ah, *src.keep, f.workspace, *out.values())
     return out

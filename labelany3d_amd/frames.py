@@ -1,11 +1,9 @@
 """Images of DIFFERENT sizes in one call (include/la3d.h "images of different sizes in one call"): the frame table, the packers that
 lay depth maps, label maps and mask stacks out by it (``pack_frames`` / ``pack_label_frames`` / ``pack_mask_frames``: one staging
-routine, one table), the bit planes of their instances and the ``fit_instances_frames*`` fits (one check of the ``frames`` argument).
-The sources of one frame size live in ``masks``, ``bits``, ``labels`` and ``depth16``; ``masks`` re-exports the public names of this
-module; the call itself in ``fitcall``."""
+routine, one table), the bit planes of their instances, the ``fit_instances_frames*`` fits and the checks every entry on such planes
+shares (``_tabled``, ``_flat_out``, ``_on_gpu``).  ``morph``, ``rle_encode``, ``components``, ``overlap`` and ``clouds`` build on this module."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import NamedTuple, Optional
 
 import numpy as np
@@ -13,12 +11,13 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
-from .batched import Depth16, _as_dev, _d16_block, _depth16_check, _dev, _ptr, _record, _stream, _upload_many, height_rule_code, padded_width, refuse_depth16
-from .fitcall import FramesDepth, fit_call, mask_source
-from .bits import _LOGIT_DTYPES, _crop_place, _crop_source, _crop_threshold, _gate_scalars, _open_scalars, _rle_capacity, _rle_encode_run, crop_params
+from ._device import _as_dev, _dev, _ptr, _record, _stream, _upload_many
+from .batched import Depth16, _d16_block, _depth16_check, height_rule_code, padded_width, refuse_depth16
+from .bits import _LOGIT_DTYPES, _crop_place, _crop_source, _crop_threshold
 from .depth16 import _D16_DTYPES
+from .fitcall import FramesDepth, fit_call, mask_source
 from .labels import _LABEL_NUMPY, _LABEL_TORCH, _label_rows
-from .masks import _rle_counts
+from .segm import _rle_counts
 
 FRAME_DTYPE = np.dtype([("depth_offset", "<i8"), ("H", "<i4"), ("W", "<i4"), ("frame_width", "<i4"), ("reserved", "<i4")])
 """One row of the frame table of a frames call: ``la3d_frame`` of include/la3d.h (24 bytes)."""
@@ -215,6 +214,24 @@ def _same_table(frames, bits) -> None:
         raise ValueError("the bit planes were laid out for another frame table than the depth: pack depth and masks of the same sizes, in the same order")
 
 
+def _tabled(who: str, frames, *bits) -> None:   # the ``frames`` of an entry that reads only its frame table, and the planes laid out for it
+    if not isinstance(frames, _TABLED):
+        raise ValueError(f"{who}: frames must be a PackedFrames / PackedFrames16 / PackedLabels / PackedMasks / FrameGrid")
+    for b in bits:
+        _same_table(frames, b)
+
+
+def _flat_out(who, out, total, planes=None) -> None:
+    """A caller's flat ``out`` (None passes) may not overlap ``planes``, the buffer the call reads, and must hold ``total`` words (None: not asked)."""
+    if out is None:
+        return
+    flat = isinstance(out, torch.Tensor) and out.dtype == torch.int32 and out.dim() == 1
+    if planes is not None and flat and out.data_ptr() < planes.data_ptr() + 4 * planes.numel() and planes.data_ptr() < out.data_ptr() + 4 * out.numel():
+        raise ValueError(f"{who}: out overlaps the input planes (the call cannot work in place)")
+    if total is not None and not (flat and out.is_cuda and out.is_contiguous() and out.numel() >= total and out.data_ptr() % 16 == 0):
+        raise ValueError(f"{who + ': ' if who else ''}out must be a flat, 16-byte aligned int32 device tensor of at least {total} words")
+
+
 def _on_gpu(flat, planes=None) -> torch.device:   # the device step of a frames entry, after every argument check
     if not flat.is_cuda or not (planes is None or planes.is_cuda):
         raise ValueError("frames and bit planes must live on the GPU (pack_frames with a GPU device)")
@@ -338,14 +355,19 @@ def frame_bits_offsets(table, image_index):
     return offsets, int(step.sum())
 
 
+def _table_device(frames, out, total: int):   # a packer that reads only the frame table -> (the table's device, P), ``out`` checked there
+    if not (isinstance(frames.table, torch.Tensor) and frames.table.is_cuda):
+        raise ValueError("the frame table must live on the GPU (pack_frames with a GPU device)")
+    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == frames.table.device):
+        raise ValueError("out must be a flat int32 tensor on the device of the frame table")
+    _flat_out(None, out, total)   # (before anything is uploaded)
+    return frames.table.device, len(frames.sizes)
+
+
 def _bits_buffers(out, total: int, B: int, dev):
     """The outputs of a frames bit packer -> (the ``total`` plane words: ``out`` where it is given and fits, the B areas)."""
-    if out is None:
-        out = torch.empty(max(total, 4), dtype=torch.int32, device=dev)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int32 and out.dim() == 1 and out.is_contiguous()
-              and out.numel() >= total and out.data_ptr() % 16 == 0):
-        raise ValueError(f"out must be a flat, 16-byte aligned int32 device tensor of at least {total} words")
-    return out, torch.empty(B, dtype=torch.int32, device=dev)
+    _flat_out(None, out, total)
+    return torch.empty(max(total, 4), dtype=torch.int32, device=dev) if out is None else out, torch.empty(B, dtype=torch.int32, device=dev)
 
 
 def pack_label_bits_frames(labels: PackedLabels, ids, stream=None, out=None) -> FrameBits:
@@ -606,15 +628,8 @@ def _annotation_rows(who, frames, B: int, image_index, sizes=None):
 
 def _pack_annotation_bits_frames(entry, name, frames, arrays, B, image_index, ii_h, offs_h, total, stream, out) -> FrameBits:
     """The device step the two annotation packers share: the small arrays up in one copy, the planes' buffers, the call."""
-    if not (isinstance(frames.table, torch.Tensor) and frames.table.is_cuda):
-        raise ValueError("the frame table must live on the GPU (pack_frames with a GPU device)")
-    dev = frames.table.device
-    P = len(frames.sizes)
-    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev):
-        raise ValueError("out must be a flat int32 tensor on the device of the frame table")
+    dev, P = _table_device(frames, out, total)
     with torch.cuda.device(dev):
-        if out is not None:
-            _bits_buffers(out, total, 0, dev)   # (its argument errors, before anything is uploaded)
         resident = all(isinstance(a, torch.Tensor) and a.is_cuda for a, _ in arrays)   # annotation arrays that are on a GPU already
         if resident:
             ann = [_as_dev(a, dt, dev) for a, dt in arrays]
@@ -675,15 +690,8 @@ def pack_crop_bits_frames(frames, crops, params, image_index, threshold=None, st
     who = "pack_crop_bits_frames"
     B = int(crops.shape[0]) if hasattr(crops, "shape") else len(crops)
     ii_h, offs_h, total = _annotation_rows(who, frames, B, image_index)
-    if not (isinstance(frames.table, torch.Tensor) and frames.table.is_cuda):
-        raise ValueError("the frame table must live on the GPU (pack_frames with a GPU device)")
-    dev = frames.table.device
-    P = len(frames.sizes)
-    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev):
-        raise ValueError("out must be a flat int32 tensor on the device of the frame table")
+    dev, P = _table_device(frames, out, total)
     with torch.cuda.device(dev):
-        if out is not None:
-            _bits_buffers(out, total, 0, dev)   # (its argument errors, before anything is uploaded)
         v, sb, sr, sp, S, B, default = _crop_source(who, crops, dev)
         thr = _crop_threshold(who, threshold, default)
         place = _crop_place(who, params, S, B, dev)
@@ -712,6 +720,11 @@ class FrameGrid(NamedTuple):
 _TABLED = (PackedFrames, PackedFrames16, PackedLabels, PackedMasks, FrameGrid)   # what an entry that reads only the frame table takes
 
 
+def _upscale_arg(who: str, upscale) -> None:   # the upscale of an opening (morph) and of the frame table of its result
+    if isinstance(upscale, bool) or not isinstance(upscale, (int, np.integer)) or int(upscale) not in (1, 2, 4):
+        raise ValueError(f"{who}: upscale must be 1, 2 or 4 (factors whose nearest-neighbour rule is u // s under every convention), not {upscale!r}")
+
+
 def _scaled_sizes(frames, s: int) -> list:
     return [(s * int(h), s * int(w)) for h, w in frames.sizes]
 
@@ -730,154 +743,11 @@ def scaled_frames(frames, upscale: int, device=None) -> FrameGrid:
     sizes ``(s * h, s * w)`` with its bounds - the layout of the planes ``open_bits_frames(..., upscale=s)`` returns, for
     ``rle_encode_bits_frames`` and ``bits_rects_frames`` on them.  One small upload, to ``device`` (default: where the table of
     ``frames`` lives; "cpu" gives the table on the host)."""
-    if not isinstance(frames, _TABLED):
-        raise ValueError("scaled_frames: frames must be a PackedFrames / PackedFrames16 / PackedLabels / PackedMasks / FrameGrid")
-    _open_scalars("scaled_frames", 1, upscale)
+    _tabled("scaled_frames", frames)
+    _upscale_arg("scaled_frames", upscale)
     dev = frames.table.device if device is None else _host_or_gpu(device)
     sizes = _scaled_sizes(frames, int(upscale))
     return FrameGrid(*_table_fields(frame_table(sizes), sizes, dev))
-
-
-# ---- morphology on the bit planes of images of different sizes (include/la3d.h "morphology on bit planes") ---------------------------
-def _open_frames_check(who: str, frames, bits, k, upscale) -> None:
-    if not isinstance(frames, _TABLED):
-        raise ValueError(f"{who}: frames must be a PackedFrames / PackedFrames16 / PackedLabels / PackedMasks / FrameGrid")
-    _same_table(frames, bits)
-    _open_scalars(who, k, upscale)
-
-
-def _open_frames_run(frames, bits: FrameBits, k: int, s: int, out, offs, stream):
-    """One ``la3d_open_bits_frames`` call on checked arguments -> stats int32 (B, 5); ``out`` None: statistics only."""
-    dev = bits.bits.device
-    B, P = int(bits.offsets.numel()), int(frames.table.shape[0])
-    with torch.cuda.device(dev):
-        ii = _as_dev(bits.image_index, torch.int32, dev)
-        stats = torch.empty((B, 5), dtype=torch.int32, device=dev)
-        ws = torch.empty(max(int(lib.la3d_open_bits_frames_workspace_bytes(B, max(int(frames.H), 1), s)) // 4, 1), dtype=torch.int32, device=dev)
-        if B:   # (an empty batch has no planes to point at)
-            check(lib.la3d_open_bits_frames(_ptr(bits.bits), int(bits.bits.numel()), _ptr(bits.offsets), _ptr(frames.table) if P else None, P,
-                                            max(int(frames.H), 1), max(int(frames.W), 1), _ptr(ii), B, k, s, _ptr(out),
-                                            0 if out is None else int(out.numel()), _ptr(offs), _ptr(stats), _ptr(ws), _stream(stream)),
-                  "la3d_open_bits_frames")
-    _record(stream, bits.bits, bits.offsets, frames.table, ii, out, offs, stats, ws)
-    return stats
-
-
-def open_bits_frames(frames, bits: FrameBits, k: int = 7, upscale: int = 1, image_index=None, stream=None, out=None,
-                     return_stats: bool = False):
-    """``open_bits`` for the planes of images of DIFFERENT sizes in one call (C-ABI ``la3d_open_bits_frames``): the opening by
-    ``np.ones((k, k))`` of the nearest x ``upscale`` upscale of every plane of ``bits``, each over its OWN image.  ``frames``: a
-    ``PackedFrames`` / ``PackedFrames16`` / ``PackedLabels`` / ``PackedMasks`` / ``FrameGrid`` whose frame table the planes were
-    laid out for (another table: ValueError before any device work); ``k``: odd, 1 .. 31; ``upscale``: 1, 2 or 4 - ONE of each per
-    call.  The plane of an image of size (h, w) comes back as the plane of an image of size (s*h, s*w): ``s*h`` rows,
-    ``padded_width(s*w)`` wide, the bits of the padding columns zero.  ``image_index``: None, or a HOST copy of the indices the planes
-    were packed with - the opened planes are then laid out compactly (``frame_bits_offsets`` on the scaled table; the offsets go up in
-    one copy); None never synchronises and lays the planes a uniform stride apart, the words of the scaled bounds' frame rounded up to
-    4 (at x4 sixteen times the largest source plane per row, whatever the row's own size).  ``out``: a flat, 16-byte aligned int32
-    device tensor of at least that many words to fill; it must not overlap ``bits.bits`` (the call cannot work in place).
-    Returns ``FrameBits`` - ``image_index`` the input's, ``area`` the opened area, ``table`` / ``H`` / ``W`` the input's at
-    ``upscale=1`` (the result goes straight into ``fit_instances_frames_bits``, ``instance_points_frames`` and
-    ``rle_encode_bits_frames`` with the same ``frames``), else those of ``scaled_frames(frames, upscale)`` - or, with
-    ``return_stats``, ``(FrameBits, stats)``: int32 (B, 5) on the device, ``area, x, y, w, h`` of each opened plane.  A row whose image
-    index, frame row or plane offset breaks the contract, or whose plane does not end inside its buffer, writes no word and gets
-    ``-1, 0, 0, 0, 0`` (``area`` 0 in the ``FrameBits``) - decided on the device, never an exception.  No host synchronisation;
-    capturable."""
-    who = "open_bits_frames"
-    _open_frames_check(who, frames, bits, k, upscale)
-    k, s = int(k), int(upscale)
-    B, P = int(bits.offsets.numel()), len(frames.table_host)
-    table = frames.table_host if s == 1 else _scaled_table(frames.table_host, s)
-    H_s, W_s = _bounds(table)
-    offs_h = None
-    if image_index is not None:
-        if isinstance(image_index, torch.Tensor) and image_index.is_cuda:
-            raise ValueError(f"{who}: image_index must be a host copy of the planes' image indices (None: the uniform-stride layout)")
-        ii = np.asarray(image_index.numpy() if isinstance(image_index, torch.Tensor) else image_index).reshape(-1)
-        if len(ii) != B or (B and not np.issubdtype(ii.dtype, np.integer)):
-            raise ValueError(f"{who}: image_index must hold one integer image index per plane ({B}), got {len(ii)} of {ii.dtype}")
-        if B and (int(ii.min()) < 0 or int(ii.max()) >= P):
-            raise ValueError(f"{who}: image_index must lie in [0, {P})")
-        offs_h, total = frame_bits_offsets(table, ii)
-    else:
-        stride = (H_s * W_s // 32 + 3) // 4 * 4
-        total = B * stride
-    if out is not None and isinstance(out, torch.Tensor) and out.dtype == torch.int32 and out.dim() == 1:
-        a0, b0 = out.data_ptr(), bits.bits.data_ptr()
-        if a0 < b0 + 4 * bits.bits.numel() and b0 < a0 + 4 * out.numel():
-            raise ValueError(f"{who}: out overlaps the input planes (the call cannot work in place)")
-    dev = _on_gpu(frames.table, bits.bits)
-    with torch.cuda.device(dev):
-        o, _ = _bits_buffers(out, total, 0, dev)
-        offs = _as_dev(offs_h, torch.int64, dev) if offs_h is not None else torch.arange(B, dtype=torch.int64, device=dev) * stride
-        stats = _open_frames_run(frames, bits, k, s, o, offs, stream)
-        area = stats[:, 0].clamp(min=0).contiguous()
-    _record(stream, area)
-    res = FrameBits(o, offs, bits.image_index, area, table, H_s, W_s)
-    return (res, stats) if return_stats else res
-
-
-def bits_rects_frames(frames, bits: FrameBits, stream=None) -> torch.Tensor:
-    """``FrameBits`` -> int32 (B, 5) on the device: ``area, x, y, w, h`` of every plane over its own image - the statistics-only call
-    of ``la3d_open_bits_frames`` with ``k = 1, upscale = 1`` (no plane is written); ``-1, 0, 0, 0, 0`` for a row the device refuses.
-    ``frames`` as in ``open_bits_frames``."""
-    _open_frames_check("bits_rects_frames", frames, bits, 1, 1)
-    _on_gpu(frames.table, bits.bits)
-    return _open_frames_run(frames, bits, 1, 1, None, None, stream)
-
-
-def select_crops_frames(frames, bits: FrameBits, min_area: int = 6400, k: int = 7, upscale: int = 4, crop_size: int = 512, image_index=None,
-                        stream=None):
-    """``select_crops`` for the planes of images of DIFFERENT sizes - the instance selection of the reference's crop stage
-    (src/batch_scripts/get_crops_enhanced.py:68-99) for a whole shard in one call: ``open_bits_frames(frames, bits, k, upscale,
-    image_index)``, then ``keep = area >= min_area`` and ``crop_params`` of the rectangles -> ``(keep, params, stats, opened)``:
-    ``keep`` bool (B,) and ``params`` float64 (B, 3) NumPy arrays - false and NaN for empty planes and for rows the device refuses
-    (``stats`` row ``-1, 0, 0, 0, 0``) -, ``stats`` int32 (B, 5) on the device, ``opened`` the ``FrameBits`` of the opened, upscaled
-    planes.  ``params`` speak of the ORIGINAL frames: they are what ``pack_crop_bits_frames(frames, crops, params, image_index)`` takes.
-    The defaults are the reference's gate (x4, 7 x 7, 6400 surviving pixels, 512-pixel crops); one device-to-host copy (the
-    statistics).  The reference walks the instances LAST TO FIRST and appends the boxes it keeps to ``bboxes.json`` in that order: rows
-    here stay in the caller's order, and the order of ``bboxes.json`` is the caller's business."""
-    _gate_scalars("select_crops_frames", min_area, crop_size)
-    opened, stats = open_bits_frames(frames, bits, k=k, upscale=upscale, image_index=image_index, stream=stream, return_stats=True)
-    if stream is not None and stream != torch.cuda.current_stream():
-        stream.synchronize()
-    host = stats.cpu().numpy()
-    return host[:, 0] >= int(min_area), crop_params(np.maximum(host, 0), crop_size=int(crop_size), upscale=int(upscale)), stats, opened
-
-
-def rle_encode_bits_frames(frames, bits: FrameBits, capacity=None, stream=None, return_status: bool = False):
-    """``rle_encode_bits`` for the planes of images of DIFFERENT sizes (the frames form of C-ABI ``la3d_rle_encode_offsets`` +
-    ``la3d_rle_encode``): ``frames`` - a ``PackedFrames`` / ``PackedFrames16`` / ``PackedLabels`` / ``PackedMasks`` whose frame table
-    the planes were laid out for (another table: ValueError before any device work) -, ``bits`` the ``FrameBits`` of a frames packer.
-    The runs of instance n are column-major over its OWN image, ``(H_p, W_p)`` unpadded.  Returns ``((counts, offsets), sizes)`` -
-    ``(counts int32, offsets int64 (B+1,))`` on the GPU is what ``fit_instances_frames(rles=...)`` and ``pack_rle_bits_frames`` take;
-    ``sizes`` int32 (B, 2) on the GPU holds the (h, w) of every instance (-1, -1 for a row whose image index lies outside the table;
-    ``rle_objects((counts, offsets), sizes=sizes)`` writes the JSON objects) - and, with ``return_status=True``, ``status`` int32 (B,)
-    as a third item: 0, 1 = no room in ``capacity``, 2 = the planes changed between the stages, 5 = a row whose image index, frame row
-    or plane offset breaks the contract (it gets no runs - decided on the device, never an exception).  ``capacity`` as in
-    ``rle_encode_bits``: None synchronises once for the exact size, an int never does.  ``frames`` may also be a ``FrameGrid``: with
-    ``scaled_frames(frames, s)`` the planes ``open_bits_frames`` made at ``upscale=s`` are encoded."""
-    who = "rle_encode_bits_frames"
-    _rle_capacity(who, capacity)
-    if not isinstance(frames, _TABLED):
-        raise ValueError(f"{who}: frames must be a PackedFrames / PackedFrames16 / PackedLabels / PackedMasks / FrameGrid")
-    _same_table(frames, bits)
-    dev = _on_gpu(frames.table, bits.bits)
-    B, P = int(bits.offsets.numel()), int(frames.table.shape[0])
-    if B and not P:
-        raise ValueError(f"{who}: instances without a frame table")
-    ii = _as_dev(bits.image_index, torch.int32, dev)
-    a = _lib.RleEncodeArgs(struct_size=C.sizeof(_lib.RleEncodeArgs), B=B, H=max(int(frames.H), 1), W=max(int(frames.W), 1), P=P,
-                           mask_bits=bits.bits.data_ptr(), frames=frames.table.data_ptr() if P else None, image_index=ii.data_ptr() if P else None,
-                           bits_offsets=bits.offsets.data_ptr() if P else None)
-    counts, offsets, status = _rle_encode_run(a, B, dev, capacity, stream, [frames.table, bits.bits, bits.offsets, ii])
-    with torch.cuda.device(dev):
-        if P:
-            ok = (ii >= 0) & (ii < P)
-            hw = frames.table[ii.clamp(0, P - 1).long()][:, [2, 4]]   # (the la3d_frame words: H, frame_width)
-            sizes = torch.where(ok[:, None], hw, torch.full_like(hw, -1))
-        else:
-            sizes = torch.zeros((0, 2), dtype=torch.int32, device=dev)
-    return ((counts, offsets), sizes, status) if return_status else ((counts, offsets), sizes)
 
 
 def fit_instances_frames_masks(frames, masks, K, threshold: float = 0.0, image_index=None, ground=None, sample_idx=None, filter=None,

@@ -10,7 +10,8 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
-from .batched import _as_dev, _bits_stride, _dev, _ptr, _record, _stream, _upload_many, height_rule_code, padded_width
+from ._device import _as_dev, _dev, _ptr, _record, _stream, _upload_many
+from .batched import _bits_stride, height_rule_code, padded_width
 from .bits import MaskBits, _bits_out, fit_instances_bits
 
 

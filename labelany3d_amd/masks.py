@@ -1,5 +1,5 @@
 """Annotation ingestion on the device: the data format immediately upstream of the box fit - COCO run lengths and
-polygons, their filters and the fits that take them; and the ratio median of the depth alignment (``masked_ratio_median``).
+polygons, their decoders, filters and the fits that take them (host-side packing - ``pack_rle``, ``pack_polygons`` -: ``segm``).
 
 The reference turns COCO / COCONut annotations into ``(N,H,W)`` bool arrays on the CPU with pycocotools
 (``mask_utils.decode``, reference src/util.py:367,401-402; encoder src/download_coconut.py:167-175) and keeps
@@ -20,66 +20,33 @@ instances, src/download_coconut.py:275-280) — take ``create_boolean_mask_from_
     masks = poly_decode(polys)                                          # the reference's boolean masks, on the GPU
     keep  = keep_instances(mask_stats_poly(polys), H, from_rle=False)   # height = last row - first row + 1 (:328-335)
 
-The other sources of ONE frame size per call live in modules of their own and are re-exported at the end: bit planes - packers, crop
-restore, run-length encoder, morphology - in ``bits`` (``MaskBits``), label maps in ``labels`` (``LabelBits``), 16-bit depth in
-``depth16`` (``pack_depth16``); so are images of different sizes (``pack_frames``, ``fit_instances_frames*``) in ``frames``.
+The other sources live in modules of their own (``bits``, ``labels``, ``depth16``, ``frames``; plane operations in ``morph`` and
+``rle_encode``) and this module is their facade: every name that was ever importable from here is imported below.
 """
 from __future__ import annotations
 
 import ctypes as C
-import itertools
 import threading
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._device import _as_dev, _dev, _plane_source, _ptr, _record, _stream, _upload_many  # noqa: F401
 from ._lib import AUX, BOX_FILTERED, REC, check, lib
-from .batched import (Depth16, InstanceFitter, _as_dev, _depth16_check, _dev, _fit_args, _ptr, _stream, _upload_many, pad_depth_rows, padded_width,
-                      refuse_depth16)
-from .fitcall import depth_rows, fit_call, mask_source
-
-
-def rle_from_string(s) -> np.ndarray:
-    """COCO compressed RLE string -> run lengths (pycocotools rleFrString), via the library's host helper."""
-    if isinstance(s, str):
-        s = s.encode("ascii")
-    cap = len(s) + 1
-    buf = (C.c_int32 * cap)()
-    n = lib.la3d_rle_from_string_host(s, len(s), buf, cap)
-    if n < 0:
-        raise ValueError("malformed COCO RLE string")
-    return np.frombuffer(buf, dtype=np.int32, count=n).copy()
-
-
-def pack_rle(rles):
-    """List of COCO RLE objects ({'size': [h, w], 'counts': list | str | bytes}, as in the annotation JSON the
-    reference reads at src/util.py:360-368) -> (counts int32 (T,), offsets int64 (B+1,), H, W) NumPy arrays."""
-    if isinstance(rles, tuple) and len(rles) == 4:
-        return rles
-    sizes = {tuple(r["size"]) for r in rles}
-    if len(sizes) > 1:
-        raise ValueError("all masks of one batch must share the frame size")
-    H, W = sizes.pop() if sizes else (0, 0)
-    counts, offsets = _rle_counts([r["counts"] for r in rles])
-    return counts, offsets, int(H), int(W)
-
-
-def _rle_counts(cs):
-    """The ``counts`` of a batch of COCO RLE objects (lists, compressed strings, arrays) -> (counts int32 (T,), offsets int64 (B+1,));
-    an empty batch gives one zero count (the kernels take no NULL)."""
-    if cs and all(type(c) is list for c in cs):   # uncompressed run lengths as the JSON holds them: one conversion loop for the batch
-        lens = np.fromiter(map(len, cs), np.int64, len(cs))
-        counts = np.fromiter(itertools.chain.from_iterable(cs), np.int64, int(lens.sum())).astype(np.int32)
-        offsets = np.zeros(len(cs) + 1, np.int64)
-        np.cumsum(lens, out=offsets[1:])
-    else:
-        parts = [rle_from_string(c) if isinstance(c, (str, bytes)) else np.asarray(c, dtype=np.int32) for c in cs]
-        offsets = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.int64)
-        counts = np.concatenate(parts).astype(np.int32) if parts and offsets[-1] else np.zeros(1, np.int32)
-    if not len(counts):
-        counts = np.zeros(1, np.int32)
-    return counts, offsets
+from .batched import Depth16, InstanceFitter, _bits_stride, _depth16_block, _depth16_check, _fit_args, height_rule_code, pad_depth_rows, padded_width, refuse_depth16  # noqa: F401
+from .bits import (_LOGIT_DTYPES, MaskBits, _annotation_bits_plan, _bits_out, _crop_place, _crop_source, _crop_threshold, _mask_bits, _pack_annotation_bits,  # noqa: F401
+                   _PackedBits, crop_placement, fit_instances_bits, mask_stats_bits, pack_crop_bits, pack_logits_bits, pack_mask_bits, pack_poly_bits, pack_rle_bits, unpack_mask_bits)
+from .depth16 import _D16_DTYPES, pack_depth16, unpack_depth16  # noqa: F401
+from .depth_align import masked_ratio_median  # noqa: F401
+from .fitcall import depth_rows, depth_rows_for_bits, fit_call, mask_source  # noqa: F401
+from .frames import (FRAME_DTYPE, MASKS_U8, FrameBits, PackedFrames, PackedFrames16, PackedLabels, PackedMasks, fit_instances_frames, fit_instances_frames_bits,  # noqa: F401
+                     fit_instances_frames_labels, fit_instances_frames_masks, frame_bits_offsets, frame_table, pack_crop_bits_frames, pack_frames, pack_label_bits_frames,
+                     pack_label_frames, pack_mask_bits_frames, pack_mask_frames, pack_poly_bits_frames, pack_rle_bits_frames, pack_rle_frames)
+from .labels import _LABEL_NUMPY, _LABEL_TORCH, LabelBits, _label_planes, _label_rows, _label_source, fit_instances_labels, label_instances, pack_label_bits  # noqa: F401
+from .morph import _gate_scalars, _open_args, _open_run, _open_scalars, bits_rects, crop_params, open_bits, select_crops  # noqa: F401
+from .rle_encode import RleRuns, _rle_capacity, _rle_encode_run, rle_encode, rle_encode_bits, rle_encode_bits_frames, rle_objects, rle_to_string  # noqa: F401
+from .segm import _rle_counts, pack_polygons, pack_rle, rle_from_string  # noqa: F401
 
 
 def rle_decode(rles, device=None, stream=None) -> torch.Tensor:
@@ -126,44 +93,6 @@ def keep_instances(stats: torch.Tensor, image_height: int, from_rle: bool = True
     height = rows holding a pixel for RLE annotations (:368-369) and last-first+1 for polygons (:328-335)."""
     height = stats[:, 1] if from_rle else stats[:, 2]
     return (height.double() / image_height > 0.0625) & (stats[:, 3] < 10) & (stats[:, 0] >= scale_threshold)
-
-
-def pack_polygons(segmentations, H=None, W=None):
-    """List of polygon segmentations (each a list of parts, each part a flat [x0, y0, x1, y1, ...] list as in the COCO /
-    COCONut JSON) -> ``(xy int32 (T,2), ring_offsets int64 (R+1,), inst_rings int64 (B+1,), H, W)``.  Vertices are
-    truncated exactly like the reference: ``np.array(polygon).reshape(-1, 2).astype(np.int32)`` (src/util.py:398) — an odd
-    number of coordinates raises the same ``ValueError`` from ``reshape``."""
-    if isinstance(segmentations, tuple) and len(segmentations) == 5:
-        return segmentations
-    if H is None or W is None:
-        raise ValueError("pack_polygons needs the frame size (H, W)")
-    for seg in segmentations:
-        if not isinstance(seg, (list, tuple)):
-            raise TypeError("polygon segmentation must be a list of parts")
-    parts = [polygon for seg in segmentations for polygon in seg]
-    inst_rings = np.zeros(len(segmentations) + 1, np.int64)
-    np.cumsum([len(seg) for seg in segmentations], out=inst_rings[1:])
-    # (a part given as nested pairs [[x, y], ...] is a list too: the flat fast path is for lists of scalars only)
-    plain = all(type(q) is list and not (q and isinstance(q[0], (list, tuple, np.ndarray))) for q in parts)
-    lens = np.fromiter(map(len, parts), np.int64, len(parts)) if plain else None
-    if plain and len(parts) and not (lens & 1).any():
-        # flat Python lists (what the annotation JSON holds): ONE conversion loop over all coordinates of the batch instead of one
-        # np.array per part (a third of the packing time of a 256-image batch); the truncation is the same astype
-        flat = np.fromiter(itertools.chain.from_iterable(parts), np.float64, int(lens.sum()))
-        xy = flat.reshape(-1, 2).astype(np.int32)
-        ring_off = np.zeros(len(parts) + 1, np.int64)
-        np.cumsum(lens >> 1, out=ring_off[1:])
-    else:   # arrays, nested pairs, or an odd count (np.reshape raises the reference's ValueError)
-        pts, ring = [], [0]
-        for polygon in parts:
-            q = np.array(polygon).reshape(-1, 2).astype(np.int32)
-            pts.append(q)
-            ring.append(ring[-1] + len(q))
-        xy = np.concatenate(pts).astype(np.int32) if pts else np.zeros((0, 2), np.int32)
-        ring_off = np.asarray(ring, np.int64)
-    if not len(xy):
-        xy = np.zeros((1, 2), np.int32)
-    return xy, ring_off, inst_rings, int(H), int(W)
 
 
 def _poly_dev(polys, dev):
@@ -554,49 +483,3 @@ def fit_instances_rle(depth, rles, K, ground=None, sample_idx=None, image_index=
     r = fit_instances_ex(depth, K, rles=rles, ground=ground, sample_idx=sample_idx, image_index=image_index, filter=filter,
                          stream=stream, device=device, method=method)
     return (r["boxes"], r["status"], r["aux"]) + ((r["stats"],) if filter else ())
-
-
-def masked_ratio_median(depth_map, depth_render, mask, render_mask=None, image_index=None, stream=None):
-    """Per instance ``np.median(depth_map[overlap] / depth_render[overlap])`` with ``overlap = mask & render_mask``
-    — the scale estimate of the reference's align_to_depth_match (src/util.py:476-486), exact (radix select on
-    the float32 ratios).  depth_map (P,H,W) or (H,W); depth_render, mask, render_mask (B,H,W).
-    Returns (median float32 (B,), count int32 (B,)) on the GPU; an empty overlap gives count 0 and NaN (the
-    reference returns the identity transform there, :476-478)."""
-    dev = mask.device if isinstance(mask, torch.Tensor) and mask.is_cuda else _dev()
-    m = _as_dev(mask, torch.uint8, dev)
-    B, H, W = m.shape
-    rm = None if render_mask is None else _as_dev(render_mask, torch.uint8, dev)
-    d = _as_dev(depth_map, torch.float32, dev)
-    if d.dim() == 2:
-        d = d[None]
-    r = _as_dev(depth_render, torch.float32, dev)
-    ii = None if image_index is None else _as_dev(image_index, torch.int32, dev)
-    if ii is None and d.shape[0] not in (1, B):
-        raise ValueError("without image_index, depth_map must have 1 or B planes")
-    med = torch.empty(B, dtype=torch.float32, device=dev)
-    cnt = torch.empty(B, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        check(lib.la3d_masked_ratio_median(_ptr(d), H * W if d.shape[0] > 1 else 0, _ptr(ii), _ptr(r), _ptr(m), _ptr(rm), B, H, W,
-                                           _ptr(med), _ptr(cnt), _stream(stream)), "la3d_masked_ratio_median")
-    return med, cnt
-
-
-# The other sources and the mixed-size ("frames") layer: every name that was importable from here stays so, and is the same object.  Last on purpose - bits and
-# frames import from this module (pack_rle, _rle_counts), and this tail is the only module-level import cycle of the package: every
-# other import runs one way, batched / fitcall <- masks <- bits <- labels, depth16 <- frames <- clouds, overlap.
-from .bits import (MaskBits, RleRuns, bits_rects, crop_params, crop_placement, fit_instances_bits, mask_stats_bits, open_bits, pack_crop_bits,  # noqa: E402,F401
-                   pack_logits_bits, pack_mask_bits, pack_poly_bits, pack_rle_bits, rle_encode, rle_encode_bits, rle_objects, rle_to_string, select_crops,
-                   unpack_mask_bits)
-from .labels import LabelBits, fit_instances_labels, label_instances, pack_label_bits  # noqa: E402,F401
-from .depth16 import pack_depth16, unpack_depth16  # noqa: E402,F401
-# (the helpers that lived in or came through this module: callers and tests that reach them here - masks._crop_source - find the same objects)
-from .batched import _bits_stride, _depth16_block, _plane_source, _record, height_rule_code  # noqa: E402,F401
-from .fitcall import depth_rows_for_bits  # noqa: E402,F401
-from .bits import (_LOGIT_DTYPES, _PackedBits, _annotation_bits_plan, _bits_out, _crop_place, _crop_source, _crop_threshold, _gate_scalars,  # noqa: E402,F401
-                   _mask_bits, _open_args, _open_run, _open_scalars, _pack_annotation_bits, _rle_capacity, _rle_encode_run)
-from .labels import _LABEL_NUMPY, _LABEL_TORCH, _label_planes, _label_rows, _label_source  # noqa: E402,F401
-from .depth16 import _D16_DTYPES  # noqa: E402,F401
-from .frames import (FRAME_DTYPE, MASKS_U8, FrameBits, PackedFrames, PackedFrames16, PackedLabels, PackedMasks, fit_instances_frames,  # noqa: E402,F401
-                     fit_instances_frames_bits, fit_instances_frames_labels, fit_instances_frames_masks, frame_bits_offsets, frame_table,
-                     pack_crop_bits_frames, pack_frames, pack_label_bits_frames, pack_label_frames, pack_mask_bits_frames, pack_mask_frames, pack_poly_bits_frames,
-                     pack_rle_bits_frames, pack_rle_frames, rle_encode_bits_frames)

@@ -11,7 +11,8 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
-from .batched import _bits_stride, _record, _stream, _upload_many
+from ._device import _record, _stream, _upload_many
+from .batched import _bits_stride
 from .frames import FrameBits, _on_gpu, _same_table
 from .bits import MaskBits
 

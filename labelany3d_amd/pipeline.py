@@ -14,6 +14,7 @@ from typing import Iterable, Iterator, Tuple
 
 import torch
 
+from ._lib import method_code
 from .batched import InstanceFitter
 
 
@@ -31,7 +32,6 @@ def fit_batches(batches: Iterable, streams: int = 2, copy: bool = True, method: 
     overwritten once the generator has been advanced TWICE more - use it before asking for the result after next.
     The size-balanced launch order is switched off PER CALL (``la3d_fit_args::opt_launch_order``): no process state is touched.
     ``method``: "pca" | "convex_hull" for every batch (see ``fit_instances``)."""
-    from ._lib import method_code
     method_code(method)   # (the reference's error for an unknown method, before any device work)
     dev = None
     pool, fitters = [], {}

@@ -19,7 +19,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .batched import refuse_depth16
+from .batched import fit_instances, refuse_depth16
+from .masks import annotation_areas, fit_annotations_all
 
 
 def partition_contiguous(costs: Sequence[float], world: int) -> List[Tuple[int, int]]:
@@ -165,7 +166,7 @@ def fit_instances_sharded(depth, masks, K, image_index, ground=None, sample_idx=
     refuse_depth16(depth, "shard.fit_instances_sharded")
     _check_method(method)
     if fit_fn is None:
-        from .batched import fit_instances as fit_fn
+        fit_fn = fit_instances
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     img = np.asarray(image_index.cpu() if isinstance(image_index, torch.Tensor) else image_index).astype(np.int64)
@@ -226,9 +227,7 @@ def fit_annotations_sharded(annotations, image_size, image_index, num_images: in
     ``method``: "pca" | "convex_hull", handed to ``fit_fn`` as a keyword when it is not "pca"."""
     _check_method(method)
     if fit_fn is None:
-        from .masks import fit_annotations_all as fit_fn
-    from .masks import annotation_areas
-
+        fit_fn = fit_annotations_all
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     img = np.asarray(image_index.cpu() if isinstance(image_index, torch.Tensor) else image_index).astype(np.int64)

@@ -11,6 +11,7 @@ import numpy as np
 
 from ._lib import check, lib
 from .batched import unproject
+from .bits import pack_crop_bits, unpack_mask_bits
 
 
 def depth_to_points(depth, K=None, R=None, t=None):
@@ -54,8 +55,6 @@ def restore_mask_from_crop(resized_mask, offset_x, offset_y, scale_factor, origi
     mask of ``original_mask_shape`` = (H, W); returns a NumPy bool (H, W) array.  One ``pack_crop_bits`` and one
     ``unpack_mask_bits``; a caller that goes on to the fit keeps the ``MaskBits`` of ``pack_crop_bits`` instead.  Unlike the
     reference, a scale that leaves no pixel and a crop wholly outside the frame give an empty mask, not an exception."""
-    from .masks import pack_crop_bits, unpack_mask_bits
-
     m = np.asarray(resized_mask)
     if m.ndim != 2 or m.shape[0] != m.shape[1]:
         raise ValueError(f"restore_mask_from_crop: resized_mask must be a square (S, S) mask, got {m.shape}")

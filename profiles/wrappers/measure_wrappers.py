@@ -16,6 +16,9 @@ Lines (us per call, the median of ``--reps`` calls after ``--warmup``):
   ex_rle_B8 / ex_rle_B1024    ``fit_instances_ex(rles=pack_rle tuple)`` on one shared 640x480 plane
   bits_B1022 / labels_B1022   ``fit_instances_bits`` on resident planes / ``fit_instances_labels`` on 146 resident U8 label maps x 7 ids
   frames_poly / frames_rle    ``fit_instances_frames`` on 256 images of 18 COCO sizes (the set of profiles/frames), ~7 instances each
+  open_bits_frames_B8 / components_bits_frames_B8 / rle_encode_bits_frames_B8 / mask_overlap_frames_B8
+                              the plane operations on the ``FrameBits`` of 8 masks over 3 images of different sizes (7 x 7 opening,
+                              largest component, encoder with ``capacity=int``, self IoU): the batch where host time is the call
   run_B1024                   the bare ``InstanceFitter.run`` enqueue, everything resident"""
 import argparse
 import json
@@ -143,6 +146,16 @@ def measure():
     img_p, img_r, area_p, area_r = (np.asarray(v, np.int32) for v in (img_p, img_r, area_p, area_r))
     lines["frames_poly"] = lambda: la.fit_instances_frames(pf, Ks, polys=polys, image_index=img_p, area_hint=area_p, filter=True, proj=True)
     lines["frames_rle"] = lambda: la.fit_instances_frames(pf, Ks, rles=(counts, offsets), image_index=img_r, area_hint=area_r)
+
+    # ---- plane operations on FrameBits at the small batch where host time is the call: 8 planes over 3 images of different sizes
+    small_sizes, per_image = [(480, 640), (375, 500), (333, 500)], [3, 3, 2]
+    pm = la.pack_mask_frames([np.stack([ellipse_mask(ellipse(rs, h, w), h, w) for _ in range(c)]) for (h, w), c in zip(small_sizes, per_image)],
+                             device=dev)
+    fb = la.pack_mask_bits_frames(pm)
+    lines["open_bits_frames_B8"] = lambda: la.open_bits_frames(pm, fb, k=7)
+    lines["components_bits_frames_B8"] = lambda: la.components_bits_frames(pm, fb, largest=True)
+    lines["rle_encode_bits_frames_B8"] = lambda: la.rle_encode_bits_frames(pm, fb, capacity=65536)
+    lines["mask_overlap_frames_B8"] = lambda: la.mask_overlap(fb, counts_a=per_image, frames=pm, iou="iou")
 
     # ---- the bare enqueue
     B = 1024

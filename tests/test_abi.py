@@ -376,36 +376,42 @@ def test_pack_polygons_accepts_every_form_the_reference_accepts():
 
 
 MASKS_PUBLIC = {   # module that defines the name -> the public names importable from labelany3d_amd.masks, as of the commit before masks.py was split by job
-    "masks": ("rle_from_string", "pack_rle", "rle_decode", "mask_stats", "mask_stats_rle", "keep_instances", "pack_polygons", "poly_decode",
-              "mask_stats_poly", "filter_annotations", "fit_instances_ex", "fit_annotations", "split_annotations", "area_hint_of",
-              "annotation_areas", "fit_annotations_all", "segmentations_to_masks", "fit_instances_poly", "fit_instances_rle",
-              "masked_ratio_median"),
+    "masks": ("rle_decode", "mask_stats", "mask_stats_rle", "keep_instances", "poly_decode", "mask_stats_poly", "filter_annotations",
+              "fit_instances_ex", "fit_annotations", "split_annotations", "area_hint_of", "annotation_areas", "fit_annotations_all",
+              "segmentations_to_masks", "fit_instances_poly", "fit_instances_rle"),
+    "segm": ("rle_from_string", "pack_rle", "pack_polygons"),
+    "depth_align": ("masked_ratio_median",),
     "bits": ("MaskBits", "pack_mask_bits", "pack_logits_bits", "pack_rle_bits", "pack_poly_bits", "crop_placement", "pack_crop_bits",
-             "unpack_mask_bits", "mask_stats_bits", "RleRuns", "rle_to_string", "rle_encode_bits", "rle_encode", "rle_objects", "open_bits",
-             "bits_rects", "crop_params", "select_crops", "fit_instances_bits"),
+             "unpack_mask_bits", "mask_stats_bits", "fit_instances_bits"),
+    "rle_encode": ("RleRuns", "rle_to_string", "rle_encode_bits", "rle_encode", "rle_objects", "rle_encode_bits_frames"),
+    "morph": ("open_bits", "bits_rects", "crop_params", "select_crops"),
     "labels": ("LabelBits", "pack_label_bits", "fit_instances_labels", "label_instances"),
     "depth16": ("pack_depth16", "unpack_depth16"),
     "batched": ("Depth16",),
     "frames": ("FRAME_DTYPE", "MASKS_U8", "FrameBits", "PackedFrames", "PackedFrames16", "PackedLabels", "PackedMasks", "fit_instances_frames",
                "fit_instances_frames_bits", "fit_instances_frames_labels", "fit_instances_frames_masks", "frame_bits_offsets", "frame_table",
                "pack_crop_bits_frames", "pack_frames", "pack_label_bits_frames", "pack_label_frames", "pack_mask_bits_frames",
-               "pack_mask_frames", "pack_poly_bits_frames", "pack_rle_bits_frames", "pack_rle_frames", "rle_encode_bits_frames"),
+               "pack_mask_frames", "pack_poly_bits_frames", "pack_rle_bits_frames", "pack_rle_frames"),
 }
 
 
 MASKS_HELPERS = {  # ... and the helpers of this package that lived in masks.py or came through it
-    "bits": ("_LOGIT_DTYPES", "_PackedBits", "_annotation_bits_plan", "_bits_out", "_crop_place", "_crop_source", "_crop_threshold", "_gate_scalars",
-             "_mask_bits", "_open_args", "_open_run", "_open_scalars", "_pack_annotation_bits", "_rle_capacity", "_rle_encode_run"),
+    "bits": ("_LOGIT_DTYPES", "_PackedBits", "_annotation_bits_plan", "_bits_out", "_crop_place", "_crop_source", "_crop_threshold", "_mask_bits",
+             "_pack_annotation_bits"),
+    "morph": ("_gate_scalars", "_open_args", "_open_run", "_open_scalars"),
+    "rle_encode": ("_rle_capacity", "_rle_encode_run"),
     "labels": ("_LABEL_NUMPY", "_LABEL_TORCH", "_label_planes", "_label_rows", "_label_source"),
     "depth16": ("_D16_DTYPES",),
-    "batched": ("_bits_stride", "_depth16_block", "_plane_source", "_record", "height_rule_code"),
+    "batched": ("_bits_stride", "_depth16_block", "height_rule_code"),
+    "_device": ("_plane_source", "_record"),
     "fitcall": ("depth_rows_for_bits",),
-    "masks": ("_rle_counts", "_poly_dev", "_ann_buffers", "_annotation_groups", "_rows", "_annotation_order", "_raw_stream", "_fit_annotations_host"),
+    "segm": ("_rle_counts",),
+    "masks": ("_poly_dev", "_ann_buffers", "_annotation_groups", "_rows", "_annotation_order", "_raw_stream", "_fit_annotations_host"),
 }
 
 
 def test_masks_keeps_every_public_name_it_had():
-    """masks.py was split by job (bits, labels, depth16; frames before them): every public name stays importable from
+    """masks.py was split by job (bits, labels, depth16; frames before them; then segm, morph, rle_encode): every public name stays importable from
     labelany3d_amd.masks and is the very object of the module that defines it - and of the package, where the package has it."""
     import importlib
 

@@ -35,14 +35,15 @@ def test_the_case_list_exercises_the_opening():
 
 def test_names_on_every_layer():
     import labelany3d_amd as la
-    from labelany3d_amd import _lib, frames
+    from labelany3d_amd import _lib, frames, morph
 
     hdr = open(os.path.join(ROOT, "include", "la3d.h")).read()
     assert re.search(r"\bsize_t la3d_open_bits_frames_workspace_bytes\s*\(", hdr) and re.search(r"\bint la3d_open_bits_frames\s*\(", hdr)
     for fn in ("la3d_open_bits_frames", "la3d_open_bits_frames_workspace_bytes"):
         assert fn in _lib.EXPORTS and hasattr(_lib.lib, fn), fn
-    for fn in ("FrameGrid", "scaled_frames", "open_bits_frames", "bits_rects_frames", "select_crops_frames"):
-        assert callable(getattr(la, fn)) and fn in la.__all__ and getattr(frames, fn) is getattr(la, fn), fn
+    homes = dict(FrameGrid=frames, scaled_frames=frames, open_bits_frames=morph, bits_rects_frames=morph, select_crops_frames=morph)
+    for fn, home in homes.items():   # (the frame table and its scaled form live in frames, morphology - both layouts - in morph)
+        assert callable(getattr(la, fn)) and fn in la.__all__ and getattr(home, fn) is getattr(la, fn), fn
     assert re.search(r"#define LA3D_ABI_VERSION 2\b", hdr) and _lib.lib.la3d_version() == 2     # additive
     assert "last to first" in la.select_crops_frames.__doc__.lower() and "bboxes.json" in la.select_crops_frames.__doc__
 

@@ -4,6 +4,7 @@
 never touches them), the string helper against the oracle's codec byte for byte, and the Python argument errors before any device
 work."""
 import ctypes as C
+import importlib
 import os
 import re
 
@@ -20,8 +21,9 @@ NEW_PY = ("RleRuns", "rle_encode_bits", "rle_encode", "rle_encode_bits_frames", 
 def test_new_symbols_on_every_layer():
     from labelany3d_amd import _lib
     import labelany3d_amd as la
-    from labelany3d_amd import frames, masks
+    from labelany3d_amd import masks
 
+    rle_encode = importlib.import_module("labelany3d_amd.rle_encode")   # (the module: ``la.rle_encode`` is the function of that name)
     hdr = open(os.path.join(ROOT, "include", "la3d.h")).read()
     declared = set(re.findall(r"\b(la3d_[a-z0-9_]+)\s*\(", hdr))
     for name in NEW_C:
@@ -33,7 +35,7 @@ def test_new_symbols_on_every_layer():
     for fn in NEW_PY:
         assert callable(getattr(la, fn)) and fn in la.__all__, fn
     assert la.RleRuns._fields == ("counts", "offsets", "H", "W")   # the 4-tuple pack_rle passes through
-    assert masks.rle_encode_bits_frames is frames.rle_encode_bits_frames is la.rle_encode_bits_frames
+    assert masks.rle_encode_bits_frames is rle_encode.rle_encode_bits_frames is la.rle_encode_bits_frames   # (one object: its home, the facade, the package)
     runs = la.RleRuns(np.array([4, 4], np.int32), np.array([0, 2], np.int64), 2, 4)
     assert la.pack_rle(runs) is runs
 
