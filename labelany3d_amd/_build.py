@@ -16,7 +16,8 @@ CSRC = os.path.join(HERE, "csrc")
 # (la3d_rle_encode.hip: bit planes -> COCO run lengths, kernels and C entries in one unit)
 # (la3d_open.hip: binary opening on bit planes, uniform and frames form, kernels and C entries in one unit)
 # (la3d_components.hip: connected components on bit planes - largest part, island removal -, uniform and frames form, kernel and C entries in one unit)
-# (la3d_bitplanes.hpp: what those three share - BitsOut, the frames prologue, pack_check -; la3d_overlap.hip takes its at() for the alignment rules)
+# (la3d_bitplanes.hpp: what those four share - BitsOut, the frames prologue, the plane locator of a frames call that reads and writes planes
+# (FramesPlanes), the row word, pack_check, the in-place rule -; la3d_cloud.hip takes its prologue, la3d_overlap.hip its at() and offset rule)
 # (la3d_align.hip: the batched RANSAC scale fit of the depth alignment, kernels and C entries in one unit)
 # (la3d_overlap.hip: pairwise mask overlap on bit planes and the mask NMS that reads it, kernels and C entries in one unit)
 # (la3d_assign.hip: the batched linear sum assignment that reads an overlap or IoU matrix, kernel and C entry in one unit)

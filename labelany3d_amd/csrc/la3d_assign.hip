@@ -37,9 +37,6 @@ struct AssignParams {
 };
 
 __device__ inline int uniform_i32(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ inline long long uniform_i64(long long v) {
-  return ((long long)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v);
-}
 template <bool I32>
 __device__ __forceinline__ double cost_at(const void* base, long long at, bool neg) {
   const double c = I32 ? (double)static_cast<const int*>(base)[at] : static_cast<const double*>(base)[at];

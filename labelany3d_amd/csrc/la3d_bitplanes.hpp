@@ -1,9 +1,12 @@
 // la3d_bitplanes.hpp - what the units that read or write bit planes share (la3d_bits.hip: decoders, packers, unpacker, statistics;
-// la3d_rle_encode.hip: the run-length encoder; la3d_open.hip: the opening; la3d_components.hip: connected components, whose frames
-// form takes the prologue; la3d_overlap.hip: at() only).
-// Device side: where the planes of a call lie (BitsOut), the geometry of one of them (plane_geometry) and the prologue of a frames
-// workgroup (frames_prologue).  Host side: how an entry describes its planes (bits_out_uniform / bits_out_frames) and the ONE
-// argument check of the packer entries (pack_check), with the wording more than one unit uses.  (Refusals: refuse, la3d_device.hpp.)
+// la3d_rle_encode.hip: the run-length encoder; la3d_open.hip: the opening; la3d_components.hip: connected components;
+// la3d_cloud.hip: the prologue; la3d_overlap.hip: at() and the offset rule).
+// Device side: where the planes of a call lie (BitsOut), the geometry of one of them (plane_geometry), the prologue of a frames
+// workgroup (frames_prologue) and, for a frames call that reads planes and may write planes, its planes and their locator
+// (FramesPlanes, frames_source, frames_dest: the end-inside-the-buffer checks behind the prologue); the rule of a plane offset
+// (plane_offset_ok) and the realigned word of an image row (plane_row_word).  Host side: how an entry describes its planes
+// (bits_out_uniform / bits_out_frames), the ONE argument check of the packer entries (pack_check), the in-place rule (planes_overlap)
+// and the wording more than one unit uses.  (Refusals: refuse, la3d_device.hpp.)
 // A BitsOut describes the planes of ONE call, in the uniform form (stride) or the frames form (offsets, frames, image_index):
 //   as a DESTINATION (every packer) the kernels store the words of instance b's plane through `bits` and, where the entry has one,
 //     its popcount to area[b];
@@ -55,9 +58,11 @@ __device__ inline unsigned image_columns(int w, int W, int fw) {
   const int rem = fw - (w % (W >> 5)) * 32;
   return rem >= 32 ? 0xffffffffu : rem <= 0 ? 0u : (1u << rem) - 1u;
 }
+// the rule of a plane's offset, in words from its buffer: >= 0 and a multiple of 4 (a 16-byte aligned plane) - the rule of the fit
+__device__ inline bool plane_offset_ok(long long off) { return off >= 0 && (off & 3) == 0; }
 __device__ inline bool frames_plane_at(const long long* __restrict__ offsets, int b, long long* off) {
-  const long long oo = poly_uniform(offsets[b]);
-  if (oo < 0 || (oo & 3) != 0) return false;
+  const long long oo = uniform_i64(offsets[b]);
+  if (!plane_offset_ok(oo)) return false;
   *off = oo;
   return true;
 }
@@ -84,6 +89,41 @@ __device__ inline bool frames_prologue(const la3d_frame* frames, int P, const in
     f->have = f->live ? image_columns(f->w, r.W, r.fw) : 0u;
   }
   return true;
+}
+
+// ---- the plane locator of a frames call that reads planes and may write planes (opening, components) ---------------------------
+// The planes of such a call (kernel argument): row b reads the plane `offsets[b]` words into a buffer of `bits_words` words and, where
+// the call stores planes, writes the one `out_offsets[b]` words into a buffer of `out_words`.
+struct FramesPlanes {
+  const long long* offsets; const long long* out_offsets;   // [B] words from the input / output buffer to the plane of each row
+  const la3d_frame* frames; const int* image_index; int P;
+  long long bits_words, out_words;         // words of the two buffers: a plane that does not end inside its buffer is refused
+};
+// Row b's SOURCE plane: steps 1 - 4 of frames_prologue (max_h, max_w: the bounds of the table), then that the plane ends inside its
+// buffer `bits`.  The plane is the f->nwords words at bits + f->off: the caller forms that address, and only behind `true`.
+__device__ inline bool frames_source(const FramesPlanes& c, const unsigned* bits, int max_h, int max_w, int b, FramesWork* f) {
+  if (!frames_prologue<true, false>(c.frames, c.P, c.image_index, max_h, max_w, const_cast<unsigned*>(bits), c.offsets, b, 0, f)) return false;
+  return f->off <= c.bits_words - f->nwords;
+}
+// Row b's DESTINATION plane of `words` words (the caller says how many its plane needs: it knows what it writes): the offset by the
+// rule of step 3, then that the plane ends inside its buffer.  Called behind frames_source, and only where the call stores planes.
+__device__ inline bool frames_dest(const FramesPlanes& c, int b, int words, long long* off) {
+  if (!frames_plane_at(c.out_offsets, b, off)) return false;
+  return *off <= c.out_words - words;
+}
+
+// the `valid` (>= 1; 32 or more: a whole word) columns from c0 on of image row v of a plane of pitch W, realigned so that column c0
+// is bit 0; the bits above them are zero whatever the plane holds - a caller that passes no more than fw - c0 never sees a padding
+// column.  nwords: the words of the plane - nothing beyond is read (N: the caller's type for it, which a word is indexed with).
+template <typename N>
+__device__ inline unsigned plane_row_word(const unsigned* __restrict__ plane, N nwords, int W, int v, int c0, int valid) {
+  const long long i = (long long)v * W + c0;
+  const N w = (N)(i >> 5);
+  const unsigned sh = (unsigned)(i & 31);
+  unsigned x = plane[w] >> sh;
+  if (sh && w + 1 < nwords) x |= plane[w + 1] << (32 - sh);
+  if (valid < 32) x &= (1u << valid) - 1u;
+  return x;
 }
 
 // The geometry and the plane of instance b.  false (frames form): the instance is refused - nothing is written for it.
@@ -129,6 +169,10 @@ BitsOut bits_out_frames(const la3d_frame* frames, int P, int H, int W, const int
 }
 
 inline uintptr_t at(const void* q) { return reinterpret_cast<uintptr_t>(q); }   // for the alignment and overlap rules an entry writes out
+// the in-place rule of an entry that cannot work in place: do `in_words` words at `in` and `out_words` words at `out` share a byte?
+inline bool planes_overlap(const void* in, uintptr_t in_words, const void* out, uintptr_t out_words) {
+  return at(in) < at(out) + out_words * 4 && at(out) < at(in) + in_words * 4;
+}
 
 // The argument check of every packer entry.  The rules and their rank are the same for all of them and stated here, once; an entry
 // brings its sizes, its pointers and ITS wording of each rule (the text of a refusal is part of the C ABI: two entries that phrase one

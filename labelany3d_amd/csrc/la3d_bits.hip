@@ -556,7 +556,7 @@ __global__ __launch_bounds__(256) void pack_masks_frames_kernel(const void* __re
   const long long oo = f.off;
   const int w = f.w;
   const bool live = f.live;
-  const long long so = poly_uniform(src_offsets[n]);
+  const long long so = uniform_i64(src_offsets[n]);
   const int pitch = src_pitch ? __builtin_amdgcn_readfirstlane(src_pitch[n]) : r.fw;
   if (so < 0 || pitch < r.fw) {   // (uniform) a source that cannot be read: an empty plane, never what the memory held before
     if (live) out[oo + w] = 0u;

@@ -14,9 +14,7 @@
 #include <cstddef>
 #include <cstring>
 
-#include "la3d_device.hpp"
-
-using namespace la3d;
+#include "la3d_bitplanes.hpp"   // (frames_prologue)
 
 namespace {
 constexpr int CT = 256;                     // threads per workgroup
@@ -53,8 +51,8 @@ struct CloudGeom {
   long long plane_words;        // words of the bit plane
 };
 
-// Frames form: the decision is made before any address is formed from the row - image index, then the frame row (frame_row_ok), then
-// the plane offset by the rule of frame_bits_offset_ok (>= 0, a multiple of 4), loaded only behind an accepted row.
+// Frames form: the decision is made before any address is formed from the row, by frames_prologue (image index, frame row, plane
+// offset; la3d_bitplanes.hpp).  The entry has no length of the bit buffer, so there is no end check here.
 template <bool FRAMES>
 __device__ inline CloudGeom cloud_geom(const CloudParams& p, int n) {
   CloudGeom g;
@@ -62,16 +60,12 @@ __device__ inline CloudGeom cloud_geom(const CloudParams& p, int n) {
   g.H = p.H; g.W = p.W; g.fw = p.fw;
   g.img = __builtin_amdgcn_readfirstlane(p.image_index ? p.image_index[n] : n);
   if (FRAMES) {
-    if ((unsigned)g.img >= (unsigned)p.P) return g;
-    const FrameRow r = frame_row_load(p.frames + g.img);
-    if (!frame_row_ok(r, p.H, p.W)) return g;
-    const long long bo_v = p.bits_offsets[n];
-    const long long bo = ((long long)__builtin_amdgcn_readfirstlane((int)(bo_v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)bo_v);
-    if (bo < 0 || (bo & 3) != 0) return g;
-    g.H = r.H; g.W = r.W; g.fw = r.fw;
-    g.depth_off = r.off;
-    g.bits = p.bits + bo;
-    g.plane_words = ((long long)r.H * r.W) >> 5;   // (W % 32 == 0: whole words)
+    FramesWork f;
+    if (!frames_prologue<true, false>(p.frames, p.P, p.image_index, p.H, p.W, const_cast<unsigned*>(p.bits), p.bits_offsets, n, 0, &f)) return g;
+    g.H = f.r.H; g.W = f.r.W; g.fw = f.r.fw;
+    g.depth_off = f.r.off;
+    g.bits = f.out;
+    g.plane_words = f.nwords;                      // (W % 32 == 0: whole words)
   } else {
     g.depth_off = (long long)g.img * p.depth_stride;
     if (p.mask) g.mask = p.mask + (long long)n * p.mask_stride;
@@ -90,10 +84,6 @@ struct CloudLds {
   unsigned short gw[BAND_WORDS];          // the word that holds rank 64 g, for every g with 64 g < the band's count: where a select starts
   unsigned wsum[CT / 64];
 };
-
-__device__ inline unsigned nz4(unsigned x) {   // four bytes -> four bits (non-zero = 1)
-  return ((x & 0xffu) ? 1u : 0u) | ((x & 0xff00u) ? 2u : 0u) | ((x & 0xff0000u) ? 4u : 0u) | ((x & 0xff000000u) ? 8u : 0u);
-}
 
 // Rows [v0, v1) of the instance's mask -> the band's bit image, columns >= frame width cleared, and its word prefix.  Returns the
 // number of set pixels.  (v1 - v0) * W <= BAND_PIX.  Every thread of the workgroup calls it.

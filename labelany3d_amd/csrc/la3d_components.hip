@@ -1,6 +1,7 @@
 // la3d_components.hip - connected components on bit planes (include/la3d.h "connected components on bit planes"):
 // la3d_components_bits and its frames form, la3d_components_bits_frames: kernels and C entries in one unit.  From la3d_bitplanes.hpp
-// come the frames prologue of a workgroup, at() and the wording shared with the packers.
+// come the planes of a frames call and their locator (FramesPlanes, frames_source, frames_dest), the realigned word of an image row
+// (plane_row_word), the in-place rule (planes_overlap), at() and the wording shared with the packers.
 #include <cstdint>
 #include <cstddef>
 
@@ -52,30 +53,23 @@ struct CompArgs {
   int* stats; int* comps;
   int* ws; long long ws_stride;            // ints per plane: 4 * max_runs + 2 * H
 };
-// frames form, beside a CompArgs whose fields that speak of ONE plane (stride, out_stride, fw, nw, nwords) are unused: those are formed
-// per workgroup (comp_plane).  A kernel argument of its own: the uniform instantiation never reads it, and its CompArgs is the block
-// it always had.
-struct CompFrames {
-  const long long* offsets; const long long* out_offsets;   // [B] words from bits / out to the plane of each row
-  const la3d_frame* frames; const int* image_index; int P;
-  long long bits_words, out_words;         // words of the two buffers: a plane that does not end inside its buffer is refused
-};
+// frames form: a FramesPlanes (la3d_bitplanes.hpp) beside a CompArgs whose fields that speak of ONE plane (stride, out_stride, fw, nw,
+// nwords) are unused - those are formed per workgroup (comp_plane).  A kernel argument of its own: the uniform instantiation never
+// reads it, and its CompArgs is the block it always had.
 // what a workgroup works on: the geometry of its plane, where it is read and where the result goes (NULL: statistics only)
 struct CompPlane { int H, W, fw, nw, nwords; const unsigned* plane; unsigned* op; };
 
 // The plane of workgroup b.  Uniform form: the argument block's own geometry, planes a stride apart.  Frames form: formed here from the
-// la3d_frame row of image_index[b] - every value wave-uniform, through scalar loads, checked before an address is formed from it, in
-// the order of frames_prologue (image index, frame row, input offset), then the output offset (the same rule), then that either plane
-// ends inside its buffer.  The output has the input's geometry.  false: refused - nothing is read, nothing is written through it.
+// la3d_frame row of image_index[b] by the locator of la3d_bitplanes.hpp (frames_source, then frames_dest where a plane is stored) -
+// every value wave-uniform, checked before an address is formed from it.  The output has the input's geometry.  false: refused -
+// nothing is read, nothing is written through it.
 template <bool FRAMES>
-__device__ inline bool comp_plane(const CompArgs& a, const CompFrames& fr, int b, CompPlane* g) {
+__device__ inline bool comp_plane(const CompArgs& a, const FramesPlanes& fr, int b, CompPlane* g) {
   if constexpr (FRAMES) {
     FramesWork f;
-    if (!frames_prologue<true, false>(fr.frames, fr.P, fr.image_index, a.H, a.W, const_cast<unsigned*>(a.bits), fr.offsets, b, 0, &f)) return false;
+    if (!frames_source(fr, a.bits, a.H, a.W, b, &f)) return false;
     long long oo = 0;
-    if (a.out && !frames_plane_at(fr.out_offsets, b, &oo)) return false;
-    if (f.off > fr.bits_words - f.nwords) return false;
-    if (a.out && oo > fr.out_words - f.nwords) return false;
+    if (a.out && !frames_dest(fr, b, f.nwords, &oo)) return false;
     g->H = f.r.H; g->W = f.r.W; g->fw = f.r.fw; g->nw = (f.r.fw + 31) >> 5; g->nwords = f.nwords;
     g->plane = a.bits + f.off;               // (formed only now: after the last check)
     g->op = a.out ? a.out + oo : nullptr;
@@ -89,14 +83,7 @@ __device__ inline bool comp_plane(const CompArgs& a, const CompFrames& fr, int b
 
 // word wc of image row v, aligned to the row's first column; columns at and beyond fw are zero whatever the plane holds
 __device__ inline unsigned comp_row_word(const CompPlane& a, const unsigned* __restrict__ plane, int v, int wc) {
-  const long long i = (long long)v * a.W + wc * 32;
-  const int w = (int)(i >> 5);
-  const unsigned sh = (unsigned)(i & 31);
-  unsigned x = plane[w] >> sh;
-  if (sh && w + 1 < a.nwords) x |= plane[w + 1] << (32 - sh);
-  const int valid = a.fw - wc * 32;
-  if (valid < 32) x &= (1u << valid) - 1u;
-  return x;
+  return plane_row_word(plane, a.nwords, a.W, v, wc * 32, a.fw - wc * 32);
 }
 
 // item `it` = (row v, word wc): its word, carry = the pixel left of the word, next = the pixel right of it (both 0 outside the row's
@@ -169,7 +156,7 @@ __device__ inline void comp_unite(int* parent, int a, int b) {
 }
 
 template <bool COMP_LDS, bool FRAMES>
-__global__ __launch_bounds__(COMP_NT) void components_kernel(const CompArgs a, const CompFrames fr) {
+__global__ __launch_bounds__(COMP_NT) void components_kernel(const CompArgs a, const FramesPlanes fr) {
   extern __shared__ __attribute__((aligned(16))) int comp_smem[];
   __shared__ int red[COMP_NW + 1];
   const int tid = threadIdx.x, b = blockIdx.x;
@@ -401,9 +388,8 @@ int la3d_components_bits(const la3d_components_args* args) {
   if (g.out_bits) {
     if (out_stride < words) return refuse(who, "out_plane_stride is smaller than la3d_mask_bits_words(H, W)");
     // a word of the output is gathered from runs listed before: the call does not work in place
-    const uintptr_t i0 = at(g.mask_bits), i1 = i0 + (uintptr_t)g.B * (uintptr_t)stride * 4;
-    const uintptr_t o0 = at(g.out_bits), o1 = o0 + (uintptr_t)g.B * (uintptr_t)out_stride * 4;
-    if (i0 < o1 && o0 < i1) return refuse(who, "the input planes and the output planes overlap");
+    if (planes_overlap(g.mask_bits, (uintptr_t)g.B * (uintptr_t)stride, g.out_bits, (uintptr_t)g.B * (uintptr_t)out_stride))
+      return refuse(who, "the input planes and the output planes overlap");
   }
   CompArgs a = {};
   a.bits = g.mask_bits; a.stride = stride; a.out = g.out_bits; a.out_stride = out_stride;
@@ -415,9 +401,9 @@ int la3d_components_bits(const la3d_components_args* args) {
   hipStream_t st = static_cast<hipStream_t>(g.stream);
   if (g.max_runs <= COMP_LDS_RUNS) {
     allow_big_lds(reinterpret_cast<const void*>(components_kernel<true, false>));
-    hipLaunchKernelGGL((components_kernel<true, false>), dim3((unsigned)g.B), dim3(COMP_NT), (size_t)g.max_runs * sizeof(int), st, a, CompFrames{});
+    hipLaunchKernelGGL((components_kernel<true, false>), dim3((unsigned)g.B), dim3(COMP_NT), (size_t)g.max_runs * sizeof(int), st, a, FramesPlanes{});
   } else {
-    hipLaunchKernelGGL((components_kernel<false, false>), dim3((unsigned)g.B), dim3(COMP_NT), 0, st, a, CompFrames{});
+    hipLaunchKernelGGL((components_kernel<false, false>), dim3((unsigned)g.B), dim3(COMP_NT), 0, st, a, FramesPlanes{});
   }
   return check_launch("components_kernel");
 }
@@ -440,10 +426,9 @@ int la3d_components_bits_frames(const la3d_components_frames_args* args) {
   if ((at(g.bits_offsets) | at(g.out_offsets) | at(g.frames)) & 7) return refuse(who, "bits_offsets, out_offsets or frames not an 8-byte aligned pointer");
   if ((at(g.stats) | at(g.components) | at(g.workspace) | at(g.image_index)) & 3)
     return refuse(who, "stats, components, workspace or image_index not a 4-byte aligned pointer");
-  if (g.bits && g.out_bits) {   // a word of the output is gathered from runs listed before: the call does not work in place
-    const uintptr_t i0 = at(g.bits), i1 = i0 + (uintptr_t)g.bits_words * 4, o0 = at(g.out_bits), o1 = o0 + (uintptr_t)g.out_words * 4;
-    if (i0 < o1 && o0 < i1) return refuse(who, "the input buffer and the output buffer overlap");
-  }
+  // a word of the output is gathered from runs listed before: the call does not work in place
+  if (g.bits && g.out_bits && planes_overlap(g.bits, (uintptr_t)g.bits_words, g.out_bits, (uintptr_t)g.out_words))
+    return refuse(who, "the input buffer and the output buffer overlap");
   if (g.B > 0) {
     if (!g.bits || !g.bits_offsets || !g.image_index || !g.workspace || (!g.frames && g.P > 0))
       return refuse(who, "NULL bits, bits_offsets, image_index, workspace or frames");
@@ -460,7 +445,7 @@ int la3d_components_bits_frames(const la3d_components_frames_args* args) {
   a.maxc = g.components ? g.max_components : 0;
   a.stats = g.stats; a.comps = g.components;
   a.ws = static_cast<int*>(g.workspace); a.ws_stride = 4 * (long long)g.max_runs + 2 * (long long)g.H;
-  CompFrames fr = {};
+  FramesPlanes fr = {};
   fr.offsets = reinterpret_cast<const long long*>(g.bits_offsets); fr.out_offsets = reinterpret_cast<const long long*>(g.out_offsets);
   fr.frames = g.frames; fr.image_index = g.image_index; fr.P = g.P;   // (P == 0: every row is refused before a frame row is addressed)
   fr.bits_words = g.bits_words; fr.out_words = g.out_bits ? g.out_words : 0;

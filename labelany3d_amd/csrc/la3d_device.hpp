@@ -1,6 +1,10 @@
-// la3d_device.hpp — device-side building blocks shared by the fit engines (la3d.hip: one workgroup per
-// instance; la3d_split.hip: band scan + tile-range-balanced passes).  Reference semantics cited per
-// function (paths relative to /root/reference).
+// la3d_device.hpp - what every unit of the library shares.  Host side: how a C entry refuses a call (refuse), the process defaults
+// (Config), the launch helpers (check_launch, allow_big_lds).  Device side: the argument block of a fit (FitParams, FitParams16) and
+// its per-workgroup state (Shared), the 3x3 algebra and the box record, wave reductions and DPP moves, wave-uniform values
+// (uniform_f64, uniform_i64), the mask-byte patterns (nz4, nz16), depth conversion of 16-bit planes, the bit image of a mask in LDS,
+// and the frame row of a frames call with its contract (FrameRow, frame_row_ok, frame_geometry).  Everything a fit kernel compiles
+// from lies here, in la3d_poly.hpp or in the engine headers; what only the bit-plane units share lies in la3d_bitplanes.hpp.
+// Reference semantics are cited per function (paths relative to the root of the reference project).
 #pragma once
 #ifndef LA3D_NT
 #define LA3D_NT 512
@@ -442,6 +446,10 @@ __device__ inline double uniform_f64(double v) {
   const unsigned hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
   return __hiloint2double((int)hi, (int)lo);
 }
+// wave-uniform 64-bit integer -> SGPR pair, likewise (offsets and ranks that come through a load)
+__device__ inline long long uniform_i64(long long v) {
+  return ((long long)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+}
 
 // XCD-aware block -> work-item map: the dispatcher is observed to place block b on XCD b % 8
 // (speed only, never correctness), so consecutive instances — which share an image's depth
@@ -766,7 +774,10 @@ __host__ __device__ inline int tiled_list_cap(int bit_bytes, int nwords, int nti
 // loads), and the contract of include/la3d.h ("images of different sizes in one call") it must keep before any address is formed from
 // it: the rule of frame_geometry below, term for term, so that packer and fit refuse exactly the same rows - a change of either is a
 // change of both.  (frame_geometry keeps its own text: calling frame_row_ok from it re-schedules the scalar compares of every frames
-// instantiation, and those keep the instruction streams they had.)
+// instantiation, and those keep the instruction streams they had.  For the same reason frame_row_load and frame_geometry keep the
+// readfirstlane pair of the row's depth_offset written out: behind uniform_i64 the value is known not to be undefined, the compiler
+// joins the compares that follow it differently, and the frames instantiations of the fit and of every packer change -
+// profiles/frames_locator/RESULTS.md.)
 struct FrameRow { long long off; int H, W, fw; };
 __device__ inline FrameRow frame_row_load(const la3d_frame* fr) {
   const long long off_v = fr->depth_offset;
@@ -821,7 +832,7 @@ __device__ inline void frame_proj(FitParams& p, const FitParams& call, int inst)
 // is streamed - like frame_depth_offset, and for the reason given there: the table is an input of the call that nothing writes
 __device__ inline long long frame_bits_offset(const FitParams& call, int inst) {
   const long long off_v = call.bits_offsets[inst];
-  return ((long long)__builtin_amdgcn_readfirstlane((int)(off_v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)off_v);
+  return uniform_i64(off_v);
 }
 __device__ inline bool frame_bits_offset_ok(const FitParams& call, int inst) {
   const long long off = frame_bits_offset(call, inst);

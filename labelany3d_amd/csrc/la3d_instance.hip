@@ -61,7 +61,7 @@ __device__ inline DepthCvt<DepthT> depth_cvt(const FitParams16& call) {
 // which nothing writes while the call runs (include/la3d.h: frames), so both loads see the same value
 __device__ inline long long frame_depth_offset(const FitParams& call, int img) {
   const long long off_v = call.frames[img].depth_offset;
-  return ((long long)__builtin_amdgcn_readfirstlane((int)(off_v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)off_v);
+  return uniform_i64(off_v);
 }
 #endif
 // ------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 // la3d_open.hip - morphology on bit planes (include/la3d.h "morphology on bit planes"): la3d_open_bits and its frames form,
 // la3d_open_bits_frames.  The checks of the two entries are written out here - their rank is theirs, not pack_check's; from
-// la3d_bitplanes.hpp come the frames prologue of a workgroup and the wording shared with the packers.
+// la3d_bitplanes.hpp come the planes of a frames call and their locator (FramesPlanes, frames_source, frames_dest), the realigned word
+// of an image row (plane_row_word), the in-place rule (planes_overlap) and the wording shared with the packers.
 #include <cstdint>
 #include <cstddef>
 
@@ -34,11 +35,8 @@ struct OpenArgs {
   int nwords_out;                           // words of an output plane
   int R, nA, nbands, vec;                   // band rows; rows of A; bands per plane; 16-byte stores allowed
   int* partial;                             // [B][nbands][8] or NULL
-  // frames form (H, W: the bounds of the table; the fields above that speak of a plane are then formed per instance, open_instance)
-  const long long* offsets; const long long* out_offsets;   // [B] words from bits / out to the plane of each instance
-  const la3d_frame* frames; const int* image_index; int P;
-  long long bits_words, out_words;          // words of the two buffers: a plane that does not end inside its buffer is refused
-};
+  FramesPlanes fr;                          // frames form (H, W: the bounds of the table; the fields above that speak of a plane are then
+};                                          // formed per instance, open_instance)
 
 __device__ inline unsigned spread_bits(unsigned x, int s) {   // the low 32 / s bits of x, each repeated s times
   if (s == 4) {
@@ -55,14 +53,7 @@ __device__ inline unsigned spread_bits(unsigned x, int s) {   // the low 32 / s 
 // word wc of the aligned, upscaled form of source row v (0 <= v < H, wc < nw): columns at and beyond fw are zero whatever the plane holds
 __device__ inline unsigned open_source_word(const OpenArgs& a, const unsigned* __restrict__ plane, int v, int wc) {
   const int nb = 32 >> (a.s >> 1), c0 = wc * nb;       // 32 / s for s = 1, 2, 4
-  const long long i = (long long)v * a.W + c0;
-  const long long w = i >> 5;
-  const unsigned sh = (unsigned)(i & 31);
-  unsigned x = plane[w] >> sh;
-  if (sh && w + 1 < a.nwords_in) x |= plane[w + 1] << (32 - sh);
-  const int valid = min(nb, a.fw - c0);
-  if (valid < 32) x &= (1u << valid) - 1u;
-  return spread_bits(x, a.s);
+  return spread_bits(plane_row_word(plane, a.nwords_in, a.W, v, c0, min(nb, a.fw - c0)), a.s);
 }
 
 __device__ inline unsigned long long and_window(unsigned long long x, int k) {   // bit i = AND of bits i .. i + k - 1
@@ -97,21 +88,18 @@ struct OpenItem {
 };
 
 // The plane geometry of instance b.  Uniform form: the argument block's own, planes a stride apart.  Frames form: formed here from the
-// la3d_frame row of image_index[b] - every value wave-uniform, through scalar loads, checked before an address is formed from it, in
-// the order of frames_prologue (image index, frame row, input offset), then the output offset (the same rule), then that either plane
-// ends inside its buffer.  The output plane is the one frame_table lays out for an image of (s * H, s * fw): pitch roundup32(s * fw),
-// so its rows are whole words.  false: refused - nothing is read, nothing is written.
+// la3d_frame row of image_index[b] by the locator of la3d_bitplanes.hpp (frames_source, then frames_dest where planes are stored) -
+// every value wave-uniform, checked before an address is formed from it.  The output plane is the one frame_table lays out for an
+// image of (s * H, s * fw): pitch roundup32(s * fw), so its rows are whole words.  false: refused - nothing is read, nothing is written.
 template <bool FRAMES>
 __device__ inline bool open_instance(const OpenArgs& a, int b, OpenArgs* g, const unsigned** plane, unsigned** op) {
   if constexpr (FRAMES) {
     FramesWork f;
-    if (!frames_prologue<true, false>(a.frames, a.P, a.image_index, a.H, a.W, const_cast<unsigned*>(a.bits), a.offsets, b, 0, &f)) return false;
-    long long oo = 0;
-    if (a.out && !frames_plane_at(a.out_offsets, b, &oo)) return false;
+    if (!frames_source(a.fr, a.bits, a.H, a.W, b, &f)) return false;
     const int fw_out = a.s * f.r.fw, W_out = (fw_out + 31) & ~31, H_out = a.s * f.r.H;
     const int words_out = H_out * (W_out >> 5);          // (<= 2^23: the entry bounds s * H * roundup32(s * W) by 2^28)
-    if (f.off > a.bits_words - f.nwords) return false;
-    if (a.out && oo > a.out_words - words_out) return false;
+    long long oo = 0;
+    if (a.out && !frames_dest(a.fr, b, words_out, &oo)) return false;
     g->H = f.r.H; g->W = f.r.W; g->fw = f.r.fw; g->nwords_in = f.nwords;
     g->H_out = H_out; g->W_out = W_out; g->nw = W_out >> 5; g->nwords_out = words_out;
     g->vec = (W_out & 127) == 0;                         // (out is 16-byte aligned - checked on the host - and the offset a multiple of 4)
@@ -354,9 +342,8 @@ int la3d_open_bits(const uint32_t* bits, int64_t bits_plane_stride, int B, int H
   if (out_bits) {
     if (out_plane_stride < words_out) return refuse(who, "out_plane_stride is smaller than la3d_mask_bits_words(upscale * H, W_out)");
     // neighbouring bands read each other's halo: the call cannot work in place
-    const uintptr_t i0 = reinterpret_cast<uintptr_t>(bits), i1 = i0 + (uintptr_t)B * (uintptr_t)bits_plane_stride * 4;
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out_bits), o1 = o0 + (uintptr_t)B * (uintptr_t)out_plane_stride * 4;
-    if (i0 < o1 && o0 < i1) return refuse(who, "the input planes and the output planes overlap");
+    if (planes_overlap(bits, (uintptr_t)B * (uintptr_t)bits_plane_stride, out_bits, (uintptr_t)B * (uintptr_t)out_plane_stride))
+      return refuse(who, "the input planes and the output planes overlap");
   }
   const int nw = (s * frame_width + 31) / 32;
   const OpenPlan p = open_plan(H_out, nw, k, s);
@@ -397,10 +384,9 @@ int la3d_open_bits_frames(const uint32_t* bits, int64_t bits_words, const int64_
   if ((at(bits) | at(out_bits)) & 15) return refuse(who, "bits or out_bits not a 16-byte aligned pointer");
   if ((at(bits_offsets) | at(out_offsets) | at(frames)) & 7) return refuse(who, "bits_offsets, out_offsets or frames not an 8-byte aligned pointer");
   if ((at(stats) | at(workspace) | at(image_index)) & 3) return refuse(who, "stats, workspace or image_index not a 4-byte aligned pointer");
-  if (bits && out_bits) {   // neighbouring bands read each other's halo: the call cannot work in place
-    const uintptr_t i0 = at(bits), i1 = i0 + (uintptr_t)bits_words * 4, o0 = at(out_bits), o1 = o0 + (uintptr_t)out_words * 4;
-    if (i0 < o1 && o0 < i1) return refuse(who, "the input buffer and the output buffer overlap");
-  }
+  // neighbouring bands read each other's halo: the call cannot work in place
+  if (bits && out_bits && planes_overlap(bits, (uintptr_t)bits_words, out_bits, (uintptr_t)out_words))
+    return refuse(who, "the input buffer and the output buffer overlap");
   if ((long long)s * W > 8192) return refuse(who, "upscale * W must not exceed 8192 (a band of rows lives in LDS)", LA3D_ERR_UNSUPPORTED);
   const long long W_out = ((long long)s * W + 31) / 32 * 32;
   if ((long long)s * H > (1LL << 28) || (long long)s * H * W_out > (1LL << 28))
@@ -412,8 +398,8 @@ int la3d_open_bits_frames(const uint32_t* bits, int64_t bits_words, const int64_
   a.bits = bits; a.H = H; a.W = W; a.k = k; a.s = s; a.out = out_bits;
   a.R = p.R; a.nA = p.nA; a.nbands = p.nbands;
   a.partial = stats ? static_cast<int*>(workspace) : nullptr;
-  a.offsets = reinterpret_cast<const long long*>(bits_offsets); a.out_offsets = reinterpret_cast<const long long*>(out_offsets);
-  a.frames = frames; a.image_index = image_index; a.P = P; a.bits_words = bits_words; a.out_words = out_bits ? out_words : 0;
+  a.fr.offsets = reinterpret_cast<const long long*>(bits_offsets); a.fr.out_offsets = reinterpret_cast<const long long*>(out_offsets);
+  a.fr.frames = frames; a.fr.image_index = image_index; a.fr.P = P; a.fr.bits_words = bits_words; a.fr.out_words = out_bits ? out_words : 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (P > 0) {   // (no image: every row is refused, which the statistics kernel alone says)
     allow_big_lds(reinterpret_cast<const void*>(open_bits_kernel<true>));

@@ -17,9 +17,7 @@
 #include <cstddef>
 #include <cstring>
 
-#include "la3d_bitplanes.hpp"   // (at)
-
-using namespace la3d;
+#include "la3d_bitplanes.hpp"   // (at, plane_offset_ok)
 
 namespace {
 constexpr int OT = 256;                  // threads of an overlap workgroup
@@ -50,9 +48,7 @@ template <bool FRAMES>
 __device__ inline bool group_ok(const OverlapParams& p, const la3d_overlap_tile& t) {
   if constexpr (FRAMES) {
     if ((unsigned)t.g >= (unsigned)p.P) return false;
-    const la3d_frame* fr = p.frames + t.g;
-    FrameRow r;
-    r.off = fr->depth_offset; r.H = fr->H; r.W = fr->W; r.fw = fr->frame_width;
+    const FrameRow r = frame_row_load(p.frames + t.g);
     if (!frame_row_ok(r, p.H, p.W)) return false;
     return (int)(((long long)r.H * r.W) >> 5) == t.nw;
   }
@@ -65,13 +61,10 @@ __device__ inline long long plane_at(long long stride, const long long* off, con
   if constexpr (FRAMES) {
     if (img[row] != g) return -1;
     const long long o = off[row];
-    if (o < 0 || (o & 3) != 0 || o > words - nw) return -1;
+    if (!plane_offset_ok(o) || o > words - nw) return -1;
     return o;
   }
   return (long long)row * stride;
-}
-__device__ inline long long uniform_i64(long long v) {
-  return ((long long)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v);
 }
 
 // the four words of one plane a lane takes in the step that starts at word `base` (a multiple of STEP).  VEC: the 16 bytes at

@@ -328,11 +328,8 @@ __device__ __forceinline__ void poly_ring_general(const int* __restrict__ xy, lo
 // All rings [r0, r1) of one instance -> bit image (zeroed here).  xy: int32 pairs; ring_off: point offsets of the rings
 // (ring r = points ring_off[r] .. ring_off[r+1]).  stage: LDS, POLY_STAGE_BYTES; flags: LDS, max(NTH/64, 4) words.
 // Returns this thread's share of the pixel count.
-// wave-uniform 64-bit value -> SGPR pair (the ring bookkeeping below is uniform, but it is loaded through vector memory
-// instructions: left alone it occupies ~10 VGPRs across the rasteriser's loops, which is what made the 64-VGPR fit kernel spill)
-__device__ inline long long poly_uniform(long long v) {
-  return ((long long)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v);
-}
+// (uniform_i64 on the ring bookkeeping below: it is uniform, but it is loaded through vector memory instructions - left alone it
+// occupies ~10 VGPRs across the rasteriser's loops, which is what made the 64-VGPR fit kernel spill)
 
 template <int NTH>
 __device__ __forceinline__ int poly_to_bits(const int* __restrict__ xy, const long long* __restrict__ ring_off, long long r0, long long r1,
@@ -342,7 +339,7 @@ __device__ __forceinline__ int poly_to_bits(const int* __restrict__ xy, const lo
   // else works on the padded rows - a span or a parity run may reach into the columns [clipW, W) - and those columns are cleared
   // before the count.
   if (clipW <= 0 || clipW > W) clipW = W;
-  r0 = poly_uniform(r0); r1 = poly_uniform(r1);
+  r0 = uniform_i64(r0); r1 = uniform_i64(r1);
   for (int i = tid; i < nwords; i += NTH) bits[i] = 0;
   int* meta = reinterpret_cast<int*>(stage + POLY_CHUNK);   // [0..8] part bounds, [9 + 4 j ..] bounding box of part j, [41] verdict
   const int nr = (int)(r1 - r0);
@@ -381,7 +378,7 @@ __device__ __forceinline__ int poly_to_bits(const int* __restrict__ xy, const lo
       __syncthreads();
       if (meta[41]) joint = nr;   // uniform
     }
-    const long long p0 = poly_uniform(ring_off[r0]);
+    const long long p0 = uniform_i64(ring_off[r0]);
     const int n = __builtin_amdgcn_readfirstlane((int)(ring_off[r0 + joint] - p0));
     if (joint == 1) {
       if (tid == 0) { meta[0] = 0; meta[1] = n; }
@@ -394,7 +391,7 @@ __device__ __forceinline__ int poly_to_bits(const int* __restrict__ xy, const lo
     r = r0 + joint;
   }
   for (; r < r1; ++r) {   // whatever is left is OR-ed in by the general form
-    const long long p0 = poly_uniform(ring_off[r]);
+    const long long p0 = uniform_i64(ring_off[r]);
     const int n = __builtin_amdgcn_readfirstlane((int)(ring_off[r + 1] - p0));
     poly_ring_general<NTH>(xy, p0, n, stage, flags, bits, H, W, tid, clipW);
   }

@@ -166,7 +166,7 @@ __global__ __launch_bounds__(NT_DEC) void rle_encode_emit_kernel(const BitsOut c
     if (tid == 0) e.status[n] = LA3D_BOX_UNSUPPORTED;
     return;
   }
-  const long long off0 = poly_uniform(e.offsets[n]), off1 = poly_uniform(e.offsets[n + 1]);
+  const long long off0 = uniform_i64(e.offsets[n]), off1 = uniform_i64(e.offsets[n + 1]);
   if (off0 < 0 || off1 < off0 || off1 > e.capacity) {   // (uniform) no room: nothing of the instance is written
     if (tid == 0) e.status[n] = LA3D_RLE_NO_ROOM;
     return;

@@ -17,6 +17,8 @@ rectangles or ellipses; ``R`` input sets in rotation (64 x 100 planes are 246 MB
   bmm.u8          the same matmul from u8 planes that are already resident (no unpack): the fairest case for the other side
   nms.torch       greedy NMS without torchvision: the bmm.u8 matrix of an image, copied to the host (one synchronisation per image),
                   and the plain loop there
+The shape ``frames<P>x<n>`` is the frames form: P images of the project's mixed-size mix with n planes each, as resident ``FrameBits``
+  self / self.iou / ab.iou   as above, through ``mask_overlap(fb, ..., frames=pm, plan=plan)``; no other route is timed for it
 Every line is warmed up and timed over ``steps`` calls between two HIP events with the host's clock beside them (``host_us``),
 ``steps`` raised until a run lasts ``--min-ms``, the lines alternated ``--reps`` times.  Before anything is timed the routes are
 compared: inter exactly, keep exactly.  Prints one JSON document."""
@@ -34,7 +36,7 @@ p = argparse.ArgumentParser()
 p.add_argument("--out", default=None)
 p.add_argument("--reps", type=int, default=3)
 p.add_argument("--min-ms", type=float, default=50.0, help="a timed run lasts at least this long")
-p.add_argument("--shapes", default="1x16,1x100,64x100,256xP7")
+p.add_argument("--shapes", default="1x16,1x100,64x100,256xP7,frames256x7")
 args = p.parse_args()
 sys.path.insert(0, ROOT)
 
@@ -88,6 +90,41 @@ def summarise(v):
     runs = sorted(t for t, _ in v)
     return dict(median=float(np.median(runs)), min=runs[0], max=runs[-1], spread=runs[-1] - runs[0], in_order=[t for t, _ in v],
                 host_us=float(np.median([h for _, h in v])))
+
+
+COCO_SIZES = [(480, 640), (640, 480), (427, 640), (640, 427), (426, 640), (428, 640), (375, 500), (500, 375), (333, 500), (425, 640),
+              (480, 480), (640, 640), (360, 640), (500, 333), (612, 612), (424, 640), (334, 500), (512, 640)]
+
+
+def coco_mix(images, seed):
+    """the sizes of ``images`` images: share 1 / rank over COCO_SIZES, in a seeded arrival order (the project's mixed-size mix,
+    profiles/open_bits_frames/bench_open_bits_frames.py, restated here because that script runs on import)"""
+    rs = np.random.RandomState(seed)
+    share = 1.0 / np.arange(1, len(COCO_SIZES) + 1)
+    share /= share.sum()
+    n = np.maximum(1, np.round(share * images).astype(int))
+    n[0] += images - n.sum()
+    sizes = [s for s, k in zip(COCO_SIZES, n) for _ in range(k)]
+    return [sizes[i] for i in rs.permutation(len(sizes))]
+
+
+def make_stacks(sizes, per, seed):
+    """one (per, h, w) uint8 stack per image, made on the device: unions of three rectangles or ellipses"""
+    rs = np.random.RandomState(seed)
+    out = []
+    for h, w in sizes:
+        vv = torch.arange(h, device=dev)[:, None]
+        uu = torch.arange(w, device=dev)[None, :]
+        m = torch.zeros((per, h, w), dtype=torch.bool, device=dev)
+        for j in range(per):
+            for _ in range(3):
+                cy, cx, hy, hx = rs.randint(0, h), rs.randint(0, w), rs.randint(8, h // 3), rs.randint(8, w // 3)
+                if rs.rand() < 0.5:
+                    m[j] |= ((vv - cy).abs() <= hy) & ((uu - cx).abs() <= hx)
+                else:
+                    m[j] |= ((vv - cy) / float(hy)) ** 2 + ((uu - cx) / float(hx)) ** 2 <= 1.0
+        out.append(m.view(torch.uint8))
+    return out
 
 
 try:
@@ -196,10 +233,43 @@ def run_shape(name):
                 keep_equals_host_loop=keep_equal, kept=int(keep.sum()), lines_us=res, rates=rates)
 
 
-doc = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__, frame=[H, W], words=NW, bmm_float32_output=F32_OUT,
+def run_frames(name):
+    """the frames form on the mixed-size mix; before anything is timed three images are compared with the uniform call on them alone"""
+    imgs, per = name[len("frames"):].split("x")
+    P, per = int(imgs), int(per)
+    sizes = coco_mix(P, 7)
+    R = 2
+    stacks = [make_stacks(sizes, per, 3100 + r) for r in range(R)]
+    pms = [la.pack_mask_frames(x) for x in stacks]
+    fbs = [la.pack_mask_bits_frames(pm) for pm in pms]
+    clist = [per] * P
+    plan_s = la.mask_overlap_plan(fbs[0], None, clist, frames=pms[0])
+    plan_ab = la.mask_overlap_plan(fbs[0], fbs[1], clist, clist, frames=pms[0])
+    ov = la.mask_overlap(fbs[0], counts_a=clist, frames=pms[0], plan=plan_s)
+    exact = all(bool((ov.matrix(g) == la.mask_overlap(la.pack_mask_bits(stacks[0][g])).matrix(0)).all()) for g in (0, P // 2, P - 1))
+    assert exact and int((ov.area_a < 0).sum()) == 0
+    lines = {
+        "self": lambda k: la.mask_overlap(fbs[k % R], counts_a=clist, frames=pms[k % R], plan=plan_s),
+        "self.iou": lambda k: la.mask_overlap(fbs[k % R], counts_a=clist, frames=pms[k % R], iou="iou", plan=plan_s),
+        "ab.iou": lambda k: la.mask_overlap(fbs[k % R], fbs[(k + 1) % R], clist, clist, frames=pms[k % R], iou="iou", plan=plan_ab),
+    }
+    steps = {}
+    for key, fn in lines.items():
+        t, _ = time_device(fn, 2, 2)
+        steps[key] = int(min(max(2, np.ceil(args.min_ms * 1e3 / max(t, 1.0))), 2000))
+    raw = {key: [] for key in lines}
+    for _ in range(args.reps):
+        for key, fn in lines.items():
+            raw[key].append(time_device(fn, steps[key], 2))
+    res = {key: dict(summarise(v), steps=steps[key]) for key, v in raw.items()}
+    return dict(images=P, planes=P * per, sets=R, distinct_sizes=len(set(sizes)), tiles_self=len(plan_s.tiles_host), tiles_ab=len(plan_ab.tiles_host),
+                inter_equals_uniform=exact, lines_us=res)
+
+
+doc = dict(build_info=la._lib.lib.la3d_build_info().decode(), device=torch.cuda.get_device_name(0), torch=torch.__version__, frame=[H, W], words=NW, bmm_float32_output=F32_OUT,
            reps=args.reps, min_ms=args.min_ms, shapes={})
 for shape in args.shapes.split(","):
-    doc["shapes"][shape] = run_shape(shape)
+    doc["shapes"][shape] = run_frames(shape) if shape.startswith("frames") else run_shape(shape)
     print(shape, json.dumps({k: round(v["median"], 1) for k, v in doc["shapes"][shape]["lines_us"].items()}), flush=True)
 text = json.dumps(doc, indent=1)
 if args.out:

@@ -11,6 +11,7 @@ import pytest
 
 from . import components_cases as CC
 from . import components_frames_cases as XC
+from . import frames_fault_rows as FR
 from . import instance_points_cases as IC
 
 pytestmark = pytest.mark.gpu
@@ -203,51 +204,33 @@ def test_uniform_sizes_equal_components_bits_480x640(la):
 # 4. refused rows
 # ------------------------------------------------------------------------------------------
 def test_refused_rows_write_nothing_and_say_so(la):
-    """One bad value per refused row; every address a defect would form from it lies inside this test's own allocations (the table,
-    the input and the output have pad in front and behind), so a defect shows as a changed word, never as a fault."""
+    """One bad value per refused row - the shared case table (tests/frames_fault_rows.py) and the faults of the output, which are this
+    entry's own; every address a defect would form from it lies inside this test's own allocations (the table, the input and the
+    output have pad in front and behind), so a defect shows as a changed word, never as a fault."""
     import torch
 
-    from labelany3d_amd.frames import FRAME_DTYPE, table_words
-
     conn, min_area, largest = 8, CC.MIN_AREA, False
-    good = [(33, 47), (40, 32), (8, 33)]
     rs = np.random.RandomState(4)
-    H, W = 40, 64                                                                # the bounds of the good rows
-    t = np.zeros(9, FRAME_DTYPE)                                                 # rows -1 and P are pad: a valid frame, which nothing may use
-    t[0] = t[8] = (0, 8, 32, 32, 0)
-    for p, (h, w) in enumerate(good):
-        t[1 + p] = (0, h, CC.padded(w), w, 0)
-    t[4] = (0, 8, 48, 40, 0)                                                     # pitch 48: no multiple of 32
-    t[5] = (0, 41, 64, 40, 0)                                                    # H above the bound
-    t[6] = (0, 8, 32, 0, 0)                                                      # frame_width 0
-    t[7] = (0, 8, 32, 33, 0)                                                     # frame_width > W
-    table = torch.as_tensor(table_words(t), device="cuda")
-    P, SLOT, PAD = 7, 128, 64                                                    # slots of 128 words hold every plane, bad rows included
-    #        image  what
-    rows = [(0, None), (-1, "image index -1"), (1, None), (P, "image index P"), (3, "pitch 48"), (2, None), (4, "H above the bound"),
-            (5, "frame_width 0"), (6, "frame_width > W"), (0, None), (1, "input offset -4"), (2, "input offset 2"), (1, None),
-            (1, "output offset 6"), (0, "input plane ends one word past bits_words"), (0, "output plane ends one word past out_words"),
-            (2, None)]
-    B = len(rows)
-    bits_words, out_words = B * SLOT + 1, B * SLOT + 1
-    ioffs, ooffs = np.arange(B, dtype=np.int64) * SLOT, np.arange(B, dtype=np.int64) * SLOT
-    ioffs[10], ioffs[11], ooffs[13] = -4, ioffs[11] + 2, ooffs[13] + 6
-    ioffs[14] = bits_words - XC.plane_words(33, 47) + 1
-    ooffs[15] = out_words - XC.plane_words(33, 47) + 1
-    assert ioffs[14] % 4 == 0 and ooffs[15] % 4 == 0 and ioffs[14] >= 0 and ooffs[15] >= 0
-    inbuf = rs.randint(0, 2 ** 32, PAD + bits_words + PAD, dtype=np.uint64).astype(np.uint32)     # garbage wherever no plane lies
-    named = {}
+    SLOT, PAD = FR.SLOT, FR.PAD                                                  # slots of 128 words hold every plane, bad rows included
+    c = FR.case(end_check=True, extra=[(1, "output offset 6"), (2, "output offset -4"), (0, "output plane ends one word past out_words")])
+    rows, B, P, H, W, good = c.rows, c.B, c.P, c.H, c.W, FR.GOOD
+    bits_words, out_words = c.words, B * SLOT + 1
+    ioffs, ooffs = c.offsets, np.arange(B, dtype=np.int64) * SLOT
     for n, (img, bad) in enumerate(rows):
-        if bad is None:
-            m = CC.blob_plane(rs, *good[img], noise=0.04)
-            named[n] = (f"refusal{n}", m)
-            wds = XC.frame_words(m)
-            inbuf[PAD + ioffs[n]:PAD + ioffs[n] + len(wds)] = wds
-    inp = torch.as_tensor(inbuf.view(np.int32), device="cuda")
+        if bad == "output offset 6":
+            ooffs[n] += 6
+        elif bad == "output offset -4":
+            ooffs[n] = -4
+        elif bad == "output plane ends one word past out_words":
+            ooffs[n] = out_words - XC.plane_words(*good[img]) + 1
+            assert ooffs[n] % 4 == 0 and ooffs[n] >= 0
+    named = {n: (f"refusal{n}", CC.blob_plane(rs, *good[rows[n][0]], noise=0.04)) for n in c.good}
+    inbuf = FR.input_words(c, rs, lambda n, h, w: XC.frame_words(named[n][1]))   # garbage wherever no plane lies
+    d = FR.on_device(c, inbuf)
+    inp, table, ii = d.bits_all, d.table_all, d.image_index
     out = torch.full((PAD + out_words + PAD,), SENTINEL, dtype=torch.int32, device="cuda")
     stats = torch.full((B, 8), -7, dtype=torch.int32, device="cuda")
     tab = torch.full((B, ROWS, 5), -7, dtype=torch.int32, device="cuda")
-    ii = torch.as_tensor(np.array([img for img, _ in rows], np.int32), device="cuda")
     ioffs_d, ooffs_d = torch.as_tensor(ioffs, device="cuda"), torch.as_tensor(ooffs, device="cuda")
     frames = C.c_void_p(table.data_ptr() + 24)
     c_comp(ptr(inp, PAD), bits_words, ioffs_d, frames, P, H, W, ii, B, ptr(out, PAD), out_words, ooffs_d, stats, tab,
@@ -270,6 +253,7 @@ def test_refused_rows_write_nothing_and_say_so(la):
     assert not len(changed), (changed[:8] - PAD, [(n, bad) for n, (_, bad) in enumerate(rows) if bad])
     np.testing.assert_array_equal(u32(inp), inbuf)
     assert sum(bad is None for _, bad in rows) == 6 and all(want_stats[n][3] > 0 for n in named)
+    assert {bad for _, bad in rows} >= set(FR.INDEX_FAULTS + FR.OFFSET_FAULTS + [FR.END_FAULT] + [f for f, _ in FR.FRAME_FAULTS])
     # the statistics-only call makes the same decisions, but for the rows whose only fault lies in the output
     stats1 = torch.full((B, 8), -7, dtype=torch.int32, device="cuda")
     c_comp(ptr(inp, PAD), bits_words, ioffs_d, frames, P, H, W, ii, B, None, 0, None, stats1, None, conn=conn, min_area=min_area,

@@ -9,7 +9,9 @@ import pytest
 
 from oracle import la3d_oracle as O
 
+from . import frames_fault_rows as FR
 from . import instance_points_cases as IC
+from . import open_bits_frames_cases as FC
 from .test_gpu_parity import assert_records, np_
 from .test_hull_contract import hull_scene
 
@@ -403,6 +405,30 @@ def test_frames_form_refuses_broken_rows_on_the_device(la):
         np.testing.assert_array_equal(pts[off[b]:off[b + 1]], np_(good.points)[goff[b]:goff[b + 1]])
         np.testing.assert_array_equal(pix[off[b]:off[b + 1]], np_(good.pixels)[goff[b]:goff[b + 1]])
     assert (pts[off[-1]:] == SENT).all() and (pix[off[-1]:] == int(SENT)).all() and off[-1] < total
+    # the shared case table (tests/frames_fault_rows.py), one fault per row: the table, the planes and the depth have pad in front
+    # and behind, so a defect shows as a row too many or a wrong status, never as a fault.  (The entry takes no length of the planes.)
+    sizes = [h * FR.padded(w) for h, w in FR.GOOD]
+    fc = FR.case(end_check=False, depth_offsets=(0, sizes[0], sizes[0] + sizes[1]))
+    rs = np.random.RandomState(6)
+    ms = {n: rs.rand(*FR.GOOD[fc.rows[n][0]]) < 0.3 for n in fc.good}
+    d = FR.on_device(fc, FR.input_words(fc, rs, lambda n, h, w: FC.frame_words(ms[n])))
+    dbuf = torch.as_tensor(rs.uniform(0.5, 10.0, FR.PAD + sum(sizes) + FR.PAD).astype(np.float32), device="cuda")
+    fpf = la.PackedFrames(dbuf[FR.PAD:FR.PAD + sum(sizes)], d.table, fc.table[1:1 + fc.P], fc.H, fc.W, list(FR.GOOD) + [(8, 32)] * (fc.P - 3))
+    fK = np.stack([IC.cameras(1, h, w)[0] for h, w in fpf.sizes])
+    good = la.instance_points_frames(fpf, FR.frame_bits(la, fc, d, fc.good), fK, pixels=True)      # the call without the bad rows
+    goff = np_(good.offsets)
+    np.testing.assert_array_equal(np_(good.counts), [ms[n].sum() for n in fc.good])
+    total = int(goff[-1])
+    out = _sentinel_out(la, total + 16, fc.B)
+    ip = la.instance_points_frames(fpf, FR.frame_bits(la, fc, d), fK, pixels=True, capacity=total + 16, _out=out)
+    status, counts, off = np_(ip.status), np_(ip.counts), np_(ip.offsets)
+    for n, (img, fault) in enumerate(fc.rows):
+        assert (status[n], counts[n] == 0, off[n + 1] - off[n] == 0) == ((5, True, True) if fault else (0, False, False)), (n, fault)
+    pts, pix = np_(out[0]), np_(out[1])
+    for k, n in enumerate(fc.good):
+        np.testing.assert_array_equal(pts[off[n]:off[n + 1]], np_(good.points)[goff[k]:goff[k + 1]], err_msg=f"row {n}")
+        np.testing.assert_array_equal(pix[off[n]:off[n + 1]], np_(good.pixels)[goff[k]:goff[k + 1]], err_msg=f"row {n}")
+    assert off[-1] == total and (pts[total:] == SENT).all() and (pix[total:] == int(SENT)).all()
 
 
 # ------------------------------------------------------------------------------------------

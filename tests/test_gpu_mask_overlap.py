@@ -2,11 +2,14 @@
 the NumPy restatement of tests/mask_overlap_cases.py.  Everything is compared EXACTLY: inter and the areas as integers, the ratios
 bit for bit against NumPy's float64 division, keep as booleans."""
 import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
+from . import frames_fault_rows as FR
 from . import mask_overlap_cases as MC
+from . import open_bits_frames_cases as FC
 
 pytestmark = pytest.mark.gpu
 
@@ -244,6 +247,75 @@ def test_frames_form_equals_the_uniform_calls_and_refuses_bad_rows(la):
         m = np_(sgot.matrix(p))
         assert (keep[r0:r0 + F_A[p]] == MC.nms_ref(m, np_(sgot.area_a)[r0:r0 + F_A[p]], np.arange(29, 0, -1.0)[r0:r0 + F_A[p]], 0.0)).all()
     torch.cuda.synchronize()
+    frames_fault_rows(la)
+
+
+def frames_fault_rows(la):
+    """The shared case table (tests/frames_fault_rows.py), one fault per row, in the group-keyed form of this entry: group g is image g
+    of the table, so a frame row that breaks the contract refuses its whole group, and an image index that is not the group's (-1, P)
+    refuses its row.  The table and the planes have pad in front and behind: a defect shows as a count that is not -1, never as a
+    fault."""
+    import torch
+
+    good, P, SLOT, PAD = FR.GOOD, FR.P, FR.SLOT, FR.PAD
+    bad_groups = [(3 + j, name) for j, (name, _) in enumerate(FR.FRAME_FAULTS)]
+    #         image  what                                   (the rows of a group are contiguous; each good group begins and ends well)
+    rows_a = [(0, None), (-1, FR.INDEX_FAULTS[0]), (0, FR.END_FAULT), (0, None),
+              (1, None), (P, FR.INDEX_FAULTS[1]), (1, FR.OFFSET_FAULTS[1]), (1, None),
+              (2, None), (2, FR.OFFSET_FAULTS[0]), (2, None)] + bad_groups
+    rows_b = [(0, None), (0, None), (1, None), (1, None), (2, None), (2, None)] + bad_groups
+    ca, cb = [4, 4, 3] + [1] * len(bad_groups), [2, 2, 2] + [1] * len(bad_groups)
+    group_a = np.repeat(np.arange(P), ca)                                   # the group a row stands in, whatever its image index says
+    rs = np.random.RandomState(8)
+
+    def side(rows):
+        c = SimpleNamespace(rows=rows, B=len(rows), P=P, H=FR.H, W=FR.W, words=len(rows) * SLOT + 1, table=FR.frame_table(),
+                            offsets=np.arange(len(rows), dtype=np.int64) * SLOT, image_index=np.array([img for img, _ in rows], np.int32),
+                            good=[n for n, (img, bad) in enumerate(rows) if bad is None])
+        for n, (img, bad) in enumerate(rows):
+            if bad == FR.OFFSET_FAULTS[0]:
+                c.offsets[n] = -4
+            elif bad == FR.OFFSET_FAULTS[1]:
+                c.offsets[n] += 2
+            elif bad == FR.END_FAULT:
+                c.offsets[n] = c.words - FR.plane_words(*good[img]) + 1
+                assert c.offsets[n] % 4 == 0 and c.offsets[n] >= 0
+        masks = {n: MC.blobs(int(rs.randint(1 << 30)), 1, *good[rows[n][0]])[0] for n in c.good}
+        inbuf = FR.input_words(c, rs, lambda n, h, w: FC.frame_words(masks[n]))
+        return c, masks, inbuf, FR.on_device(c, inbuf)
+
+    (A, ma, buf_a, da), (B, mb, buf_b, db) = side(rows_a), side(rows_b)
+    grid = FR.frame_grid(la, A, da)
+    got = la.mask_overlap(FR.frame_bits(la, A, da), FR.frame_bits(la, B, db), counts_a=ca, counts_b=cb, frames=grid, iou="iou")
+    # the call without the bad rows: the good rows of the good groups only
+    ga = [[n for n in A.good if group_a[n] == g] for g in range(3)]
+    gb = [[n for n in B.good if rows_b[n][0] == g] for g in range(3)]
+    zeros = [0] * len(bad_groups)
+    ref = la.mask_overlap(FR.frame_bits(la, A, da, sum(ga, [])), FR.frame_bits(la, B, db, sum(gb, [])), counts_a=[len(x) for x in ga] + zeros,
+                          counts_b=[len(x) for x in gb] + zeros, frames=grid, iou="iou")
+    assert int(np_(ref.inter).sum()) > 0
+    area_a, area_b = np_(got.area_a), np_(got.area_b)
+    first_a = np.concatenate([[0], np.cumsum(ca)])
+    for g in range(P):
+        m, r = np_(got.matrix(g)), np_(got.matrix(g, "iou"))
+        if g >= 3:                                                            # a frame row that breaks the contract: the whole group
+            assert (m == -1).all() and np.isnan(r).all() and m.shape == (1, 1), (g, rows_a[first_a[g]][1])
+            assert area_a[first_a[g]] == -1 and area_b[6 + g - 3] == -1, g
+            continue
+        want, want_r = np_(ref.matrix(g)), np_(ref.matrix(g, "iou"))
+        k = 0
+        for i in range(ca[g]):
+            n = first_a[g] + i
+            if rows_a[n][1] is None:
+                assert (m[i] == want[k]).all() and area_a[n] == ma[n].sum(), (n, g)
+                same_bits(r[i], want_r[k])
+                k += 1
+            else:
+                assert (m[i] == -1).all() and np.isnan(r[i]).all() and area_a[n] == -1, (n, rows_a[n][1])
+        assert k == len(ga[g]) and (area_b[2 * g:2 * g + 2] == [mb[n].sum() for n in gb[g]]).all()
+    assert {bad for _, bad in rows_a} >= set(FR.INDEX_FAULTS + FR.OFFSET_FAULTS + [FR.END_FAULT] + [f for f, _ in FR.FRAME_FAULTS])
+    np.testing.assert_array_equal(np_(da.bits_all).view(np.uint32), buf_a)
+    np.testing.assert_array_equal(np_(db.bits_all).view(np.uint32), buf_b)
 
 
 def test_the_source_of_the_planes_does_not_matter(la):

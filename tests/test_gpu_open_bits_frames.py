@@ -11,6 +11,7 @@ import pytest
 
 from . import instance_points_cases as IC
 from . import open_bits_cases as OC
+from . import frames_fault_rows as FR
 from . import open_bits_frames_cases as FC
 
 pytestmark = pytest.mark.gpu
@@ -182,47 +183,32 @@ def test_exactly_the_words_of_each_plane_are_written(la, k, s):
 # 4. refused rows
 # ------------------------------------------------------------------------------------------
 def test_refused_rows_write_nothing_and_say_so(la):
-    """One bad value per refused row; every address a defect would form from it lies inside this test's own allocations (the table,
-    the input and the output have pad in front and behind), so a defect shows as a changed word, never as a fault."""
+    """One bad value per refused row - the shared case table (tests/frames_fault_rows.py) and the faults of the output, which are this
+    entry's own; every address a defect would form from it lies inside this test's own allocations (the table, the input and the
+    output have pad in front and behind), so a defect shows as a changed word, never as a fault."""
     import torch
 
-    from labelany3d_amd.frames import FRAME_DTYPE, table_words
-
     k, s = 3, 2
-    good = [(33, 47), (40, 32), (8, 33)]
     rs = np.random.RandomState(4)
-    H, W = 40, 64                                                                # the bounds of the good rows
-    t = np.zeros(8, FRAME_DTYPE)                                                 # rows -1 and P are pad: a valid frame, which nothing may use
-    t[0] = t[7] = (0, 8, 32, 32, 0)
-    for p, (h, w) in enumerate(good):
-        t[1 + p] = (0, h, OC.padded(w), w, 0)
-    t[4] = (0, 8, 48, 40, 0)                                                     # pitch 48: no multiple of 32
-    t[5] = (0, 41, 64, 40, 0)                                                    # H above the bound
-    t[6] = (0, 8, 32, 0, 0)                                                      # frame_width 0
-    table = torch.as_tensor(table_words(t), device="cuda")
-    P, IN, OUT, PAD = 6, 128, 512, 64                                            # slots of 128 / 512 words hold every plane, bad rows included
-    #        image  what
-    rows = [(0, None), (-1, "image index -1"), (1, None), (P, "image index P"), (3, "pitch 48"), (2, None), (4, "H above the bound"),
-            (5, "frame_width 0"), (0, None), (1, "input offset -4"), (2, "input offset 2"), (1, None), (1, "output offset 6"),
-            (0, "input plane ends one word past bits_words"), (0, "output plane ends one word past out_words"), (2, None)]
-    B = len(rows)
-    bits_words, out_words = B * IN + 1, B * OUT + 1
-    ioffs, ooffs = np.arange(B, dtype=np.int64) * IN, np.arange(B, dtype=np.int64) * OUT
-    ioffs[9], ioffs[10], ooffs[12] = -4, ioffs[10] + 2, ooffs[12] + 6
-    ioffs[13] = bits_words - FC.plane_words(33, 47) + 1
-    ooffs[14] = out_words - FC.plane_words(66, 94) + 1
-    assert ioffs[13] % 4 == 0 and ooffs[14] % 4 == 0 and ioffs[13] >= 0 and ooffs[14] >= 0
-    inbuf = rs.randint(0, 2 ** 32, PAD + bits_words + PAD, dtype=np.uint64).astype(np.uint32)     # garbage wherever no plane lies
-    masks = {}
+    OUT, PAD = 512, FR.PAD                                                       # output slots of 512 words hold every scaled plane
+    c = FR.case(end_check=True, extra=[(1, "output offset 6"), (2, "output offset -4"), (0, "output plane ends one word past out_words")])
+    rows, B, P, H, W, good = c.rows, c.B, c.P, c.H, c.W, FR.GOOD
+    bits_words, out_words = c.words, B * OUT + 1
+    ioffs, ooffs = c.offsets, np.arange(B, dtype=np.int64) * OUT
     for n, (img, bad) in enumerate(rows):
-        if bad is None:
-            masks[n] = OC.blob_plane(rs, *good[img])
-            wds = FC.frame_words(masks[n])
-            inbuf[PAD + ioffs[n]:PAD + ioffs[n] + len(wds)] = wds
-    inp = torch.as_tensor(inbuf.view(np.int32), device="cuda")
+        if bad == "output offset 6":
+            ooffs[n] += 6
+        elif bad == "output offset -4":
+            ooffs[n] = -4
+        elif bad == "output plane ends one word past out_words":
+            ooffs[n] = out_words - FC.plane_words(s * good[img][0], s * good[img][1]) + 1
+            assert ooffs[n] % 4 == 0 and ooffs[n] >= 0
+    masks = {n: OC.blob_plane(rs, *good[rows[n][0]]) for n in c.good}
+    inbuf = FR.input_words(c, rs, lambda n, h, w: FC.frame_words(masks[n]))      # garbage wherever no plane lies
+    d = FR.on_device(c, inbuf)
+    inp, table, ii = d.bits_all, d.table_all, d.image_index
     out = torch.full((PAD + out_words + PAD,), SENTINEL, dtype=torch.int32, device="cuda")
     stats = torch.full((B, 5), -7, dtype=torch.int32, device="cuda")
-    ii = torch.as_tensor(np.array([img for img, _ in rows], np.int32), device="cuda")
     c_open(la, ptr(inp, PAD), bits_words, torch.as_tensor(ioffs, device="cuda"), C.c_void_p(table.data_ptr() + 24), P, H, W, ii, B, k, s,
            ptr(out, PAD), out_words, torch.as_tensor(ooffs, device="cuda"), stats, workspace(la, B, H, s))
     expect = np.full(PAD + out_words + PAD, SENTINEL, np.uint32)
@@ -242,6 +228,7 @@ def test_refused_rows_write_nothing_and_say_so(la):
     assert not len(changed), (changed[:8] - PAD, [(n, bad) for n, (_, bad) in enumerate(rows) if bad])
     np.testing.assert_array_equal(u32(inp), inbuf)
     assert sum(bad is None for _, bad in rows) == 6 and any(r[0] > 0 for r in want_stats)
+    assert {bad for _, bad in rows} >= set(FR.INDEX_FAULTS + FR.OFFSET_FAULTS + [FR.END_FAULT] + [f for f, _ in FR.FRAME_FAULTS])
     # the statistics-only call makes the same decisions, but for the rows whose only fault lies in the output
     stats1 = torch.full((B, 5), -7, dtype=torch.int32, device="cuda")
     c_open(la, ptr(inp, PAD), bits_words, torch.as_tensor(ioffs, device="cuda"), C.c_void_p(table.data_ptr() + 24), P, H, W, ii, B, 1, 1,

@@ -9,6 +9,8 @@ import pytest
 
 from oracle import la3d_oracle as O
 
+from . import frames_fault_rows as FR
+
 pytestmark = pytest.mark.gpu
 
 SENTINEL = 0x5A5A5A5A
@@ -436,3 +438,31 @@ def test_frames_form_refuses_rows_on_the_device(la):
     assert np_(t["status"]).tolist() == [5 if n in (2, 5) else 0 for n in range(7)]
     got = np_(t["counts"])
     assert (got[total:] == SENTINEL).all() and got[:total].tolist() == [c for n in keep for c in want[n]]
+    # the shared case table (tests/frames_fault_rows.py), one fault per row, through the C entries: the table and the planes have pad
+    # in front and behind, so a defect shows as a run too many or a wrong status, never as a fault.  (The entry takes no length.)
+    fc = FR.case(end_check=False)
+    rs = np.random.RandomState(5)
+    ms = {n: rs.rand(*FR.GOOD[fc.rows[n][0]]) < 0.3 for n in fc.good}
+    inbuf = FR.input_words(fc, rs, lambda n, h, w: plane_words(ms[n], FR.padded(w), garbage=True))
+    d = FR.on_device(fc, inbuf)
+    want = {n: O.rle_encode(ms[n])["counts"] for n in fc.good}
+    B, total = fc.B, sum(len(w) for w in want.values())
+    t = dict(runs=torch.full((B,), -7, dtype=torch.int32, device="cuda"), offsets=torch.full((B + 1,), -7, dtype=torch.int64, device="cuda"),
+             status=torch.full((B,), -7, dtype=torch.int32, device="cuda"), counts=torch.full((total + 16,), SENTINEL, dtype=torch.int32, device="cuda"),
+             ws=torch.zeros(int(_lib.lib.la3d_rle_encode_workspace_bytes(B, fc.H, fc.W)) // 8, dtype=torch.int64, device="cuda"))
+    a = _lib.RleEncodeArgs(struct_size=C.sizeof(_lib.RleEncodeArgs), B=B, H=fc.H, W=fc.W, P=fc.P, mask_bits=d.bits.data_ptr(),
+                           frames=d.table.data_ptr(), image_index=d.image_index.data_ptr(), bits_offsets=d.offsets.data_ptr(),
+                           runs=t["runs"].data_ptr(), offsets=t["offsets"].data_ptr(), counts=t["counts"].data_ptr(), status=t["status"].data_ptr(),
+                           capacity=total + 16, workspace=t["ws"].data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    c_stage("la3d_rle_encode_offsets", a)
+    c_stage("la3d_rle_encode", a)
+    torch.cuda.synchronize()
+    for n, (img, fault) in enumerate(fc.rows):
+        assert (int(t["runs"][n]), int(t["status"][n])) == ((len(want[n]), 0) if fault is None else (0, 5)), (n, fault)
+    got = np_(t["counts"])
+    assert (got[total:] == SENTINEL).all() and got[:total].tolist() == [x for n in fc.good for x in want[n]]
+    np.testing.assert_array_equal(np_(d.bits_all).view(np.uint32), inbuf)
+    # every good row equals the call without the bad rows
+    (counts, offsets), sizes, status = la.rle_encode_bits_frames(FR.frame_grid(la, fc, d), FR.frame_bits(la, fc, d, fc.good), return_status=True)
+    assert np_(status).tolist() == [0] * len(fc.good) and split(counts, offsets) == [want[n] for n in fc.good]
+    assert np_(sizes).tolist() == [list(ms[n].shape) for n in fc.good]
