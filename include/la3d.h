@@ -912,6 +912,60 @@ typedef struct la3d_components_frames_args {
 } la3d_components_frames_args;
 int la3d_components_bits_frames(const la3d_components_frames_args* args);
 
+/* ---- depth gate on bit planes ------------------------------------------------------------------------------------------
+ * What the depth says about a mask: the depth + mask fit takes every set pixel and its extents are plain minima and maxima, so one
+ * wrong depth under a mask sets the size of the box - a fill value of the depth stage (the reference's align_depth writes 10000.0
+ * where it cannot predict), or the few background pixels of a mask that bleeds over an occlusion edge.  la3d_open_bits removes by
+ * shape, la3d_components_bits by component; this entry removes by DEPTH, for a batch of planes in one launch.
+ * RULE, per instance, with d the float32 depth plane of its image and m its plane (image columns < frame_width only) - NumPy:
+ *     valid = m & isfinite(d) & (d >= float32(near)) & (d <= float32(far))
+ *     v     = d[valid]                                        float32
+ *     med   = np.median(v)                                    float32; an even count averages the two middle values in float32
+ *     mad   = np.median(np.abs(v - med))                      float32, same rule
+ *     thr   = np.maximum(float32(k) * mad, float32(min_band)) one float32 product
+ *     keep  = valid & (np.abs(d - med) <= thr)                one float32 subtraction per pixel
+ *   k (finite, >= 0; 4.5 is about three sigma of a Gaussian, and a surface whose depths are spread uniformly over their range keeps
+ *   every pixel) scales the band; min_band (finite, >= 0) is a floor for the band in depth units - needed where quantised depth
+ *   gives mad == 0, which with min_band = 0 keeps only the pixels AT the median; near / far (-inf / +inf: none; NaN refused) bound
+ *   the depths that count at all - far = 9999 handles the reference's fill by itself.  No valid pixel: the output plane is empty and
+ *   med, mad, thr are NaN.  Magnitudes whose float32 sum or difference overflows, and subnormal depths, are outside the contract.
+ * INPUT.  B planes of "masks as bit planes" (H rows, pitch W, frame_width image columns), bits_plane_stride words apart; depth:
+ *   float32 planes of pitch W (as wide as the planes are STORED), depth_plane_stride elements apart - 0: one plane shared by every
+ *   instance -; instance b reads plane image_index[b], or plane b when image_index is NULL.  The index is not range-checked.
+ * OUTPUT.  out_bits (NULL: statistics only, no plane is written): the plane of keep in the input's geometry, out_plane_stride words
+ *   apart - all la3d_mask_bits_words(H, W) words of it are written; every bit of a column >= frame_width, and beyond H * W in the
+ *   last word, is written as zero whatever the input held there.  counts[b] (i32 [3]) = area_in (the set bits of the image columns),
+ *   n_valid, area_out.  levels[b] (f32 [3]) = med, mad, thr.  Planes and counts equal the rule exactly, levels value for value (the
+ *   sign of a zero aside).
+ * IN PLACE.  out_bits may be EXACTLY the input (out_bits == mask_bits with equal strides): a workgroup holds its plane in LDS before
+ *   it stores a word.  Word ranges [mask_bits, mask_bits + B * bits_plane_stride) and [out_bits, out_bits + B * out_plane_stride)
+ *   that overlap in any other way are refused.
+ * One kernel, one 512-thread workgroup per instance: the plane is copied into LDS once, both medians are exact selections on
+ *   order-preserving keys (the second over |d - med| re-derived from memory), the last pass writes the words.  Integer LDS atomics
+ *   only, no workspace, no allocation, no host synchronisation: the call can be captured into a HIP graph, and a plane's result
+ *   depends neither on the rest of the batch nor on the run.
+ * Refused before any launch, in this order - LA3D_ERR_ARG: a NULL block or a bad struct_size; B < 0, H, W <= 0; frame_width outside
+ *   [0, W]; k or min_band negative or not finite; near or far NaN; nonzero reserved; a stride that is negative or - unless 0 - shorter
+ *   than a plane (0: depth - one shared plane; bits, out - the words of a plane).  LA3D_ERR_UNSUPPORTED: a frame whose bit image,
+ *   chunk list and selection buffers exceed one CU's 160 KiB of LDS - every H * W up to 857728 stored pixels fits (640 x 1280 =
+ *   819200 does).  B == 0 then returns 0 with no launch.  With B > 0, LA3D_ERR_ARG: out_bits, counts and levels all NULL; depth or
+ *   mask_bits NULL; a pointer that is not 4-byte aligned; planes that overlap without being the same planes. */
+typedef struct la3d_depth_gate_args {                    /* 120 bytes */
+  int32_t struct_size;                                   /* sizeof(la3d_depth_gate_args) of the caller */
+  int32_t B, H, W;                                       /* W: the pitch of the planes as stored, bits and depth alike */
+  int32_t frame_width;                                   /* 0 = W */
+  float k, min_band, near, far;
+  int32_t reserved;                                      /* 0 */
+  const float* depth; int64_t depth_plane_stride;        /* dev f32, pitch W; elements between planes, 0 = one shared plane */
+  const int32_t* image_index;                            /* dev [B] or NULL */
+  const uint32_t* mask_bits; int64_t bits_plane_stride;  /* bit planes; words between planes, 0 = the words of a plane */
+  uint32_t* out_bits; int64_t out_plane_stride;          /* NULL: statistics only; words between planes, 0 = the words of a plane */
+  int32_t* counts;                                       /* dev [B][3] or NULL */
+  float* levels;                                         /* dev [B][3] or NULL */
+  void* stream;
+} la3d_depth_gate_args;
+int la3d_depth_gate_bits(const la3d_depth_gate_args* args);
+
 /* ---- mask overlap on bit planes ----------------------------------------------------------------------------------------
  * What relates two planes of one image: for every GROUP g (an image) and every pair of a row i of A_g and a row j of B_g
  *     inter[offsets[g] + i * nb_g + j] = popcount(A_i & B_j)   over the words [0, nwords) of the planes,

@@ -158,6 +158,17 @@ class IouGroupsArgs(C.Structure):
                 ("offsets", C.c_void_p), ("npairs", C.c_int64), ("out", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class DepthGateArgs(C.Structure):
+    """``la3d_depth_gate_args`` of include/la3d.h (argument block of la3d_depth_gate_bits, 120 bytes); field order is the header's."""
+    _fields_ = [("struct_size", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("frame_width", C.c_int32),
+                ("k", C.c_float), ("min_band", C.c_float), ("near", C.c_float), ("far", C.c_float), ("reserved", C.c_int32),
+                ("depth", C.c_void_p), ("depth_plane_stride", C.c_int64), ("image_index", C.c_void_p),
+                ("mask_bits", C.c_void_p), ("bits_plane_stride", C.c_int64), ("out_bits", C.c_void_p), ("out_plane_stride", C.c_int64),
+                ("counts", C.c_void_p), ("levels", C.c_void_p), ("stream", C.c_void_p)]
+
+
+DEPTH_GATE_MAX_PIXELS = 857728                                         # la3d_depth_gate_bits: the stored pixels of a frame its LDS layout holds
+
 ASSIGN_F64, ASSIGN_I32 = 0, 1                                          # la3d_assign_args.cost_dtype
 ASSIGN_MAX_N, ASSIGN_STAGE_MAX = 256, 2048                             # rows / columns of a group; elements staged in LDS
 ASSIGN_OK, ASSIGN_INVALID, ASSIGN_INFEASIBLE, ASSIGN_TOO_LARGE, ASSIGN_BROKEN = 0, 1, 2, 3, 4   # status of a group
@@ -166,6 +177,7 @@ OVERLAP_MIRROR, OVERLAP_AREA_A, OVERLAP_AREA_B = 1, 2, 4              # la3d_ove
 OVERLAP_TILE, OVERLAP_STEP = 8, 1024                                   # planes per side of a tile; words a chunk is a multiple of
 
 _SIGS = {
+    "la3d_depth_gate_bits": (C.c_int, [C.POINTER(DepthGateArgs)]),
     "la3d_mask_overlap_plan": (C.c_int64, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "la3d_mask_overlap_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "la3d_mask_overlap": (C.c_int, [C.POINTER(MaskOverlapArgs)]),

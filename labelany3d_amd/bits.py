@@ -1,9 +1,10 @@
 """Masks as bit planes of ONE frame size per call (include/la3d.h "masks as bit planes" and what followed it): ``MaskBits``, the packers
-(u8 masks, logits, run lengths, polygons), the restore of crop-space masks, the unpacker and the plane statistics, and the fit that takes
-the planes (``fit_instances_bits``).  ``labels`` builds on this module; mixed-size packers: ``frames``; plane operations: ``morph``, ``rle_encode``."""
+(u8 masks, logits, run lengths, polygons), the restore of crop-space masks, the unpacker and the plane statistics, the depth gate
+(``gate_depth_bits``) and the fit that takes the planes (``fit_instances_bits``).  ``labels`` builds on this module; mixed-size packers: ``frames``; plane operations: ``morph``, ``rle_encode``."""
 from __future__ import annotations
 
 import contextlib
+import ctypes as C
 from typing import NamedTuple
 
 import numpy as np
@@ -300,6 +301,114 @@ def mask_stats_bits(bits, boundary_threshold: int = 10, stream=None) -> torch.Te
                                        int(boundary_threshold), _ptr(out), _stream(stream)), "la3d_mask_stats_bits")
     _record(stream, mb.bits, out)
     return out
+
+
+# ---- the depth gate (include/la3d.h "depth gate on bit planes") -----------------------------------------------------------------------
+class DepthGateStats(NamedTuple):
+    """What ``gate_depth_bits`` / ``depth_gate_stats`` say about every plane, on the GPU: ``counts`` int32 (B, 3) = ``area_in`` (set
+    pixels of the image columns), ``n_valid`` (of them, those whose depth is finite and inside ``[near, far]``), ``area_out`` (kept);
+    ``levels`` float32 (B, 3) = ``med, mad, thr`` (NaN where no pixel is valid)."""
+    counts: torch.Tensor
+    levels: torch.Tensor
+
+
+def _gate_level(who: str, name: str, v, default: float) -> float:
+    """``near`` / ``far``: None (no bound) or a real number that is not NaN -> the float the block takes."""
+    if v is None:
+        return default
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or v != v:
+        raise ValueError(f"{who}: {name} must be None or a number that is not NaN, not {v!r}")
+    return float(v)
+
+
+def _gate_band(who: str, name: str, v) -> float:
+    """``k`` / ``min_band``: a real number that is finite and >= 0 as a float32."""
+    ok = not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))
+    with np.errstate(over="ignore"):
+        ok = ok and bool(np.isfinite(np.float32(v))) and v >= 0
+    if not ok:
+        raise ValueError(f"{who}: {name} must be a finite number >= 0, not {v!r}")
+    return float(v)
+
+
+def _gate_run(who: str, depth, bits, k, min_band, near, far, image_index, stream, out, want_plane: bool, want_stats: bool):
+    """The checks of ``gate_depth_bits`` / ``depth_gate_stats`` and one ``la3d_depth_gate_bits`` call -> (MaskBits or None, stats or None)."""
+    if not isinstance(bits, MaskBits):
+        raise ValueError(f"{who}: bits must be a MaskBits (pack_mask_bits, pack_rle_bits, pack_poly_bits, pack_crop_bits, ...)")
+    k, min_band = _gate_band(who, "k", k), _gate_band(who, "min_band", min_band)
+    near, far = _gate_level(who, "near", near, float("-inf")), _gate_level(who, "far", far, float("inf"))
+    if isinstance(depth, Depth16):
+        raise ValueError(f"{who}: depth must be float32 planes, not a Depth16 (unpack_depth16 gives them)")
+    dtype = depth.dtype if isinstance(depth, torch.Tensor) else np.asarray(depth).dtype
+    if dtype not in (torch.float32, np.dtype(np.float32)):
+        raise ValueError(f"{who}: depth must be float32, not {dtype}")
+    mb = _mask_bits(bits)
+    B, H, W, fw, dev = int(mb.bits.shape[0]), mb.H, mb.W, mb.frame_width, mb.bits.device
+    if H <= 0 or W <= 0:
+        raise ValueError(f"{who}: the planes state an empty frame {(H, W)}")
+    if H * W > _lib.DEPTH_GATE_MAX_PIXELS:
+        raise ValueError(f"{who}: a frame of {(H, W)} has more than {_lib.DEPTH_GATE_MAX_PIXELS} stored pixels")
+    for name, t in (("depth", depth), ("image_index", image_index), ("out", out)):
+        if isinstance(t, torch.Tensor) and t.is_cuda and t.device != dev:
+            raise ValueError(f"{who}: {name} lives on another device than the bit planes")
+    shape = tuple(depth.shape)
+    if len(shape) not in (2, 3) or shape[-2] != H:
+        raise ValueError(f"{who}: depth {shape} must be (H, W), (P, H, W) or (B, H, W) planes of {H} rows")
+    P = 1 if len(shape) == 2 else int(shape[0])
+    if image_index is None:
+        if P not in (1, B):
+            raise ValueError(f"{who}: {P} depth planes for {B} instances need an image_index")
+    elif tuple(image_index.shape) != (B,):
+        raise ValueError(f"{who}: image_index must be (B,)")
+    elif not (isinstance(image_index, torch.Tensor) and image_index.is_cuda) and B:   # (a device index is not read back)
+        host = np.asarray(image_index)
+        if host.min() < 0 or host.max() >= P:
+            raise ValueError(f"{who}: image_index must lie in [0, {P})")
+    o = _bits_out(out, B, H, W, dev) if want_plane else None
+    with torch.cuda.device(dev):
+        d, _ = depth_rows_for_bits(depth, W, fw, dev)
+        d = _as_dev(d, torch.float32, dev)
+        ii = None if image_index is None else _as_dev(image_index, torch.int32, dev)
+        counts = torch.empty((B, 3), dtype=torch.int32, device=dev) if want_stats else None
+        levels = torch.empty((B, 3), dtype=torch.float32, device=dev) if want_stats else None
+        if B:   # (an empty batch has no planes to point at)
+            a = _lib.DepthGateArgs(struct_size=C.sizeof(_lib.DepthGateArgs), B=B, H=H, W=W, frame_width=0 if fw == W else fw,
+                                   k=k, min_band=min_band, near=near, far=far, depth=d.data_ptr(), depth_plane_stride=0 if P == 1 else H * W,
+                                   image_index=None if ii is None else ii.data_ptr(),
+                                   mask_bits=mb.bits.data_ptr(), bits_plane_stride=_bits_stride(mb.bits, B, H, W),
+                                   out_bits=None if o is None else o.data_ptr(), out_plane_stride=0 if o is None else _bits_stride(o, B, H, W),
+                                   counts=None if counts is None else counts.data_ptr(), levels=None if levels is None else levels.data_ptr(),
+                                   stream=_stream(stream))
+            check(lib.la3d_depth_gate_bits(C.byref(a)), "la3d_depth_gate_bits")
+    _record(stream, d, ii, mb.bits, o, counts, levels)
+    return (None if o is None else MaskBits(o, H, W, fw)), (DepthGateStats(counts, levels) if want_stats else None)
+
+
+def gate_depth_bits(depth, bits: MaskBits, k: float = 4.5, min_band: float = 0.0, near=None, far=None, image_index=None, stream=None,
+                    out=None, return_stats: bool = False):
+    """Drop every mask's depth outliers before ``fit_instances_bits`` takes every set pixel (C-ABI ``la3d_depth_gate_bits``): the
+    fit's extents are plain minima and maxima, so one fill value of the depth stage (the reference's ``align_depth`` writes 10000.0)
+    or a few background pixels behind an occlusion edge set the size of the box.  Per plane, with ``d`` its depth plane:
+    ``valid = m & isfinite(d) & (d >= near) & (d <= far)``, ``med = np.median(d[valid])``, ``mad = np.median(|d[valid] - med|)``,
+    ``thr = max(k * mad, min_band)``, ``keep = valid & (|d - med| <= thr)`` - all in float32, the medians exact (an even count
+    averages the two middle values).  ``k``: the band in MADs (4.5 is about three sigma of a Gaussian; a surface whose depths are
+    spread uniformly over their range keeps every pixel); ``min_band``: a floor for the band in depth units - needed where quantised
+    depth gives ``mad == 0``, which otherwise keeps only the pixels exactly at the median; ``near`` / ``far``: None, or the depths
+    that count at all (``far=9999`` handles the reference's fill by itself).  A plane without a valid pixel comes back empty, with NaN
+    levels.  ``depth``: float32 - (H, W) shared by every plane, (P, H, W) with ``image_index`` (B,), or (B, H, W) -, as wide as the
+    planes are stored (``bits.W``) or ``bits.frame_width`` wide - then the rows are padded here, as ``fit_instances_bits`` does; a
+    ``Depth16`` or another dtype is refused.  ``out``: None (a fresh tensor), an int32 (B, >= words) device tensor to fill, or
+    ``bits.bits`` itself (in place); any other overlap with the input is refused.  Returns the ``MaskBits`` of the kept pixels in the
+    input's geometry (pad columns and tail bits zero whatever the input held there) - or ``(MaskBits, DepthGateStats)`` with
+    ``return_stats``.  One kernel, no host synchronisation; capturable."""
+    res, stats = _gate_run("gate_depth_bits", depth, bits, k, min_band, near, far, image_index, stream, out, True, bool(return_stats))
+    return (res, stats) if return_stats else res
+
+
+def depth_gate_stats(depth, bits: MaskBits, k: float = 4.5, min_band: float = 0.0, near=None, far=None, image_index=None,
+                     stream=None) -> DepthGateStats:
+    """The ``DepthGateStats`` of ``gate_depth_bits`` without its planes (``out_bits = NULL``: no plane is written)."""
+    return _gate_run("depth_gate_stats", depth, bits, k, min_band, near, far, image_index, stream, None, False, True)[1]
 
 
 def fit_instances_bits(depth, bits, K, ground=None, sample_idx=None, image_index=None, stream=None, device=None, filter=None,

@@ -36,7 +36,7 @@ from ._device import _as_dev, _dev, _plane_source, _ptr, _record, _stream, _uplo
 from ._lib import AUX, BOX_FILTERED, REC, check, lib
 from .batched import Depth16, InstanceFitter, _bits_stride, _depth16_block, _depth16_check, _fit_args, height_rule_code, pad_depth_rows, padded_width, refuse_depth16  # noqa: F401
 from .bits import (_LOGIT_DTYPES, MaskBits, _annotation_bits_plan, _bits_out, _crop_place, _crop_source, _crop_threshold, _mask_bits, _pack_annotation_bits,  # noqa: F401
-                   _PackedBits, crop_placement, fit_instances_bits, mask_stats_bits, pack_crop_bits, pack_logits_bits, pack_mask_bits, pack_poly_bits, pack_rle_bits, unpack_mask_bits)
+                   _PackedBits, DepthGateStats, crop_placement, depth_gate_stats, fit_instances_bits, gate_depth_bits, mask_stats_bits, pack_crop_bits, pack_logits_bits, pack_mask_bits, pack_poly_bits, pack_rle_bits, unpack_mask_bits)
 from .depth16 import _D16_DTYPES, pack_depth16, unpack_depth16  # noqa: F401
 from .depth_align import masked_ratio_median  # noqa: F401
 from .fitcall import depth_rows, depth_rows_for_bits, fit_call, mask_source  # noqa: F401
