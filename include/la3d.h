@@ -966,6 +966,62 @@ typedef struct la3d_depth_gate_args {                    /* 120 bytes */
 } la3d_depth_gate_args;
 int la3d_depth_gate_bits(const la3d_depth_gate_args* args);
 
+/* la3d_depth_gate_bits_frames: the gate for the planes of images of DIFFERENT sizes, over depth as it is stored - float32, float16 or
+ * uint16 -, in one call ("images of different sizes in one call": the la3d_frame table, P rows, and its bounds H, W - the largest rows
+ * and the largest pitch).  One k, min_band, near and far per call.
+ * INPUT.  Row n belongs to image image_index[n]; its plane lies at bits + bits_offsets[n] and holds the H_f * W_f / 32 words of that
+ *   image's frame row (H_f rows, pitch W_f - a multiple of 32 -, frame_width fw_f image columns).  Columns at and beyond fw_f count as
+ *   zero whatever the plane holds.  bits_words: the words of the buffer at bits.  The depth plane of the image lies depth_offset
+ *   elements into the depth buffer, pitch W_f, H_f rows: exactly one of `depth` (float32, 16-byte aligned) and `depth16` is given.
+ *   With depth16 the rules of la3d_fit_instances_frames_depth16 apply: plane_stride 0, an 8-byte aligned base, depth_offset counted
+ *   in 16-bit ELEMENTS; the float32 value of a stored word is the one of "16-bit depth planes" - F16 exact, U16 ONE rounded
+ *   float32(x) * scale that is never contracted into the subtraction of the median, a stored 0 a NaN (hence not valid) with
+ *   LA3D_DEPTH_ZERO_IS_HOLE - and from that value on the RULE above applies unchanged: a 16-bit call gives, word for word, what the
+ *   float32 call gives on the up-converted planes.  depth_elems: the elements of the depth buffer.
+ * OUTPUT.  out_bits (NULL: statistics only): the plane of row n at out_bits + out_offsets[n], in the input's geometry.  A conforming
+ *   row writes exactly the H_f * W_f / 32 words of its plane - the bits of the padding columns zero - and nothing else; out_words: the
+ *   words of the buffer at out_bits.  counts[n] (i32 [3]) and levels[n] (f32 [3]) as in la3d_depth_gate_bits.
+ * CONFORMING ROWS get what la3d_depth_gate_bits gives for the same plane with H = H_f, W = W_f, frame_width = fw_f over the same depth.
+ * IN PLACE.  The output may be EXACTLY the input - out_bits == bits, out_words == bits_words and out_offsets the very pointer given
+ *   as bits_offsets: a workgroup holds its plane in LDS before it stores a word.  Word ranges [bits, bits + bits_words) and [out_bits,
+ *   out_bits + out_words) that overlap in any other way are refused.  The planes of different rows must not overlap each other: the
+ *   caller's contract, as for la3d_components_bits_frames.
+ * CHECKED ON THE DEVICE, per row, every value wave-uniform and before an address is formed from it, in this order: image_index[n]
+ *   inside [0, P); the frame row against the la3d_frame contract and the bounds (the check of the fit); bits_offsets[n] >= 0 and a
+ *   multiple of 4; bits_offsets[n] + words <= bits_words; with out_bits, out_offsets[n] by the same two rules against out_words; then
+ *   depth_offset + H_f * W_f <= depth_elems.  A refused row reads no plane word and no depth, writes no plane word and gets counts
+ *   -2, 0, 0 and levels NaN, NaN, NaN (both addressed by n alone): -2 is the marker of la3d_open_bits_frames and
+ *   la3d_components_bits_frames; an empty plane has 0, 0, 0.  The other rows of the call are not affected.
+ * One kernel - la3d_depth_gate_bits' own, per row geometry -, one 512-thread workgroup per row; its dynamic LDS is sized by the
+ *   BOUNDS (bit image, chunk list and selection buffers of H * roundup32(W) stored pixels: 94 KB at 640 x 640, one workgroup per CU
+ *   from 80 KB on).  Integer LDS atomics only, no workspace, no allocation, no host synchronisation: the call can be captured into a
+ *   HIP graph.
+ * Refused before any launch, for B == 0 too, in this order - LA3D_ERR_ARG: a NULL block or a bad struct_size; B, P < 0, bounds H, W
+ *   <= 0; k or min_band negative or not finite; near or far NaN; nonzero reserved; both or neither of depth and depth16; a bad
+ *   la3d_depth16 block (struct_size, dtype, scale, flags, nonzero plane_stride, NULL planes); depth_elems < 0, bits_words < 0, out_words < 0
+ *   with out_bits; bits or out_bits not 16-byte aligned; float32 depth not 16-byte, 16-bit planes not 8-byte aligned; bits_offsets,
+ *   out_offsets or frames not 8-byte aligned; image_index, counts or levels not 4-byte aligned; out_bits, counts and levels all NULL;
+ *   buffers that overlap without being the same planes; and with B > 0: bits, bits_offsets, image_index or - with P > 0 - frames
+ *   NULL, out_offsets NULL with out_bits.  LA3D_ERR_UNSUPPORTED: bounds with H * roundup32(W) > 857728 stored pixels (the LDS of
+ *   la3d_depth_gate_bits).  B == 0 then returns 0 with nothing launched.  P == 0 with B > 0: every row is refused on the device. */
+typedef struct la3d_depth_gate_frames_args {             /* 152 bytes */
+  int32_t struct_size;                                   /* sizeof(la3d_depth_gate_frames_args) of the caller */
+  int32_t B, P;
+  int32_t H, W;                                          /* bounds of the table */
+  float k, min_band, near, far;                          /* as in la3d_depth_gate_args */
+  int32_t reserved;                                      /* 0 */
+  const float* depth;                                    /* dev f32 buffer, 16-byte aligned, or NULL */
+  const la3d_depth16* depth16;                           /* 16-bit buffer (plane_stride 0, 8-byte aligned), or NULL: exactly one of the two */
+  int64_t depth_elems;                                   /* elements of the depth buffer */
+  const la3d_frame* frames; const int32_t* image_index;                        /* dev [P], dev [B] */
+  const uint32_t* bits; int64_t bits_words; const int64_t* bits_offsets;      /* the buffer, its words, dev [B] */
+  uint32_t* out_bits; int64_t out_words; const int64_t* out_offsets;          /* NULL: statistics only; dev [B] */
+  int32_t* counts;                                       /* dev [B][3] or NULL */
+  float* levels;                                         /* dev [B][3] or NULL */
+  void* stream;
+} la3d_depth_gate_frames_args;
+int la3d_depth_gate_bits_frames(const la3d_depth_gate_frames_args* args);
+
 /* ---- mask overlap on bit planes ----------------------------------------------------------------------------------------
  * What relates two planes of one image: for every GROUP g (an image) and every pair of a row i of A_g and a row j of B_g
  *     inter[offsets[g] + i * nb_g + j] = popcount(A_i & B_j)   over the words [0, nwords) of the planes,

@@ -167,7 +167,19 @@ class DepthGateArgs(C.Structure):
                 ("counts", C.c_void_p), ("levels", C.c_void_p), ("stream", C.c_void_p)]
 
 
-DEPTH_GATE_MAX_PIXELS = 857728                                         # la3d_depth_gate_bits: the stored pixels of a frame its LDS layout holds
+class DepthGateFramesArgs(C.Structure):
+    """``la3d_depth_gate_frames_args`` of include/la3d.h (argument block of la3d_depth_gate_bits_frames, 152 bytes); field order is the
+    header's."""
+    _fields_ = [("struct_size", C.c_int32), ("B", C.c_int32), ("P", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("k", C.c_float), ("min_band", C.c_float), ("near", C.c_float), ("far", C.c_float), ("reserved", C.c_int32),
+                ("depth", C.c_void_p), ("depth16", C.POINTER(Depth16Block)), ("depth_elems", C.c_int64),
+                ("frames", C.c_void_p), ("image_index", C.c_void_p),
+                ("bits", C.c_void_p), ("bits_words", C.c_int64), ("bits_offsets", C.c_void_p),
+                ("out_bits", C.c_void_p), ("out_words", C.c_int64), ("out_offsets", C.c_void_p),
+                ("counts", C.c_void_p), ("levels", C.c_void_p), ("stream", C.c_void_p)]
+
+
+DEPTH_GATE_MAX_PIXELS = 857728                                         # la3d_depth_gate_bits[_frames]: the stored pixels of a frame (of the bounds) its LDS layout holds
 
 ASSIGN_F64, ASSIGN_I32 = 0, 1                                          # la3d_assign_args.cost_dtype
 ASSIGN_MAX_N, ASSIGN_STAGE_MAX = 256, 2048                             # rows / columns of a group; elements staged in LDS
@@ -178,6 +190,7 @@ OVERLAP_TILE, OVERLAP_STEP = 8, 1024                                   # planes 
 
 _SIGS = {
     "la3d_depth_gate_bits": (C.c_int, [C.POINTER(DepthGateArgs)]),
+    "la3d_depth_gate_bits_frames": (C.c_int, [C.POINTER(DepthGateFramesArgs)]),
     "la3d_mask_overlap_plan": (C.c_int64, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "la3d_mask_overlap_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "la3d_mask_overlap": (C.c_int, [C.POINTER(MaskOverlapArgs)]),

@@ -44,7 +44,7 @@ from .frames import (FRAME_DTYPE, MASKS_U8, FrameBits, PackedFrames, PackedFrame
                      fit_instances_frames_labels, fit_instances_frames_masks, frame_bits_offsets, frame_table, pack_crop_bits_frames, pack_frames, pack_label_bits_frames,
                      pack_label_frames, pack_mask_bits_frames, pack_mask_frames, pack_poly_bits_frames, pack_rle_bits_frames, pack_rle_frames)
 from .labels import _LABEL_NUMPY, _LABEL_TORCH, LabelBits, _label_planes, _label_rows, _label_source, fit_instances_labels, label_instances, pack_label_bits  # noqa: F401
-from .morph import _gate_scalars, _open_args, _open_run, _open_scalars, bits_rects, crop_params, open_bits, select_crops  # noqa: F401
+from .morph import _gate_scalars, _open_args, _open_run, _open_scalars, bits_rects, crop_params, depth_gate_stats_frames, gate_depth_bits_frames, open_bits, select_crops  # noqa: F401
 from .rle_encode import RleRuns, _rle_capacity, _rle_encode_run, rle_encode, rle_encode_bits, rle_encode_bits_frames, rle_objects, rle_to_string  # noqa: F401
 from .segm import _rle_counts, pack_polygons, pack_rle, rle_from_string  # noqa: F401
 

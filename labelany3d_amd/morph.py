@@ -1,14 +1,19 @@
-"""Morphology on bit planes (include/la3d.h): opening, rectangles and the crop gate, for ``MaskBits`` and - ``*_frames`` - ``FrameBits``."""
+"""Morphology on bit planes (include/la3d.h): opening, rectangles and the crop gate, for ``MaskBits`` and - ``*_frames`` - ``FrameBits``;
+the depth gate of a ``FrameBits`` (``gate_depth_bits_frames``: the planes of images of different sizes over the depth of their frames)."""
 from __future__ import annotations
+
+import ctypes as C
 
 import numpy as np
 import torch
 
+from . import _lib
 from ._device import _as_dev, _int_arg, _ptr, _record, _stream
 from ._lib import check, lib
 from .batched import _bits_stride, padded_width
-from .bits import MaskBits, _bits_out, _mask_bits
-from .frames import FrameBits, _bits_buffers, _bounds, _flat_out, _on_gpu, _scaled_table, _tabled, _upscale_arg, frame_bits_offsets
+from .bits import DepthGateStats, MaskBits, _bits_out, _gate_band, _gate_level, _mask_bits
+from .frames import (FrameBits, _bits_buffers, _bounds, _flat_out, _frames_depth, _on_gpu, _same_table, _scaled_table, _tabled, _upscale_arg,
+                     frame_bits_offsets)
 
 
 def _open_scalars(who: str, k, upscale) -> None:   # the k and upscale of an opening, of either form
@@ -213,3 +218,75 @@ def select_crops_frames(frames, bits: FrameBits, min_area: int = 6400, k: int = 
         stream.synchronize()
     host = stats.cpu().numpy()
     return host[:, 0] >= int(min_area), crop_params(np.maximum(host, 0), crop_size=int(crop_size), upscale=int(upscale)), stats, opened
+
+
+# ---- the depth gate of a FrameBits (include/la3d.h "depth gate on bit planes": la3d_depth_gate_bits_frames) ---------------------------
+def _gate_frames_run(who: str, frames, bits, k, min_band, near, far, stream, out, want_plane: bool, want_stats: bool):
+    """The checks of ``gate_depth_bits_frames`` / ``depth_gate_stats_frames`` and one ``la3d_depth_gate_bits_frames`` call ->
+    (FrameBits or None, stats or None)."""
+    flat, depth = _frames_depth(frames, who)   # (a PackedFrames / PackedFrames16: the call reads depth)
+    _same_table(frames, bits)
+    k, min_band = _gate_band(who, "k", k), _gate_band(who, "min_band", min_band)
+    near, far = _gate_level(who, "near", near, float("-inf")), _gate_level(who, "far", far, float("inf"))
+    H, W = max(int(frames.H), 1), max(int(frames.W), 1)
+    if H * W > _lib.DEPTH_GATE_MAX_PIXELS:
+        raise ValueError(f"{who}: bounds of {(H, W)} have more than {_lib.DEPTH_GATE_MAX_PIXELS} stored pixels")
+    total = int(bits.bits.numel())
+    in_place = isinstance(out, torch.Tensor) and out.dtype == torch.int32 and out.dim() == 1 and out.numel() == total and \
+        out.data_ptr() == bits.bits.data_ptr()
+    if want_plane and not in_place:
+        _flat_out(who, out, total, bits.bits)
+    dev = _on_gpu(flat, bits.bits)
+    if frames.table.device != dev or (out is not None and out.device != dev):
+        raise ValueError(f"{who}: the frame table or out lives on another device")
+    B, P = int(bits.offsets.numel()), int(frames.table.shape[0])
+    with torch.cuda.device(dev):
+        o = None if not want_plane else torch.empty(max(total, 4), dtype=torch.int32, device=dev) if out is None else out
+        ii = _as_dev(bits.image_index, torch.int32, dev)
+        counts = torch.empty((B, 3), dtype=torch.int32, device=dev)   # (always: the area of the result comes from it)
+        levels = torch.empty((B, 3), dtype=torch.float32, device=dev) if want_stats else None
+        if B:   # (an empty batch has no planes to point at)
+            a = _lib.DepthGateFramesArgs(struct_size=C.sizeof(_lib.DepthGateFramesArgs), B=B, P=P, H=H, W=W, k=k, min_band=min_band, near=near,
+                                         far=far, depth=flat.data_ptr() if depth.d16 is None else None,
+                                         depth16=None if depth.d16 is None else C.pointer(depth.d16), depth_elems=int(flat.numel()),
+                                         frames=frames.table.data_ptr() if P else None, image_index=ii.data_ptr(),
+                                         bits=bits.bits.data_ptr(), bits_words=total, bits_offsets=bits.offsets.data_ptr(),
+                                         out_bits=None if o is None else o.data_ptr(), out_words=0 if o is None else int(o.numel()),
+                                         out_offsets=None if o is None else bits.offsets.data_ptr(),
+                                         counts=counts.data_ptr(), levels=None if levels is None else levels.data_ptr(), stream=_stream(stream))
+            check(lib.la3d_depth_gate_bits_frames(C.byref(a)), "la3d_depth_gate_bits_frames")
+        res = None
+        if want_plane:
+            area = torch.empty(B, dtype=torch.int32, device=dev)
+            with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):   # behind the kernel, on ITS stream
+                torch.clamp(counts[:, 2], min=0, out=area)
+            res = FrameBits(o, bits.offsets, bits.image_index, area, bits.table, bits.H, bits.W)
+            _record(stream, area)
+    _record(stream, flat, frames.table, ii, bits.bits, bits.offsets, o, counts, levels)
+    return res, (DepthGateStats(counts, levels) if want_stats else None)
+
+
+def gate_depth_bits_frames(frames, bits: FrameBits, k: float = 4.5, min_band: float = 0.0, near=None, far=None, stream=None, out=None,
+                           return_stats: bool = False):
+    """``gate_depth_bits`` for the planes of images of DIFFERENT sizes in one call, over depth as it is stored (C-ABI
+    ``la3d_depth_gate_bits_frames``): every plane of ``bits`` loses its depth outliers over its OWN image's depth plane before
+    ``fit_instances_frames_bits`` takes every set pixel - the rule, ``k``, ``min_band``, ``near`` and ``far`` of ``gate_depth_bits``,
+    ONE of each per call.  ``frames``: the ``PackedFrames`` (float32) or ``PackedFrames16`` (float16 / uint16, gated where it lies: the
+    value of a stored word is the fit's - float16 exact, uint16 one rounded ``float32(x) * scale``, a stored 0 a hole with
+    ``zero_is_hole`` - and the result is, word for word, the float32 call's on the up-converted planes) whose frame table the planes
+    were laid out for (another table, or a ``frames`` without depth: ValueError before any device work).  Bounds of more than 857728
+    stored pixels are refused.  ``out``: None (a fresh tensor), a flat, 16-byte aligned int32 device tensor of at least
+    ``bits.bits.numel()`` words to fill, or ``bits.bits`` itself (in place); any other overlap with the input is refused.  Returns
+    ``FrameBits(out, bits.offsets, bits.image_index, area, bits.table, bits.H, bits.W)`` - the planes lie where the input's lie in
+    their buffer, the offsets tensor is shared, ``area`` is the kept area -, which goes straight into ``fit_instances_frames_bits`` and
+    every other frames consumer with the same ``frames``; or ``(FrameBits, DepthGateStats)`` with ``return_stats``.  A row whose
+    image index, frame row or plane offset breaks the contract, or whose plane or depth plane does not end inside its buffer, writes no
+    word and gets ``counts = -2, 0, 0`` and NaN levels (``area`` 0 in the ``FrameBits``) - decided on the device, never an exception.
+    One kernel, no host synchronisation and no host copy of the image indices; capturable."""
+    res, stats = _gate_frames_run("gate_depth_bits_frames", frames, bits, k, min_band, near, far, stream, out, True, bool(return_stats))
+    return (res, stats) if return_stats else res
+
+
+def depth_gate_stats_frames(frames, bits: FrameBits, k: float = 4.5, min_band: float = 0.0, near=None, far=None, stream=None) -> DepthGateStats:
+    """The ``DepthGateStats`` of ``gate_depth_bits_frames`` without its planes (``out_bits = NULL``: no plane is written)."""
+    return _gate_frames_run("depth_gate_stats_frames", frames, bits, k, min_band, near, far, stream, None, False, True)[1]
