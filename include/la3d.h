@@ -1318,6 +1318,104 @@ int la3d_align_ransac_subsets(const int64_t* counts, int P, double min_samples, 
 int la3d_align_apply_batch(const float* relative, const float* metric, const uint8_t* mask, int P, int64_t n, const float* coef,
                            const int32_t* status, float fill, float* out, void* stream);
 
+/* ---- ground plane: RANSAC plane fit ---------------------------------------------------------------------------------
+ * The `ground` vector the fit entries take, from the depth itself: the dominant plane of P images of ONE size (float32 depth), found by
+ * a batched RANSAC over back-projected grid samples.  Two entries, each a chain of launches on `stream` that allocates nothing and
+ * reads nothing back, uses no floating-point atomics and merges every float sum in a fixed order: a frame's result does not depend on
+ * the batch it is in, is the same from run to run, and a call with a given workspace can be captured in a graph.
+ *
+ * la3d_plane_select_batch - the samples.  Per image p the grid pixels (v, u) with v % step == 0, u % step == 0 (u < W, v < H), in
+ *   raster order; a pixel is kept where isfinite(d) & d > 0 & near_depth <= d <= far_depth, compared on the float32 depth (0 and +inf
+ *   keep every positive finite depth), and - with `candidates` - where its bit is set in plane p: P bit planes in the layout of
+ *   "masks as bit planes" with a stored width cand_width that is a multiple of 32 and >= W, pixel (v, u) = bit v * cand_width + u of
+ *   the plane, planes cand_plane_stride words apart (0: H * cand_width / 32); columns >= W are never read as image.  K: dev f64, one
+ *   matrix (k_stride 0) or one per image (k_stride >= 9 doubles apart), inverted in the kernel as la3d_unproject_batch inverts it.
+ *   With cap = ceil(H / step) * ceil(W / step):
+ *     points  dev f64 [P][cap][3]   the rows of la3d_unproject_batch at the kept pixels, bit for bit
+ *     pixel   dev i32 [P][cap]      v * W + u
+ *     counts  dev i64 [P]
+ *   Slots at and beyond counts[p] are not written.  workspace: la3d_plane_select_workspace_bytes(P, H, W, step) bytes, 4-byte aligned.
+ *
+ * la3d_plane_ransac_batch - the fit of P point sets: points dev f64 [P][n][3] and counts dev i64 [P], from the select or from any
+ *   other source.  All arithmetic is float64 without contraction: the products and sums below are rounded one by one in the order
+ *   written, and a trial's decisions use + - * only.
+ *   Trial t of frame p uses the sample indices (i, j, k) = subsets[p][t][0..2] (dev i32 [P][max_trials][3]), or - subsets NULL - the
+ *   device draw of the scale fit above with m = 3, keyed by (seed, p, t): la3d_align_ransac_subsets(counts, P, 3.0, max_trials, seed,
+ *   out, 3, stream) writes exactly these rows, and a fit fed them equals the seeded fit bit for bit.  With a, b, c = points[i], [j], [k]:
+ *     w = (b - a) x (c - a)      w_x = u_y v_z - u_z v_y, w_y = u_z v_x - u_x v_z, w_z = u_x v_y - u_y v_x  (u = b - a, v = c - a)
+ *     s = w_x w_x + w_y w_y + w_z w_z
+ *     skipped  when !(s > 0) or s is not finite (repeated indices, collinear triples, non-finite points), when an index lies outside
+ *              [0, counts[p]), or when !(w_y w_y >= cos2_tilt * s): the prior against walls, cos2_tilt = cos^2 of the largest angle
+ *              between the plane's normal and the camera's y axis (0: every orientation)
+ *     sample q is an inlier iff its three coordinates are finite and e e <= (tol tol) s with
+ *              e = w_x (x_q - a_x) + w_y (y_q - a_y) + w_z (z_q - a_z),  tol = thr_abs + thr_rel * z_q
+ *     k_t = the number of inliers.  The best trial has the largest k_t, ties go to the lower t; all max_trials trials are judged.
+ *   Refit over the inliers of the best trial: the mean mu from fixed-order sums, the covariance ABOUT mu in a second pass, n = the unit
+ *     eigenvector of its smallest eigenvalue (cyclic Jacobi), negated if n_y > 0 - so that dot([0,-1,0], n) >= 0, the side the fit's
+ *     flip rule keeps -, d = -(n . mu).  A non-finite refit reports the trial's plane: w / sqrt(s), oriented likewise, d = -(n . a).
+ *   Reported under the REPORTED plane: r = n_x x + n_y y + n_z z + d, a final inlier iff its coordinates are finite and |r| <= tol;
+ *     n_inliers = their number, rms = sqrt(mean r^2) over them, `inliers` (dev u8 [P][n] | NULL) their flags (every slot of a row is
+ *     written).
+ *     plane dev f64 [P][4] = (n_x, n_y, n_z, d);  k_trial, n_inliers, best_trial, status dev i32 [P];  rms dev f64 [P]
+ *     status  0 fitted;  1 fewer than 3 samples;  2 no accepted trial, or k_trial < min_inliers (0 means the default, 3);
+ *             3 a broken row (counts[p] outside [0, n]).  For a status other than 0 the plane is four NaN, best_trial -1, k_trial and
+ *             n_inliers 0, rms NaN, and no flag is set.
+ *   workspace: la3d_plane_ransac_workspace_bytes(P, n, max_trials) bytes, 16-byte aligned.
+ *
+ * LA3D_ERR_ARG before any launch: a bad struct_size; negative P, n, H or W; step < 1; max_trials < 1; thr_abs < 0, thr_rel < 0 or
+ *   both zero (or not finite); cos2_tilt outside [0, 1]; min_inliers < 0; near_depth / far_depth NaN; k_stride neither 0 nor >= 9; a
+ *   non-zero reserved; a cand_width that is no multiple of 32 or below W, a cand_plane_stride below the words of a plane; misaligned
+ *   pointers; NULL pointers with work to do.  LA3D_ERR_UNSUPPORTED:
+ *   max_trials > LA3D_PLANE_MAX_TRIALS, n > LA3D_PLANE_MAX_N, P > 65535, H * W > 2^30.  P == 0 is
+ *   "nothing to do", ranked behind the argument checks. */
+#define LA3D_PLANE_MAX_N (1 << 24)
+#define LA3D_PLANE_MAX_TRIALS 1024
+#define LA3D_PLANE_SEGMENT 1024         /* samples one workgroup of the candidates pass judges */
+typedef struct la3d_plane_select_args {
+  int32_t struct_size;        /* sizeof(la3d_plane_select_args) of the caller */
+  int32_t P, H, W;            /* images, their size */
+  int32_t step;               /* grid pitch in pixels, >= 1 */
+  int32_t k_stride;           /* doubles between the K of consecutive images: 0 (shared) or >= 9 */
+  float near_depth, far_depth;
+  const float* depth;         /* dev f32 [P][H][W] */
+  const double* K;            /* dev f64 [9] or [P][k_stride] */
+  const uint32_t* candidates; /* dev bit planes | NULL */
+  int64_t cand_plane_stride;  /* words; 0 = H * cand_width / 32 */
+  int32_t cand_width;         /* stored width of a candidates row: a multiple of 32, >= W */
+  int32_t reserved;           /* 0 */
+  double* points;             /* dev f64 [P][cap][3] */
+  int32_t* pixel;             /* dev i32 [P][cap] */
+  int64_t* counts;            /* dev i64 [P] */
+  void* workspace;
+  void* stream;
+} la3d_plane_select_args;
+typedef struct la3d_plane_ransac_args {
+  int32_t struct_size;        /* sizeof(la3d_plane_ransac_args) of the caller */
+  int32_t P;                  /* point sets */
+  int64_t n;                  /* samples a row holds (rows are n apart) */
+  const double* points;       /* dev f64 [P][n][3] */
+  const int64_t* counts;      /* dev i64 [P] */
+  double thr_abs, thr_rel;    /* tol = thr_abs + thr_rel * z */
+  double cos2_tilt;           /* [0, 1] */
+  int32_t max_trials;
+  int32_t min_inliers;        /* 0: 3 */
+  const int32_t* subsets;     /* dev i32 [P][max_trials][3] | NULL: drawn on the device from seed */
+  uint64_t seed;
+  double* plane;              /* dev f64 [P][4] */
+  int32_t* k_trial;           /* dev i32 [P] */
+  int32_t* n_inliers;         /* dev i32 [P] */
+  int32_t* best_trial;        /* dev i32 [P] */
+  double* rms;                /* dev f64 [P] */
+  int32_t* status;            /* dev i32 [P] */
+  uint8_t* inliers;           /* dev u8 [P][n] | NULL */
+  void* workspace;
+  void* stream;
+} la3d_plane_ransac_args;
+size_t la3d_plane_select_workspace_bytes(int P, int H, int W, int step);
+int la3d_plane_select_batch(const la3d_plane_select_args* args);
+size_t la3d_plane_ransac_workspace_bytes(int P, int64_t n, int max_trials);
+int la3d_plane_ransac_batch(const la3d_plane_ransac_args* args);
+
 /* ---- sparse unprojection at match points -------------------------------------------------------
  * Reference src/matching/matcher.py:70-91: depth dev f32 [H][W] looked up at (int(v), int(u)) of each match
  * uv dev f64 [N][2]; matches whose depth is -1 (or that fall outside the frame) get valid = 0 and NaNs;

@@ -23,9 +23,11 @@ CSRC = os.path.join(HERE, "csrc")
 # (la3d_assign.hip: the batched linear sum assignment that reads an overlap or IoU matrix, kernel and C entry in one unit)
 # (la3d_depth_gate.hip: the depth gate on bit planes - a mask's depth outliers dropped before the fit -, kernel and C entry in one unit;
 # la3d_select.hpp: the exact median under a bit image, which it shares with la3d_consumers.hip)
-SOURCES = [os.path.join(CSRC, f) for f in ("la3d_instance.hip", "la3d_instance_f16.hip", "la3d_instance_u16.hip", "la3d_hull_finish.hip", "la3d_band.hip", "la3d_rows.hip", "la3d_split.hip", "la3d_points.hip", "la3d_masks.hip", "la3d_bits.hip", "la3d_rle_encode.hip", "la3d_open.hip", "la3d_components.hip", "la3d_depth16.hip", "la3d_consumers.hip", "la3d_cloud.hip", "la3d_align.hip", "la3d_overlap.hip", "la3d_assign.hip", "la3d_depth_gate.hip", "la3d.hip",
+# (la3d_plane.hip: the ground plane from the depth - sample select and batched RANSAC plane fit -, kernels and C entries in one unit;
+# la3d_point.hpp: the back-projected pixel it shares with la3d_cloud.hip; la3d_draw.hpp: the device draw it shares with la3d_align.hip)
+SOURCES = [os.path.join(CSRC, f) for f in ("la3d_instance.hip", "la3d_instance_f16.hip", "la3d_instance_u16.hip", "la3d_hull_finish.hip", "la3d_band.hip", "la3d_rows.hip", "la3d_split.hip", "la3d_points.hip", "la3d_masks.hip", "la3d_bits.hip", "la3d_rle_encode.hip", "la3d_open.hip", "la3d_components.hip", "la3d_depth16.hip", "la3d_consumers.hip", "la3d_cloud.hip", "la3d_align.hip", "la3d_overlap.hip", "la3d_assign.hip", "la3d_depth_gate.hip", "la3d_plane.hip", "la3d.hip",
                                            "la3d_json.cpp")]
-HEADERS = [os.path.join(CSRC, f) for f in ("la3d_device.hpp", "la3d_walks.hpp", "la3d_stages.hpp", "la3d_instance_phases.hpp", "la3d_engines.hpp", "la3d_poly.hpp", "la3d_hull.hpp", "la3d_bitplanes.hpp", "la3d_select.hpp")] + \
+HEADERS = [os.path.join(CSRC, f) for f in ("la3d_device.hpp", "la3d_walks.hpp", "la3d_stages.hpp", "la3d_instance_phases.hpp", "la3d_engines.hpp", "la3d_poly.hpp", "la3d_hull.hpp", "la3d_bitplanes.hpp", "la3d_select.hpp", "la3d_point.hpp", "la3d_draw.hpp")] + \
           [os.path.join(ROOT, "include", "la3d.h")]
 LIB = os.environ.get("LA3D_LIB") or os.path.join(HERE, "lib", "libla3d.so")  # LA3D_LIB: experiment builds only
 INCLUDE = os.path.join(ROOT, "include")

@@ -76,6 +76,28 @@ class AlignRansacArgs(C.Structure):
 ALIGN_OK, ALIGN_EMPTY, ALIGN_FAILED = 0, 1, 2       # status of la3d_align_ransac_batch
 ALIGN_RANSAC_MAX_N, ALIGN_RANSAC_MAX_TRIALS = 1 << 24, 1024
 
+class PlaneSelectArgs(C.Structure):
+    """``la3d_plane_select_args`` of include/la3d.h (argument block of la3d_plane_select_batch, 112 bytes); field order is the header's."""
+    _fields_ = [("struct_size", C.c_int32), ("P", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("step", C.c_int32), ("k_stride", C.c_int32), ("near_depth", C.c_float), ("far_depth", C.c_float),
+                ("depth", C.c_void_p), ("K", C.c_void_p), ("candidates", C.c_void_p), ("cand_plane_stride", C.c_int64),
+                ("cand_width", C.c_int32), ("reserved", C.c_int32),
+                ("points", C.c_void_p), ("pixel", C.c_void_p), ("counts", C.c_void_p), ("workspace", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class PlaneRansacArgs(C.Structure):
+    """``la3d_plane_ransac_args`` of include/la3d.h (argument block of la3d_plane_ransac_batch, 152 bytes); field order is the header's."""
+    _fields_ = [("struct_size", C.c_int32), ("P", C.c_int32), ("n", C.c_int64),
+                ("points", C.c_void_p), ("counts", C.c_void_p),
+                ("thr_abs", C.c_double), ("thr_rel", C.c_double), ("cos2_tilt", C.c_double),
+                ("max_trials", C.c_int32), ("min_inliers", C.c_int32), ("subsets", C.c_void_p), ("seed", C.c_uint64),
+                ("plane", C.c_void_p), ("k_trial", C.c_void_p), ("n_inliers", C.c_void_p), ("best_trial", C.c_void_p),
+                ("rms", C.c_void_p), ("status", C.c_void_p), ("inliers", C.c_void_p), ("workspace", C.c_void_p), ("stream", C.c_void_p)]
+
+
+PLANE_OK, PLANE_TOO_FEW, PLANE_FAILED, PLANE_BROKEN = 0, 1, 2, 3   # status of la3d_plane_ransac_batch
+PLANE_MAX_N, PLANE_MAX_TRIALS, PLANE_SEGMENT = 1 << 24, 1024, 1024
+
 CLOUD_OK, CLOUD_NO_ROOM, CLOUD_MISMATCH = 0, 1, 2  # status of la3d_gather_instance_points (5 = BOX_UNSUPPORTED: a refused frames row)
 
 
@@ -189,6 +211,10 @@ OVERLAP_MIRROR, OVERLAP_AREA_A, OVERLAP_AREA_B = 1, 2, 4              # la3d_ove
 OVERLAP_TILE, OVERLAP_STEP = 8, 1024                                   # planes per side of a tile; words a chunk is a multiple of
 
 _SIGS = {
+    "la3d_plane_select_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "la3d_plane_select_batch": (C.c_int, [C.POINTER(PlaneSelectArgs)]),
+    "la3d_plane_ransac_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
+    "la3d_plane_ransac_batch": (C.c_int, [C.POINTER(PlaneRansacArgs)]),
     "la3d_depth_gate_bits": (C.c_int, [C.POINTER(DepthGateArgs)]),
     "la3d_depth_gate_bits_frames": (C.c_int, [C.POINTER(DepthGateFramesArgs)]),
     "la3d_mask_overlap_plan": (C.c_int64, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -15,6 +15,7 @@
 #include <cstring>
 
 #include "la3d_bitplanes.hpp"   // (frames_prologue)
+#include "la3d_point.hpp"
 
 namespace {
 constexpr int CT = 256;                     // threads per workgroup
@@ -207,17 +208,7 @@ __device__ inline int band_select(const CloudLds& L, unsigned q, int nw64, unsig
   return lo * 64 + select64(L.words[lo], q - L.pre[lo]);
 }
 
-// (d * Kinv) @ [u, v, 1], then the identity R, t multiply: unproject_frame of la3d_masks.hip, term for term (src/util.py:71-74) - a
-// NaN / inf depth poisons its row exactly as there
-__device__ inline void cloud_point(double d, unsigned u, unsigned v, const double* kinv, double* w) {
-  const double ud = (double)u, vd = (double)v;
-  double q[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) q[r] = (d * kinv[r * 3]) * ud + (d * kinv[r * 3 + 1]) * vd + (d * kinv[r * 3 + 2]);
-  w[0] = 1.0 * q[0] + 0.0 * q[1] + 0.0 * q[2] + 0.0;
-  w[1] = 0.0 * q[0] + 1.0 * q[1] + 0.0 * q[2] + 0.0;
-  w[2] = 0.0 * q[0] + 0.0 * q[1] + 1.0 * q[2] + 0.0;
-}
+// a point of the cloud: cloud_point (la3d_point.hpp), shared with the ground plane's sample select
 
 __device__ inline void band_rows(const CloudGeom& g, int nb, int band, int* v0, int* v1) {
   const int rpb = (g.H + nb - 1) / nb;

@@ -12,17 +12,21 @@ alignment helpers, on the MI355X.
 * ``align_depth_batch`` - ``align_depth`` for a stack of frames with the estimator on the GPU as well (``ransac_scale_batch``, C-ABI
   ``la3d_align_ransac_batch``: scikit-learn's RANSAC loop for the one-parameter model, all trials judged in one sweep): select -> fit
   -> apply without a host synchronisation.  The subsets are drawn on the device from a seed (not NumPy's stream), or given.
+* ``ground_planes`` - the ``ground`` vector of the fit entries from the depth itself (include/la3d.h "ground plane: RANSAC plane fit"):
+  ``plane_select_batch`` (grid samples, back-projected) -> ``plane_ransac_batch`` (batched RANSAC plane fit, the same device draw with
+  m = 3), for a stack of images of one size, without a host synchronisation; ``PlaneFit.for_instances`` hands the planes to a fit.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from ._device import _as_dev, _dev, _ptr, _record, _stream
-from ._lib import AlignRansacArgs, check, lib
+from ._lib import AlignRansacArgs, PlaneRansacArgs, PlaneSelectArgs, check, lib
+from .bits import MaskBits
 
 
 def align_select(relative_depth, metric_depth, mask=None, max_valid_depth: float = 400.0, device=None, stream=None):
@@ -207,6 +211,123 @@ def align_depth_batch(relative_depth, metric_depth, mask=None, min_samples=0.2, 
                                          _stream(stream)), "la3d_align_apply_batch")
     _record(stream, rel, met, m, out)
     return out, res
+
+
+class PlaneFit(NamedTuple):
+    """Result of ``plane_ransac_batch`` / ``ground_planes``, device tensors with one row per image: ``plane`` float64 (P,4) =
+    (n_x, n_y, n_z, d) with n . x + d = 0, |n| = 1 and n_y <= 0 (four NaN where status != 0); ``k_trial`` (inliers of the best trial),
+    ``n_inliers`` (inliers of the reported plane), ``best_trial`` (-1 where status != 0) and ``status`` int32 - 0 fitted, 1 fewer than
+    three samples, 2 no accepted trial or too few inliers, 3 a broken row -; ``rms`` float64 (NaN where status != 0); ``inliers`` uint8
+    (P,n) flags of the reported plane's inliers, or None when they were not asked for."""
+    plane: torch.Tensor
+    k_trial: torch.Tensor
+    n_inliers: torch.Tensor
+    best_trial: torch.Tensor
+    rms: torch.Tensor
+    status: torch.Tensor
+    inliers: Optional[torch.Tensor]
+
+    def for_instances(self, image_index) -> torch.Tensor:
+        """The (B,4) float64 device tensor the fit entries take as ``ground``: row b is the plane of image ``image_index[b]`` (a
+        device ``index_select``, no host read-back).  Rows of images that were not fitted stay NaN, which the fit reads as "no ground"."""
+        ii = _as_dev(image_index, torch.int64, self.plane.device).reshape(-1)
+        return self.plane.index_select(0, ii)
+
+
+def plane_select_batch(depth, K, candidates=None, step: int = 4, near: float = 0.0, far: float = float("inf"), stream=None):
+    """The samples of the plane fit (C-ABI ``la3d_plane_select_batch``): ``depth`` (P,H,W) float32, ``K`` (3,3) or (P,3,3) ->
+    ``(points (P,cap,3) float64, pixel (P,cap) int32, counts (P,) int64)`` on the GPU, cap = ceil(H/step) * ceil(W/step).  Image p's
+    samples are the grid pixels (v % step == 0, u % step == 0) in raster order with a finite depth > 0 inside [near, far] and - with
+    ``candidates``, a ``MaskBits`` of P planes whose stored width is a multiple of 32 (``frame_pad=True``) and whose ``frame_width`` is
+    W, e.g. ``pack_label_bits(panoptic, ids=floor_and_road_ids)`` - a set candidate bit; ``points[p, :counts[p]]`` are the rows of
+    ``unproject(depth, K)`` at ``pixel[p, :counts[p]]`` (= v * W + u), bit for bit.  Slots behind ``counts[p]`` are not written.  No
+    host synchronisation."""
+    dev = depth.device if isinstance(depth, torch.Tensor) and depth.is_cuda else _dev(None)
+    d = _as_dev(depth, torch.float32, dev)
+    if d.dim() != 3:
+        raise ValueError("depth must be a (P,H,W) stack")
+    P, H, W = d.shape
+    k = _as_dev(K, torch.float64, dev, cache=True).reshape(-1, 9)
+    if k.shape[0] not in (1, P):
+        raise ValueError("K must be (3,3) or (P,3,3)")
+    cb, cw, cs = None, 0, 0
+    if candidates is not None:
+        if not (isinstance(candidates, tuple) and len(candidates) == 4):
+            raise ValueError("candidates must be a MaskBits (bits, H, W, frame_width)")
+        mb = MaskBits(candidates[0], int(candidates[1]), int(candidates[2]), int(candidates[3]))
+        cb = _as_dev(mb.bits, torch.int32, dev)
+        if cb.dim() != 2 or cb.shape[0] != P or mb.H != H or mb.frame_width != W or mb.W % 32 != 0 or cb.shape[1] < H * mb.W // 32:
+            raise ValueError("candidates must hold one plane per image of the depth's size, stored with a width that is a multiple of 32")
+        cw, cs = mb.W, int(cb.shape[1])
+    step = int(step)
+    cap = (-(-H // step)) * (-(-W // step)) if step >= 1 else 0
+    pts = torch.empty((P, cap, 3), dtype=torch.float64, device=dev)
+    pix = torch.empty((P, cap), dtype=torch.int32, device=dev)
+    cnt = torch.empty(P, dtype=torch.int64, device=dev)
+    ws = torch.empty(int(lib.la3d_plane_select_workspace_bytes(P, H, W, step)), dtype=torch.uint8, device=dev)
+    a = PlaneSelectArgs(struct_size=C.sizeof(PlaneSelectArgs), P=P, H=H, W=W, step=step, k_stride=9 if k.shape[0] > 1 else 0,
+                        near_depth=float(near), far_depth=float(far), depth=d.data_ptr(), K=k.data_ptr(),
+                        candidates=None if cb is None else cb.data_ptr(), cand_plane_stride=cs, cand_width=cw,
+                        points=pts.data_ptr(), pixel=pix.data_ptr(), counts=cnt.data_ptr(), workspace=ws.data_ptr())
+    with torch.cuda.device(dev):
+        a.stream = _stream(stream).value
+        check(lib.la3d_plane_select_batch(C.byref(a)), "la3d_plane_select_batch")
+    _record(stream, d, k, cb, pts, pix, cnt, ws)
+    return pts, pix, cnt
+
+
+def plane_ransac_batch(points, counts, threshold: float = 0.02, threshold_rel: float = 0.0, max_trials: int = 256, max_tilt=None,
+                       min_inliers: int = 3, subsets=None, seed: int = 0, inliers: bool = False, stream=None) -> PlaneFit:
+    """Batched RANSAC plane fit on the GPU (C-ABI ``la3d_plane_ransac_batch``; semantics in include/la3d.h): ``points`` (P,n,3) float64
+    and ``counts`` (P,) int64 as ``plane_select_batch`` leaves them, or from any other source.  A sample at depth z is an inlier within
+    ``threshold + threshold_rel * z`` of the plane; ``max_tilt`` (radians, None = any) is the largest angle between the plane's normal and
+    the camera's y axis - the prior that keeps walls out; ``min_inliers`` the fewest inliers of the best trial that count as a fit.
+    ``subsets``: int32 (P, max_trials, 3) sample indices per trial, or None: drawn on the device from ``seed`` -
+    ``ransac_subsets(counts, 3, max_trials, seed)`` exports exactly that draw.  All trials are judged; the best plane is refitted over
+    its inliers (covariance about their mean, smallest eigenvector) and oriented so that n_y <= 0.  ``inliers=True`` also returns the
+    flags.  No host synchronisation; returns a ``PlaneFit`` of device tensors."""
+    dev = points.device if isinstance(points, torch.Tensor) and points.is_cuda else _dev(None)
+    x = _as_dev(points, torch.float64, dev)
+    if x.dim() != 3 or x.shape[2] != 3:
+        raise ValueError("points must be (P, n, 3)")
+    P, n = int(x.shape[0]), int(x.shape[1])
+    cnt = _as_dev(counts, torch.int64, dev).reshape(-1)
+    if cnt.numel() != P:
+        raise ValueError("counts must hold one entry per point set")
+    sub = None
+    if subsets is not None:
+        sub = _as_dev(subsets, torch.int32, dev)
+        if sub.shape != (P, int(max_trials), 3):
+            raise ValueError("subsets must be (P, max_trials, 3)")
+    cos2 = 0.0 if max_tilt is None else float(np.cos(np.float64(max_tilt)) ** 2)
+    plane = torch.empty((P, 4), dtype=torch.float64, device=dev)
+    rms = torch.empty(P, dtype=torch.float64, device=dev)
+    ints = torch.empty((4, P), dtype=torch.int32, device=dev)
+    flags = torch.empty((P, n), dtype=torch.uint8, device=dev) if inliers else None
+    ws = torch.empty(int(lib.la3d_plane_ransac_workspace_bytes(P, n, int(max_trials))), dtype=torch.uint8, device=dev)
+    a = PlaneRansacArgs(struct_size=C.sizeof(PlaneRansacArgs), P=P, n=n, points=x.data_ptr(), counts=cnt.data_ptr(),
+                        thr_abs=float(threshold), thr_rel=float(threshold_rel), cos2_tilt=cos2, max_trials=int(max_trials),
+                        min_inliers=int(min_inliers), subsets=None if sub is None else sub.data_ptr(), seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
+                        plane=plane.data_ptr(), k_trial=ints[0].data_ptr(), n_inliers=ints[1].data_ptr(), best_trial=ints[2].data_ptr(),
+                        rms=rms.data_ptr(), status=ints[3].data_ptr(), inliers=None if flags is None else flags.data_ptr(),
+                        workspace=ws.data_ptr())
+    with torch.cuda.device(dev):
+        a.stream = _stream(stream).value
+        check(lib.la3d_plane_ransac_batch(C.byref(a)), "la3d_plane_ransac_batch")
+    _record(stream, x, cnt, sub, plane, rms, ints, flags, ws)
+    return PlaneFit(plane, ints[0], ints[1], ints[2], rms, ints[3], flags)
+
+
+def ground_planes(depth, K, candidates=None, step: int = 4, near: float = 0.0, far: float = float("inf"), threshold: float = 0.02,
+                  threshold_rel: float = 0.0, max_trials: int = 256, max_tilt=None, min_inliers: int = 3, seed: int = 0,
+                  inliers: bool = False, stream=None) -> PlaneFit:
+    """The dominant plane of every image of a (P,H,W) float32 depth stack - the floor or the road of most scenes -, every step on the
+    GPU and without any host read-back: ``plane_select_batch`` -> ``plane_ransac_batch`` (their arguments).  ``candidates``: a
+    ``MaskBits`` of the pixels that may be ground (the floor / road ids of a panoptic label map through ``pack_label_bits``).
+    ``gp.for_instances(image_index)`` is the ``ground`` argument of the fit entries; ``inliers`` flags index the samples of the select,
+    not the pixels."""
+    pts, _, cnt = plane_select_batch(depth, K, candidates, step, near, far, stream)
+    return plane_ransac_batch(pts, cnt, threshold, threshold_rel, max_trials, max_tilt, min_inliers, None, seed, inliers, stream)
 
 
 def masked_ratio_median(depth_map, depth_render, mask, render_mask=None, image_index=None, stream=None):
